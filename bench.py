@@ -14,7 +14,9 @@ the render) and gathered to rank 0 over RCCL/xGMI once per step — inside the t
                                            rl_rtiow_render_multi_device: RCCL send/recv inside the library)
 It never prints a line whose n_gpus differs from --gpus.
 
-Prints ONE JSON line (rank 0). Extra objects:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up (--warmup steps of the timed path), times --steps steps and prints the
+headline figure (`value`, `ms_per_step`, `config`); --dump-outputs DIR also writes the last timed step's frame as DIR/frame.npy.
+Everything else runs only with --full, which adds the counting render before the warm-up and these objects:
   roofline     — the kernel is bound by VALU issue under divergence (the scene lives in LDS / L2; measured HBM traffic is the
                  framebuffer), so the bound is the chip's vector-instruction issue capacity: achieved = VALU lane-operations per
                  ray (rocprofv3 SQ counters of the same kernel on the same workload, profiles/valu.json: instruction counts are a
@@ -57,6 +59,10 @@ def parse_args():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--spp", type=int, default=1024)
     ap.add_argument("--depth", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's frame to DIR/frame.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the counting render, roofline, check, CPU baseline, live counter passes and other configs; the options "
+                         "from --no-cpu-baseline to --cfg5-spp act only with it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true", help="skip the post-run frame check (profiling passes)")
     ap.add_argument("--check-rows", type=int, default=8)
@@ -68,7 +74,10 @@ def parse_args():
     ap.add_argument("--inprocess", action="store_true", help="N GPUs from ONE process through rl_init_multi / rl_rtiow_render_multi_device")
     ap.add_argument("--emulate-shard", type=int, default=0,
                     help="single-GPU rehearsal of an N-way shard: render only rows 0 mod N (not the headline metric)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def spawn_ranks(args):
@@ -379,14 +388,31 @@ def other_configs(args, rl, np, torch, dev):
     return res
 
 
+DUMP_MAX_BYTES = 60_000_000  # stays under 64 MB with the .npy headers
+
+
+def dump_outputs(out_dir, frame):
+    """DIR/frame.npy: the timed path's framebuffer after its last step, as the caller receives it (float64 per-pixel colour sums over the
+    samples; --emulate-shard: only the rendered rows).  A larger frame is cut to a fixed, seeded sample of its rows, whose indices go to
+    DIR/frame_rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = frame.cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_MAX_BYTES // (a.nbytes // a.shape[0]), replace=False))
+        a = a[rows]
+        np.save(os.path.join(out_dir, "frame_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "frame.npy"), a)
+
+
 def main():
     args = parse_args()
     ws_env = os.environ.get("WORLD_SIZE")
     if ws_env is None and args.gpus > 1 and not args.inprocess:
         spawn_ranks(args)
     world_size = int(ws_env) if ws_env is not None else 1
-    live = live_valu_profile(args)  # (child processes: before anything here touches the GPU)
-    if world_size == 1:
+    live = live_valu_profile(args) if args.full else None  # (child processes: before anything here touches the GPU)
+    if world_size == 1 and args.full:
         live_cfg_profiles(args)
     if args.inprocess:
         if world_size != 1:
@@ -472,15 +498,19 @@ def main():
             return rl.api.render_status(world)
         return None
 
-    # ---- counters for this exact workload (deterministic: identical for every launch) — untimed; keep the counting frame
-    st = {}
-    step(stats=st)
-    torch.cuda.synchronize(dev)
-    counting_frame = (frame if world_size > 1 else shard).clone() if rank == 0 else None
-    for _ in range(max(0, args.warmup - 1)):
+    # ---- --full: counters for this exact workload (deterministic: identical for every launch) — untimed, the first warm-up step; keep the
+    # counting frame for the check
+    st, counting_frame, warm = None, None, args.warmup
+    if args.full:
+        st = {}
+        step(stats=st)
+        torch.cuda.synchronize(dev)
+        counting_frame = (frame if world_size > 1 else shard).clone() if rank == 0 else None
+        warm -= 1
+    for _ in range(max(0, warm)):
         step()
     finish()
-    if world_size > 1:  # the exchange step alone (untimed run): rows already rendered, one gather to rank 0
+    if world_size > 1 and args.full:  # the exchange step alone (untimed run): rows already rendered, one gather to rank 0
         dist.barrier()
         torch.cuda.synchronize(dev)
         g0 = time.perf_counter()
@@ -520,8 +550,8 @@ def main():
         kernel_ms = sum(a.elapsed_time(b) for a, b in evs) / max(1, args.steps)
         timed_status = rl.api.render_status(world)  # rays / flagged counted by the TIMED kernel itself (last step)
 
-    tot = torch.tensor([float(st["rays"]), float(st["node_tests"]), float(st["sphere_tests"]), elapsed, kernel_ms, float(timed_status["rays"])],
-                       dtype=torch.float64, device="cpu" if rehearsal else dev)
+    counts = [float(st[k]) for k in ("rays", "node_tests", "sphere_tests")] if st else [0.0, 0.0, 0.0]
+    tot = torch.tensor(counts + [elapsed, kernel_ms, float(timed_status["rays"])], dtype=torch.float64, device="cpu" if rehearsal else dev)
     if world_size > 1:
         mx = tot.clone()
         dist.all_reduce(tot, op=dist.ReduceOp.SUM)
@@ -531,6 +561,8 @@ def main():
     else:
         kernel_ms_max = kernel_ms
     rays, nodes, spheres, timed_rays = float(tot[0]), float(tot[1]), float(tot[2]), float(tot[5])
+    if not st:  # plain run: the timed kernels' own ray count (--full's check shows it equal to the counting render's)
+        rays = timed_rays
     if world_size > 1:  # every rank's own kernel time (HIP events on its launch stream)
         per_rank = [torch.zeros(1, dtype=torch.float64, device="cpu" if rehearsal else dev) for _ in range(world_size)]
         dist.all_gather(per_rank, torch.tensor([kernel_ms], dtype=torch.float64, device="cpu" if rehearsal else dev))
@@ -539,47 +571,6 @@ def main():
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = rays * args.steps / elapsed / 1e6
-        rank_rays = float(st["rays"]) if not args.inprocess else rays / G  # rank 0's kernel (per-GPU share in-process)
-        k_s = kernel_ms * 1e-3
-        launches = 2 if (args.spp >= 64 and os.environ.get("RL_LPT", "1") != "0") else 1
-        # SURVEY.md §8d's algorithmic bytes (what a scene-from-HBM traversal would move): reported, NOT the bound
-        alg_bytes = 64.0 * st["node_tests"] + 64.0 * st["sphere_tests"] + 208.0 * st["rays"]
-        vp = valu_profile(W, H, args.spp, args.depth, live)
-        roof = {"bound": "valu", "unit": "Tlane-op/s", "peak": VALU_PEAK_TLANEOPS, "kernel": vp["kernel"] if vp else "rtiow_wave_kernel<1024,4,false>",
-                "kernel_ms": kernel_ms, "kernel_ms_max_rank": kernel_ms_max, "launches_per_step": launches, "kernel_avg_launch_ms": kernel_ms / launches,
-                "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_gbs": alg_bytes / k_s / 1e9, "traffic": None}
-        if vp:
-            lane_ops = vp["valu_lane_ops_per_ray_f32_weighted"]   # lanes x instructions, binary64 instructions counted twice
-            wave_insts = vp["valu_issue_slots_per_ray"]            # wave-instructions, binary64 counted twice (2-cycle slots)
-            achieved = lane_ops * rank_rays / k_s / 1e12
-            issue = wave_insts * rank_rays / k_s / (N_CU * N_SIMD * CLOCK_GHZ * 1e9 / 2.0)
-            lds_frac = vp["lds_array_cycles_per_ray"] * rank_rays / k_s / (N_CU * CLOCK_GHZ * 1e9)  # LDS-array busy cycles / CU cycles
-            roof.update({"achieved": achieved, "frac": achieved / VALU_PEAK_TLANEOPS,
-                         "valu_issue_frac": issue, "lanes_active_frac": vp["lanes_active_frac"],
-                         "lds_frac": lds_frac, "lds_bank_conflict_frac": vp["lds_bank_conflict_frac"],
-                         "valu_wave_insts_per_ray": vp["valu_wave_insts_per_ray"], "valu_issue_slots_per_ray": wave_insts,
-                         "fp64_flop_per_ray": vp.get("fp64_flop_per_ray"),
-                         "fp64_tflops": (vp["fp64_flop_per_ray"] * rank_rays / k_s / 1e12) if vp.get("fp64_flop_per_ray") else None,
-                         "fp64_peak_tflops_unfused": 39.3,
-                         "traffic": (vp["hbm_bytes_per_ray"] * rank_rays / launches) if vp.get("hbm_bytes_per_ray") is not None else vp.get("hbm_bytes_per_launch"),
-                         "hbm_gbs": (vp["hbm_bytes_per_ray"] * rank_rays / k_s / 1e9) if vp.get("hbm_bytes_per_ray") is not None else None,
-                         "hbm_frac_of_8TBs": (vp["hbm_bytes_per_ray"] * rank_rays / k_s / 8e12) if vp.get("hbm_bytes_per_ray") is not None else None,
-                         "l2_hit_rate": vp.get("l2_hit_rate"), "pmc_spp": vp.get("pmc_spp"), "counters_measured_in_this_run": bool(vp.get("live")),
-                         "wave_cycle_shares": vp.get("wave_cycle_shares"),
-                         "per_ray_figures_from": vp.get("source"),
-                         "note": ("per-ray instruction counts are rocprofv3 SQ counters of this kernel on this workload" +
-                                  ("" if vp.get("pmc_spp") == args.spp else f" at {vp.get('pmc_spp')} spp (this run: {args.spp}: the 8-sample probe launch has another share of the frame)") +
-                                  (", collected by child passes of this run before the timed loop; " if vp.get("live") else " (profiles/, not collected in this run); ")) +
-                                 "rays and kernel time are this run's. frac = valu_issue_frac x lanes_active_frac at the nominal 2.4 GHz; the scene is LDS / L2-resident, "
-                                 "HBM traffic is the framebuffer"})
-        else:
-            roof.update({"achieved": None, "frac": None, "note": "no profiles/valu.json for this workload: VALU figures not available"})
-        # a rank whose shard has at most three pixels per lane renders its resume launch with the work-stealing instantiation:
-        # taken-over pixels run through the cooperative body, whose instruction mix valu.json (profiled at N = 1) does not describe
-        rank_pixels = rl.api.rows_for(H, row_first, row_step) * W
-        if rank_pixels <= 3 * N_CU * 1024 and os.environ.get("RL_STEAL", "3") not in ("0", "0.0"):
-            roof["kernel"] = "rtiow_wave_kernel<1024,4,false,true> (work stealing)"
-            roof["note"] = (roof.get("note") or "") + "; this rank's shard is small enough for work stealing: the VALU figures are those of the N = 1 kernel and only indicative here"
         out = {
             "metric": "Mrays/sec (primary+secondary), 1080p 1024spp depth50; 1/2/4/8 GPU",
             "value": value, "unit": "Mrays/s", "n_gpus": G, "steps": args.steps, "warmup": args.warmup,
@@ -589,9 +580,54 @@ def main():
                        "baseline_config": "configs[1]",
                        "sharding": (f"one process, rl_rtiow_render_multi_device over {G} GPU(s): rows interleaved, RCCL send/recv to GPU 0 inside the library" if args.inprocess
                                     else f"rows interleaved over {G} rank(s), RCCL gather to rank 0"),
-                       "rays_per_step": rays, "aabb_tests_per_ray": nodes / rays, "sphere_tests_per_ray": spheres / rays},
-            "roofline": roof,
+                       "rays_per_step": rays},
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, frame if world_size > 1 else shard)
+        if args.full:
+            out["config"].update({"aabb_tests_per_ray": nodes / rays, "sphere_tests_per_ray": spheres / rays})
+            rank_rays = float(st["rays"]) if not args.inprocess else rays / G  # rank 0's kernel (per-GPU share in-process)
+            k_s = kernel_ms * 1e-3
+            launches = 2 if (args.spp >= 64 and os.environ.get("RL_LPT", "1") != "0") else 1
+            # SURVEY.md §8d's algorithmic bytes (what a scene-from-HBM traversal would move): reported, NOT the bound
+            alg_bytes = 64.0 * st["node_tests"] + 64.0 * st["sphere_tests"] + 208.0 * st["rays"]
+            vp = valu_profile(W, H, args.spp, args.depth, live)
+            roof = {"bound": "valu", "unit": "Tlane-op/s", "peak": VALU_PEAK_TLANEOPS, "kernel": vp["kernel"] if vp else "rtiow_wave_kernel<1024,4,false>",
+                    "kernel_ms": kernel_ms, "kernel_ms_max_rank": kernel_ms_max, "launches_per_step": launches, "kernel_avg_launch_ms": kernel_ms / launches,
+                    "algorithmic_bytes_per_launch": alg_bytes, "algorithmic_gbs": alg_bytes / k_s / 1e9, "traffic": None}
+            if vp:
+                lane_ops = vp["valu_lane_ops_per_ray_f32_weighted"]   # lanes x instructions, binary64 instructions counted twice
+                wave_insts = vp["valu_issue_slots_per_ray"]            # wave-instructions, binary64 counted twice (2-cycle slots)
+                achieved = lane_ops * rank_rays / k_s / 1e12
+                issue = wave_insts * rank_rays / k_s / (N_CU * N_SIMD * CLOCK_GHZ * 1e9 / 2.0)
+                lds_frac = vp["lds_array_cycles_per_ray"] * rank_rays / k_s / (N_CU * CLOCK_GHZ * 1e9)  # LDS-array busy cycles / CU cycles
+                roof.update({"achieved": achieved, "frac": achieved / VALU_PEAK_TLANEOPS,
+                             "valu_issue_frac": issue, "lanes_active_frac": vp["lanes_active_frac"],
+                             "lds_frac": lds_frac, "lds_bank_conflict_frac": vp["lds_bank_conflict_frac"],
+                             "valu_wave_insts_per_ray": vp["valu_wave_insts_per_ray"], "valu_issue_slots_per_ray": wave_insts,
+                             "fp64_flop_per_ray": vp.get("fp64_flop_per_ray"),
+                             "fp64_tflops": (vp["fp64_flop_per_ray"] * rank_rays / k_s / 1e12) if vp.get("fp64_flop_per_ray") else None,
+                             "fp64_peak_tflops_unfused": 39.3,
+                             "traffic": (vp["hbm_bytes_per_ray"] * rank_rays / launches) if vp.get("hbm_bytes_per_ray") is not None else vp.get("hbm_bytes_per_launch"),
+                             "hbm_gbs": (vp["hbm_bytes_per_ray"] * rank_rays / k_s / 1e9) if vp.get("hbm_bytes_per_ray") is not None else None,
+                             "hbm_frac_of_8TBs": (vp["hbm_bytes_per_ray"] * rank_rays / k_s / 8e12) if vp.get("hbm_bytes_per_ray") is not None else None,
+                             "l2_hit_rate": vp.get("l2_hit_rate"), "pmc_spp": vp.get("pmc_spp"), "counters_measured_in_this_run": bool(vp.get("live")),
+                             "wave_cycle_shares": vp.get("wave_cycle_shares"),
+                             "per_ray_figures_from": vp.get("source"),
+                             "note": ("per-ray instruction counts are rocprofv3 SQ counters of this kernel on this workload" +
+                                      ("" if vp.get("pmc_spp") == args.spp else f" at {vp.get('pmc_spp')} spp (this run: {args.spp}: the 8-sample probe launch has another share of the frame)") +
+                                      (", collected by child passes of this run before the timed loop; " if vp.get("live") else " (profiles/, not collected in this run); ")) +
+                                     "rays and kernel time are this run's. frac = valu_issue_frac x lanes_active_frac at the nominal 2.4 GHz; the scene is LDS / L2-resident, "
+                                     "HBM traffic is the framebuffer"})
+            else:
+                roof.update({"achieved": None, "frac": None, "note": "no profiles/valu.json for this workload: VALU figures not available"})
+            # a rank whose shard has at most three pixels per lane renders its resume launch with the work-stealing instantiation:
+            # taken-over pixels run through the cooperative body, whose instruction mix valu.json (profiled at N = 1) does not describe
+            rank_pixels = rl.api.rows_for(H, row_first, row_step) * W
+            if rank_pixels <= 3 * N_CU * 1024 and os.environ.get("RL_STEAL", "3") not in ("0", "0.0"):
+                roof["kernel"] = "rtiow_wave_kernel<1024,4,false,true> (work stealing)"
+                roof["note"] = (roof.get("note") or "") + "; this rank's shard is small enough for work stealing: the VALU figures are those of the N = 1 kernel and only indicative here"
+            out["roofline"] = roof
         if comm is not None:
             out["rccl"] = comm
         if args.emulate_shard > 1:
@@ -599,7 +635,7 @@ def main():
         if rehearsal or (args.inprocess and os.environ.get("RL_BENCH_EMULATE_DEVICES")):
             out["config"]["rehearsal"] = "all ranks / device contexts on GPU 0: NOT a measurement"
         # ---- the check: the TIMED frame against the counting kernel's frame and against the CPU oracle at full spp
-        if not args.no_check:
+        if args.full and not args.no_check:
             timed_frame = frame if world_size > 1 else shard
             chk = {"timed_frame_equals_counting_frame": bool(torch.equal(timed_frame, counting_frame)),
                    "timed_rays_equal_counting_rays": timed_rays == rays, "flagged": int(st["flagged"])}
@@ -632,7 +668,7 @@ def main():
                             "max_abs_err": float(np.abs(timed_rows.cpu().numpy() - cpu).max() / max(1, args.spp)),
                             "tolerance": 1e-4, "oracle_seconds": cdt})
             out["check"] = chk
-        if world_size == 1 and not args.inprocess and not args.no_cpu_baseline:
+        if args.full and world_size == 1 and not args.inprocess and not args.no_cpu_baseline:
             sys.path.insert(0, os.path.join(ROOT, "oracle"))
             oracle = importlib.import_module("rl_oracle")
             try:
@@ -658,7 +694,7 @@ def main():
                                    "sample": f"same scene/camera {W}x{H} depth {args.depth}: rows y%{cstep}==0 ({rl.api.rows_for(H, 0, cstep)} rows), "
                                              f"{cspp} spp, {cst['rays']} rays in {cdt:.1f} s on {threads} threads (one task per pixel); CPU restatement of the "
                                              "reference algorithm (oracle/, -O3 -ffp-contract=off), not the Rust reference"}
-        if world_size == 1 and not args.inprocess and args.emulate_shard <= 1 and args.configs:
+        if args.full and world_size == 1 and not args.inprocess and args.emulate_shard <= 1 and args.configs:
             del shard, counting_frame
             out["configs"] = other_configs(args, rl, np, torch, dev)
         print(json.dumps(out), flush=True)

@@ -8,7 +8,7 @@ cd $R
 for v in "$@"; do
   export RL_RTIOW_KERNEL=$v
   timeout -k 10 300 python -m pytest tests/test_gpu_parity.py -x -q -k rtiow > $OUT/test_$v.log 2>&1; echo "$v tests exit=$? $(tail -1 $OUT/test_$v.log)"
-  timeout -k 10 300 python bench.py --spp $SPP --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_$v.json 2> $OUT/bench_$v.err || { echo "$v bench failed"; tail -3 $OUT/bench_$v.err; continue; }
+  timeout -k 10 300 python bench.py --full --spp $SPP --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_$v.json 2> $OUT/bench_$v.err || { echo "$v bench failed"; tail -3 $OUT/bench_$v.err; continue; }
   python - <<PY
 import json
 j=json.load(open("$OUT/bench_$v.json"))
