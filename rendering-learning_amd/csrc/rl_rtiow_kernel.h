@@ -97,20 +97,35 @@ __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return __builtin
 // 4728 instructions and no spills left, stealing instantiation 13943 -> 8986 and 38 -> 6 spilled VGPRs; 6709 -> 6770 Mrays/s, 1/8 shard
 // 174 -> 163 ms.  The cooperative one-wave-per-pixel body keeps the unrolled form: there a block is on the pixel's critical path.
 // (A real function call for the rare mid-SHADE refill was measured too: its register convention spills 36 more VGPRs in the main loop, 4940 Mrays/s.)
-template <int NT, bool ROLLED = false>
-__device__ __forceinline__ void chacha8_block_to_lds(const uint32_t *key, uint32_t ctr_lo, uint64_t stream, unsigned long long *s_rng, int tid) {
+// (chacha8_block_to_lds_job: the same block function with its inputs {counter, stream, destination} produced by `job()`, which it
+// calls twice — before the rounds and again for the feed-forward and the stores — so that a job that can re-derive its inputs
+// cheaply (rl_rtiow_wave.h Ring::coop_blocks: a few lane permutes) does not hold them in registers through the rounds; a lane
+// whose job has store = false computes a block and discards it)
+struct ChachaJob {
+  uint32_t ctr_lo;
+  uint64_t stream;
+  unsigned long long *s_rng;
+  int tid;
+  bool store;
+};
+template <int NT, bool ROLLED, class Job>
+__device__ __forceinline__ void chacha8_block_to_lds_job(const uint32_t *key, Job job) {
   const uint32_t c0 = 0x61707865u, c1 = 0x3320646eu, c2 = 0x79622d32u, c3 = 0x6b206574u;
-  uint32_t s12 = ctr_lo, s13 = 0u, s14 = (uint32_t)stream, s15 = (uint32_t)(stream >> 32);
+  const ChachaJob in = job();
   uint32_t x0 = c0, x1 = c1, x2 = c2, x3 = c3, x4 = key[0], x5 = key[1], x6 = key[2], x7 = key[3], x8 = key[4], x9 = key[5], x10 = key[6],
-           x11 = key[7], x12 = s12, x13 = s13, x14 = s14, x15 = s15;
+           x11 = key[7], x12 = in.ctr_lo, x13 = 0u, x14 = (uint32_t)in.stream, x15 = (uint32_t)(in.stream >> 32);
 #pragma unroll(ROLLED ? 1 : 4)
   for (int r = 0; r < 4; r++) {
     RL_QR(x0, x4, x8, x12) RL_QR(x1, x5, x9, x13) RL_QR(x2, x6, x10, x14) RL_QR(x3, x7, x11, x15)
     RL_QR(x0, x5, x10, x15) RL_QR(x1, x6, x11, x12) RL_QR(x2, x7, x8, x13) RL_QR(x3, x4, x9, x14)
   }
+  const ChachaJob j = job();
   x0 += c0, x1 += c1, x2 += c2, x3 += c3;
   x4 += key[0], x5 += key[1], x6 += key[2], x7 += key[3], x8 += key[4], x9 += key[5], x10 += key[6], x11 += key[7];
-  x12 += s12, x13 += s13, x14 += s14, x15 += s15;
+  x12 += j.ctr_lo, x14 += (uint32_t)j.stream, x15 += (uint32_t)(j.stream >> 32);
+  unsigned long long *s_rng = j.s_rng;
+  const int tid = j.tid;
+  if (!j.store) return;
   s_rng[0 * NT + tid] = (unsigned long long)x0 | ((unsigned long long)x1 << 32);
   s_rng[1 * NT + tid] = (unsigned long long)x2 | ((unsigned long long)x3 << 32);
   s_rng[2 * NT + tid] = (unsigned long long)x4 | ((unsigned long long)x5 << 32);
@@ -119,6 +134,10 @@ __device__ __forceinline__ void chacha8_block_to_lds(const uint32_t *key, uint32
   s_rng[5 * NT + tid] = (unsigned long long)x10 | ((unsigned long long)x11 << 32);
   s_rng[6 * NT + tid] = (unsigned long long)x12 | ((unsigned long long)x13 << 32);
   s_rng[7 * NT + tid] = (unsigned long long)x14 | ((unsigned long long)x15 << 32);
+}
+template <int NT, bool ROLLED = false>
+__device__ __forceinline__ void chacha8_block_to_lds(const uint32_t *key, uint32_t ctr_lo, uint64_t stream, unsigned long long *s_rng, int tid) {
+  chacha8_block_to_lds_job<NT, ROLLED>(key, [&] { return ChachaJob{ctr_lo, stream, s_rng, tid, true}; });
 }
 
 // per-lane RNG state: stream + word position; the current block lives in LDS

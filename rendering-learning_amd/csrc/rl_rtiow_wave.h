@@ -34,6 +34,11 @@ namespace rl {
 #ifndef RL_SPLIT_LEAF
 #define RL_SPLIT_LEAF false
 #endif
+// GEN's stream resets through Ring::coop_blocks: 0 = per lane, two blocks one after the other (the old path); 1 = one wave-wide pass;
+// 2 = as 1, and lanes waiting in FILL take the pass's spare job slots (when that adds no pass): measured 775.6 against 774.0 ms per step, not kept
+#ifndef RL_COOP_GEN
+#define RL_COOP_GEN 1
+#endif
 enum : uint32_t { ST_GEN = 0, ST_TRAV = 1, ST_SHADE = 2, ST_FILL = 3, ST_DONE = 4, ST_LEAF = 5, ST_SHADE2 = 6, ST_PARK = 7, ST_LEAF2 = 8 };
 // The latency modes of DESIGN.md §6 (RL_THIN: thin tiles, RL_PRIO: wave priority) — measured, no gain — are compiled into the
 // experimental library only (make exp); the product kernel carries none of their code.
@@ -68,8 +73,56 @@ struct Ring {
   __device__ __forceinline__ void top_up() {  // make block (newest+1) resident, dropping the oldest
     uint32_t c = blk_lo + nres;
     gen_block(c);
+    top_up_done();
+  }
+  __device__ __forceinline__ void top_up_done() {  // bookkeeping of top_up once block (newest+1) is resident
     if (nres == 2) blk_lo++;
     else nres++;
+  }
+  // Wave-cooperative block generation (RL_COOP_GEN).  Called by ALL 64 lanes of the wave (full exec).  A lane with nb = 1 or 2 needs
+  // blocks first .. first + nb - 1 of its `stream` in its own ring column.  The wave's requests become a job list — [every lane with
+  // nb >= 1: block first][every lane with nb == 2: block first + 1] — and lane l runs job l (then l + 64) of it, writing the block
+  // into the REQUESTER's column: 2 x 25 stream resets of a GEN block are one pass of the block function instead of two passes at
+  // 40 % lane use.  Same blocks, same LDS slots as per-lane generation.  Cross-lane traffic is permutes only (no LDS allocation).
+  // ONES: some lanes may want one block (else nb is 0 or 2 and one compaction serves both halves of the job list).
+  template <bool ONES>
+  __device__ __forceinline__ void coop_blocks(uint32_t nb, uint32_t first) {
+    const unsigned long long m1 = __ballot(nb != 0u), m2 = ONES ? __ballot(nb == 2u) : m1;
+    const uint32_t n1 = (uint32_t)__popcll(m1), jobs = n1 + (uint32_t)__popcll(m2);
+    // compaction (a forward permute): lane r receives the id of the r-th lane of mask m; the lanes outside it all send to lane 63,
+    // which is then never read (it is the mask's last member only when all 64 lanes are in it)
+    auto compact = [](unsigned long long m, uint32_t lane) {
+      const uint32_t r = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+      return (uint32_t)__builtin_amdgcn_ds_permute((int)((((m >> lane) & 1ull) ? r : 63u) << 2), (int)lane);
+    };
+    __builtin_amdgcn_wave_barrier();  // every lane has finished reading the blocks about to be overwritten
+#pragma unroll 1
+    for (uint32_t j0 = 0; j0 < jobs; j0 += 64u) {  // a second pass only when more than 64 blocks are wanted (launch start)
+      // lane l's job j0 + l: requester, counter, stream and destination, all re-derived from the wave-uniform masks and the lane id —
+      // twice (chacha8_block_to_lds_job; the empty asm makes the second derivation a new one), so that nothing but the block's 16
+      // words is held through the rounds: the headline kernel stays within its 128 VGPRs
+      auto job = [&] {
+        uint32_t lane = (uint32_t)tid & 63u;
+        asm volatile("" : "+v"(lane));
+        const uint32_t j = j0 + lane;
+        const bool second = j >= n1;
+        const int k4 = (int)((second ? j - n1 : j) << 2);
+        uint32_t req = (uint32_t)__builtin_amdgcn_ds_bpermute(k4, (int)compact(m1, lane));
+        if (ONES) {
+          const uint32_t r2 = (uint32_t)__builtin_amdgcn_ds_bpermute(k4, (int)compact(m2, lane));
+          req = second ? r2 : req;
+        }
+        const int r4 = (int)((req & 63u) << 2);
+        const uint32_t slo = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)(uint32_t)stream);
+        const uint32_t shi = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)(uint32_t)(stream >> 32));
+        const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)first) + (second ? 1u : 0u);
+        return ChachaJob{c, ((uint64_t)shi << 32) | slo, s_rng + (size_t)(c & 1u) * 8 * NT, (tid & ~63) | (r4 >> 2), j < jobs};
+      };
+      chacha8_block_to_lds_job<NT, ROLL_HOT>(key, job);  // all 64 lanes (the permutes read from lanes that have no job)
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   __device__ __forceinline__ uint64_t next_u64() {
     uint32_t c = pos >> 4;
@@ -796,8 +849,9 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
         state = shade_state();
       }
     } else if (pick == ST_GEN) {
+      bool active = false;
       if (state == ST_GEN) {
-        bool active = true;
+        active = true;
         if (STEAL && P.steal_state && have_pixel && n < spp) {  // a sample boundary: has a wave without work asked for this pixel?
           const size_t pix = (size_t)pr * W + px;
           if (__atomic_load_n(&P.steal_state[pix], __ATOMIC_RELAXED) == 1u) {
@@ -852,8 +906,12 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
             uint32_t tile = slot >> 6, in = slot & 63u;
             if (P.tile_order) tile = P.tile_order[tile];  // expensive tiles first
             ptile = tile;
-            px = (tile % P.tiles_x) * 8u + (in & 7u);
-            pr = (tile / P.tiles_x) * 8u + (in >> 3);
+            // (the empty asm: the division's reciprocal is formed here, once per pixel, instead of being hoisted out of the loop into a
+            // VGPR held through every block — with RL_COOP_GEN that register would spill)
+            uint32_t tiles_x = P.tiles_x;
+            asm volatile("" : "+s"(tiles_x));
+            px = (tile % tiles_x) * 8u + (in & 7u);
+            pr = (tile / tiles_x) * 8u + (in >> 3);
             if (px >= W || pr >= P.nrows) active = false;  // slot outside the image: stay in GEN, claim again next time
             else {
               have_pixel = true;
@@ -876,31 +934,51 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
         if (active) {
           uint32_t y = P.row_first + pr * P.row_step;
           uint64_t sample_index = (uint64_t)n + P.first_sample;
-          rng.reset_stream(sample_index * WH + (uint64_t)px * (uint64_t)W + (uint64_t)y);  // camera.rs:167-170
-          // get_ray camera.rs:203-216
-          D3 p00 = ld3(cam.pixel_00), du = ld3(cam.pixel_du), dv = ld3(cam.pixel_dv);
-          D3 pixel_center = (p00 + du * (double)px) + dv * (double)y;
-          double sx = -0.5 + rng.gen_f64();
-          double sy = -0.5 + rng.gen_f64();
-          D3 pixel_sample = pixel_center + (du * sx + dv * sy);
-          if (cam.defocus_angle <= 0.0) o = ld3(cam.lookfrom);
-          else {
-            double a, b;
-            rng.unit_disc(a, b);
-            o = (ld3(cam.lookfrom) + ld3(cam.defocus_disk_u) * a) + ld3(cam.defocus_disk_v) * b;
-          }
-          d = pixel_sample - o;
-          time = rng.gen_f64();
-          thr = d3(1.0, 1.0, 1.0);
-          depth = cam.max_depth;
-          if (depth == 0) {  // ray_color(depth 0) = black: the sample contributes (0,0,0)
-            sum = sum + d3(0.0, 0.0, 0.0);
-            n++;
-          } else {
-            c_rays++;
-            pix_rays++;
-            start_ray();
-          }
+          const uint64_t stream = sample_index * WH + (uint64_t)px * (uint64_t)W + (uint64_t)y;  // camera.rs:167-170
+          if (RL_COOP_GEN) rng.stream = stream, rng.blk_lo = rng.pos >> 4;  // blocks blk_lo, blk_lo + 1: generated below, wave-wide
+          else rng.reset_stream(stream);
+        }
+      }
+      bool fill = false;
+      if (RL_COOP_GEN) {
+        uint32_t nb = active ? 2u : 0u, first = rng.blk_lo;
+        if (RL_COOP_GEN == 2) {  // FILL lanes ride along when the pass has room for them: one block each, top_up's
+          const uint32_t g2 = 2u * (uint32_t)__popcll(__ballot(active)), nf = (uint32_t)__popcll(__ballot(state == ST_FILL));
+          fill = state == ST_FILL && (g2 + nf + 63u) / 64u <= (g2 > 64u ? 2u : 1u);
+          if (fill) nb = 1u, first = rng.blk_lo + rng.nres;
+        }
+        rng.template coop_blocks<RL_COOP_GEN == 2>(nb, first);
+        if (active) rng.nres = 2;
+        if (fill) {
+          rng.top_up_done();
+          state = shade_state();
+        }
+      }
+      if (active) {
+        uint32_t y = P.row_first + pr * P.row_step;
+        // get_ray camera.rs:203-216
+        D3 p00 = ld3(cam.pixel_00), du = ld3(cam.pixel_du), dv = ld3(cam.pixel_dv);
+        D3 pixel_center = (p00 + du * (double)px) + dv * (double)y;
+        double sx = -0.5 + rng.gen_f64();
+        double sy = -0.5 + rng.gen_f64();
+        D3 pixel_sample = pixel_center + (du * sx + dv * sy);
+        if (cam.defocus_angle <= 0.0) o = ld3(cam.lookfrom);
+        else {
+          double a, b;
+          rng.unit_disc(a, b);
+          o = (ld3(cam.lookfrom) + ld3(cam.defocus_disk_u) * a) + ld3(cam.defocus_disk_v) * b;
+        }
+        d = pixel_sample - o;
+        time = rng.gen_f64();
+        thr = d3(1.0, 1.0, 1.0);
+        depth = cam.max_depth;
+        if (depth == 0) {  // ray_color(depth 0) = black: the sample contributes (0,0,0)
+          sum = sum + d3(0.0, 0.0, 0.0);
+          n++;
+        } else {
+          c_rays++;
+          pix_rays++;
+          start_ray();
         }
       }
       if (LATENCY_MODES && LDS_SCENE == 4 && P.prio_tiles != 0u) {  // A/B: issue priority for the waves that hold the frame's longest sample chains
