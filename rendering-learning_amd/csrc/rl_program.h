@@ -53,6 +53,7 @@ static_assert(sizeof(CompactOp) == 32, "CompactOp must be 32 B");
 // the two of them and descends into the nearer one first.  The boxes only ever REJECT (rl_rtiow_wave.h).  child = eA | eB << 16 with
 // entry ids e: inner node i -> i, sphere s -> n_inner + s; FAST_NONE = empty stack.
 static const uint32_t FAST_NONE = 1023u;
+static const uint32_t FAST_DEPTH_MASK = 0x3FFFFFu;  // rtiow_wave_kernel<.., 4, ..> keeps the remaining depth in 22 bits: variant 1029 needs max_depth < 2^22
 static const uint32_t FAST_MAX_DEPTH = 14;  // the per-lane stack holds 15 ten-bit entries above its sentinel
 struct alignas(16) FastNode {
   float box[2][6];  // [child][x.min, x.max, y.min, y.max, z.min, z.max]

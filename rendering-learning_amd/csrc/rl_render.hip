@@ -859,6 +859,8 @@ static int choose_rtiow_variant(const rl_scene *scene, const rl_rtiow_camera *ca
     // pixels on the wave-scheduled kernel with work stealing is as fast or faster (37 k: 173 ms, 90 k: 170 ms; tools/steal_ab.py).
     if (variant == 1029 && !want_stats && g_sw.coop_small && (uint64_t)nrows * W <= (uint64_t)g_cus * 16u * 10u) variant = 1033;
   }
+  // 1029 keeps a path's remaining depth in 22 bits (rl_rtiow_wave.h, the self-test skip): deeper paths take the next layout that fits
+  if (variant == 1029 && cam->max_depth > FAST_DEPTH_MASK) variant = fits_compact ? 1027 : fits_ops ? 1025 : 1024;
   out.variant = variant, out.general = general, out.compact_bytes = compact_bytes, out.fast_bytes = fast_bytes, out.scene_bytes = scene_bytes, out.fits_fast = fits_fast;
   return RL_OK;
 }
@@ -1454,7 +1456,8 @@ int rl_debug_has_experimental(void) {
 #endif
 }
 
-// Not part of the ABI (tools only): scheduler occupancy counters of the last STATS launch, 32 x u64.
+// Not part of the ABI (tools only): scheduler occupancy counters of the last STATS launch, 32 x u64 ([3s .. 3s+2] per state; [24]: the
+// fast kernel's skipped self tests, rl_rtiow_wave.h fast_self_miss).
 int rl_debug_sched(const rl_scene *scene, unsigned long long *out32) {
   if (!scene || !out32) return RL_E_INVALID;
   HIP_TRY(hipMemcpy(out32, scene->d_scratch + 128, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));

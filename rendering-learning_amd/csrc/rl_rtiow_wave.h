@@ -364,6 +364,31 @@ __device__ __forceinline__ void fast_sphere_hit(const DevSphere &s, uint32_t pay
   if (t <= closest) closest = t, hit_prim = payload;
 }
 
+// The self test of a scattered ray.  A ray that leaves a sphere starts at p, the rounded hit point, so its origin lies inside that sphere's
+// padded box and the reject-only box test can never drop the sphere: without this every secondary ray pays a LEAF visit on the sphere it
+// just left, which almost always returns nothing.  SHADE proves that here and the TRAV step then skips that one child entry.
+// With o = p, oc = p - center is the value fast_sphere_hit would form (same time, same expressions), and so are a = len2(d),
+// half_b = dot(oc, d) and c = len2(oc) - r2.  The visit accepts nothing when both ROUNDED roots are below 1e-10 (u = 2^-53, sqrt
+// faithful: one rounding of <= 2u):
+//   r_l:  half_b > 0  =>  -half_b - sq < 0  =>  r_l < 0.
+//   r_u:  disc = RN(RN(half_b^2) - RN(a c)) differs from half_b^2 by <= 2.01u half_b^2 + 1.01 a|c|.  If disc <= half_b^2, sq <= (1 + 2u) half_b;
+//         else sqrt(disc) - half_b = (disc - half_b^2) / (sqrt(disc) + half_b) < (2.01u half_b^2 + 1.01 a|c|) / (2 half_b).  Either way
+//         sq - half_b <= 3.01u half_b + 0.51 a|c| / half_b, and the subtraction and the division add two roundings:
+//         r_u <= (3.02u half_b^2 + 0.52 a|c|) / (a half_b).
+// So the test is  4u half_b^2 + 0.6 a|c| < 1e-10 a half_b  (its own roundings, a few u, sit far inside the 4 / 3.02 and 0.6 / 0.52 headroom)
+// together with  1e-270 <= 1e-10 a half_b <= DBL_MAX.  The lower end asks half_b > 0 and a > 0 and keeps underflow out of it: the products
+// of disc that go subnormal add <= 1.5e-323 to it, i.e. <= 1.5e-323 / (a half_b) < 1e-60 to r_u.  The upper end keeps overflow out (an
+// infinite right-hand side would pass any finite left-hand side).  A NaN anywhere fails a comparison: no skip.  The reference's
+// Sphere::hit on this sphere then returns None for every window that starts at 1e-10 — so the fold's answer, the tie and order checks
+// (amb) and the panic-site count cannot change.  An inward ray (refraction into the sphere, half_b < 0) and a camera ray never skip.
+__device__ __forceinline__ bool fast_self_miss(const DevSphere &s, D3 oc, D3 d) {
+  const double a = len2(d);
+  const double half_b = dot(oc, d);
+  const double c = len2(oc) - s.r2;
+  const double rhs = 1e-10 * (a * half_b);
+  return rhs >= 1e-270 && rhs <= 1.7976931348623157e308 && 4.4408920985006262e-16 * (half_b * half_b) + 0.6 * (a * fabs(c)) < rhs;  // 4u
+}
+
 // The reference's fold, verbatim: threaded program in stored order, exact divisions, Sphere::hit with ray_t.max = closest so far
 // (bvh.rs:79-95, hittable/mod.rs:88-111).  Returns the number of from_normalized asserts tripped on the way.
 __device__ __forceinline__ uint32_t fast_slow_trace(const DevOp *ops, const DevSphere *spheres, D3 o, D3 d, double time, double &closest, uint32_t &hit_prim) {
@@ -519,8 +544,12 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
   RayAux32 ra32 = ray_aux32(ra);
   double time = 0.0, closest = INF;
   uint32_t pc = 0, hit_prim = NONE, depth = 0;
+  // fast traversal: depth carries, in its top ten bits, the entry id of the sphere the ray has just left when fast_self_miss proved that the
+  // ray's own LEAF visit would accept nothing (FAST_NONE otherwise, and for camera rays); the remaining depth sits in the low 22 bits
+  // (the host runs variant 1029 for max_depth < 2^22 only).  The kernel is at exactly 128 VGPRs, and one more register costs a wave per SIMD.
+  constexpr uint32_t DEPTH_MASK = LDS_SCENE == 4 ? FAST_DEPTH_MASK : ~0u;
   uint32_t c_rays = 0, c_flag = 0, c_slow = 0;  // c_slow: rays the fast traversal handed to the reference-order fold
-  unsigned long long c_nodes = 0, c_sph = 0, c_words = 0;
+  unsigned long long c_nodes = 0, c_sph = 0, c_words = 0, c_self = 0;  // c_self (STATS): self tests skipped
 
   // fast traversal (LDS_SCENE = 4): 16 ten-bit entry ids in five registers, newest in the low bits of stk0; all ones = empty
   uint32_t stk0 = ~0u, stk1 = ~0u, stk2 = ~0u, stk3 = ~0u, stk4 = ~0u;
@@ -658,10 +687,20 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
           } else {
             path_done = true;  // Flat
           }
+          // fast traversal: may the next ray skip its test of this sphere?  (decided for every hit: a path that ends here starts its
+          // next sample in GEN, which clears the entry.)  The sphere is read again and its centre and oc = p - center re-derived — the
+          // same expressions, the same values — instead of being held through the material code above (that costs 21 spilled VGPRs)
+          if (LDS_SCENE == 4) {
+            const DevSphere *sp = spheres + si;
+            asm volatile("" : "+v"(sp));  // a fresh load, not the registers of the first one
+            D3 c1 = ld3(sp->c0);
+            if (hit_prim & SPH_MOVING) c1 = c1 + ld3(sp->dc) * time;
+            depth = (depth & DEPTH_MASK) | ((fast_self_miss(*sp, p - c1, nd) ? P.n_fast_inner + si : FAST_NONE) << 22);
+          }
         }
         if (!path_done) {
           depth--;
-          if (depth == 0) path_done = true;  // ray_color(.., 0) = black
+          if ((depth & DEPTH_MASK) == 0) path_done = true;  // ray_color(.., 0) = black
         }
         if (path_done) {
           n++;
@@ -752,9 +791,11 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
             };
             if (STATS) c_nodes += 2;  // debug instantiation only (rl_debug_fast_stats): the fast structure's own tests, not the reference's
             float tA, tB;
-            const bool hitA = !missed(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tA);
-            const bool hitB = !missed(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, tB);
-            const uint32_t eA = w & 0xFFFFu, eB = w >> 16;
+            const uint32_t eA = w & 0xFFFFu, eB = w >> 16, self = depth >> 22;  // self: the sphere the ray left, proven missed (fast_self_miss)
+            const bool boxA = !missed(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tA);
+            const bool boxB = !missed(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, tB);
+            const bool hitA = boxA && eA != self, hitB = boxB && eB != self;
+            if (STATS) c_self += (boxA && !hitA) + (boxB && !hitB);
             const bool a_first = hitA && (!hitB || tA <= tB);
             uint32_t first = a_first ? eA : eB;
             if (hitA && hitB) fast_push(a_first ? eB : eA);
@@ -971,8 +1012,8 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
         d = pixel_sample - o;
         time = rng.gen_f64();
         thr = d3(1.0, 1.0, 1.0);
-        depth = cam.max_depth;
-        if (depth == 0) {  // ray_color(depth 0) = black: the sample contributes (0,0,0)
+        depth = LDS_SCENE == 4 ? cam.max_depth | (FAST_NONE << 22) : cam.max_depth;  // a camera ray has no sphere of its own
+        if (cam.max_depth == 0) {  // ray_color(depth 0) = black: the sample contributes (0,0,0)
           sum = sum + d3(0.0, 0.0, 0.0);
           n++;
         } else {
@@ -1031,6 +1072,10 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_kernel(RtiowPar
     if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
     v = wave_sum(c_words);
     if ((tid & 63) == 0) atomicAdd(&P.stats[5], v);
+    if (LDS_SCENE == 4) {
+      v = wave_sum(c_self);
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 24], v);  // after the scheduler's 21 words (rl_debug_sched out[24])
+    }
   }
 }
 

@@ -15,6 +15,8 @@ L = rl.api.render_lib(); L.rl_debug_sched.argtypes = [C.c_void_p, C.c_void_p]
 L.rl_debug_sched(w.device(), out)
 names = {0: "GEN", 1: "TRAV", 2: "SHADE", 3: "FILL", 5: "LEAF", 6: "SHADE2"}
 print("rays", st["rays"], "kernel_ms", st["kernel_ms"], "Mrays/s", st["rays"] / st["kernel_ms"] / 1e3, "box tests/ray", st["node_tests"] / st["rays"], "sphere tests/ray", st["sphere_tests"] / st["rays"])
+if out[24]:  # the fast kernel's self tests skipped in TRAV (rl_rtiow_wave.h fast_self_miss): sphere tests/ray + this = without the skip
+    print("self tests skipped/ray", out[24] / st["rays"])
 tot = sum(out[3 * k + 2] for k in names)
 for k, nm in names.items():
     ex, pop, cyc = out[3 * k], out[3 * k + 1], out[3 * k + 2]
