@@ -257,6 +257,25 @@ int rl_rtiow_render_device(const rl_scene *, const rl_rtiow_camera *, uint64_t f
                            uint32_t row_first, uint32_t row_step, void *d_out_rgb_sum,
                            void *hip_stream, rl_stats *opt_stats);
 
+/* Sample-parallel rendering with independent sample streams.  Every sample is rendered as the reference renders the FIRST sample of
+ * a render: c_s(x, y) = Camera::_render(s, world) with samples_per_pixel = 1 — a fresh ChaCha8Rng at word position 0 on stream
+ * s*W*H + x*W + y, get_ray, ray_color (ray-tracing-one-weekend/src/camera.rs:145-174).  With F = first_sample and S =
+ * cam->samples_per_pixel the output is, per component, in f64 and left to right without contraction:
+ *     out(x, y) = ((((A + c_F) + c_{F+1}) + ...) + c_{F+S-1}),   A = 0.0 (accumulate = 0) or the sums already in out (accumulate = 1)
+ * — bit for bit the canvas of S repetitions of `canvas = cam1.render_from_checkpoint(world, &canvas)` from a canvas that holds A with
+ * samples = F (cam1: the same camera with samples_per_pixel = 1; camera.rs:136-143, Canvas::merge camera.rs:273-291).  The samples do
+ * not chain, so the frame does not depend on how the work is split: a + b samples in two calls with accumulate = 1, any row shard and
+ * any number of passes give the same bits as one call.  It is a different image from rl_rtiow_render* of S samples (same distribution,
+ * other random numbers).  Output: compact shard rows as rl_rtiow_render_rows; when accumulate = 1 the buffer is read first.
+ * The _rows form takes a host buffer; the _device form a device buffer and a hipStream_t, asynchronous unless opt_stats is non-NULL
+ * (then all seven counters, as the sums of the S single-sample counting renders).  rl_render_status reports rays and flagged for the
+ * asynchronous form; a reached panic site returns RL_E_DEGENERATE.  rl_rtiow_render_progress reports nothing for these renders. */
+int rl_rtiow_render_independent_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first,
+                                     uint32_t row_step, uint32_t accumulate, double *out_rgb_sum, rl_stats *opt_stats);
+int rl_rtiow_render_independent_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first,
+                                       uint32_t row_step, uint32_t accumulate, void *d_out_rgb_sum, void *hip_stream,
+                                       rl_stats *opt_stats);
+
 /* Completion + status of the ASYNCHRONOUS renders of this scene since the last call (rl_*_render_device / rl_*_render_multi_device
  * with opt_stats == NULL): waits for all of them, fills opt_stats->rays with the ray count of the most recently enqueued one and
  * ->flagged with the panic sites reached by any of them (the other counters need a counting render) and returns RL_E_DEGENERATE

@@ -165,6 +165,7 @@ def host_lib():
 RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", "rl_last_error", "rl_abi_version", "rl_device_info", "rl_rtiow_render_progress",
                   "rl_scene_destroy", "rl_render_status",
                   "rl_rtiow_scene_create", "rl_bvh_build", "rl_rtiow_render", "rl_rtiow_render_rows", "rl_rtiow_render_device",
+                  "rl_rtiow_render_independent_rows", "rl_rtiow_render_independent_device",
                   "rl_rtiow_render_multi", "rl_rtiow_render_multi_device", "rl_rtiow_encode_rgb8_device", "rl_rtiow_render_rgb8",
                   "rl_rtc_scene_create", "rl_rtc_render", "rl_rtc_render_rows", "rl_rtc_render_device",
                   "rl_rtc_render_multi", "rl_rtc_render_multi_device", "rl_rtc_encode_rgb8_device", "rl_rtc_render_rgb8"]
@@ -190,6 +191,10 @@ def render_lib():
         L.rl_rtiow_render.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtiow_render_independent_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                       C.POINTER(Stats)]
+        L.rl_rtiow_render_independent_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                         C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_rgb8.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_encode_rgb8_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
         L.rl_rtc_render_rgb8.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
@@ -269,6 +274,20 @@ def set_steal(max_fill):
     L = render_lib()
     L.rl_debug_set_steal.argtypes = [C.c_double]
     L.rl_debug_set_steal(float(max_fill))
+
+
+def set_indep_cap(nbytes):
+    """Tests / tools: cap of the sample-parallel mode's pass buffer in bytes (0: the default 1 GiB); a small cap forces several passes."""
+    L = render_lib()
+    L.rl_debug_set_indep_cap.argtypes = [C.c_ulonglong]
+    L.rl_debug_set_indep_cap(int(nbytes))
+
+
+def set_indep_k(k):
+    """Tests / tools: samples of one pixel per claim in the sample-parallel mode (default 1)."""
+    L = render_lib()
+    L.rl_debug_set_indep_k.argtypes = [C.c_uint]
+    L.rl_debug_set_indep_k(int(k))
 
 
 def has_experimental():
@@ -645,6 +664,51 @@ class Camera:
 
     def render_rows(self, world: World, row_first, row_step, first_sample=0, stats=None):
         return self._render(first_sample, world, row_first, row_step, stats)
+
+    # ---- sample-parallel rendering with independent sample streams (include/rl_render.h rl_rtiow_render_independent*): every sample is
+    # rendered as the first sample of a render is (fresh ChaCha8 stream at word 0), and the S colours are added to the sums left to right
+    def render_independent(self, world: World, checkpoint: Canvas = None, stats=None, allow_degenerate=False) -> Canvas:
+        """S = samples_per_pixel independent samples; with a checkpoint they continue its sums from sample checkpoint.samples on, and the
+        canvas holds checkpoint.samples + S samples.  Bit for bit S repetitions of render_from_checkpoint with samples_per_pixel = 1."""
+        if checkpoint is None:
+            data = self.render_independent_rows(world, 0, 1, stats=stats, allow_degenerate=allow_degenerate)
+            return Canvas(self.params.samples_per_pixel, self.c.image_width, self.c.image_height, data)
+        assert checkpoint.width == self.c.image_width and checkpoint.height == self.c.image_height
+        data = np.array(checkpoint.data, dtype=np.float64, order="C").reshape(self.c.image_height, self.c.image_width, 3)
+        self.render_independent_rows(world, 0, 1, first_sample=checkpoint.samples, accumulate=True, out=data, stats=stats,
+                                     allow_degenerate=allow_degenerate)
+        return Canvas(checkpoint.samples + self.params.samples_per_pixel, self.c.image_width, self.c.image_height, data)
+
+    def render_independent_rows(self, world: World, row_first, row_step, first_sample=0, accumulate=False, out=None, stats=None,
+                                allow_degenerate=False):
+        """Compact shard rows [nrows, W, 3] of samples first_sample .. first_sample + S - 1; accumulate=True adds them to `out`
+        (a C-contiguous f64 array of that shape, updated in place)."""
+        nrows = rows_for(self.c.image_height, row_first, row_step)
+        if out is None:
+            if accumulate:
+                raise ValueError("accumulate=True needs the sums to continue from (out=)")
+            out = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
+        if out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or out.size != nrows * self.c.image_width * 3:
+            raise ValueError("out must be a C-contiguous float64 array of nrows * W * 3 values")
+        st = Stats()
+        rc = render_lib().rl_rtiow_render_independent_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, int(bool(accumulate)),
+                                                           out.ctypes.data, C.byref(st))
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+        return out
+
+    def render_independent_device(self, world: World, d_ptr, stream=0, row_first=0, row_step=1, first_sample=0, accumulate=False, stats=None,
+                                  allow_degenerate=False):
+        """Output stays in HBM (d_ptr: nrows*W*3 f64, read first when accumulate).  Async unless stats is a dict."""
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_independent_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, int(bool(accumulate)),
+                                                             C.c_void_p(d_ptr), C.c_void_p(stream), C.byref(st) if st is not None else None)
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
 
     def render_multi(self, world: World, first_sample=0, stats=None, allow_degenerate=False) -> Canvas:
         """rl_rtiow_render_multi: the whole frame over every GPU of init_multi (rows interleaved, one RCCL exchange)."""

@@ -66,6 +66,8 @@ struct Switches {
   bool rtc_force_full = false;   // RL_RTC_FORCE_FULL
   int rtc_regs = 256;            // RL_RTC_REGS=768|1024: rtc_kernel at the register budget of three / four waves per SIMD (experimental library only)
   int rtc_full_regs = 768;       // RL_RTC_FULL_REGS (256 / 512: experimental library only)
+  unsigned indep_k = 1;          // RL_INDEP_K=<k>: samples of one pixel per claim in the sample-parallel mode
+  size_t indep_cap = (size_t)1 << 30;  // RL_INDEP_CAP_MB=<MiB>: cap of that mode's pass buffer (a smaller one forces more passes: tests)
 } g_sw;
 unsigned long long g_last_slow_traces = 0;
 bool g_fast_debug_stats = false;  // tools only (experimental library): counting renders run the fast kernel too (counters are then NOT the reference's)
@@ -103,6 +105,8 @@ void read_switches() {
   w.rtc_force_full = std::getenv("RL_RTC_FORCE_FULL") != nullptr;
   if (const char *v = std::getenv("RL_RTC_REGS")) w.rtc_regs = std::atoi(v);
   if (const char *v = std::getenv("RL_RTC_FULL_REGS")) w.rtc_full_regs = std::atoi(v);
+  if (const char *v = std::getenv("RL_INDEP_K")) w.indep_k = (unsigned)std::max(1, std::atoi(v));
+  if (const char *v = std::getenv("RL_INDEP_CAP_MB")) w.indep_cap = (size_t)std::max(1, std::atoi(v)) << 20;
   g_sw = w;
 #ifdef RL_EXPERIMENTAL
   rl::set_build_octo(w.fastg_octo != 0);
@@ -289,7 +293,7 @@ static void destroy_one(rl_scene *s) {
   if (s->ev0) hipEventDestroy(s->ev0);
   if (s->ev1) hipEventDestroy(s->ev1);
   if (s->ev_gather_read) hipEventDestroy(s->ev_gather_read);
-  hipFree(s->d_params);
+  hipFree(s->d_params), hipFree(s->d_indep);
   hipFree(s->d_wfg_pix), hipFree(s->d_wfg_ray), hipFree(s->d_wfg_q0), hipFree(s->d_wfg_q1), hipFree(s->d_wfg_qs), hipFree(s->d_wfg_ctl);
   if (s->h_wfg) hipHostFree(s->h_wfg);
   delete s;
@@ -1192,6 +1196,141 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
   if (rc == RL_OK) rc = mark_render_end(scene, stream);
   return rc;
 }
+
+// The sample-parallel mode (include/rl_render.h rl_rtiow_render_independent*).  A work item is (sample group of indep_k samples, pixel),
+// every sample from ChaCha word 0 on its own stream; the samples of a PASS write their colours to the scene's pass buffer and
+// rtiow_indep_fold adds them to d_out in ascending sample order.  Passes are sized so the buffer stays under g_sw.indep_cap and the
+// pass's slots fit the u32 work counter; they are enqueued back to back on `stream`.  The stats words are zeroed once per render.
+int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                              bool accumulate, void *d_out, hipStream_t stream, bool want_stats) {
+  const RtiowProgram &rt = scene->rt();
+  const HostRtiow &H = *scene->hrt;
+  const uint32_t H_ = cam->image_height, W = cam->image_width;
+  const uint32_t nrows = row_first < H_ ? (H_ - row_first + row_step - 1) / row_step : 0;
+  RtiowParams P;
+  uint64_t tile_slots = 0;
+  {
+    int rcp = fill_rtiow_params(scene, cam, first_sample, row_first, row_step, nrows, d_out, want_stats, P, tile_slots);
+    if (rcp != RL_OK) return rcp;
+  }
+  P.pix_rays = nullptr, P.pos_state = nullptr, P.tile_order = nullptr, P.tile_cost = nullptr, P.resume = 0;
+  RtiowChoice choice;
+  {
+    int rcv = choose_rtiow_variant(scene, cam, P, nrows, want_stats, choice);
+    if (rcv != RL_OK) return rcv;
+  }
+  // the fast traversals where the automatic choice takes them (the cooperative kernel's small frames included: here they have
+  // pixels x samples of parallelism), and the reference-order wave-scheduled general kernel for everything else (counting renders too)
+  int variant = choice.variant;
+  if (variant == 1033) variant = 1029;
+  if (variant == 1035) variant = 1031;
+  if ((variant == 1029 && want_stats) || (variant != 1029 && variant != 1031)) variant = 4;
+  const uint32_t S = cam->samples_per_pixel;
+  const uint64_t n_vals = (uint64_t)nrows * W * 3u;
+  const size_t sample_bytes = (size_t)n_vals * sizeof(double);
+  const uint32_t K = g_sw.indep_k ? g_sw.indep_k : 1u;
+  // samples per pass: the buffer cap, and the slots (groups x tile slots) below the u32 work counter's end
+  uint64_t per_pass = std::max<uint64_t>(1, g_sw.indep_cap / sample_bytes);
+  const uint64_t max_groups = std::max<uint64_t>(1, (0xFFFF0000ull - 1) / tile_slots);
+  per_pass = std::min<uint64_t>(per_pass, max_groups * K);
+  per_pass = std::min<uint64_t>(per_pass, std::max<uint32_t>(S, 1u));
+  rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only; the scene program is immutable
+  {
+    int rco = order_after_previous(scene, stream);
+    if (rco != RL_OK) return rco;
+  }
+  const size_t buf_bytes = (size_t)per_pass * sample_bytes;
+  if (S > 0 && ms->indep_bytes < buf_bytes) {
+    hipFree(ms->d_indep);
+    ms->d_indep = nullptr, ms->indep_bytes = 0;
+    HIP_TRY(hipMalloc((void **)&ms->d_indep, buf_bytes));
+    ms->indep_bytes = buf_bytes;
+  }
+  P.indep_buf = ms->d_indep, P.indep_k = K, P.indep_tile_slots = (uint32_t)tile_slots;
+  HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 512, stream));  // work counter and stats: once per render
+  const bool trans = rt.has_noise || rt.has_sphere_uv;
+  const bool fg_media = H.fg.stage_roots.size() > 1;
+  const bool one_wave = variant == 1031 && trans && fg_media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : (uint64_t)nrows * W <= (uint64_t)g_cus * 1536u);
+  int nt = 512;
+  size_t lds = 0;
+  if (variant == 1029) {
+    nt = 1024, lds = (size_t)16 * 1024 * sizeof(unsigned long long) + choice.fast_bytes;
+    if (!g_sw.tune_set) P.tune[1] = 4, P.tune[2] = 4;
+  } else if (variant == 1031) {
+    if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
+    const int SD = (one_wave || fg_media || trans) ? 40 : 20;
+    nt = one_wave ? 256 : (fg_media || trans) ? 512 : 768;
+    const size_t base = (size_t)nt * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));  // as in rtiow_render_launch's fastg_lds
+    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
+    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(H.fg.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
+    lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
+    if (one_wave && lds < 90000) lds = 90000;  // one workgroup per CU
+  } else {
+    lds = (size_t)512 * (16 + (rt.has_media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long);
+  }
+  uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));  // persistent lanes: as many workgroups as stay resident
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu * (uint32_t)nt > 2048) per_cu = 2048 / (uint32_t)nt;
+  auto blocks_of = [&](const void *kern, uint32_t &blocks) -> int {
+    blocks = (uint32_t)(((uint64_t)P.n_slots + nt - 1) / nt);
+    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
+    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;
+    if (ensure_lds_attr(kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    return RL_OK;
+  };
+  auto launch = [&](void (*kern)(RtiowParams)) -> int {  // parameter block by value
+    uint32_t blocks = 0;
+    int rcb = blocks_of((const void *)kern, blocks);
+    if (rcb != RL_OK) return rcb;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
+    HIP_TRY(hipGetLastError());
+    return RL_OK;
+  };
+  auto launch_ptr = [&](void (*kern)(const RtiowParams *)) -> int {  // by pointer: each pass its own stream-ordered copy (two slots)
+    uint32_t blocks = 0;
+    int rcb = blocks_of((const void *)kern, blocks);
+    if (rcb != RL_OK) return rcb;
+    if (!ms->d_params) HIP_TRY(hipMalloc((void **)&ms->d_params, 2 * sizeof(RtiowParams)));
+    RtiowParams *slot = (RtiowParams *)ms->d_params + (ms->params_slot++ & 1);
+    HIP_TRY(hipMemcpyAsync(slot, &P, sizeof(RtiowParams), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, (const RtiowParams *)slot);
+    HIP_TRY(hipGetLastError());
+    return RL_OK;
+  };
+  auto launch_pass = [&]() -> int {
+    if (variant == 1029) return launch(rtiow_wave_indep_kernel<1024, 4, false>);
+    if (variant == 1031) {
+      if (one_wave) return launch_ptr(rtiow_fast_general_indep_kernel<256, 40, true, true>);
+      if (fg_media) return trans ? launch_ptr(rtiow_fast_general_indep_kernel<512, 40, true, true>) : launch_ptr(rtiow_fast_general_indep_kernel<512, 40, false, true>);
+      if (trans) return launch_ptr(rtiow_fast_general_indep_kernel<512, 40, true, false>);
+      return launch_ptr(rtiow_fast_general_indep_kernel<768, 20, false, false>);
+    }
+    if (rt.has_media) {
+      if (trans) return want_stats ? launch(rtiow_wave_general_indep_kernel<512, true, true, true>) : launch(rtiow_wave_general_indep_kernel<512, true, false, true>);
+      return want_stats ? launch(rtiow_wave_general_indep_kernel<512, false, true, true>) : launch(rtiow_wave_general_indep_kernel<512, false, false, true>);
+    }
+    if (trans) return want_stats ? launch(rtiow_wave_general_indep_kernel<512, true, true, false>) : launch(rtiow_wave_general_indep_kernel<512, true, false, false>);
+    return want_stats ? launch(rtiow_wave_general_indep_kernel<512, false, true, false>) : launch(rtiow_wave_general_indep_kernel<512, false, false, false>);
+  };
+  if (want_stats) HIP_TRY(hipEventRecord(scene->ev0, stream));
+  int rc = RL_OK;
+  if (S == 0 && !accumulate && n_vals) HIP_TRY(hipMemsetAsync(d_out, 0, sample_bytes, stream));  // no samples: the empty sum
+  for (uint64_t b = 0; b < S && rc == RL_OK; b += per_pass) {
+    const uint32_t e = (uint32_t)std::min<uint64_t>(S, b + per_pass), np = e - (uint32_t)b;
+    P.sample_begin = (uint32_t)b, P.sample_end = e;
+    P.n_slots = (uint32_t)((uint64_t)((np + K - 1) / K) * tile_slots);
+    if (b != 0) HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 4, stream));  // work counter only; stats keep accumulating
+    rc = launch_pass();
+    if (rc != RL_OK) break;
+    const uint32_t fb = 256;
+    hipLaunchKernelGGL(rtiow_indep_fold, dim3((unsigned)((n_vals + fb - 1) / fb)), dim3(fb), 0, stream, (double *)d_out, (const double *)ms->d_indep, (unsigned long long)n_vals, np,
+                       (uint32_t)(b != 0 || accumulate));
+    HIP_TRY(hipGetLastError());
+  }
+  if (want_stats) HIP_TRY(hipEventRecord(scene->ev1, stream));
+  if (rc == RL_OK) rc = mark_render_end(scene, stream);
+  return rc;
+}
 }  // namespace rl
 
 extern "C" {
@@ -1208,6 +1347,22 @@ int rl_rtiow_render_device(const rl_scene *scene, const rl_rtiow_camera *cam, ui
   }
   std::lock_guard<std::mutex> lk(scene->mu);  // concurrent renders of one scene: see rl_scene::mu
   int rc = rl::rtiow_render_launch(scene, cam, first_sample, row_first, row_step, d_out, stream, st != nullptr);
+  if (rc != RL_OK) return rc;
+  return st ? rl::collect_stats(scene, stream, st) : post_status(scene, stream);
+}
+
+int rl_rtiow_render_independent_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                       uint32_t accumulate, void *d_out, void *hip_stream, rl_stats *st) {
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 1 || !cam || !d_out || row_step == 0) return set_err(RL_E_INVALID, "bad argument");
+  if (cam->image_width == 0 || cam->image_height == 0) return set_err(RL_E_INVALID, "empty image");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  if (row_first >= cam->image_height) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  std::lock_guard<std::mutex> lk(scene->mu);  // concurrent renders of one scene: see rl_scene::mu
+  int rc = rl::rtiow_render_indep_launch(scene, cam, first_sample, row_first, row_step, accumulate != 0, d_out, stream, st != nullptr);
   if (rc != RL_OK) return rc;
   return st ? rl::collect_stats(scene, stream, st) : post_status(scene, stream);
 }
@@ -1427,6 +1582,8 @@ void rl_debug_set_coop(int on) { g_sw.coop_small = on != 0; }
 void rl_debug_set_steal(double max_fill) { g_sw.steal_max_fill = max_fill; }
 void rl_debug_set_fast_traversal(int on) { g_sw.fast_traversal = on != 0; }
 void rl_debug_set_rtc_blocks(int per_cu) { g_sw.rtc_blocks_per_cu = per_cu < 0 ? 0 : per_cu; }  // 0: as many as are resident (default); n: n per CU (tests)
+void rl_debug_set_indep_cap(unsigned long long bytes) { g_sw.indep_cap = bytes ? (size_t)bytes : (size_t)1 << 30; }  // sample-parallel pass buffer cap (0: default 1 GiB)
+void rl_debug_set_indep_k(unsigned k) { g_sw.indep_k = k ? k : 1u; }  // samples of one pixel per claim in the sample-parallel mode
 void rl_debug_set_fastg_one_wave(int mode) { g_sw.fastg_nt256 = mode; }  // -1: by frame size (default), 0 / 1: never / always the one-wave-per-SIMD form (tests)
 void rl_debug_fast_stats(int on) {  // the instrumented fast kernel <1024, 4, true> exists in the experimental library only
 #ifdef RL_EXPERIMENTAL
@@ -1500,6 +1657,38 @@ int rl_rtiow_render_rows(const rl_scene *scene, const rl_rtiow_camera *cam, uint
   HIP_TRY(hipMalloc((void **)&d_out, bytes));
   rl_stats local;
   int rc = rl_rtiow_render_device(scene, cam, first_sample, row_first, row_step, d_out, g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+  }
+  hipFree(d_out);
+  if (st) *st = local;
+  return rc;
+}
+
+int rl_rtiow_render_independent_rows(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                     uint32_t accumulate, double *out, rl_stats *st) {
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || !cam || !out || row_step == 0) return set_err(RL_E_INVALID, "bad argument");
+  uint32_t H = cam->image_height, W = cam->image_width;
+  uint32_t nrows = row_first < H ? (H - row_first + row_step - 1) / row_step : 0;
+  size_t bytes = (size_t)nrows * W * 3 * sizeof(double);
+  if (bytes == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  int rc0 = rl::use_context(scene->ctx);
+  if (rc0 != RL_OK) return rc0;
+  double *d_out = nullptr;
+  HIP_TRY(hipMalloc((void **)&d_out, bytes));
+  int rc = RL_OK;
+  if (accumulate) {  // the caller's sums are the fold's start
+    hipError_t e = hipMemcpy(d_out, out, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
+  }
+  rl_stats local;
+  std::memset(&local, 0, sizeof local);
+  if (rc == RL_OK) rc = rl_rtiow_render_independent_device(scene, cam, first_sample, row_first, row_step, accumulate, d_out, g_ctx[(size_t)scene->ctx].stream, &local);
   if (rc == RL_OK || rc == RL_E_DEGENERATE) {
     hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));

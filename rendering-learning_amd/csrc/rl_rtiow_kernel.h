@@ -79,7 +79,28 @@ struct RtiowParams {
   const FastMedium *fg_media;    // ... and the media between them
   uint32_t fg_n_seg;
   uint32_t fg_top;  // the first fg_top nodes of fg_nodes (the tree's top, breadth first) are copied into LDS by every workgroup (0: none)
+  // sample-parallel mode (INDEP instantiations, rl_rtiow_render_independent*): a slot is (sample group, pixel); groups of indep_k samples,
+  // sample-major (slot / indep_tile_slots = group); each sample's colour goes to indep_buf[sample - sample_begin][nrows * W][3]
+  double *indep_buf;
+  uint32_t indep_k, indep_tile_slots;
 };
+
+// INDEP: the colour of sample `rel` (relative to the pass's sample_begin) of shard pixel (pr, px) into the pass buffer
+__device__ __forceinline__ void rtiow_indep_store(const RtiowParams &P, uint32_t rel, uint32_t pr, uint32_t px, const D3 &c) {
+  const size_t W = P.cam.image_width;
+  double *b = P.indep_buf + ((size_t)rel * ((size_t)P.nrows * W) + (size_t)pr * W + px) * 3;
+  b[0] = c.x, b[1] = c.y, b[2] = c.z;
+}
+
+// The ordered fold of one pass: out = (((A + c_0) + c_1) + ... ) + c_{np-1} per component, left to right, A = out (accumulate) or 0.0.
+// (No special case for the first sample: 0.0 + c is what Canvas::merge of a fresh canvas computes, -0.0 included.)
+__global__ void rtiow_indep_fold(double *__restrict__ out, const double *__restrict__ buf, unsigned long long n_vals, uint32_t np, uint32_t accumulate) {
+  const unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_vals) return;
+  double acc = accumulate ? out[i] : 0.0;
+  for (uint32_t p = 0; p < np; p++) acc = acc + buf[(size_t)p * n_vals + i];
+  out[i] = acc;
+}
 
 // ---------------------------------------------------------------- ChaCha8
 __device__ __forceinline__ uint32_t rotl32(uint32_t x, int r) { return __builtin_rotateleft32(x, r); }

@@ -135,6 +135,8 @@ struct rl_scene {
   void *d_params = nullptr;  // device copies (two slots) of the parameter block for the kernels that take it by pointer
   unsigned params_slot = 0;
   uint32_t *d_pix_rays = nullptr;  // debug (tools/): per-pixel ray counts of the last counting render
+  double *d_indep = nullptr;       // sample-parallel mode: the pass buffer [samples of a pass][shard pixels][3] (rl_rtiow_render_independent*)
+  size_t indep_bytes = 0;
   void *exp = nullptr;             // experimental kernels' work buffers (rl_render.hip, RL_EXPERIMENTAL builds only)
 };
 

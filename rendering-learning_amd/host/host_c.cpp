@@ -453,6 +453,23 @@ char *rlh_rtiow_run_golden_test(int from_checkpoint, uint64_t *len) {
     return nullptr;
   }
 }
+// golden_test_scene at image_width = width, samples_per_pixel = spp through rtiow::Camera::render_independent_from_checkpoint, from a
+// checkpoint of ckpt_samples samples whose sums are in data (W*H*3 f64, overwritten with the result).  0 or -1 (rlh_last_error).
+int rlh_rtiow_golden_independent(uint32_t width, uint32_t spp, uint64_t ckpt_samples, double *data, uint64_t n_vals) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    s.params.image_width = width, s.params.samples_per_pixel = spp;
+    rtiow::Camera cam(s.params);
+    rtiow::Canvas ckpt{(size_t)ckpt_samples, (size_t)width, cam.image_height, std::vector<double>(data, data + n_vals)};
+    rtiow::Canvas c = cam.render_independent_from_checkpoint(*s.world, ckpt);
+    if (c.data.size() != n_vals) throw std::runtime_error("rlh_rtiow_golden_independent: size mismatch");
+    std::copy(c.data.begin(), c.data.end(), data);
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // tests/ray_tracer.rs:242-275 (which = 0, needs the OBJ text), :56-240 mirror (1), :277-368 csg (2): Camera::render -> Canvas::ppm
 char *rlh_rtc_run_golden_test(int which, const char *obj_text, uint64_t obj_len, uint64_t *len) {
   try {

@@ -22,6 +22,27 @@ Canvas Camera::render_internal(uint64_t samples_already_rendered, const Hittable
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render: ") + rl_last_error());
   return c;
 }
+static Canvas render_independent_impl(const Camera &camera, const Hittable &world, const Canvas *checkpoint) {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_rtiow_camera cam = camera.derived();
+  const size_t n = (size_t)cam.image_width * cam.image_height * 3;
+  if (checkpoint && (checkpoint->width != cam.image_width || checkpoint->height != cam.image_height || checkpoint->data.size() != n))
+    throw std::runtime_error("render_independent_from_checkpoint: size mismatch");
+  Canvas c{(checkpoint ? checkpoint->samples : 0) + camera.params.samples_per_pixel, cam.image_width, cam.image_height,
+           checkpoint ? checkpoint->data : std::vector<double>(n)};
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  int rc = rl_rtiow_render_independent_rows(sc, &cam, checkpoint ? checkpoint->samples : 0, 0, 1, checkpoint ? 1u : 0u, c.data.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_independent_rows: ") + rl_last_error());
+  return c;
+}
+Canvas Camera::render_independent(const Hittable &world) const { return render_independent_impl(*this, world, nullptr); }
+Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
+  return render_independent_impl(*this, world, &checkpoint);
+}
 Canvas Camera::render(const Hittable &world) const { return render_internal(0, world); }  // camera.rs:122
 Canvas Camera::render_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {  // camera.rs:136-143
   return render_internal(checkpoint.samples, world).merge(checkpoint);

@@ -769,6 +769,11 @@ struct Camera {
   Canvas render(const Hittable &world) const;
   Canvas render_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const;
   Canvas render_internal(uint64_t samples_already_rendered, const Hittable &world) const;
+  // sample-parallel rendering with independent sample streams (rl_rtiow_render_independent_rows): every sample as the first sample of a
+  // render, the colours added to the sums left to right; from a checkpoint: samples checkpoint.samples .. + samples_per_pixel - 1 added to
+  // its sums (bit for bit samples_per_pixel repetitions of render_from_checkpoint with one sample per pixel)
+  Canvas render_independent(const Hittable &world) const;
+  Canvas render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const;
 };
 
 // ---------------------------------------------------------------- color.rs / output.rs
