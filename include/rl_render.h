@@ -279,7 +279,8 @@ int rl_rtiow_render_independent_device(const rl_scene *, const rl_rtiow_camera *
 /* Completion + status of the ASYNCHRONOUS renders of this scene since the last call (rl_*_render_device / rl_*_render_multi_device
  * with opt_stats == NULL): waits for all of them, fills opt_stats->rays with the ray count of the most recently enqueued one and
  * ->flagged with the panic sites reached by any of them (the other counters need a counting render) and returns RL_E_DEGENERATE
- * if a reference panic site (camera.rs:86, material.rs:151, vec3.rs:220, ...) was reached, else RL_OK. */
+ * if a reference panic site (camera.rs:86, material.rs:151, vec3.rs:220, ...) was reached, else RL_OK.  Renders of one scene issued
+ * concurrently (several threads, streams or multi-GPU frames) each count exactly once. */
 int rl_render_status(const rl_scene *, rl_stats *opt_stats);
 
 /* Progress of the RTIOW render that is executing on this scene — the reference logs "Scanline-equivalents remaining" once per `image_width`
@@ -288,7 +289,8 @@ int rl_render_status(const rl_scene *, rl_stats *opt_stats);
  * 8 x 8 tiles); phase: a render of >= 64 samples per pixel is two launches (0: samples [0, 8) of every pixel, 1: the rest).  Never waits:
  * the FIRST call switches progress counting on for the renders enqueued after it (their work counters then live in pinned host memory the
  * kernels reach over PCIe, one atomic per wave per 64 pixels) and reports zeros; later calls are two host loads.  Frames of at most ~41 k
- * pixels (cooperative kernel) and counting renders report through the same words.  All three outputs are optional (NULL). */
+ * pixels (cooperative kernel) and counting renders report through the same words.  All three outputs are optional (NULL).  A scene
+ * created under rl_init_multi (one replica per device) is not followed: RL_E_UNSUPPORTED. */
 int rl_rtiow_render_progress(const rl_scene *, uint64_t *pixels_claimed, uint64_t *pixels_total, uint32_t *phase);
 
 /* Camera::render on every GPU of rl_init_multi: image row r is rendered by GPU r mod G with the single-GPU

@@ -16,6 +16,7 @@ Class / function names mirror the reference:
 """
 import ctypes as C
 import os
+import threading
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -110,6 +111,7 @@ class RtcSceneDesc(C.Structure):
 # ----------------------------------------------------------------------------- library loading
 _host = None
 _render = None
+_create_mu = threading.Lock()  # World / RtcWorld.device(): two threads' first renders of one world must not upload it twice
 
 
 def _one_hip_runtime():
@@ -290,6 +292,23 @@ def set_indep_k(k):
     L.rl_debug_set_indep_k(int(k))
 
 
+def set_fastg_one_wave(mode):
+    """Tests / tools: the fast general kernel's one-wave-per-SIMD form: -1 by frame size (default), 0 never, 1 always (where it applies)."""
+    L = render_lib()
+    L.rl_debug_set_fastg_one_wave.argtypes = [C.c_int]
+    L.rl_debug_set_fastg_one_wave(int(mode))
+
+
+def set_status_gap(device_us, host_us=0):
+    """Tests only: a wait of device_us on the render's stream before each asynchronous status copy, and a host sleep of host_us
+    between a multi-GPU frame and its status post (each capped at 20 ms; 0, 0: off, the default)."""
+    if not _inited:
+        init()
+    L = render_lib()
+    L.rl_debug_set_status_gap.argtypes = [C.c_uint, C.c_uint]
+    _check(L.rl_debug_set_status_gap(int(device_us), int(host_us)))
+
+
 def has_experimental():
     return bool(render_lib().rl_debug_has_experimental())
 
@@ -447,13 +466,15 @@ class World:
     def device(self):
         """rl_rtiow_scene_create — uploads once, cached."""
         if self._device is None:
-            if not _inited:
-                init()
-            L = render_lib()
-            h = L.rl_rtiow_scene_create(self.desc)
-            if not h:
-                raise RLError(RL_E_INVALID, L.rl_last_error().decode())
-            self._device = h
+            with _create_mu:
+                if self._device is None:
+                    if not _inited:
+                        init()
+                    L = render_lib()
+                    h = L.rl_rtiow_scene_create(self.desc)
+                    if not h:
+                        raise RLError(RL_E_INVALID, L.rl_last_error().decode())
+                    self._device = h
         return self._device
 
 
@@ -821,13 +842,15 @@ class RtcWorld:
 
     def device(self):
         if self._device is None:
-            if not _inited:
-                init()
-            L = render_lib()
-            h = L.rl_rtc_scene_create(self.desc)
-            if not h:
-                raise RLError(RL_E_INVALID, L.rl_last_error().decode())
-            self._device = h
+            with _create_mu:
+                if self._device is None:
+                    if not _inited:
+                        init()
+                    L = render_lib()
+                    h = L.rl_rtc_scene_create(self.desc)
+                    if not h:
+                        raise RLError(RL_E_INVALID, L.rl_last_error().decode())
+                    self._device = h
         return self._device
 
     def render(self, aa_samples=1, camera=None, row_first=0, row_step=1, stats=None, allow_degenerate=False):

@@ -15,9 +15,11 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <thread>
 #include <type_traits>
 #include <vector>
 
@@ -101,6 +103,27 @@ __global__ void deinterleave_rows(const double *gathered, double *out, uint32_t 
   out[i] = gathered[(uint64_t)(r % G) * slot_vals + (uint64_t)(r / G) * row_vals + x];
 }
 
+// asynchronous multi-GPU frames: every replica's status into its ring.  Called by render_multi while it still holds scene->mu, so that no
+// other frame of the scene lands on a context stream between a frame's kernels and its status copies.  replicas[0] == scene: its ring is
+// posted under that lock; the other replicas' under their own, taken inside scene->mu (rl_render_status takes one replica's at a time).
+int post_status_multi(const rl_scene *scene, uint32_t H) {
+  const int G = n_contexts();
+  if (unsigned us = status_gap_host_us()) std::this_thread::sleep_for(std::chrono::microseconds(us));  // test hook (rl_debug_set_status_gap)
+  for (int g = 0; g < G && (uint32_t)g < H; g++) {
+    rl_scene *r = scene->replicas.empty() ? const_cast<rl_scene *>(scene) : scene->replicas[(size_t)g];
+    int rc = use_context(g);
+    if (rc != RL_OK) return rc;
+    if (r == scene) rc = post_status(r, context(g).stream);
+    else {
+      std::lock_guard<std::mutex> lk(r->mu);
+      rc = post_status(r, context(g).stream);
+    }
+    if (rc != RL_OK) return rc;
+    if (scene->replicas.empty()) break;
+  }
+  return use_context(0);
+}
+
 // One frame over all device contexts.  render_shard(replica, g, G, d_rows, stream, want_stats) enqueues rank g's rows.
 template <class F>
 int render_multi(const rl_scene *scene, uint32_t W, uint32_t H, void *d_out0, rl_stats *st, F render_shard) {
@@ -117,7 +140,7 @@ int render_multi(const rl_scene *scene, uint32_t W, uint32_t H, void *d_out0, rl
     rc = render_shard(scene, 0, 1, d_out0, context(0).stream, st != nullptr);
     if (rc != RL_OK) return rc;
     if (st) return collect_stats(scene, context(0).stream, st);
-    return RL_OK;
+    return post_status_multi(scene, H);
   }
   const uint32_t max_rows = (H + (uint32_t)G - 1) / (uint32_t)G;
   const uint64_t row_vals = (uint64_t)W * 3, slot_vals = (uint64_t)max_rows * row_vals;
@@ -186,7 +209,7 @@ int render_multi(const rl_scene *scene, uint32_t W, uint32_t H, void *d_out0, rl
   if (!root->ev_gather_read) HIP_TRY(hipEventCreateWithFlags(&root->ev_gather_read, hipEventDisableTiming));
   HIP_TRY(hipEventRecord(root->ev_gather_read, context(0).stream));
   root->ev_gather_read_valid = true;
-  if (!st) return RL_OK;
+  if (!st) return post_status_multi(scene, H);
   std::memset(st, 0, sizeof *st);
   int worst = RL_OK;
   for (int g = 0; g < G && (uint32_t)g < H; g++) {
@@ -200,22 +223,6 @@ int render_multi(const rl_scene *scene, uint32_t W, uint32_t H, void *d_out0, rl
   if ((rc = use_context(0)) != RL_OK) return rc;
   HIP_TRY(hipStreamSynchronize(context(0).stream));  // the de-interleave
   return worst;
-}
-
-int post_status_multi(const rl_scene *scene, uint32_t H) {
-  const int G = n_contexts();
-  for (int g = 0; g < G && (uint32_t)g < H; g++) {
-    rl_scene *r = scene->replicas.empty() ? const_cast<rl_scene *>(scene) : scene->replicas[(size_t)g];
-    int rc = use_context(g);
-    if (rc != RL_OK) return rc;
-    {
-      std::lock_guard<std::mutex> lk(r->mu);
-      rc = post_status(r, context(g).stream);
-    }
-    if (rc != RL_OK) return rc;
-    if (scene->replicas.empty()) break;
-  }
-  return use_context(0);
 }
 
 int init_contexts(const std::vector<int> &devices, bool emulated) {
@@ -296,8 +303,7 @@ int rl_rtiow_render_multi_device(const rl_scene *scene, const rl_rtiow_camera *c
                         [&](const rl_scene *rep, uint32_t g, uint32_t G, void *d_rows, hipStream_t stream, bool want_stats) {
                           return rtiow_render_launch(rep, cam, first_sample, g, G, d_rows, stream, want_stats);
                         });
-  if (rc != RL_OK || st) return rc;
-  return post_status_multi(scene, cam->image_height);
+  return rc;
 }
 
 int rl_rtiow_render_multi(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, double *out_rgb_sum, rl_stats *st) {
@@ -327,8 +333,7 @@ int rl_rtc_render_multi_device(const rl_scene *scene, const rl_rtc_camera *cam, 
   int rc = render_multi(scene, cam->hsize, cam->vsize, d_out_rgb, st, [&](const rl_scene *rep, uint32_t g, uint32_t G, void *d_rows, hipStream_t stream, bool want_stats) {
     return rtc_render_launch(rep, cam, aa, g, G, d_rows, stream, want_stats);
   });
-  if (rc != RL_OK || st) return rc;
-  return post_status_multi(scene, cam->vsize);
+  return rc;
 }
 
 int rl_rtc_render_multi(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, double *out_rgb, rl_stats *st) {

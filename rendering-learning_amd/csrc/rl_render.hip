@@ -168,6 +168,14 @@ __global__ void encode_rtc_rgb8(const double *rgb, unsigned long long n_vals, un
   out[i] = (unsigned char)(q < 0 ? 0 : (q > 255 ? 255 : q));
 }
 
+// Test hook (rl_debug_set_status_gap): one lane holds its stream for `ticks` of the 100 MHz wall clock.  Each s_sleep(127) lasts
+// 127 x 64 shader clocks (>= 3 us at any clock up to 2.7 GHz), so `max_sleeps` = the wait in us ends the loop even if the clock stalls.
+__global__ void status_gap_wait(unsigned long long ticks, unsigned max_sleeps) {
+  const unsigned long long t0 = wall_clock64();
+  for (unsigned n = 0; n < max_sleeps && wall_clock64() - t0 < ticks; n++) __builtin_amdgcn_s_sleep(127);
+}
+unsigned g_status_gap_dev_us = 0, g_status_gap_host_us = 0;  // rl_debug_set_status_gap (0 / 0: off)
+
 int init_context(DevCtx &c, int device) {
   c.device = device;
   HIP_TRY(hipSetDevice(device));
@@ -558,6 +566,10 @@ namespace rl {
 int collect_stats(const rl_scene *scene, hipStream_t stream, rl_stats *st) {
   unsigned long long h[8];
   HIP_TRY(hipMemcpyAsync(h, scene->d_scratch + 64, sizeof h, hipMemcpyDeviceToHost, stream));
+  {
+    int rc = mark_render_end(scene, stream);
+    if (rc != RL_OK) return rc;
+  }
   HIP_TRY(hipStreamSynchronize(stream));
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, scene->ev0, scene->ev1));
@@ -576,6 +588,8 @@ static void fold_status(rl_scene *ms, int slot) {
   ms->status_pending[slot] = false;
 }
 // asynchronous renders: leave the stats words in pinned host memory behind an event (rl_render_status reads them).  Caller holds scene->mu.
+// The render ends HERE, not at its last kernel: ev_last follows the copy, so that the next render of the scene on another stream (which
+// waits only for ev_last) cannot zero or add to d_scratch before this render's counters have been read.
 int post_status(const rl_scene *scene, hipStream_t stream) {
   rl_scene *ms = const_cast<rl_scene *>(scene);
   const int slot = ms->status_next;
@@ -583,17 +597,22 @@ int post_status(const rl_scene *scene, hipStream_t stream) {
     HIP_TRY(hipEventSynchronize(ms->ev_status[slot]));
     fold_status(ms, slot);
   }
+  if (g_status_gap_dev_us) {  // test hook: widen the window between the render's last kernel and this copy
+    hipLaunchKernelGGL(status_gap_wait, dim3(1), dim3(1), 0, stream, (unsigned long long)g_status_gap_dev_us * 100ull, g_status_gap_dev_us);
+    HIP_TRY(hipGetLastError());
+  }
   HIP_TRY(hipMemcpyAsync(ms->h_status + (size_t)slot * 8, scene->d_scratch + 64, 64, hipMemcpyDeviceToHost, stream));
   HIP_TRY(hipEventRecord(ms->ev_status[slot], stream));
   ms->status_pending[slot] = true, ms->status_seq[slot] = ++ms->next_seq;
   ms->status_next = (slot + 1) % rl_scene::N_STATUS;
-  return RL_OK;
+  return mark_render_end(scene, stream);
 }
 int order_after_previous(const rl_scene *scene, hipStream_t stream) {
   if (scene->has_last && scene->last_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, scene->ev_last, 0));
   return RL_OK;
 }
-int mark_render_end(const rl_scene *scene, hipStream_t stream) {
+unsigned status_gap_host_us() { return g_status_gap_host_us; }
+int mark_render_end(const rl_scene *scene, hipStream_t stream) {  // collect_stats / post_status, behind the render's stats copy
   rl_scene *ms = const_cast<rl_scene *>(scene);
   HIP_TRY(hipEventRecord(ms->ev_last, stream));
   ms->last_stream = stream, ms->has_last = true;
@@ -1193,8 +1212,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     rc = launch_variant();
   }
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev1, stream));
-  if (rc == RL_OK) rc = mark_render_end(scene, stream);
-  return rc;
+  return rc;  // the caller ends the render with collect_stats / post_status, which record ev_last behind the stats copy
 }
 
 // The sample-parallel mode (include/rl_render.h rl_rtiow_render_independent*).  A work item is (sample group of indep_k samples, pixel),
@@ -1328,8 +1346,7 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
     HIP_TRY(hipGetLastError());
   }
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev1, stream));
-  if (rc == RL_OK) rc = mark_render_end(scene, stream);
-  return rc;
+  return rc;  // the caller ends the render with collect_stats / post_status, which record ev_last behind the stats copy
 }
 }  // namespace rl
 
@@ -1407,12 +1424,14 @@ int rl_render_status(const rl_scene *scene, rl_stats *st) {
 int rl_rtiow_render_progress(const rl_scene *scene, uint64_t *pixels_claimed, uint64_t *pixels_total, uint32_t *phase) {
   if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
   if (!scene || scene->kind != 1) return set_err(RL_E_INVALID, "bad argument");
+  if (!scene->replicas.empty()) return set_err(RL_E_UNSUPPORTED, "rl_rtiow_render_progress does not follow multi-GPU renders (scene created under rl_init_multi)");
   rl_scene *ms = const_cast<rl_scene *>(scene);
   unsigned long long total = 0, c0 = 0, c1 = 0;
   {
     std::lock_guard<std::mutex> lk(ms->mu);
     if (!ms->progress_on) {  // first call: renders enqueued from now on count in host-visible memory
-      if (ms->ctx < 0 || (size_t)ms->ctx >= g_ctx.size()) return set_err(RL_E_INVALID, "scene belongs to a device context that no longer exists");
+      if (ms->ctx < 0 || (size_t)ms->ctx >= g_ctx.size() || g_ctx[(size_t)ms->ctx].device != ms->device)
+        return set_err(RL_E_INVALID, "scene belongs to a device context that no longer exists (created under another rl_init / rl_init_multi)");
       int rc = rl::use_context(ms->ctx);
       if (rc != RL_OK) return rc;
       HIP_TRY(hipHostMalloc((void **)&ms->h_progress, 64, hipHostMallocMapped | hipHostMallocCoherent));
@@ -1585,6 +1604,14 @@ void rl_debug_set_rtc_blocks(int per_cu) { g_sw.rtc_blocks_per_cu = per_cu < 0 ?
 void rl_debug_set_indep_cap(unsigned long long bytes) { g_sw.indep_cap = bytes ? (size_t)bytes : (size_t)1 << 30; }  // sample-parallel pass buffer cap (0: default 1 GiB)
 void rl_debug_set_indep_k(unsigned k) { g_sw.indep_k = k ? k : 1u; }  // samples of one pixel per claim in the sample-parallel mode
 void rl_debug_set_fastg_one_wave(int mode) { g_sw.fastg_nt256 = mode; }  // -1: by frame size (default), 0 / 1: never / always the one-wave-per-SIMD form (tests)
+// Tests only: widen the windows in which concurrent renders of one scene could lose a panic-site count.  device_us: a one-lane wait
+// kernel on the render's stream just before its status copy; host_us: a host sleep between a multi-GPU frame and its status post.
+// Each is capped at 20 ms; 0 / 0 (the default) adds nothing to the render path.
+int rl_debug_set_status_gap(unsigned device_us, unsigned host_us) {
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  g_status_gap_dev_us = std::min(device_us, 20000u), g_status_gap_host_us = std::min(host_us, 20000u);
+  return RL_OK;
+}
 void rl_debug_fast_stats(int on) {  // the instrumented fast kernel <1024, 4, true> exists in the experimental library only
 #ifdef RL_EXPERIMENTAL
   g_fast_debug_stats = on != 0;
@@ -1943,7 +1970,7 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
   }
   HIP_TRY(hipGetLastError());
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev1, stream));
-  return mark_render_end(scene, stream);
+  return RL_OK;  // the caller ends the render with collect_stats / post_status, which record ev_last behind the stats copy
 }
 }  // namespace rl
 

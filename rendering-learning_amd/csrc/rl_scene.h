@@ -93,9 +93,11 @@ struct rl_scene {
   unsigned char *d_scratch = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // Renders of one scene may be issued from several host threads and on several streams at once (the reference's Camera::render takes
-  // &self, camera.rs:122).  The scene owns ONE set of work buffers, so: `mu` serialises the host side (enqueueing a render, handing its
-  // status over), and a render enqueued on another stream than its predecessor first waits, on the device, for the predecessor's last
-  // kernel (`ev_last`) — concurrent callers are safe, their frames are rendered one after the other (each one fills the GPU anyway).
+  // &self, camera.rs:122).  The scene owns ONE set of work buffers, so: `mu` serialises the host side (enqueueing a render and handing
+  // its status over, in one hold: a multi-GPU frame posts every replica's status before it lets go), and a render enqueued on another
+  // stream than its predecessor first waits, on the device, for the predecessor's END (`ev_last`: recorded behind its stats copy by
+  // post_status / collect_stats, so the next render's memset of d_scratch cannot overtake that copy) — concurrent callers are safe, their
+  // frames are rendered one after the other (each one fills the GPU anyway).
   mutable std::mutex mu;
   hipStream_t last_stream = nullptr;
   hipEvent_t ev_last = nullptr;
@@ -149,8 +151,8 @@ DevCtx &context(int i);
 int use_context(int i);  // hipSetDevice(context(i).device)
 void drop_multi_state();  // rl_multi.hip: RCCL communicators + the emulation flag, dropped whenever the context list is rebuilt
 
-// Launch-only halves of the render entry points (rl_render.hip): enqueue everything on `stream`, never synchronise.  With
-// want_stats the caller finishes with collect_stats (which synchronises the stream).
+// Launch-only halves of the render entry points (rl_render.hip): enqueue everything on `stream`, never synchronise.  The caller finishes
+// the render, holding scene->mu since the launch, with collect_stats (want_stats; synchronises the stream) or post_status.
 int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, void *d_out,
                         hipStream_t stream, bool want_stats);
 int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, uint32_t row_first, uint32_t row_step, void *d_out, hipStream_t stream,
@@ -158,7 +160,8 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
 int collect_stats(const rl_scene *scene, hipStream_t stream, rl_stats *st);  // RL_OK / RL_E_DEGENERATE / RL_E_DEVICE
 int post_status(const rl_scene *scene, hipStream_t stream);                  // asynchronous renders: next slot of the status ring
 int order_after_previous(const rl_scene *scene, hipStream_t stream);         // start of a render: device-side wait for the scene's previous render
-int mark_render_end(const rl_scene *scene, hipStream_t stream);              // end of a render's launch chain
+int mark_render_end(const rl_scene *scene, hipStream_t stream);              // end of a render: behind its stats copy (collect_stats / post_status)
 void add_stats(rl_stats *acc, const rl_stats &s);                             // sums counters, max of kernel_ms
+unsigned status_gap_host_us();                                                // rl_debug_set_status_gap's host sleep (tests; 0: none)
 
 }  // namespace rl

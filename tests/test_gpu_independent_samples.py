@@ -248,3 +248,75 @@ def test_independent_from_checkpoint_through_the_cpp_mirror(rl):
     data = np.ascontiguousarray(ckpt.data, dtype=np.float64).copy()
     assert L.rlh_rtiow_golden_independent(48, 7, 3, data.ctypes.data, data.size) == 0, L.rlh_last_error()
     assert np.array_equal(data.reshape(c.data.shape), c.data)
+
+
+def _flavour(rl, name):
+    """(world, camera params, one-wave switch) of each kernel flavour the sample-parallel mode reaches besides the sphere kernel."""
+    if name == "reference_order":  # 512 spheres: one more than the fast sphere tree's entry ids allow -> variant 4
+        api = rl.api
+        tex = np.zeros(1, dtype=api.TEXTURE)
+        tex[0]["kind"], tex[0]["color"] = api.TEX_SOLID, (0.5, 0.4, 0.3)
+        mats = np.zeros(3, dtype=api.MATERIAL)
+        mats[0]["kind"], mats[0]["texture"] = api.MAT_LAMBERTIAN, 0
+        mats[1]["kind"], mats[1]["ior"] = api.MAT_DIELECTRIC, 1.5
+        mats[2]["kind"], mats[2]["albedo"], mats[2]["fuzz"] = api.MAT_METAL, (0.9, 0.9, 0.9), 0.2
+        rng = np.random.default_rng(99)
+        sph = np.zeros(512, dtype=api.SPHERE)
+        sph["center0"], sph["radius"], sph["material"] = rng.uniform(-4, 4, (512, 3)), rng.uniform(0.05, 0.3, 512), rng.integers(0, 3, 512)
+        world = rl.World.from_spheres(sph, mats, tex, True)
+        p = rl.CameraParams(aspect_ratio=1.5, image_width=48, samples_per_pixel=1, max_depth=8, vfov=60.0, lookfrom=(0.0, 1.0, 9.0), lookat=(0, 0, 0))
+        return world, p, -1
+    if name == "perlin_spheres":
+        world = rl.World.perlin_spheres()
+    elif name == "final_scene_one_wave":
+        world = rl.World.example_scene("final_scene", rgb8=_synthetic_image())
+    else:
+        world = rl.World.example_scene(name)
+    p = world.params
+    p.image_width = 48
+    p.max_depth = min(p.max_depth, 20)
+    return world, p, 1 if name.endswith("_one_wave") else -1
+
+
+@pytest.mark.parametrize("name", ["cornell_box", "cornell_smoke", "perlin_spheres", "final_scene_one_wave", "reference_order"])
+def test_independent_splits_on_every_kernel_flavour(rl, name):
+    """4 on the other flavours: the fast general kernel (cornell_box: <768, 20>), its media (cornell_smoke), texture (perlin_spheres) and
+    one-wave (final_scene, forced) forms, which take their parameters through the two-slot ring, and the reference-order wave kernel
+    (variant 4): one call = a + (S - a) = 3+ passes = claims of 3 samples cut at a pass end = 3 row shards = the chained fold, also from
+    a first sample beyond 2^32."""
+    world, p, one_wave = _flavour(rl, name)
+    F, S, a = 3, 11, 4
+    cam = _cam(rl, p, S)
+    per_sample = cam.c.image_height * cam.c.image_width * 3 * 8
+    try:
+        rl.api.set_fastg_one_wave(one_wave)
+        ref, tot = _chained(rl, world, p, F, S)
+        one, st = _device(rl, cam, world, first_sample=F)
+        assert np.array_equal(one, ref), (name, np.abs(one - ref).max())
+        assert st["rays"] == tot["rays"] and st["flagged"] == tot["flagged"] == 0, (name, st, tot["rays"])
+        first, _ = _device(rl, _cam(rl, p, a), world, first_sample=F)
+        two, _ = _device(rl, _cam(rl, p, S - a), world, first_sample=F + a, accumulate=True, init=first)
+        assert np.array_equal(two, ref), name
+        rl.api.set_indep_cap(per_sample * 3)  # 3 + 3 + 3 + 2: four passes, the parameter ring wraps twice
+        passes, _ = _device(rl, cam, world, first_sample=F)
+        assert np.array_equal(passes, ref), name
+        rl.api.set_indep_cap(per_sample * 5)  # 5 + 5 + 1 with 3 samples per claim: groups of 3, 2 / 3, 2 / 1
+        rl.api.set_indep_k(3)
+        passes_k, _ = _device(rl, cam, world, first_sample=F)
+        assert np.array_equal(passes_k, ref), name
+        rl.api.set_indep_cap(0)
+        rl.api.set_indep_k(1)
+        shards = np.zeros_like(ref)
+        for g in range(3):
+            part, _ = _device(rl, cam, world, row_first=g, row_step=3, first_sample=F)
+            shards[g::3] = part
+        assert np.array_equal(shards, ref), name
+        big = (1 << 32) + 5
+        far_ref, _ = _chained(rl, world, p, big, 4)
+        far, _ = _device(rl, _cam(rl, p, 4), world, first_sample=big)
+        assert np.array_equal(far, far_ref), name
+        assert not np.array_equal(far, _chained(rl, world, p, 5, 4)[0]), name  # the sample index is not truncated to 32 bits
+    finally:
+        rl.api.set_fastg_one_wave(-1)
+        rl.api.set_indep_cap(0)
+        rl.api.set_indep_k(1)
