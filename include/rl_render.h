@@ -433,6 +433,58 @@ int rl_rtc_render_multi_device(const rl_scene *, const rl_rtc_camera *, uint32_t
 int rl_rtc_encode_rgb8_device(const void *d_rgb, uint64_t n_pixels, void *d_rgb8, void *hip_stream);
 int rl_rtc_render_rgb8(const rl_scene *, const rl_rtc_camera *, uint32_t aa_samples, uint8_t *out_rgb8, rl_stats *opt_stats);
 
+/* =====================================================================
+ *  Batched ray queries: the reference's per-ray primitives on the device
+ * =====================================================================
+ *   rl_rtiow_hit_rays*      <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval) -> Option<(&Material, HitRecord)>
+ *                              on the scene root (the slice fold hittable/mod.rs:88-111, Bvh::hit bvh.rs:79-95, ...)
+ *   rl_rtc_intersect_rays*  <- ray-tracer-challenge/src/scene/world.rs:46  World::intersect, scene/intersect.rs:159-168  hit
+ *   rl_rtc_color_at_rays*   <- ray-tracer-challenge/src/scene/world.rs:100 World::color_at(&Ray)
+ * Rays are plain records, used as given: `dir` is NOT normalised (the reference does not normalise either).  The plain forms take
+ * host buffers; the _device forms take device buffers and a hipStream_t and are asynchronous unless opt_stats is non-NULL.
+ * opt_stats counts as a render does: rays = the queried rays (color_at: + the reflection / refraction / shadow rays, as rl_rtc_render);
+ * a reached panic site sets flagged and returns RL_E_DEGENERATE with every output written; rl_render_status covers the asynchronous
+ * forms, each query counting once.  n = 0: RL_OK, no buffer is touched (opt_stats, when given, is zeroed).  NULL buffers with n > 0, a
+ * NaN interval bound, a scene of the other family: RL_E_INVALID.  Concurrency: as the renders (serialised per scene).  Under
+ * rl_init_multi the query runs on device 0's replica (a batch is not split across GPUs).
+ * Results, and all counters, are those of the reference's algorithm on the same ray.  rl_rtiow_hit_rays* without opt_stats and with
+ * tmin == 1e-10 (camera.rs:242-245) may be served by a fast tree walk that re-traces every order-sensitive ray: the records are bit for bit
+ * those of the reference-order kernel.  A zero `dir` reaches no panic site (Sphere::hit: a = 0, NaN roots, no hit; RTC: no intersection). */
+typedef struct rl_ray { /* ray.rs:5-9 Ray{origin, direction, time} / RTC ray.rs Ray{origin, direction} */
+  double origin[3], dir[3];
+  double time; /* RTIOW only (moving spheres, sphere.rs:36); ignored by the RTC queries */
+} rl_ray;      /* 56 bytes */
+typedef struct rl_rtiow_hit { /* hittable/mod.rs:24-30 HitRecord + the &Material of the returned tuple */
+  double t, p[3], normal[3], u, v;
+  uint32_t hit;        /* 0: None (then t = +inf and every other field is 0) */
+  uint32_t front_face; /* Face::Front = 1 */
+  uint32_t material;   /* index into the scene's materials */
+  uint32_t _pad;
+} rl_rtiow_hit; /* 88 bytes */
+typedef struct rl_rtc_isect { /* scene/intersect.rs:11-16 Intersection{t, object, normal} */
+  double t, normal[3];
+  uint32_t object; /* object identity: triangles first (index into triangles[]), then shapes (n_triangles + index into shapes[]) */
+  uint32_t _pad;
+} rl_rtc_isect; /* 40 bytes */
+
+/* out_hits[i] = world.hit(&rays[i], &Interval{min: tmin, max: tmax}); the interval is closed at both ends (interval.rs).
+ * Scenes with ConstantMedium objects: RL_E_UNSUPPORTED — a medium's hit draws its free path from the pixel's RNG stream
+ * (constant_medium.rs:55, see rl_medium), and a bare ray has none. */
+int rl_rtiow_hit_rays(const rl_scene *, const rl_ray *rays, uint64_t n, double tmin, double tmax, rl_rtiow_hit *out_hits, rl_stats *opt_stats);
+int rl_rtiow_hit_rays_device(const rl_scene *, const void *d_rays, uint64_t n, double tmin, double tmax, void *d_out_hits, void *hip_stream,
+                             rl_stats *opt_stats);
+/* out_counts[i] = the length of World::intersect(&rays[i])'s sorted list; out_isects[i*k .. i*k + min(count, k)) = its first entries in
+ * the reference's order (stable by t; the entries beyond are left untouched); k = 0 with out_isects = NULL asks for the counts only.
+ * out_hit_index (optional): the index hit() picks in that list (lowest t >= 0, later wins ties), reported also when it lies beyond k,
+ * or UINT32_MAX.  A ray with more than 48 intersections is flagged (as in the renders) and reports 48. */
+int rl_rtc_intersect_rays(const rl_scene *, const rl_ray *rays, uint64_t n, uint32_t k, rl_rtc_isect *out_isects, uint32_t *out_counts,
+                          uint32_t *out_hit_index, rl_stats *opt_stats);
+int rl_rtc_intersect_rays_device(const rl_scene *, const void *d_rays, uint64_t n, uint32_t k, void *d_out_isects, void *d_out_counts,
+                                 void *d_out_hit_index, void *hip_stream, rl_stats *opt_stats);
+/* out_rgb[3*i ..] = World::color_at(&rays[i]) with the scene's max_reflection_depth. */
+int rl_rtc_color_at_rays(const rl_scene *, const rl_ray *rays, uint64_t n, double *out_rgb, rl_stats *opt_stats);
+int rl_rtc_color_at_rays_device(const rl_scene *, const void *d_rays, uint64_t n, void *d_out_rgb, void *hip_stream, rl_stats *opt_stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,13 @@ RTC_SHAPE = np.dtype([("kind", "<u4"), ("material", "<u4"), ("has_minimum", "<u4
 RTC_CSG = np.dtype([("operation", "<u4"), ("reserved", "<u4"), ("left", HREF), ("right", HREF)])
 RTC_PATTERN = np.dtype([("kind", "<u4"), ("reserved", "<u4"), ("a", "<f8", 3), ("b", "<f8", 3), ("inverse", "<f8", 16)])
 RTC_LIGHT = np.dtype([("position", "<f8", 3), ("intensity", "<f8", 3)])
+# ray queries (rl_ray / rl_rtiow_hit / rl_rtc_isect)
+RAY = np.dtype([("origin", "<f8", 3), ("dir", "<f8", 3), ("time", "<f8")])
+RTIOW_HIT = np.dtype([("t", "<f8"), ("p", "<f8", 3), ("normal", "<f8", 3), ("u", "<f8"), ("v", "<f8"),
+                      ("hit", "<u4"), ("front_face", "<u4"), ("material", "<u4"), ("_pad", "<u4")])
+RTC_ISECT = np.dtype([("t", "<f8"), ("normal", "<f8", 3), ("object", "<u4"), ("_pad", "<u4")])
+assert RAY.itemsize == 56 and RTIOW_HIT.itemsize == 88 and RTC_ISECT.itemsize == 40
+NO_HIT = 0xFFFFFFFF  # out_hit_index of a ray hit() returns None for
 
 MAT_FLAT, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC = 0, 1, 2, 3, 4, 5
 TEX_SOLID, TEX_CHECKER, TEX_IMAGE, TEX_NOISE = 0, 1, 2, 3
@@ -170,7 +177,9 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtiow_render_independent_rows", "rl_rtiow_render_independent_device",
                   "rl_rtiow_render_multi", "rl_rtiow_render_multi_device", "rl_rtiow_encode_rgb8_device", "rl_rtiow_render_rgb8",
                   "rl_rtc_scene_create", "rl_rtc_render", "rl_rtc_render_rows", "rl_rtc_render_device",
-                  "rl_rtc_render_multi", "rl_rtc_render_multi_device", "rl_rtc_encode_rgb8_device", "rl_rtc_render_rgb8"]
+                  "rl_rtc_render_multi", "rl_rtc_render_multi_device", "rl_rtc_encode_rgb8_device", "rl_rtc_render_rgb8",
+                  "rl_rtiow_hit_rays", "rl_rtiow_hit_rays_device", "rl_rtc_intersect_rays", "rl_rtc_intersect_rays_device",
+                  "rl_rtc_color_at_rays", "rl_rtc_color_at_rays_device"]
 
 
 def render_lib():
@@ -204,6 +213,13 @@ def render_lib():
         L.rl_rtc_render.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         L.rl_rtc_render_rows.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
         L.rl_rtc_render_device.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtiow_hit_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtiow_hit_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtc_intersect_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtc_intersect_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(Stats)]
+        L.rl_rtc_color_at_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtc_color_at_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -317,6 +333,39 @@ def _check(rc, allow_degenerate=False):
     if rc == RL_OK or (allow_degenerate and rc == RL_E_DEGENERATE):
         return rc
     raise RLError(rc, render_lib().rl_last_error().decode())
+
+
+def pack_rays(origins, dirs, times=None):
+    """[n, 3] origins and directions (+ optional [n] times) -> the rl_ray records the queries take.  Shape errors are the caller's: ValueError."""
+    o = np.asarray(origins, dtype=np.float64)
+    d = np.asarray(dirs, dtype=np.float64)
+    if o.ndim != 2 or o.shape[1] != 3 or d.shape != o.shape:
+        raise ValueError(f"origins and dirs must both be [n, 3] (got {o.shape} and {d.shape})")
+    rays = np.zeros(o.shape[0], dtype=RAY)
+    rays["origin"], rays["dir"] = o, d
+    if times is not None:
+        t = np.asarray(times, dtype=np.float64)
+        if t.shape != (o.shape[0],):
+            raise ValueError(f"times must be [n] (got {t.shape})")
+        rays["time"] = t
+    return rays
+
+
+def last_query():
+    """rl_debug_last_query: which kernel served the most recent hit_rays* call ("fast" / "reference") and, for a synchronous call, how
+    many of its rays the fast walk re-traced in the reference's order."""
+    out = (C.c_uint64 * 2)()
+    L = render_lib()
+    L.rl_debug_last_query.argtypes = [C.c_void_p]
+    _check(L.rl_debug_last_query(out))
+    return {"kernel": {1: "reference", 2: "fast"}.get(int(out[0]), "none"), "retraced": int(out[1])}
+
+
+def _finish_query(rc, st, stats, allow_degenerate):
+    _check(rc, allow_degenerate)
+    if stats is not None:
+        stats.update(st.as_dict())
+        stats["rc"] = rc
 
 
 def rows_for(height, row_first, row_step):
@@ -476,6 +525,24 @@ class World:
                         raise RLError(RL_E_INVALID, L.rl_last_error().decode())
                     self._device = h
         return self._device
+
+    def hit_rays(self, origins, dirs, times=None, tmin=1e-10, tmax=float("inf"), stats=None, allow_degenerate=False):
+        """Hittable::hit(&Ray, &Interval{tmin, tmax}) on the scene root for every ray (hittable/mod.rs:42), on the GPU -> RTIOW_HIT[n]."""
+        rays = pack_rays(origins, dirs, times)
+        out = np.zeros(rays.shape[0], dtype=RTIOW_HIT)
+        st = Stats()
+        # without `stats` the call is counter-free: the fast traversal serves it where it applies (same bits, see last_query())
+        rc = render_lib().rl_rtiow_hit_rays(self.device(), rays.ctypes.data, rays.shape[0], tmin, tmax, out.ctypes.data,
+                                            C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+        return out
+
+    def hit_rays_device(self, d_rays, d_out, n, tmin=1e-10, tmax=float("inf"), stream=0, stats=None, allow_degenerate=False):
+        """Device buffers (n rl_ray in, n rl_rtiow_hit out; e.g. torch tensors' data_ptr).  Asynchronous unless stats is a dict."""
+        st = Stats()
+        rc = render_lib().rl_rtiow_hit_rays_device(self.device(), C.c_void_p(d_rays), n, tmin, tmax, C.c_void_p(d_out), C.c_void_p(stream),
+                                                   C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
 
 
 class SceneBuilder:
@@ -893,6 +960,42 @@ class RtcWorld:
         _check(rc)
         if stats is not None:
             stats.update(st.as_dict())
+
+    def intersect_rays(self, origins, dirs, k=8, stats=None, allow_degenerate=False):
+        """World::intersect (world.rs:46) + hit (intersect.rs:159-168) for every ray -> (counts[n], isects RTC_ISECT[n, k], hit_index[n]);
+        isects[i, :min(counts[i], k)] are the first entries of the sorted list, hit_index[i] == NO_HIT when hit() returns None."""
+        rays = pack_rays(origins, dirs)
+        n = rays.shape[0]
+        counts = np.zeros(n, dtype=np.uint32)
+        isects = np.zeros((n, k), dtype=RTC_ISECT)
+        hit_index = np.full(n, NO_HIT, dtype=np.uint32)
+        st = Stats()
+        rc = render_lib().rl_rtc_intersect_rays(self.device(), rays.ctypes.data, n, k, isects.ctypes.data if k else None, counts.ctypes.data,
+                                                hit_index.ctypes.data, C.byref(st))
+        _finish_query(rc, st, stats, allow_degenerate)
+        return counts, isects, hit_index
+
+    def intersect_rays_device(self, d_rays, n, k, d_isects, d_counts, d_hit_index=0, stream=0, stats=None, allow_degenerate=False):
+        st = Stats()
+        rc = render_lib().rl_rtc_intersect_rays_device(self.device(), C.c_void_p(d_rays), n, k, C.c_void_p(d_isects) if d_isects else None,
+                                                       C.c_void_p(d_counts), C.c_void_p(d_hit_index) if d_hit_index else None, C.c_void_p(stream),
+                                                       C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+
+    def color_at_rays(self, origins, dirs, stats=None, allow_degenerate=False):
+        """World::color_at(&ray) (world.rs:100) for every ray, with the world's max_reflection_depth -> [n, 3]."""
+        rays = pack_rays(origins, dirs)
+        out = np.zeros((rays.shape[0], 3), dtype=np.float64)
+        st = Stats()
+        rc = render_lib().rl_rtc_color_at_rays(self.device(), rays.ctypes.data, rays.shape[0], out.ctypes.data, C.byref(st))
+        _finish_query(rc, st, stats, allow_degenerate)
+        return out
+
+    def color_at_rays_device(self, d_rays, d_rgb, n, stream=0, stats=None, allow_degenerate=False):
+        st = Stats()
+        rc = render_lib().rl_rtc_color_at_rays_device(self.device(), C.c_void_p(d_rays), n, C.c_void_p(d_rgb), C.c_void_p(stream),
+                                                      C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
 
 
 def rtc_camera(hsize, vsize, fov, frm, to, up) -> RtcCamera:  # Camera::new + view_transform

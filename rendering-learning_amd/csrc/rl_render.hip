@@ -24,6 +24,7 @@
 #include "rl_rtiow_wave_general.h"
 #include "rl_rtiow_fastgen.h"
 #include "rl_rtiow_coop.h"
+#include "rl_ray_query.h"
 #ifdef RL_EXPERIMENTAL  // the measured-and-lost restructurings: only in librl_render_exp.so, never in the product library
 #include "experimental/rl_rtiow_pool.h"
 #include "experimental/rl_rtiow_wave2.h"
@@ -485,6 +486,8 @@ static int build_host_rtiow(const rl_rtiow_scene_desc *desc, std::shared_ptr<con
           if (e >= n_inner && e - n_inner < ns) std::memcpy(&H->fast_leaf_boxes[(size_t)(e - n_inner) * 8], nd.box[k], 6 * sizeof(float));
         }
     }
+    // ray queries walk the four-wide world-space tree on every kind of scene (rl_ray_query.h rtiow_hit_rays_fast_kernel)
+    if (rt.ops.size() < (1u << 31) && !build_fast_general(*desc, rt, H->qfg)) H->qfg = FastGeneral{};
   } else if (rt.ops.size() < (1u << 31)) {
     // general scenes (planars, instances, image / noise textures): world-space tree over the primitive occurrences
     if (!build_fast_general(*desc, rt, H->fg)) H->fg = FastGeneral{};
@@ -498,6 +501,7 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
   rl_scene *s = new rl_scene();
   s->kind = 1, s->ctx = ctx, s->device = g_ctx[(size_t)ctx].device, s->hrt = H;
   const RtiowProgram &rt = H->rt;
+  const FastGeneral &QF = H->query_tree();  // general scenes: the renders' tree; sphere-only scenes: the queries' own
   int rc = RL_OK;
   if ((rc = upload(rt.ops, &s->d_ops)) || (rc = upload(rt.spheres, &s->d_spheres)) || (rc = upload(rt.sphere_material, &s->d_sphere_material)) ||
       (rc = upload(rt.planars, &s->d_planars)) || (rc = upload(rt.translates, &s->d_translates)) || (rc = upload(rt.transforms, &s->d_transforms)) ||
@@ -507,8 +511,8 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
       (!H->lops.empty() && ((rc = upload(H->lops, &s->d_lops)) || (rc = upload(H->sphere_flat, &s->d_sphere_flat)))) ||
       (!H->cops.empty() && ((rc = upload(H->cops, &s->d_cops)) || (rc = upload(H->movbits, &s->d_movbits)))) ||
       (H->fast_root != FAST_NONE && ((rc = upload(H->fast_nodes, &s->d_fast_nodes)) || (rc = upload(H->fast_leaf_boxes, &s->d_fast_leaf_boxes)))) ||
-      (H->fg.ok && ((rc = upload(H->fg.qnodes, &s->d_fg_nodes)) || (rc = upload(H->fg.onodes, &s->d_fg_onodes)) || (rc = upload(H->fg.stage_roots, &s->d_fg_seg_roots)) ||
-                    (rc = upload(H->fg.media, &s->d_fg_media)) || (rc = upload(H->fg.items, &s->d_fg_items)) || (rc = upload(H->fg.item_spheres, &s->d_fg_spheres)) || (rc = upload(H->fg.item_material, &s->d_fg_material))))) {
+      (QF.ok && ((rc = upload(QF.qnodes, &s->d_fg_nodes)) || (rc = upload(QF.onodes, &s->d_fg_onodes)) || (rc = upload(QF.stage_roots, &s->d_fg_seg_roots)) ||
+                 (rc = upload(QF.media, &s->d_fg_media)) || (rc = upload(QF.items, &s->d_fg_items)) || (rc = upload(QF.item_spheres, &s->d_fg_spheres)) || (rc = upload(QF.item_material, &s->d_fg_material))))) {
     destroy_one(s);
     return nullptr;
   }
@@ -2062,6 +2066,268 @@ int rl_rtc_render_rgb8(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t
 
 int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, double *out, rl_stats *st) {
   return rl_rtc_render_rows(scene, cam, aa, 0, 1, out, st);
+}
+
+}  // extern "C"
+
+// =====================================================================
+//  Batched ray queries (rl_ray_query.h)
+// =====================================================================
+namespace {
+constexpr int QNT = 256;
+// the grid of a query kernel: what is resident at once (occupancy API, cached per kernel and device), at most one lane per ray
+uint32_t query_grid(const rl_scene *scene, const void *kern, uint64_t n) {
+  static std::mutex mu;
+  static std::map<std::pair<const void *, int>, int> cache;
+  int per_cu;
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    auto key = std::make_pair(kern, scene->device);
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+      int nb = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, QNT, 0) != hipSuccess || nb < 1) nb = 2;
+      it = cache.emplace(key, nb).first;
+    }
+    per_cu = it->second;
+  }
+  uint64_t want = (n + QNT - 1) / QNT, cap = (uint64_t)g_cus * (uint64_t)per_cu;
+  return (uint32_t)(want < cap ? want : cap);
+}
+int query_begin(const rl_scene *scene, hipStream_t stream, bool want_stats) {
+  int rco = rl::order_after_previous(scene, stream);
+  if (rco != RL_OK) return rco;
+  HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 512, stream));
+  if (want_stats) HIP_TRY(hipEventRecord(scene->ev0, stream));
+  return RL_OK;
+}
+int query_end(const rl_scene *scene, hipStream_t stream, rl_stats *st) {
+  HIP_TRY(hipGetLastError());
+  if (st) HIP_TRY(hipEventRecord(scene->ev1, stream));
+  return st ? rl::collect_stats(scene, stream, st) : post_status(scene, stream);
+}
+RtcFullParams rtc_query_params(const rl_scene *scene) {
+  const RtcProgram &rc_ = scene->rc();
+  RtcFullParams F{};
+  RtcParams &P = F.R;
+  P.ops = scene->d_ops, P.tris = scene->d_tris, P.xforms = scene->d_xforms, P.materials = scene->d_rmaterials, P.lights = scene->d_lights;
+  P.n_ops = (uint32_t)rc_.ops.size(), P.n_tris = (uint32_t)rc_.tris.size();
+  const uint32_t n_guards = (uint32_t)scene->hrc->guards.size();  // reject-only box trees over the triangle ranges, as the renders use them
+  P.guards = n_guards ? scene->d_guards : nullptr, P.n_guards = n_guards;
+  P.n_xforms = (uint32_t)rc_.xforms.size(), P.n_lights = (uint32_t)rc_.lights.size();
+  P.aa = 1, P.row_step = 1;
+  std::memcpy(P.void_color, rc_.void_color, 24);
+  P.stats = (unsigned long long *)(scene->d_scratch + 64);
+  F.shapes = scene->d_shapes, F.csgs = scene->d_csgs, F.patterns = scene->d_patterns;
+  F.n_tris = P.n_tris, F.max_reflection_depth = rc_.max_reflection_depth;
+  return F;
+}
+// host-buffer forms: stage the rays, run the device form on the library's stream of the scene's context, copy the results back
+struct QueryStage {
+  void *d[4] = {nullptr, nullptr, nullptr, nullptr};
+  ~QueryStage() {
+    for (void *p : d)
+      if (p) hipFree(p);
+  }
+  int alloc(int i, size_t bytes) {
+    HIP_TRY(hipMalloc(&d[i], bytes ? bytes : 1));
+    return RL_OK;
+  }
+};
+}  // namespace
+
+extern "C" {
+
+// counting: the caller wants the reference's counters (reference-order kernel).  Otherwise the fast kernel serves the call where the
+// scene has a fast tree and tmin is the interval its filters are derived for (camera.rs:242-245).  sync_st: filled synchronously (the
+// host forms; rays and flagged only when !counting); null: asynchronous, status ring.
+static int g_last_query_kernel = 0;                  // rl_debug_last_query: 1 reference order, 2 fast
+static unsigned long long g_last_query_retraced = 0;  // ... and the rays the fast kernel re-traced (synchronous calls)
+static int rtiow_hit_rays_impl(const rl_scene *scene, const void *d_rays, uint64_t n, double tmin, double tmax, void *d_out, hipStream_t stream,
+                               bool counting, rl_stats *sync_st) {
+  const RtiowProgram &rt = scene->rt();
+  const FastGeneral &QF = scene->hrt->query_tree();
+  RtiowParams P = RtiowParams{};
+  P.ops = scene->d_ops, P.spheres = scene->d_spheres, P.sphere_material = scene->d_sphere_material;
+  P.planars = scene->d_planars, P.translates = scene->d_translates, P.transforms = scene->d_transforms, P.media = scene->d_media;
+  P.n_ops = (uint32_t)rt.ops.size(), P.n_spheres = (uint32_t)rt.spheres.size();
+  P.stats = (unsigned long long *)(scene->d_scratch + 64);
+  RayQuery Q{};
+  Q.rays = (const rl_ray *)d_rays, Q.n = n, Q.tmin = tmin, Q.tmax = tmax, Q.hits = (rl_rtiow_hit *)d_out;
+  const bool fast = !counting && tmin == 1e-10 && QF.ok && QF.media.empty() && g_sw.fast_traversal;
+  std::lock_guard<std::mutex> lk(scene->mu);  // queries and renders of one scene: see rl_scene::mu
+  int rc = query_begin(scene, stream, sync_st != nullptr);
+  if (rc != RL_OK) return rc;
+  if (fast) {
+    constexpr int SD = 40;
+    P.fg_nodes = scene->d_fg_nodes, P.fg_items = scene->d_fg_items, P.fg_spheres = scene->d_fg_spheres, P.fg_material = scene->d_fg_material;
+    P.fg_root = QF.qroot, P.fg_rsafe2 = QF.r_safe * QF.r_safe * 0.9999f;
+    P.fg_seg_roots = scene->d_fg_seg_roots, P.fg_n_seg = (uint32_t)QF.stage_roots.size();
+    P.fg_center[0] = QF.center[0], P.fg_center[1] = QF.center[1], P.fg_center[2] = QF.center[2];
+    P.fg_radius = QF.radius, P.fg_pad_k = QF.pad_k;
+    // LDS: the per-lane stacks, and the tree's top (breadth first) in what is left — no RNG rings here, so more of it than a render has
+    const size_t base = (size_t)QNT * SD * sizeof(uint32_t);
+    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
+    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(QF.top_nodes, room) : 0u;
+    const size_t lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
+    const void *kern = (const void *)rtiow_hit_rays_fast_kernel<QNT, SD>;
+    if (ensure_lds_attr(kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    uint64_t want = (n + QNT - 1) / QNT, cap = (uint64_t)g_cus * (uint64_t)std::max<size_t>(1, std::min<size_t>(g_lds_max / lds, 2048 / QNT));
+    hipLaunchKernelGGL((rtiow_hit_rays_fast_kernel<QNT, SD>), dim3((uint32_t)std::min(want, cap)), dim3(QNT), lds, stream, P, Q);
+  } else if (counting)
+    hipLaunchKernelGGL((rtiow_hit_rays_kernel<QNT, true>), dim3(query_grid(scene, (const void *)rtiow_hit_rays_kernel<QNT, true>, n)), dim3(QNT), 0, stream, P, Q);
+  else
+    hipLaunchKernelGGL((rtiow_hit_rays_kernel<QNT, false>), dim3(query_grid(scene, (const void *)rtiow_hit_rays_kernel<QNT, false>, n)), dim3(QNT), 0, stream, P, Q);
+  g_last_query_kernel = fast ? 2 : 1;
+  rc = query_end(scene, stream, sync_st);
+  if (sync_st && (rc == RL_OK || rc == RL_E_DEGENERATE)) {  // (the stream is idle and the scene is still ours)
+    unsigned long long slow = 0;
+    if (hipMemcpy(&slow, scene->d_scratch + 64 + 56, 8, hipMemcpyDeviceToHost) == hipSuccess) g_last_query_retraced = slow;
+  }
+  return rc;
+}
+
+static int rtiow_hit_rays_check(const rl_scene *scene, const void *rays, uint64_t n, double tmin, double tmax, const void *out, rl_stats *st, bool &done) {
+  done = true;
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 1) return set_err(RL_E_INVALID, "not an RTIOW scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!rays || !out) return set_err(RL_E_INVALID, "null ray / output buffer");
+  if (std::isnan(tmin) || std::isnan(tmax)) return set_err(RL_E_INVALID, "NaN interval bound");
+  if (n > (uint64_t)1 << 40) return set_err(RL_E_INVALID, "batch too large");
+  if (scene->rt().has_media)
+    return set_err(RL_E_UNSUPPORTED, "ConstantMedium::hit draws from the pixel's RNG stream (constant_medium.rs:55); a bare ray has none");
+  done = false;
+  return RL_OK;
+}
+
+int rl_rtiow_hit_rays_device(const rl_scene *scene, const void *d_rays, uint64_t n, double tmin, double tmax, void *d_out, void *hip_stream,
+                             rl_stats *st) {
+  bool done;
+  int rc = rtiow_hit_rays_check(scene, d_rays, n, tmin, tmax, d_out, st, done);
+  if (done) return rc;
+  return rtiow_hit_rays_impl(scene, d_rays, n, tmin, tmax, d_out, (hipStream_t)hip_stream, st != nullptr, st);
+}
+
+// which kernel served the most recent rl_rtiow_hit_rays* call of this process (1: reference order, 2: fast walk), and how many rays of
+// the most recent SYNCHRONOUS one the fast walk re-traced in the reference's order (asynchronous calls: rl_render_status + rl_debug_slow_traces)
+int rl_debug_last_query(unsigned long long *out2) {
+  if (!out2) return set_err(RL_E_INVALID, "bad argument");
+  out2[0] = (unsigned long long)g_last_query_kernel, out2[1] = g_last_query_retraced;
+  return RL_OK;
+}
+
+int rl_rtc_intersect_rays_device(const rl_scene *scene, const void *d_rays, uint64_t n, uint32_t k, void *d_isects, void *d_counts, void *d_hit_index,
+                                 void *hip_stream, rl_stats *st) {
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 2) return set_err(RL_E_INVALID, "not an RTC scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!d_rays || !d_counts || (k != 0) != (d_isects != nullptr)) return set_err(RL_E_INVALID, "null buffer (out_isects goes with k > 0)");
+  if (n * (uint64_t)(k ? k : 1) / (uint64_t)(k ? k : 1) != n) return set_err(RL_E_INVALID, "n * k overflows");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RtcFullParams F = rtc_query_params(scene);
+  RayQuery Q{};
+  Q.rays = (const rl_ray *)d_rays, Q.n = n, Q.k = k, Q.isects = (rl_rtc_isect *)d_isects, Q.counts = (uint32_t *)d_counts, Q.hit_index = (uint32_t *)d_hit_index;
+  std::lock_guard<std::mutex> lk(scene->mu);
+  int rc = query_begin(scene, stream, st != nullptr);
+  if (rc != RL_OK) return rc;
+  hipLaunchKernelGGL((rtc_intersect_rays_kernel<QNT, 512>), dim3(query_grid(scene, (const void *)rtc_intersect_rays_kernel<QNT, 512>, n)), dim3(QNT), 0, stream, F, Q);
+  return query_end(scene, stream, st);
+}
+
+int rl_rtc_color_at_rays_device(const rl_scene *scene, const void *d_rays, uint64_t n, void *d_rgb, void *hip_stream, rl_stats *st) {
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 2) return set_err(RL_E_INVALID, "not an RTC scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!d_rays || !d_rgb) return set_err(RL_E_INVALID, "null ray / output buffer");
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RtcFullParams F = rtc_query_params(scene);
+  RayQuery Q{};
+  Q.rays = (const rl_ray *)d_rays, Q.n = n, Q.rgb = (double *)d_rgb;
+  std::lock_guard<std::mutex> lk(scene->mu);
+  int rc = query_begin(scene, stream, st != nullptr);
+  if (rc != RL_OK) return rc;
+  // the register budget rtc_full_kernel runs at (three waves per SIMD): the same per-ray body
+  hipLaunchKernelGGL((rtc_color_at_rays_kernel<QNT, 768>), dim3(query_grid(scene, (const void *)rtc_color_at_rays_kernel<QNT, 768>, n)), dim3(QNT), 0, stream, F, Q);
+  return query_end(scene, stream, st);
+}
+
+int rl_rtiow_hit_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, double tmin, double tmax, rl_rtiow_hit *out, rl_stats *st) {
+  bool done;
+  int rc0 = rtiow_hit_rays_check(scene, rays, n, tmin, tmax, out, st, done);
+  if (done) return rc0;
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * sizeof(rl_ray))) || (rc0 = q.alloc(1, n * sizeof(rl_rtiow_hit)))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], rays, n * sizeof(rl_ray), hipMemcpyHostToDevice));
+  rl_stats local;  // without opt_stats the call is counter-free (the fast kernel where it applies); rays and flagged are still collected
+  int rc = rtiow_hit_rays_impl(scene, q.d[0], n, tmin, tmax, q.d[1], g_ctx[(size_t)scene->ctx].stream, st != nullptr, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    hipError_t e = hipMemcpy(out, q.d[1], n * sizeof(rl_rtiow_hit), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
+    if (st) *st = local;
+  }
+  return rc;
+}
+
+int rl_rtc_intersect_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, uint32_t k, rl_rtc_isect *out_isects, uint32_t *out_counts,
+                          uint32_t *out_hit_index, rl_stats *st) {
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 2) return set_err(RL_E_INVALID, "not an RTC scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!rays || !out_counts || (k != 0) != (out_isects != nullptr)) return set_err(RL_E_INVALID, "null buffer (out_isects goes with k > 0)");
+  int rc0 = rl::use_context(scene->ctx);
+  if (rc0 != RL_OK) return rc0;
+  QueryStage q;
+  if (n > (uint64_t)1 << 40 || (k && n > ((uint64_t)1 << 44) / k)) return set_err(RL_E_INVALID, "n * k too large");
+  const size_t ib = (size_t)n * k * sizeof(rl_rtc_isect);
+  if ((rc0 = q.alloc(0, n * sizeof(rl_ray))) || (rc0 = q.alloc(1, ib)) || (rc0 = q.alloc(2, n * 4)) || (rc0 = q.alloc(3, n * 4))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], rays, n * sizeof(rl_ray), hipMemcpyHostToDevice));
+  if (k) HIP_TRY(hipMemcpy(q.d[1], out_isects, ib, hipMemcpyHostToDevice));  // entries beyond a ray's count stay the caller's
+  rl_stats local;
+  int rc = rl_rtc_intersect_rays_device(scene, q.d[0], n, k, k ? q.d[1] : nullptr, q.d[2], out_hit_index ? q.d[3] : nullptr,
+                                        g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    if (k) HIP_TRY(hipMemcpy(out_isects, q.d[1], ib, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_counts, q.d[2], n * 4, hipMemcpyDeviceToHost));
+    if (out_hit_index) HIP_TRY(hipMemcpy(out_hit_index, q.d[3], n * 4, hipMemcpyDeviceToHost));
+    if (st) *st = local;
+  }
+  return rc;
+}
+
+int rl_rtc_color_at_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, double *out_rgb, rl_stats *st) {
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 2) return set_err(RL_E_INVALID, "not an RTC scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!rays || !out_rgb) return set_err(RL_E_INVALID, "null ray / output buffer");
+  int rc0 = rl::use_context(scene->ctx);
+  if (rc0 != RL_OK) return rc0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * sizeof(rl_ray))) || (rc0 = q.alloc(1, n * 24))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], rays, n * sizeof(rl_ray), hipMemcpyHostToDevice));
+  rl_stats local;
+  int rc = rl_rtc_color_at_rays_device(scene, q.d[0], n, q.d[1], g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    HIP_TRY(hipMemcpy(out_rgb, q.d[1], n * 24, hipMemcpyDeviceToHost));
+    if (st) *st = local;
+  }
+  return rc;
 }
 
 }  // extern "C"

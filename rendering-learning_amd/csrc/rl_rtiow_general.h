@@ -143,7 +143,9 @@ struct GenCounters {
 // (wo, wd) = the world ray (POP ops restore the parent-scope ray by replaying the PUSH chain from it).
 // MEDIA: ConstantMedium ops are evaluated (constant_medium.rs:27-80, deterministic variant of include/rl_render.h rl_medium:
 // `draw()` supplies gen::<f64>() from the pixel's ChaCha8 stream); their boundaries run through this function with MEDIA = false.
-template <bool STATS, bool MEDIA, class Draw>
+// ALL_UV: every sphere's record carries get_sphere_uv's argument (ray queries return u, v of any hit, rl_ray_query.h), not only those
+// of spheres whose texture samples an Image.
+template <bool STATS, bool MEDIA, bool ALL_UV = false, class Draw>
 __device__ __forceinline__ void general_trace(const RtiowParams &P, const DevOp *ops, uint32_t pc, uint32_t pc_end, D3 o, D3 d, D3 wo, D3 wd, double time,
                                               double tmin, Rec &rec, GenCounters &gc, Draw &draw) {
   const double INF = __longlong_as_double(0x7FF0000000000000ll);
@@ -173,6 +175,7 @@ __device__ __forceinline__ void general_trace(const RtiowParams &P, const DevOp 
       }
       uint32_t a = op.a, b = op.b;
       if (code == OP_BOX_SPH) {
+        if (ALL_UV) a |= SPH_UV, b |= b != NONE ? SPH_UV : 0u;
         if (STATS) gc.spheres++;
         uint32_t ai = a & SPH_INDEX;
         if (sphere_hit_rec(P.spheres[ai], a, P.sphere_material[ai], pc, o, d, time, rec, tmin)) gc.flagged++;
@@ -194,7 +197,7 @@ __device__ __forceinline__ void general_trace(const RtiowParams &P, const DevOp 
     }
     if (code == OP_SPHERE) {
       if (STATS) gc.spheres++;
-      uint32_t a = op.a, ai = a & SPH_INDEX;
+      uint32_t a = ALL_UV ? (op.a | SPH_UV) : op.a, ai = a & SPH_INDEX;
       if (sphere_hit_rec(P.spheres[ai], a, P.sphere_material[ai], pc, o, d, time, rec, tmin)) gc.flagged++;
       pc++;
       continue;

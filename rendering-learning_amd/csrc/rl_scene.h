@@ -31,6 +31,8 @@ struct HostRtiow {
   uint32_t fast_root = FAST_NONE;
   std::vector<float> fast_leaf_boxes;  // [n_spheres][8]: each sphere's padded leaf box of the fast tree (rl_rtiow_coop.h)
   FastGeneral fg;  // fast traversal structure of a general scene (fg.ok == false: the scene does not qualify)
+  FastGeneral qfg;  // sphere-only scenes: the same structure for ray queries (rl_ray_query.h; the renders walk fast_nodes from LDS instead)
+  const FastGeneral &query_tree() const { return fg.ok ? fg : qfg; }
   // the guard boxes' padding is rigorous for ray origins within guard_reach of guard_center (rl_render.hip link_ops)
   double guard_center[3] = {0, 0, 0}, guard_reach = 0;
 };

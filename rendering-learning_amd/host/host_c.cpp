@@ -470,6 +470,30 @@ int rlh_rtiow_golden_independent(uint32_t width, uint32_t spp, uint64_t ckpt_sam
     return -1;
   }
 }
+// Ray queries through the C++ mirror.  which = 0: rtiow::hit on golden_test_scene with Interval{tmin, tmax}, out = n rl_rtiow_hit;
+// which = 1: rtc::World::color_at on the mirror scene, out = n * 3 doubles; which = 2: rtc::World::intersect on the mirror scene,
+// out = n uint32 counts.  0 or -1 (rlh_last_error).
+int rlh_ray_query_probe(int which, const rl_ray *rays, uint64_t n, double tmin, double tmax, void *out) {
+  try {
+    if (which == 0) {
+      scenes::RtiowScene s = scenes::golden_test_scene();
+      std::vector<rl_rtiow_hit> h = rtiow::hit(*s.world, rays, (size_t)n, rtiow::Interval{tmin, tmax});
+      std::memcpy(out, h.data(), h.size() * sizeof(rl_rtiow_hit));
+    } else if (which == 1) {
+      scenes::RtcScene s = scenes::rtc_test_mirror_scene();
+      std::vector<double> c = s.world.color_at(rays, (size_t)n);
+      std::memcpy(out, c.data(), c.size() * sizeof(double));
+    } else {
+      scenes::RtcScene s = scenes::rtc_test_mirror_scene();
+      std::vector<uint32_t> c = s.world.intersect(rays, (size_t)n);
+      std::memcpy(out, c.data(), c.size() * sizeof(uint32_t));
+    }
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // tests/ray_tracer.rs:242-275 (which = 0, needs the OBJ text), :56-240 mirror (1), :277-368 csg (2): Camera::render -> Canvas::ppm
 char *rlh_rtc_run_golden_test(int which, const char *obj_text, uint64_t obj_len, uint64_t *len) {
   try {

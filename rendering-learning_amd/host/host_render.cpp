@@ -43,6 +43,18 @@ Canvas Camera::render_independent(const Hittable &world) const { return render_i
 Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
   return render_independent_impl(*this, world, &checkpoint);
 }
+std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t n, Interval ray_t) {  // hittable/mod.rs:42
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  std::vector<rl_rtiow_hit> out(n);
+  int rc = rl_rtiow_hit_rays(sc, rays, n, ray_t.min, ray_t.max, out.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_hit_rays: ") + rl_last_error());
+  return out;
+}
 Canvas Camera::render(const Hittable &world) const { return render_internal(0, world); }  // camera.rs:122
 Canvas Camera::render_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {  // camera.rs:136-143
   return render_internal(checkpoint.samples, world).merge(checkpoint);
@@ -62,5 +74,34 @@ Canvas Camera::render(const World &world, const RenderOpts &opts) const {  // sc
   rl_scene_destroy(sc);
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtc_render: ") + rl_last_error());
   return c;
+}
+std::vector<double> World::color_at(const rl_ray *rays, size_t n) const {  // world.rs:100
+  Flattened f;
+  flatten(f);
+  rl_rtc_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtc_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtc_scene_create: ") + rl_last_error());
+  std::vector<double> out(n * 3);
+  int rc = rl_rtc_color_at_rays(sc, rays, n, out.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtc_color_at_rays: ") + rl_last_error());
+  return out;
+}
+std::vector<uint32_t> World::intersect(const rl_ray *rays, size_t n, uint32_t k, std::vector<rl_rtc_isect> *isects,
+                                       std::vector<uint32_t> *hit_index) const {  // world.rs:46, intersect.rs:159
+  Flattened f;
+  flatten(f);
+  rl_rtc_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtc_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtc_scene_create: ") + rl_last_error());
+  std::vector<uint32_t> counts(n);
+  const bool want = isects && k > 0;
+  if (want) isects->assign(n * k, rl_rtc_isect{});
+  if (hit_index) hit_index->assign(n, 0u);
+  int rc = rl_rtc_intersect_rays(sc, rays, n, want ? k : 0u, want ? isects->data() : nullptr, counts.data(), hit_index ? hit_index->data() : nullptr,
+                                 nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtc_intersect_rays: ") + rl_last_error());
+  return counts;
 }
 }  // namespace rtc

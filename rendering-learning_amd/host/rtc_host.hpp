@@ -564,6 +564,11 @@ struct World {
     f.max_reflection_depth = (uint32_t)max_reflection_depth;
     f.void_color[0] = void_color.r, f.void_color[1] = void_color.g, f.void_color[2] = void_color.b;
   }
+  // World::color_at / World::intersect (world.rs:100, :46) for a batch of rays, on the GPU (rl_rtc_color_at_rays / rl_rtc_intersect_rays;
+  // host_render.cpp).  color_at: n * 3 doubles.  intersect: the counts; `isects` (optional) receives [n][k] entries, `hit_index` the hit()'s.
+  std::vector<double> color_at(const rl_ray *rays, size_t n) const;
+  std::vector<uint32_t> intersect(const rl_ray *rays, size_t n, uint32_t k = 0, std::vector<rl_rtc_isect> *isects = nullptr,
+                                  std::vector<uint32_t> *hit_index = nullptr) const;
 };
 
 struct RenderOpts {

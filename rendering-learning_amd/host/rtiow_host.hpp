@@ -671,6 +671,10 @@ struct DeviceBvh : Hittable {
 };
 
 // ---------------------------------------------------------------- camera.rs
+// Hittable::hit(&Ray, &Interval) (hittable/mod.rs:42) for a batch of rays, on the GPU (rl_rtiow_hit_rays): out[i] is the record of
+// world.hit(&rays[i], &ray_t), out[i].hit == 0 for None.  Throws on any error but RL_E_DEGENERATE (host_render.cpp).
+std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t n, Interval ray_t);
+
 struct CameraParams {  // camera.rs:23-59 (defaults as in the reference)
   double aspect_ratio = 1.0;
   size_t image_width = 100;
