@@ -315,6 +315,38 @@ def set_fastg_one_wave(mode):
     L.rl_debug_set_fastg_one_wave(int(mode))
 
 
+def set_pixel_entry(max_entries):
+    """Tests / tools: the fast sphere kernel's camera rays start at their pixel's entry cut of up to max_entries (1 .. 3) entries of the
+    fast tree; 0: at the root, as scattered rays do (csrc/rl_pixel_entry.h; the same switch as RL_PIXEL_ENTRY)."""
+    L = render_lib()
+    L.rl_debug_set_pixel_entry.argtypes = [C.c_int]
+    L.rl_debug_set_pixel_entry(int(max_entries))
+
+
+def pixel_entry_table(world, n_pixels):
+    """Tests: the entry words of the scene's most recent fast-traversal render (finished), one uint32 per pixel of the rows it rendered."""
+    L = render_lib()
+    L.rl_debug_pixel_entry_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+    out = np.zeros(int(n_pixels), dtype=np.uint32)
+    _check(L.rl_debug_pixel_entry_read(world.device(), out.ctypes.data_as(C.c_void_p), int(n_pixels)))
+    return out
+
+
+def fast_tree(world):
+    """Tests: the fast traversal tree of a sphere scene as (children [n_inner, 2] entry ids, root entry); entry e < n_inner is an inner
+    node, e >= n_inner the sphere e - n_inner.  None when the scene has no fast structure."""
+    L = render_lib()
+    L.rl_debug_fast_tree.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    L.rl_debug_fast_tree.restype = C.c_int
+    root = C.c_uint32()
+    n = L.rl_debug_fast_tree(world.device(), None, 0, C.byref(root))
+    if n < 0:
+        return None
+    ch = np.zeros((max(n, 1), 2), dtype=np.uint32)
+    L.rl_debug_fast_tree(world.device(), ch.ctypes.data_as(C.c_void_p), n, C.byref(root))
+    return ch[:n], int(root.value)
+
+
 def set_status_gap(device_us, host_us=0):
     """Tests only: a wait of device_us on the render's stream before each asynchronous status copy, and a host sleep of host_us
     between a multi-GPU frame and its status post (each capped at 20 ms; 0, 0: off, the default)."""

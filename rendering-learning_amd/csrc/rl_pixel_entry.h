@@ -1,0 +1,189 @@
+// Per-pixel entry of the FAST traversal (rl_rtiow_wave.h, LDS_SCENE = 4): where the camera rays of a pixel start their walk.
+//
+// All camera rays of one pixel leave the same lens disc through the same pixel square, and each of them walks the tree from the root with
+// closest = +inf, re-discovering the same missed boxes.  Camera and scene are fixed for a render call, so this kernel does that part of
+// the walk once per pixel: it walks the tree with the pixel's BEAM — every ray get_ray (camera.rs:203-216, the GEN block) can produce for
+// the pixel — and writes one word per pixel, the entries a camera ray of that pixel starts from instead of the root:
+//     word = e0 | e1 << 10 | e2 << 20 | 3 << 30        (entry ids as on the walk's stack, FAST_NONE = unused, e0 is visited first)
+// The entries are disjoint subtrees (or leaves) that together hold every leaf whose box some ray of the beam touches:
+//     no such leaf -> all FAST_NONE (the sample is a miss without a single step);  one -> that leaf;  otherwise the deepest inner node
+//     whose subtree holds them all, and with max_entries = 2 / 3 that node split once / twice into the reduced entries of its children
+//     (the child subtree's own deepest holder), nearest first by the beam's entry distance.
+//
+// Why the frames cannot change.  A sphere outside the entries' subtrees has a padded leaf box that no ray of the beam touches in exact
+// arithmetic.  By the guard_pad argument (rl_fast_bvh.cpp) its rounded discriminant is negative, so Sphere::hit returns None for every
+// window: it can neither be the answer, nor be within a tie band of the answer, nor trip an order check, and the root walk — whether
+// it rejects that sphere's boxes or visits them — gets nothing from it.  Inside an entry's subtree the walk is the root walk's own
+// reject-only walk.  So answer, amb flag, re-traces and panic-site counts are those of the root walk for every ray it trusts.
+//
+// The beam test is CONSERVATIVE: "missed" only when no ray of the beam touches the stored box.  A ray is o + t d, t >= 0, with
+// o = lookfrom + a U + b V (|(a, b)| <= 1; U = V = 0 without defocus) and o + d = T = pixel_center + sx du + sy dv, |sx|, |sy| <= 1/2; so
+// its points are (1 - t) o + t T.  Per axis k, with O_k = [lookfrom_k -+ (|U_k| + |V_k|)] and T_k = [pc_k -+ (|du_k| + |dv_k|) / 2]:
+//     0 <= t <= 1:  x_k(t) in [Olo + t (Tlo - Olo), Ohi + t (Thi - Ohi)]
+//     t >= 1:       x_k(t) in [Ohi + t (Tlo - Ohi), Olo + t (Thi - Olo)]
+// both ends linear in t: "inside the box's slab" is two linear inequalities per axis and piece, the six of a piece cut an interval of t,
+// and the box is missed when that interval is empty in both pieces (a superset test: the three axes may use different rays).
+// Rounding.  The kernel's ray is the ROUNDED (o, d) of GEN: pixel_center, pixel_sample and o carry at most 8u M of error each, u = 2^-53,
+// M = the sum of the magnitudes that enter them (|p00| + W |du| + H |dv| + |lookfrom| + |U| + |V|, largest axis), and d = RN(ps - o)
+// moves the point at t by t u |d| <= 2 t u M: the ray's points lie within 18u M (1 + t) of the exact beam's.  The lines above are
+// evaluated in binary64 too (their offsets and slopes carry <= 4u M).  So every line is pushed OUTWARDS by delta (1 + t) with
+// delta = 2^-40 M = 8192u M — offset -+ delta, slope -+ delta — several hundred times the sum of all of that.  The inequalities are then
+// solved by one subtraction and one division each (relative error <= 2.01u in the bound of t, sign exact); an interval [lo, hi] of t
+// counts as empty only when lo > hi + 1e-12 (|lo| + |hi|), five thousand times those roundings.  NaN fails every comparison and fmax / fmin
+// drop it: a NaN or infinity anywhere removes constraints, never adds one, and a non-finite delta makes every box "touched".
+#pragma once
+#include "rl_rtiow_kernel.h"
+
+namespace rl {
+
+// How many entries a pixel's word may hold by default (RL_PIXEL_ENTRY / rl_debug_set_pixel_entry change it; 0 = no table, root walk)
+static constexpr int PIXEL_ENTRY_DEFAULT = 3;
+
+struct PixelBeam {
+  double olo[3], ohi[3], tlo[3], thi[3];  // origin and target intervals per axis (not yet pushed outwards)
+  double delta;
+};
+
+// true when some ray of the beam MAY touch the box b = {x.min, x.max, y.min, y.max, z.min, z.max}; t_near: a lower bound of t over the touching rays
+__device__ __forceinline__ bool beam_touches(const PixelBeam &B, const float *b, double &t_near) {
+  const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  if (!(B.delta < INF)) {  // also NaN
+    t_near = 0.0;
+    return true;
+  }
+  bool touched = false;
+  t_near = INF;
+#pragma unroll
+  for (int piece = 0; piece < 2; piece++) {
+    double lo = piece ? 1.0 : 0.0, hi = piece ? INF : 1.0;
+    bool empty = false;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      const double bl = (double)b[2 * k], bh = (double)b[2 * k + 1];
+      // lower line A + t S (pushed down), upper line C + t E (pushed up)
+      const double A = (piece ? B.ohi[k] : B.olo[k]) - B.delta, S = (B.tlo[k] - (piece ? B.ohi[k] : B.olo[k])) - B.delta;
+      const double C = (piece ? B.olo[k] : B.ohi[k]) + B.delta, E = (B.thi[k] - (piece ? B.olo[k] : B.ohi[k])) + B.delta;
+      // A + t S <= bh
+      const double a = bh - A;
+      if (S > 0.0) hi = fmin(hi, a / S);
+      else if (S < 0.0) lo = fmax(lo, a / S);
+      else if (a < 0.0) empty = true;
+      // C + t E >= bl
+      const double c = bl - C;
+      if (E > 0.0) lo = fmax(lo, c / E);
+      else if (E < 0.0) hi = fmin(hi, c / E);
+      else if (c > 0.0) empty = true;
+    }
+    if (lo > hi + 1e-12 * (fabs(lo) + fabs(hi))) empty = true;
+    if (!empty) touched = true, t_near = fmin(t_near, lo);
+  }
+  return touched;
+}
+
+// What a subtree reduces to: the number of its leaves the beam may touch, the deepest entry that holds them all, the nearest t among them
+struct EntryCut {
+  uint32_t count, entry;
+  double t_near;
+};
+
+// Reduces the subtree of entry e (its own box already found touched, at t_e): post-order walk with an explicit stack, depth <= FAST_MAX_DEPTH
+__device__ __forceinline__ EntryCut reduce_subtree(const RtiowParams &P, const PixelBeam &B, uint32_t e, double t_e) {
+  if (e >= P.n_fast_inner) return EntryCut{1u, e, t_e};
+  const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  constexpr int MAXD = (int)FAST_MAX_DEPTH + 2;
+  uint32_t node[MAXD], phase[MAXD];  // phase: children of node[] already handled (0 .. 2)
+  EntryCut acc[MAXD];                // what the handled children reduced to
+  int sp = 0;
+  node[0] = e, phase[0] = 0, acc[0] = EntryCut{0u, FAST_NONE, INF};
+  EntryCut done{0u, FAST_NONE, INF};
+  for (;;) {
+    if (phase[sp] == 2u) {  // both children handled: this node's result goes to its parent
+      done = acc[sp];
+      if (sp == 0) break;
+      sp--;
+    } else {
+      const FastNode &nd = P.fast_nodes[node[sp]];
+      const uint32_t side = phase[sp]++;
+      const uint32_t ce = side ? (nd.child >> 16) : (nd.child & 0xFFFFu);
+      double tc;
+      done = EntryCut{0u, FAST_NONE, INF};
+      if (beam_touches(B, nd.box[side], tc)) {
+        if (ce >= P.n_fast_inner) done = EntryCut{1u, ce, tc};
+        else if (sp + 1 < MAXD) {  // (always: the tree is at most FAST_MAX_DEPTH deep)
+          sp++;
+          node[sp] = ce, phase[sp] = 0, acc[sp] = EntryCut{0u, FAST_NONE, INF};
+          continue;
+        } else done = EntryCut{2u, ce, tc};  // not walked: the child itself holds whatever lies below it
+      }
+    }
+    // fold `done` (a child's result) into the node on top of the stack
+    EntryCut &a = acc[sp];
+    if (done.count != 0u) {
+      if (a.count != 0u) a = EntryCut{a.count + done.count, node[sp], fmin(a.t_near, done.t_near)};
+      else a = done;
+    }
+  }
+  return done;
+}
+
+// One thread per pixel of the rows this call renders: out[pr * W + px] (the kernels' shard-local pixel index)
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(RtiowParams P, const float *leaf_boxes, uint32_t max_entries, uint32_t *out) {
+  const uint32_t W = P.cam.image_width;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint64_t)P.nrows * W) return;
+  const uint32_t pr = (uint32_t)(i / W), px = (uint32_t)(i - (uint64_t)pr * W);
+  const uint32_t y = P.row_first + pr * P.row_step;
+  const rl_rtiow_camera &cam = P.cam;
+  PixelBeam B;
+  double M = 0.0;
+  const bool lens = !(cam.defocus_angle <= 0.0);  // (NaN: GEN takes the disc branch too)
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double pc = (cam.pixel_00[k] + cam.pixel_du[k] * (double)px) + cam.pixel_dv[k] * (double)y;
+    const double ht = 0.5 * (fabs(cam.pixel_du[k]) + fabs(cam.pixel_dv[k]));
+    const double ho = lens ? fabs(cam.defocus_disk_u[k]) + fabs(cam.defocus_disk_v[k]) : 0.0;
+    B.tlo[k] = pc - ht, B.thi[k] = pc + ht;
+    B.olo[k] = cam.lookfrom[k] - ho, B.ohi[k] = cam.lookfrom[k] + ho;
+    M = fmax(M, fabs(cam.pixel_00[k]) + fabs(cam.pixel_du[k]) * (double)W + fabs(cam.pixel_dv[k]) * (double)cam.image_height + fabs(cam.lookfrom[k]) +
+                    fabs(cam.defocus_disk_u[k]) + fabs(cam.defocus_disk_v[k]));
+  }
+  B.delta = M * 0x1.0p-40;
+  if (!(M >= 0.0)) B.delta = __longlong_as_double(0x7FF0000000000000ll);  // NaN
+  // the root: a leaf of its own (one sphere, no node) is tested against its leaf box, an inner node is walked
+  const uint32_t root = P.fast_root;
+  EntryCut c[3];
+  uint32_t nc = 1;
+  if (root >= P.n_fast_inner) {
+    double t0;
+    const bool hit = beam_touches(B, leaf_boxes + (size_t)(root - P.n_fast_inner) * 8, t0);
+    c[0] = hit ? EntryCut{1u, root, t0} : EntryCut{0u, FAST_NONE, 0.0};
+  } else c[0] = reduce_subtree(P, B, root, 0.0);
+  // split the holder of several leaves into its children's reduced entries, the one with the most leaves first, up to max_entries
+  while (nc < max_entries && nc < 3u) {
+    uint32_t pick = 3u, best = 1u;
+    for (uint32_t k = 0; k < nc; k++)
+      if (c[k].entry < P.n_fast_inner && c[k].count > best) pick = k, best = c[k].count;
+    if (pick == 3u) break;
+    const FastNode &nd = P.fast_nodes[c[pick].entry];
+    double ta, tb;
+    // (a holder of several leaves has them on both sides: both boxes are touched, and both reductions count at least one)
+    const bool ha = beam_touches(B, nd.box[0], ta), hb = beam_touches(B, nd.box[1], tb);
+    if (!(ha && hb)) break;
+    const EntryCut ra = reduce_subtree(P, B, nd.child & 0xFFFFu, ta), rb = reduce_subtree(P, B, nd.child >> 16, tb);
+    if (ra.count == 0u || rb.count == 0u) break;
+    c[pick] = ra, c[nc++] = rb;
+  }
+  // nearest first (at most three: a sorting network)
+  auto order = [&](uint32_t a, uint32_t b) {
+    if (b < nc && c[b].t_near < c[a].t_near) {
+      const EntryCut t = c[a];
+      c[a] = c[b], c[b] = t;
+    }
+  };
+  order(0, 1), order(1, 2), order(0, 1);
+  uint32_t w = 3u << 30;
+  for (uint32_t k = 0; k < 3u; k++) w |= (k < nc && c[k].count != 0u ? c[k].entry : FAST_NONE) << (10u * k);
+  out[i] = w;
+}
+
+}  // namespace rl

@@ -24,6 +24,7 @@
 #include "rl_rtiow_wave_general.h"
 #include "rl_rtiow_fastgen.h"
 #include "rl_rtiow_coop.h"
+#include "rl_pixel_entry.h"
 #include "rl_ray_query.h"
 #ifdef RL_EXPERIMENTAL  // the measured-and-lost restructurings: only in librl_render_exp.so, never in the product library
 #include "experimental/rl_rtiow_pool.h"
@@ -69,6 +70,7 @@ struct Switches {
   int rtc_full_regs = 768;       // RL_RTC_FULL_REGS (256 / 512: experimental library only)
   unsigned indep_k = 1;          // RL_INDEP_K=<k>: samples of one pixel per claim in the sample-parallel mode
   size_t indep_cap = (size_t)1 << 30;  // RL_INDEP_CAP_MB=<MiB>: cap of that mode's pass buffer (a smaller one forces more passes: tests)
+  int pixel_entry = rl::PIXEL_ENTRY_DEFAULT;  // RL_PIXEL_ENTRY=0|1|2|3: the fast kernel's camera rays start at the root / at their pixel's entry cut of up to n entries (rl_pixel_entry.h)
 } g_sw;
 unsigned long long g_last_slow_traces = 0;
 bool g_fast_debug_stats = false;  // tools only (experimental library): counting renders run the fast kernel too (counters are then NOT the reference's)
@@ -107,6 +109,7 @@ void read_switches() {
   if (const char *v = std::getenv("RL_RTC_REGS")) w.rtc_regs = std::atoi(v);
   if (const char *v = std::getenv("RL_RTC_FULL_REGS")) w.rtc_full_regs = std::atoi(v);
   if (const char *v = std::getenv("RL_INDEP_K")) w.indep_k = (unsigned)std::max(1, std::atoi(v));
+  if (const char *v = std::getenv("RL_PIXEL_ENTRY")) w.pixel_entry = std::min(3, std::max(0, std::atoi(v)));
   if (const char *v = std::getenv("RL_INDEP_CAP_MB")) w.indep_cap = (size_t)std::max(1, std::atoi(v)) << 20;
   g_sw = w;
 #ifdef RL_EXPERIMENTAL
@@ -286,7 +289,7 @@ static void destroy_one(rl_scene *s) {
   hipFree(s->d_ops), hipFree(s->d_lops), hipFree(s->d_sphere_flat), hipFree(s->d_cops), hipFree(s->d_movbits), hipFree(s->d_spheres), hipFree(s->d_sphere_material), hipFree(s->d_planars), hipFree(s->d_translates);
   hipFree(s->d_transforms), hipFree(s->d_materials), hipFree(s->d_textures), hipFree(s->d_images), hipFree(s->d_image_pool), hipFree(s->d_perlins), hipFree(s->d_media);
   hipFree(s->d_tris), hipFree(s->d_xforms), hipFree(s->d_rmaterials), hipFree(s->d_lights), hipFree(s->d_scratch);
-  hipFree(s->d_pos), hipFree(s->d_tile_cost), hipFree(s->d_tile_order), hipFree(s->d_tile_keys), hipFree(s->d_tile_iota), hipFree(s->d_sort_temp);
+  hipFree(s->d_pos), hipFree(s->d_tile_cost), hipFree(s->d_tile_order), hipFree(s->d_tile_keys), hipFree(s->d_tile_iota), hipFree(s->d_sort_temp), hipFree(s->d_pixel_entry);
   hipFree(s->d_shapes), hipFree(s->d_csgs), hipFree(s->d_patterns), hipFree(s->d_guards), hipFree(s->d_shard), hipFree(s->d_pix_rays), hipFree(s->d_fast_nodes), hipFree(s->d_fast_leaf_boxes), hipFree(s->d_coop_pixels), hipFree(s->d_steal_state), hipFree(s->d_steal_n), hipFree(s->d_fg_nodes), hipFree(s->d_fg_onodes), hipFree(s->d_fg_seg_roots), hipFree(s->d_fg_media), hipFree(s->d_fg_items), hipFree(s->d_fg_spheres), hipFree(s->d_fg_material);
 #ifdef RL_EXPERIMENTAL
   if (ExpBuffers *E = (ExpBuffers *)s->exp) {
@@ -892,6 +895,26 @@ static int choose_rtiow_variant(const rl_scene *scene, const rl_rtiow_camera *ca
   return RL_OK;
 }
 
+// Variant 1029 only: the per-pixel entry table of this render's camera and rows (rl_pixel_entry.h), built on `stream` ahead of the render
+// kernels into the scene's own buffer (grown on demand, like d_pos).  Nothing is kept from call to call: the camera may differ.
+static int build_pixel_entry(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream) {
+  P.pixel_entry = nullptr;
+  const size_t npix = (size_t)nrows * P.cam.image_width;
+  if (g_sw.pixel_entry <= 0 || npix == 0) return RL_OK;
+  rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only
+  if (ms->pixel_entry_pix < npix) {
+    hipFree(ms->d_pixel_entry);
+    ms->d_pixel_entry = nullptr, ms->pixel_entry_pix = 0;
+    HIP_TRY(hipMalloc((void **)&ms->d_pixel_entry, npix * sizeof(uint32_t)));
+    ms->pixel_entry_pix = npix;
+  }
+  hipLaunchKernelGGL(rtiow_pixel_entry_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, P, (const float *)scene->d_fast_leaf_boxes, (uint32_t)g_sw.pixel_entry,
+                     ms->d_pixel_entry);
+  HIP_TRY(hipGetLastError());
+  P.pixel_entry = ms->d_pixel_entry;
+  return RL_OK;
+}
+
 namespace rl {
 int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, void *d_out,
                         hipStream_t stream, bool want_stats) {
@@ -956,6 +979,10 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
   }
   const int variant = choice.variant;
   const size_t compact_bytes = choice.compact_bytes, fast_bytes = choice.fast_bytes;
+  if (variant == 1029) {
+    int rce = build_pixel_entry(scene, P, nrows, stream);
+    if (rce != RL_OK) return rce;
+  }
   bool steal = false;  // set for the resume launch of a small shard (variant 1029)
   auto launch_coop = [&](const uint32_t *d_pixels, uint32_t n_pixels) -> int {
     constexpr int NW = 4;
@@ -1269,6 +1296,10 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
     ms->indep_bytes = buf_bytes;
   }
   P.indep_buf = ms->d_indep, P.indep_k = K, P.indep_tile_slots = (uint32_t)tile_slots;
+  if (variant == 1029) {  // the sample-parallel fast kernel shares the body: its camera rays start at their pixel's entry too
+    int rce = build_pixel_entry(scene, P, nrows, stream);
+    if (rce != RL_OK) return rce;
+  }
   HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 512, stream));  // work counter and stats: once per render
   const bool trans = rt.has_noise || rt.has_sphere_uv;
   const bool fg_media = H.fg.stage_roots.size() > 1;
@@ -1607,6 +1638,24 @@ void rl_debug_set_fast_traversal(int on) { g_sw.fast_traversal = on != 0; }
 void rl_debug_set_rtc_blocks(int per_cu) { g_sw.rtc_blocks_per_cu = per_cu < 0 ? 0 : per_cu; }  // 0: as many as are resident (default); n: n per CU (tests)
 void rl_debug_set_indep_cap(unsigned long long bytes) { g_sw.indep_cap = bytes ? (size_t)bytes : (size_t)1 << 30; }  // sample-parallel pass buffer cap (0: default 1 GiB)
 void rl_debug_set_indep_k(unsigned k) { g_sw.indep_k = k ? k : 1u; }  // samples of one pixel per claim in the sample-parallel mode
+void rl_debug_set_pixel_entry(int max_entries) { g_sw.pixel_entry = std::min(3, std::max(0, max_entries)); }  // 0: camera rays start at the root (A/B, tests)
+// Tests: the entry table of the scene's most recent fast-traversal render (n_pixels words, rows x W of the shard rendered), after that render has finished
+int rl_debug_pixel_entry_read(const rl_scene *scene, uint32_t *out, uint64_t n_pixels) {
+  if (!scene || !out || !scene->d_pixel_entry || n_pixels > scene->pixel_entry_pix) return RL_E_INVALID;
+  int rc0 = rl::use_context(scene->ctx);
+  if (rc0 != RL_OK) return rc0;
+  HIP_TRY(hipMemcpy(out, scene->d_pixel_entry, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RL_OK;
+}
+// Tests: the fast tree's shape — children[2 i], children[2 i + 1] = the entry ids of inner node i's children, for the first `cap` nodes; *root = the
+// entry a root walk starts at.  Returns the number of inner nodes, -1 when the scene has no fast structure.
+int rl_debug_fast_tree(const rl_scene *scene, uint32_t *children, uint32_t cap, uint32_t *root) {
+  if (!scene || scene->kind != 1 || !scene->hrt || scene->hrt->fast_root == FAST_NONE) return -1;
+  const HostRtiow &H = *scene->hrt;
+  if (root) *root = H.fast_root;
+  for (uint32_t i = 0; children && i < cap && i < H.fast_nodes.size(); i++) children[2 * i] = H.fast_nodes[i].child & 0xFFFFu, children[2 * i + 1] = H.fast_nodes[i].child >> 16;
+  return (int)H.fast_nodes.size();
+}
 void rl_debug_set_fastg_one_wave(int mode) { g_sw.fastg_nt256 = mode; }  // -1: by frame size (default), 0 / 1: never / always the one-wave-per-SIMD form (tests)
 // Tests only: widen the windows in which concurrent renders of one scene could lose a panic-site count.  device_us: a one-lane wait
 // kernel on the render's stream just before its status copy; host_us: a host sleep between a multi-GPU frame and its status post.

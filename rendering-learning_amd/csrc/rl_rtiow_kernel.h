@@ -83,6 +83,8 @@ struct RtiowParams {
   // sample-major (slot / indep_tile_slots = group); each sample's colour goes to indep_buf[sample - sample_begin][nrows * W][3]
   double *indep_buf;
   uint32_t indep_k, indep_tile_slots;
+  // fast traversal (LDS_SCENE = 4): per-pixel entry words of this render's camera rays, [nrows * W] (rl_pixel_entry.h); null: every ray starts at fast_root
+  const uint32_t *pixel_entry;
 };
 
 // INDEP: the colour of sample `rel` (relative to the pass's sample_begin) of shard pixel (pr, px) into the pass buffer

@@ -97,6 +97,8 @@
   constexpr uint32_t DEPTH_MASK = LDS_SCENE == 4 ? FAST_DEPTH_MASK : ~0u;
   uint32_t c_rays = 0, c_flag = 0, c_slow = 0;  // c_slow: rays the fast traversal handed to the reference-order fold
   unsigned long long c_nodes = 0, c_sph = 0, c_words = 0, c_self = 0;  // c_self (STATS): self tests skipped
+  // STATS census (tools/sched.py): the camera rays' share — a camera ray is the one whose remaining depth is still cam.max_depth
+  unsigned long long c_cam_trav = 0, c_cam_leaf = 0, c_cam_rays = 0;
 
   // fast traversal (LDS_SCENE = 4): 16 ten-bit entry ids in five registers, newest in the low bits of stk0; all ones = empty
   uint32_t stk0 = ~0u, stk1 = ~0u, stk2 = ~0u, stk3 = ~0u, stk4 = ~0u;
@@ -143,7 +145,10 @@
     } else if (e >= P.n_fast_inner) pc = e, state = ST_LEAF;
     else pc = lds_base + (e << 6), state = ST_TRAV;
   };
-  auto start_ray = [&]() {  // o, d set: per-ray constants of the box filter, then the first traversal state
+  // w (fast traversal): where the walk starts — up to three entry ids, the first one in the low ten bits, FAST_NONE in the unused slots,
+  // the top two bits set.  fast_root_word for a scattered ray; a camera ray takes its pixel's word of P.pixel_entry (rl_pixel_entry.h)
+  const uint32_t fast_root_word = P.fast_root | ~1023u;
+  auto start_ray = [&](uint32_t w) {  // o, d set: per-ray constants of the box filter, then the first traversal state
     closest = INF, hit_prim = NONE;
     if (LDS_SCENE == 4) ra32 = ray_aux32_direct(o, d);
     else {
@@ -152,9 +157,9 @@
       ra32 = ray_aux32(ra);
     }
     if (LDS_SCENE == 4) {
-      stk0 = stk1 = stk2 = stk3 = stk4 = ~0u;
+      stk0 = (w >> 10) | (FAST_NONE << 22), stk1 = stk2 = stk3 = stk4 = ~0u;
       amb = !(ra32.slack < __int_as_float(0x7F800000));  // outside the binary32 filter's range: the reference's order from the start
-      fast_go(amb ? FAST_NONE : P.fast_root);
+      fast_go(amb ? FAST_NONE : w & 1023u);
     } else {
       pc = entry0 & 0x1FFFFFFFu;
       state = entry0 >> 29;
@@ -257,7 +262,7 @@
           pix_rays++;
           o = p;
           d = nd;
-          start_ray();
+          start_ray(fast_root_word);
         }
   };
 
@@ -337,6 +342,7 @@
               return diff < -thresh;  // certainly tmin > tmax; false for NaN arithmetic: visit
             };
             if (STATS) c_nodes += 2;  // debug instantiation only (rl_debug_fast_stats): the fast structure's own tests, not the reference's
+            if (STATS && (depth & DEPTH_MASK) == cam.max_depth) c_cam_trav++;
             float tA, tB;
             const uint32_t eA = w & 0xFFFFu, eB = w >> 16, self = depth >> 22;  // self: the sphere the ray left, proven missed (fast_self_miss)
             const bool boxA = !missed(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tA);
@@ -394,6 +400,7 @@
             const uint32_t sidx = pc - P.n_fast_inner;
             const uint32_t payload = sidx | (((s_bits[sidx >> 5] >> (sidx & 31u)) & 1u) ? SPH_MOVING : 0u);
             if (STATS) c_sph++;
+            if (STATS && (depth & DEPTH_MASK) == cam.max_depth) c_cam_leaf++;
             if (SPLIT_LEAF) {
               if (fast_sphere_misses(spheres[sidx], payload, o, d, time)) fast_go(fast_pop());
               else state = ST_LEAF2;
@@ -575,7 +582,9 @@
         } else {
           c_rays++;
           pix_rays++;
-          start_ray();
+          if (STATS) c_cam_rays++;
+          // the pixel's entry word: read and used up here, so that it is not held across blocks (the kernel sits at 128 VGPRs)
+          start_ray(LDS_SCENE == 4 && P.pixel_entry ? P.pixel_entry[(size_t)pr * W + px] : fast_root_word);
         }
       }
       if (LATENCY_MODES && LDS_SCENE == 4 && P.prio_tiles != 0u) {  // A/B: issue priority for the waves that hold the frame's longest sample chains
@@ -631,5 +640,11 @@
     if (LDS_SCENE == 4) {
       v = wave_sum(c_self);
       if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 24], v);  // after the scheduler's 21 words (rl_debug_sched out[24])
+      v = wave_sum(c_cam_trav);  // the census: camera rays' TRAV lane-steps, LEAF visits, and their number (out[25 .. 27])
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 25], v);
+      v = wave_sum(c_cam_leaf);
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 26], v);
+      v = wave_sum(c_cam_rays);
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 27], v);
     }
   }

@@ -119,6 +119,8 @@ struct rl_scene {
   void *d_sort_temp = nullptr;
   size_t sort_temp_bytes = 0;
   size_t lpt_pix = 0, lpt_tiles = 0;
+  uint32_t *d_pixel_entry = nullptr;  // fast traversal: the current render's per-pixel entry words (rl_pixel_entry.h), grown on demand
+  size_t pixel_entry_pix = 0;
   // multi-GPU: this replica's row shard / on replica 0 the gather buffer [G][max_rows][W][3]
   double *d_shard = nullptr;
   size_t shard_bytes = 0;

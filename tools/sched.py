@@ -17,6 +17,11 @@ names = {0: "GEN", 1: "TRAV", 2: "SHADE", 3: "FILL", 5: "LEAF", 6: "SHADE2"}
 print("rays", st["rays"], "kernel_ms", st["kernel_ms"], "Mrays/s", st["rays"] / st["kernel_ms"] / 1e3, "box tests/ray", st["node_tests"] / st["rays"], "sphere tests/ray", st["sphere_tests"] / st["rays"])
 if out[24]:  # the fast kernel's self tests skipped in TRAV (rl_rtiow_wave.h fast_self_miss): sphere tests/ray + this = without the skip
     print("self tests skipped/ray", out[24] / st["rays"])
+if out[27]:  # census of the fast kernel's camera rays (remaining depth still max_depth): their share of the TRAV lane-steps and LEAF visits
+    trav, leaf = out[3 * 1 + 1], out[3 * 5 + 1]
+    print(f"camera rays {out[27]} ({100 * out[27] / st['rays']:.1f} % of the rays)  TRAV lane-steps {out[25]} of {trav} ({100 * out[25] / max(trav, 1):.1f} %, "
+          f"{out[25] / out[27]:.2f} per camera ray, {(trav - out[25]) / max(st['rays'] - out[27], 1):.2f} per scattered ray)  "
+          f"LEAF visits {out[26]} of {leaf} ({100 * out[26] / max(leaf, 1):.1f} %, {out[26] / out[27]:.3f} per camera ray)")
 tot = sum(out[3 * k + 2] for k in names)
 for k, nm in names.items():
     ex, pop, cyc = out[3 * k], out[3 * k + 1], out[3 * k + 2]
