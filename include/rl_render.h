@@ -469,7 +469,8 @@ typedef struct rl_rtc_isect { /* scene/intersect.rs:11-16 Intersection{t, object
 
 /* out_hits[i] = world.hit(&rays[i], &Interval{min: tmin, max: tmax}); the interval is closed at both ends (interval.rs).
  * Scenes with ConstantMedium objects: RL_E_UNSUPPORTED — a medium's hit draws its free path from the pixel's RNG stream
- * (constant_medium.rs:55, see rl_medium), and a bare ray has none. */
+ * (constant_medium.rs:55, see rl_medium), and a bare ray has none.  rl_rtiow_ray_color_rays below is the seeded alternative: there
+ * every ray carries an RNG cursor, and media scenes are accepted. */
 int rl_rtiow_hit_rays(const rl_scene *, const rl_ray *rays, uint64_t n, double tmin, double tmax, rl_rtiow_hit *out_hits, rl_stats *opt_stats);
 int rl_rtiow_hit_rays_device(const rl_scene *, const void *d_rays, uint64_t n, double tmin, double tmax, void *d_out_hits, void *hip_stream,
                              rl_stats *opt_stats);
@@ -484,6 +485,50 @@ int rl_rtc_intersect_rays_device(const rl_scene *, const void *d_rays, uint64_t 
 /* out_rgb[3*i ..] = World::color_at(&rays[i]) with the scene's max_reflection_depth. */
 int rl_rtc_color_at_rays(const rl_scene *, const rl_ray *rays, uint64_t n, double *out_rgb, rl_stats *opt_stats);
 int rl_rtc_color_at_rays_device(const rl_scene *, const void *d_rays, uint64_t n, void *d_out_rgb, void *hip_stream, rl_stats *opt_stats);
+
+/* =====================================================================
+ *  Seeded path queries: Camera::get_ray and Camera::ray_color for ray buffers
+ * =====================================================================
+ *   rl_rtiow_camera_rays*     <- ray-tracing-one-weekend/src/camera.rs:203-216  Camera::get_ray(&mut rng, x, y)
+ *   rl_rtiow_ray_color_rays*  <- ray-tracing-one-weekend/src/camera.rs:232-260  Camera::ray_color(&mut rng, &ray, world, depth)
+ * Both take, per ray, an RNG cursor and return the advanced one.  A cursor is ChaCha8Rng::seed_from_u64(seed) after
+ * set_stream(stream), at word position word_pos (get_word_pos; a draw is two words).  The reference's _render derives its stream per
+ * pixel and sample as sample_index * W * H + x * W + y and keeps the word position from sample to sample (camera.rs:161-170); the
+ * library does not compute streams for the caller.  With both calls a host rebuilds that loop itself and gets the library's own frames
+ * bit for bit: cursors (s*W*H + x*W + y, 0) for every sample give rl_rtiow_render_independent*, carrying each pixel's word_pos from one
+ * sample's output cursor into the next sample's input gives rl_rtiow_render*.  The kernels keep the position in 32 bits: an input
+ * word_pos >= 2^31 is RL_E_INVALID (host forms; the device forms document it as undefined).
+ * Status, concurrency, rl_init_multi, n = 0, NULL buffers and the wrong scene family: as stated for the batched ray queries above. */
+typedef struct rl_rng_cursor {
+  uint64_t stream;   /* ChaCha8Rng::set_stream */
+  uint64_t word_pos; /* ChaCha8Rng::get_word_pos, < 2^31 */
+} rl_rng_cursor;     /* 16 bytes */
+
+/* out_rays[i] = cam.get_ray(&mut rng_i, px[i], py[i]), rng_i = cursors[i] of seed cam->seed; out_cursors[i] = rng_i afterwards
+ * (out_cursors may alias cursors).  The draws are, in order: the pixel square's two, UnitDisc only when defocus_angle > 0, then time.
+ * px[i] >= image_width or py[i] >= image_height: RL_E_INVALID (host form; device form: undefined).  Needs an initialised device
+ * context but no scene; the host form runs on the current context's library stream and is synchronous, the device form is asynchronous
+ * on hip_stream (HIP errors are reported by the stream's next synchronising call). */
+int rl_rtiow_camera_rays(const rl_rtiow_camera *, uint64_t n, const uint32_t *px, const uint32_t *py, const rl_rng_cursor *cursors,
+                         rl_ray *out_rays, rl_rng_cursor *out_cursors);
+int rl_rtiow_camera_rays_device(const rl_rtiow_camera *, uint64_t n, const void *d_px, const void *d_py, const void *d_cursors,
+                                void *d_out_rays, void *d_out_cursors, void *hip_stream);
+
+/* out_rgb[3*i ..] = ray_color(&mut rng_i, &rays[i], world, max_depth) with rng_i = cursors[i] of `seed`, under the renders' arithmetic
+ * contract: it is the value a render adds to a pixel for that sample, defined as the sample-parallel mode defines a sample's colour
+ * (the accumulator starts at 0.0).  opt_out_cursors[i] = the cursor behind the path (may alias cursors); opt_out_ray_counts[i] = the
+ * rays traced for path i, their sum is stats.rays.  max_depth == 0: black, no ray, the cursor unchanged.  Rays are used as given, from
+ * any origin, without normalisation; a NaN or zero ray gives a defined result and is flagged only where the reference would panic.
+ * Scenes with ConstantMedium objects are accepted: the free path is drawn from the ray's own cursor where the reference's fold
+ * evaluates the medium, as in the renders.  Without opt_stats the call is counter-free and may be served by the fast tree walk (same
+ * bits; order-sensitive rays are re-traced in the reference's order); with opt_stats all counters are the reference's, rng_words = the
+ * words the paths consumed.  A batch beyond the 32-bit work counter runs as several passes back to back on the stream. */
+int rl_rtiow_ray_color_rays(const rl_scene *, const rl_ray *rays, const rl_rng_cursor *cursors, uint64_t n, uint64_t seed,
+                            uint32_t max_depth, const double background[3], double *out_rgb, rl_rng_cursor *opt_out_cursors,
+                            uint32_t *opt_out_ray_counts, rl_stats *opt_stats);
+int rl_rtiow_ray_color_rays_device(const rl_scene *, const void *d_rays, const void *d_cursors, uint64_t n, uint64_t seed,
+                                   uint32_t max_depth, const double background[3], void *d_out_rgb, void *d_opt_out_cursors,
+                                   void *d_opt_out_ray_counts, void *hip_stream, rl_stats *opt_stats);
 
 #ifdef __cplusplus
 }

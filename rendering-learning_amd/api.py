@@ -179,7 +179,8 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtc_scene_create", "rl_rtc_render", "rl_rtc_render_rows", "rl_rtc_render_device",
                   "rl_rtc_render_multi", "rl_rtc_render_multi_device", "rl_rtc_encode_rgb8_device", "rl_rtc_render_rgb8",
                   "rl_rtiow_hit_rays", "rl_rtiow_hit_rays_device", "rl_rtc_intersect_rays", "rl_rtc_intersect_rays_device",
-                  "rl_rtc_color_at_rays", "rl_rtc_color_at_rays_device"]
+                  "rl_rtc_color_at_rays", "rl_rtc_color_at_rays_device",
+                  "rl_rtiow_camera_rays", "rl_rtiow_camera_rays_device", "rl_rtiow_ray_color_rays", "rl_rtiow_ray_color_rays_device"]
 
 
 def render_lib():
@@ -220,6 +221,12 @@ def render_lib():
                                                    C.POINTER(Stats)]
         L.rl_rtc_color_at_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
         L.rl_rtc_color_at_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtiow_camera_rays.argtypes = [C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rl_rtiow_camera_rays_device.argtypes = [C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rl_rtiow_ray_color_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        L.rl_rtiow_ray_color_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -383,8 +390,42 @@ def pack_rays(origins, dirs, times=None):
     return rays
 
 
+RNG_CURSOR = np.dtype([("stream", "<u8"), ("word_pos", "<u8")])  # rl_rng_cursor
+
+
+def pack_cursors(streams, word_pos=0):
+    """[n] ChaCha8 stream numbers (+ a word position, one for all or [n]) -> the rl_rng_cursor records the seeded path queries take.
+    camera.rs:161-170 derives the stream of sample s at pixel (x, y) as s*W*H + x*W + y.  Shape errors are the caller's: ValueError."""
+    st = np.asarray(streams)
+    if st.ndim != 1 or st.dtype.kind not in "iu":
+        raise ValueError(f"streams must be [n] integers (got shape {st.shape}, dtype {st.dtype})")
+    wp = np.asarray(word_pos)
+    if wp.dtype.kind not in "iu" or wp.shape not in ((), st.shape):
+        raise ValueError(f"word_pos must be one integer or [n] integers (got shape {wp.shape}, dtype {wp.dtype})")
+    if (st.dtype.kind == "i" and (st < 0).any()) or (wp.dtype.kind == "i" and (wp < 0).any()):
+        raise ValueError("streams and word positions are unsigned")
+    cur = np.zeros(st.shape[0], dtype=RNG_CURSOR)
+    cur["stream"], cur["word_pos"] = st, wp
+    return cur
+
+
+def _cursors_arg(cursors, n):
+    cur = np.ascontiguousarray(cursors)
+    if cur.dtype != RNG_CURSOR or cur.shape != (n,):
+        raise ValueError(f"cursors must be [{n}] RNG_CURSOR records (pack_cursors); got shape {cur.shape}, dtype {cur.dtype}")
+    return cur
+
+
+def set_query_pass_cap(rays):
+    """rl_debug_set_query_pass_cap: rays per pass of ray_color_rays* (0: what the 32-bit work counter allows); tests force several passes."""
+    L = render_lib()
+    L.rl_debug_set_query_pass_cap.argtypes = [C.c_uint64]
+    L.rl_debug_set_query_pass_cap.restype = None
+    L.rl_debug_set_query_pass_cap(int(rays))
+
+
 def last_query():
-    """rl_debug_last_query: which kernel served the most recent hit_rays* call ("fast" / "reference") and, for a synchronous call, how
+    """rl_debug_last_query: which kernel served the most recent hit_rays* / ray_color_rays* call ("fast" / "reference") and, for a synchronous call, how
     many of its rays the fast walk re-traced in the reference's order."""
     out = (C.c_uint64 * 2)()
     L = render_lib()
@@ -574,6 +615,34 @@ class World:
         st = Stats()
         rc = render_lib().rl_rtiow_hit_rays_device(self.device(), C.c_void_p(d_rays), n, tmin, tmax, C.c_void_p(d_out), C.c_void_p(stream),
                                                    C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+
+    def ray_color_rays(self, origins, dirs, times, cursors, seed, max_depth, background, stats=None, allow_degenerate=False, rays=None):
+        """Camera::ray_color(&mut rng, &ray, world, max_depth) (camera.rs:232-260) for every ray, on the GPU, ray i drawing from
+        cursors[i] of `seed` -> (rgb [n, 3], cursors behind the paths [n], rays traced per path [n]).  rays=: RAY records as get_rays returns
+        them, instead of origins / dirs / times.  Media scenes are accepted.  Without `stats` the call is counter-free (last_query())."""
+        rays = pack_rays(origins, dirs, times) if rays is None else np.ascontiguousarray(rays)
+        if rays.dtype != RAY or rays.ndim != 1:
+            raise ValueError("rays must be [n] RAY records")
+        n = rays.shape[0]
+        out_cur = _cursors_arg(cursors, n).copy()
+        bg = (C.c_double * 3)(*[float(v) for v in background])
+        rgb = np.zeros((n, 3), dtype=np.float64)
+        counts = np.zeros(n, dtype=np.uint32)
+        st = Stats()
+        rc = render_lib().rl_rtiow_ray_color_rays(self.device(), rays.ctypes.data, out_cur.ctypes.data, n, int(seed), int(max_depth), bg, rgb.ctypes.data,
+                                                  out_cur.ctypes.data, counts.ctypes.data, C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+        return rgb, out_cur, counts
+
+    def ray_color_rays_device(self, d_rays, d_cursors, n, seed, max_depth, background, d_rgb, d_out_cursors=0, d_ray_counts=0, stream=0, stats=None,
+                              allow_degenerate=False):
+        """Device buffers (n rl_ray and n rl_rng_cursor in; n*3 f64, optionally n rl_rng_cursor and n u32 out).  Asynchronous unless stats is a dict."""
+        bg = (C.c_double * 3)(*[float(v) for v in background])
+        st = Stats()
+        rc = render_lib().rl_rtiow_ray_color_rays_device(self.device(), C.c_void_p(d_rays), C.c_void_p(d_cursors), n, int(seed), int(max_depth), bg,
+                                                         C.c_void_p(d_rgb), C.c_void_p(d_out_cursors or None), C.c_void_p(d_ray_counts or None),
+                                                         C.c_void_p(stream), C.byref(st) if stats is not None else None)
         _finish_query(rc, st, stats, allow_degenerate)
 
 
@@ -829,6 +898,28 @@ class Camera:
         if stats is not None:
             stats.update(st.as_dict())
             stats["rc"] = rc
+
+    # ---- seeded path queries (include/rl_render.h rl_rtiow_camera_rays*): Camera::get_ray for a batch of pixels, each with its own RNG cursor
+    def get_rays(self, px, py, cursors):
+        """cam.get_ray(&mut rng_i, px[i], py[i]) (camera.rs:203-216), rng_i = cursors[i] of the camera's seed -> (RAY[n], cursors behind the draws)."""
+        x = np.ascontiguousarray(px, dtype=np.uint32)
+        y = np.ascontiguousarray(py, dtype=np.uint32)
+        if x.ndim != 1 or y.shape != x.shape:
+            raise ValueError(f"px and py must both be [n] (got {x.shape} and {y.shape})")
+        n = x.shape[0]
+        out_cur = _cursors_arg(cursors, n).copy()
+        if not _inited:
+            init()
+        rays = np.zeros(n, dtype=RAY)
+        _check(render_lib().rl_rtiow_camera_rays(C.byref(self.c), n, x.ctypes.data, y.ctypes.data, out_cur.ctypes.data, rays.ctypes.data, out_cur.ctypes.data))
+        return rays, out_cur
+
+    def get_rays_device(self, d_px, d_py, d_cursors, d_rays, d_out_cursors, n, stream=0):
+        """Device buffers (n u32 px, n u32 py, n rl_rng_cursor in; n rl_ray and n rl_rng_cursor out, which may be d_cursors).  Asynchronous."""
+        if not _inited:
+            init()
+        _check(render_lib().rl_rtiow_camera_rays_device(C.byref(self.c), n, C.c_void_p(d_px), C.c_void_p(d_py), C.c_void_p(d_cursors), C.c_void_p(d_rays),
+                                                        C.c_void_p(d_out_cursors), C.c_void_p(stream)))
 
     def render_multi(self, world: World, first_sample=0, stats=None, allow_degenerate=False) -> Canvas:
         """rl_rtiow_render_multi: the whole frame over every GPU of init_multi (rows interleaved, one RCCL exchange)."""

@@ -324,4 +324,48 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtc_color_at_rays_ke
   rtc_query_flush(cnt, P.stats, tid);
 }
 
+// Camera::get_ray (camera.rs:203-216) for a buffer of (x, y, cursor): GEN's camera arithmetic of the render kernels, expression for
+// expression, with the draws taken from the ray's own cursor.  One lane per ray, grid-stride; the lane's ChaCha8 blocks live in a Ring
+// column (ODD: a cursor may stand at any word).  Not a hot path: a few draws per ray.
+struct CameraRaysQuery {
+  rl_rtiow_camera cam;
+  uint32_t key[8];
+  const uint32_t *px, *py;
+  const rl_rng_cursor *cursors;
+  rl_ray *rays;
+  rl_rng_cursor *out_cursors;
+  unsigned long long n;
+};
+template <int NT>
+__global__ void __launch_bounds__(NT) rtiow_camera_rays_kernel(CameraRaysQuery Q) {
+  __shared__ unsigned long long s_rng[16 * NT];
+  const int tid = threadIdx.x;
+  const rl_rtiow_camera &cam = Q.cam;
+  Ring<NT, true, true> rng{Q.key, s_rng, tid, 0ull, 0u, 0u, 0u};
+  for (unsigned long long idx = (unsigned long long)blockIdx.x * NT + tid; idx < Q.n; idx += (unsigned long long)gridDim.x * NT) {
+    const uint64_t *cur = (const uint64_t *)(Q.cursors + idx);
+    const uint32_t px = Q.px[idx], y = Q.py[idx];
+    rng.pos = (uint32_t)cur[1], rng.nres = 0;
+    rng.reset_stream(cur[0]);
+    D3 p00 = ld3(cam.pixel_00), du = ld3(cam.pixel_du), dv = ld3(cam.pixel_dv);
+    D3 pixel_center = (p00 + du * (double)px) + dv * (double)y;
+    double sx = -0.5 + rng.gen_f64();
+    double sy = -0.5 + rng.gen_f64();
+    D3 pixel_sample = pixel_center + (du * sx + dv * sy);
+    D3 wo;
+    if (cam.defocus_angle <= 0.0) wo = ld3(cam.lookfrom);
+    else {
+      double a, b;
+      rng.unit_disc(a, b);
+      wo = (ld3(cam.lookfrom) + ld3(cam.defocus_disk_u) * a) + ld3(cam.defocus_disk_v) * b;
+    }
+    const D3 wd = pixel_sample - wo;
+    const double time = rng.gen_f64();
+    double *r = (double *)(Q.rays + idx);
+    r[0] = wo.x, r[1] = wo.y, r[2] = wo.z, r[3] = wd.x, r[4] = wd.y, r[5] = wd.z, r[6] = time;
+    uint64_t *oc = (uint64_t *)(Q.out_cursors + idx);
+    oc[0] = rng.stream, oc[1] = (uint64_t)rng.pos;
+  }
+}
+
 }  // namespace rl

@@ -2261,7 +2261,7 @@ int rl_rtiow_hit_rays_device(const rl_scene *scene, const void *d_rays, uint64_t
   return rtiow_hit_rays_impl(scene, d_rays, n, tmin, tmax, d_out, (hipStream_t)hip_stream, st != nullptr, st);
 }
 
-// which kernel served the most recent rl_rtiow_hit_rays* call of this process (1: reference order, 2: fast walk), and how many rays of
+// which kernel served the most recent rl_rtiow_hit_rays* / rl_rtiow_ray_color_rays* call of this process (1: reference order, 2: fast walk), and how many rays of
 // the most recent SYNCHRONOUS one the fast walk re-traced in the reference's order (asynchronous calls: rl_render_status + rl_debug_slow_traces)
 int rl_debug_last_query(unsigned long long *out2) {
   if (!out2) return set_err(RL_E_INVALID, "bad argument");
@@ -2377,6 +2377,223 @@ int rl_rtc_color_at_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, 
     if (st) *st = local;
   }
   return rc;
+}
+
+// ---- seeded path queries (include/rl_render.h): Camera::get_ray and Camera::ray_color for ray buffers
+static uint64_t g_query_pass_cap = 0;  // rl_debug_set_query_pass_cap: rays per pass of rl_rtiow_ray_color_rays* (0: what the work counter allows)
+void rl_debug_set_query_pass_cap(unsigned long long rays) { g_query_pass_cap = rays; }
+
+static int cursors_check(const rl_rng_cursor *cursors, uint64_t n) {
+  for (uint64_t i = 0; i < n; i++)
+    if (cursors[i].word_pos >= (uint64_t)1 << 31) return set_err(RL_E_INVALID, "cursor word_pos >= 2^31 (the kernels keep the position in 32 bits)");
+  return RL_OK;
+}
+
+// The same flavour choice as rtiow_render_indep_launch without the LDS sphere kernels: the counter-free general fast kernel wherever the
+// scene has a world-space SAH tree (sphere-only scenes: the queries' own, HostRtiow::qfg), the reference-order wave-scheduled kernel for
+// counting calls, scenes without one and RL_FAST=0.  sync_st as in rtiow_hit_rays_impl.
+static int rtiow_ray_color_impl(const rl_scene *scene, const void *d_rays, const void *d_cursors, uint64_t n, uint64_t seed, uint32_t max_depth,
+                                const double background[3], void *d_rgb, void *d_out_cursors, void *d_counts, hipStream_t stream, bool counting,
+                                rl_stats *sync_st) {
+  const RtiowProgram &rt = scene->rt();
+  const FastGeneral &QF = scene->hrt->query_tree();
+  rl_rtiow_camera qcam{};  // what a render takes from its camera and a query from the call
+  qcam.image_width = 8, qcam.image_height = 8, qcam.samples_per_pixel = 1, qcam.max_depth = max_depth, qcam.seed = seed;
+  qcam.background[0] = background[0], qcam.background[1] = background[1], qcam.background[2] = background[2];
+  RtiowParams P;
+  uint64_t unused_slots = 0;
+  {
+    int rcp = fill_rtiow_params(scene, &qcam, 0, 0, 1, 8, nullptr, false, P, unused_slots);
+    if (rcp != RL_OK) return rcp;
+  }
+  P.fg_root = QF.qroot, P.fg_rsafe2 = QF.r_safe * QF.r_safe * 0.9999f, P.fg_n_seg = (uint32_t)QF.stage_roots.size();
+  P.fg_center[0] = QF.center[0], P.fg_center[1] = QF.center[1], P.fg_center[2] = QF.center[2];
+  P.fg_radius = QF.radius, P.fg_pad_k = QF.pad_k;
+  P.q_rays = (const rl_ray *)d_rays, P.q_cursors = (const rl_rng_cursor *)d_cursors, P.q_rgb = (double *)d_rgb;
+  P.q_out_cursors = (rl_rng_cursor *)d_out_cursors, P.q_ray_counts = (uint32_t *)d_counts;
+  const bool fast = !counting && QF.ok && g_sw.fast_traversal;
+  const bool trans = rt.has_noise || rt.has_sphere_uv;
+  const bool fg_media = QF.stage_roots.size() > 1;
+  int nt = 512;
+  size_t lds = 0;
+  if (fast) {
+    if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
+    const int SD = (fg_media || trans) ? 40 : 20;
+    nt = (fg_media || trans) ? 512 : 768;
+    const size_t base = (size_t)nt * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));
+    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
+    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(QF.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
+    lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
+  } else {
+    lds = (size_t)512 * (16 + (rt.has_media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long);
+  }
+  uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));  // persistent lanes: as many workgroups as stay resident
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu * (uint32_t)nt > 2048) per_cu = 2048 / (uint32_t)nt;
+  rl_scene *ms = const_cast<rl_scene *>(scene);
+  auto blocks_of = [&](const void *kern, uint32_t &blocks) -> int {
+    blocks = (uint32_t)(((uint64_t)P.n_slots + nt - 1) / nt);
+    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
+    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;
+    if (ensure_lds_attr(kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    return RL_OK;
+  };
+  auto launch = [&](void (*kern)(RtiowParams)) -> int {
+    uint32_t blocks = 0;
+    int rcb = blocks_of((const void *)kern, blocks);
+    if (rcb != RL_OK) return rcb;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
+    HIP_TRY(hipGetLastError());
+    return RL_OK;
+  };
+  auto launch_ptr = [&](void (*kern)(const RtiowParams *)) -> int {  // by pointer: each pass its own stream-ordered copy (two slots)
+    uint32_t blocks = 0;
+    int rcb = blocks_of((const void *)kern, blocks);
+    if (rcb != RL_OK) return rcb;
+    if (!ms->d_params) HIP_TRY(hipMalloc((void **)&ms->d_params, 2 * sizeof(RtiowParams)));
+    RtiowParams *slot = (RtiowParams *)ms->d_params + (ms->params_slot++ & 1);
+    HIP_TRY(hipMemcpyAsync(slot, &P, sizeof(RtiowParams), hipMemcpyHostToDevice, stream));
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, (const RtiowParams *)slot);
+    HIP_TRY(hipGetLastError());
+    return RL_OK;
+  };
+  auto launch_pass = [&]() -> int {
+    if (fast) {
+      if (fg_media) return trans ? launch_ptr(rtiow_fast_general_rays_kernel<512, 40, true, true>) : launch_ptr(rtiow_fast_general_rays_kernel<512, 40, false, true>);
+      if (trans) return launch_ptr(rtiow_fast_general_rays_kernel<512, 40, true, false>);
+      return launch_ptr(rtiow_fast_general_rays_kernel<768, 20, false, false>);
+    }
+    if (rt.has_media) {
+      if (trans) return counting ? launch(rtiow_wave_general_rays_kernel<512, true, true, true>) : launch(rtiow_wave_general_rays_kernel<512, true, false, true>);
+      return counting ? launch(rtiow_wave_general_rays_kernel<512, false, true, true>) : launch(rtiow_wave_general_rays_kernel<512, false, false, true>);
+    }
+    if (trans) return counting ? launch(rtiow_wave_general_rays_kernel<512, true, true, false>) : launch(rtiow_wave_general_rays_kernel<512, true, false, false>);
+    return counting ? launch(rtiow_wave_general_rays_kernel<512, false, true, false>) : launch(rtiow_wave_general_rays_kernel<512, false, false, false>);
+  };
+  // rays per pass: below the u32 work counter's end, with room for every resident lane's last claim (which overshoots)
+  uint64_t per_pass = 0xFF000000ull;
+  if (g_query_pass_cap && g_query_pass_cap < per_pass) per_pass = g_query_pass_cap;
+  std::lock_guard<std::mutex> lk(scene->mu);  // queries and renders of one scene: see rl_scene::mu
+  int rc = query_begin(scene, stream, sync_st != nullptr);
+  if (rc != RL_OK) return rc;
+  for (uint64_t b = 0; b < n && rc == RL_OK; b += per_pass) {
+    P.q_first = b, P.n_slots = (uint32_t)std::min<uint64_t>(per_pass, n - b);
+    if (b != 0) HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 4, stream));  // work counter only; stats keep accumulating
+    rc = launch_pass();
+  }
+  if (rc != RL_OK) return rc;
+  g_last_query_kernel = fast ? 2 : 1;
+  rc = query_end(scene, stream, sync_st);
+  if (sync_st && (rc == RL_OK || rc == RL_E_DEGENERATE)) {  // (the stream is idle and the scene is still ours)
+    unsigned long long slow = 0;
+    if (hipMemcpy(&slow, scene->d_scratch + 64 + 56, 8, hipMemcpyDeviceToHost) == hipSuccess) g_last_query_retraced = slow;
+  }
+  return rc;
+}
+
+static int rtiow_ray_color_check(const rl_scene *scene, const void *rays, const void *cursors, uint64_t n, const double *background, const void *rgb,
+                                 rl_stats *st, bool &done) {
+  done = true;
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 1) return set_err(RL_E_INVALID, "not an RTIOW scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!rays || !cursors || !rgb || !background) return set_err(RL_E_INVALID, "null ray / cursor / background / output buffer");
+  if (n > (uint64_t)1 << 40) return set_err(RL_E_INVALID, "batch too large");
+  done = false;
+  return RL_OK;
+}
+
+int rl_rtiow_ray_color_rays_device(const rl_scene *scene, const void *d_rays, const void *d_cursors, uint64_t n, uint64_t seed, uint32_t max_depth,
+                                   const double background[3], void *d_out_rgb, void *d_opt_out_cursors, void *d_opt_out_ray_counts, void *hip_stream,
+                                   rl_stats *st) {
+  bool done;
+  int rc = rtiow_ray_color_check(scene, d_rays, d_cursors, n, background, d_out_rgb, st, done);
+  if (done) return rc;
+  return rtiow_ray_color_impl(scene, d_rays, d_cursors, n, seed, max_depth, background, d_out_rgb, d_opt_out_cursors, d_opt_out_ray_counts,
+                              (hipStream_t)hip_stream, st != nullptr, st);
+}
+
+int rl_rtiow_ray_color_rays(const rl_scene *scene, const rl_ray *rays, const rl_rng_cursor *cursors, uint64_t n, uint64_t seed, uint32_t max_depth,
+                            const double background[3], double *out_rgb, rl_rng_cursor *opt_out_cursors, uint32_t *opt_out_ray_counts, rl_stats *st) {
+  bool done;
+  int rc0 = rtiow_ray_color_check(scene, rays, cursors, n, background, out_rgb, st, done);
+  if (done) return rc0;
+  if ((rc0 = cursors_check(cursors, n)) != RL_OK) return rc0;
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * sizeof(rl_ray))) || (rc0 = q.alloc(1, n * sizeof(rl_rng_cursor))) || (rc0 = q.alloc(2, n * 24)) || (rc0 = q.alloc(3, n * 4))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], rays, n * sizeof(rl_ray), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(q.d[1], cursors, n * sizeof(rl_rng_cursor), hipMemcpyHostToDevice));
+  rl_stats local;  // without opt_stats the call is counter-free (the fast kernel where it applies); rays and flagged are still collected
+  int rc = rtiow_ray_color_impl(scene, q.d[0], q.d[1], n, seed, max_depth, background, q.d[2], opt_out_cursors ? q.d[1] : nullptr,
+                                opt_out_ray_counts ? q.d[3] : nullptr, g_ctx[(size_t)scene->ctx].stream, st != nullptr, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    HIP_TRY(hipMemcpy(out_rgb, q.d[2], n * 24, hipMemcpyDeviceToHost));
+    if (opt_out_cursors) HIP_TRY(hipMemcpy(opt_out_cursors, q.d[1], n * sizeof(rl_rng_cursor), hipMemcpyDeviceToHost));
+    if (opt_out_ray_counts) HIP_TRY(hipMemcpy(opt_out_ray_counts, q.d[3], n * 4, hipMemcpyDeviceToHost));
+    if (st) *st = local;
+  }
+  return rc;
+}
+
+static int camera_rays_check(const rl_rtiow_camera *cam, uint64_t n, const void *px, const void *py, const void *cursors, const void *rays, const void *out_cursors,
+                             bool &done) {
+  done = true;
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!cam) return set_err(RL_E_INVALID, "bad argument");
+  if (n == 0) return RL_OK;
+  if (!px || !py || !cursors || !rays || !out_cursors) return set_err(RL_E_INVALID, "null pixel / cursor / output buffer");
+  if (n > (uint64_t)1 << 40) return set_err(RL_E_INVALID, "batch too large");
+  done = false;
+  return RL_OK;
+}
+
+static int camera_rays_launch(const rl_rtiow_camera *cam, uint64_t n, const void *d_px, const void *d_py, const void *d_cursors, void *d_rays,
+                              void *d_out_cursors, hipStream_t stream) {
+  CameraRaysQuery Q{};
+  Q.cam = *cam;
+  chacha_key_from_seed(cam->seed, Q.key);
+  Q.px = (const uint32_t *)d_px, Q.py = (const uint32_t *)d_py, Q.cursors = (const rl_rng_cursor *)d_cursors;
+  Q.rays = (rl_ray *)d_rays, Q.out_cursors = (rl_rng_cursor *)d_out_cursors, Q.n = n;
+  const uint64_t want = (n + QNT - 1) / QNT, cap = (uint64_t)std::max(1, g_cus) * 8u;
+  hipLaunchKernelGGL((rtiow_camera_rays_kernel<QNT>), dim3((uint32_t)std::min(want, cap)), dim3(QNT), 0, stream, Q);
+  HIP_TRY(hipGetLastError());
+  return RL_OK;
+}
+
+int rl_rtiow_camera_rays_device(const rl_rtiow_camera *cam, uint64_t n, const void *d_px, const void *d_py, const void *d_cursors, void *d_out_rays,
+                                void *d_out_cursors, void *hip_stream) {
+  bool done;
+  int rc = camera_rays_check(cam, n, d_px, d_py, d_cursors, d_out_rays, d_out_cursors, done);
+  if (done) return rc;
+  return camera_rays_launch(cam, n, d_px, d_py, d_cursors, d_out_rays, d_out_cursors, (hipStream_t)hip_stream);
+}
+
+int rl_rtiow_camera_rays(const rl_rtiow_camera *cam, uint64_t n, const uint32_t *px, const uint32_t *py, const rl_rng_cursor *cursors, rl_ray *out_rays,
+                         rl_rng_cursor *out_cursors) {
+  bool done;
+  int rc = camera_rays_check(cam, n, px, py, cursors, out_rays, out_cursors, done);
+  if (done) return rc;
+  for (uint64_t i = 0; i < n; i++)
+    if (px[i] >= cam->image_width || py[i] >= cam->image_height) return set_err(RL_E_INVALID, "pixel outside the image");
+  if ((rc = cursors_check(cursors, n)) != RL_OK) return rc;
+  if ((rc = rl::use_context(0)) != RL_OK) return rc;
+  hipStream_t stream = g_ctx[0].stream;
+  QueryStage q;
+  void *d_xy = nullptr;
+  if ((rc = q.alloc(0, n * 8)) || (rc = q.alloc(1, n * sizeof(rl_rng_cursor))) || (rc = q.alloc(2, n * sizeof(rl_ray)))) return rc;
+  d_xy = q.d[0];
+  HIP_TRY(hipMemcpy(d_xy, px, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy((unsigned char *)d_xy + n * 4, py, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(q.d[1], cursors, n * sizeof(rl_rng_cursor), hipMemcpyHostToDevice));
+  if ((rc = camera_rays_launch(cam, n, d_xy, (unsigned char *)d_xy + n * 4, q.d[1], q.d[2], q.d[1], stream)) != RL_OK) return rc;
+  HIP_TRY(hipStreamSynchronize(stream));
+  HIP_TRY(hipMemcpy(out_rays, q.d[2], n * sizeof(rl_ray), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(out_cursors, q.d[1], n * sizeof(rl_rng_cursor), hipMemcpyDeviceToHost));
+  return RL_OK;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-  // The body of rtiow_fast_general_kernel / rtiow_fast_general_indep_kernel (rl_rtiow_fastgen.h): included inside both kernels, with INDEP (and the
-  // kernel's template parameters) in scope.
+  // The body of rtiow_fast_general_kernel / rtiow_fast_general_indep_kernel / rtiow_fast_general_rays_kernel (rl_rtiow_fastgen.h): included inside
+  // all three, with INDEP, RAYS (and the kernel's template parameters) in scope.
   // the parameter block is read from memory where it is needed (uniform addresses: scalar loads through the constant cache) instead of
   // arriving by value: by value every field that is live anywhere is loaded at kernel entry and pins SGPRs for the kernel's life time
   const RtiowParams &P = *Pp;
@@ -23,10 +23,11 @@
   const double INF = __longlong_as_double(0x7FF0000000000000ll);
   const float FINF = __int_as_float(0x7F800000);
 
-  Ring<NT> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
+  Ring<NT, true, RAYS> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
   uint32_t state = ST_GEN;
   uint32_t px = 0, pr = 0, n = spp;
   uint32_t n_end = spp;  // INDEP: end of the lane's sample group
+  uint64_t q_idx = 0;    // RAYS: the lane's ray
   uint32_t ptile = 0, pix_rays = 0;
   bool have_pixel = false;
   D3 sum = d3(0.0, 0.0, 0.0);
@@ -384,6 +385,32 @@
       if (state == ST_FILL) {
         rng.top_up();
         state = ST_SHADE;
+      }
+    } else if (RAYS && pick == ST_GEN) {  // a work item is one ray of the caller's batch with its own cursor, not a (pixel, sample) pair
+      if (state == ST_GEN) {
+        if (have_pixel) {  // the path is done: colour, cursor and ray count to the ray's own index
+          rtiow_rays_store(P, q_idx, sum, rng.stream, rng.pos, pix_rays);
+          have_pixel = false;
+        }
+        const uint32_t slot = wave_claim(P.work_counter);
+        if (slot >= P.n_slots) state = ST_DONE;
+        else {
+          q_idx = P.q_first + slot;
+          have_pixel = true;
+          const rl_ray &ray = P.q_rays[q_idx];
+          const uint64_t *cur = (const uint64_t *)(P.q_cursors + q_idx);
+          wo = ld3(ray.origin), wd = ld3(ray.dir), time = ray.time;
+          rng.pos = (uint32_t)cur[1], rng.nres = 0;
+          rng.reset_stream(cur[0]);
+          sum = d3(0.0, 0.0, 0.0), thr = d3(1.0, 1.0, 1.0);
+          pix_rays = 0;
+          depth = cam.max_depth;
+          if (depth != 0) {  // (max_depth 0: black, no ray, the cursor as it came — stored at the lane's next GEN visit)
+            c_rays++;
+            pix_rays++;
+            start_ray();
+          }
+        }
       }
     } else if (pick == ST_GEN) {
       if (state == ST_GEN) {

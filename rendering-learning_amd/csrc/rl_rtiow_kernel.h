@@ -85,7 +85,26 @@ struct RtiowParams {
   uint32_t indep_k, indep_tile_slots;
   // fast traversal (LDS_SCENE = 4): per-pixel entry words of this render's camera rays, [nrows * W] (rl_pixel_entry.h); null: every ray starts at fast_root
   const uint32_t *pixel_entry;
+  // ray-buffer mode (RAYS instantiations, rl_rtiow_ray_color_rays*): a slot is one ray of the caller's batch, q_first + slot its index.
+  // cam holds what the call gives instead of a camera: background and max_depth; key is expanded from the call's seed.
+  const rl_ray *q_rays;
+  const rl_rng_cursor *q_cursors;
+  double *q_rgb;                  // [n][3]
+  rl_rng_cursor *q_out_cursors;   // [n] or null
+  uint32_t *q_ray_counts;         // [n] or null
+  uint64_t q_first;
 };
+
+// RAYS: the path's colour, the cursor behind it and its ray count to the ray's own index
+__device__ __forceinline__ void rtiow_rays_store(const RtiowParams &P, uint64_t idx, const D3 &c, uint64_t stream, uint32_t pos, uint32_t rays) {
+  double *b = P.q_rgb + idx * 3;
+  b[0] = c.x, b[1] = c.y, b[2] = c.z;
+  if (P.q_out_cursors) {
+    uint64_t *q = (uint64_t *)(P.q_out_cursors + idx);
+    q[0] = stream, q[1] = (uint64_t)pos;
+  }
+  if (P.q_ray_counts) P.q_ray_counts[idx] = rays;
+}
 
 // INDEP: the colour of sample `rel` (relative to the pass's sample_begin) of shard pixel (pr, px) into the pass buffer
 __device__ __forceinline__ void rtiow_indep_store(const RtiowParams &P, uint32_t rel, uint32_t pr, uint32_t px, const D3 &c) {

@@ -51,7 +51,10 @@ static constexpr bool LATENCY_MODES = false;
 // two-block ChaCha ring in LDS: 16 u64 slots per lane, slot-major ([slot][lane]) => conflict-free
 // ROLL_HOT: also the block generations on the hot paths (stream reset, FILL) use the rolled block function (rl_rtiow_kernel.h
 // chacha8_block_to_lds<NT, true>); the refill in the middle of a SHADE block (rare: long rejection streaks) always does.
-template <int NT, bool ROLL_HOT = true>
+// ODD (the ray-buffer kernels, rl_rng_cursor): the word position may be odd — a caller's cursor may stand anywhere in the stream, and a
+// draw is words pos, pos + 1 (rand_core BlockRng::next_u64), so an odd position reads the halves of two neighbouring u64 slots, the
+// second one possibly in the next block.  A render's positions are always even: its kernels keep the plain form.
+template <int NT, bool ROLL_HOT = true, bool ODD = false>
 struct Ring {
   const uint32_t *key;
   unsigned long long *s_rng;  // [16][NT]
@@ -69,7 +72,10 @@ struct Ring {
     for (uint32_t k = 0; k < 2u; k++) gen_block(blk_lo + k);  // (rolled: one copy of the block function's 2 KB, not two)
     nres = 2;
   }
-  __device__ __forceinline__ bool low() const { return (pos >> 4) >= blk_lo + nres - 1u; }  // reading from the newest block
+  __device__ __forceinline__ bool low() const {  // reading from the newest block
+    if (ODD) return ((pos + (pos & 1u)) >> 4) >= blk_lo + nres - 1u;  // (the draw's second word counts)
+    return (pos >> 4) >= blk_lo + nres - 1u;
+  }
   __device__ __forceinline__ void top_up() {  // make block (newest+1) resident, dropping the oldest
     uint32_t c = blk_lo + nres;
     gen_block(c);
@@ -125,6 +131,7 @@ struct Ring {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   __device__ __forceinline__ uint64_t next_u64() {
+    if (ODD) return next_u64_any();
     uint32_t c = pos >> 4;
     if (__builtin_expect(c - blk_lo >= nres, 0)) {  // rare inline path (long rejection streaks): always the rolled block function, a quarter of the code per call site
       const uint32_t nc = blk_lo + nres;
@@ -133,6 +140,22 @@ struct Ring {
       else nres++;
     }
     uint64_t v = s_rng[((size_t)(c & 1u) * 8 + ((pos & 15u) >> 1)) * NT + tid];
+    pos += 2;
+    return v;
+  }
+  // ODD: words pos, pos + 1 from any position.  An odd one takes the high half of its u64 slot and the low half of the next slot,
+  // which may lie in the next block: residency is checked for the block of the draw's SECOND word (the first one's is resident).
+  __device__ __forceinline__ uint64_t next_u64_any() {
+    const uint32_t p1 = pos + (pos & 1u);
+    const uint32_t c = p1 >> 4;
+    if (__builtin_expect(c - blk_lo >= nres, 0)) {
+      const uint32_t nc = blk_lo + nres;
+      chacha8_block_to_lds<NT, true>(key, nc, stream, s_rng + (size_t)(nc & 1u) * 8 * NT, tid);
+      if (nres == 2) blk_lo++;
+      else nres++;
+    }
+    uint64_t v = s_rng[((size_t)((pos >> 4) & 1u) * 8 + ((pos & 15u) >> 1)) * NT + tid];
+    if (pos & 1u) v = (v >> 32) | (s_rng[((size_t)(c & 1u) * 8 + ((p1 & 15u) >> 1)) * NT + tid] << 32);
     pos += 2;
     return v;
   }

@@ -28,12 +28,19 @@ static const int MEDIA_SAVE_WORDS = 12;  // parked Rec: t, p, normal, u, v, w, {
 // INDEP: the sample-parallel mode, as in rtiow_wave_indep_kernel (rl_rtiow_wave.h; the body is included into both kernels for the same reason); rng_words are counted at every sample end
 template <int NT, bool TRANS, bool STATS, bool MEDIA = false>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_kernel(RtiowParams P) {
-  constexpr bool INDEP = false;
+  constexpr bool INDEP = false, RAYS = false;
 #include "rl_rtiow_wave_general_body.inc"
 }
 template <int NT, bool TRANS, bool STATS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_indep_kernel(RtiowParams P) {
-  constexpr bool INDEP = true;
+  constexpr bool INDEP = true, RAYS = false;
+#include "rl_rtiow_wave_general_body.inc"
+}
+// RAYS (rl_rtiow_ray_color_rays*): the reference-order form of the ray-buffer path query — counting calls, scenes without a
+// fast tree, RL_FAST=0.  A slot is one ray with its own RNG cursor; rng_words counts the words each path consumed.
+template <int NT, bool TRANS, bool STATS, bool MEDIA>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_rays_kernel(RtiowParams P) {
+  constexpr bool INDEP = false, RAYS = true;
 #include "rl_rtiow_wave_general_body.inc"
 }
 

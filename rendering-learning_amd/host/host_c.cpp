@@ -494,6 +494,27 @@ int rlh_ray_query_probe(int which, const rl_ray *rays, uint64_t n, double tmin, 
     return -1;
   }
 }
+// Seeded path queries through the C++ mirror on golden_test_scene and its camera.  which = 0: Camera::get_rays for pixels (i % W, 0),
+// out = n rl_ray; which = 1: rtiow::ray_color_rays of `rays`, out = n * 3 doubles.  cursors are advanced in place.  0 or -1 (rlh_last_error).
+int rlh_path_query_probe(int which, const rl_ray *rays, rl_rng_cursor *cursors, uint64_t n, void *out) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    if (which == 0) {
+      rtiow::Camera cam(s.params);
+      std::vector<uint32_t> px((size_t)n), py((size_t)n, 0u);
+      for (size_t i = 0; i < (size_t)n; i++) px[i] = (uint32_t)(i % s.params.image_width);
+      std::vector<rl_ray> r = cam.get_rays(px.data(), py.data(), cursors, (size_t)n);
+      std::memcpy(out, r.data(), r.size() * sizeof(rl_ray));
+    } else {
+      std::vector<double> c = rtiow::ray_color_rays(*s.world, rays, cursors, (size_t)n, s.params.seed, s.params.max_depth, s.params.background);
+      std::memcpy(out, c.data(), c.size() * sizeof(double));
+    }
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // tests/ray_tracer.rs:242-275 (which = 0, needs the OBJ text), :56-240 mirror (1), :277-368 csg (2): Camera::render -> Canvas::ppm
 char *rlh_rtc_run_golden_test(int which, const char *obj_text, uint64_t obj_len, uint64_t *len) {
   try {

@@ -55,6 +55,28 @@ std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t 
   if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_hit_rays: ") + rl_last_error());
   return out;
 }
+std::vector<double> ray_color_rays(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed, size_t max_depth,
+                                   const Color &background, std::vector<uint32_t> *ray_counts) {  // camera.rs:232-260
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  std::vector<double> out(n * 3);
+  if (ray_counts) ray_counts->assign(n, 0u);
+  const double bg[3] = {background.x(), background.y(), background.z()};
+  int rc = rl_rtiow_ray_color_rays(sc, rays, cursors, n, seed, (uint32_t)max_depth, bg, out.data(), cursors, ray_counts ? ray_counts->data() : nullptr, nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_ray_color_rays: ") + rl_last_error());
+  return out;
+}
+std::vector<rl_ray> Camera::get_rays(const uint32_t *px, const uint32_t *py, rl_rng_cursor *cursors, size_t n) const {  // camera.rs:203-216
+  rl_rtiow_camera cam = derived();
+  std::vector<rl_ray> out(n);
+  int rc = rl_rtiow_camera_rays(&cam, n, px, py, cursors, out.data(), cursors);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_camera_rays: ") + rl_last_error());
+  return out;
+}
 Canvas Camera::render(const Hittable &world) const { return render_internal(0, world); }  // camera.rs:122
 Canvas Camera::render_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {  // camera.rs:136-143
   return render_internal(checkpoint.samples, world).merge(checkpoint);

@@ -675,6 +675,12 @@ struct DeviceBvh : Hittable {
 // world.hit(&rays[i], &ray_t), out[i].hit == 0 for None.  Throws on any error but RL_E_DEGENERATE (host_render.cpp).
 std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t n, Interval ray_t);
 
+// Camera::ray_color(&mut rng, &ray, world, depth) (camera.rs:232-260) for a batch of rays, on the GPU (rl_rtiow_ray_color_rays): rng_i is
+// ChaCha8Rng::seed_from_u64(seed) after set_stream(cursors[i].stream) at word cursors[i].word_pos; cursors[i] is advanced behind the path.
+// Returns n * 3 colour values; ray_counts (optional) receives the rays traced per path.  Throws on any error but RL_E_DEGENERATE.
+std::vector<double> ray_color_rays(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed, size_t max_depth,
+                                   const Color &background, std::vector<uint32_t> *ray_counts = nullptr);
+
 struct CameraParams {  // camera.rs:23-59 (defaults as in the reference)
   double aspect_ratio = 1.0;
   size_t image_width = 100;
@@ -778,6 +784,10 @@ struct Camera {
   // its sums (bit for bit samples_per_pixel repetitions of render_from_checkpoint with one sample per pixel)
   Canvas render_independent(const Hittable &world) const;
   Canvas render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const;
+  // Camera::get_ray(&mut rng, x, y) (camera.rs:203-216) for a batch of pixels, on the GPU (rl_rtiow_camera_rays): rng_i as for
+  // ray_color_rays with seed = params.seed; cursors[i] is advanced behind the draws.  _render's stream of sample s at pixel (x, y) is
+  // s * W * H + x * W + y (camera.rs:161-170).
+  std::vector<rl_ray> get_rays(const uint32_t *px, const uint32_t *py, rl_rng_cursor *cursors, size_t n) const;
 };
 
 // ---------------------------------------------------------------- color.rs / output.rs
