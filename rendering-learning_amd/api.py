@@ -368,6 +368,17 @@ def has_experimental():
     return bool(render_lib().rl_debug_has_experimental())
 
 
+def live_buffers():
+    """Tests: (count, bytes) of the device allocations the library owns right now (rl_debug_live_buffers): scenes' buffers and work
+    buffers; the staging of a host-buffer call is gone again when the call returns."""
+    out = (C.c_ulonglong * 2)()
+    L = render_lib()
+    L.rl_debug_live_buffers.argtypes = [C.c_void_p]
+    L.rl_debug_live_buffers.restype = None
+    L.rl_debug_live_buffers(out)
+    return int(out[0]), int(out[1])
+
+
 def _check(rc, allow_degenerate=False):
     if rc == RL_OK or (allow_degenerate and rc == RL_E_DEGENERATE):
         return rc

@@ -18,21 +18,14 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/rl_render.h"
-
-namespace rl {
-int set_err_public(int code, const std::string &m);  // rl_render.hip
-}
+#include "rl_devbuf.h"
 
 namespace {
 
-#define BVH_TRY(expr)                                                                                   \
-  do {                                                                                                  \
-    hipError_t e_ = (expr);                                                                             \
-    if (e_ != hipSuccess) {                                                                             \
-      rc = rl::set_err_public(RL_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-      goto done;                                                                                        \
-    }                                                                                                   \
+#define BVH_TRY(expr)                                                                                               \
+  do {                                                                                                              \
+    hipError_t e_ = (expr);                                                                                         \
+    if (e_ != hipSuccess) return rl::set_err_public(RL_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
 __device__ __forceinline__ unsigned long long total_order_key(double v) {  // ascending u64 == f64::total_cmp
@@ -99,29 +92,22 @@ uint32_t count_nodes(uint32_t n, std::unordered_map<uint32_t, uint32_t> &memo) {
 namespace rl {
 // Cost-sorted launch order of rl_rtiow_render_device, on the device: order = tile ids sorted by cost, most expensive first,
 // ties in ascending tile id (what std::stable_sort(order, cost[a] > cost[b]) gives).  keys_tmp / order_in: n u32 each;
-// *temp / *temp_bytes: scratch owned by the caller, grown on demand.  Asynchronous on `stream`.
+// temp: scratch owned by the caller, grown on demand.  Asynchronous on `stream`.
 __global__ void iota_u32(uint32_t *p, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = i;
 }
-int sort_tiles_by_cost_desc(const uint32_t *d_cost, uint32_t *d_keys_tmp, uint32_t *d_order_in, uint32_t *d_order_out, uint32_t n, void **temp, size_t *temp_bytes,
+int sort_tiles_by_cost_desc(const uint32_t *d_cost, uint32_t *d_keys_tmp, uint32_t *d_order_in, uint32_t *d_order_out, uint32_t n, DevBuf<unsigned char> &temp,
                             hipStream_t stream) {
   hipLaunchKernelGGL(iota_u32, dim3((n + 255) / 256), dim3(256), 0, stream, d_order_in, n);
   size_t need = 0;
   hipError_t e = hipcub::DeviceRadixSort::SortPairsDescending(nullptr, need, d_cost, d_keys_tmp, d_order_in, d_order_out, (int)n, 0, 32, stream);
   if (e != hipSuccess) return set_err_public(RL_E_DEVICE, std::string("tile sort (size query): ") + hipGetErrorString(e));
-  if (need > *temp_bytes) {
-    if (*temp) {
-      hipStreamSynchronize(stream);  // an earlier sort on this stream may still use the old buffer
-      hipFree(*temp);
-    }
-    *temp = nullptr, *temp_bytes = 0;
-    e = hipMalloc(temp, need);
-    if (e != hipSuccess) return set_err_public(RL_E_DEVICE, std::string("tile sort (temp storage): ") + hipGetErrorString(e));
-    *temp_bytes = need;
-  }
-  need = *temp_bytes;
-  e = hipcub::DeviceRadixSort::SortPairsDescending(*temp, need, d_cost, d_keys_tmp, d_order_in, d_order_out, (int)n, 0, 32, stream);
+  if (temp && need > temp.size()) hipStreamSynchronize(stream);  // an earlier sort on this stream may still use the old buffer
+  e = temp.reserve(need);
+  if (e != hipSuccess) return set_err_public(RL_E_DEVICE, std::string("tile sort (temp storage): ") + hipGetErrorString(e));
+  need = temp.size();
+  e = hipcub::DeviceRadixSort::SortPairsDescending(temp.get(), need, d_cost, d_keys_tmp, d_order_in, d_order_out, (int)n, 0, 32, stream);
   if (e != hipSuccess) return set_err_public(RL_E_DEVICE, std::string("tile sort: ") + hipGetErrorString(e));
   return RL_OK;
 }
@@ -137,14 +123,12 @@ extern "C" int rl_bvh_build(const double *prim_boxes, const rl_href *prims, uint
   if (out_n_nodes) *out_n_nodes = total_nodes;
   if (cap < total_nodes) return rl::set_err_public(RL_E_INVALID, "rl_bvh_build: output capacity too small");
 
-  int rc = RL_OK;
-  double *d_boxes = nullptr, *d_seg_box = nullptr;
-  uint32_t *d_idx[2] = {nullptr, nullptr}, *d_seg_axis = nullptr;
-  unsigned long long *d_keys[2] = {nullptr, nullptr};
-  Seg *d_segs = nullptr;
-  int *d_beg = nullptr, *d_end = nullptr;
-  void *d_temp = nullptr;
-  size_t temp_bytes = 0;
+  rl::DevBuf<double> d_boxes, d_seg_box;
+  rl::DevBuf<uint32_t> d_idx[2], d_seg_axis;
+  rl::DevBuf<unsigned long long> d_keys[2];
+  rl::DevBuf<Seg> d_segs;
+  rl::DevBuf<int> d_beg, d_end;
+  rl::DevBuf<unsigned char> d_temp;
   struct Open {
     uint32_t start, len, node;  // node = index in the output (recursion order)
   };
@@ -171,23 +155,23 @@ extern "C" int rl_bvh_build(const double *prim_boxes, const rl_href *prims, uint
     out_nodes[o.node] = nd;
   };
 
-  BVH_TRY(hipMalloc((void **)&d_boxes, (size_t)n * 6 * sizeof(double)));
+  BVH_TRY(d_boxes.reserve((size_t)n * 6));
   BVH_TRY(hipMemcpy(d_boxes, prim_boxes, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice));
   for (int k = 0; k < 2; k++) {
-    BVH_TRY(hipMalloc((void **)&d_idx[k], (size_t)n * sizeof(uint32_t)));
-    BVH_TRY(hipMalloc((void **)&d_keys[k], (size_t)n * sizeof(unsigned long long)));
+    BVH_TRY(d_idx[k].reserve(n));
+    BVH_TRY(d_keys[k].reserve(n));
   }
-  BVH_TRY(hipMalloc((void **)&d_segs, max_segs * sizeof(Seg)));
-  BVH_TRY(hipMalloc((void **)&d_beg, max_segs * sizeof(int)));
-  BVH_TRY(hipMalloc((void **)&d_end, max_segs * sizeof(int)));
-  BVH_TRY(hipMalloc((void **)&d_seg_axis, max_segs * sizeof(uint32_t)));
-  BVH_TRY(hipMalloc((void **)&d_seg_box, max_segs * 6 * sizeof(double)));
+  BVH_TRY(d_segs.reserve(max_segs));
+  BVH_TRY(d_beg.reserve(max_segs));
+  BVH_TRY(d_end.reserve(max_segs));
+  BVH_TRY(d_seg_axis.reserve(max_segs));
+  BVH_TRY(d_seg_box.reserve(max_segs * 6));
   for (uint32_t i = 0; i < n; i++) order[i] = i;
   BVH_TRY(hipMemcpy(d_idx[0], order.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice));
 
   if (n <= 2) {
     leaf(Open{0, n, 0});
-    goto done;
+    return RL_OK;
   }
   open.push_back(Open{0, n, 0});
   while (!open.empty()) {
@@ -204,14 +188,9 @@ extern "C" int rl_bvh_build(const double *prim_boxes, const rl_href *prims, uint
     BVH_TRY(hipMemcpyAsync(d_idx[cur ^ 1], d_idx[cur], (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToDevice, 0));
     {
       size_t need = 0;
-      BVH_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, need, d_keys[0], d_keys[1], d_idx[cur], d_idx[cur ^ 1], (int)n, (int)ns, d_beg, d_end, 0, 64, 0));
-      if (need > temp_bytes) {
-        hipFree(d_temp);
-        d_temp = nullptr;
-        BVH_TRY(hipMalloc(&d_temp, need));
-        temp_bytes = need;
-      }
-      BVH_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(d_temp, need, d_keys[0], d_keys[1], d_idx[cur], d_idx[cur ^ 1], (int)n, (int)ns, d_beg, d_end, 0, 64, 0));
+      BVH_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(nullptr, need, d_keys[0].get(), d_keys[1].get(), d_idx[cur].get(), d_idx[cur ^ 1].get(), (int)n, (int)ns, d_beg.get(), d_end.get(), 0, 64, 0));
+      BVH_TRY(d_temp.reserve(need));
+      BVH_TRY(hipcub::DeviceSegmentedRadixSort::SortPairs(d_temp.get(), need, d_keys[0].get(), d_keys[1].get(), d_idx[cur].get(), d_idx[cur ^ 1].get(), (int)n, (int)ns, d_beg.get(), d_end.get(), 0, 64, 0));
     }
     cur ^= 1;
     seg_box.resize(ns * 6);
@@ -239,8 +218,5 @@ extern "C" int rl_bvh_build(const double *prim_boxes, const rl_href *prims, uint
       else open.push_back(o);
     }
   }
-done:
-  hipFree(d_boxes), hipFree(d_seg_box), hipFree(d_idx[0]), hipFree(d_idx[1]), hipFree(d_seg_axis), hipFree(d_keys[0]), hipFree(d_keys[1]);
-  hipFree(d_segs), hipFree(d_beg), hipFree(d_end), hipFree(d_temp);
-  return rc;
+  return RL_OK;
 }

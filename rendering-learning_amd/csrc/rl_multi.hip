@@ -150,17 +150,10 @@ int render_multi(const rl_scene *scene, uint32_t W, uint32_t H, void *d_out0, rl
   // buffers: every replica owns its shard; replica 0's holds the whole gather [G][max_rows][W][3] (slot 0 = its own rows)
   for (int g = 0; g < G; g++) {
     rl_scene *r = scene->replicas[(size_t)g];
-    size_t need = (size_t)(g == 0 ? (uint64_t)G * slot_vals : slot_vals) * sizeof(double);
+    size_t need = (size_t)(g == 0 ? (uint64_t)G * slot_vals : slot_vals);
     if ((rc = use_context(g)) != RL_OK) return rc;
-    if (r->shard_bytes < need) {
-      if (r->d_shard) {
-        HIP_TRY(hipStreamSynchronize(context(g).stream));
-        hipFree(r->d_shard);
-      }
-      r->d_shard = nullptr, r->shard_bytes = 0;
-      HIP_TRY(hipMalloc((void **)&r->d_shard, need));
-      r->shard_bytes = need;
-    }
+    if (r->d_shard && r->d_shard.size() < need) HIP_TRY(hipStreamSynchronize(context(g).stream));  // an earlier frame may still use the old buffer
+    HIP_TRY(r->d_shard.reserve(need));
   }
   // back-to-back asynchronous frames: the previous frame's de-interleave (stream 0) still reads the gather slots that this frame's
   // peer copies (stream g) will overwrite, and nothing else orders stream g behind it
@@ -206,7 +199,7 @@ int render_multi(const rl_scene *scene, uint32_t W, uint32_t H, void *d_out0, rl
   hipLaunchKernelGGL(deinterleave_rows, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, context(0).stream, root->d_shard, (double *)d_out0, H, (uint32_t)row_vals,
                      (uint32_t)G, slot_vals);
   HIP_TRY(hipGetLastError());
-  if (!root->ev_gather_read) HIP_TRY(hipEventCreateWithFlags(&root->ev_gather_read, hipEventDisableTiming));
+  HIP_TRY(root->ev_gather_read.create(hipEventDisableTiming));
   HIP_TRY(hipEventRecord(root->ev_gather_read, context(0).stream));
   root->ev_gather_read_valid = true;
   if (!st) return post_status_multi(scene, H);
@@ -313,15 +306,14 @@ int rl_rtiow_render_multi(const rl_scene *scene, const rl_rtiow_camera *cam, uin
   if (bytes == 0) return set_err_public(RL_E_INVALID, "empty image");
   int rc = use_context(0);
   if (rc != RL_OK) return rc;
-  double *d_out = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_out, bytes));
+  DevBuf<double> d_out;
+  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
   rl_stats local;
   rc = rl_rtiow_render_multi_device(scene, cam, first_sample, d_out, &local);
   if (rc == RL_OK || rc == RL_E_DEGENERATE) {
     hipError_t e = hipMemcpy(out_rgb_sum, d_out, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err_public(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
   }
-  hipFree(d_out);
   if (st) *st = local;
   return rc;
 }
@@ -343,15 +335,14 @@ int rl_rtc_render_multi(const rl_scene *scene, const rl_rtc_camera *cam, uint32_
   if (bytes == 0) return set_err_public(RL_E_INVALID, "empty image");
   int rc = use_context(0);
   if (rc != RL_OK) return rc;
-  double *d_out = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_out, bytes));
+  DevBuf<double> d_out;
+  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
   rl_stats local;
   rc = rl_rtc_render_multi_device(scene, cam, aa, d_out, &local);
   if (rc == RL_OK || rc == RL_E_DEGENERATE) {
     hipError_t e = hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err_public(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
   }
-  hipFree(d_out);
   if (st) *st = local;
   return rc;
 }

@@ -140,15 +140,6 @@ int set_err(int code, const std::string &m) {
     if (e_ != hipSuccess) return set_err(RL_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
   } while (0)
 
-template <class T>
-int upload(const std::vector<T> &v, T **out) {
-  *out = nullptr;
-  size_t bytes = (v.size() ? v.size() : 1) * sizeof(T);
-  HIP_TRY(hipMalloc((void **)out, bytes));
-  if (!v.empty()) HIP_TRY(hipMemcpy(*out, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return RL_OK;
-}
-
 __global__ void iota_u32(uint32_t *out, uint32_t n) {
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) out[i] = i;
@@ -226,7 +217,7 @@ int set_contexts(const std::vector<int> &devices) {
   if (!g_ctx.empty()) hipSetDevice(g_ctx[0].device);
   return RL_OK;
 }
-int sort_tiles_by_cost_desc(const uint32_t *d_cost, uint32_t *d_keys_tmp, uint32_t *d_order_in, uint32_t *d_order_out, uint32_t n, void **temp, size_t *temp_bytes,
+int sort_tiles_by_cost_desc(const uint32_t *d_cost, uint32_t *d_keys_tmp, uint32_t *d_order_in, uint32_t *d_order_out, uint32_t n, DevBuf<unsigned char> &temp,
                             hipStream_t stream);  // rl_bvh_build.hip (hipCUB)
 void add_stats(rl_stats *acc, const rl_stats &s) {
   acc->rays += s.rays, acc->node_tests += s.node_tests, acc->sphere_tests += s.sphere_tests, acc->planar_tests += s.planar_tests;
@@ -234,16 +225,6 @@ void add_stats(rl_stats *acc, const rl_stats &s) {
   acc->kernel_ms = std::max(acc->kernel_ms, s.kernel_ms);
 }
 }  // namespace rl
-
-#ifdef RL_EXPERIMENTAL
-struct ExpBuffers {  // wavefront (v3) buffers: per-pixel state, ray and hit records, queues, control words
-  PixState *wf_pix = nullptr;
-  RayRec *wf_ray = nullptr;
-  HitRec *wf_hit = nullptr;
-  uint32_t *wf_qtrav = nullptr, *wf_qshade = nullptr, *wf_qgen = nullptr, *wf_ctl = nullptr;
-  size_t wf_npix = 0;
-};
-#endif
 
 extern "C" {
 
@@ -286,28 +267,6 @@ int rl_device_info(char *name, int cap) {
 
 static void destroy_one(rl_scene *s) {
   if ((size_t)s->ctx < g_ctx.size()) hipSetDevice(g_ctx[(size_t)s->ctx].device);
-  hipFree(s->d_ops), hipFree(s->d_lops), hipFree(s->d_sphere_flat), hipFree(s->d_cops), hipFree(s->d_movbits), hipFree(s->d_spheres), hipFree(s->d_sphere_material), hipFree(s->d_planars), hipFree(s->d_translates);
-  hipFree(s->d_transforms), hipFree(s->d_materials), hipFree(s->d_textures), hipFree(s->d_images), hipFree(s->d_image_pool), hipFree(s->d_perlins), hipFree(s->d_media);
-  hipFree(s->d_tris), hipFree(s->d_xforms), hipFree(s->d_rmaterials), hipFree(s->d_lights), hipFree(s->d_scratch);
-  hipFree(s->d_pos), hipFree(s->d_tile_cost), hipFree(s->d_tile_order), hipFree(s->d_tile_keys), hipFree(s->d_tile_iota), hipFree(s->d_sort_temp), hipFree(s->d_pixel_entry);
-  hipFree(s->d_shapes), hipFree(s->d_csgs), hipFree(s->d_patterns), hipFree(s->d_guards), hipFree(s->d_shard), hipFree(s->d_pix_rays), hipFree(s->d_fast_nodes), hipFree(s->d_fast_leaf_boxes), hipFree(s->d_coop_pixels), hipFree(s->d_steal_state), hipFree(s->d_steal_n), hipFree(s->d_fg_nodes), hipFree(s->d_fg_onodes), hipFree(s->d_fg_seg_roots), hipFree(s->d_fg_media), hipFree(s->d_fg_items), hipFree(s->d_fg_spheres), hipFree(s->d_fg_material);
-#ifdef RL_EXPERIMENTAL
-  if (ExpBuffers *E = (ExpBuffers *)s->exp) {
-    hipFree(E->wf_pix), hipFree(E->wf_ray), hipFree(E->wf_hit), hipFree(E->wf_qtrav), hipFree(E->wf_qshade), hipFree(E->wf_qgen), hipFree(E->wf_ctl);
-    delete E;
-  }
-#endif
-  if (s->h_status) hipHostFree(s->h_status);
-  for (hipEvent_t e : s->ev_status)
-    if (e) hipEventDestroy(e);
-  if (s->ev_last) hipEventDestroy(s->ev_last);
-  if (s->h_progress) hipHostFree(s->h_progress);
-  if (s->ev0) hipEventDestroy(s->ev0);
-  if (s->ev1) hipEventDestroy(s->ev1);
-  if (s->ev_gather_read) hipEventDestroy(s->ev_gather_read);
-  hipFree(s->d_params), hipFree(s->d_indep);
-  hipFree(s->d_wfg_pix), hipFree(s->d_wfg_ray), hipFree(s->d_wfg_q0), hipFree(s->d_wfg_q1), hipFree(s->d_wfg_qs), hipFree(s->d_wfg_ctl);
-  if (s->h_wfg) hipHostFree(s->h_wfg);
   delete s;
 }
 
@@ -319,13 +278,13 @@ void rl_scene_destroy(rl_scene *s) {
 }
 
 static int scene_common(rl_scene *s) {
-  HIP_TRY(hipMalloc((void **)&s->d_scratch, 512));
+  HIP_TRY(s->d_scratch.reserve(512));
   HIP_TRY(hipMemset(s->d_scratch, 0, 512));
-  HIP_TRY(hipEventCreate(&s->ev0));
-  HIP_TRY(hipEventCreate(&s->ev1));
-  for (hipEvent_t &e : s->ev_status) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  HIP_TRY(hipEventCreateWithFlags(&s->ev_last, hipEventDisableTiming));
-  HIP_TRY(hipHostMalloc((void **)&s->h_status, (size_t)rl_scene::N_STATUS * 64, hipHostMallocDefault));
+  HIP_TRY(s->ev0.create());
+  HIP_TRY(s->ev1.create());
+  for (Event &e : s->ev_status) HIP_TRY(e.create(hipEventDisableTiming));
+  HIP_TRY(s->ev_last.create(hipEventDisableTiming));
+  HIP_TRY(s->h_status.reserve((size_t)rl_scene::N_STATUS * 8, hipHostMallocDefault));
   std::memset(s->h_status, 0, (size_t)rl_scene::N_STATUS * 64);
   return RL_OK;
 }
@@ -506,16 +465,16 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
   const RtiowProgram &rt = H->rt;
   const FastGeneral &QF = H->query_tree();  // general scenes: the renders' tree; sphere-only scenes: the queries' own
   int rc = RL_OK;
-  if ((rc = upload(rt.ops, &s->d_ops)) || (rc = upload(rt.spheres, &s->d_spheres)) || (rc = upload(rt.sphere_material, &s->d_sphere_material)) ||
-      (rc = upload(rt.planars, &s->d_planars)) || (rc = upload(rt.translates, &s->d_translates)) || (rc = upload(rt.transforms, &s->d_transforms)) ||
-      (rc = upload(rt.materials, &s->d_materials)) || (rc = upload(rt.textures, &s->d_textures)) || (rc = upload(rt.images, &s->d_images)) ||
-      (rc = upload(rt.image_pool, &s->d_image_pool)) || (rc = upload(rt.perlins, &s->d_perlins)) || (rc = upload(rt.media, &s->d_media)) ||
+  if ((rc = s->d_ops.upload(rt.ops)) || (rc = s->d_spheres.upload(rt.spheres)) || (rc = s->d_sphere_material.upload(rt.sphere_material)) ||
+      (rc = s->d_planars.upload(rt.planars)) || (rc = s->d_translates.upload(rt.translates)) || (rc = s->d_transforms.upload(rt.transforms)) ||
+      (rc = s->d_materials.upload(rt.materials)) || (rc = s->d_textures.upload(rt.textures)) || (rc = s->d_images.upload(rt.images)) ||
+      (rc = s->d_image_pool.upload(rt.image_pool)) || (rc = s->d_perlins.upload(rt.perlins)) || (rc = s->d_media.upload(rt.media)) ||
       (rc = scene_common(s)) ||
-      (!H->lops.empty() && ((rc = upload(H->lops, &s->d_lops)) || (rc = upload(H->sphere_flat, &s->d_sphere_flat)))) ||
-      (!H->cops.empty() && ((rc = upload(H->cops, &s->d_cops)) || (rc = upload(H->movbits, &s->d_movbits)))) ||
-      (H->fast_root != FAST_NONE && ((rc = upload(H->fast_nodes, &s->d_fast_nodes)) || (rc = upload(H->fast_leaf_boxes, &s->d_fast_leaf_boxes)))) ||
-      (QF.ok && ((rc = upload(QF.qnodes, &s->d_fg_nodes)) || (rc = upload(QF.onodes, &s->d_fg_onodes)) || (rc = upload(QF.stage_roots, &s->d_fg_seg_roots)) ||
-                 (rc = upload(QF.media, &s->d_fg_media)) || (rc = upload(QF.items, &s->d_fg_items)) || (rc = upload(QF.item_spheres, &s->d_fg_spheres)) || (rc = upload(QF.item_material, &s->d_fg_material))))) {
+      (!H->lops.empty() && ((rc = s->d_lops.upload(H->lops)) || (rc = s->d_sphere_flat.upload(H->sphere_flat)))) ||
+      (!H->cops.empty() && ((rc = s->d_cops.upload(H->cops)) || (rc = s->d_movbits.upload(H->movbits)))) ||
+      (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)))) ||
+      (QF.ok && ((rc = s->d_fg_nodes.upload(QF.qnodes)) || (rc = s->d_fg_onodes.upload(QF.onodes)) || (rc = s->d_fg_seg_roots.upload(QF.stage_roots)) ||
+                 (rc = s->d_fg_media.upload(QF.media)) || (rc = s->d_fg_items.upload(QF.items)) || (rc = s->d_fg_spheres.upload(QF.item_spheres)) || (rc = s->d_fg_material.upload(QF.item_material))))) {
     destroy_one(s);
     return nullptr;
   }
@@ -633,25 +592,19 @@ using rl::post_status;
 // chunks and the finished-pixel counter is polled once per chunk.
 static int render_wavefront(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream, bool want_stats) {
   rl_scene *sc = const_cast<rl_scene *>(scene);  // work buffers only; the scene program is immutable
-  if (!sc->exp) sc->exp = new ExpBuffers();
-  ExpBuffers *ms = (ExpBuffers *)sc->exp;
+  ExpBuffers *ms = &sc->exp;
   const uint32_t Wd = P.cam.image_width;
   size_t npix = (size_t)nrows * Wd;
   if (npix >= 0xFFFF0000ull) return set_err(RL_E_INVALID, "image too large");
-  if (ms->wf_npix < npix) {
-    hipFree(ms->wf_pix), hipFree(ms->wf_ray), hipFree(ms->wf_hit), hipFree(ms->wf_qtrav), hipFree(ms->wf_qshade), hipFree(ms->wf_qgen);
-    ms->wf_pix = nullptr, ms->wf_ray = nullptr, ms->wf_hit = nullptr, ms->wf_qtrav = ms->wf_qshade = ms->wf_qgen = nullptr, ms->wf_npix = 0;
-    HIP_TRY(hipMalloc((void **)&ms->wf_pix, npix * sizeof(PixState)));
-    HIP_TRY(hipMalloc((void **)&ms->wf_ray, npix * sizeof(RayRec)));
-    HIP_TRY(hipMalloc((void **)&ms->wf_hit, npix * sizeof(HitRec)));
-    HIP_TRY(hipMalloc((void **)&ms->wf_qtrav, 2 * npix * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&ms->wf_qgen, npix * sizeof(uint32_t)));
-    ms->wf_npix = npix;
-  }
-  if (!ms->wf_ctl) HIP_TRY(hipMalloc((void **)&ms->wf_ctl, WC_WORDS * sizeof(uint32_t)));
+  HIP_TRY(ms->wf_pix.reserve(npix * sizeof(PixState)));
+  HIP_TRY(ms->wf_ray.reserve(npix * sizeof(RayRec)));
+  HIP_TRY(ms->wf_hit.reserve(npix * sizeof(HitRec)));
+  HIP_TRY(ms->wf_qtrav.reserve(2 * npix));
+  HIP_TRY(ms->wf_qgen.reserve(npix));
+  HIP_TRY(ms->wf_ctl.reserve(WC_WORDS));
   WfParams Wp{};
   Wp.R = P;
-  Wp.pix = ms->wf_pix, Wp.ray = ms->wf_ray, Wp.hit = ms->wf_hit;
+  Wp.pix = (PixState *)ms->wf_pix.get(), Wp.ray = (RayRec *)ms->wf_ray.get(), Wp.hit = (HitRec *)ms->wf_hit.get();
   Wp.q_trav = ms->wf_qtrav, Wp.q_gen = ms->wf_qgen, Wp.ctl = ms->wf_ctl;
   Wp.npix = (uint32_t)npix;
 
@@ -718,20 +671,15 @@ static int render_wavefront(const rl_scene *scene, RtiowParams &P, uint32_t nrow
 static int render_wfg(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream, bool trans) {
   rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only; the scene program is immutable
   const size_t npix = (size_t)nrows * P.cam.image_width, nslots = P.n_slots;
-  if (ms->wfg_pix_cap < npix || ms->wfg_slot_cap < nslots) {
-    hipFree(ms->d_wfg_pix), hipFree(ms->d_wfg_ray), hipFree(ms->d_wfg_q0), hipFree(ms->d_wfg_q1), hipFree(ms->d_wfg_qs);
-    ms->d_wfg_pix = nullptr, ms->d_wfg_ray = nullptr, ms->d_wfg_q0 = ms->d_wfg_q1 = ms->d_wfg_qs = nullptr, ms->wfg_pix_cap = ms->wfg_slot_cap = 0;
-    HIP_TRY(hipMalloc((void **)&ms->d_wfg_pix, npix * sizeof(WfgPix)));
-    HIP_TRY(hipMalloc((void **)&ms->d_wfg_ray, npix * sizeof(WfgRay)));
-    HIP_TRY(hipMalloc((void **)&ms->d_wfg_q0, nslots * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&ms->d_wfg_q1, nslots * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void **)&ms->d_wfg_qs, nslots * sizeof(uint32_t)));
-    ms->wfg_pix_cap = npix, ms->wfg_slot_cap = nslots;
-  }
-  if (!ms->d_wfg_ctl) HIP_TRY(hipMalloc((void **)&ms->d_wfg_ctl, WFG_CTL_WORDS * sizeof(uint32_t)));
-  if (!ms->h_wfg) HIP_TRY(hipHostMalloc((void **)&ms->h_wfg, 64, hipHostMallocDefault));
+  HIP_TRY(ms->d_wfg_pix.reserve(npix * sizeof(WfgPix)));
+  HIP_TRY(ms->d_wfg_ray.reserve(npix * sizeof(WfgRay)));
+  HIP_TRY(ms->d_wfg_q0.reserve(nslots));
+  HIP_TRY(ms->d_wfg_q1.reserve(nslots));
+  HIP_TRY(ms->d_wfg_qs.reserve(nslots));
+  HIP_TRY(ms->d_wfg_ctl.reserve(WFG_CTL_WORDS));
+  HIP_TRY(ms->h_wfg.reserve(16, hipHostMallocDefault));
   WfgParams Q{};
-  Q.pix = (WfgPix *)ms->d_wfg_pix, Q.ray = (WfgRay *)ms->d_wfg_ray, Q.queue[0] = ms->d_wfg_q0, Q.queue[1] = ms->d_wfg_q1, Q.slow_queue = ms->d_wfg_qs, Q.ctl = ms->d_wfg_ctl;
+  Q.pix = (WfgPix *)ms->d_wfg_pix.get(), Q.ray = (WfgRay *)ms->d_wfg_ray.get(), Q.queue[0] = ms->d_wfg_q0, Q.queue[1] = ms->d_wfg_q1, Q.slow_queue = ms->d_wfg_qs, Q.ctl = ms->d_wfg_ctl;
   P.sample_begin = 0, P.sample_end = P.cam.samples_per_pixel, P.resume = 0, P.pos_state = nullptr, P.tile_order = nullptr, P.tile_cost = nullptr;
   if (!g_sw.tune_set) P.tune[0] = 4, P.tune[3] = FASTG_STEP_BUDGET;
   hipLaunchKernelGGL(wfg_init, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, stream, P, Q);
@@ -805,7 +753,7 @@ static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, 
   slots = (uint64_t)P.tiles_x * ((nrows + 7) / 8) * 64ull;
   if (slots >= 0xFFFF0000ull) return set_err(RL_E_INVALID, "image too large");
   P.n_slots = (uint32_t)slots;
-  P.work_counter = (uint32_t *)scene->d_scratch;
+  P.work_counter = (uint32_t *)scene->d_scratch.get();
   P.stats = (unsigned long long *)(scene->d_scratch + 64);
   P.out = (double *)d_out;
   P.k8u = 8.8817841970012523e-16;
@@ -902,16 +850,22 @@ static int build_pixel_entry(const rl_scene *scene, RtiowParams &P, uint32_t nro
   const size_t npix = (size_t)nrows * P.cam.image_width;
   if (g_sw.pixel_entry <= 0 || npix == 0) return RL_OK;
   rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only
-  if (ms->pixel_entry_pix < npix) {
-    hipFree(ms->d_pixel_entry);
-    ms->d_pixel_entry = nullptr, ms->pixel_entry_pix = 0;
-    HIP_TRY(hipMalloc((void **)&ms->d_pixel_entry, npix * sizeof(uint32_t)));
-    ms->pixel_entry_pix = npix;
-  }
+  HIP_TRY(ms->d_pixel_entry.reserve(npix));
   hipLaunchKernelGGL(rtiow_pixel_entry_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, P, (const float *)scene->d_fast_leaf_boxes, (uint32_t)g_sw.pixel_entry,
                      ms->d_pixel_entry);
   HIP_TRY(hipGetLastError());
   P.pixel_entry = ms->d_pixel_entry;
+  return RL_OK;
+}
+
+// The kernels that take the parameter block by pointer read a device copy of it.  Two slots, used in turn: the cost-sorted render launches
+// twice with different parameters (and the sample-parallel mode and the ray queries once per pass), all enqueued before the first one runs.
+static int stage_params(const rl_scene *scene, const RtiowParams &P, hipStream_t stream, const RtiowParams *&slot) {
+  rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only
+  HIP_TRY(ms->d_params.reserve(2 * sizeof(RtiowParams)));
+  RtiowParams *dst = (RtiowParams *)ms->d_params.get() + (ms->params_slot++ & 1);
+  HIP_TRY(hipMemcpyAsync(dst, &P, sizeof(RtiowParams), hipMemcpyHostToDevice, stream));
+  slot = dst;
   return RL_OK;
 }
 
@@ -955,11 +909,9 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     return RL_OK;
   };
   auto launch_ptr = [&](auto kern, int nt, size_t rng_bytes) -> int {  // kernels that take the parameter block by pointer (device copy)
-    rl_scene *ms = const_cast<rl_scene *>(scene);
-    if (!ms->d_params) HIP_TRY(hipMalloc((void **)&ms->d_params, 2 * sizeof(RtiowParams)));
-    // two slots: the cost-sorted render launches twice with different parameters, both enqueued before the first one runs
-    RtiowParams *slot = (RtiowParams *)ms->d_params + (ms->params_slot++ & 1);
-    HIP_TRY(hipMemcpyAsync(slot, &P, sizeof(RtiowParams), hipMemcpyHostToDevice, stream));
+    const RtiowParams *slot = nullptr;
+    int rcs = stage_params(scene, P, stream, slot);
+    if (rcs != RL_OK) return rcs;
     size_t lds = rng_bytes;
     uint32_t blocks = (uint32_t)((slots + nt - 1) / nt);
     uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));
@@ -968,7 +920,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
     if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;
     if (ensure_lds_attr((const void *)kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, (const RtiowParams *)slot);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
     HIP_TRY(hipGetLastError());
     return RL_OK;
   };
@@ -1136,12 +1088,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     } else if (variant == 1033) {  // A/B: EVERY pixel through the cooperative one-wave-per-pixel kernel (rl_rtiow_coop.h)
       rl_scene *ms = const_cast<rl_scene *>(scene);
       const size_t npix = (size_t)nrows * W;
-      if (ms->coop_pixels_cap < npix) {
-        hipFree(ms->d_coop_pixels);
-        ms->d_coop_pixels = nullptr, ms->coop_pixels_cap = 0;
-        HIP_TRY(hipMalloc((void **)&ms->d_coop_pixels, npix * sizeof(uint32_t)));
-        ms->coop_pixels_cap = npix;
-      }
+      HIP_TRY(ms->d_coop_pixels.reserve(npix));
       hipLaunchKernelGGL(iota_u32, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, ms->d_coop_pixels, (uint32_t)npix);
       rc = launch_coop(ms->d_coop_pixels, (uint32_t)npix);
     } else if (variant == 1029) {  // 4 waves per SIMD: rings + fast traversal nodes in LDS, spheres read from L2; never a counting render
@@ -1185,28 +1132,17 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
   else {
     rl_scene *ms = const_cast<rl_scene *>(scene);  // scratch buffers only; the scene program itself is immutable
     size_t npix = (size_t)nrows * W, ntiles = (size_t)(slots >> 6);
-    if (ms->lpt_pix < npix) {
-      hipFree(ms->d_pos);
-      ms->d_pos = nullptr, ms->lpt_pix = 0;
-      HIP_TRY(hipMalloc((void **)&ms->d_pos, npix * sizeof(uint32_t)));
-      ms->lpt_pix = npix;
-    }
-    if (ms->lpt_tiles < ntiles) {
-      hipFree(ms->d_tile_cost), hipFree(ms->d_tile_order), hipFree(ms->d_tile_keys), hipFree(ms->d_tile_iota);
-      ms->d_tile_cost = ms->d_tile_order = ms->d_tile_keys = ms->d_tile_iota = nullptr, ms->lpt_tiles = 0;
-      HIP_TRY(hipMalloc((void **)&ms->d_tile_cost, ntiles * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc((void **)&ms->d_tile_order, ntiles * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc((void **)&ms->d_tile_keys, ntiles * sizeof(uint32_t)));
-      HIP_TRY(hipMalloc((void **)&ms->d_tile_iota, ntiles * sizeof(uint32_t)));
-      ms->lpt_tiles = ntiles;
-    }
+    HIP_TRY(ms->d_pos.reserve(npix));
+    HIP_TRY(ms->d_tile_cost.reserve(ntiles));
+    HIP_TRY(ms->d_tile_order.reserve(ntiles));
+    HIP_TRY(ms->d_tile_keys.reserve(ntiles));
+    HIP_TRY(ms->d_tile_iota.reserve(ntiles));
     HIP_TRY(hipMemsetAsync(ms->d_tile_cost, 0, ntiles * sizeof(uint32_t), stream));
     P.sample_end = lpt_first, P.pos_state = ms->d_pos, P.tile_cost = ms->d_tile_cost;
     rc = launch_variant();
     if (rc != RL_OK) return rc;
     // tiles by cost, most expensive first, on the device (stable radix sort): the whole render stays asynchronous on `stream`
-    rc = rl::sort_tiles_by_cost_desc(ms->d_tile_cost, ms->d_tile_keys, ms->d_tile_iota, ms->d_tile_order, (uint32_t)ntiles, &ms->d_sort_temp, &ms->sort_temp_bytes,
-                                     stream);
+    rc = rl::sort_tiles_by_cost_desc(ms->d_tile_cost, ms->d_tile_keys, ms->d_tile_iota, ms->d_tile_order, (uint32_t)ntiles, ms->d_sort_temp, stream);
     if (rc != RL_OK) return rc;
     HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 4, stream));  // work counter only; stats keep accumulating
     if (scene->progress_on) P.work_counter = scene->d_progress + 1;  // the resume launch counts in the second host-visible word
@@ -1214,13 +1150,8 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     P.tile_order = ms->d_tile_order, P.tile_cost = nullptr;
     if (variant == 1029 && !want_stats && g_sw.steal_max_fill > 0.0 && (double)npix <= g_sw.steal_max_fill * (double)g_cus * 1024.0) {
       // small shard: waves that run out of pixels take over pixels other lanes are still rendering (rl_rtiow_coop.h rtiow_steal_loop)
-      if (ms->steal_pix < npix) {
-        hipFree(ms->d_steal_state), hipFree(ms->d_steal_n);
-        ms->d_steal_state = ms->d_steal_n = nullptr, ms->steal_pix = 0;
-        HIP_TRY(hipMalloc((void **)&ms->d_steal_state, npix * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void **)&ms->d_steal_n, npix * sizeof(uint32_t)));
-        ms->steal_pix = npix;
-      }
+      HIP_TRY(ms->d_steal_state.reserve(npix));
+      HIP_TRY(ms->d_steal_n.reserve(npix));
       HIP_TRY(hipMemsetAsync(ms->d_steal_state, 0, npix * sizeof(uint32_t), stream));
       HIP_TRY(hipMemsetAsync(scene->d_scratch + 256, 0, 4, stream));
       P.steal_state = ms->d_steal_state, P.steal_n = ms->d_steal_n, P.steal_counter = (uint32_t *)(scene->d_scratch + 256);
@@ -1288,13 +1219,7 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
     int rco = order_after_previous(scene, stream);
     if (rco != RL_OK) return rco;
   }
-  const size_t buf_bytes = (size_t)per_pass * sample_bytes;
-  if (S > 0 && ms->indep_bytes < buf_bytes) {
-    hipFree(ms->d_indep);
-    ms->d_indep = nullptr, ms->indep_bytes = 0;
-    HIP_TRY(hipMalloc((void **)&ms->d_indep, buf_bytes));
-    ms->indep_bytes = buf_bytes;
-  }
+  if (S > 0) HIP_TRY(ms->d_indep.reserve((size_t)per_pass * (size_t)n_vals));
   P.indep_buf = ms->d_indep, P.indep_k = K, P.indep_tile_slots = (uint32_t)tile_slots;
   if (variant == 1029) {  // the sample-parallel fast kernel shares the body: its camera rays start at their pixel's entry too
     int rce = build_pixel_entry(scene, P, nrows, stream);
@@ -1343,10 +1268,10 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
     uint32_t blocks = 0;
     int rcb = blocks_of((const void *)kern, blocks);
     if (rcb != RL_OK) return rcb;
-    if (!ms->d_params) HIP_TRY(hipMalloc((void **)&ms->d_params, 2 * sizeof(RtiowParams)));
-    RtiowParams *slot = (RtiowParams *)ms->d_params + (ms->params_slot++ & 1);
-    HIP_TRY(hipMemcpyAsync(slot, &P, sizeof(RtiowParams), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, (const RtiowParams *)slot);
+    const RtiowParams *slot = nullptr;
+    int rcs = stage_params(scene, P, stream, slot);
+    if (rcs != RL_OK) return rcs;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
     HIP_TRY(hipGetLastError());
     return RL_OK;
   };
@@ -1469,7 +1394,7 @@ int rl_rtiow_render_progress(const rl_scene *scene, uint64_t *pixels_claimed, ui
         return set_err(RL_E_INVALID, "scene belongs to a device context that no longer exists (created under another rl_init / rl_init_multi)");
       int rc = rl::use_context(ms->ctx);
       if (rc != RL_OK) return rc;
-      HIP_TRY(hipHostMalloc((void **)&ms->h_progress, 64, hipHostMallocMapped | hipHostMallocCoherent));
+      HIP_TRY(ms->h_progress.reserve(16, hipHostMallocMapped | hipHostMallocCoherent));
       std::memset(ms->h_progress, 0, 64);
       HIP_TRY(hipHostGetDevicePointer((void **)&ms->d_progress, ms->h_progress, 0));
       ms->progress_on = true;
@@ -1641,7 +1566,7 @@ void rl_debug_set_indep_k(unsigned k) { g_sw.indep_k = k ? k : 1u; }  // samples
 void rl_debug_set_pixel_entry(int max_entries) { g_sw.pixel_entry = std::min(3, std::max(0, max_entries)); }  // 0: camera rays start at the root (A/B, tests)
 // Tests: the entry table of the scene's most recent fast-traversal render (n_pixels words, rows x W of the shard rendered), after that render has finished
 int rl_debug_pixel_entry_read(const rl_scene *scene, uint32_t *out, uint64_t n_pixels) {
-  if (!scene || !out || !scene->d_pixel_entry || n_pixels > scene->pixel_entry_pix) return RL_E_INVALID;
+  if (!scene || !out || !scene->d_pixel_entry || n_pixels > scene->d_pixel_entry.size()) return RL_E_INVALID;
   int rc0 = rl::use_context(scene->ctx);
   if (rc0 != RL_OK) return rc0;
   HIP_TRY(hipMemcpy(out, scene->d_pixel_entry, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -1693,6 +1618,9 @@ int rl_debug_has_experimental(void) {
 #endif
 }
 
+// Not part of the ABI (tests): the device allocations the library owns right now, out[0] their number, out[1] their bytes (rl_devbuf.h)
+void rl_debug_live_buffers(unsigned long long out[2]) { out[0] = rl::g_live_buffers.load(), out[1] = rl::g_live_bytes.load(); }
+
 // Not part of the ABI (tools only): scheduler occupancy counters of the last STATS launch, 32 x u64 ([3s .. 3s+2] per state; [24]: the
 // fast kernel's skipped self tests, rl_rtiow_wave.h fast_self_miss).
 int rl_debug_sched(const rl_scene *scene, unsigned long long *out32) {
@@ -1706,10 +1634,9 @@ int rl_debug_sched(const rl_scene *scene, unsigned long long *out32) {
 int rl_debug_pixel_rays(const rl_scene *scene, uint64_t n_pixels) {
   if (!scene) return RL_E_INVALID;
   rl_scene *ms = const_cast<rl_scene *>(scene);
-  hipFree(ms->d_pix_rays);
-  ms->d_pix_rays = nullptr;
+  ms->d_pix_rays.release();
   if (n_pixels) {
-    HIP_TRY(hipMalloc((void **)&ms->d_pix_rays, n_pixels * sizeof(uint32_t)));
+    HIP_TRY(ms->d_pix_rays.reserve(n_pixels));
     HIP_TRY(hipMemset(ms->d_pix_rays, 0, n_pixels * sizeof(uint32_t)));
   }
   return RL_OK;
@@ -1733,15 +1660,14 @@ int rl_rtiow_render_rows(const rl_scene *scene, const rl_rtiow_camera *cam, uint
   }
   int rc0 = rl::use_context(scene->ctx);
   if (rc0 != RL_OK) return rc0;
-  double *d_out = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_out, bytes));
+  DevBuf<double> d_out;
+  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
   rl_stats local;
   int rc = rl_rtiow_render_device(scene, cam, first_sample, row_first, row_step, d_out, g_ctx[(size_t)scene->ctx].stream, &local);
   if (rc == RL_OK || rc == RL_E_DEGENERATE) {
     hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
   }
-  hipFree(d_out);
   if (st) *st = local;
   return rc;
 }
@@ -1759,8 +1685,8 @@ int rl_rtiow_render_independent_rows(const rl_scene *scene, const rl_rtiow_camer
   }
   int rc0 = rl::use_context(scene->ctx);
   if (rc0 != RL_OK) return rc0;
-  double *d_out = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_out, bytes));
+  DevBuf<double> d_out;
+  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
   int rc = RL_OK;
   if (accumulate) {  // the caller's sums are the fold's start
     hipError_t e = hipMemcpy(d_out, out, bytes, hipMemcpyHostToDevice);
@@ -1773,7 +1699,6 @@ int rl_rtiow_render_independent_rows(const rl_scene *scene, const rl_rtiow_camer
     hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
   }
-  hipFree(d_out);
   if (st) *st = local;
   return rc;
 }
@@ -1797,14 +1722,11 @@ int rl_rtiow_render_rgb8(const rl_scene *scene, const rl_rtiow_camera *cam, uint
   int rc0 = rl::use_context(scene->ctx);
   if (rc0 != RL_OK) return rc0;
   hipStream_t stream = g_ctx[(size_t)scene->ctx].stream;
-  double *d_sum = nullptr;
-  unsigned char *d_u8 = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_sum, npix * 3 * sizeof(double)));
-  hipError_t e = hipMalloc((void **)&d_u8, npix * 3);
-  if (e != hipSuccess) {
-    hipFree(d_sum);
-    return set_err(RL_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
+  DevBuf<double> d_sum;
+  DevBuf<unsigned char> d_u8;
+  HIP_TRY(d_sum.reserve(npix * 3));
+  hipError_t e = d_u8.reserve(npix * 3);
+  if (e != hipSuccess) return set_err(RL_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
   rl_stats local;
   int rc = rl_rtiow_render_device(scene, cam, first_sample, 0, 1, d_sum, stream, &local);
   if (rc == RL_OK || rc == RL_E_DEGENERATE) {
@@ -1816,7 +1738,6 @@ int rl_rtiow_render_rgb8(const rl_scene *scene, const rl_rtiow_camera *cam, uint
       if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("D2H: ") + hipGetErrorString(e));
     }
   }
-  hipFree(d_sum), hipFree(d_u8);
   if (st) *st = local;
   return rc;
 }
@@ -1882,9 +1803,9 @@ static rl_scene *upload_rtc(const std::shared_ptr<const HostRtc> &H, int ctx) {
   s->kind = 2, s->ctx = ctx, s->device = g_ctx[(size_t)ctx].device, s->hrc = H;
   const RtcProgram &rc_ = H->rc;
   int rc = RL_OK;
-  if ((!H->guards.empty() && (rc = upload(H->guards, &s->d_guards))) || (rc = upload(rc_.ops, &s->d_ops)) || (rc = upload(rc_.tris, &s->d_tris)) ||
-      (rc = upload(rc_.xforms, &s->d_xforms)) || (rc = upload(rc_.materials, &s->d_rmaterials)) || (rc = upload(rc_.lights, &s->d_lights)) ||
-      (rc = upload(rc_.shapes, &s->d_shapes)) || (rc = upload(rc_.csgs, &s->d_csgs)) || (rc = upload(rc_.patterns, &s->d_patterns)) || (rc = scene_common(s))) {
+  if ((!H->guards.empty() && (rc = s->d_guards.upload(H->guards))) || (rc = s->d_ops.upload(rc_.ops)) || (rc = s->d_tris.upload(rc_.tris)) ||
+      (rc = s->d_xforms.upload(rc_.xforms)) || (rc = s->d_rmaterials.upload(rc_.materials)) || (rc = s->d_lights.upload(rc_.lights)) ||
+      (rc = s->d_shapes.upload(rc_.shapes)) || (rc = s->d_csgs.upload(rc_.csgs)) || (rc = s->d_patterns.upload(rc_.patterns)) || (rc = scene_common(s))) {
     destroy_one(s);
     return nullptr;
   }
@@ -2058,15 +1979,14 @@ int rl_rtc_render_rows(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t
   }
   int rc0 = rl::use_context(scene->ctx);
   if (rc0 != RL_OK) return rc0;
-  double *d_out = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_out, bytes));
+  DevBuf<double> d_out;
+  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
   rl_stats local;
   int rc = rl_rtc_render_device(scene, cam, aa, row_first, row_step, d_out, g_ctx[(size_t)scene->ctx].stream, &local);
   if (rc == RL_OK || rc == RL_E_DEGENERATE) {
     hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
     if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
   }
-  hipFree(d_out);
   if (st) *st = local;
   return rc;
 }
@@ -2089,14 +2009,11 @@ int rl_rtc_render_rgb8(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t
   int rc0 = rl::use_context(scene->ctx);
   if (rc0 != RL_OK) return rc0;
   hipStream_t stream = g_ctx[(size_t)scene->ctx].stream;
-  double *d_rgb = nullptr;
-  unsigned char *d_u8 = nullptr;
-  HIP_TRY(hipMalloc((void **)&d_rgb, npix * 3 * sizeof(double)));
-  hipError_t e = hipMalloc((void **)&d_u8, npix * 3);
-  if (e != hipSuccess) {
-    hipFree(d_rgb);
-    return set_err(RL_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-  }
+  DevBuf<double> d_rgb;
+  DevBuf<unsigned char> d_u8;
+  HIP_TRY(d_rgb.reserve(npix * 3));
+  hipError_t e = d_u8.reserve(npix * 3);
+  if (e != hipSuccess) return set_err(RL_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
   rl_stats local;
   int rc = rl_rtc_render_device(scene, cam, aa, 0, 1, d_rgb, stream, &local);
   if (rc == RL_OK || rc == RL_E_DEGENERATE) {
@@ -2108,7 +2025,6 @@ int rl_rtc_render_rgb8(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t
       if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("D2H: ") + hipGetErrorString(e));
     }
   }
-  hipFree(d_rgb), hipFree(d_u8);
   if (st) *st = local;
   return rc;
 }
@@ -2173,13 +2089,9 @@ RtcFullParams rtc_query_params(const rl_scene *scene) {
 }
 // host-buffer forms: stage the rays, run the device form on the library's stream of the scene's context, copy the results back
 struct QueryStage {
-  void *d[4] = {nullptr, nullptr, nullptr, nullptr};
-  ~QueryStage() {
-    for (void *p : d)
-      if (p) hipFree(p);
-  }
+  DevBuf<unsigned char> d[4];
   int alloc(int i, size_t bytes) {
-    HIP_TRY(hipMalloc(&d[i], bytes ? bytes : 1));
+    HIP_TRY(d[i].reserve(bytes ? bytes : 1));
     return RL_OK;
   }
 };
@@ -2430,7 +2342,6 @@ static int rtiow_ray_color_impl(const rl_scene *scene, const void *d_rays, const
   uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));  // persistent lanes: as many workgroups as stay resident
   if (per_cu < 1) per_cu = 1;
   if (per_cu * (uint32_t)nt > 2048) per_cu = 2048 / (uint32_t)nt;
-  rl_scene *ms = const_cast<rl_scene *>(scene);
   auto blocks_of = [&](const void *kern, uint32_t &blocks) -> int {
     blocks = (uint32_t)(((uint64_t)P.n_slots + nt - 1) / nt);
     if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
@@ -2450,10 +2361,10 @@ static int rtiow_ray_color_impl(const rl_scene *scene, const void *d_rays, const
     uint32_t blocks = 0;
     int rcb = blocks_of((const void *)kern, blocks);
     if (rcb != RL_OK) return rcb;
-    if (!ms->d_params) HIP_TRY(hipMalloc((void **)&ms->d_params, 2 * sizeof(RtiowParams)));
-    RtiowParams *slot = (RtiowParams *)ms->d_params + (ms->params_slot++ & 1);
-    HIP_TRY(hipMemcpyAsync(slot, &P, sizeof(RtiowParams), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, (const RtiowParams *)slot);
+    const RtiowParams *slot = nullptr;
+    int rcs = stage_params(scene, P, stream, slot);
+    if (rcs != RL_OK) return rcs;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
     HIP_TRY(hipGetLastError());
     return RL_OK;
   };

@@ -1,5 +1,6 @@
 // Internal (not part of the ABI): the library's per-device context and the rl_scene object, shared by rl_render.hip (the
-// single-device entry points) and rl_multi.hip (one process driving several GPUs).
+// single-device entry points) and rl_multi.hip (one process driving several GPUs).  Device buffers, pinned memory and events are held
+// by the owning types of rl_devbuf.h (DevBuf<T>, PinnedBuf<T>, Event): rl_scene has no hand-written teardown.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <string>
 #include <vector>
 
+#include "rl_devbuf.h"
 #include "rl_program.h"
 
 namespace rl {
@@ -40,6 +42,11 @@ struct HostRtc {
   RtcProgram rc;
   std::vector<RtcGuard> guards;
 };
+// wavefront (v3) work buffers of the experimental library: per-pixel state, ray and hit records, queues, control words
+struct ExpBuffers {
+  DevBuf<unsigned char> wf_pix, wf_ray, wf_hit;
+  DevBuf<uint32_t> wf_qtrav, wf_qgen, wf_ctl;
+};
 
 }  // namespace rl
 
@@ -52,48 +59,45 @@ struct rl_scene {
   const rl::RtiowProgram &rt() const { return hrt->rt; }
   const rl::RtcProgram &rc() const { return hrc->rc; }
   std::vector<rl_scene *> replicas;  // multi-GPU: replicas[g] lives on device context g; replicas[0] == this (empty: single device)
+  // Every d_* / h_* / ev* member owns what it names (rl_devbuf.h): deleting the scene releases all of it, and a buffer that is grown
+  // on demand is one reserve() at its use site.
   // RTIOW
-  rl::DevOp *d_ops = nullptr;
-  rl::DevOp *d_lops = nullptr;
-  rl::DevMaterial *d_sphere_flat = nullptr;
-  rl::CompactOp *d_cops = nullptr;
-  uint32_t *d_movbits = nullptr;
-  rl::FastNode *d_fast_nodes = nullptr;
-  float *d_fast_leaf_boxes = nullptr;
-  uint32_t *d_coop_pixels = nullptr;  // cooperative kernel: pixel list (scratch, grown on demand)
-  size_t coop_pixels_cap = 0;
-  uint32_t *d_steal_state = nullptr, *d_steal_n = nullptr;  // work stealing on small shards (RtiowParams::steal_state)
-  size_t steal_pix = 0;
-  rl::FastNodeQ *d_fg_nodes = nullptr;
-  rl::FastNodeO *d_fg_onodes = nullptr;
-  uint32_t *d_fg_seg_roots = nullptr;
-  rl::FastMedium *d_fg_media = nullptr;
-  rl::FastItem *d_fg_items = nullptr;
-  rl::DevSphere *d_fg_spheres = nullptr;
-  uint32_t *d_fg_material = nullptr;
-  rl::DevSphere *d_spheres = nullptr;
-  uint32_t *d_sphere_material = nullptr;
-  rl::DevPlanar *d_planars = nullptr;
-  rl_translate *d_translates = nullptr;
-  rl_transform *d_transforms = nullptr;
-  rl::DevMaterial *d_materials = nullptr;
-  rl::DevTexture *d_textures = nullptr;
-  rl::DevImage *d_images = nullptr;
-  float *d_image_pool = nullptr;
-  rl_perlin *d_perlins = nullptr;
-  rl_medium *d_media = nullptr;
+  rl::DevBuf<rl::DevOp> d_ops, d_lops;
+  rl::DevBuf<rl::DevMaterial> d_sphere_flat;
+  rl::DevBuf<rl::CompactOp> d_cops;
+  rl::DevBuf<uint32_t> d_movbits;
+  rl::DevBuf<rl::FastNode> d_fast_nodes;
+  rl::DevBuf<float> d_fast_leaf_boxes;
+  rl::DevBuf<uint32_t> d_coop_pixels;  // cooperative kernel: pixel list (scratch, grown on demand)
+  rl::DevBuf<uint32_t> d_steal_state, d_steal_n;  // work stealing on small shards (RtiowParams::steal_state)
+  rl::DevBuf<rl::FastNodeQ> d_fg_nodes;
+  rl::DevBuf<rl::FastNodeO> d_fg_onodes;
+  rl::DevBuf<uint32_t> d_fg_seg_roots;
+  rl::DevBuf<rl::FastMedium> d_fg_media;
+  rl::DevBuf<rl::FastItem> d_fg_items;
+  rl::DevBuf<rl::DevSphere> d_fg_spheres;
+  rl::DevBuf<uint32_t> d_fg_material;
+  rl::DevBuf<rl::DevSphere> d_spheres;
+  rl::DevBuf<uint32_t> d_sphere_material;
+  rl::DevBuf<rl::DevPlanar> d_planars;
+  rl::DevBuf<rl_translate> d_translates;
+  rl::DevBuf<rl_transform> d_transforms;
+  rl::DevBuf<rl::DevMaterial> d_materials;
+  rl::DevBuf<rl::DevTexture> d_textures;
+  rl::DevBuf<rl::DevImage> d_images;
+  rl::DevBuf<float> d_image_pool;
+  rl::DevBuf<rl_perlin> d_perlins;
+  rl::DevBuf<rl_medium> d_media;
   // RTC
-  rl::DevTri *d_tris = nullptr;
-  rl_rtc_transformed *d_xforms = nullptr;
-  rl_rtc_material *d_rmaterials = nullptr;
-  rl_rtc_light *d_lights = nullptr;
-  rl_rtc_shape *d_shapes = nullptr;
-  rl_rtc_csg *d_csgs = nullptr;
-  rl_rtc_pattern *d_patterns = nullptr;
-  rl::RtcGuard *d_guards = nullptr;
-  // per-scene scratch: [0] work counter (u32), [64..] 8 x u64 stats, [128..] scheduler debug counters
-  unsigned char *d_scratch = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  rl::DevBuf<rl::DevTri> d_tris;
+  rl::DevBuf<rl_rtc_transformed> d_xforms;
+  rl::DevBuf<rl_rtc_material> d_rmaterials;
+  rl::DevBuf<rl_rtc_light> d_lights;
+  rl::DevBuf<rl_rtc_shape> d_shapes;
+  rl::DevBuf<rl_rtc_csg> d_csgs;
+  rl::DevBuf<rl_rtc_pattern> d_patterns;
+  rl::DevBuf<rl::RtcGuard> d_guards;
+  rl::Event ev0, ev1;  // bracket the kernels of a counting render
   // Renders of one scene may be issued from several host threads and on several streams at once (the reference's Camera::render takes
   // &self, camera.rs:122).  The scene owns ONE set of work buffers, so: `mu` serialises the host side (enqueueing a render and handing
   // its status over, in one hold: a multi-GPU frame posts every replica's status before it lets go), and a render enqueued on another
@@ -102,48 +106,45 @@ struct rl_scene {
   // frames are rendered one after the other (each one fills the GPU anyway).
   mutable std::mutex mu;
   hipStream_t last_stream = nullptr;
-  hipEvent_t ev_last = nullptr;
+  rl::Event ev_last;
   bool has_last = false;
   // status of the asynchronous renders (opt_stats == NULL) not yet collected by rl_render_status: a ring of N_STATUS slots of 8 stats
   // words in pinned host memory, each behind the event that follows its copy; a slot that comes round again while still pending is
   // waited for and folded into `folded_*`, so no panic-site count is ever lost
   static constexpr int N_STATUS = 8;
-  unsigned long long *h_status = nullptr;  // [N_STATUS][8]
-  hipEvent_t ev_status[N_STATUS] = {};
+  rl::PinnedBuf<unsigned long long> h_status;  // [N_STATUS][8]
+  rl::Event ev_status[N_STATUS];
   bool status_pending[N_STATUS] = {};
   unsigned long long status_seq[N_STATUS] = {};
   int status_next = 0;
   unsigned long long next_seq = 0, folded_seq = 0, folded_rays = 0, folded_flagged = 0, folded_slow = 0;
-  // cost-sorted (LPT) two-phase render: per-pixel ChaCha word positions, per-tile cost and order
-  uint32_t *d_pos = nullptr, *d_tile_cost = nullptr, *d_tile_order = nullptr, *d_tile_keys = nullptr, *d_tile_iota = nullptr;
-  void *d_sort_temp = nullptr;
-  size_t sort_temp_bytes = 0;
-  size_t lpt_pix = 0, lpt_tiles = 0;
-  uint32_t *d_pixel_entry = nullptr;  // fast traversal: the current render's per-pixel entry words (rl_pixel_entry.h), grown on demand
-  size_t pixel_entry_pix = 0;
+  // cost-sorted (LPT) two-phase render: per-pixel ChaCha word positions, per-tile cost and order, the radix sort's scratch
+  rl::DevBuf<uint32_t> d_pos, d_tile_cost, d_tile_order, d_tile_keys, d_tile_iota;
+  rl::DevBuf<unsigned char> d_sort_temp;
+  rl::DevBuf<uint32_t> d_pixel_entry;  // fast traversal: the current render's per-pixel entry words (rl_pixel_entry.h), grown on demand
   // multi-GPU: this replica's row shard / on replica 0 the gather buffer [G][max_rows][W][3]
-  double *d_shard = nullptr;
-  size_t shard_bytes = 0;
-  hipEvent_t ev_gather_read = nullptr;  // replica 0: recorded behind the de-interleave kernel that reads the gather slots
+  rl::DevBuf<double> d_shard;
+  rl::Event ev_gather_read;  // replica 0: recorded behind the de-interleave kernel that reads the gather slots
   bool ev_gather_read_valid = false;
   // wavefront form (rl_rtiow_wfg.h): per-pixel records, ray records, the two queues, control words, the polled word in pinned memory
-  void *d_wfg_pix = nullptr, *d_wfg_ray = nullptr;
-  uint32_t *d_wfg_q0 = nullptr, *d_wfg_q1 = nullptr, *d_wfg_qs = nullptr, *d_wfg_ctl = nullptr;
-  size_t wfg_pix_cap = 0, wfg_slot_cap = 0;
-  void *h_wfg = nullptr;
+  rl::DevBuf<unsigned char> d_wfg_pix, d_wfg_ray;
+  rl::DevBuf<uint32_t> d_wfg_q0, d_wfg_q1, d_wfg_qs, d_wfg_ctl;
+  rl::PinnedBuf<uint32_t> h_wfg;
   // rl_rtiow_render_progress (opt-in: its first call switches it on for the renders that follow): the kernels' work counters then live
   // in two words of pinned HOST memory the device reaches over PCIe — [0] the first (or only) launch of a render, [1] the cost-sorted
   // resume launch — so that the host reads them with plain loads while the kernels run; `progress_total` = slots of the render enqueued last
   bool progress_on = false;
   unsigned long long progress_total = 0;
-  uint32_t *h_progress = nullptr;   // host address
-  uint32_t *d_progress = nullptr;   // the same words as the device sees them
-  void *d_params = nullptr;  // device copies (two slots) of the parameter block for the kernels that take it by pointer
+  rl::PinnedBuf<uint32_t> h_progress;  // host address
+  uint32_t *d_progress = nullptr;      // the same words as the device sees them (not an allocation of its own)
+  rl::DevBuf<unsigned char> d_params;  // device copies (two slots) of the parameter block for the kernels that take it by pointer
   unsigned params_slot = 0;
-  uint32_t *d_pix_rays = nullptr;  // debug (tools/): per-pixel ray counts of the last counting render
-  double *d_indep = nullptr;       // sample-parallel mode: the pass buffer [samples of a pass][shard pixels][3] (rl_rtiow_render_independent*)
-  size_t indep_bytes = 0;
-  void *exp = nullptr;             // experimental kernels' work buffers (rl_render.hip, RL_EXPERIMENTAL builds only)
+  rl::DevBuf<uint32_t> d_pix_rays;  // debug (tools/): per-pixel ray counts of the last counting render
+  rl::DevBuf<double> d_indep;       // sample-parallel mode: the pass buffer [samples of a pass][shard pixels][3] (rl_rtiow_render_independent*)
+  rl::ExpBuffers exp;               // experimental kernels' work buffers (used by RL_EXPERIMENTAL builds only)
+  // per-scene scratch: [0] work counter (u32), [64..] 8 x u64 stats, [128..] scheduler debug counters.  Declared LAST, so released FIRST:
+  // every scene has it, and its hipFree waits for the device's work in flight before the events and the pinned memory above go.
+  rl::DevBuf<unsigned char> d_scratch;
 };
 
 namespace rl {

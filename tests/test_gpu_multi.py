@@ -28,6 +28,7 @@ def golden(name):
 # ---- single context first: the reference frames
 api.init(0)
 assert api.render_lib().rl_device_count() == 1
+live0 = api.live_buffers()   # device allocations the library owns before any scene of this process exists
 world = rl.World.bouncing_spheres(1)
 p = world.params
 p.image_width, p.samples_per_pixel, p.max_depth = 101, 66, 50   # 101 x 56: ragged against every G; 66 spp: two-launch path
@@ -96,6 +97,12 @@ n = api.init_multi(0)
 assert n >= 1
 wn = rl.World.bouncing_spheres(1)
 assert np.array_equal(cam.render_multi(wn).data, single)
+# every scene of this process (replicas, shard and gather buffers included) has released what it owned
+assert api.live_buffers() > live0
+del wn
+import gc
+gc.collect()
+assert api.live_buffers() == live0, (api.live_buffers(), live0)
 print("MULTI_OK", n, int(api.render_lib().rl_debug_multi_uses_rccl()))
 '''
 
