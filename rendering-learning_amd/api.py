@@ -330,6 +330,14 @@ def set_pixel_entry(max_entries):
     L.rl_debug_set_pixel_entry(int(max_entries))
 
 
+def set_pixel_entry_sphere(on):
+    """Tests / tools: the entry cut keeps only the leaves whose SPHERE the pixel's beam may touch (default); off: every leaf whose padded box
+    it touches, the box-only cut (csrc/rl_pixel_entry.h; the same switch as RL_PIXEL_ENTRY_SPHERE)."""
+    L = render_lib()
+    L.rl_debug_set_pixel_entry_sphere.argtypes = [C.c_int]
+    L.rl_debug_set_pixel_entry_sphere(int(bool(on)))
+
+
 def pixel_entry_table(world, n_pixels):
     """Tests: the entry words of the scene's most recent fast-traversal render (finished), one uint32 per pixel of the rows it rendered."""
     L = render_lib()

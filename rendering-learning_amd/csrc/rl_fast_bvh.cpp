@@ -185,6 +185,24 @@ bool build_fast_bvh(const rl_rtiow_scene_desc &d, const RtiowProgram &rt, const 
   return true;
 }
 
+// The ball the entry table tests a leaf's sphere with: centre at time 1/2, R = r + pad + |dc| / 2, where pad is the largest of the three pads
+// of the sphere's leaf box above (>= guard_pad: a ray that stays R away from this centre stays r + guard_pad away from the centre at every
+// time in [0, 1], and its rounded discriminant is negative).  Everything is rounded upwards by a relative 1e-12, thousands of roundings.
+void fast_leaf_balls(const rl_rtiow_scene_desc &d, const GuardFrame &f, std::vector<double> &balls) {
+  balls.assign((size_t)d.n_spheres * 4, 0.0);
+  for (uint32_t i = 0; i < d.n_spheres; i++) {
+    const rl_sphere &sp = d.spheres[i];
+    double r = std::fabs(sp.radius), pad = guard_pad(f, r), dc2 = 0.0, cmax = 0.0;
+    for (int ax = 0; ax < 3; ax++) {
+      double c0 = sp.center0[ax], c1 = sp.moving ? sp.center1[ax] : sp.center0[ax];
+      pad = std::fmax(pad, 1e-9 * (std::fabs(std::fmin(c0, c1) - r) + std::fabs(std::fmax(c0, c1) + r) + r));
+      balls[(size_t)i * 4 + ax] = 0.5 * c0 + 0.5 * c1;
+      dc2 += (c1 - c0) * (c1 - c0);
+      cmax = std::fmax(cmax, std::fmax(std::fabs(c0), std::fabs(c1)));
+    }
+    balls[(size_t)i * 4 + 3] = (r + pad + 0.5 * std::sqrt(dc2)) * (1.0 + 1e-12) + 1e-12 * cmax;  // (+ the rounding of the midpoint and of c0 + dc t)
+  }
+}
 
 // =====================================================================================================================
 // General scenes: world-space tree over primitive occurrences.

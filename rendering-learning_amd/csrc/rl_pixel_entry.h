@@ -5,7 +5,8 @@
 // the walk once per pixel: it walks the tree with the pixel's BEAM — every ray get_ray (camera.rs:203-216, the GEN block) can produce for
 // the pixel — and writes one word per pixel, the entries a camera ray of that pixel starts from instead of the root:
 //     word = e0 | e1 << 10 | e2 << 20 | 3 << 30        (entry ids as on the walk's stack, FAST_NONE = unused, e0 is visited first)
-// The entries are disjoint subtrees (or leaves) that together hold every leaf whose box some ray of the beam touches:
+// The entries are disjoint subtrees (or leaves) that together hold every leaf the beam may touch — its box is touched by some ray of the
+// beam AND (RL_PIXEL_ENTRY_SPHERE, default on) the beam is not proven to miss the sphere itself, see "The sphere test" below:
 //     no such leaf -> all FAST_NONE (the sample is a miss without a single step);  one -> that leaf;  otherwise the deepest inner node
 //     whose subtree holds them all, and with max_entries = 2 / 3 that node split once / twice into the reduced entries of its children
 //     (the child subtree's own deepest holder), nearest first by the beam's entry distance.
@@ -15,6 +16,14 @@
 // window: it can neither be the answer, nor be within a tie band of the answer, nor trip an order check, and the root walk — whether
 // it rejects that sphere's boxes or visits them — gets nothing from it.  Inside an entry's subtree the walk is the root walk's own
 // reject-only walk.  So answer, amb flag, re-traces and panic-site counts are those of the root walk for every ray it trusts.
+// A leaf that only the sphere test removed has its box touched, so the box-only cut visits it.  No point (t >= 0) of any camera ray of
+// the pixel lies within r + pad of its centre, pad = guard_pad (the sphere grown by it lies inside the leaf box; the ball tested below is larger still).  Either the ray's LINE stays that far away too: then r^2 - b^2 <= -2 r pad
+// and by the guard_pad argument the rounded discriminant is negative, fast_sphere_hit returns at `disc < 0`.  Or the line meets the
+// sphere behind the origin only: then c = |oc|^2 - r^2 >= 2 r pad, eight times what rounding moves a c by, so the rounded a c is positive and
+// disc <= RN(half_b^2), sq <= |half_b| (sqrt of a rounded square returns the magnitude), and half_b > 0: both rounded roots are <= 0 < 1e-10
+// and the visit returns at the window test.  Both returns come before closest, hit_prim or amb are touched: the visit the box-only cut
+// pays changes nothing, and answer, re-traces (slow_traces) and panic-site counts are those of the box-only table.
+// (No occlusion culling here: a leaf behind a sphere the whole beam hits stays, since dropping it would change which rays are re-traced.)
 //
 // The beam test is CONSERVATIVE: "missed" only when no ray of the beam touches the stored box.  A ray is o + t d, t >= 0, with
 // o = lookfrom + a U + b V (|(a, b)| <= 1; U = V = 0 without defocus) and o + d = T = pixel_center + sx du + sy dv, |sx|, |sy| <= 1/2; so
@@ -31,6 +40,23 @@
 // solved by one subtraction and one division each (relative error <= 2.01u in the bound of t, sign exact); an interval [lo, hi] of t
 // counts as empty only when lo > hi + 1e-12 (|lo| + |hi|), five thousand times those roundings.  NaN fails every comparison and fmax / fmin
 // drop it: a NaN or infinity anywhere removes constraints, never adds one, and a non-finite delta makes every box "touched".
+//
+// The sphere test (leaves only; inner nodes keep the box test).  Camera rays skim the sphere field and cross many box corners without
+// meeting the sphere; each such leaf in a word costs every camera ray of the pixel a binary64 Sphere::hit that ends at the discriminant.
+// With the axis A(t) = (1 - t) lookfrom + t pixel_center, a point of the beam is P(t) - A(t) = (1 - t)(a U + b V) + t (sx du + sy dv), so
+//     |P(t) - A(t)| <= w(t) = |1 - t| rho_o + t rho_t,    rho_o = the largest singular value of [U V] (0 without defocus) >= |a U + b V|,
+//                                                         rho_t = max(|du + dv|, |du - dv|) / 2 >= |sx du + sy dv|  (convex: a corner)
+// and |P(t) - c| >= dist - w(t) for a centre c at distance dist from the axis LINE.  A ray can be within the sphere only while it is inside
+// the sphere's padded box, i.e. for t in the hull [t_lo, t_hi] of the non-empty pieces beam_touches finds, and w is convex, so
+//     dist - max(w(t_lo), w(t_hi)) > R      =>      no point of any ray of the beam lies within R of c.
+// R = r + pad + |dc| / 2 around the centre at time 1/2 (rl_fast_bvh.cpp fast_leaf_balls; a moving centre stays within |dc| / 2 of it, pad is
+// the largest pad of the sphere's leaf box, >= guard_pad).  Rounding.  The axis is the line through the ROUNDED lookfrom and pixel_center,
+// exact by definition; the rounded ray's points lie within 18u M (1 + t) of the exact beam's and pixel_center within 8u M (above), so w
+// gets the same delta (1 + t) as the box lines.  t_lo and t_hi carry <= 2.01u relative error and w has slope <= rho_o + rho_t + delta <= 2 M:
+// 5u M t, inside that delta as well.  rho_o and rho_t are grown by 2^-40 relative (a dozen roundings each).  dist = |(c - lookfrom) x D| / |D|:
+// the difference carries u (|c| + |lookfrom|) per axis, each component of the product 4u |c - lookfrom| |D|, root and quotient 3u:
+// under 16u (|c| + |lookfrom|) in all, and the test allows eps = 2^-40 (|c|_1 + |lookfrom|_1 + R), five hundred times that.  An infinite t_hi
+// and a NaN w are tested for; a non-finite R, dist or delta, or D = 0 (NaN by 0 * inf) fail the final comparison: "touched".  The test only ever removes a leaf.
 #pragma once
 #include "rl_rtiow_kernel.h"
 
@@ -42,17 +68,19 @@ static constexpr int PIXEL_ENTRY_DEFAULT = 3;
 struct PixelBeam {
   double olo[3], ohi[3], tlo[3], thi[3];  // origin and target intervals per axis (not yet pushed outwards)
   double delta;
+  // the sphere test: axis origin and direction (rounded lookfrom, pixel_center - lookfrom), 1 / |dir|, the radii of w(t) (grown)
+  double f[3], dir[3], inv_len, rho_o, rho_t;
 };
 
-// true when some ray of the beam MAY touch the box b = {x.min, x.max, y.min, y.max, z.min, z.max}; t_near: a lower bound of t over the touching rays
-__device__ __forceinline__ bool beam_touches(const PixelBeam &B, const float *b, double &t_near) {
+// true when some ray of the beam MAY touch the box b = {x.min, x.max, y.min, y.max, z.min, z.max}; [t_near, t_far]: the hull of t over the touching rays
+__device__ __forceinline__ bool beam_touches(const PixelBeam &B, const float *b, double &t_near, double &t_far) {
   const double INF = __longlong_as_double(0x7FF0000000000000ll);
   if (!(B.delta < INF)) {  // also NaN
-    t_near = 0.0;
+    t_near = 0.0, t_far = INF;
     return true;
   }
   bool touched = false;
-  t_near = INF;
+  t_near = INF, t_far = 0.0;
 #pragma unroll
   for (int piece = 0; piece < 2; piece++) {
     double lo = piece ? 1.0 : 0.0, hi = piece ? INF : 1.0;
@@ -75,9 +103,33 @@ __device__ __forceinline__ bool beam_touches(const PixelBeam &B, const float *b,
       else if (c > 0.0) empty = true;
     }
     if (lo > hi + 1e-12 * (fabs(lo) + fabs(hi))) empty = true;
-    if (!empty) touched = true, t_near = fmin(t_near, lo);
+    if (!empty) touched = true, t_near = fmin(t_near, lo), t_far = fmax(t_far, hi);
   }
   return touched;
+}
+__device__ __forceinline__ bool beam_touches(const PixelBeam &B, const float *b, double &t_near) {
+  double t_far;
+  return beam_touches(B, b, t_near, t_far);
+}
+
+// false only when NO ray of the beam comes within R of c while t is in [t_lo, t_hi], ball = {c.x, c.y, c.z, R} (header: the sphere test)
+__device__ __forceinline__ bool beam_may_touch_ball(const PixelBeam &B, const double *ball, double t_lo, double t_hi) {
+  if (!(t_hi < __longlong_as_double(0x7FF0000000000000ll))) return true;  // (also NaN; with rho_o = 0 an infinite t would make w NaN, which fmax drops)
+  const double ax = ball[0] - B.f[0], ay = ball[1] - B.f[1], az = ball[2] - B.f[2], R = ball[3];
+  const double cx = ay * B.dir[2] - az * B.dir[1], cy = az * B.dir[0] - ax * B.dir[2], cz = ax * B.dir[1] - ay * B.dir[0];
+  const double dist = sqrt(cx * cx + cy * cy + cz * cz) * B.inv_len;
+  const double w_lo = fabs(1.0 - t_lo) * B.rho_o + t_lo * B.rho_t + B.delta * (1.0 + t_lo);
+  const double w_hi = fabs(1.0 - t_hi) * B.rho_o + t_hi * B.rho_t + B.delta * (1.0 + t_hi);
+  const double eps = 0x1.0p-40 * (fabs(ball[0]) + fabs(ball[1]) + fabs(ball[2]) + fabs(B.f[0]) + fabs(B.f[1]) + fabs(B.f[2]) + R);
+  if (!(w_lo >= 0.0 && w_hi >= 0.0)) return true;  // NaN
+  return !(dist - fmax(w_lo, w_hi) - eps > R);
+}
+
+// a leaf: its box and, with `balls`, its sphere
+__device__ __forceinline__ bool beam_touches_leaf(const PixelBeam &B, const float *box, const double *balls, uint32_t sphere, double &t_near) {
+  double t_far;
+  if (!beam_touches(B, box, t_near, t_far)) return false;
+  return !balls || beam_may_touch_ball(B, balls + (size_t)sphere * 4, t_near, t_far);
 }
 
 // What a subtree reduces to: the number of its leaves the beam may touch, the deepest entry that holds them all, the nearest t among them
@@ -87,7 +139,8 @@ struct EntryCut {
 };
 
 // Reduces the subtree of entry e (its own box already found touched, at t_e): post-order walk with an explicit stack, depth <= FAST_MAX_DEPTH
-__device__ __forceinline__ EntryCut reduce_subtree(const RtiowParams &P, const PixelBeam &B, uint32_t e, double t_e) {
+// (a leaf e has passed beam_touches_leaf at its parent; balls: null = box-only cut)
+__device__ __forceinline__ EntryCut reduce_subtree(const RtiowParams &P, const PixelBeam &B, const double *balls, uint32_t e, double t_e) {
   if (e >= P.n_fast_inner) return EntryCut{1u, e, t_e};
   const double INF = __longlong_as_double(0x7FF0000000000000ll);
   constexpr int MAXD = (int)FAST_MAX_DEPTH + 2;
@@ -107,9 +160,10 @@ __device__ __forceinline__ EntryCut reduce_subtree(const RtiowParams &P, const P
       const uint32_t ce = side ? (nd.child >> 16) : (nd.child & 0xFFFFu);
       double tc;
       done = EntryCut{0u, FAST_NONE, INF};
-      if (beam_touches(B, nd.box[side], tc)) {
-        if (ce >= P.n_fast_inner) done = EntryCut{1u, ce, tc};
-        else if (sp + 1 < MAXD) {  // (always: the tree is at most FAST_MAX_DEPTH deep)
+      if (ce >= P.n_fast_inner) {
+        if (beam_touches_leaf(B, nd.box[side], balls, ce - P.n_fast_inner, tc)) done = EntryCut{1u, ce, tc};
+      } else if (beam_touches(B, nd.box[side], tc)) {
+        if (sp + 1 < MAXD) {  // (always: the tree is at most FAST_MAX_DEPTH deep)
           sp++;
           node[sp] = ce, phase[sp] = 0, acc[sp] = EntryCut{0u, FAST_NONE, INF};
           continue;
@@ -127,7 +181,7 @@ __device__ __forceinline__ EntryCut reduce_subtree(const RtiowParams &P, const P
 }
 
 // One thread per pixel of the rows this call renders: out[pr * W + px] (the kernels' shard-local pixel index)
-__global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(RtiowParams P, const float *leaf_boxes, uint32_t max_entries, uint32_t *out) {
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(RtiowParams P, const float *leaf_boxes, const double *leaf_balls, uint32_t max_entries, uint32_t *out) {
   const uint32_t W = P.cam.image_width;
   const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (uint64_t)P.nrows * W) return;
@@ -135,7 +189,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(
   const uint32_t y = P.row_first + pr * P.row_step;
   const rl_rtiow_camera &cam = P.cam;
   PixelBeam B;
-  double M = 0.0;
+  double M = 0.0, len2 = 0.0, uu = 0.0, vv = 0.0, uv = 0.0, dp2 = 0.0, dm2 = 0.0;
   const bool lens = !(cam.defocus_angle <= 0.0);  // (NaN: GEN takes the disc branch too)
 #pragma unroll
   for (int k = 0; k < 3; k++) {
@@ -146,7 +200,15 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(
     B.olo[k] = cam.lookfrom[k] - ho, B.ohi[k] = cam.lookfrom[k] + ho;
     M = fmax(M, fabs(cam.pixel_00[k]) + fabs(cam.pixel_du[k]) * (double)W + fabs(cam.pixel_dv[k]) * (double)cam.image_height + fabs(cam.lookfrom[k]) +
                     fabs(cam.defocus_disk_u[k]) + fabs(cam.defocus_disk_v[k]));
+    B.f[k] = cam.lookfrom[k], B.dir[k] = pc - cam.lookfrom[k];
+    len2 += B.dir[k] * B.dir[k];
+    const double U = cam.defocus_disk_u[k], V = cam.defocus_disk_v[k], dp = cam.pixel_du[k] + cam.pixel_dv[k], dm = cam.pixel_du[k] - cam.pixel_dv[k];
+    uu += U * U, vv += V * V, uv += U * V, dp2 += dp * dp, dm2 += dm * dm;
   }
+  B.inv_len = 1.0 / sqrt(len2);
+  B.rho_o = lens ? sqrt(0.5 * ((uu + vv) + sqrt((uu - vv) * (uu - vv) + 4.0 * uv * uv))) * (1.0 + 0x1.0p-40) : 0.0;
+  B.rho_t = 0.5 * sqrt(fmax(dp2, dm2)) * (1.0 + 0x1.0p-40);
+  if (!(B.rho_o >= 0.0) || !(B.rho_t >= 0.0)) leaf_balls = nullptr;  // NaN: the box-only cut
   B.delta = M * 0x1.0p-40;
   if (!(M >= 0.0)) B.delta = __longlong_as_double(0x7FF0000000000000ll);  // NaN
   // the root: a leaf of its own (one sphere, no node) is tested against its leaf box, an inner node is walked
@@ -155,9 +217,9 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(
   uint32_t nc = 1;
   if (root >= P.n_fast_inner) {
     double t0;
-    const bool hit = beam_touches(B, leaf_boxes + (size_t)(root - P.n_fast_inner) * 8, t0);
+    const bool hit = beam_touches_leaf(B, leaf_boxes + (size_t)(root - P.n_fast_inner) * 8, leaf_balls, root - P.n_fast_inner, t0);
     c[0] = hit ? EntryCut{1u, root, t0} : EntryCut{0u, FAST_NONE, 0.0};
-  } else c[0] = reduce_subtree(P, B, root, 0.0);
+  } else c[0] = reduce_subtree(P, B, leaf_balls, root, 0.0);
   // split the holder of several leaves into its children's reduced entries, the one with the most leaves first, up to max_entries
   while (nc < max_entries && nc < 3u) {
     uint32_t pick = 3u, best = 1u;
@@ -166,10 +228,11 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(
     if (pick == 3u) break;
     const FastNode &nd = P.fast_nodes[c[pick].entry];
     double ta, tb;
-    // (a holder of several leaves has them on both sides: both boxes are touched, and both reductions count at least one)
+    // (a holder of several leaves has them on both sides: both boxes are touched, both reductions count at least one, and a child that is
+    // a leaf itself is one the reduction accepted)
     const bool ha = beam_touches(B, nd.box[0], ta), hb = beam_touches(B, nd.box[1], tb);
     if (!(ha && hb)) break;
-    const EntryCut ra = reduce_subtree(P, B, nd.child & 0xFFFFu, ta), rb = reduce_subtree(P, B, nd.child >> 16, tb);
+    const EntryCut ra = reduce_subtree(P, B, leaf_balls, nd.child & 0xFFFFu, ta), rb = reduce_subtree(P, B, leaf_balls, nd.child >> 16, tb);
     if (ra.count == 0u || rb.count == 0u) break;
     c[pick] = ra, c[nc++] = rb;
   }

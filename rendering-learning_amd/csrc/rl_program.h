@@ -127,6 +127,9 @@ double guard_pad(const GuardFrame &f, double radius);  // how far outside a sphe
 // Fast traversal structure for a sphere-only scene; false when the scene does not qualify (too many spheres for the LDS budget,
 // degenerate spheres, spheres referenced more than once or not at all...).  root_entry: entry id a new ray starts at.
 bool build_fast_bvh(const rl_rtiow_scene_desc &d, const RtiowProgram &rt, const GuardFrame &f, std::vector<FastNode> &nodes, uint32_t &root_entry);
+// For a scene build_fast_bvh accepted: per sphere {c.x, c.y, c.z, R}, a ball that holds the sphere grown by its leaf box's pad at every time
+// in [0, 1] (the per-pixel entry table's sphere test, rl_pixel_entry.h)
+void fast_leaf_balls(const rl_rtiow_scene_desc &d, const GuardFrame &f, std::vector<double> &balls);
 
 // ---- fast traversal structure for GENERAL scenes (planars, instances, any number of primitives; rl_fast_bvh.cpp, rl_rtiow_fastgen.h):
 // a surface-area-heuristic binary tree in WORLD space over the primitive OCCURRENCES of the threaded program (a primitive under a

@@ -71,6 +71,7 @@ struct Switches {
   unsigned indep_k = 1;          // RL_INDEP_K=<k>: samples of one pixel per claim in the sample-parallel mode
   size_t indep_cap = (size_t)1 << 30;  // RL_INDEP_CAP_MB=<MiB>: cap of that mode's pass buffer (a smaller one forces more passes: tests)
   int pixel_entry = rl::PIXEL_ENTRY_DEFAULT;  // RL_PIXEL_ENTRY=0|1|2|3: the fast kernel's camera rays start at the root / at their pixel's entry cut of up to n entries (rl_pixel_entry.h)
+  bool pixel_entry_sphere = true;  // RL_PIXEL_ENTRY_SPHERE=0: that cut keeps every leaf whose BOX the pixel's beam touches; default: only those whose sphere it may touch
 } g_sw;
 unsigned long long g_last_slow_traces = 0;
 bool g_fast_debug_stats = false;  // tools only (experimental library): counting renders run the fast kernel too (counters are then NOT the reference's)
@@ -110,6 +111,7 @@ void read_switches() {
   if (const char *v = std::getenv("RL_RTC_FULL_REGS")) w.rtc_full_regs = std::atoi(v);
   if (const char *v = std::getenv("RL_INDEP_K")) w.indep_k = (unsigned)std::max(1, std::atoi(v));
   if (const char *v = std::getenv("RL_PIXEL_ENTRY")) w.pixel_entry = std::min(3, std::max(0, std::atoi(v)));
+  if (const char *v = std::getenv("RL_PIXEL_ENTRY_SPHERE")) w.pixel_entry_sphere = std::string(v) != "0";
   if (const char *v = std::getenv("RL_INDEP_CAP_MB")) w.indep_cap = (size_t)std::max(1, std::atoi(v)) << 20;
   g_sw = w;
 #ifdef RL_EXPERIMENTAL
@@ -447,6 +449,7 @@ static int build_host_rtiow(const rl_rtiow_scene_desc *desc, std::shared_ptr<con
           const uint32_t e = k == 0 ? (nd.child & 0xFFFFu) : (nd.child >> 16);
           if (e >= n_inner && e - n_inner < ns) std::memcpy(&H->fast_leaf_boxes[(size_t)(e - n_inner) * 8], nd.box[k], 6 * sizeof(float));
         }
+      fast_leaf_balls(*desc, frame, H->fast_leaf_balls);
     }
     // ray queries walk the four-wide world-space tree on every kind of scene (rl_ray_query.h rtiow_hit_rays_fast_kernel)
     if (rt.ops.size() < (1u << 31) && !build_fast_general(*desc, rt, H->qfg)) H->qfg = FastGeneral{};
@@ -472,7 +475,8 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
       (rc = scene_common(s)) ||
       (!H->lops.empty() && ((rc = s->d_lops.upload(H->lops)) || (rc = s->d_sphere_flat.upload(H->sphere_flat)))) ||
       (!H->cops.empty() && ((rc = s->d_cops.upload(H->cops)) || (rc = s->d_movbits.upload(H->movbits)))) ||
-      (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)))) ||
+      (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)) ||
+                                      (rc = s->d_fast_leaf_balls.upload(H->fast_leaf_balls)))) ||
       (QF.ok && ((rc = s->d_fg_nodes.upload(QF.qnodes)) || (rc = s->d_fg_onodes.upload(QF.onodes)) || (rc = s->d_fg_seg_roots.upload(QF.stage_roots)) ||
                  (rc = s->d_fg_media.upload(QF.media)) || (rc = s->d_fg_items.upload(QF.items)) || (rc = s->d_fg_spheres.upload(QF.item_spheres)) || (rc = s->d_fg_material.upload(QF.item_material))))) {
     destroy_one(s);
@@ -851,8 +855,8 @@ static int build_pixel_entry(const rl_scene *scene, RtiowParams &P, uint32_t nro
   if (g_sw.pixel_entry <= 0 || npix == 0) return RL_OK;
   rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only
   HIP_TRY(ms->d_pixel_entry.reserve(npix));
-  hipLaunchKernelGGL(rtiow_pixel_entry_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, P, (const float *)scene->d_fast_leaf_boxes, (uint32_t)g_sw.pixel_entry,
-                     ms->d_pixel_entry);
+  hipLaunchKernelGGL(rtiow_pixel_entry_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, P, (const float *)scene->d_fast_leaf_boxes,
+                     g_sw.pixel_entry_sphere ? (const double *)scene->d_fast_leaf_balls : (const double *)nullptr, (uint32_t)g_sw.pixel_entry, ms->d_pixel_entry);
   HIP_TRY(hipGetLastError());
   P.pixel_entry = ms->d_pixel_entry;
   return RL_OK;
@@ -1564,6 +1568,7 @@ void rl_debug_set_rtc_blocks(int per_cu) { g_sw.rtc_blocks_per_cu = per_cu < 0 ?
 void rl_debug_set_indep_cap(unsigned long long bytes) { g_sw.indep_cap = bytes ? (size_t)bytes : (size_t)1 << 30; }  // sample-parallel pass buffer cap (0: default 1 GiB)
 void rl_debug_set_indep_k(unsigned k) { g_sw.indep_k = k ? k : 1u; }  // samples of one pixel per claim in the sample-parallel mode
 void rl_debug_set_pixel_entry(int max_entries) { g_sw.pixel_entry = std::min(3, std::max(0, max_entries)); }  // 0: camera rays start at the root (A/B, tests)
+void rl_debug_set_pixel_entry_sphere(int on) { g_sw.pixel_entry_sphere = on != 0; }  // 0: the box-only cut (A/B, tests)
 // Tests: the entry table of the scene's most recent fast-traversal render (n_pixels words, rows x W of the shard rendered), after that render has finished
 int rl_debug_pixel_entry_read(const rl_scene *scene, uint32_t *out, uint64_t n_pixels) {
   if (!scene || !out || !scene->d_pixel_entry || n_pixels > scene->d_pixel_entry.size()) return RL_E_INVALID;
@@ -1622,7 +1627,8 @@ int rl_debug_has_experimental(void) {
 void rl_debug_live_buffers(unsigned long long out[2]) { out[0] = rl::g_live_buffers.load(), out[1] = rl::g_live_bytes.load(); }
 
 // Not part of the ABI (tools only): scheduler occupancy counters of the last STATS launch, 32 x u64 ([3s .. 3s+2] per state; [24]: the
-// fast kernel's skipped self tests, rl_rtiow_wave.h fast_self_miss).
+// fast kernel's skipped self tests, rl_rtiow_wave.h fast_self_miss; [25 .. 28]: the camera rays' TRAV lane-steps, LEAF visits, number, and
+// LEAF visits that ended at disc < 0).
 int rl_debug_sched(const rl_scene *scene, unsigned long long *out32) {
   if (!scene || !out32) return RL_E_INVALID;
   HIP_TRY(hipMemcpy(out32, scene->d_scratch + 128, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));

@@ -98,7 +98,8 @@
   uint32_t c_rays = 0, c_flag = 0, c_slow = 0;  // c_slow: rays the fast traversal handed to the reference-order fold
   unsigned long long c_nodes = 0, c_sph = 0, c_words = 0, c_self = 0;  // c_self (STATS): self tests skipped
   // STATS census (tools/sched.py): the camera rays' share — a camera ray is the one whose remaining depth is still cam.max_depth
-  unsigned long long c_cam_trav = 0, c_cam_leaf = 0, c_cam_rays = 0;
+  // c_cam_miss: those of their LEAF visits that return at the discriminant test (disc < 0) — a sphere whose box the ray passed but not the sphere
+  unsigned long long c_cam_trav = 0, c_cam_leaf = 0, c_cam_rays = 0, c_cam_miss = 0;
 
   // fast traversal (LDS_SCENE = 4): 16 ten-bit entry ids in five registers, newest in the low bits of stk0; all ones = empty
   uint32_t stk0 = ~0u, stk1 = ~0u, stk2 = ~0u, stk3 = ~0u, stk4 = ~0u;
@@ -400,7 +401,10 @@
             const uint32_t sidx = pc - P.n_fast_inner;
             const uint32_t payload = sidx | (((s_bits[sidx >> 5] >> (sidx & 31u)) & 1u) ? SPH_MOVING : 0u);
             if (STATS) c_sph++;
-            if (STATS && (depth & DEPTH_MASK) == cam.max_depth) c_cam_leaf++;
+            if (STATS && (depth & DEPTH_MASK) == cam.max_depth) {
+              c_cam_leaf++;
+              if (fast_sphere_misses(spheres[sidx], payload, o, d, time)) c_cam_miss++;
+            }
             if (SPLIT_LEAF) {
               if (fast_sphere_misses(spheres[sidx], payload, o, d, time)) fast_go(fast_pop());
               else state = ST_LEAF2;
@@ -646,5 +650,7 @@
       if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 26], v);
       v = wave_sum(c_cam_rays);
       if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 27], v);
+      v = wave_sum(c_cam_miss);  // out[28]
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 28], v);
     }
   }

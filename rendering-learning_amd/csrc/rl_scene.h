@@ -32,6 +32,7 @@ struct HostRtiow {
   std::vector<FastNode> fast_nodes;  // fast traversal structure (rl_fast_bvh.cpp); fast_root == FAST_NONE: the scene does not qualify
   uint32_t fast_root = FAST_NONE;
   std::vector<float> fast_leaf_boxes;  // [n_spheres][8]: each sphere's padded leaf box of the fast tree (rl_rtiow_coop.h)
+  std::vector<double> fast_leaf_balls;  // [n_spheres][4]: centre and radius of a ball around each padded sphere (rl_fast_bvh.cpp fast_leaf_balls)
   FastGeneral fg;  // fast traversal structure of a general scene (fg.ok == false: the scene does not qualify)
   FastGeneral qfg;  // sphere-only scenes: the same structure for ray queries (rl_ray_query.h; the renders walk fast_nodes from LDS instead)
   const FastGeneral &query_tree() const { return fg.ok ? fg : qfg; }
@@ -68,6 +69,7 @@ struct rl_scene {
   rl::DevBuf<uint32_t> d_movbits;
   rl::DevBuf<rl::FastNode> d_fast_nodes;
   rl::DevBuf<float> d_fast_leaf_boxes;
+  rl::DevBuf<double> d_fast_leaf_balls;
   rl::DevBuf<uint32_t> d_coop_pixels;  // cooperative kernel: pixel list (scratch, grown on demand)
   rl::DevBuf<uint32_t> d_steal_state, d_steal_n;  // work stealing on small shards (RtiowParams::steal_state)
   rl::DevBuf<rl::FastNodeQ> d_fg_nodes;

@@ -22,6 +22,8 @@ if out[27]:  # census of the fast kernel's camera rays (remaining depth still ma
     print(f"camera rays {out[27]} ({100 * out[27] / st['rays']:.1f} % of the rays)  TRAV lane-steps {out[25]} of {trav} ({100 * out[25] / max(trav, 1):.1f} %, "
           f"{out[25] / out[27]:.2f} per camera ray, {(trav - out[25]) / max(st['rays'] - out[27], 1):.2f} per scattered ray)  "
           f"LEAF visits {out[26]} of {leaf} ({100 * out[26] / max(leaf, 1):.1f} %, {out[26] / out[27]:.3f} per camera ray)")
+    # of those, the visits that end at the discriminant test: the ray passed the sphere's box, not the sphere
+    print(f"camera LEAF visits with disc < 0: {out[28]} ({out[28] / out[27]:.3f} per camera ray, {100 * out[28] / max(leaf, 1):.1f} % of all LEAF visits)")
 tot = sum(out[3 * k + 2] for k in names)
 for k, nm in names.items():
     ex, pop, cyc = out[3 * k], out[3 * k + 1], out[3 * k + 2]
