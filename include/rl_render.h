@@ -530,6 +530,53 @@ int rl_rtiow_ray_color_rays_device(const rl_scene *, const void *d_rays, const v
                                    uint32_t max_depth, const double background[3], void *d_out_rgb, void *d_opt_out_cursors,
                                    void *d_opt_out_ray_counts, void *hip_stream, rl_stats *opt_stats);
 
+/* =====================================================================
+ *  Material queries: Material::scatter, Material::emitted and Texture::value for buffers
+ * =====================================================================
+ *   rl_rtiow_scatter_rays*    <- ray-tracing-one-weekend/src/material.rs:11-20  Material::scatter(&mut rng, &ray, &hit_record) -> Option<(Color, Ray)>
+ *                                and Material::emitted(u, v, &p)
+ *   rl_rtiow_texture_values*  <- ray-tracing-one-weekend/src/texture.rs  Texture::value(u, v, &p)
+ * What ray_color (camera.rs:232-260) does with a hit, as a primitive of its own: with rl_rtiow_hit_rays a host writes its own
+ * light-transport loop (its own depth rule, Russian roulette, probe rays, per-bounce buffers) and still shades as the library does.  The
+ * arithmetic is that of the render kernels, so the loop
+ *     sum = 0, thr = 1; up to max_depth times: hit = hit_rays(ray, tmin = 1e-10); a miss: sum += thr * background, stop;
+ *     s = scatter_rays(ray, hit, cursor); sum = sum + thr * s.emitted; s.scatter == 0: stop; thr = thr * s.attenuation; ray = s.scattered
+ * gives rl_rtiow_ray_color_rays' colours, cursors and ray counts bit for bit (scenes without ConstantMedium objects, which
+ * rl_rtiow_hit_rays refuses).  Cursors, seed and the word_pos rules are those of the seeded path queries above (odd positions are legal;
+ * word_pos >= 2^31 is RL_E_INVALID in the host form).  Status, concurrency, rl_init_multi, n = 0, NULL buffers and the wrong scene family:
+ * as stated for the batched ray queries. */
+typedef struct rl_rtiow_scatter { /* material.rs:11-20: scatter's Option<(Color, Ray)> + emitted's Color */
+  double attenuation[3];          /* zeros unless scatter == 1 */
+  double emitted[3];              /* mat.emitted(hit.u, hit.v, &hit.p) */
+  rl_ray scattered;               /* origin = hit.p, time = rays[i].time; zeros unless scatter == 1 */
+  uint32_t scatter;               /* 1: Some, 0: None (Flat, DiffuseLight, an absorbed Metal reflection, hit == 0) */
+  uint32_t _pad;
+} rl_rtiow_scatter;               /* 112 bytes */
+
+/* out[i]: mat = materials[hits[i].material], rng_i = cursors[i] of `seed`; emitted = mat.emitted(hits[i].u, hits[i].v, &hits[i].p) and
+ * mat.scatter(&mut rng_i, &rays[i], &hits[i]); opt_out_cursors[i] = rng_i afterwards (may alias cursors).  Inputs are used as given: of
+ * rays[i] only dir and time are read; hits[i].normal is neither normalised nor checked; p, u, v, front_face and material are read, t is
+ * not.  hits[i].hit == 0: the record is all zeros and the cursor unchanged.  All six material kinds are served in every RTIOW scene,
+ * RL_MAT_ISOTROPIC included (it needs only a hit record, so a caller may make one for a medium of its own).  The draws: UnitSphere's
+ * rejection loop for Lambertian, Metal (also when the reflection is then absorbed) and Isotropic; one f64 for Dielectric's Schlick test,
+ * drawn only when refraction is possible; none for Flat and DiffuseLight.
+ * hits[i].material outside the scene's table: RL_E_INVALID before anything is launched (host form); the device form treats the
+ * element as hit == 0 and never reads outside the table.
+ * The one panic site is Dielectric with a zero-length incident direction (material.rs:150-151): counted in flagged, RL_E_DEGENERATE is
+ * returned, every output is written and the element's values are those a render produces there.
+ * opt_stats: rays = elements with hit != 0, rng_words = words consumed, flagged as above; the traversal counters are 0. */
+int rl_rtiow_scatter_rays(const rl_scene *, const rl_ray *rays, const rl_rtiow_hit *hits, const rl_rng_cursor *cursors, uint64_t n,
+                          uint64_t seed, rl_rtiow_scatter *out, rl_rng_cursor *opt_out_cursors, rl_stats *opt_stats);
+int rl_rtiow_scatter_rays_device(const rl_scene *, const void *d_rays, const void *d_hits, const void *d_cursors, uint64_t n,
+                                 uint64_t seed, void *d_out, void *d_opt_out_cursors, void *hip_stream, rl_stats *opt_stats);
+
+/* out_rgb[3*i ..] = textures[textures[i]].value(uv[2*i], uv[2*i + 1], &p[3*i ..]) over the whole texture tree: Solid, Checker, Image,
+ * Noise.  A texture id outside the scene's table: RL_E_INVALID (host form); zeros (device form).  No RNG, no stats; the device form is
+ * asynchronous on hip_stream, and rl_render_status counts it as a query of 0 rays. */
+int rl_rtiow_texture_values(const rl_scene *, const uint32_t *textures, const double *uv, const double *p, uint64_t n, double *out_rgb);
+int rl_rtiow_texture_values_device(const rl_scene *, const void *d_textures, const void *d_uv, const void *d_p, uint64_t n, void *d_out_rgb,
+                                   void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

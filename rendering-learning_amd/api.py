@@ -90,6 +90,9 @@ RTIOW_HIT = np.dtype([("t", "<f8"), ("p", "<f8", 3), ("normal", "<f8", 3), ("u",
                       ("hit", "<u4"), ("front_face", "<u4"), ("material", "<u4"), ("_pad", "<u4")])
 RTC_ISECT = np.dtype([("t", "<f8"), ("normal", "<f8", 3), ("object", "<u4"), ("_pad", "<u4")])
 assert RAY.itemsize == 56 and RTIOW_HIT.itemsize == 88 and RTC_ISECT.itemsize == 40
+# material queries (rl_rtiow_scatter)
+SCATTER = np.dtype([("attenuation", "<f8", 3), ("emitted", "<f8", 3), ("scattered", RAY), ("scatter", "<u4"), ("_pad", "<u4")])
+assert SCATTER.itemsize == 112
 NO_HIT = 0xFFFFFFFF  # out_hit_index of a ray hit() returns None for
 
 MAT_FLAT, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC = 0, 1, 2, 3, 4, 5
@@ -97,6 +100,22 @@ TEX_SOLID, TEX_CHECKER, TEX_IMAGE, TEX_NOISE = 0, 1, 2, 3
 O_TRIANGLE, O_GROUP, O_BOUNDED, O_TRANSFORMED, O_SPHERE, O_PLANE, O_CUBE, O_CYLINDER, O_CONE, O_CSG = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
 CSG_UNION, CSG_INTERSECTION, CSG_DIFFERENCE = 0, 1, 2
 PAT_STRIPE, PAT_RING, PAT_GRADIENT, PAT_CHECKER3D = 1, 2, 3, 4
+
+
+class RtiowSceneDesc(C.Structure):  # rl_rtiow_scene_desc
+    _fields_ = [("spheres", C.c_void_p), ("n_spheres", C.c_uint32),
+                ("planars", C.c_void_p), ("n_planars", C.c_uint32),
+                ("translates", C.c_void_p), ("n_translates", C.c_uint32),
+                ("transforms", C.c_void_p), ("n_transforms", C.c_uint32),
+                ("bvh_nodes", C.c_void_p), ("n_bvh_nodes", C.c_uint32),
+                ("lists", C.c_void_p), ("n_lists", C.c_uint32),
+                ("list_items", C.c_void_p), ("n_list_items", C.c_uint32),
+                ("materials", C.c_void_p), ("n_materials", C.c_uint32),
+                ("textures", C.c_void_p), ("n_textures", C.c_uint32),
+                ("images", C.c_void_p), ("n_images", C.c_uint32),
+                ("root", C.c_uint32 * 2),
+                ("perlins", C.c_void_p), ("n_perlins", C.c_uint32),
+                ("media", C.c_void_p), ("n_media", C.c_uint32)]
 
 
 class RtcSceneDesc(C.Structure):
@@ -180,7 +199,16 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtc_render_multi", "rl_rtc_render_multi_device", "rl_rtc_encode_rgb8_device", "rl_rtc_render_rgb8",
                   "rl_rtiow_hit_rays", "rl_rtiow_hit_rays_device", "rl_rtc_intersect_rays", "rl_rtc_intersect_rays_device",
                   "rl_rtc_color_at_rays", "rl_rtc_color_at_rays_device",
-                  "rl_rtiow_camera_rays", "rl_rtiow_camera_rays_device", "rl_rtiow_ray_color_rays", "rl_rtiow_ray_color_rays_device"]
+                  "rl_rtiow_camera_rays", "rl_rtiow_camera_rays_device", "rl_rtiow_ray_color_rays", "rl_rtiow_ray_color_rays_device",
+                  "rl_rtiow_scatter_rays", "rl_rtiow_scatter_rays_device", "rl_rtiow_texture_values", "rl_rtiow_texture_values_device"]
+
+
+def _material_query_argtypes(L):
+    L.rl_rtiow_scatter_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtiow_scatter_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.POINTER(Stats)]
+    L.rl_rtiow_texture_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.rl_rtiow_texture_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
 
 
 def render_lib():
@@ -227,6 +255,8 @@ def render_lib():
                                               C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_ray_color_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+        if hasattr(L, "rl_rtiow_scatter_rays"):  # (absent from an older library selected with RL_RENDER_LIB for an A/B run: calling them then fails loudly)
+            _material_query_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -453,6 +483,22 @@ def last_query():
     return {"kernel": {1: "reference", 2: "fast"}.get(int(out[0]), "none"), "retraced": int(out[1])}
 
 
+def material_query_max_lanes():
+    """rl_debug_material_query_lanes: the most lanes one scatter_rays* / texture_values* launch has on the current device (the grid cap,
+    csrc/rl_material_query.h MATERIAL_QUERY_MAX_BLOCKS_PER_CU workgroups per CU); a larger batch puts several elements through one lane."""
+    L = render_lib()
+    L.rl_debug_material_query_lanes.restype = C.c_uint64
+    L.rl_debug_material_query_lanes.argtypes = []
+    return int(L.rl_debug_material_query_lanes())
+
+
+def _records_arg(a, dtype, n, what):
+    r = np.ascontiguousarray(a)
+    if r.dtype != dtype or r.ndim != 1 or (n is not None and r.shape[0] != n):
+        raise ValueError(f"{what} must be [{'n' if n is None else n}] {what.upper()} records; got shape {r.shape}, dtype {r.dtype}")
+    return r
+
+
 def _finish_query(rc, st, stats, allow_degenerate):
     _check(rc, allow_degenerate)
     if stats is not None:
@@ -513,6 +559,25 @@ class World:
         L.rlh_rtiow_counts.argtypes = [C.c_void_p, C.c_void_p]
         L.rlh_rtiow_counts(self._h, out)
         return dict(zip(("spheres", "planars", "media", "translates", "transforms", "lists", "bvh_nodes", "materials", "textures"), list(out)))
+
+    def _table(self, field, dtype):
+        d = RtiowSceneDesc.from_address(self.desc)
+        n, ptr = getattr(d, "n_" + field), getattr(d, field)
+        if not n:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * (n * dtype.itemsize)).from_address(ptr), dtype=dtype).copy()
+
+    def materials(self):
+        """The flattened scene's material table (MATERIAL records): what RTIOW_HIT.material indexes."""
+        return self._table("materials", MATERIAL)
+
+    def textures(self):
+        """The flattened scene's texture table (TEXTURE records): what MATERIAL.texture and texture_values index."""
+        return self._table("textures", TEXTURE)
+
+    def perlins(self):
+        """The flattened scene's Perlin tables (PERLIN records): what a Noise texture's `image` field indexes."""
+        return self._table("perlins", PERLIN)
 
     def __del__(self):
         try:
@@ -663,6 +728,53 @@ class World:
                                                          C.c_void_p(d_rgb), C.c_void_p(d_out_cursors or None), C.c_void_p(d_ray_counts or None),
                                                          C.c_void_p(stream), C.byref(st) if stats is not None else None)
         _finish_query(rc, st, stats, allow_degenerate)
+
+    def scatter_rays(self, rays, hits, cursors, seed, stats=None, allow_degenerate=False):
+        """Material::scatter(&mut rng, &ray, &hit_record) + Material::emitted(u, v, &p) (material.rs:11-20) for every element, on the GPU,
+        element i drawing from cursors[i] of `seed`: RAY[n] (only dir and time are read), RTIOW_HIT[n] as hit_rays returns them (or
+        hand-made) -> (SCATTER[n], cursors behind the draws [n]).  With hit_rays a host writes its own ray_color loop and gets
+        ray_color_rays' bits."""
+        rays = _records_arg(rays, RAY, None, "rays")
+        n = rays.shape[0]
+        hits = _records_arg(hits, RTIOW_HIT, n, "hits")
+        out_cur = _cursors_arg(cursors, n).copy()
+        out = np.zeros(n, dtype=SCATTER)
+        st = Stats()
+        rc = render_lib().rl_rtiow_scatter_rays(self.device(), rays.ctypes.data, hits.ctypes.data, out_cur.ctypes.data, n, int(seed), out.ctypes.data,
+                                                out_cur.ctypes.data, C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+        return out, out_cur
+
+    def scatter_rays_device(self, d_rays, d_hits, d_cursors, n, seed, d_out, d_out_cursors=0, stream=0, stats=None, allow_degenerate=False):
+        """Device buffers (n rl_ray, n rl_rtiow_hit and n rl_rng_cursor in; n rl_rtiow_scatter and optionally n rl_rng_cursor out, which may be
+        d_cursors).  Asynchronous unless stats is a dict.  A material index outside the scene's table gives a zero record."""
+        st = Stats()
+        rc = render_lib().rl_rtiow_scatter_rays_device(self.device(), C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_void_p(d_cursors), n, int(seed),
+                                                       C.c_void_p(d_out), C.c_void_p(d_out_cursors or None), C.c_void_p(stream),
+                                                       C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+
+    def texture_values(self, textures, uv, p):
+        """Texture::value(u, v, &p) (texture.rs) of the scene's textures[textures[i]] at (uv[i], p[i]), on the GPU -> rgb [n, 3]."""
+        tex = np.asarray(textures)
+        if tex.shape == (0,):
+            tex = tex.astype(np.uint32)
+        if tex.ndim != 1 or tex.dtype.kind not in "iu" or (tex.dtype.kind == "i" and (tex < 0).any()) or (tex.size and int(tex.max()) >= 2 ** 32):
+            raise ValueError(f"textures must be [n] texture ids (got shape {tex.shape}, dtype {tex.dtype})")
+        tex = np.ascontiguousarray(tex, dtype=np.uint32)
+        n = tex.shape[0]
+        uv = np.ascontiguousarray(uv, dtype=np.float64)
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        if uv.shape != (n, 2) or p.shape != (n, 3):
+            raise ValueError(f"uv must be [{n}, 2] and p [{n}, 3] (got {uv.shape} and {p.shape})")
+        rgb = np.zeros((n, 3), dtype=np.float64)
+        _check(render_lib().rl_rtiow_texture_values(self.device(), tex.ctypes.data, uv.ctypes.data, p.ctypes.data, n, rgb.ctypes.data))
+        return rgb
+
+    def texture_values_device(self, d_textures, d_uv, d_p, n, d_rgb, stream=0):
+        """Device buffers (n u32 texture ids, n*2 and n*3 f64 in; n*3 f64 out).  Asynchronous; an id outside the scene's table gives zeros."""
+        _check(render_lib().rl_rtiow_texture_values_device(self.device(), C.c_void_p(d_textures), C.c_void_p(d_uv), C.c_void_p(d_p), n, C.c_void_p(d_rgb),
+                                                           C.c_void_p(stream)))
 
 
 class SceneBuilder:

@@ -26,6 +26,7 @@
 #include "rl_rtiow_coop.h"
 #include "rl_pixel_entry.h"
 #include "rl_ray_query.h"
+#include "rl_material_query.h"
 #ifdef RL_EXPERIMENTAL  // the measured-and-lost restructurings: only in librl_render_exp.so, never in the product library
 #include "experimental/rl_rtiow_pool.h"
 #include "experimental/rl_rtiow_wave2.h"
@@ -2511,6 +2512,131 @@ int rl_rtiow_camera_rays(const rl_rtiow_camera *cam, uint64_t n, const uint32_t 
   HIP_TRY(hipMemcpy(out_rays, q.d[2], n * sizeof(rl_ray), hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(out_cursors, q.d[1], n * sizeof(rl_rng_cursor), hipMemcpyDeviceToHost));
   return RL_OK;
+}
+
+// ---- material queries (include/rl_render.h): Material::scatter / emitted and Texture::value for buffers
+static int material_query_check(const rl_scene *scene, uint64_t n, bool buffers_ok, rl_stats *st, bool &done) {
+  done = true;
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 1) return set_err(RL_E_INVALID, "not an RTIOW scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!buffers_ok) return set_err(RL_E_INVALID, "null input / output buffer");
+  if (n > (uint64_t)1 << 40) return set_err(RL_E_INVALID, "batch too large");
+  done = false;
+  return RL_OK;
+}
+
+static void material_query_params(const rl_scene *scene, uint64_t n, RtiowParams &P, MaterialQuery &Q, uint32_t &blocks) {
+  const RtiowProgram &rt = scene->rt();
+  P = RtiowParams{};
+  P.materials = scene->d_materials, P.textures = scene->d_textures, P.images = scene->d_images, P.image_pool = scene->d_image_pool;
+  P.perlins = scene->d_perlins;
+  P.stats = (unsigned long long *)(scene->d_scratch + 64);
+  Q = MaterialQuery{};
+  Q.n = n, Q.n_materials = (uint32_t)rt.materials.size(), Q.n_textures = (uint32_t)rt.textures.size();
+  const uint64_t want = (n + MATERIAL_QUERY_NT - 1) / MATERIAL_QUERY_NT, cap = (uint64_t)std::max(1, g_cus) * MATERIAL_QUERY_MAX_BLOCKS_PER_CU;
+  blocks = (uint32_t)std::min(want, cap);
+}
+
+// the most lanes one material-query launch has on the current device: a larger batch puts several elements through one lane
+unsigned long long rl_debug_material_query_lanes(void) {
+  return (unsigned long long)std::max(1, g_cus) * MATERIAL_QUERY_MAX_BLOCKS_PER_CU * MATERIAL_QUERY_NT;
+}
+
+// sync_st: filled synchronously (the host form, and the device form with opt_stats); null: asynchronous, status ring
+static int rtiow_scatter_impl(const rl_scene *scene, const void *d_rays, const void *d_hits, const void *d_cursors, uint64_t n, uint64_t seed, void *d_out,
+                              void *d_out_cursors, hipStream_t stream, rl_stats *sync_st) {
+  RtiowParams P;
+  MaterialQuery Q;
+  uint32_t blocks = 0;
+  material_query_params(scene, n, P, Q, blocks);
+  chacha_key_from_seed(seed, P.key);
+  Q.rays = (const rl_ray *)d_rays, Q.hits = (const rl_rtiow_hit *)d_hits, Q.cursors = (const rl_rng_cursor *)d_cursors;
+  Q.out = (rl_rtiow_scatter *)d_out, Q.out_cursors = (rl_rng_cursor *)d_out_cursors;
+  std::lock_guard<std::mutex> lk(scene->mu);  // queries and renders of one scene: see rl_scene::mu
+  int rc = query_begin(scene, stream, sync_st != nullptr);
+  if (rc != RL_OK) return rc;
+  hipLaunchKernelGGL((rtiow_scatter_rays_kernel<MATERIAL_QUERY_NT>), dim3(blocks), dim3(MATERIAL_QUERY_NT), 0, stream, P, Q);
+  return query_end(scene, stream, sync_st);
+}
+
+int rl_rtiow_scatter_rays_device(const rl_scene *scene, const void *d_rays, const void *d_hits, const void *d_cursors, uint64_t n, uint64_t seed,
+                                 void *d_out, void *d_opt_out_cursors, void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = material_query_check(scene, n, d_rays && d_hits && d_cursors && d_out, st, done);
+  if (done) return rc;
+  return rtiow_scatter_impl(scene, d_rays, d_hits, d_cursors, n, seed, d_out, d_opt_out_cursors, (hipStream_t)hip_stream, st);
+}
+
+int rl_rtiow_scatter_rays(const rl_scene *scene, const rl_ray *rays, const rl_rtiow_hit *hits, const rl_rng_cursor *cursors, uint64_t n, uint64_t seed,
+                          rl_rtiow_scatter *out, rl_rng_cursor *opt_out_cursors, rl_stats *st) {
+  bool done;
+  int rc0 = material_query_check(scene, n, rays && hits && cursors && out, st, done);
+  if (done) return rc0;
+  if ((rc0 = cursors_check(cursors, n)) != RL_OK) return rc0;
+  const uint32_t n_materials = (uint32_t)scene->rt().materials.size();
+  for (uint64_t i = 0; i < n; i++)
+    if (hits[i].hit != 0u && hits[i].material >= n_materials) return set_err(RL_E_INVALID, "hit record's material index outside the scene's table");
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * sizeof(rl_ray))) || (rc0 = q.alloc(1, n * sizeof(rl_rtiow_hit))) || (rc0 = q.alloc(2, n * sizeof(rl_rng_cursor))) ||
+      (rc0 = q.alloc(3, n * sizeof(rl_rtiow_scatter))))
+    return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], rays, n * sizeof(rl_ray), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(q.d[1], hits, n * sizeof(rl_rtiow_hit), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(q.d[2], cursors, n * sizeof(rl_rng_cursor), hipMemcpyHostToDevice));
+  rl_stats local;
+  int rc = rtiow_scatter_impl(scene, q.d[0], q.d[1], q.d[2], n, seed, q.d[3], opt_out_cursors ? q.d[2] : nullptr, g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    HIP_TRY(hipMemcpy(out, q.d[3], n * sizeof(rl_rtiow_scatter), hipMemcpyDeviceToHost));
+    if (opt_out_cursors) HIP_TRY(hipMemcpy(opt_out_cursors, q.d[2], n * sizeof(rl_rng_cursor), hipMemcpyDeviceToHost));
+    if (st) *st = local;
+  }
+  return rc;
+}
+
+static int rtiow_texture_values_impl(const rl_scene *scene, const void *d_textures, const void *d_uv, const void *d_p, uint64_t n, void *d_out,
+                                     hipStream_t stream, rl_stats *sync_st) {
+  RtiowParams P;
+  MaterialQuery Q;
+  uint32_t blocks = 0;
+  material_query_params(scene, n, P, Q, blocks);
+  Q.tex_ids = (const uint32_t *)d_textures, Q.uv = (const double *)d_uv, Q.p = (const double *)d_p, Q.rgb = (double *)d_out;
+  std::lock_guard<std::mutex> lk(scene->mu);
+  int rc = query_begin(scene, stream, sync_st != nullptr);
+  if (rc != RL_OK) return rc;
+  hipLaunchKernelGGL((rtiow_texture_values_kernel<MATERIAL_QUERY_NT>), dim3(blocks), dim3(MATERIAL_QUERY_NT), 0, stream, P, Q);
+  return query_end(scene, stream, sync_st);
+}
+
+int rl_rtiow_texture_values_device(const rl_scene *scene, const void *d_textures, const void *d_uv, const void *d_p, uint64_t n, void *d_out_rgb,
+                                   void *hip_stream) {
+  bool done;
+  int rc = material_query_check(scene, n, d_textures && d_uv && d_p && d_out_rgb, nullptr, done);
+  if (done) return rc;
+  return rtiow_texture_values_impl(scene, d_textures, d_uv, d_p, n, d_out_rgb, (hipStream_t)hip_stream, nullptr);
+}
+
+int rl_rtiow_texture_values(const rl_scene *scene, const uint32_t *textures, const double *uv, const double *p, uint64_t n, double *out_rgb) {
+  bool done;
+  int rc0 = material_query_check(scene, n, textures && uv && p && out_rgb, nullptr, done);
+  if (done) return rc0;
+  const uint32_t n_textures = (uint32_t)scene->rt().textures.size();
+  for (uint64_t i = 0; i < n; i++)
+    if (textures[i] >= n_textures) return set_err(RL_E_INVALID, "texture id outside the scene's table");
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * 4)) || (rc0 = q.alloc(1, n * 16)) || (rc0 = q.alloc(2, n * 24)) || (rc0 = q.alloc(3, n * 24))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], textures, n * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(q.d[1], uv, n * 16, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(q.d[2], p, n * 24, hipMemcpyHostToDevice));
+  rl_stats local;
+  int rc = rtiow_texture_values_impl(scene, q.d[0], q.d[1], q.d[2], n, q.d[3], g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK) HIP_TRY(hipMemcpy(out_rgb, q.d[3], n * 24, hipMemcpyDeviceToHost));
+  return rc;
 }
 
 }  // extern "C"

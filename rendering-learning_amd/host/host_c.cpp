@@ -515,6 +515,26 @@ int rlh_path_query_probe(int which, const rl_ray *rays, rl_rng_cursor *cursors, 
     return -1;
   }
 }
+// Material queries through the C++ mirror on golden_test_scene.  which = 0: rtiow::scatter of (rays, hits) with seed = the scene's,
+// out = n rl_rtiow_scatter, cursors advanced in place; which = 1: rtiow::texture_values, `rays` = n texture ids (uint32), `hits` = n (u, v)
+// pairs, `cursors` = n points (3 doubles each), out = n * 3 doubles.  0 or -1 (rlh_last_error).
+int rlh_material_query_probe(int which, const void *rays, const void *hits, void *cursors, uint64_t n, void *out) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    if (which == 0) {
+      std::vector<rl_rtiow_scatter> r =
+          rtiow::scatter(*s.world, (const rl_ray *)rays, (const rl_rtiow_hit *)hits, (rl_rng_cursor *)cursors, (size_t)n, s.params.seed);
+      std::memcpy(out, r.data(), r.size() * sizeof(rl_rtiow_scatter));
+    } else {
+      std::vector<double> c = rtiow::texture_values(*s.world, (const uint32_t *)rays, (const double *)hits, (const double *)cursors, (size_t)n);
+      std::memcpy(out, c.data(), c.size() * sizeof(double));
+    }
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // tests/ray_tracer.rs:242-275 (which = 0, needs the OBJ text), :56-240 mirror (1), :277-368 csg (2): Camera::render -> Canvas::ppm
 char *rlh_rtc_run_golden_test(int which, const char *obj_text, uint64_t obj_len, uint64_t *len) {
   try {

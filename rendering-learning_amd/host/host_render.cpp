@@ -70,6 +70,31 @@ std::vector<double> ray_color_rays(const Hittable &world, const rl_ray *rays, rl
   if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_ray_color_rays: ") + rl_last_error());
   return out;
 }
+std::vector<rl_rtiow_scatter> scatter(const Hittable &world, const rl_ray *rays, const rl_rtiow_hit *hits, rl_rng_cursor *cursors, size_t n,
+                                      uint64_t seed) {  // material.rs:11-20
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  std::vector<rl_rtiow_scatter> out(n);
+  int rc = rl_rtiow_scatter_rays(sc, rays, hits, cursors, n, seed, out.data(), cursors, nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_scatter_rays: ") + rl_last_error());
+  return out;
+}
+std::vector<double> texture_values(const Hittable &world, const uint32_t *textures, const double *uv, const double *p, size_t n) {  // texture.rs
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  std::vector<double> out(n * 3);
+  int rc = rl_rtiow_texture_values(sc, textures, uv, p, n, out.data());
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_texture_values: ") + rl_last_error());
+  return out;
+}
 std::vector<rl_ray> Camera::get_rays(const uint32_t *px, const uint32_t *py, rl_rng_cursor *cursors, size_t n) const {  // camera.rs:203-216
   rl_rtiow_camera cam = derived();
   std::vector<rl_ray> out(n);

@@ -681,6 +681,13 @@ std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t 
 std::vector<double> ray_color_rays(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed, size_t max_depth,
                                    const Color &background, std::vector<uint32_t> *ray_counts = nullptr);
 
+// Material::scatter(&mut rng, &ray, &hit_record) and Material::emitted(u, v, &p) (material.rs:11-20) for a batch of hit records, on the
+// GPU (rl_rtiow_scatter_rays): out[i].scatter == 0 for None; cursors[i] is advanced behind the draws.  With rtiow::hit a host writes its
+// own ray_color loop.  Throws on any error but RL_E_DEGENERATE.
+std::vector<rl_rtiow_scatter> scatter(const Hittable &world, const rl_ray *rays, const rl_rtiow_hit *hits, rl_rng_cursor *cursors, size_t n, uint64_t seed);
+// Texture::value(u, v, &p) (texture.rs) of the flattened world's textures (rl_rtiow_texture_values): n * 3 colour values.
+std::vector<double> texture_values(const Hittable &world, const uint32_t *textures, const double *uv, const double *p, size_t n);
+
 struct CameraParams {  // camera.rs:23-59 (defaults as in the reference)
   double aspect_ratio = 1.0;
   size_t image_width = 100;
