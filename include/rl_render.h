@@ -577,6 +577,88 @@ int rl_rtiow_texture_values(const rl_scene *, const uint32_t *textures, const do
 int rl_rtiow_texture_values_device(const rl_scene *, const void *d_textures, const void *d_uv, const void *d_p, uint64_t n, void *d_out_rgb,
                                    void *hip_stream);
 
+/* =====================================================================
+ *  RTC shading queries: prepare_computations, shade_hit, shadow_attenuation and lighting for buffers
+ * =====================================================================
+ *   rl_rtc_prepare_rays*        <- ray-tracer-challenge/src/scene/intersect.rs:159-168 hit + :38-115 Intersection::prepare_computations
+ *   rl_rtc_shade_hits*          <- ray-tracer-challenge/src/scene/world.rs:57-87 World::shade_hit up to its recursion, with
+ *                                  intersect.rs:139-156 Precomputation::schlick and the rays of world.rs:128-159
+ *   rl_rtc_shadow_attenuation*  <- ray-tracer-challenge/src/scene/world.rs:104-126 World::shadow_attenuation(&point, light)
+ *   rl_rtc_lighting*            <- ray-tracer-challenge/src/scene/material.rs:54-90 material::lighting
+ * What World::color_at (world.rs:89-102) does with a hit, as primitives of their own: with them a host writes its own integrator (its own
+ * depth rule, area lights sampled with many shadow queries, visibility from arbitrary points, per-bounce buffers) and still shades as the
+ * library does.  The arithmetic is that of the render kernels, so the loop
+ *     c = 0; stack = [(ray, w = 1, remaining = max_reflection_depth, mult = 1)]
+ *     while stack: pop (ray, w, remaining, mult)
+ *       k = prepare_rays(ray);  k.hit == 0 or n_lights == 0:  c = c + void_color * w; continue
+ *       s = shade_hits(k);      c = c + s.surface * w
+ *       m = materials[k.material]; wl = w * (double)n_lights; both = m.reflectivity > 0 && m.transparency > 0
+ *       remaining > 0 && s.refract: push (s.refracted, wl * m.transparency * (both ? 1 - s.schlick : 1), remaining - 1, mult * n_lights)
+ *       remaining > 0 && s.reflect: push (s.reflected, wl * m.reflectivity * (both ? s.schlick : 1), remaining - 1, mult * n_lights)
+ * gives rl_rtc_color_at_rays' colours bit for bit (the refraction is pushed first, so the reflection is popped first; multiplications
+ * associate left to right), and the sum over all nodes of mult * (prepare's stats.rays + shade's stats.rays) is a counting
+ * rl_rtc_color_at_rays' stats.rays (the reference evaluates reflected_color / refracted_color once per light, world.rs:73-74).
+ * Status, concurrency, rl_init_multi, n = 0, NULL buffers and the wrong scene family (here: an RTIOW scene): as stated for the batched
+ * ray queries. */
+typedef struct rl_rtc_comps {      /* scene/intersect.rs:123-137 Precomputation */
+  double t, point[3], eye_v[3], normal_v[3], over_point[3], under_point[3], reflect_v[3];
+  double n1, n2;                   /* refraction_exiting, refraction_entering */
+  double object_color[3];          /* Surface::color_at at the hit: the pattern evaluated as the render does (rtc_hit_color) */
+  uint32_t hit;                    /* 0: intersect::hit gave None; every other field is 0 */
+  uint32_t inside;
+  uint32_t object;                 /* identity as in rl_rtc_isect.object */
+  uint32_t material;               /* index into the scene's materials */
+} rl_rtc_comps;                    /* 208 bytes */
+
+typedef struct rl_rtc_shade {      /* what World::shade_hit (world.rs:57-87) computes before it recurses */
+  double surface[3];               /* lighting(.., shadow_attenuation) summed over the lights in order; the first light's value starts the sum */
+  double schlick;                  /* Precomputation::schlick (intersect.rs:139-156), always computed */
+  rl_ray reflected;                /* origin over_point, dir reflect_v, time 0; zeros unless reflect == 1 */
+  rl_ray refracted;                /* origin under_point, dir by world.rs:143-154; zeros unless refract == 1 */
+  uint32_t reflect;                /* material.reflectivity != 0 */
+  uint32_t refract;                /* material.transparency != 0 and no total internal reflection */
+} rl_rtc_shade;                    /* 152 bytes */
+
+/* out_comps[i] = hit(&World::intersect(&rays[i])).map(|h| h.prepare_computations(&rays[i], &xs)) (intersect.rs:159-168, :48-115).
+ * n1 and n2 are computed for every material, as the reference does (the containers walk of intersect.rs:72-99); the renders compute them
+ * only where a transparent material reads them.  inside = normal . eye_v < 0, and normal_v is then the negated normal.
+ * Panic sites (intersect.rs:57, :70): a failed eye_v or reflect_v normalisation is counted in flagged and the element carries the value
+ * the renders go on with (-dir, dir); a ray with more than 48 intersections is flagged, as in the renders.  RL_E_DEGENERATE is then
+ * returned with every output written.  A zero dir gives hit == 0 and reaches no panic site.
+ * opt_stats: rays = n, the traversal counters as rl_rtc_intersect_rays reports them. */
+int rl_rtc_prepare_rays(const rl_scene *, const rl_ray *rays, uint64_t n, rl_rtc_comps *out_comps, rl_stats *opt_stats);
+int rl_rtc_prepare_rays_device(const rl_scene *, const void *d_rays, uint64_t n, void *d_out_comps, void *hip_stream, rl_stats *opt_stats);
+
+/* out[i]: what world.shade_hit(&comps[i], remaining) (world.rs:57-87) computes itself: per light, in order, shadow_attenuation from
+ * over_point (world.rs:61) and lighting (:63-71), summed as the reference's reduce sums them; schlick; and the rays reflected_color /
+ * refracted_color would trace (world.rs:132, :143-154).  comps are used as given and need not come from rl_rtc_prepare_rays: t, inside,
+ * object and under_point / reflect_v of an element without a secondary ray are not read.  comps[i].hit == 0: an all-zero record, no ray.
+ * A scene without lights: surface = 0 and reflect = refract = 0 (the reference's reduce over no lights is None).
+ * opt_out_shadow ([n][n_lights], may be NULL): the attenuation used for each light (zeros where hit == 0).
+ * comps[i].material outside the scene's table: RL_E_INVALID before anything is launched (host form); the device form treats the element
+ * as hit == 0 and never reads outside the table.
+ * opt_stats: rays = the shadow rays traced (none for a light at over_point itself, world.rs:107-125), the traversal counters theirs. */
+int rl_rtc_shade_hits(const rl_scene *, const rl_rtc_comps *comps, uint64_t n, rl_rtc_shade *out, double *opt_out_shadow, rl_stats *opt_stats);
+int rl_rtc_shade_hits_device(const rl_scene *, const void *d_comps, uint64_t n, void *d_out, void *d_opt_out_shadow, void *hip_stream,
+                             rl_stats *opt_stats);
+
+/* out_att[i] = world.shadow_attenuation(&points[3*i ..], light at light_positions[3*i ..]) (world.rs:104-126): the product of the
+ * transparencies of the distinct objects between the point and the position, which need not be one of the scene's lights.  Coincident
+ * point and position: 1.0, no ray (world.rs:107, :125).  opt_stats: rays = the shadow rays traced. */
+int rl_rtc_shadow_attenuation(const rl_scene *, const double *points, const double *light_positions, uint64_t n, double *out_att,
+                              rl_stats *opt_stats);
+int rl_rtc_shadow_attenuation_device(const rl_scene *, const void *d_points, const void *d_light_positions, uint64_t n, void *d_out_att,
+                                     void *hip_stream, rl_stats *opt_stats);
+
+/* out_rgb[3*i ..] = lighting(materials[comps[i].material], &comps[i].point, &comps[i].object_color, &PointLight{light_positions[3*i ..],
+ * light_intensities[3*i ..]}, &comps[i].eye_v, &comps[i].normal_v, shadow_att[i]) (material.rs:54-90).  hit == 0: zeros.  A material
+ * outside the scene's table: RL_E_INVALID (host form); zeros (device form).  No traversal, no stats; the device form is asynchronous on
+ * hip_stream, and rl_render_status counts it as a query of 0 rays. */
+int rl_rtc_lighting(const rl_scene *, const rl_rtc_comps *comps, const double *light_positions, const double *light_intensities,
+                    const double *shadow_att, uint64_t n, double *out_rgb);
+int rl_rtc_lighting_device(const rl_scene *, const void *d_comps, const void *d_light_positions, const void *d_light_intensities,
+                           const void *d_shadow_att, uint64_t n, void *d_out_rgb, void *hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -93,6 +93,12 @@ assert RAY.itemsize == 56 and RTIOW_HIT.itemsize == 88 and RTC_ISECT.itemsize ==
 # material queries (rl_rtiow_scatter)
 SCATTER = np.dtype([("attenuation", "<f8", 3), ("emitted", "<f8", 3), ("scattered", RAY), ("scatter", "<u4"), ("_pad", "<u4")])
 assert SCATTER.itemsize == 112
+# RTC shading queries (rl_rtc_comps / rl_rtc_shade)
+RTC_COMPS = np.dtype([("t", "<f8"), ("point", "<f8", 3), ("eye_v", "<f8", 3), ("normal_v", "<f8", 3), ("over_point", "<f8", 3),
+                      ("under_point", "<f8", 3), ("reflect_v", "<f8", 3), ("n1", "<f8"), ("n2", "<f8"), ("object_color", "<f8", 3),
+                      ("hit", "<u4"), ("inside", "<u4"), ("object", "<u4"), ("material", "<u4")])
+RTC_SHADE = np.dtype([("surface", "<f8", 3), ("schlick", "<f8"), ("reflected", RAY), ("refracted", RAY), ("reflect", "<u4"), ("refract", "<u4")])
+assert RTC_COMPS.itemsize == 208 and RTC_SHADE.itemsize == 152
 NO_HIT = 0xFFFFFFFF  # out_hit_index of a ray hit() returns None for
 
 MAT_FLAT, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC = 0, 1, 2, 3, 4, 5
@@ -200,7 +206,9 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtiow_hit_rays", "rl_rtiow_hit_rays_device", "rl_rtc_intersect_rays", "rl_rtc_intersect_rays_device",
                   "rl_rtc_color_at_rays", "rl_rtc_color_at_rays_device",
                   "rl_rtiow_camera_rays", "rl_rtiow_camera_rays_device", "rl_rtiow_ray_color_rays", "rl_rtiow_ray_color_rays_device",
-                  "rl_rtiow_scatter_rays", "rl_rtiow_scatter_rays_device", "rl_rtiow_texture_values", "rl_rtiow_texture_values_device"]
+                  "rl_rtiow_scatter_rays", "rl_rtiow_scatter_rays_device", "rl_rtiow_texture_values", "rl_rtiow_texture_values_device",
+                  "rl_rtc_prepare_rays", "rl_rtc_prepare_rays_device", "rl_rtc_shade_hits", "rl_rtc_shade_hits_device",
+                  "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device"]
 
 
 def _material_query_argtypes(L):
@@ -209,6 +217,17 @@ def _material_query_argtypes(L):
                                                C.POINTER(Stats)]
     L.rl_rtiow_texture_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.rl_rtiow_texture_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+
+
+def _rtc_shade_query_argtypes(L):
+    L.rl_rtc_prepare_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtc_prepare_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtc_shade_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtc_shade_hits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtc_shadow_attenuation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtc_shadow_attenuation_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtc_lighting.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    L.rl_rtc_lighting_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
 
 
 def render_lib():
@@ -257,6 +276,8 @@ def render_lib():
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
         if hasattr(L, "rl_rtiow_scatter_rays"):  # (absent from an older library selected with RL_RENDER_LIB for an A/B run: calling them then fails loudly)
             _material_query_argtypes(L)
+        if hasattr(L, "rl_rtc_prepare_rays"):  # (likewise)
+            _rtc_shade_query_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -1250,6 +1271,113 @@ class RtcWorld:
         rc = render_lib().rl_rtc_color_at_rays_device(self.device(), C.c_void_p(d_rays), n, C.c_void_p(d_rgb), C.c_void_p(stream),
                                                       C.byref(st) if stats is not None else None)
         _finish_query(rc, st, stats, allow_degenerate)
+
+    # ---- shading queries (include/rl_render.h "RTC shading queries")
+    def _table(self, field, dtype):
+        d = RtcSceneDesc.from_address(self.desc)
+        n, ptr = getattr(d, "n_" + field), getattr(d, field)
+        if not n:
+            return np.zeros(0, dtype=dtype)
+        return np.frombuffer((C.c_char * (n * dtype.itemsize)).from_address(ptr), dtype=dtype).copy()
+
+    def materials(self):
+        """The flattened world's material table (RTC_MATERIAL records): what RTC_COMPS.material indexes."""
+        return self._table("materials", RTC_MATERIAL)
+
+    def lights(self):
+        """The world's lights in order (RTC_LIGHT records)."""
+        return self._table("lights", RTC_LIGHT)
+
+    def prepare_rays(self, origins, dirs, stats=None, allow_degenerate=False):
+        """hit(&World::intersect(&ray)).map(|h| h.prepare_computations(&ray, &xs)) (intersect.rs:159-168, :48-115) for every ray, on the GPU
+        -> RTC_COMPS[n]; hit == 0 (and zeros) where hit() returns None."""
+        rays = pack_rays(origins, dirs)
+        n = rays.shape[0]
+        out = np.zeros(n, dtype=RTC_COMPS)
+        st = Stats()
+        rc = render_lib().rl_rtc_prepare_rays(self.device(), rays.ctypes.data, n, out.ctypes.data, C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+        return out
+
+    def prepare_rays_device(self, d_rays, n, d_comps, stream=0, stats=None, allow_degenerate=False):
+        """Device buffers (n rl_ray in, n rl_rtc_comps out).  Asynchronous unless stats is a dict."""
+        st = Stats()
+        rc = render_lib().rl_rtc_prepare_rays_device(self.device(), C.c_void_p(d_rays), n, C.c_void_p(d_comps), C.c_void_p(stream),
+                                                     C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+
+    def shade_hits(self, comps, stats=None, allow_degenerate=False):
+        """What World::shade_hit (world.rs:57-87) computes before it recurses, for every RTC_COMPS record (from prepare_rays or hand-made)
+        -> (RTC_SHADE[n], shadow attenuations [n, n_lights]).  With prepare_rays a host writes its own color_at loop and gets
+        color_at_rays' bits."""
+        comps = _records_arg(comps, RTC_COMPS, None, "comps")
+        n = comps.shape[0]
+        out = np.zeros(n, dtype=RTC_SHADE)
+        shadow = np.zeros((n, RtcSceneDesc.from_address(self.desc).n_lights), dtype=np.float64)
+        st = Stats()
+        rc = render_lib().rl_rtc_shade_hits(self.device(), comps.ctypes.data, n, out.ctypes.data, shadow.ctypes.data if shadow.size else None,
+                                            C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+        return out, shadow
+
+    def shade_hits_device(self, d_comps, n, d_out, d_out_shadow=0, stream=0, stats=None, allow_degenerate=False):
+        """Device buffers (n rl_rtc_comps in; n rl_rtc_shade and optionally n * n_lights f64 out).  Asynchronous unless stats is a dict.
+        A material index outside the scene's table gives a zero record."""
+        st = Stats()
+        rc = render_lib().rl_rtc_shade_hits_device(self.device(), C.c_void_p(d_comps), n, C.c_void_p(d_out), C.c_void_p(d_out_shadow or None),
+                                                   C.c_void_p(stream), C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+
+    @staticmethod
+    def _vec3_arg(a, n, what):
+        v = np.asarray(a, dtype=np.float64)
+        if n is not None and v.shape == (3,):
+            v = np.broadcast_to(v, (n, 3))
+        if v.ndim != 2 or v.shape[1] != 3 or (n is not None and v.shape[0] != n):
+            raise ValueError(f"{what} must be [{'n' if n is None else n}, 3] (got {v.shape})")
+        return np.ascontiguousarray(v)
+
+    def shadow_attenuation(self, points, light_positions, stats=None, allow_degenerate=False):
+        """World::shadow_attenuation(&point, light) (world.rs:104-126) for arbitrary points [n, 3] and light positions ([n, 3], or one [3]
+        for all) -> [n]."""
+        pts = self._vec3_arg(points, None, "points")
+        n = pts.shape[0]
+        lp = self._vec3_arg(light_positions, n, "light_positions")
+        out = np.zeros(n, dtype=np.float64)
+        st = Stats()
+        rc = render_lib().rl_rtc_shadow_attenuation(self.device(), pts.ctypes.data, lp.ctypes.data, n, out.ctypes.data,
+                                                    C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+        return out
+
+    def shadow_attenuation_device(self, d_points, d_light_positions, n, d_out, stream=0, stats=None, allow_degenerate=False):
+        """Device buffers (n * 3 and n * 3 f64 in, n f64 out).  Asynchronous unless stats is a dict."""
+        st = Stats()
+        rc = render_lib().rl_rtc_shadow_attenuation_device(self.device(), C.c_void_p(d_points), C.c_void_p(d_light_positions), n, C.c_void_p(d_out),
+                                                           C.c_void_p(stream), C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+
+    def lighting(self, comps, light_positions, light_intensities, shadow_att):
+        """material::lighting (material.rs:54-90) of every RTC_COMPS record under PointLight{light_positions[i], light_intensities[i]} ([n, 3],
+        or one [3] for all) with shadow_att ([n], or one number) -> rgb [n, 3]."""
+        comps = _records_arg(comps, RTC_COMPS, None, "comps")
+        n = comps.shape[0]
+        lp = self._vec3_arg(light_positions, n, "light_positions")
+        li = self._vec3_arg(light_intensities, n, "light_intensities")
+        att = np.asarray(shadow_att, dtype=np.float64)
+        if att.shape == ():
+            att = np.broadcast_to(att, (n,))
+        if att.shape != (n,):
+            raise ValueError(f"shadow_att must be [{n}] (got {att.shape})")
+        att = np.ascontiguousarray(att)
+        rgb = np.zeros((n, 3), dtype=np.float64)
+        _check(render_lib().rl_rtc_lighting(self.device(), comps.ctypes.data, lp.ctypes.data, li.ctypes.data, att.ctypes.data, n, rgb.ctypes.data))
+        return rgb
+
+    def lighting_device(self, d_comps, d_light_positions, d_light_intensities, d_shadow_att, n, d_rgb, stream=0):
+        """Device buffers (n rl_rtc_comps, n * 3, n * 3 and n f64 in; n * 3 f64 out).  Asynchronous; a material outside the table gives zeros."""
+        _check(render_lib().rl_rtc_lighting_device(self.device(), C.c_void_p(d_comps), C.c_void_p(d_light_positions), C.c_void_p(d_light_intensities),
+                                                   C.c_void_p(d_shadow_att), n, C.c_void_p(d_rgb), C.c_void_p(stream)))
 
 
 def rtc_camera(hsize, vsize, fov, frm, to, up) -> RtcCamera:  # Camera::new + view_transform

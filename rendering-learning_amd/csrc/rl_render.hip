@@ -27,6 +27,7 @@
 #include "rl_pixel_entry.h"
 #include "rl_ray_query.h"
 #include "rl_material_query.h"
+#include "rl_rtc_shade_query.h"
 #ifdef RL_EXPERIMENTAL  // the measured-and-lost restructurings: only in librl_render_exp.so, never in the product library
 #include "experimental/rl_rtiow_pool.h"
 #include "experimental/rl_rtiow_wave2.h"
@@ -2636,6 +2637,179 @@ int rl_rtiow_texture_values(const rl_scene *scene, const uint32_t *textures, con
   rl_stats local;
   int rc = rtiow_texture_values_impl(scene, q.d[0], q.d[1], q.d[2], n, q.d[3], g_ctx[(size_t)scene->ctx].stream, &local);
   if (rc == RL_OK) HIP_TRY(hipMemcpy(out_rgb, q.d[3], n * 24, hipMemcpyDeviceToHost));
+  return rc;
+}
+
+// ---- RTC shading queries (include/rl_render.h): prepare_computations, shade_hit, shadow_attenuation, lighting for buffers
+static int rtc_shade_query_check(const rl_scene *scene, uint64_t n, bool buffers_ok, rl_stats *st, bool &done) {
+  done = true;
+  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
+  if (!scene || scene->kind != 2) return set_err(RL_E_INVALID, "not an RTC scene");
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (!buffers_ok) return set_err(RL_E_INVALID, "null input / output buffer");
+  if (n > (uint64_t)1 << 40) return set_err(RL_E_INVALID, "batch too large");
+  done = false;
+  return RL_OK;
+}
+
+// the host forms' rule for comps[i].material (the device forms give such an element zeros)
+static int rtc_comps_check(const rl_scene *scene, const rl_rtc_comps *comps, uint64_t n) {
+  const uint32_t n_materials = (uint32_t)scene->rc().materials.size();
+  for (uint64_t i = 0; i < n; i++)
+    if (comps[i].hit != 0u && comps[i].material >= n_materials) return set_err(RL_E_INVALID, "comps record's material index outside the scene's table");
+  return RL_OK;
+}
+
+static RtcShadeQuery rtc_shade_query(const rl_scene *scene, uint64_t n) {
+  RtcShadeQuery Q{};
+  Q.n = n, Q.n_materials = (uint32_t)scene->rc().materials.size();
+  return Q;
+}
+
+int rl_rtc_prepare_rays_device(const rl_scene *scene, const void *d_rays, uint64_t n, void *d_out_comps, void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = rtc_shade_query_check(scene, n, d_rays && d_out_comps, st, done);
+  if (done) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RtcFullParams F = rtc_query_params(scene);
+  RtcShadeQuery Q = rtc_shade_query(scene, n);
+  Q.rays = (const rl_ray *)d_rays, Q.out_comps = (rl_rtc_comps *)d_out_comps;
+  std::lock_guard<std::mutex> lk(scene->mu);  // queries and renders of one scene: see rl_scene::mu
+  if ((rc = query_begin(scene, stream, st != nullptr)) != RL_OK) return rc;
+  hipLaunchKernelGGL((rtc_prepare_rays_kernel<QNT, 512>), dim3(query_grid(scene, (const void *)rtc_prepare_rays_kernel<QNT, 512>, n)), dim3(QNT), 0, stream, F, Q);
+  return query_end(scene, stream, st);
+}
+
+int rl_rtc_shade_hits_device(const rl_scene *scene, const void *d_comps, uint64_t n, void *d_out, void *d_opt_out_shadow, void *hip_stream,
+                             rl_stats *st) {
+  bool done;
+  int rc = rtc_shade_query_check(scene, n, d_comps && d_out, st, done);
+  if (done) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RtcFullParams F = rtc_query_params(scene);
+  RtcShadeQuery Q = rtc_shade_query(scene, n);
+  Q.comps = (const rl_rtc_comps *)d_comps, Q.out = (rl_rtc_shade *)d_out, Q.out_shadow = (double *)d_opt_out_shadow;
+  std::lock_guard<std::mutex> lk(scene->mu);
+  if ((rc = query_begin(scene, stream, st != nullptr)) != RL_OK) return rc;
+  hipLaunchKernelGGL((rtc_shade_hits_kernel<QNT, 512>), dim3(query_grid(scene, (const void *)rtc_shade_hits_kernel<QNT, 512>, n)), dim3(QNT), 0, stream, F, Q);
+  return query_end(scene, stream, st);
+}
+
+int rl_rtc_shadow_attenuation_device(const rl_scene *scene, const void *d_points, const void *d_light_positions, uint64_t n, void *d_out_att,
+                                     void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = rtc_shade_query_check(scene, n, d_points && d_light_positions && d_out_att, st, done);
+  if (done) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  RtcFullParams F = rtc_query_params(scene);
+  RtcShadeQuery Q = rtc_shade_query(scene, n);
+  Q.points = (const double *)d_points, Q.light_pos = (const double *)d_light_positions, Q.out_att = (double *)d_out_att;
+  std::lock_guard<std::mutex> lk(scene->mu);
+  if ((rc = query_begin(scene, stream, st != nullptr)) != RL_OK) return rc;
+  hipLaunchKernelGGL((rtc_shadow_attenuation_kernel<QNT, 512>), dim3(query_grid(scene, (const void *)rtc_shadow_attenuation_kernel<QNT, 512>, n)), dim3(QNT), 0,
+                     stream, F, Q);
+  return query_end(scene, stream, st);
+}
+
+// sync_st: the host form waits for the kernel through it; null: asynchronous, status ring
+static int rtc_lighting_impl(const rl_scene *scene, const void *d_comps, const void *d_light_positions, const void *d_light_intensities,
+                             const void *d_shadow_att, uint64_t n, void *d_out_rgb, hipStream_t stream, rl_stats *sync_st) {
+  RtcShadeQuery Q = rtc_shade_query(scene, n);
+  Q.comps = (const rl_rtc_comps *)d_comps, Q.light_pos = (const double *)d_light_positions, Q.light_int = (const double *)d_light_intensities;
+  Q.shadow_att = (const double *)d_shadow_att, Q.out_rgb = (double *)d_out_rgb;
+  const rl_rtc_material *materials = scene->d_rmaterials;
+  std::lock_guard<std::mutex> lk(scene->mu);
+  int rc = query_begin(scene, stream, sync_st != nullptr);
+  if (rc != RL_OK) return rc;
+  hipLaunchKernelGGL((rtc_lighting_kernel<QNT>), dim3(query_grid(scene, (const void *)rtc_lighting_kernel<QNT>, n)), dim3(QNT), 0, stream, materials, Q);
+  return query_end(scene, stream, sync_st);
+}
+
+int rl_rtc_lighting_device(const rl_scene *scene, const void *d_comps, const void *d_light_positions, const void *d_light_intensities,
+                           const void *d_shadow_att, uint64_t n, void *d_out_rgb, void *hip_stream) {
+  bool done;
+  int rc = rtc_shade_query_check(scene, n, d_comps && d_light_positions && d_light_intensities && d_shadow_att && d_out_rgb, nullptr, done);
+  if (done) return rc;
+  return rtc_lighting_impl(scene, d_comps, d_light_positions, d_light_intensities, d_shadow_att, n, d_out_rgb, (hipStream_t)hip_stream, nullptr);
+}
+
+int rl_rtc_prepare_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, rl_rtc_comps *out_comps, rl_stats *st) {
+  bool done;
+  int rc0 = rtc_shade_query_check(scene, n, rays && out_comps, st, done);
+  if (done) return rc0;
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * sizeof(rl_ray))) || (rc0 = q.alloc(1, n * sizeof(rl_rtc_comps)))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], rays, n * sizeof(rl_ray), hipMemcpyHostToDevice));
+  rl_stats local;
+  int rc = rl_rtc_prepare_rays_device(scene, q.d[0], n, q.d[1], g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    HIP_TRY(hipMemcpy(out_comps, q.d[1], n * sizeof(rl_rtc_comps), hipMemcpyDeviceToHost));
+    if (st) *st = local;
+  }
+  return rc;
+}
+
+int rl_rtc_shade_hits(const rl_scene *scene, const rl_rtc_comps *comps, uint64_t n, rl_rtc_shade *out, double *opt_out_shadow, rl_stats *st) {
+  bool done;
+  int rc0 = rtc_shade_query_check(scene, n, comps && out, st, done);
+  if (done) return rc0;
+  if ((rc0 = rtc_comps_check(scene, comps, n)) != RL_OK) return rc0;
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  const size_t sb = opt_out_shadow ? (size_t)n * scene->rc().lights.size() * sizeof(double) : 0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * sizeof(rl_rtc_comps))) || (rc0 = q.alloc(1, n * sizeof(rl_rtc_shade))) || (rc0 = q.alloc(2, sb))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], comps, n * sizeof(rl_rtc_comps), hipMemcpyHostToDevice));
+  rl_stats local;
+  int rc = rl_rtc_shade_hits_device(scene, q.d[0], n, q.d[1], opt_out_shadow ? (void *)q.d[2] : nullptr, g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    HIP_TRY(hipMemcpy(out, q.d[1], n * sizeof(rl_rtc_shade), hipMemcpyDeviceToHost));
+    if (sb) HIP_TRY(hipMemcpy(opt_out_shadow, q.d[2], sb, hipMemcpyDeviceToHost));
+    if (st) *st = local;
+  }
+  return rc;
+}
+
+int rl_rtc_shadow_attenuation(const rl_scene *scene, const double *points, const double *light_positions, uint64_t n, double *out_att,
+                              rl_stats *st) {
+  bool done;
+  int rc0 = rtc_shade_query_check(scene, n, points && light_positions && out_att, st, done);
+  if (done) return rc0;
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * 24)) || (rc0 = q.alloc(1, n * 24)) || (rc0 = q.alloc(2, n * 8))) return rc0;
+  HIP_TRY(hipMemcpy(q.d[0], points, n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(q.d[1], light_positions, n * 24, hipMemcpyHostToDevice));
+  rl_stats local;
+  int rc = rl_rtc_shadow_attenuation_device(scene, q.d[0], q.d[1], n, q.d[2], g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
+    HIP_TRY(hipMemcpy(out_att, q.d[2], n * 8, hipMemcpyDeviceToHost));
+    if (st) *st = local;
+  }
+  return rc;
+}
+
+int rl_rtc_lighting(const rl_scene *scene, const rl_rtc_comps *comps, const double *light_positions, const double *light_intensities,
+                    const double *shadow_att, uint64_t n, double *out_rgb) {
+  bool done;
+  int rc0 = rtc_shade_query_check(scene, n, comps && light_positions && light_intensities && shadow_att && out_rgb, nullptr, done);
+  if (done) return rc0;
+  if ((rc0 = rtc_comps_check(scene, comps, n)) != RL_OK) return rc0;
+  if ((rc0 = rl::use_context(scene->ctx)) != RL_OK) return rc0;
+  // one staging buffer for the three light inputs: positions, intensities, attenuations
+  QueryStage q;
+  if ((rc0 = q.alloc(0, n * sizeof(rl_rtc_comps))) || (rc0 = q.alloc(1, n * 56)) || (rc0 = q.alloc(2, n * 24))) return rc0;
+  unsigned char *d_in = q.d[1];
+  HIP_TRY(hipMemcpy(q.d[0], comps, n * sizeof(rl_rtc_comps), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_in, light_positions, n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_in + n * 24, light_intensities, n * 24, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_in + n * 48, shadow_att, n * 8, hipMemcpyHostToDevice));
+  rl_stats local;
+  int rc = rtc_lighting_impl(scene, q.d[0], d_in, d_in + n * 24, d_in + n * 48, n, q.d[2], g_ctx[(size_t)scene->ctx].stream, &local);
+  if (rc == RL_OK) HIP_TRY(hipMemcpy(out_rgb, q.d[2], n * 24, hipMemcpyDeviceToHost));
   return rc;
 }
 

@@ -535,6 +535,32 @@ int rlh_material_query_probe(int which, const void *rays, const void *hits, void
     return -1;
   }
 }
+// RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
+// which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
+// b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,
+// c = n light intensities, d = n attenuations, out = n * 3 doubles.  0 or -1 (rlh_last_error).
+int rlh_rtc_shade_query_probe(int which, const void *a, const void *b, const void *c, const void *d, uint64_t n, void *out) {
+  try {
+    scenes::RtcScene s = scenes::rtc_test_mirror_scene();
+    if (which == 0) {
+      std::vector<rl_rtc_comps> r = s.world.prepare((const rl_ray *)a, (size_t)n);
+      std::memcpy(out, r.data(), r.size() * sizeof(rl_rtc_comps));
+    } else if (which == 1) {
+      std::vector<rl_rtc_shade> r = s.world.shade((const rl_rtc_comps *)a, (size_t)n);
+      std::memcpy(out, r.data(), r.size() * sizeof(rl_rtc_shade));
+    } else if (which == 2) {
+      std::vector<double> r = s.world.shadow_attenuation((const double *)a, (const double *)b, (size_t)n);
+      std::memcpy(out, r.data(), r.size() * sizeof(double));
+    } else {
+      std::vector<double> r = s.world.lighting((const rl_rtc_comps *)a, (const double *)b, (const double *)c, (const double *)d, (size_t)n);
+      std::memcpy(out, r.data(), r.size() * sizeof(double));
+    }
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // tests/ray_tracer.rs:242-275 (which = 0, needs the OBJ text), :56-240 mirror (1), :277-368 csg (2): Camera::render -> Canvas::ppm
 char *rlh_rtc_run_golden_test(int which, const char *obj_text, uint64_t obj_len, uint64_t *len) {
   try {

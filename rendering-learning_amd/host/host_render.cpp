@@ -151,4 +151,49 @@ std::vector<uint32_t> World::intersect(const rl_ray *rays, size_t n, uint32_t k,
   if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtc_intersect_rays: ") + rl_last_error());
   return counts;
 }
+namespace {
+struct SceneGuard {  // the flattened world on the device for one query
+  rl_scene *sc;
+  explicit SceneGuard(const World &w) {
+    Flattened f;
+    w.flatten(f);
+    rl_rtc_scene_desc d = f.desc();
+    sc = rl_rtc_scene_create(&d);
+    if (!sc) throw std::runtime_error(std::string("rl_rtc_scene_create: ") + rl_last_error());
+  }
+  ~SceneGuard() { rl_scene_destroy(sc); }
+  SceneGuard(const SceneGuard &) = delete;
+  SceneGuard &operator=(const SceneGuard &) = delete;
+};
+}  // namespace
+std::vector<rl_rtc_comps> World::prepare(const rl_ray *rays, size_t n) const {  // intersect.rs:159-168, :48-115
+  SceneGuard g(*this);
+  std::vector<rl_rtc_comps> out(n);
+  int rc = rl_rtc_prepare_rays(g.sc, rays, n, out.data(), nullptr);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtc_prepare_rays: ") + rl_last_error());
+  return out;
+}
+std::vector<rl_rtc_shade> World::shade(const rl_rtc_comps *comps, size_t n, std::vector<double> *shadow) const {  // world.rs:57-87
+  SceneGuard g(*this);
+  std::vector<rl_rtc_shade> out(n);
+  if (shadow) shadow->assign(n * lights.size(), 0.0);
+  int rc = rl_rtc_shade_hits(g.sc, comps, n, out.data(), shadow && !shadow->empty() ? shadow->data() : nullptr, nullptr);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtc_shade_hits: ") + rl_last_error());
+  return out;
+}
+std::vector<double> World::shadow_attenuation(const double *points, const double *light_positions, size_t n) const {  // world.rs:104-126
+  SceneGuard g(*this);
+  std::vector<double> out(n);
+  int rc = rl_rtc_shadow_attenuation(g.sc, points, light_positions, n, out.data(), nullptr);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtc_shadow_attenuation: ") + rl_last_error());
+  return out;
+}
+std::vector<double> World::lighting(const rl_rtc_comps *comps, const double *light_positions, const double *light_intensities,
+                                    const double *shadow_att, size_t n) const {  // material.rs:54-90
+  SceneGuard g(*this);
+  std::vector<double> out(n * 3);
+  int rc = rl_rtc_lighting(g.sc, comps, light_positions, light_intensities, shadow_att, n, out.data());
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtc_lighting: ") + rl_last_error());
+  return out;
+}
 }  // namespace rtc

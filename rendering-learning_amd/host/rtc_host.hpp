@@ -569,6 +569,15 @@ struct World {
   std::vector<double> color_at(const rl_ray *rays, size_t n) const;
   std::vector<uint32_t> intersect(const rl_ray *rays, size_t n, uint32_t k = 0, std::vector<rl_rtc_isect> *isects = nullptr,
                                   std::vector<uint32_t> *hit_index = nullptr) const;
+  // The shading queries (rl_rtc_prepare_rays / rl_rtc_shade_hits / rl_rtc_shadow_attenuation / rl_rtc_lighting; host_render.cpp), on the
+  // GPU.  prepare: hit(&intersect(&ray)).map(prepare_computations) (intersect.rs:159-168, :48-115), hit == 0 for None.  shade: what
+  // shade_hit (world.rs:57-87) computes before it recurses; `shadow` (optional) receives [n][lights.size()] attenuations.
+  // shadow_attenuation (world.rs:104-126): n points and n light positions (3 doubles each).  lighting (material.rs:54-90): n * 3 doubles.
+  std::vector<rl_rtc_comps> prepare(const rl_ray *rays, size_t n) const;
+  std::vector<rl_rtc_shade> shade(const rl_rtc_comps *comps, size_t n, std::vector<double> *shadow = nullptr) const;
+  std::vector<double> shadow_attenuation(const double *points, const double *light_positions, size_t n) const;
+  std::vector<double> lighting(const rl_rtc_comps *comps, const double *light_positions, const double *light_intensities, const double *shadow_att,
+                               size_t n) const;
 };
 
 struct RenderOpts {
