@@ -92,6 +92,9 @@ void drop_multi_state() {  // rl_init / rl_shutdown: communicators never outlive
   g_emulated = false;
 }
 }  // namespace rl
+
+#include "rl_host_api.h"  // render_check, HostStaging
+
 namespace {
 
 // out[r][x][c] = gathered[r % G][r / G][x][c]: the rows of rank g sit compact in slot g of the gather buffer
@@ -289,62 +292,45 @@ int rl_debug_rccl_loadable(void) { return load_rccl() ? 1 : 0; }
 int rl_debug_multi_uses_rccl(void) { return !g_emulated && (int)g_rccl.comms.size() == n_contexts() && n_contexts() > 1; }
 
 int rl_rtiow_render_multi_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, void *d_out_rgb_sum, rl_stats *st) {
-  if (!lib_ready()) return set_err_public(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || scene->kind != 1 || !cam || !d_out_rgb_sum) return set_err_public(RL_E_INVALID, "bad argument");
-  if (cam->image_width == 0 || cam->image_height == 0) return set_err_public(RL_E_INVALID, "empty image");
-  int rc = render_multi(scene, cam->image_width, cam->image_height, d_out_rgb_sum, st,
-                        [&](const rl_scene *rep, uint32_t g, uint32_t G, void *d_rows, hipStream_t stream, bool want_stats) {
-                          return rtiow_render_launch(rep, cam, first_sample, g, G, d_rows, stream, want_stats);
-                        });
-  return rc;
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), d_out_rgb_sum != nullptr, 0, "empty image", st, done);
+  if (done) return rc;
+  return render_multi(scene, cam->image_width, cam->image_height, d_out_rgb_sum, st,
+                      [&](const rl_scene *rep, uint32_t g, uint32_t G, void *d_rows, hipStream_t stream, bool want_stats) {
+                        return rtiow_render_launch(rep, cam, first_sample, g, G, d_rows, stream, want_stats);
+                      });
 }
 
 int rl_rtiow_render_multi(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, double *out_rgb_sum, rl_stats *st) {
-  if (!lib_ready()) return set_err_public(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || !cam || !out_rgb_sum) return set_err_public(RL_E_INVALID, "bad argument");
-  size_t bytes = (size_t)cam->image_width * cam->image_height * 3 * sizeof(double);
-  if (bytes == 0) return set_err_public(RL_E_INVALID, "empty image");
-  int rc = use_context(0);
-  if (rc != RL_OK) return rc;
-  DevBuf<double> d_out;
-  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), out_rgb_sum != nullptr, 0, "empty image", st, done);
+  if (done) return rc;
+  HostStaging q(nullptr);
+  void *d_out = q.out(out_rgb_sum, frame_of(cam).rows_bytes(0, 1));
+  if (q.rc != RL_OK) return q.rc;
   rl_stats local;
-  rc = rl_rtiow_render_multi_device(scene, cam, first_sample, d_out, &local);
-  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
-    hipError_t e = hipMemcpy(out_rgb_sum, d_out, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err_public(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  }
-  if (st) *st = local;
-  return rc;
+  return q.finish(rl_rtiow_render_multi_device(scene, cam, first_sample, d_out, &local), st, local);
 }
 
 int rl_rtc_render_multi_device(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, void *d_out_rgb, rl_stats *st) {
-  if (!lib_ready()) return set_err_public(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || scene->kind != 2 || !cam || !d_out_rgb || aa == 0) return set_err_public(RL_E_INVALID, "bad argument");
-  if (cam->hsize == 0 || cam->vsize == 0) return set_err_public(RL_E_INVALID, "empty image");
-  int rc = render_multi(scene, cam->hsize, cam->vsize, d_out_rgb, st, [&](const rl_scene *rep, uint32_t g, uint32_t G, void *d_rows, hipStream_t stream, bool want_stats) {
+  bool done;
+  int rc = render_check(scene, 2, frame_of(cam), d_out_rgb && aa != 0, 0, "empty image", st, done);
+  if (done) return rc;
+  return render_multi(scene, cam->hsize, cam->vsize, d_out_rgb, st, [&](const rl_scene *rep, uint32_t g, uint32_t G, void *d_rows, hipStream_t stream, bool want_stats) {
     return rtc_render_launch(rep, cam, aa, g, G, d_rows, stream, want_stats);
   });
-  return rc;
 }
 
+// (aa == 0 is left to the _device form: an empty image is refused as such whatever aa is, as it always was)
 int rl_rtc_render_multi(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, double *out_rgb, rl_stats *st) {
-  if (!lib_ready()) return set_err_public(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || !cam || !out_rgb) return set_err_public(RL_E_INVALID, "bad argument");
-  size_t bytes = (size_t)cam->hsize * cam->vsize * 3 * sizeof(double);
-  if (bytes == 0) return set_err_public(RL_E_INVALID, "empty image");
-  int rc = use_context(0);
-  if (rc != RL_OK) return rc;
-  DevBuf<double> d_out;
-  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
+  bool done;
+  int rc = render_check(scene, 2, frame_of(cam), out_rgb != nullptr, 0, "empty image", st, done);
+  if (done) return rc;
+  HostStaging q(nullptr);
+  void *d_out = q.out(out_rgb, frame_of(cam).rows_bytes(0, 1));
+  if (q.rc != RL_OK) return q.rc;
   rl_stats local;
-  rc = rl_rtc_render_multi_device(scene, cam, aa, d_out, &local);
-  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
-    hipError_t e = hipMemcpy(out_rgb, d_out, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err_public(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  }
-  if (st) *st = local;
-  return rc;
+  return q.finish(rl_rtc_render_multi_device(scene, cam, aa, d_out, &local), st, local);
 }
 
 }  // extern "C"

@@ -1,16 +1,15 @@
 // The host side of the batched queries (include/rl_render.h rl_*_rays*, rl_rtiow_texture_values*, rl_rtc_lighting*; DESIGN.md §3.8 - §3.11;
 // kernels: rl_ray_query.h, rl_material_query.h, rl_rtc_shade_query.h and the *_rays_kernel forms of the render kernels): 11 queries, each in a
 // host-buffer and a _device form.  Not a translation unit of its own: rl_render.hip includes it once, at its end, and it uses that file's
-// statics (g_sw, g_cus, g_lds_max, g_ctx, ensure_lds_attr, fill_rtiow_params, stage_params, chacha_key_from_seed).
+// statics (g_sw, g_cus, g_lds_max, ensure_lds_attr, fill_rtiow_params, stage_params, chacha_key_from_seed).
 //
 // Every entry point is made of three moves, each of which exists once:
 //   query_check   — library ready, scene family, the empty batch, null buffers, the batch bound; what is particular to a call follows it
 //   query_run     — the scene's lock around query_begin, the call's launches and query_end
-//   QueryStaging  — the host forms' device copies of the caller's arrays, and the copy back
+//   HostStaging   — the host forms' device copies of the caller's arrays, and the copy back (rl_host_api.h: the render forms' too)
 // A new query is a check line, a run callable and a staging list.
 #pragma once
 #include <atomic>
-#include <initializer_list>
 #include <utility>
 
 namespace {
@@ -88,9 +87,6 @@ int query_check(const void *subject, int kind, uint64_t n, bool buffers_ok, rl_s
   return RL_OK;
 }
 
-// a query that ended with one of these has written every output
-bool outputs_written(int rc) { return rc == RL_OK || rc == RL_E_DEGENERATE; }
-
 // rl_debug_last_query.  Atomic: queries of two scenes run under two locks.
 std::atomic<int> g_last_query_kernel{0};                  // 1 reference order, 2 fast
 std::atomic<unsigned long long> g_last_query_retraced{0};  // the rays the fast kernel re-traced (synchronous calls)
@@ -113,76 +109,6 @@ int query_run(const rl_scene *scene, hipStream_t stream, rl_stats *sync_st, Laun
   return rc;
 }
 
-// The host-buffer forms: the caller's arrays staged in device memory of context `ctx`, the query run on that context's library stream
-// (synchronously: every form passes a local rl_stats or waits itself), the outputs copied back.  in / out / inout / back return the
-// device pointer; an absent optional output is null in and null out.  The first failure stays in `rc` and makes the later steps do
-// nothing: a form looks at it once, before it launches.
-class QueryStaging {
- public:
-  int rc;
-  hipStream_t stream = nullptr;
-  explicit QueryStaging(int ctx) : rc(rl::use_context(ctx)) {
-    if (rc == RL_OK) stream = g_ctx[(size_t)ctx].stream;
-    bufs_.reserve(4), back_.reserve(4);  // what the largest form stages: one host allocation each, whatever the call
-  }
-  // host arrays uploaded back to back into one allocation
-  void *in(std::initializer_list<std::pair<const void *, size_t>> parts) {
-    size_t total = 0, at = 0;
-    for (const auto &p : parts) total += p.second;
-    unsigned char *d = (unsigned char *)reserve(total);
-    for (const auto &p : parts) {
-      if (rc == RL_OK) rc = upload(d + at, p.first, p.second);
-      at += p.second;
-    }
-    return d;
-  }
-  void *in(const void *host, size_t bytes) { return in({{host, bytes}}); }
-  void *out(void *host, size_t bytes) { return host ? back(host, reserve(bytes), bytes) : nullptr; }
-  void *inout(void *host, size_t bytes) { return host ? back(host, in(host, bytes), bytes) : nullptr; }
-  // `dev` (staged by in) is also an output, copied to another host array than it came from
-  void *back(void *host, void *dev, size_t bytes) {
-    if (!host) return nullptr;
-    back_.push_back({host, dev, bytes});
-    return dev;
-  }
-  // after the query returned qrc: the copies back, and *st = local when the caller gave opt_stats, where every output is written
-  // (RL_OK, RL_E_DEGENERATE).  -> qrc, or what a copy failed with.
-  int finish(int qrc, rl_stats *st, const rl_stats &local) {
-    if (!outputs_written(qrc)) return qrc;
-    int rcb = copy_back();
-    if (rcb != RL_OK) return rcb;
-    if (st) *st = local;
-    return qrc;
-  }
-  // the forms without statistics: the copies back on RL_OK only
-  int finish(int qrc) { return qrc == RL_OK ? copy_back() : qrc; }
-
- private:
-  struct Back {
-    void *host, *dev;
-    size_t bytes;
-  };
-  std::vector<DevBuf<unsigned char>> bufs_;
-  std::vector<Back> back_;
-  int copy_back() {
-    for (const Back &b : back_)
-      if (b.bytes) HIP_TRY(hipMemcpy(b.host, b.dev, b.bytes, hipMemcpyDeviceToHost));
-    return RL_OK;
-  }
-  void *reserve(size_t bytes) {
-    if (rc != RL_OK) return nullptr;
-    bufs_.emplace_back();
-    rc = [&]() -> int {
-      HIP_TRY(bufs_.back().reserve(bytes ? bytes : 1));
-      return RL_OK;
-    }();
-    return bufs_.back().get();
-  }
-  static int upload(void *dev, const void *host, size_t bytes) {
-    if (bytes) HIP_TRY(hipMemcpy(dev, host, bytes, hipMemcpyHostToDevice));
-    return RL_OK;
-  }
-};
 }  // namespace
 
 extern "C" {
@@ -290,7 +216,7 @@ int rl_rtiow_hit_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, dou
   int rc = query_check(scene, 1, n, rays && out, st, done);
   if (done) return rc;
   if ((rc = rtiow_hit_rays_rules(scene, tmin, tmax)) != RL_OK) return rc;
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_rays = q.in(rays, n * sizeof(rl_ray)), *d_out = q.out(out, n * sizeof(rl_rtiow_hit));
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;  // without opt_stats the call is counter-free (the fast kernel where it applies); rays and flagged are still collected
@@ -304,7 +230,7 @@ int rl_rtc_intersect_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n,
   if (done) return rc;
   if ((k != 0) != (out_isects != nullptr)) return set_err(RL_E_INVALID, "null buffer (out_isects goes with k > 0)");
   if (k && n > ((uint64_t)1 << 44) / k) return set_err(RL_E_INVALID, "n * k too large");
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_rays = q.in(rays, n * sizeof(rl_ray));
   void *d_isects = q.inout(out_isects, (size_t)n * k * sizeof(rl_rtc_isect));  // uploaded: entries beyond a ray's count stay the caller's
   void *d_counts = q.out(out_counts, n * 4), *d_hit_index = q.out(out_hit_index, n * 4);
@@ -317,7 +243,7 @@ int rl_rtc_color_at_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, 
   bool done;
   int rc = query_check(scene, 2, n, rays && out_rgb, st, done);
   if (done) return rc;
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_rays = q.in(rays, n * sizeof(rl_ray)), *d_rgb = q.out(out_rgb, n * 24);
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;
@@ -444,7 +370,7 @@ int rl_rtiow_ray_color_rays(const rl_scene *scene, const rl_ray *rays, const rl_
   int rc = query_check(scene, 1, n, rays && cursors && out_rgb && background, st, done);
   if (done) return rc;
   if ((rc = cursors_check(cursors, n)) != RL_OK) return rc;
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_rays = q.in(rays, n * sizeof(rl_ray)), *d_cursors = q.in(cursors, n * sizeof(rl_rng_cursor)), *d_rgb = q.out(out_rgb, n * 24);
   void *d_out_cursors = q.back(opt_out_cursors, d_cursors, n * sizeof(rl_rng_cursor));  // the staged copy: the caller's cursors are never written
   void *d_counts = q.out(opt_out_ray_counts, n * 4);
@@ -484,7 +410,7 @@ int rl_rtiow_camera_rays(const rl_rtiow_camera *cam, uint64_t n, const uint32_t 
   for (uint64_t i = 0; i < n; i++)
     if (px[i] >= cam->image_width || py[i] >= cam->image_height) return set_err(RL_E_INVALID, "pixel outside the image");
   if ((rc = cursors_check(cursors, n)) != RL_OK) return rc;
-  QueryStaging q(0);
+  HostStaging q(nullptr);
   unsigned char *d_xy = (unsigned char *)q.in({{px, n * 4}, {py, n * 4}});
   void *d_cursors = q.in(cursors, n * sizeof(rl_rng_cursor)), *d_rays = q.out(out_rays, n * sizeof(rl_ray));
   q.back(out_cursors, d_cursors, n * sizeof(rl_rng_cursor));
@@ -545,7 +471,7 @@ int rl_rtiow_scatter_rays(const rl_scene *scene, const rl_ray *rays, const rl_rt
   const uint32_t n_materials = (uint32_t)scene->rt().materials.size();
   for (uint64_t i = 0; i < n; i++)
     if (hits[i].hit != 0u && hits[i].material >= n_materials) return set_err(RL_E_INVALID, "hit record's material index outside the scene's table");
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_rays = q.in(rays, n * sizeof(rl_ray)), *d_hits = q.in(hits, n * sizeof(rl_rtiow_hit)), *d_cursors = q.in(cursors, n * sizeof(rl_rng_cursor));
   void *d_out = q.out(out, n * sizeof(rl_rtiow_scatter));
   void *d_out_cursors = q.back(opt_out_cursors, d_cursors, n * sizeof(rl_rng_cursor));  // the staged copy: the caller's cursors are never written
@@ -582,7 +508,7 @@ int rl_rtiow_texture_values(const rl_scene *scene, const uint32_t *textures, con
   const uint32_t n_textures = (uint32_t)scene->rt().textures.size();
   for (uint64_t i = 0; i < n; i++)
     if (textures[i] >= n_textures) return set_err(RL_E_INVALID, "texture id outside the scene's table");
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_textures = q.in(textures, n * 4), *d_uv = q.in(uv, n * 16), *d_p = q.in(p, n * 24), *d_rgb = q.out(out_rgb, n * 24);
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;  // (waits for the kernel; the call has no opt_stats and copies back on RL_OK only)
@@ -674,7 +600,7 @@ int rl_rtc_prepare_rays(const rl_scene *scene, const rl_ray *rays, uint64_t n, r
   bool done;
   int rc = query_check(scene, 2, n, rays && out_comps, st, done);
   if (done) return rc;
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_rays = q.in(rays, n * sizeof(rl_ray)), *d_comps = q.out(out_comps, n * sizeof(rl_rtc_comps));
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;
@@ -686,7 +612,7 @@ int rl_rtc_shade_hits(const rl_scene *scene, const rl_rtc_comps *comps, uint64_t
   int rc = query_check(scene, 2, n, comps && out, st, done);
   if (done) return rc;
   if ((rc = rtc_comps_check(scene, comps, n)) != RL_OK) return rc;
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_comps = q.in(comps, n * sizeof(rl_rtc_comps)), *d_out = q.out(out, n * sizeof(rl_rtc_shade));
   void *d_shadow = q.out(opt_out_shadow, (size_t)n * scene->rc().lights.size() * sizeof(double));  // [n][the scene's lights]
   if (q.rc != RL_OK) return q.rc;
@@ -699,7 +625,7 @@ int rl_rtc_shadow_attenuation(const rl_scene *scene, const double *points, const
   bool done;
   int rc = query_check(scene, 2, n, points && light_positions && out_att, st, done);
   if (done) return rc;
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_points = q.in(points, n * 24), *d_light_positions = q.in(light_positions, n * 24), *d_att = q.out(out_att, n * 8);
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;
@@ -712,7 +638,7 @@ int rl_rtc_lighting(const rl_scene *scene, const rl_rtc_comps *comps, const doub
   int rc = query_check(scene, 2, n, comps && light_positions && light_intensities && shadow_att && out_rgb, nullptr, done);
   if (done) return rc;
   if ((rc = rtc_comps_check(scene, comps, n)) != RL_OK) return rc;
-  QueryStaging q(scene->ctx);
+  HostStaging q(scene);
   void *d_comps = q.in(comps, n * sizeof(rl_rtc_comps)), *d_rgb = q.out(out_rgb, n * 24);
   // one allocation for the three light inputs: positions, intensities, attenuations
   unsigned char *d_in = (unsigned char *)q.in({{light_positions, n * 24}, {light_intensities, n * 24}, {shadow_att, n * 8}});

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <limits>
 #include <map>
@@ -75,7 +76,7 @@ struct Switches {
   int pixel_entry = rl::PIXEL_ENTRY_DEFAULT;  // RL_PIXEL_ENTRY=0|1|2|3: the fast kernel's camera rays start at the root / at their pixel's entry cut of up to n entries (rl_pixel_entry.h)
   bool pixel_entry_sphere = true;  // RL_PIXEL_ENTRY_SPHERE=0: that cut keeps every leaf whose BOX the pixel's beam touches; default: only those whose sphere it may touch
 } g_sw;
-unsigned long long g_last_slow_traces = 0;
+std::atomic<unsigned long long> g_last_slow_traces{0};  // rl_debug_slow_traces.  Atomic: rl_render_status of two scenes runs under two locks.
 bool g_fast_debug_stats = false;  // tools only (experimental library): counting renders run the fast kernel too (counters are then NOT the reference's)
 
 void read_switches() {
@@ -592,6 +593,8 @@ int mark_render_end(const rl_scene *scene, hipStream_t stream) {  // collect_sta
 }
 }  // namespace rl
 using rl::post_status;
+
+#include "rl_host_api.h"  // scene_context, render_check, render_run, HostStaging
 
 #ifdef RL_EXPERIMENTAL
 // Wavefront (v3) driver: one PASS = begin_pass, TRAV, SHADE, GEN (rl_rtiow_wavefront.h); passes are enqueued in
@@ -1320,34 +1323,21 @@ extern "C" {
 
 int rl_rtiow_render_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
                            void *d_out, void *hip_stream, rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || scene->kind != 1 || !cam || !d_out || row_step == 0) return set_err(RL_E_INVALID, "bad argument");
-  if (cam->image_width == 0 || cam->image_height == 0) return set_err(RL_E_INVALID, "empty image");
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), d_out && row_step != 0, row_first, "empty image", st, done);
+  if (done) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (row_first >= cam->image_height) {
-    if (st) std::memset(st, 0, sizeof *st);
-    return RL_OK;
-  }
-  std::lock_guard<std::mutex> lk(scene->mu);  // concurrent renders of one scene: see rl_scene::mu
-  int rc = rl::rtiow_render_launch(scene, cam, first_sample, row_first, row_step, d_out, stream, st != nullptr);
-  if (rc != RL_OK) return rc;
-  return st ? rl::collect_stats(scene, stream, st) : post_status(scene, stream);
+  return render_run(scene, stream, st, [&] { return rl::rtiow_render_launch(scene, cam, first_sample, row_first, row_step, d_out, stream, st != nullptr); });
 }
 
 int rl_rtiow_render_independent_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
                                        uint32_t accumulate, void *d_out, void *hip_stream, rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || scene->kind != 1 || !cam || !d_out || row_step == 0) return set_err(RL_E_INVALID, "bad argument");
-  if (cam->image_width == 0 || cam->image_height == 0) return set_err(RL_E_INVALID, "empty image");
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), d_out && row_step != 0, row_first, "empty image", st, done);
+  if (done) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (row_first >= cam->image_height) {
-    if (st) std::memset(st, 0, sizeof *st);
-    return RL_OK;
-  }
-  std::lock_guard<std::mutex> lk(scene->mu);  // concurrent renders of one scene: see rl_scene::mu
-  int rc = rl::rtiow_render_indep_launch(scene, cam, first_sample, row_first, row_step, accumulate != 0, d_out, stream, st != nullptr);
-  if (rc != RL_OK) return rc;
-  return st ? rl::collect_stats(scene, stream, st) : post_status(scene, stream);
+  return render_run(scene, stream, st,
+                    [&] { return rl::rtiow_render_indep_launch(scene, cam, first_sample, row_first, row_step, accumulate != 0, d_out, stream, st != nullptr); });
 }
 
 // Completion + status of the last ASYNCHRONOUS render of this scene (rl_*_render_device / rl_*_render_multi_device with
@@ -1366,9 +1356,8 @@ int rl_render_status(const rl_scene *scene, rl_stats *st) {
     bool any = false;
     for (int k = 0; k < rl_scene::N_STATUS; k++) any |= r->status_pending[k];
     if (any) {
-      if (r->ctx < 0 || (size_t)r->ctx >= g_ctx.size() || g_ctx[(size_t)r->ctx].device != r->device)
-        return set_err(RL_E_INVALID, "scene belongs to a device context that no longer exists (created under another rl_init / rl_init_multi)");
-      int rc = rl::use_context(r->ctx);
+      DevCtx *c;
+      int rc = scene_context(r, c);
       if (rc != RL_OK) return rc;
       for (int k = 0; k < rl_scene::N_STATUS; k++)
         if (r->status_pending[k]) {
@@ -1396,9 +1385,8 @@ int rl_rtiow_render_progress(const rl_scene *scene, uint64_t *pixels_claimed, ui
   {
     std::lock_guard<std::mutex> lk(ms->mu);
     if (!ms->progress_on) {  // first call: renders enqueued from now on count in host-visible memory
-      if (ms->ctx < 0 || (size_t)ms->ctx >= g_ctx.size() || g_ctx[(size_t)ms->ctx].device != ms->device)
-        return set_err(RL_E_INVALID, "scene belongs to a device context that no longer exists (created under another rl_init / rl_init_multi)");
-      int rc = rl::use_context(ms->ctx);
+      DevCtx *c;
+      int rc = scene_context(ms, c);
       if (rc != RL_OK) return rc;
       HIP_TRY(ms->h_progress.reserve(16, hipHostMallocMapped | hipHostMallocCoherent));
       std::memset(ms->h_progress, 0, 64);
@@ -1574,7 +1562,8 @@ void rl_debug_set_pixel_entry_sphere(int on) { g_sw.pixel_entry_sphere = on != 0
 // Tests: the entry table of the scene's most recent fast-traversal render (n_pixels words, rows x W of the shard rendered), after that render has finished
 int rl_debug_pixel_entry_read(const rl_scene *scene, uint32_t *out, uint64_t n_pixels) {
   if (!scene || !out || !scene->d_pixel_entry || n_pixels > scene->d_pixel_entry.size()) return RL_E_INVALID;
-  int rc0 = rl::use_context(scene->ctx);
+  DevCtx *c;
+  int rc0 = scene_context(scene, c);
   if (rc0 != RL_OK) return rc0;
   HIP_TRY(hipMemcpy(out, scene->d_pixel_entry, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return RL_OK;
@@ -1657,58 +1646,27 @@ int rl_debug_pixel_rays_read(const rl_scene *scene, uint32_t *out, uint64_t n_pi
 
 int rl_rtiow_render_rows(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
                          double *out, rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || !cam || !out || row_step == 0) return set_err(RL_E_INVALID, "bad argument");
-  uint32_t H = cam->image_height, W = cam->image_width;
-  uint32_t nrows = row_first < H ? (H - row_first + row_step - 1) / row_step : 0;
-  size_t bytes = (size_t)nrows * W * 3 * sizeof(double);
-  if (bytes == 0) {
-    if (st) std::memset(st, 0, sizeof *st);
-    return RL_OK;
-  }
-  int rc0 = rl::use_context(scene->ctx);
-  if (rc0 != RL_OK) return rc0;
-  DevBuf<double> d_out;
-  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), out && row_step != 0, row_first, nullptr, st, done);
+  if (done) return rc;
+  HostStaging q(scene);
+  void *d_out = q.out(out, frame_of(cam).rows_bytes(row_first, row_step));
+  if (q.rc != RL_OK) return q.rc;
   rl_stats local;
-  int rc = rl_rtiow_render_device(scene, cam, first_sample, row_first, row_step, d_out, g_ctx[(size_t)scene->ctx].stream, &local);
-  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
-    hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  }
-  if (st) *st = local;
-  return rc;
+  return q.finish(rl_rtiow_render_device(scene, cam, first_sample, row_first, row_step, d_out, q.stream, &local), st, local);
 }
 
 int rl_rtiow_render_independent_rows(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
                                      uint32_t accumulate, double *out, rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || !cam || !out || row_step == 0) return set_err(RL_E_INVALID, "bad argument");
-  uint32_t H = cam->image_height, W = cam->image_width;
-  uint32_t nrows = row_first < H ? (H - row_first + row_step - 1) / row_step : 0;
-  size_t bytes = (size_t)nrows * W * 3 * sizeof(double);
-  if (bytes == 0) {
-    if (st) std::memset(st, 0, sizeof *st);
-    return RL_OK;
-  }
-  int rc0 = rl::use_context(scene->ctx);
-  if (rc0 != RL_OK) return rc0;
-  DevBuf<double> d_out;
-  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
-  int rc = RL_OK;
-  if (accumulate) {  // the caller's sums are the fold's start
-    hipError_t e = hipMemcpy(d_out, out, bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy H2D: ") + hipGetErrorString(e));
-  }
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), out && row_step != 0, row_first, nullptr, st, done);
+  if (done) return rc;
+  HostStaging q(scene);
+  const size_t bytes = frame_of(cam).rows_bytes(row_first, row_step);
+  void *d_out = accumulate ? q.inout(out, bytes) : q.out(out, bytes);  // accumulate: the caller's sums are the fold's start
+  if (q.rc != RL_OK) return q.rc;
   rl_stats local;
-  std::memset(&local, 0, sizeof local);
-  if (rc == RL_OK) rc = rl_rtiow_render_independent_device(scene, cam, first_sample, row_first, row_step, accumulate, d_out, g_ctx[(size_t)scene->ctx].stream, &local);
-  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
-    hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  }
-  if (st) *st = local;
-  return rc;
+  return q.finish(rl_rtiow_render_independent_device(scene, cam, first_sample, row_first, row_step, accumulate, d_out, q.stream, &local), st, local);
 }
 
 int rl_rtiow_encode_rgb8_device(const void *d_rgb_sum, uint64_t n_pixels, uint32_t samples, void *d_rgb8, void *hip_stream) {
@@ -1723,31 +1681,14 @@ int rl_rtiow_encode_rgb8_device(const void *d_rgb_sum, uint64_t n_pixels, uint32
 }
 
 int rl_rtiow_render_rgb8(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint8_t *out, rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || !cam || !out) return set_err(RL_E_INVALID, "bad argument");
-  size_t npix = (size_t)cam->image_width * cam->image_height;
-  if (npix == 0 || cam->samples_per_pixel == 0) return set_err(RL_E_INVALID, "empty image / zero samples");
-  int rc0 = rl::use_context(scene->ctx);
-  if (rc0 != RL_OK) return rc0;
-  hipStream_t stream = g_ctx[(size_t)scene->ctx].stream;
-  DevBuf<double> d_sum;
-  DevBuf<unsigned char> d_u8;
-  HIP_TRY(d_sum.reserve(npix * 3));
-  hipError_t e = d_u8.reserve(npix * 3);
-  if (e != hipSuccess) return set_err(RL_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-  rl_stats local;
-  int rc = rl_rtiow_render_device(scene, cam, first_sample, 0, 1, d_sum, stream, &local);
-  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
-    int rc2 = rl_rtiow_encode_rgb8_device(d_sum, npix, cam->samples_per_pixel, d_u8, stream);
-    if (rc2 != RL_OK) rc = rc2;
-    else {
-      e = hipMemcpyAsync(out, d_u8, npix * 3, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("D2H: ") + hipGetErrorString(e));
-    }
-  }
-  if (st) *st = local;
-  return rc;
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), out != nullptr, 0, "empty image / zero samples", st, done);
+  if (done) return rc;
+  if (cam->samples_per_pixel == 0) return set_err(RL_E_INVALID, "empty image / zero samples");
+  const size_t npix = (size_t)cam->image_width * cam->image_height;
+  return render_rgb8(
+      scene, npix, out, st, [&](void *d_sum, hipStream_t stream, rl_stats *local) { return rl_rtiow_render_device(scene, cam, first_sample, 0, 1, d_sum, stream, local); },
+      [&](void *d_sum, void *d_u8, hipStream_t stream) { return rl_rtiow_encode_rgb8_device(d_sum, npix, cam->samples_per_pixel, d_u8, stream); });
 }
 
 int rl_rtiow_render(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, double *out, rl_stats *st) {
@@ -1960,43 +1901,24 @@ extern "C" {
 
 int rl_rtc_render_device(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, uint32_t row_first, uint32_t row_step, void *d_out,
                          void *hip_stream, rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || scene->kind != 2 || !cam || !d_out || row_step == 0 || aa == 0) return set_err(RL_E_INVALID, "bad argument");
-  if (cam->hsize == 0 || cam->vsize == 0) return set_err(RL_E_INVALID, "empty image");
+  bool done;
+  int rc = render_check(scene, 2, frame_of(cam), d_out && row_step != 0 && aa != 0, row_first, "empty image", st, done);
+  if (done) return rc;
   hipStream_t stream = (hipStream_t)hip_stream;
-  if (row_first >= cam->vsize) {
-    if (st) std::memset(st, 0, sizeof *st);
-    return RL_OK;
-  }
-  std::lock_guard<std::mutex> lk(scene->mu);  // concurrent renders of one scene: see rl_scene::mu
-  int rc = rl::rtc_render_launch(scene, cam, aa, row_first, row_step, d_out, stream, st != nullptr);
-  if (rc != RL_OK) return rc;
-  return st ? rl::collect_stats(scene, stream, st) : post_status(scene, stream);
+  return render_run(scene, stream, st, [&] { return rl::rtc_render_launch(scene, cam, aa, row_first, row_step, d_out, stream, st != nullptr); });
 }
 
+// (the host forms leave aa == 0 to the _device form they call: a render of no rows is RL_OK whatever aa is, as it always was)
 int rl_rtc_render_rows(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, uint32_t row_first, uint32_t row_step, double *out,
                        rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || !cam || !out || row_step == 0) return set_err(RL_E_INVALID, "bad argument");
-  uint32_t H = cam->vsize, W = cam->hsize;
-  uint32_t nrows = row_first < H ? (H - row_first + row_step - 1) / row_step : 0;
-  size_t bytes = (size_t)nrows * W * 3 * sizeof(double);
-  if (bytes == 0) {
-    if (st) std::memset(st, 0, sizeof *st);
-    return RL_OK;
-  }
-  int rc0 = rl::use_context(scene->ctx);
-  if (rc0 != RL_OK) return rc0;
-  DevBuf<double> d_out;
-  HIP_TRY(d_out.reserve(bytes / sizeof(double)));
+  bool done;
+  int rc = render_check(scene, 2, frame_of(cam), out && row_step != 0, row_first, nullptr, st, done);
+  if (done) return rc;
+  HostStaging q(scene);
+  void *d_out = q.out(out, frame_of(cam).rows_bytes(row_first, row_step));
+  if (q.rc != RL_OK) return q.rc;
   rl_stats local;
-  int rc = rl_rtc_render_device(scene, cam, aa, row_first, row_step, d_out, g_ctx[(size_t)scene->ctx].stream, &local);
-  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
-    hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("hipMemcpy D2H: ") + hipGetErrorString(e));
-  }
-  if (st) *st = local;
-  return rc;
+  return q.finish(rl_rtc_render_device(scene, cam, aa, row_first, row_step, d_out, q.stream, &local), st, local);
 }
 
 int rl_rtc_encode_rgb8_device(const void *d_rgb, uint64_t n_pixels, void *d_rgb8, void *hip_stream) {
@@ -2010,31 +1932,13 @@ int rl_rtc_encode_rgb8_device(const void *d_rgb, uint64_t n_pixels, void *d_rgb8
 }
 
 int rl_rtc_render_rgb8(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, uint8_t *out, rl_stats *st) {
-  if (!g_ready) return set_err(RL_E_NO_DEVICE, "rl_init has not succeeded");
-  if (!scene || !cam || !out) return set_err(RL_E_INVALID, "bad argument");
-  size_t npix = (size_t)cam->hsize * cam->vsize;
-  if (npix == 0) return set_err(RL_E_INVALID, "empty image");
-  int rc0 = rl::use_context(scene->ctx);
-  if (rc0 != RL_OK) return rc0;
-  hipStream_t stream = g_ctx[(size_t)scene->ctx].stream;
-  DevBuf<double> d_rgb;
-  DevBuf<unsigned char> d_u8;
-  HIP_TRY(d_rgb.reserve(npix * 3));
-  hipError_t e = d_u8.reserve(npix * 3);
-  if (e != hipSuccess) return set_err(RL_E_DEVICE, std::string("hipMalloc: ") + hipGetErrorString(e));
-  rl_stats local;
-  int rc = rl_rtc_render_device(scene, cam, aa, 0, 1, d_rgb, stream, &local);
-  if (rc == RL_OK || rc == RL_E_DEGENERATE) {
-    int rc2 = rl_rtc_encode_rgb8_device(d_rgb, npix, d_u8, stream);
-    if (rc2 != RL_OK) rc = rc2;
-    else {
-      e = hipMemcpyAsync(out, d_u8, npix * 3, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) rc = set_err(RL_E_DEVICE, std::string("D2H: ") + hipGetErrorString(e));
-    }
-  }
-  if (st) *st = local;
-  return rc;
+  bool done;
+  int rc = render_check(scene, 2, frame_of(cam), out != nullptr, 0, "empty image", st, done);
+  if (done) return rc;
+  const size_t npix = (size_t)cam->hsize * cam->vsize;
+  return render_rgb8(
+      scene, npix, out, st, [&](void *d_rgb, hipStream_t stream, rl_stats *local) { return rl_rtc_render_device(scene, cam, aa, 0, 1, d_rgb, stream, local); },
+      [&](void *d_rgb, void *d_u8, hipStream_t stream) { return rl_rtc_encode_rgb8_device(d_rgb, npix, d_u8, stream); });
 }
 
 int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, double *out, rl_stats *st) {

@@ -1,11 +1,14 @@
-// Stand-alone host check of the batched queries' 22 entry points (include/rl_render.h; csrc/rl_query_api.h) on a machine without a GPU:
-// every form must return RL_E_NO_DEVICE before it touches a buffer — with valid buffers, with n = 0, and with every pointer NULL and
-// n > 0.  Meant to be built with the host sanitizers (the library's host code and this file; no Python involved):
+// Stand-alone host check of the batched queries' 22 entry points and the 14 render entry points with rl_render_status and
+// rl_rtiow_render_progress (include/rl_render.h; csrc/rl_query_api.h, csrc/rl_host_api.h) on a machine without a GPU: every form must
+// return RL_E_NO_DEVICE before it touches a buffer or opt_stats — with valid buffers, with nothing to do (n = 0; an image whose row_first
+// equals its height) and with every pointer NULL.  Meant to be built with the host sanitizers (the library's host code and this file; no
+// Python involved):
 //   cd rendering-learning_amd/csrc && for f in rl_render.hip rl_multi.hip rl_bvh_build.hip rl_program.cpp rl_fast_bvh.cpp; do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -Xarch_host -fsanitize=address,undefined -c -o /tmp/san_${f%.*}.o $f; done
 //   clang++ -std=c++17 -g -fsanitize=address,undefined -I../../include -c -o /tmp/san_main.o ../../tools/query_nodevice.cpp
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined -o /tmp/query_nodevice /tmp/san_*.o -ldl && /tmp/query_nodevice
 #include <cstdio>
+#include <cstring>
 #include <vector>
 
 #include "rl_render.h"
@@ -101,9 +104,57 @@ int main() {
   EXPECT(rl_rtc_shadow_attenuation_device(nullptr, nullptr, nullptr, n, nullptr, nullptr, nullptr), RL_E_NO_DEVICE);
   EXPECT(rl_rtc_lighting(nullptr, nullptr, nullptr, nullptr, nullptr, n, nullptr), RL_E_NO_DEVICE);
   EXPECT(rl_rtc_lighting_device(nullptr, nullptr, nullptr, nullptr, nullptr, n, nullptr, nullptr), RL_E_NO_DEVICE);
+  // ---- the render entry points: valid buffers; an image whose row_first equals its height (the forms without row arguments start at
+  // row 0: an image without rows); every pointer NULL.  A prefilled opt_stats stays as it was.
+  rl_rtc_camera rcam{};
+  rcam.hsize = 8, rcam.vsize = 8;
+  std::vector<double> frame(8 * 8 * 3, -1.0);
+  std::vector<uint8_t> bytes(8 * 8 * 3, 0xAB);
+  rl_stats filled, before;
+  std::memset(&filled, 0xA5, sizeof filled);
+  before = filled;
+  uint64_t claimed = 7, total = 7;
+  uint32_t phase = 7;
+  for (int way = 0; way < 3; way++) {
+    rl_rtiow_camera c1 = cam;
+    rl_rtc_camera c2 = rcam;
+    if (way == 1) c1.image_height = 0, c2.vsize = 0;  // for the forms that always start at row 0
+    const rl_rtiow_camera *pc1 = way == 2 ? nullptr : &c1, *pr1 = way == 2 ? nullptr : &cam;  // pr*: the forms with a row_first of their own
+    const rl_rtc_camera *pc2 = way == 2 ? nullptr : &c2, *pr2 = way == 2 ? nullptr : &rcam;
+    double *f = way == 2 ? nullptr : frame.data();
+    uint8_t *b = way == 2 ? nullptr : bytes.data();
+    rl_stats *s = way == 2 ? nullptr : &filled;
+    const uint32_t row_first = way == 1 ? 8 : 0, row_step = way == 2 ? 0 : 1;
+    EXPECT(rl_rtiow_render(nullptr, pc1, 0, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtiow_render_rows(nullptr, pr1, 0, row_first, row_step, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtiow_render_device(nullptr, pr1, 0, row_first, row_step, f, nullptr, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtiow_render_independent_rows(nullptr, pr1, 0, row_first, row_step, 1, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtiow_render_independent_device(nullptr, pr1, 0, row_first, row_step, 1, f, nullptr, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtiow_render_multi(nullptr, pc1, 0, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtiow_render_multi_device(nullptr, pc1, 0, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtiow_render_rgb8(nullptr, pc1, 0, b, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtc_render(nullptr, pc2, 1, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtc_render_rows(nullptr, pr2, 1, row_first, row_step, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtc_render_device(nullptr, pr2, 1, row_first, row_step, f, nullptr, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtc_render_multi(nullptr, pc2, 1, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtc_render_multi_device(nullptr, pc2, 1, f, s), RL_E_NO_DEVICE);
+    EXPECT(rl_rtc_render_rgb8(nullptr, pc2, 1, b, s), RL_E_NO_DEVICE);
+    EXPECT(rl_render_status(nullptr, s), RL_E_NO_DEVICE);
+    if (way == 2)
+      EXPECT(rl_rtiow_render_progress(nullptr, nullptr, nullptr, nullptr), RL_E_NO_DEVICE);
+    else
+      EXPECT(rl_rtiow_render_progress(nullptr, &claimed, &total, &phase), RL_E_NO_DEVICE);
+  }
+  calls++;
+  if (std::memcmp(&filled, &before, sizeof filled) != 0 || claimed != 7 || total != 7 || phase != 7) {
+    std::printf("FAIL a render entry point wrote opt_stats or a progress output without a device\n");
+    failures++;
+  }
+  for (double v : frame) failures += v != -1.0;
+  for (uint8_t v : bytes) failures += v != 0xAB;
   if (failures)
-    std::printf("%d of %d calls failed\n", failures, calls);
+    std::printf("%d of %d checks failed\n", failures, calls);
   else
-    std::printf("batched queries, no-device paths: ok (%d calls)\n", calls);
+    std::printf("batched queries and renders, no-device paths: ok (%d checks)\n", calls);
   return failures ? 1 : 0;
 }
