@@ -469,8 +469,8 @@ typedef struct rl_rtc_isect { /* scene/intersect.rs:11-16 Intersection{t, object
 
 /* out_hits[i] = world.hit(&rays[i], &Interval{min: tmin, max: tmax}); the interval is closed at both ends (interval.rs).
  * Scenes with ConstantMedium objects: RL_E_UNSUPPORTED — a medium's hit draws its free path from the pixel's RNG stream
- * (constant_medium.rs:55, see rl_medium), and a bare ray has none.  rl_rtiow_ray_color_rays below is the seeded alternative: there
- * every ray carries an RNG cursor, and media scenes are accepted. */
+ * (constant_medium.rs:55, see rl_medium), and a bare ray has none.  rl_rtiow_hit_rays_seeded below is the seeded form of this call:
+ * there every ray carries an RNG cursor, and media scenes are accepted (as in rl_rtiow_ray_color_rays, which traces whole paths). */
 int rl_rtiow_hit_rays(const rl_scene *, const rl_ray *rays, uint64_t n, double tmin, double tmax, rl_rtiow_hit *out_hits, rl_stats *opt_stats);
 int rl_rtiow_hit_rays_device(const rl_scene *, const void *d_rays, uint64_t n, double tmin, double tmax, void *d_out_hits, void *hip_stream,
                              rl_stats *opt_stats);
@@ -541,9 +541,10 @@ int rl_rtiow_ray_color_rays_device(const rl_scene *, const void *d_rays, const v
  * arithmetic is that of the render kernels, so the loop
  *     sum = 0, thr = 1; up to max_depth times: hit = hit_rays(ray, tmin = 1e-10); a miss: sum += thr * background, stop;
  *     s = scatter_rays(ray, hit, cursor); sum = sum + thr * s.emitted; s.scatter == 0: stop; thr = thr * s.attenuation; ray = s.scattered
- * gives rl_rtiow_ray_color_rays' colours, cursors and ray counts bit for bit (scenes without ConstantMedium objects, which
- * rl_rtiow_hit_rays refuses).  Cursors, seed and the word_pos rules are those of the seeded path queries above (odd positions are legal;
- * word_pos >= 2^31 is RL_E_INVALID in the host form).  Status, concurrency, rl_init_multi, n = 0, NULL buffers and the wrong scene family:
+ * gives rl_rtiow_ray_color_rays' colours, cursors and ray counts bit for bit.  A scene with ConstantMedium objects, which
+ * rl_rtiow_hit_rays refuses: use rl_rtiow_hit_rays_seeded there (hit, cursor = hit_rays_seeded(ray, cursor, tmin = 1e-10), the cursor then
+ * passed on to scatter_rays); it serves every RTIOW scene.  Cursors, seed and the word_pos rules are those of the seeded path queries above
+ * (odd positions are legal; word_pos >= 2^31 is RL_E_INVALID in the host form).  Status, concurrency, rl_init_multi, n = 0, NULL buffers and the wrong scene family:
  * as stated for the batched ray queries. */
 typedef struct rl_rtiow_scatter { /* material.rs:11-20: scatter's Option<(Color, Ray)> + emitted's Color */
   double attenuation[3];          /* zeros unless scatter == 1 */
@@ -576,6 +577,34 @@ int rl_rtiow_scatter_rays_device(const rl_scene *, const void *d_rays, const voi
 int rl_rtiow_texture_values(const rl_scene *, const uint32_t *textures, const double *uv, const double *p, uint64_t n, double *out_rgb);
 int rl_rtiow_texture_values_device(const rl_scene *, const void *d_textures, const void *d_uv, const void *d_p, uint64_t n, void *d_out_rgb,
                                    void *hip_stream);
+
+/* =====================================================================
+ *  Seeded hit queries: Hittable::hit for rays that carry an RNG cursor
+ * =====================================================================
+ *   rl_rtiow_hit_rays_seeded*  <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval) on the scene root, with
+ *                                 ray-tracing-one-weekend/src/hittable/constant_medium.rs:27-80  ConstantMedium::hit (the deterministic
+ *                                 variant of rl_medium: the free path is drawn from the pixel's ChaCha8 stream)
+ * rl_rtiow_hit_rays for every RTIOW scene, ConstantMedium objects included: the one primitive of the host loop above that needs
+ * randomness only in some scenes.  out_hits[i] = world.hit(&rays[i], &Interval{min: tmin, max: tmax}) with rng_i = cursors[i] of `seed`.
+ * Every ConstantMedium::hit the reference's fold reaches with rec1.t < rec2.t after clamping (constant_medium.rs:42-47) takes one
+ * gen::<f64>() (two words) from rng_i, in the fold's evaluation order: an object listed before the medium does not keep the medium from
+ * drawing, a closer hit found BEFORE the medium that cuts its chord to nothing does.  opt_out_cursors[i] = rng_i afterwards (may alias
+ * cursors).  A ray whose fold reaches no such medium leaves its cursor unchanged.
+ * A medium's hit record is the reference's own: t, p = r.at(t), material = the medium's phase-function material, and the reference's
+ * arbitrary fields as they are: normal (1, 0, 0), u = v = 0, front_face = 1.  The interval is the caller's and closed at both ends, as
+ * rl_rtiow_hit_rays treats it; inside a medium it clamps the chord (rec1.t.max(tmin), rec2.t.min(tmax)).  Rays are used as given: `dir`
+ * is not normalised, and its length scales the medium's free path (ray_length, constant_medium.rs:49).
+ * Scenes without media are accepted: the records are bit for bit those of rl_rtiow_hit_rays (the same kernels and the same fast /
+ * reference-order selection), the cursors come back unchanged (opt_out_cursors, when given and not the input, receives a copy) and
+ * rng_words is 0.  Scenes with media: with opt_stats every counter is the reference's (the nested boundary traces included, as in the
+ * renders) and rng_words = the words consumed; without it the call is counter-free and records, cursors and flagged are the same bits.
+ * Cursor rules as the seeded path queries state them: odd positions are legal; word_pos >= 2^31 is RL_E_INVALID in the host form and
+ * undefined in the device form.  NaN interval bounds, NULL buffers with n > 0, n = 0, a scene of the other family, status, concurrency
+ * and rl_init_multi: as stated for the batched ray queries. */
+int rl_rtiow_hit_rays_seeded(const rl_scene *, const rl_ray *rays, const rl_rng_cursor *cursors, uint64_t n, uint64_t seed, double tmin,
+                             double tmax, rl_rtiow_hit *out_hits, rl_rng_cursor *opt_out_cursors, rl_stats *opt_stats);
+int rl_rtiow_hit_rays_seeded_device(const rl_scene *, const void *d_rays, const void *d_cursors, uint64_t n, uint64_t seed, double tmin,
+                                    double tmax, void *d_out_hits, void *d_opt_out_cursors, void *hip_stream, rl_stats *opt_stats);
 
 /* =====================================================================
  *  RTC shading queries: prepare_computations, shade_hit, shadow_attenuation and lighting for buffers

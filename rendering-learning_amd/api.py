@@ -207,6 +207,7 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtc_color_at_rays", "rl_rtc_color_at_rays_device",
                   "rl_rtiow_camera_rays", "rl_rtiow_camera_rays_device", "rl_rtiow_ray_color_rays", "rl_rtiow_ray_color_rays_device",
                   "rl_rtiow_scatter_rays", "rl_rtiow_scatter_rays_device", "rl_rtiow_texture_values", "rl_rtiow_texture_values_device",
+                  "rl_rtiow_hit_rays_seeded", "rl_rtiow_hit_rays_seeded_device",
                   "rl_rtc_prepare_rays", "rl_rtc_prepare_rays_device", "rl_rtc_shade_hits", "rl_rtc_shade_hits_device",
                   "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device"]
 
@@ -217,6 +218,13 @@ def _material_query_argtypes(L):
                                                C.POINTER(Stats)]
     L.rl_rtiow_texture_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.rl_rtiow_texture_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+
+
+def _seeded_hit_query_argtypes(L):
+    L.rl_rtiow_hit_rays_seeded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                           C.POINTER(Stats)]
+    L.rl_rtiow_hit_rays_seeded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.POINTER(Stats)]
 
 
 def _rtc_shade_query_argtypes(L):
@@ -278,6 +286,8 @@ def render_lib():
             _material_query_argtypes(L)
         if hasattr(L, "rl_rtc_prepare_rays"):  # (likewise)
             _rtc_shade_query_argtypes(L)
+        if hasattr(L, "rl_rtiow_hit_rays_seeded"):  # (likewise)
+            _seeded_hit_query_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -720,6 +730,31 @@ class World:
         st = Stats()
         rc = render_lib().rl_rtiow_hit_rays_device(self.device(), C.c_void_p(d_rays), n, tmin, tmax, C.c_void_p(d_out), C.c_void_p(stream),
                                                    C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+
+    def hit_rays_seeded(self, rays, cursors, seed, tmin=1e-10, tmax=float("inf"), stats=None, allow_degenerate=False):
+        """Hittable::hit(&Ray, &Interval{tmin, tmax}) for every ray of RAY[n], ray i drawing from cursors[i] of `seed` where the reference's fold
+        evaluates a ConstantMedium (constant_medium.rs:55) -> (RTIOW_HIT[n], cursors behind the draws [n]).  Serves every RTIOW scene: one
+        without media gives hit_rays' records and the cursors back unchanged.  With scatter_rays a host writes its own ray_color loop
+        through smoke and gets ray_color_rays' bits."""
+        rays = _records_arg(rays, RAY, None, "rays")
+        n = rays.shape[0]
+        out_cur = _cursors_arg(cursors, n).copy()
+        out = np.zeros(n, dtype=RTIOW_HIT)
+        st = Stats()
+        rc = render_lib().rl_rtiow_hit_rays_seeded(self.device(), rays.ctypes.data, out_cur.ctypes.data, n, int(seed), tmin, tmax, out.ctypes.data,
+                                                   out_cur.ctypes.data, C.byref(st) if stats is not None else None)
+        _finish_query(rc, st, stats, allow_degenerate)
+        return out, out_cur
+
+    def hit_rays_seeded_device(self, d_rays, d_cursors, n, seed, d_out, d_out_cursors=0, tmin=1e-10, tmax=float("inf"), stream=0, stats=None,
+                               allow_degenerate=False):
+        """Device buffers (n rl_ray and n rl_rng_cursor in; n rl_rtiow_hit and optionally n rl_rng_cursor out, which may be d_cursors).
+        Asynchronous unless stats is a dict."""
+        st = Stats()
+        rc = render_lib().rl_rtiow_hit_rays_seeded_device(self.device(), C.c_void_p(d_rays), C.c_void_p(d_cursors), n, int(seed), tmin, tmax,
+                                                          C.c_void_p(d_out), C.c_void_p(d_out_cursors or None), C.c_void_p(stream),
+                                                          C.byref(st) if stats is not None else None)
         _finish_query(rc, st, stats, allow_degenerate)
 
     def ray_color_rays(self, origins, dirs, times, cursors, seed, max_depth, background, stats=None, allow_degenerate=False, rays=None):

@@ -1,5 +1,5 @@
-// The host side of the batched queries (include/rl_render.h rl_*_rays*, rl_rtiow_texture_values*, rl_rtc_lighting*; DESIGN.md §3.8 - §3.11;
-// kernels: rl_ray_query.h, rl_material_query.h, rl_rtc_shade_query.h and the *_rays_kernel forms of the render kernels): 11 queries, each in a
+// The host side of the batched queries (include/rl_render.h rl_*_rays*, rl_rtiow_texture_values*, rl_rtc_lighting*; DESIGN.md §3.8 - §3.12;
+// kernels: rl_ray_query.h, rl_material_query.h, rl_rtc_shade_query.h and the *_rays_kernel forms of the render kernels): 12 queries, each in a
 // host-buffer and a _device form.  Not a translation unit of its own: rl_render.hip includes it once, at its end, and it uses that file's
 // statics (g_sw, g_cus, g_lds_max, ensure_lds_attr, fill_rtiow_params, stage_params, chacha_key_from_seed).
 //
@@ -111,25 +111,34 @@ int query_run(const rl_scene *scene, hipStream_t stream, rl_stats *sync_st, Laun
 
 }  // namespace
 
+// what the reference-order fold (general_trace) reads of an RTIOW scene: rl_rtiow_hit_rays* and rl_rtiow_hit_rays_seeded*
+static RtiowParams hit_query_params(const rl_scene *scene) {
+  const RtiowProgram &rt = scene->rt();
+  RtiowParams P = RtiowParams{};
+  P.ops = scene->d_ops, P.spheres = scene->d_spheres, P.sphere_material = scene->d_sphere_material;
+  P.planars = scene->d_planars, P.translates = scene->d_translates, P.transforms = scene->d_transforms, P.media = scene->d_media;
+  P.n_ops = (uint32_t)rt.ops.size(), P.n_spheres = (uint32_t)rt.spheres.size();
+  P.stats = (unsigned long long *)(scene->d_scratch + 64);
+  return P;
+}
+
 extern "C" {
 
 // ---- batched ray queries (include/rl_render.h): Hittable::hit, World::intersect and World::color_at for ray buffers
 // counting: the caller wants the reference's counters (reference-order kernel).  Otherwise the fast kernel serves the call where the
 // scene has a fast tree and tmin is the interval its filters are derived for (camera.rs:242-245).  sync_st: filled synchronously (the
 // host forms; rays and flagged only when !counting); null: asynchronous, status ring.
+// pass_from / pass_to (rl_rtiow_hit_rays_seeded* on a scene without media): n rl_rng_cursor copied device to device ahead of the kernel, as
+// one of this query's enqueues (under the scene's lock, behind the scene's previous work, reported with the query).
 static int rtiow_hit_rays_impl(const rl_scene *scene, const void *d_rays, uint64_t n, double tmin, double tmax, void *d_out, hipStream_t stream,
-                               bool counting, rl_stats *sync_st) {
-  const RtiowProgram &rt = scene->rt();
+                               bool counting, rl_stats *sync_st, const void *pass_from = nullptr, void *pass_to = nullptr) {
   const FastGeneral &QF = scene->hrt->query_tree();
-  RtiowParams P = RtiowParams{};
-  P.ops = scene->d_ops, P.spheres = scene->d_spheres, P.sphere_material = scene->d_sphere_material;
-  P.planars = scene->d_planars, P.translates = scene->d_translates, P.transforms = scene->d_transforms, P.media = scene->d_media;
-  P.n_ops = (uint32_t)rt.ops.size(), P.n_spheres = (uint32_t)rt.spheres.size();
-  P.stats = (unsigned long long *)(scene->d_scratch + 64);
+  RtiowParams P = hit_query_params(scene);
   RayQuery Q{};
   Q.rays = (const rl_ray *)d_rays, Q.n = n, Q.tmin = tmin, Q.tmax = tmax, Q.hits = (rl_rtiow_hit *)d_out;
   const bool fast = !counting && tmin == 1e-10 && QF.ok && QF.media.empty() && g_sw.fast_traversal;
   auto launch = [&]() -> int {
+    if (pass_to) HIP_TRY(hipMemcpyAsync(pass_to, pass_from, (size_t)n * sizeof(rl_rng_cursor), hipMemcpyDeviceToDevice, stream));
     if (fast) {
       constexpr int SD = 40;
       P.fg_nodes = scene->d_fg_nodes, P.fg_items = scene->d_fg_items, P.fg_spheres = scene->d_fg_spheres, P.fg_material = scene->d_fg_material;
@@ -418,6 +427,61 @@ int rl_rtiow_camera_rays(const rl_rtiow_camera *cam, uint64_t n, const uint32_t 
   if ((rc = camera_rays_launch(cam, n, d_xy, d_xy + n * 4, d_cursors, d_rays, d_cursors, q.stream)) != RL_OK) return rc;
   HIP_TRY(hipStreamSynchronize(q.stream));
   return q.finish(RL_OK);
+}
+
+// ---- seeded hit queries (include/rl_render.h): Hittable::hit for rays that carry an RNG cursor, media scenes included
+// A scene without media draws nothing: the bare-ray kernels serve it (rtiow_hit_rays_impl: fast / reference-order selection,
+// rl_debug_last_query) and the cursors pass through.  A scene with media: the reference-order fold with MEDIA = true, counting or not.
+// sync_st as in rtiow_hit_rays_impl.
+static int rtiow_hit_rays_seeded_impl(const rl_scene *scene, const void *d_rays, const void *d_cursors, uint64_t n, uint64_t seed, double tmin, double tmax,
+                                      void *d_out, void *d_out_cursors, hipStream_t stream, bool counting, rl_stats *sync_st) {
+  if (!scene->rt().has_media)
+    return rtiow_hit_rays_impl(scene, d_rays, n, tmin, tmax, d_out, stream, counting, sync_st, d_cursors, d_out_cursors != d_cursors ? d_out_cursors : nullptr);
+  RtiowParams P = hit_query_params(scene);
+  chacha_key_from_seed(seed, P.key);
+  SeededHitQuery Q{};
+  Q.rays = (const rl_ray *)d_rays, Q.cursors = (const rl_rng_cursor *)d_cursors, Q.n = n, Q.tmin = tmin, Q.tmax = tmax;
+  Q.hits = (rl_rtiow_hit *)d_out, Q.out_cursors = (rl_rng_cursor *)d_out_cursors;
+  auto launch = [&]() -> int {
+    if (counting)
+      hipLaunchKernelGGL((rtiow_hit_rays_seeded_kernel<QNT, true>), dim3(query_grid(scene, (const void *)rtiow_hit_rays_seeded_kernel<QNT, true>, n)), dim3(QNT), 0,
+                         stream, P, Q);
+    else
+      hipLaunchKernelGGL((rtiow_hit_rays_seeded_kernel<QNT, false>), dim3(query_grid(scene, (const void *)rtiow_hit_rays_seeded_kernel<QNT, false>, n)), dim3(QNT), 0,
+                         stream, P, Q);
+    g_last_query_kernel = 1, g_last_query_retraced = 0;  // (no fast walk, nothing re-traced: nothing to read back after the call)
+    return RL_OK;
+  };
+  return query_run(scene, stream, sync_st, launch);
+}
+
+// what rl_rtiow_hit_rays_seeded* adds to query_check; cursors: the host form's (null: the device form, where word_pos >= 2^31 is undefined)
+static int rtiow_hit_rays_seeded_rules(double tmin, double tmax, const rl_rng_cursor *cursors, uint64_t n) {
+  if (std::isnan(tmin) || std::isnan(tmax)) return set_err(RL_E_INVALID, "NaN interval bound");
+  return cursors ? cursors_check(cursors, n) : RL_OK;
+}
+
+int rl_rtiow_hit_rays_seeded_device(const rl_scene *scene, const void *d_rays, const void *d_cursors, uint64_t n, uint64_t seed, double tmin, double tmax,
+                                    void *d_out_hits, void *d_opt_out_cursors, void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = query_check(scene, 1, n, d_rays && d_cursors && d_out_hits, st, done);
+  if (done) return rc;
+  if ((rc = rtiow_hit_rays_seeded_rules(tmin, tmax, nullptr, n)) != RL_OK) return rc;
+  return rtiow_hit_rays_seeded_impl(scene, d_rays, d_cursors, n, seed, tmin, tmax, d_out_hits, d_opt_out_cursors, (hipStream_t)hip_stream, st != nullptr, st);
+}
+
+int rl_rtiow_hit_rays_seeded(const rl_scene *scene, const rl_ray *rays, const rl_rng_cursor *cursors, uint64_t n, uint64_t seed, double tmin, double tmax,
+                             rl_rtiow_hit *out_hits, rl_rng_cursor *opt_out_cursors, rl_stats *st) {
+  bool done;
+  int rc = query_check(scene, 1, n, rays && cursors && out_hits, st, done);
+  if (done) return rc;
+  if ((rc = rtiow_hit_rays_seeded_rules(tmin, tmax, cursors, n)) != RL_OK) return rc;
+  HostStaging q(scene);
+  void *d_rays = q.in(rays, n * sizeof(rl_ray)), *d_cursors = q.in(cursors, n * sizeof(rl_rng_cursor)), *d_out = q.out(out_hits, n * sizeof(rl_rtiow_hit));
+  void *d_out_cursors = q.back(opt_out_cursors, d_cursors, n * sizeof(rl_rng_cursor));  // the staged copy: the caller's cursors are never written
+  if (q.rc != RL_OK) return q.rc;
+  rl_stats local;  // without opt_stats the call is counter-free; rays, words and flagged are still collected
+  return q.finish(rtiow_hit_rays_seeded_impl(scene, d_rays, d_cursors, n, seed, tmin, tmax, d_out, d_out_cursors, q.stream, st != nullptr, &local), st, local);
 }
 
 // ---- material queries (include/rl_render.h): Material::scatter / emitted and Texture::value for buffers

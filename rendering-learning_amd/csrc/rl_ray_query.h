@@ -2,6 +2,7 @@
 //
 //   rtiow_hit_rays_kernel      Hittable::hit(&Ray, &Interval) on the scene root (hittable/mod.rs:42, the fold of :88-111, bvh.rs:79-95):
 //                              general_trace, the reference-order fold the counting renders use, with the caller's interval.
+//   rtiow_hit_rays_seeded_kernel  the same fold with ConstantMedium objects evaluated: every ray carries an rl_rng_cursor to draw from
 //   rtiow_hit_rays_fast_kernel counter-free queries with tmin == 1e-10 on scenes that have a fast tree: the four-wide SAH walk of
 //                              rl_rtiow_fastgen.h as a flat per-lane loop; order-sensitive rays are re-traced by general_trace.
 //   rtc_intersect_rays_kernel  World::intersect (world.rs:46-55) + hit (intersect.rs:159-168): rtc_intersect_all.
@@ -67,6 +68,71 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_kernel(Rtio
   unsigned long long v;
   v = wave_sum(c_rays);
   if ((tid & 63) == 0 && v) atomicAdd(&P.stats[0], v);
+  v = wave_sum(c_flag);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
+  if (STATS) {
+    v = wave_sum(c_nodes);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[1], v);
+    v = wave_sum(c_sph);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
+    v = wave_sum(c_pl);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[3], v);
+    v = wave_sum(c_inst);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[4], v);
+  }
+}
+
+// Hittable::hit for rays that carry an RNG cursor (rl_rtiow_hit_rays_seeded*, scenes with ConstantMedium objects): the fold of
+// rtiow_hit_rays_kernel with MEDIA = true, the free path of every medium the fold evaluates drawn from the ray's own cursor.  The lane's
+// ChaCha8 blocks live in a Ring column (ODD: a cursor may stand at any word) and are generated at the ray's FIRST draw: a ray whose fold
+// reaches no medium with rec1.t < rec2.t costs no block and returns its cursor as it came.  draw() runs in divergent control flow (only
+// some lanes are inside a boundary); the ring's refill is per lane — its own LDS column, no cross-lane step — so that is safe.
+// stats[5] += the words consumed (position difference), counting or not.
+struct SeededHitQuery {
+  const rl_ray *rays;
+  const rl_rng_cursor *cursors;
+  unsigned long long n;
+  double tmin, tmax;
+  rl_rtiow_hit *hits;
+  rl_rng_cursor *out_cursors;  // null: not wanted (may be `cursors`: a lane reads its element's cursor before it writes it)
+};
+template <int NT, bool STATS>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_seeded_kernel(RtiowParams P, SeededHitQuery Q) {
+  __shared__ unsigned long long s_rng[16 * NT];
+  const int tid = threadIdx.x;
+  const DevOp *ops = P.ops;
+  Ring<NT, true, true> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
+  unsigned long long c_rays = 0, c_nodes = 0, c_sph = 0, c_pl = 0, c_inst = 0, c_flag = 0, c_words = 0;
+  for (unsigned long long idx = (unsigned long long)blockIdx.x * NT + tid; idx < Q.n; idx += (unsigned long long)gridDim.x * NT) {
+    const uint64_t *cur = (const uint64_t *)(Q.cursors + idx);
+    const uint64_t stream = cur[0], word_pos = cur[1];
+    const rl_ray &ray = Q.rays[idx];
+    const D3 o = ld3(ray.origin), d = ld3(ray.dir);
+    const double time = ray.time;
+    c_rays++;
+    rng.stream = stream, rng.pos = (uint32_t)word_pos, rng.nres = 0;
+    Rec rec;
+    rec.t = Q.tmax, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
+    rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+    GenCounters gc{0, 0, 0, 0, 0};
+    auto draw = [&]() {
+      if (rng.nres == 0u) rng.reset_stream(stream);  // the ray's first draw: blocks pos / 16 and the next one
+      return rng.gen_f64();
+    };
+    general_trace<STATS, true, true>(P, ops, 0u, NONE, o, d, o, d, time, Q.tmin, rec, gc, draw);
+    c_nodes += gc.nodes, c_sph += gc.spheres, c_pl += gc.planars, c_inst += gc.instances, c_flag += gc.flagged;
+    c_words += rng.pos - (uint32_t)word_pos;
+    hit_record_store(&Q.hits[idx], rec);
+    if (Q.out_cursors) {
+      uint64_t *oc = (uint64_t *)(Q.out_cursors + idx);
+      oc[0] = stream, oc[1] = (uint64_t)rng.pos;
+    }
+  }
+  unsigned long long v;
+  v = wave_sum(c_rays);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[0], v);
+  v = wave_sum(c_words);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[5], v);
   v = wave_sum(c_flag);
   if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
   if (STATS) {

@@ -73,7 +73,10 @@ struct Ring {
     nres = 2;
   }
   __device__ __forceinline__ bool low() const {  // reading from the newest block
-    if (ODD) return ((pos + (pos & 1u)) >> 4) >= blk_lo + nres - 1u;  // (the draw's second word counts)
+    // ODD too goes by the draw's FIRST word: top_up drops the oldest block, and at pos = 16 b + 15 with blocks b, b + 1 resident that is
+    // the block of the draw's first word (going by the second word, b + 1, dropped it, and the draw then took its low half from the
+    // stale slot: seen only where a colour depends continuously on the path, e.g. a Noise texture after a medium's 2-word draw).  The
+    // second word's block, when it is not resident yet, is generated by next_u64_any itself, which never drops the first word's.
     return (pos >> 4) >= blk_lo + nres - 1u;
   }
   __device__ __forceinline__ void top_up() {  // make block (newest+1) resident, dropping the oldest

@@ -535,6 +535,19 @@ int rlh_material_query_probe(int which, const void *rays, const void *hits, void
     return -1;
   }
 }
+// Seeded hit queries through the C++ mirror: rtiow::hit_rays_seeded on cornell_smoke (examples/cornell_smoke.rs) with the scene's seed
+// and Interval{tmin, tmax}, out = n rl_rtiow_hit, cursors advanced in place.  0 or -1 (rlh_last_error).
+int rlh_seeded_hit_query_probe(const rl_ray *rays, rl_rng_cursor *cursors, uint64_t n, double tmin, double tmax, void *out) {
+  try {
+    scenes::RtiowScene s = scenes::cornell_scene(true);
+    std::vector<rl_rtiow_hit> h = rtiow::hit_rays_seeded(*s.world, rays, cursors, (size_t)n, s.params.seed, rtiow::Interval{tmin, tmax});
+    std::memcpy(out, h.data(), h.size() * sizeof(rl_rtiow_hit));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
 // which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
 // b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,

@@ -55,6 +55,19 @@ std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t 
   if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_hit_rays: ") + rl_last_error());
   return out;
 }
+std::vector<rl_rtiow_hit> hit_rays_seeded(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed,
+                                          Interval ray_t) {  // hittable/mod.rs:42 with constant_medium.rs:27-80
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  std::vector<rl_rtiow_hit> out(n);
+  int rc = rl_rtiow_hit_rays_seeded(sc, rays, cursors, n, seed, ray_t.min, ray_t.max, out.data(), cursors, nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_hit_rays_seeded: ") + rl_last_error());
+  return out;
+}
 std::vector<double> ray_color_rays(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed, size_t max_depth,
                                    const Color &background, std::vector<uint32_t> *ray_counts) {  // camera.rs:232-260
   Flattened f;

@@ -675,6 +675,11 @@ struct DeviceBvh : Hittable {
 // world.hit(&rays[i], &ray_t), out[i].hit == 0 for None.  Throws on any error but RL_E_DEGENERATE (host_render.cpp).
 std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t n, Interval ray_t);
 
+// The same for rays that carry an RNG cursor (rl_rtiow_hit_rays_seeded): worlds with ConstantMedium objects are served, the free path of
+// every medium the fold evaluates drawn from cursors[i] of `seed` (constant_medium.rs:55); cursors[i] is advanced behind the draws, and
+// stays as it is where none was taken.  Throws on any error but RL_E_DEGENERATE.
+std::vector<rl_rtiow_hit> hit_rays_seeded(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed, Interval ray_t);
+
 // Camera::ray_color(&mut rng, &ray, world, depth) (camera.rs:232-260) for a batch of rays, on the GPU (rl_rtiow_ray_color_rays): rng_i is
 // ChaCha8Rng::seed_from_u64(seed) after set_stream(cursors[i].stream) at word cursors[i].word_pos; cursors[i] is advanced behind the path.
 // Returns n * 3 colour values; ray_counts (optional) receives the rays traced per path.  Throws on any error but RL_E_DEGENERATE.

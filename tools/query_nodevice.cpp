@@ -1,4 +1,4 @@
-// Stand-alone host check of the batched queries' 22 entry points and the 14 render entry points with rl_render_status and
+// Stand-alone host check of the batched queries' 24 entry points and the 14 render entry points with rl_render_status and
 // rl_rtiow_render_progress (include/rl_render.h; csrc/rl_query_api.h, csrc/rl_host_api.h) on a machine without a GPU: every form must
 // return RL_E_NO_DEVICE before it touches a buffer or opt_stats — with valid buffers, with nothing to do (n = 0; an image whose row_first
 // equals its height) and with every pointer NULL.  Meant to be built with the host sanitizers (the library's host code and this file; no
@@ -63,6 +63,10 @@ int main() {
       EXPECT(rl_rtiow_scatter_rays(nullptr, rays.data(), hits.data(), cur.data(), m, 1, scat.data(), cur2.data(), s), RL_E_NO_DEVICE);
       EXPECT(rl_rtiow_scatter_rays(nullptr, rays.data(), hits.data(), cur.data(), m, 1, scat.data(), nullptr, s), RL_E_NO_DEVICE);
       EXPECT(rl_rtiow_scatter_rays_device(nullptr, rays.data(), hits.data(), cur.data(), m, 1, scat.data(), cur2.data(), nullptr, s), RL_E_NO_DEVICE);
+      // seeded hit queries
+      EXPECT(rl_rtiow_hit_rays_seeded(nullptr, rays.data(), cur.data(), m, 1, 1e-10, inf, hits.data(), cur2.data(), s), RL_E_NO_DEVICE);
+      EXPECT(rl_rtiow_hit_rays_seeded(nullptr, rays.data(), cur.data(), m, 1, 1e-10, inf, hits.data(), nullptr, s), RL_E_NO_DEVICE);
+      EXPECT(rl_rtiow_hit_rays_seeded_device(nullptr, rays.data(), cur.data(), m, 1, 1e-10, inf, hits.data(), cur2.data(), nullptr, s), RL_E_NO_DEVICE);
       // RTC shading queries
       EXPECT(rl_rtc_prepare_rays(nullptr, rays.data(), m, comps.data(), s), RL_E_NO_DEVICE);
       EXPECT(rl_rtc_prepare_rays_device(nullptr, rays.data(), m, comps.data(), nullptr, s), RL_E_NO_DEVICE);
@@ -94,6 +98,8 @@ int main() {
   EXPECT(rl_rtiow_camera_rays_device(nullptr, n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr), RL_E_NO_DEVICE);
   EXPECT(rl_rtiow_scatter_rays(nullptr, nullptr, nullptr, nullptr, n, 1, nullptr, nullptr, nullptr), RL_E_NO_DEVICE);
   EXPECT(rl_rtiow_scatter_rays_device(nullptr, nullptr, nullptr, nullptr, n, 1, nullptr, nullptr, nullptr, nullptr), RL_E_NO_DEVICE);
+  EXPECT(rl_rtiow_hit_rays_seeded(nullptr, nullptr, nullptr, n, 1, 1e-10, inf, nullptr, nullptr, nullptr), RL_E_NO_DEVICE);
+  EXPECT(rl_rtiow_hit_rays_seeded_device(nullptr, nullptr, nullptr, n, 1, 1e-10, inf, nullptr, nullptr, nullptr, nullptr), RL_E_NO_DEVICE);
   EXPECT(rl_rtiow_texture_values(nullptr, nullptr, nullptr, nullptr, n, nullptr), RL_E_NO_DEVICE);
   EXPECT(rl_rtiow_texture_values_device(nullptr, nullptr, nullptr, nullptr, n, nullptr, nullptr), RL_E_NO_DEVICE);
   EXPECT(rl_rtc_prepare_rays(nullptr, nullptr, n, nullptr, nullptr), RL_E_NO_DEVICE);
