@@ -434,6 +434,38 @@ int rl_rtc_encode_rgb8_device(const void *d_rgb, uint64_t n_pixels, void *d_rgb8
 int rl_rtc_render_rgb8(const rl_scene *, const rl_rtc_camera *, uint32_t aa_samples, uint8_t *out_rgb8, rl_stats *opt_stats);
 
 /* =====================================================================
+ *  Pixel-list renders: the pixels of the caller's choosing, not a frame or a set of rows
+ * =====================================================================
+ *   rl_rtiow_render_pixels*  <- ray-tracing-one-weekend/src/camera.rs:145-199  Camera::_render's per-pixel loop, for the listed pixels only
+ *   rl_rtc_render_pixels*    <- ray-tracer-challenge/src/scene/camera.rs:93-124 Camera::render's per-pixel body (rays_for_pixel, color_at, the AA mean)
+ * (xs[i], ys[i]), i < n, are pixels of the camera's WHOLE frame (x < W, y < H).  The list may be unsorted and may hold duplicates: every
+ * element is rendered on its own, duplicates get identical bits.  Output is compact: element i is written at out[3*i ..], never at
+ * (y*W + x)*3.
+ * Values.  out[i] is bit for bit what rl_rtiow_render_rows(.., first_sample, 0, 1, ..) / rl_rtc_render(.., aa_samples, ..) writes for
+ * that pixel, whatever else is in the list: for RTIOW the sum over cam->samples_per_pixel CHAINED samples accumulated from 0.0, sample s
+ * on stream (first_sample + s)*W*H + x*W + y with the ChaCha word position carried from sample to sample (camera.rs:161-174); for RTC the
+ * mean over the aa_samples x aa_samples grid.  Scenes with ConstantMedium objects are accepted, as in the renders.
+ * Stats.  With opt_stats all seven counters are the reference's for exactly the listed pixels (a duplicate counts twice), from the
+ * reference-order kernels; without it the call is counter-free, may take the fast traversals and gives the same bits.
+ * Forms.  The plain forms take host buffers; the _device forms take device buffers (d_xs, d_ys: n uint32 each; d_out: n*3 f64) and a
+ * hipStream_t and are asynchronous unless opt_stats is non-NULL; rl_render_status covers them, each call counting once.
+ * Errors.  A pixel outside the image: RL_E_INVALID from the plain forms, before anything is launched and with `out` untouched; in the
+ * _device forms (which cannot look at the list) such an element is written as zeros and traces nothing.  n = 0: RL_OK, no buffer is
+ * touched (opt_stats, when given, is zeroed).  NULL buffers with n > 0, aa_samples = 0, an empty image, a scene of the other family:
+ * RL_E_INVALID; n >= 0xFFFF0000 (the 32-bit work counter): RL_E_INVALID "image too large".  A reached panic site sets flagged and
+ * returns RL_E_DEGENERATE with every output written.  Concurrency: as the renders (serialised per scene).  Under rl_init_multi the call
+ * runs on device 0's replica (a list is not split across GPUs).
+ * Progress.  rl_rtiow_render_progress follows an RTIOW pixel-list render: pixels_claimed of pixels_total = n list elements, phase 0. */
+int rl_rtiow_render_pixels(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys,
+                           uint64_t n, double *out_rgb_sum /* [n][3] */, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs, const void *d_ys,
+                                  uint64_t n, void *d_out_rgb_sum, void *hip_stream, rl_stats *opt_stats);
+int rl_rtc_render_pixels(const rl_scene *, const rl_rtc_camera *, uint32_t aa_samples, const uint32_t *xs, const uint32_t *ys,
+                         uint64_t n, double *out_rgb /* [n][3] */, rl_stats *opt_stats);
+int rl_rtc_render_pixels_device(const rl_scene *, const rl_rtc_camera *, uint32_t aa_samples, const void *d_xs, const void *d_ys,
+                                uint64_t n, void *d_out_rgb, void *hip_stream, rl_stats *opt_stats);
+
+/* =====================================================================
  *  Batched ray queries: the reference's per-ray primitives on the device
  * =====================================================================
  *   rl_rtiow_hit_rays*      <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval) -> Option<(&Material, HitRecord)>

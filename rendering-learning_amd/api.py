@@ -209,7 +209,8 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtiow_scatter_rays", "rl_rtiow_scatter_rays_device", "rl_rtiow_texture_values", "rl_rtiow_texture_values_device",
                   "rl_rtiow_hit_rays_seeded", "rl_rtiow_hit_rays_seeded_device",
                   "rl_rtc_prepare_rays", "rl_rtc_prepare_rays_device", "rl_rtc_shade_hits", "rl_rtc_shade_hits_device",
-                  "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device"]
+                  "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device",
+                  "rl_rtiow_render_pixels", "rl_rtiow_render_pixels_device", "rl_rtc_render_pixels", "rl_rtc_render_pixels_device"]
 
 
 def _material_query_argtypes(L):
@@ -236,6 +237,31 @@ def _rtc_shade_query_argtypes(L):
     L.rl_rtc_shadow_attenuation_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.rl_rtc_lighting.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
     L.rl_rtc_lighting_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+
+
+def _render_pixels_argtypes(L):
+    L.rl_rtiow_render_pixels.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtiow_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                C.POINTER(Stats)]
+    L.rl_rtc_render_pixels.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtc_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                              C.POINTER(Stats)]
+
+
+def _pixel_list(xs, ys):
+    """The (xs, ys) of a pixel-list render as two contiguous uint32 arrays; ValueError for what is not a list of pixel coordinates."""
+    xs, ys = np.asarray(xs), np.asarray(ys)
+    for name, a in (("xs", xs), ("ys", ys)):
+        if a.ndim != 1:
+            raise ValueError(f"{name} must be one-dimensional, got shape {a.shape}")
+        if a.size and not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"{name} must hold integers, got dtype {a.dtype}")
+    if xs.shape != ys.shape:
+        raise ValueError(f"xs and ys differ in length: {xs.size} and {ys.size}")
+    for name, a in (("xs", xs), ("ys", ys)):
+        if a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise ValueError(f"{name} holds a value that is not a pixel coordinate (negative, or beyond 32 bits)")
+    return np.ascontiguousarray(xs, dtype=np.uint32), np.ascontiguousarray(ys, dtype=np.uint32)
 
 
 def render_lib():
@@ -288,6 +314,8 @@ def render_lib():
             _rtc_shade_query_argtypes(L)
         if hasattr(L, "rl_rtiow_hit_rays_seeded"):  # (likewise)
             _seeded_hit_query_argtypes(L)
+        if hasattr(L, "rl_rtiow_render_pixels"):  # (likewise)
+            _render_pixels_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -353,6 +381,13 @@ def set_fast_traversal(on):
 def set_coop(on):
     """Tests / tools: counter-free renders of SMALL frames of sphere scenes use the cooperative one-wave-per-pixel kernel unless switched off."""
     render_lib().rl_debug_set_coop(int(bool(on)))
+
+
+def set_coop_pixels_max(n):
+    """Tests / tools: the longest pixel list (render_pixels) of a sphere scene the cooperative kernel takes; 0 = the default, 160 per CU."""
+    L = render_lib()
+    L.rl_debug_set_coop_pixels_max.argtypes = [C.c_uint64]
+    L.rl_debug_set_coop_pixels_max(int(n))
 
 
 def set_steal(max_fill):
@@ -1136,6 +1171,33 @@ class Camera:
         if stats is not None:
             stats.update(st.as_dict())
 
+    # ---- pixel-list renders (include/rl_render.h rl_rtiow_render_pixels*): the pixels of the caller's choosing, each bit for bit the
+    # frame's pixel; compact output
+    def render_pixels(self, world: World, xs, ys, first_sample=0, stats=None, allow_degenerate=False) -> np.ndarray:
+        """[n, 3] sums of pixels (xs[i], ys[i]): what render_rows(world, 0, 1, first_sample) holds at [ys[i], xs[i]].  The list may be
+        unsorted and hold duplicates.  stats (a dict): a counting call, the reference's counters for exactly the listed pixels; without
+        it the call is counter-free.  A pixel outside the image: RLError(RL_E_INVALID)."""
+        xs, ys = _pixel_list(xs, ys)
+        out = np.empty((xs.size, 3), dtype=np.float64)
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_pixels(world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, out.ctypes.data,
+                                                 C.byref(st) if st is not None else None)
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+        return out
+
+    def render_pixels_device(self, world: World, d_xs, d_ys, n, d_out, stream=0, first_sample=0, stats=None):
+        """d_xs / d_ys: device pointers of n uint32; d_out: of n*3 f64.  Async unless stats is a dict; an element outside the image is
+        written as zeros."""
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_pixels_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
+                                                        C.c_void_p(d_out), C.c_void_p(stream), C.byref(st) if st is not None else None)
+        _check(rc)
+        if stats is not None:
+            stats.update(st.as_dict())
+
 
 def _take_string(ptr, n):
     s = C.string_at(ptr, n.value)
@@ -1267,6 +1329,28 @@ class RtcWorld:
         st = Stats() if stats is not None else None
         rc = render_lib().rl_rtc_render_device(self.device(), C.byref(cam), aa_samples, row_first, row_step, C.c_void_p(d_ptr),
                                                C.c_void_p(stream), C.byref(st) if st is not None else None)
+        _check(rc)
+        if stats is not None:
+            stats.update(st.as_dict())
+
+    def render_pixels(self, xs, ys, aa_samples=1, camera=None, stats=None, allow_degenerate=False):
+        """rl_rtc_render_pixels: [n, 3] means of pixels (xs[i], ys[i]), each bit for bit render(aa_samples)[ys[i], xs[i]]."""
+        cam = camera or self.camera
+        xs, ys = _pixel_list(xs, ys)
+        out = np.empty((xs.size, 3), dtype=np.float64)
+        st = Stats()
+        rc = render_lib().rl_rtc_render_pixels(self.device(), C.byref(cam), aa_samples, xs.ctypes.data, ys.ctypes.data, xs.size, out.ctypes.data, C.byref(st))
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+        return out
+
+    def render_pixels_device(self, d_xs, d_ys, n, d_out, aa_samples=1, camera=None, stream=0, stats=None):
+        cam = camera or self.camera
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtc_render_pixels_device(self.device(), C.byref(cam), aa_samples, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n), C.c_void_p(d_out),
+                                                      C.c_void_p(stream), C.byref(st) if st is not None else None)
         _check(rc)
         if stats is not None:
             stats.update(st.as_dict())

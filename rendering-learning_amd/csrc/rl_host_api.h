@@ -2,6 +2,7 @@
 // its own: rl_render.hip and rl_multi.hip include it once each, behind their HIP_TRY, which it uses.  No kernel is named here.
 //   scene_context — the device context a scene lives on, made current; a scene whose context is gone is refused
 //   render_check  — library ready, scene family, null arguments, the empty image, row_first past the last row
+//   list_length_check / pixel_list_check — what the pixel-list renders add to it: the empty list, the list's bound, an element outside the image
 //   render_run    — the scene's lock around a render's launches and its status (the queries' counterpart: rl_query_api.h query_run)
 //   HostStaging   — the host-buffer forms' device copies of the caller's arrays, and the copy back
 //   render_rgb8   — the two _rgb8 forms: staged sums, the family's render and encode, the bytes copied back
@@ -56,6 +57,26 @@ int render_check(const rl_scene *scene, int kind, const Frame &f, bool args_ok, 
     return RL_OK;
   }
   done = false;
+  return RL_OK;
+}
+
+// The pixel-list renders (rl_*_render_pixels*): an empty list is RL_OK, touches no buffer and zeroes `st` when given, as the empty batch of
+// a query; a list the 32-bit work counter cannot number is refused; done: the call ends here with the returned code.  Both before
+// anything is read, staged or launched.  The host forms then refuse a list with an element outside the image (pixel_list_check).
+constexpr uint64_t PIXEL_LIST_MAX_N = 0xFFFF0000ull;  // n < this
+int list_length_check(uint64_t n, rl_stats *st, bool &done) {
+  done = true;
+  if (n == 0) {
+    if (st) std::memset(st, 0, sizeof *st);
+    return RL_OK;
+  }
+  if (n >= PIXEL_LIST_MAX_N) return rl::set_err_public(RL_E_INVALID, "image too large");
+  done = false;
+  return RL_OK;
+}
+int pixel_list_check(const Frame &f, const uint32_t *xs, const uint32_t *ys, uint64_t n) {
+  for (uint64_t i = 0; i < n; i++)
+    if (xs[i] >= f.w || ys[i] >= f.h) return rl::set_err_public(RL_E_INVALID, "pixel outside the image");
   return RL_OK;
 }
 

@@ -51,6 +51,7 @@ struct Switches {
   int rtiow_variant = 0;         // RL_RTIOW_KERNEL (0 = automatic)
   bool lpt = true;               // RL_LPT=0: single launch instead of the cost-sorted two-phase render
   bool coop_small = true;        // RL_COOP=0: small frames through the wave-scheduled kernel instead of the cooperative one
+  unsigned long long coop_pixels_max = 0;  // RL_COOP_PIXELS_MAX=<n>: the longest pixel LIST the cooperative kernel takes (0 = default: 160 elements per CU, the frame path's bound)
   double steal_max_fill = 3.0;   // RL_STEAL=<pixels per lane> (0 = off): work stealing on small shards
   bool fast_traversal = true;    // RL_FAST=0: counter-free renders use the reference-order kernels too
   unsigned fastg_top_max = 512;  // RL_FASTG_TOP=<n > 1>: at most n nodes
@@ -87,6 +88,7 @@ void read_switches() {
   }
   if (const char *v = std::getenv("RL_LPT")) w.lpt = std::string(v) != "0";
   if (const char *v = std::getenv("RL_COOP")) w.coop_small = std::string(v) != "0";
+  if (const char *v = std::getenv("RL_COOP_PIXELS_MAX")) w.coop_pixels_max = std::strtoull(v, nullptr, 10);
   if (const char *v = std::getenv("RL_STEAL")) w.steal_max_fill = std::atof(v);
   if (const char *v = std::getenv("RL_FAST")) w.fast_traversal = std::string(v) != "0";
   if (const char *t = std::getenv("RL_TUNE")) {
@@ -1319,6 +1321,139 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
 }
 }  // namespace rl
 
+// Which kernel renders a pixel LIST (rl_rtiow_render_pixels*).  The list kernels are the cooperative one-wave-per-pixel
+// kernel (sphere-only scenes that have the fast structure, counter-free), the fast general kernel (general scenes with a fast tree,
+// counter-free) and the reference-order wave-scheduled general kernel (every counting call, and every scene the other two do not take).
+// rl_debug_set_fast_traversal(0) / rl_debug_set_coop(0) send the counter-free calls to the reference-order kernel (tests, A/B).
+enum PixelsKernel { PIXELS_REFERENCE = 0, PIXELS_FAST_GENERAL = 1, PIXELS_COOP = 2 };
+static int choose_rtiow_pixels_kernel(const rl_scene *scene, const rl_rtiow_camera *cam, const RtiowParams &P, uint64_t n, bool want_stats, PixelsKernel &out) {
+  RtiowChoice choice;
+  int rc = choose_rtiow_variant(scene, cam, P, cam->image_height, want_stats, choice);  // for what fits: the frame's own rules
+  if (rc != RL_OK) return rc;
+  const HostRtiow &H = *scene->hrt;
+  out = PIXELS_REFERENCE;
+  if (want_stats) return RL_OK;
+  if (choice.general) {
+    if (H.fg.ok && g_sw.fast_traversal) out = PIXELS_FAST_GENERAL;
+  } else if (choice.fits_fast && cam->max_depth <= FAST_DEPTH_MASK && g_sw.coop_small) {
+    // one wave per pixel is a latency kernel: beyond the frame path's bound (160 pixels per CU, choose_rtiow_variant) its throughput is a
+    // fraction of a lane-per-pixel kernel's (measured: DESIGN.md §3.13), and the reference-order kernel takes the list
+    const uint64_t limit = g_sw.coop_pixels_max ? g_sw.coop_pixels_max : (uint64_t)g_cus * 160u;
+    if (n <= limit) out = PIXELS_COOP;
+  }
+  return RL_OK;
+}
+
+namespace rl {
+// The launch half of rl_rtiow_render_pixels*: n list elements (d_xs[i], d_ys[i]) of the whole frame -> d_out[i], all on `stream`.
+// want_stats: a counting call (reference-order kernel); timed: the caller reads the stats words synchronously (ev0 / ev1 bracket the kernel)
+int rtiow_render_pixels_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const uint32_t *d_xs, const uint32_t *d_ys, uint64_t n,
+                               void *d_out, hipStream_t stream, bool want_stats, bool timed) {
+  const RtiowProgram &rt = scene->rt();
+  const HostRtiow &H = *scene->hrt;
+  if (n >= PIXEL_LIST_MAX_N) return set_err(RL_E_INVALID, "image too large");  // the u32 work counter (the entry points have checked already)
+  RtiowParams P;
+  uint64_t tile_slots = 0;
+  {
+    int rcp = fill_rtiow_params(scene, cam, first_sample, 0, 1, cam->image_height, d_out, want_stats, P, tile_slots);
+    if (rcp != RL_OK) return rcp;
+  }
+  P.n_slots = (uint32_t)n, P.pix_xs = d_xs, P.pix_ys = d_ys;
+  P.pix_rays = nullptr, P.pos_state = nullptr, P.tile_order = nullptr, P.tile_cost = nullptr, P.resume = 0;
+  P.sample_begin = 0, P.sample_end = cam->samples_per_pixel;
+  PixelsKernel which;
+  {
+    int rcv = choose_rtiow_pixels_kernel(scene, cam, P, n, want_stats, which);
+    if (rcv != RL_OK) return rcv;
+  }
+  {
+    int rco = order_after_previous(scene, stream);
+    if (rco != RL_OK) return rco;
+  }
+  HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 512, stream));  // [0] work counter, [64..] stats, [256] the cooperative kernel's counter
+  uint32_t *coop_counter = (uint32_t *)(scene->d_scratch + 256);
+  if (scene->progress_on) {  // rl_rtiow_render_progress: the list's elements claimed so far, of n (one launch: phase 0)
+    const_cast<rl_scene *>(scene)->progress_total = n;
+    P.work_counter = scene->d_progress, coop_counter = scene->d_progress;
+    HIP_TRY(hipMemsetAsync(scene->d_progress, 0, 8, stream));
+  }
+  // persistent lanes: as many workgroups as stay resident, at most one lane per list element
+  auto blocks_of = [&](const void *kern, int nt, size_t lds, uint32_t &blocks) -> int {
+    uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));
+    if (per_cu < 1) per_cu = 1;
+    if (per_cu * (uint32_t)nt > 2048) per_cu = 2048 / (uint32_t)nt;
+    blocks = (uint32_t)((n + nt - 1) / nt);
+    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
+    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;  // A/B only
+    if (ensure_lds_attr(kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+    return RL_OK;
+  };
+  auto launch = [&](void (*kern)(RtiowParams), int nt, size_t lds) -> int {  // parameter block by value
+    uint32_t blocks = 0;
+    int rcb = blocks_of((const void *)kern, nt, lds, blocks);
+    if (rcb != RL_OK) return rcb;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
+    HIP_TRY(hipGetLastError());
+    return RL_OK;
+  };
+  auto launch_ptr = [&](void (*kern)(const RtiowParams *), int nt, size_t lds) -> int {  // by pointer: a stream-ordered device copy
+    uint32_t blocks = 0;
+    int rcb = blocks_of((const void *)kern, nt, lds, blocks);
+    if (rcb != RL_OK) return rcb;
+    const RtiowParams *slot = nullptr;
+    int rcs = stage_params(scene, P, stream, slot);
+    if (rcs != RL_OK) return rcs;
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
+    HIP_TRY(hipGetLastError());
+    return RL_OK;
+  };
+  const bool trans = rt.has_noise || rt.has_sphere_uv;
+  if (timed) HIP_TRY(hipEventRecord(scene->ev0, stream));
+  int rc = RL_OK;
+  if (which == PIXELS_COOP) {  // one wave per element; the two register modes by list length, as the frame path's launch_coop
+    constexpr int NW = 4;
+    CoopParams C{};
+    C.pixels = nullptr, C.n_pixels = (uint32_t)n, C.leaf_boxes = scene->d_fast_leaf_boxes, C.counter = coop_counter, C.max_cand = 128;
+    const size_t lds = (size_t)8 * NW * 64 * sizeof(unsigned long long) + (size_t)NW * C.max_cand * sizeof(uint32_t);
+    uint32_t blocks = (uint32_t)((n + NW - 1) / NW);
+    const uint32_t cap = (uint32_t)g_cus * (16 / NW);  // 4 waves per SIMD at 128 VGPRs
+    if (blocks > cap) blocks = cap;
+    const int mode = g_sw.coop_mode >= 0 ? g_sw.coop_mode : (n <= (uint64_t)g_cus * 8u ? 2 : 0);
+    if (mode == 2) {
+      if (ensure_lds_attr((const void *)rtiow_coop_pixels_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
+      hipLaunchKernelGGL((rtiow_coop_pixels_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
+    } else {
+      if (ensure_lds_attr((const void *)rtiow_coop_pixels_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
+      hipLaunchKernelGGL((rtiow_coop_pixels_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
+    }
+    HIP_TRY(hipGetLastError());
+  } else if (which == PIXELS_FAST_GENERAL) {  // the flavours and LDS layout of the frame's variant 1031 (rtiow_render_launch)
+    if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
+    const bool media = H.fg.stage_roots.size() > 1;
+    const bool one_wave = trans && media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : n <= (uint64_t)g_cus * 1536u);
+    const int SD = (media || trans) ? 40 : 20, nt = one_wave ? 256 : (media || trans) ? 512 : 768;
+    const size_t base = (size_t)nt * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));
+    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
+    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(H.fg.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
+    size_t lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
+    if (one_wave && lds < 90000) lds = 90000;  // one workgroup per CU
+    if (one_wave) rc = launch_ptr(rtiow_fast_general_pixels_kernel<256, 40, true, true>, nt, lds);
+    else if (media) rc = trans ? launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, true, true>, nt, lds) : launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, false, true>, nt, lds);
+    else if (trans) rc = launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, true, false>, nt, lds);
+    else rc = launch_ptr(rtiow_fast_general_pixels_kernel<768, 20, false, false>, nt, lds);
+  } else {  // reference order: 512 lanes per CU, rings (and a medium scope's parked HitRecord) in LDS, as the frame's variant 4
+    const size_t lds = (size_t)512 * (16 + (rt.has_media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long);
+    if (rt.has_media) {
+      if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, true, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, true, false, true>, 512, lds);
+      else rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, false, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, false, false, true>, 512, lds);
+    } else if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, true, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, true, false, false>, 512, lds);
+    else rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, false, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, false, false, false>, 512, lds);
+  }
+  if (timed) HIP_TRY(hipEventRecord(scene->ev1, stream));
+  return rc;  // the caller ends the render with collect_stats / post_status, which record ev_last behind the stats copy
+}
+}  // namespace rl
+
 extern "C" {
 
 int rl_rtiow_render_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
@@ -1338,6 +1473,25 @@ int rl_rtiow_render_independent_device(const rl_scene *scene, const rl_rtiow_cam
   hipStream_t stream = (hipStream_t)hip_stream;
   return render_run(scene, stream, st,
                     [&] { return rl::rtiow_render_indep_launch(scene, cam, first_sample, row_first, row_step, accumulate != 0, d_out, stream, st != nullptr); });
+}
+
+// Pixel-list renders (include/rl_render.h "Pixel-list renders").  counting: the caller gave opt_stats (reference-order
+// kernel, all seven counters); sync_st: filled synchronously (the host form always; rays and flagged only when !counting); null: asynchronous.
+static int rtiow_render_pixels_impl(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const void *d_xs, const void *d_ys, uint64_t n,
+                                    void *d_out, hipStream_t stream, bool counting, rl_stats *sync_st) {
+  return render_run(scene, stream, sync_st, [&] {
+    return rl::rtiow_render_pixels_launch(scene, cam, first_sample, (const uint32_t *)d_xs, (const uint32_t *)d_ys, n, d_out, stream, counting, sync_st != nullptr);
+  });
+}
+
+int rl_rtiow_render_pixels_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const void *d_xs, const void *d_ys, uint64_t n,
+                                  void *d_out, void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), n == 0 || (d_xs && d_ys && d_out), 0, "empty image", st, done);
+  if (done) return rc;
+  rc = list_length_check(n, st, done);
+  if (done) return rc;
+  return rtiow_render_pixels_impl(scene, cam, first_sample, d_xs, d_ys, n, d_out, (hipStream_t)hip_stream, st != nullptr, st);
 }
 
 // Completion + status of the last ASYNCHRONOUS render of this scene (rl_*_render_device / rl_*_render_multi_device with
@@ -1552,6 +1706,7 @@ int rl_debug_host_structures(const rl_rtiow_scene_desc *desc, unsigned long long
 void rl_debug_set_rtiow_variant(int v) { g_sw.rtiow_variant = v; }
 void rl_debug_set_lpt(int on) { g_sw.lpt = on != 0; }
 void rl_debug_set_coop(int on) { g_sw.coop_small = on != 0; }
+void rl_debug_set_coop_pixels_max(unsigned long long n) { g_sw.coop_pixels_max = n; }  // longest pixel list through the cooperative kernel (0: default; tests, A/B)
 void rl_debug_set_steal(double max_fill) { g_sw.steal_max_fill = max_fill; }
 void rl_debug_set_fast_traversal(int on) { g_sw.fast_traversal = on != 0; }
 void rl_debug_set_rtc_blocks(int per_cu) { g_sw.rtc_blocks_per_cu = per_cu < 0 ? 0 : per_cu; }  // 0: as many as are resident (default); n: n per CU (tests)
@@ -1667,6 +1822,22 @@ int rl_rtiow_render_independent_rows(const rl_scene *scene, const rl_rtiow_camer
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;
   return q.finish(rl_rtiow_render_independent_device(scene, cam, first_sample, row_first, row_step, accumulate, d_out, q.stream, &local), st, local);
+}
+
+int rl_rtiow_render_pixels(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys, uint64_t n,
+                           double *out, rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), n == 0 || (xs && ys && out), 0, "empty image", st, done);
+  if (done) return rc;
+  rc = list_length_check(n, st, done);
+  if (done) return rc;
+  if ((rc = pixel_list_check(frame_of(cam), xs, ys, n)) != RL_OK) return rc;
+  HostStaging q(scene);
+  const unsigned char *d_xy = (const unsigned char *)q.in({{xs, (size_t)n * sizeof(uint32_t)}, {ys, (size_t)n * sizeof(uint32_t)}});
+  void *d_out = q.out(out, (size_t)n * 3 * sizeof(double));
+  if (q.rc != RL_OK) return q.rc;
+  rl_stats local;
+  return q.finish(rtiow_render_pixels_impl(scene, cam, first_sample, d_xy, d_xy + (size_t)n * sizeof(uint32_t), n, d_out, q.stream, st != nullptr, &local), st, local);
 }
 
 int rl_rtiow_encode_rgb8_device(const void *d_rgb_sum, uint64_t n_pixels, uint32_t samples, void *d_rgb8, void *hip_stream) {
@@ -1806,9 +1977,12 @@ rl_scene *rl_rtc_scene_create(const rl_rtc_scene_desc *desc) {
 }  // extern "C"
 
 namespace rl {
+// d_xs != null: the list flavour (rtc_render_pixels_launch) — n elements (d_xs[i], d_ys[i]) of the whole frame instead of the shard's pixels
 int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, uint32_t row_first, uint32_t row_step, void *d_out, hipStream_t stream,
-                      bool want_stats) {
+                      bool want_stats, const uint32_t *d_xs, const uint32_t *d_ys, uint64_t n_list) {
   const RtcProgram &rc_ = scene->rc();
+  const bool list = d_xs != nullptr;
+  if (list && n_list >= PIXEL_LIST_MAX_N) return set_err(RL_E_INVALID, "image too large");  // the RTIOW list renders' bound (the entry points have checked already)
   uint32_t H = cam->vsize, W = cam->hsize;
   uint32_t nrows = row_first < H ? (H - row_first + row_step - 1) / row_step : 0;
   const uint32_t n_guards = (uint32_t)scene->hrc->guards.size();
@@ -1832,7 +2006,7 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
   size_t scene_bytes = (size_t)P.n_ops * sizeof(DevOp) + (size_t)P.n_tris * sizeof(DevTri) + (size_t)P.n_guards * sizeof(RtcGuard);
   bool lds_scene = scene_bytes <= 65536;
   size_t lds = lds_scene ? scene_bytes : 0;
-  uint64_t total = (uint64_t)W * nrows;
+  uint64_t total = list ? n_list : (uint64_t)W * nrows;
   uint64_t want = (total + NT - 1) / NT;
   // The grid is exactly what is RESIDENT at once (occupancy API: 2 workgroups per CU for rtc_kernel's 241 VGPRs, 3 for rtc_full_kernel's budget):
   // every workgroup stages the scene in LDS once and strides over the pixels.  Measured against the 8 per CU of rounds 1 - 2 (workgroups
@@ -1865,25 +2039,34 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
     // register budget of three waves per SIMD (168 VGPRs; ~165 of the kernel's binary64 temporaries then live in scratch, at points that
     // run once per ray): measured 13.3 / 14.0 / 19.2 ms for 3 / 2 / 1 waves on the mirror scene at 1080p, 2.7 / 2.9 / 4.2 ms on the teapot
     // forced through this kernel.  RL_RTC_FULL_REGS=256|512 selects the other budgets (A/B).
-#ifdef RL_EXPERIMENTAL
-    if (g_sw.rtc_full_regs == 512) { blocks = grid_for((const void *)rtc_full_kernel<NT, 512>, 0); hipLaunchKernelGGL((rtc_full_kernel<NT, 512>), dim3(blocks), dim3(NT), 0, stream, F); }
-    else if (g_sw.rtc_full_regs == 256) { blocks = grid_for((const void *)rtc_full_kernel<NT, 256>, 0); hipLaunchKernelGGL((rtc_full_kernel<NT, 256>), dim3(blocks), dim3(NT), 0, stream, F); }
+#ifdef RL_EXPERIMENTAL  // (the other register budgets exist for the frame kernels only: a list call takes the product flavour)
+    if (!list && g_sw.rtc_full_regs == 512) { blocks = grid_for((const void *)rtc_full_kernel<NT, 512>, 0); hipLaunchKernelGGL((rtc_full_kernel<NT, 512>), dim3(blocks), dim3(NT), 0, stream, F); }
+    else if (!list && g_sw.rtc_full_regs == 256) { blocks = grid_for((const void *)rtc_full_kernel<NT, 256>, 0); hipLaunchKernelGGL((rtc_full_kernel<NT, 256>), dim3(blocks), dim3(NT), 0, stream, F); }
     else
 #endif
-    {
+    if (list) {
+      blocks = grid_for((const void *)rtc_full_pixels_kernel<NT, 768>, 0);
+      hipLaunchKernelGGL((rtc_full_pixels_kernel<NT, 768>), dim3(blocks), dim3(NT), 0, stream, F, d_xs, d_ys, n_list);
+    } else {
       blocks = grid_for((const void *)rtc_full_kernel<NT, 768>, 0);
       hipLaunchKernelGGL((rtc_full_kernel<NT, 768>), dim3(blocks), dim3(NT), 0, stream, F);
     }
   // (241 VGPRs -> two waves per SIMD.  Measured in round 3 with the register budgets of three / four waves (68 / 128 spilled VGPRs): AA 8 19.5 -> 21.1 /
   // 22.5 ms, AA 1 0.547 -> 0.518 / 0.517 ms: the binary64 Moeller-Trumbore + Phong temporaries in scratch cost more than the extra waves hide.)
 #ifdef RL_EXPERIMENTAL
-  } else if (lds_scene && g_sw.rtc_regs == 768) {
+  } else if (!list && lds_scene && g_sw.rtc_regs == 768) {
     blocks = grid_for((const void *)rtc_kernel<NT, true, 768>, lds);
     hipLaunchKernelGGL((rtc_kernel<NT, true, 768>), dim3(blocks), dim3(NT), lds, stream, P);
-  } else if (lds_scene && g_sw.rtc_regs == 1024) {
+  } else if (!list && lds_scene && g_sw.rtc_regs == 1024) {
     blocks = grid_for((const void *)rtc_kernel<NT, true, 1024>, lds);
     hipLaunchKernelGGL((rtc_kernel<NT, true, 1024>), dim3(blocks), dim3(NT), lds, stream, P);
 #endif
+  } else if (list && lds_scene) {
+    blocks = grid_for((const void *)rtc_pixels_kernel<NT, true>, lds);
+    hipLaunchKernelGGL((rtc_pixels_kernel<NT, true>), dim3(blocks), dim3(NT), lds, stream, P, d_xs, d_ys, n_list);
+  } else if (list) {
+    blocks = grid_for((const void *)rtc_pixels_kernel<NT, false>, 0);
+    hipLaunchKernelGGL((rtc_pixels_kernel<NT, false>), dim3(blocks), dim3(NT), 0, stream, P, d_xs, d_ys, n_list);
   } else if (lds_scene) {
     blocks = grid_for((const void *)rtc_kernel<NT, true>, lds);
     hipLaunchKernelGGL((rtc_kernel<NT, true>), dim3(blocks), dim3(NT), lds, stream, P);
@@ -1894,6 +2077,11 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
   HIP_TRY(hipGetLastError());
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev1, stream));
   return RL_OK;  // the caller ends the render with collect_stats / post_status, which record ev_last behind the stats copy
+}
+// The launch half of rl_rtc_render_pixels*: rtc_render_launch's parameters, kernel choice and grid with the list flavours of the two kernels
+int rtc_render_pixels_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, const uint32_t *d_xs, const uint32_t *d_ys, uint64_t n, void *d_out,
+                             hipStream_t stream, bool want_stats) {
+  return rtc_render_launch(scene, cam, aa, 0, 1, d_out, stream, want_stats, d_xs, d_ys, n);
 }
 }  // namespace rl
 
@@ -1919,6 +2107,35 @@ int rl_rtc_render_rows(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;
   return q.finish(rl_rtc_render_device(scene, cam, aa, row_first, row_step, d_out, q.stream, &local), st, local);
+}
+
+int rl_rtc_render_pixels_device(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, const void *d_xs, const void *d_ys, uint64_t n, void *d_out,
+                                void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 2, frame_of(cam), aa != 0 && (n == 0 || (d_xs && d_ys && d_out)), 0, "empty image", st, done);
+  if (done) return rc;
+  rc = list_length_check(n, st, done);
+  if (done) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  return render_run(scene, stream, st, [&] {
+    return rl::rtc_render_pixels_launch(scene, cam, aa, (const uint32_t *)d_xs, (const uint32_t *)d_ys, n, d_out, stream, st != nullptr);
+  });
+}
+
+int rl_rtc_render_pixels(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, const uint32_t *xs, const uint32_t *ys, uint64_t n, double *out,
+                         rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 2, frame_of(cam), aa != 0 && (n == 0 || (xs && ys && out)), 0, "empty image", st, done);
+  if (done) return rc;
+  rc = list_length_check(n, st, done);
+  if (done) return rc;
+  if ((rc = pixel_list_check(frame_of(cam), xs, ys, n)) != RL_OK) return rc;
+  HostStaging q(scene);
+  const unsigned char *d_xy = (const unsigned char *)q.in({{xs, (size_t)n * sizeof(uint32_t)}, {ys, (size_t)n * sizeof(uint32_t)}});
+  void *d_out = q.out(out, (size_t)n * 3 * sizeof(double));
+  if (q.rc != RL_OK) return q.rc;
+  rl_stats local;
+  return q.finish(rl_rtc_render_pixels_device(scene, cam, aa, d_xy, d_xy + (size_t)n * sizeof(uint32_t), n, d_out, q.stream, &local), st, local);
 }
 
 int rl_rtc_encode_rgb8_device(const void *d_rgb, uint64_t n_pixels, void *d_rgb8, void *hip_stream) {

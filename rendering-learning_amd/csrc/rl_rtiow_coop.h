@@ -121,8 +121,8 @@ __device__ __forceinline__ void rtiow_coop_body(const RtiowParams &P, const floa
     uint32_t pix = 0, n_begin = 0, pos0 = 0;
     D3 sum = d3(0.0, 0.0, 0.0);
     if (!src.next(P, lane, pix, sum, pos0, n_begin)) break;
-    const uint32_t x = pix % W, r = pix / W;
-    const uint32_t y = P.row_first + r * P.row_step;
+    uint32_t x, y;
+    src.locate(P, pix, x, y);
     WaveRng<NT> rng{P.key, s_rng, tid, 0ull, pos0, 0xFFFFFFFFu};
     for (uint32_t n = n_begin; n < P.sample_end; n++) {
       uint64_t sample_index = (uint64_t)n + P.first_sample;
@@ -325,6 +325,13 @@ __device__ __forceinline__ void rtiow_coop_body(const RtiowParams &P, const floa
   }
 }
 
+// the image pixel of a virtual index pr * W + px over the shard's rows: the work item of CoopListSource and CoopStealSource
+__device__ __forceinline__ void virtual_index_pixel(const RtiowParams &P, uint32_t pix, uint32_t &x, uint32_t &y) {
+  const uint32_t W = P.cam.image_width;
+  x = pix % W;
+  y = P.row_first + (pix / W) * P.row_step;
+}
+
 // Work source of the stand-alone kernel: the pixels of a list, each from the state the previous launch left (P.resume) or from scratch
 struct CoopListSource {
   const uint32_t *pixels;
@@ -344,6 +351,7 @@ struct CoopListSource {
     }
     return true;
   }
+  __device__ __forceinline__ void locate(const RtiowParams &P, uint32_t pix, uint32_t &x, uint32_t &y) const { virtual_index_pixel(P, pix, x, y); }
   __device__ __forceinline__ void finish(const RtiowParams &P, int lane, uint32_t pix, D3 sum, uint32_t pos) const {
     if (lane == 0) {
       double *outp = P.out + (size_t)pix * 3;
@@ -367,6 +375,49 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_coop_kernel(Rt
   unsigned long long *s_rng = (unsigned long long *)smem;
   uint32_t *s_cand = (uint32_t *)(smem + (size_t)8 * NT * sizeof(unsigned long long)) + (size_t)(threadIdx.x >> 6) * C.max_cand;
   rtiow_coop_body<NT, BOXES_IN_REGS>(P, C.leaf_boxes, C.max_cand, s_rng, CoopLinearCand{s_cand}, CoopListSource{C.pixels, C.n_pixels, C.counter});
+}
+
+// Work source of rl_rtiow_render_pixels* (DESIGN.md §3.13): the elements of the caller's (x, y) list, one wave per element.  The work item is
+// the element's INDEX, which is also where its sums go (compact output); an element outside the image (the _device form) is written as
+// zeros and traces nothing.  Always from scratch: no resume, no saved word positions.
+struct CoopPixelListSource {
+  const uint32_t *xs, *ys;
+  uint32_t n_pixels;
+  uint32_t *counter;
+  __device__ __forceinline__ bool next(const RtiowParams &P, int lane, uint32_t &pix, D3 &sum, uint32_t &pos, uint32_t &n_begin) const {
+    for (;;) {
+      uint32_t idx = 0;
+      if (lane == 0) idx = atomicAdd(counter, 1u);
+      idx = __shfl(idx, 0, 64);
+      if (idx >= n_pixels) return false;
+      if (xs[idx] >= P.cam.image_width || ys[idx] >= P.cam.image_height) {
+        if (lane == 0) {
+          double *outp = P.out + (size_t)idx * 3;
+          outp[0] = 0.0, outp[1] = 0.0, outp[2] = 0.0;
+        }
+        continue;
+      }
+      pix = idx;
+      n_begin = P.sample_begin, pos = 0u, sum = d3(0.0, 0.0, 0.0);
+      return true;
+    }
+  }
+  __device__ __forceinline__ void locate(const RtiowParams &, uint32_t pix, uint32_t &x, uint32_t &y) const { x = xs[pix], y = ys[pix]; }
+  __device__ __forceinline__ void finish(const RtiowParams &P, int lane, uint32_t pix, D3 sum, uint32_t) const {
+    if (lane == 0) {
+      double *outp = P.out + (size_t)pix * 3;
+      outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+    }
+  }
+};
+// the stand-alone form over a pixel list: same body, same two register modes as rtiow_coop_kernel (C.pixels is not read)
+template <int NW, bool BOXES_IN_REGS, int REGS_FOR>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_coop_pixels_kernel(RtiowParams P, CoopParams C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NT = NW * 64;
+  unsigned long long *s_rng = (unsigned long long *)smem;
+  uint32_t *s_cand = (uint32_t *)(smem + (size_t)8 * NT * sizeof(unsigned long long)) + (size_t)(threadIdx.x >> 6) * C.max_cand;
+  rtiow_coop_body<NT, BOXES_IN_REGS>(P, C.leaf_boxes, C.max_cand, s_rng, CoopLinearCand{s_cand}, CoopPixelListSource{P.pix_xs, P.pix_ys, C.n_pixels, C.counter});
 }
 
 // ---- work stealing (the STEAL instantiation of rtiow_wave_kernel, small shards): see RtiowParams::steal_state
@@ -411,6 +462,7 @@ struct CoopStealSource {
       return true;
     }
   }
+  __device__ __forceinline__ void locate(const RtiowParams &P, uint32_t pix, uint32_t &x, uint32_t &y) const { virtual_index_pixel(P, pix, x, y); }
   __device__ __forceinline__ void finish(const RtiowParams &P, int lane, uint32_t pix, D3 sum, uint32_t pos) const {
     if (lane == 0) {
       double *outp = P.out + (size_t)pix * 3;

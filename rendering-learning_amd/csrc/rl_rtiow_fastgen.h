@@ -177,12 +177,12 @@ __device__ __forceinline__ void fastg_sphere_hit(const DevSphere &s, uint32_t pa
 // INDEP: the sample-parallel mode, as in rtiow_wave_indep_kernel (rl_rtiow_wave.h; the body is included into both kernels for the same reason)
 template <int NT, int SD, bool TRANS, bool OCTO = false, bool MEDIA = false>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = false, RAYS = false;
+  constexpr bool INDEP = false, RAYS = false, PIXELS = false;
 #include "rl_rtiow_fastgen_body.inc"
 }
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_indep_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = true, OCTO = false, RAYS = false;
+  constexpr bool INDEP = true, OCTO = false, RAYS = false, PIXELS = false;
 #include "rl_rtiow_fastgen_body.inc"
 }
 // RAYS (rl_rtiow_ray_color_rays*): Camera::ray_color for a buffer of rays, each with its own RNG cursor.  GEN claims rays
@@ -190,7 +190,14 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_indep_k
 // treatment of start_ray, the exact re-trace — is the body's own.  P.cam carries the call's background and max_depth, P.key its seed.
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_rays_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = false, OCTO = false, RAYS = true;
+  constexpr bool INDEP = false, OCTO = false, RAYS = true, PIXELS = false;
+#include "rl_rtiow_fastgen_body.inc"
+}
+// PIXELS (rl_rtiow_render_pixels*): GEN claims elements of the caller's (x, y) list instead of tile slots and stores a pixel's
+// sums at its element index; everything behind the claim is the body's own, so a listed pixel is the frame's pixel bit for bit.
+template <int NT, int SD, bool TRANS, bool MEDIA>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_pixels_kernel(const RtiowParams *__restrict__ Pp) {
+  constexpr bool INDEP = false, OCTO = false, RAYS = false, PIXELS = true;
 #include "rl_rtiow_fastgen_body.inc"
 }
 

@@ -93,6 +93,9 @@ struct RtiowParams {
   rl_rng_cursor *q_out_cursors;   // [n] or null
   uint32_t *q_ray_counts;         // [n] or null
   uint64_t q_first;
+  // pixel-list mode (PIXELS instantiations, rl_rtiow_render_pixels*): a slot is element i of the caller's list, pixel (pix_xs[i], pix_ys[i]) of
+  // the whole frame (row_first = 0, row_step = 1); its sums go to out[i], never to out[y * W + x].  n_slots = the list's length.
+  const uint32_t *pix_xs, *pix_ys;
 };
 
 // RAYS: the path's colour, the cursor behind it and its ray count to the ray's own index

@@ -1,5 +1,5 @@
-  // The body of rtiow_wave_general_kernel / rtiow_wave_general_indep_kernel / rtiow_wave_general_rays_kernel (rl_rtiow_wave_general.h): included
-  // inside all three, with INDEP, RAYS (and the kernel's template parameters) in scope.
+  // The body of rtiow_wave_general_kernel / rtiow_wave_general_indep_kernel / rtiow_wave_general_rays_kernel / rtiow_wave_general_pixels_kernel
+  // (rl_rtiow_wave_general.h): included inside all four, with INDEP, RAYS, PIXELS (and the kernel's template parameters) in scope.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   unsigned long long *s_rng = (unsigned long long *)smem;  // [16][NT]
@@ -228,7 +228,34 @@
           if (n >= n_end) have_pixel = false;
           else rng.pos = 0, rng.nres = 0, sum = d3(0.0, 0.0, 0.0);
         }
-        if (n >= (INDEP ? n_end : spp)) {
+        if constexpr (PIXELS) {  // a work item is element q_idx of the caller's pixel list: (x, y) read once, compact output, no tiles / resume
+          if (n >= spp) {
+            if (have_pixel) {
+              double *outp = P.out + (size_t)q_idx * 3;
+              outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+              if (STATS) c_words += rng.pos;
+              have_pixel = false;
+            }
+            const uint32_t slot = wave_claim(P.work_counter);  // 64 consecutive list elements per wave claim
+            active = false;
+            if (slot >= P.n_slots) state = ST_DONE;
+            else {
+              q_idx = slot;
+              px = P.pix_xs[slot], pr = P.pix_ys[slot];
+              if (px >= W || pr >= cam.image_height) {  // not a pixel of the image (the _device form): zeros, nothing traced
+                double *outp = P.out + (size_t)slot * 3;
+                outp[0] = 0.0, outp[1] = 0.0, outp[2] = 0.0;
+              } else {
+                have_pixel = true;
+                n = s_begin;
+                pix_rays = 0;
+                rng.pos = 0, rng.nres = 0;
+                sum = d3(0.0, 0.0, 0.0);
+                active = n < spp;
+              }
+            }
+          }
+        } else if (n >= (INDEP ? n_end : spp)) {
           if (have_pixel) {
             size_t pix = (size_t)pr * W + px;
             double *outp = P.out + pix * 3;

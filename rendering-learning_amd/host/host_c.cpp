@@ -548,6 +548,29 @@ int rlh_seeded_hit_query_probe(const rl_ray *rays, rl_rng_cursor *cursors, uint6
     return -1;
   }
 }
+// Pixel-list renders through the C++ mirror.  family = 0: rtiow::Camera::render_pixels on golden_test_scene at image_width = width,
+// samples_per_pixel = spp_or_aa; family = 1: rtc::Camera::render_pixels on the mirror scene at width x (2 width / 3), AA = spp_or_aa.
+// out = n * 3 doubles.  0 or -1 (rlh_last_error).
+int rlh_render_pixels_probe(int family, uint64_t width, uint64_t spp_or_aa, const uint32_t *xs, const uint32_t *ys, uint64_t n, double *out) {
+  try {
+    std::vector<double> v;
+    if (family == 0) {
+      scenes::RtiowScene s = scenes::golden_test_scene();
+      s.params.image_width = (size_t)width, s.params.samples_per_pixel = (size_t)spp_or_aa;
+      v = rtiow::Camera(s.params).render_pixels(*s.world, xs, ys, (size_t)n);
+    } else {
+      scenes::RtcScene s = scenes::rtc_test_mirror_scene((size_t)width, (size_t)(width * 2 / 3));
+      rtc::RenderOpts opts;
+      opts.anti_aliasing_samples = (size_t)spp_or_aa;
+      v = s.camera->render_pixels(s.world, opts, xs, ys, (size_t)n);
+    }
+    std::memcpy(out, v.data(), v.size() * sizeof(double));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
 // which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
 // b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,

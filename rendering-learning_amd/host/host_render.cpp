@@ -39,6 +39,19 @@ static Canvas render_independent_impl(const Camera &camera, const Hittable &worl
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_independent_rows: ") + rl_last_error());
   return c;
 }
+std::vector<double> Camera::render_pixels(const Hittable &world, const uint32_t *xs, const uint32_t *ys, size_t n, uint64_t first_sample) const {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  rl_rtiow_camera cam = derived();
+  std::vector<double> out(n * 3);
+  int rc = rl_rtiow_render_pixels(sc, &cam, first_sample, xs, ys, n, out.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_pixels: ") + rl_last_error());
+  return out;
+}
 Canvas Camera::render_independent(const Hittable &world) const { return render_independent_impl(*this, world, nullptr); }
 Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
   return render_independent_impl(*this, world, &checkpoint);
@@ -134,6 +147,19 @@ Canvas Camera::render(const World &world, const RenderOpts &opts) const {  // sc
   rl_scene_destroy(sc);
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtc_render: ") + rl_last_error());
   return c;
+}
+std::vector<double> Camera::render_pixels(const World &world, const RenderOpts &opts, const uint32_t *xs, const uint32_t *ys, size_t n) const {
+  Flattened f;
+  world.flatten(f);
+  rl_rtc_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtc_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtc_scene_create: ") + rl_last_error());
+  rl_rtc_camera cam = derived();
+  std::vector<double> out(n * 3);
+  int rc = rl_rtc_render_pixels(sc, &cam, (uint32_t)opts.anti_aliasing_samples, xs, ys, n, out.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtc_render_pixels: ") + rl_last_error());
+  return out;
 }
 std::vector<double> World::color_at(const rl_ray *rays, size_t n) const {  // world.rs:100
   Flattened f;

@@ -614,6 +614,8 @@ struct Camera {  // scene/camera.rs:11-57
     return c;
   }
   Canvas render(const World &world, const RenderOpts &opts) const;  // GPU, through the C ABI (host_render.cpp)
+  // the pixels of the caller's choosing (rl_rtc_render_pixels): out[3 i ..] = render(world, opts) at pixel (xs[i], ys[i]), bit for bit
+  std::vector<double> render_pixels(const World &world, const RenderOpts &opts, const uint32_t *xs, const uint32_t *ys, size_t n) const;
 };
 
 // Canvas::ppm (draw/canvas.rs:50-97): round(c*255) clamp 0..255, 70-column wrap per row, no gamma

@@ -796,6 +796,9 @@ struct Camera {
   // its sums (bit for bit samples_per_pixel repetitions of render_from_checkpoint with one sample per pixel)
   Canvas render_independent(const Hittable &world) const;
   Canvas render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const;
+  // the pixels of the caller's choosing (rl_rtiow_render_pixels): out[3 i ..] = the sums _render(first_sample, world) leaves at pixel
+  // (xs[i], ys[i]), bit for bit, for any list (unsorted, duplicates); a pixel outside the image throws
+  std::vector<double> render_pixels(const Hittable &world, const uint32_t *xs, const uint32_t *ys, size_t n, uint64_t first_sample = 0) const;
   // Camera::get_ray(&mut rng, x, y) (camera.rs:203-216) for a batch of pixels, on the GPU (rl_rtiow_camera_rays): rng_i as for
   // ray_color_rays with seed = params.seed; cursors[i] is advanced behind the draws.  _render's stream of sample s at pixel (x, y) is
   // s * W * H + x * W + y (camera.rs:161-170).
