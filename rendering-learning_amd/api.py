@@ -22,7 +22,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# RL_RENDER_LIB selects another build of the same ABI (csrc/librl_render_exp.so: + the experimental kernel variants, A/B runs only)
+# RL_RENDER_LIB selects another build of the same ABI (csrc/librl_render_verify.so, or a build of another commit for an A/B run)
 RENDER_LIB = os.environ.get("RL_RENDER_LIB") or os.path.join(_HERE, "csrc", "librl_render.so")
 HOST_LIB = os.path.join(_HERE, "host", "librl_host.so")
 
@@ -466,10 +466,6 @@ def set_status_gap(device_us, host_us=0):
     L = render_lib()
     L.rl_debug_set_status_gap.argtypes = [C.c_uint, C.c_uint]
     _check(L.rl_debug_set_status_gap(int(device_us), int(host_us)))
-
-
-def has_experimental():
-    return bool(render_lib().rl_debug_has_experimental())
 
 
 def live_buffers():
@@ -991,7 +987,8 @@ class SceneBuilder:
 
 
 def set_rtiow_variant(v):
-    """Tests / tools: force a kernel variant (0 auto, 1 nested-loop, 2 general, 512/768/1024 wave)."""
+    """Tests / tools: force a kernel variant (0 auto, 2 general, 4 wave-scheduled general, 1024 / 1025 / 1027 / 1029 wave layouts, 1031 fast general,
+    1033 cooperative); a retired number makes the next render fail with RL_E_UNSUPPORTED."""
     L = render_lib()
     L.rl_debug_set_rtiow_variant.argtypes = [C.c_int]
     L.rl_debug_set_rtiow_variant(int(v))

@@ -29,12 +29,6 @@
 #include "rl_ray_query.h"
 #include "rl_material_query.h"
 #include "rl_rtc_shade_query.h"
-#ifdef RL_EXPERIMENTAL  // the measured-and-lost restructurings: only in librl_render_exp.so, never in the product library
-#include "experimental/rl_rtiow_pool.h"
-#include "experimental/rl_rtiow_wave2.h"
-#include "experimental/rl_rtiow_wavefront.h"
-#include "experimental/rl_rtiow_wfg.h"
-#endif
 
 using namespace rl;
 
@@ -61,24 +55,22 @@ struct Switches {
   bool tune_set = false;         // RL_TUNE="steps,floor16[,batch,fill]"
   unsigned tune[4] = {24, 6, 24, 40};
   unsigned blocks_cap = 0;       // RL_BLOCKS
-  int coop_mode = -1;            // RL_COOP_MODE
-  int general_regs = 512;        // RL_GENERAL_REGS (256 / 768: experimental library only)
-  bool fastg512 = false;         // RL_FASTG512 (experimental library only)
-  int fastg_octo = 0;            // RL_FASTG_OCTO=1: the eight-wide quantised nodes instead of the four-wide ones (experimental library only)
-  int general_nt = 512;          // RL_GENERAL_NT (768: experimental library only)
-  double thin_permille = 0.0, prio_permille = 0.0;  // RL_THIN / RL_PRIO (experimental library only)
-  int thin_shift = 2;            // RL_THIN_SHIFT
-  int wavefront = -1;            // RL_WAVEFRONT=1: general fast-traversal scenes in wavefront form (experimental library only)
+  int coop_mode = -1;            // RL_COOP_MODE=2|0: boxes in registers / from L2 (any other value: as 0)
   bool rtc_force_full = false;   // RL_RTC_FORCE_FULL
-  int rtc_regs = 256;            // RL_RTC_REGS=768|1024: rtc_kernel at the register budget of three / four waves per SIMD (experimental library only)
-  int rtc_full_regs = 768;       // RL_RTC_FULL_REGS (256 / 512: experimental library only)
   unsigned indep_k = 1;          // RL_INDEP_K=<k>: samples of one pixel per claim in the sample-parallel mode
   size_t indep_cap = (size_t)1 << 30;  // RL_INDEP_CAP_MB=<MiB>: cap of that mode's pass buffer (a smaller one forces more passes: tests)
   int pixel_entry = rl::PIXEL_ENTRY_DEFAULT;  // RL_PIXEL_ENTRY=0|1|2|3: the fast kernel's camera rays start at the root / at their pixel's entry cut of up to n entries (rl_pixel_entry.h)
   bool pixel_entry_sphere = true;  // RL_PIXEL_ENTRY_SPHERE=0: that cut keeps every leaf whose BOX the pixel's beam touches; default: only those whose sphere it may touch
 } g_sw;
 std::atomic<unsigned long long> g_last_slow_traces{0};  // rl_debug_slow_traces.  Atomic: rl_render_status of two scenes runs under two locks.
-bool g_fast_debug_stats = false;  // tools only (experimental library): counting renders run the fast kernel too (counters are then NOT the reference's)
+// The instrumented fast sphere kernel rtiow_wave_kernel<1024, 4, true> (rl_debug_fast_stats, tools/sched.py) is compiled into the verify
+// build only (make verify); in the product library rl_debug_fast_stats does nothing.
+#ifdef RL_FASTG_VERIFY
+constexpr bool FAST_STATS_KERNEL = true;
+#else
+constexpr bool FAST_STATS_KERNEL = false;
+#endif
+bool g_fast_debug_stats = false;  // verify build, tools only: counting renders run the fast kernel too (counters are then NOT the reference's)
 
 void read_switches() {
   Switches w;
@@ -100,28 +92,15 @@ void read_switches() {
   }
   if (const char *v = std::getenv("RL_BLOCKS")) w.blocks_cap = (unsigned)std::atoi(v);
   if (const char *v = std::getenv("RL_COOP_MODE")) w.coop_mode = std::atoi(v);
-  if (const char *v = std::getenv("RL_GENERAL_REGS")) w.general_regs = std::atoi(v);
-  w.fastg512 = std::getenv("RL_FASTG512") != nullptr;
-  if (const char *v = std::getenv("RL_FASTG_OCTO")) w.fastg_octo = std::atoi(v);
   if (const char *v = std::getenv("RL_RTC_BLOCKS")) w.rtc_blocks_per_cu = std::max(0, std::atoi(v));
   if (const char *v = std::getenv("RL_FASTG_NT256")) w.fastg_nt256 = std::atoi(v) != 0;
   if (const char *v = std::getenv("RL_FASTG_TOP")) w.fastg_top = std::atoi(v) != 0, w.fastg_top_max = (unsigned)std::atoi(v) > 1u ? (unsigned)std::atoi(v) : 512u;
-  if (const char *v = std::getenv("RL_GENERAL_NT")) w.general_nt = std::atoi(v);
-  if (const char *v = std::getenv("RL_THIN")) w.thin_permille = std::atof(v);
-  if (const char *v = std::getenv("RL_PRIO")) w.prio_permille = std::atof(v);
-  if (const char *v = std::getenv("RL_THIN_SHIFT")) w.thin_shift = std::min(6, std::max(1, std::atoi(v)));
-  if (const char *v = std::getenv("RL_WAVEFRONT")) w.wavefront = std::atoi(v);
   w.rtc_force_full = std::getenv("RL_RTC_FORCE_FULL") != nullptr;
-  if (const char *v = std::getenv("RL_RTC_REGS")) w.rtc_regs = std::atoi(v);
-  if (const char *v = std::getenv("RL_RTC_FULL_REGS")) w.rtc_full_regs = std::atoi(v);
   if (const char *v = std::getenv("RL_INDEP_K")) w.indep_k = (unsigned)std::max(1, std::atoi(v));
   if (const char *v = std::getenv("RL_PIXEL_ENTRY")) w.pixel_entry = std::min(3, std::max(0, std::atoi(v)));
   if (const char *v = std::getenv("RL_PIXEL_ENTRY_SPHERE")) w.pixel_entry_sphere = std::string(v) != "0";
   if (const char *v = std::getenv("RL_INDEP_CAP_MB")) w.indep_cap = (size_t)std::max(1, std::atoi(v)) << 20;
   g_sw = w;
-#ifdef RL_EXPERIMENTAL
-  rl::set_build_octo(w.fastg_octo != 0);
-#endif
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is sticky per (kernel, device): set it when a launch needs more than any before it did
@@ -482,7 +461,7 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
       (!H->cops.empty() && ((rc = s->d_cops.upload(H->cops)) || (rc = s->d_movbits.upload(H->movbits)))) ||
       (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)) ||
                                       (rc = s->d_fast_leaf_balls.upload(H->fast_leaf_balls)))) ||
-      (QF.ok && ((rc = s->d_fg_nodes.upload(QF.qnodes)) || (rc = s->d_fg_onodes.upload(QF.onodes)) || (rc = s->d_fg_seg_roots.upload(QF.stage_roots)) ||
+      (QF.ok && ((rc = s->d_fg_nodes.upload(QF.qnodes)) || (rc = s->d_fg_seg_roots.upload(QF.stage_roots)) ||
                  (rc = s->d_fg_media.upload(QF.media)) || (rc = s->d_fg_items.upload(QF.items)) || (rc = s->d_fg_spheres.upload(QF.item_spheres)) || (rc = s->d_fg_material.upload(QF.item_material))))) {
     destroy_one(s);
     return nullptr;
@@ -598,142 +577,6 @@ using rl::post_status;
 
 #include "rl_host_api.h"  // scene_context, render_check, render_run, HostStaging
 
-#ifdef RL_EXPERIMENTAL
-// Wavefront (v3) driver: one PASS = begin_pass, TRAV, SHADE, GEN (rl_rtiow_wavefront.h); passes are enqueued in
-// chunks and the finished-pixel counter is polled once per chunk.
-static int render_wavefront(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream, bool want_stats) {
-  rl_scene *sc = const_cast<rl_scene *>(scene);  // work buffers only; the scene program is immutable
-  ExpBuffers *ms = &sc->exp;
-  const uint32_t Wd = P.cam.image_width;
-  size_t npix = (size_t)nrows * Wd;
-  if (npix >= 0xFFFF0000ull) return set_err(RL_E_INVALID, "image too large");
-  HIP_TRY(ms->wf_pix.reserve(npix * sizeof(PixState)));
-  HIP_TRY(ms->wf_ray.reserve(npix * sizeof(RayRec)));
-  HIP_TRY(ms->wf_hit.reserve(npix * sizeof(HitRec)));
-  HIP_TRY(ms->wf_qtrav.reserve(2 * npix));
-  HIP_TRY(ms->wf_qgen.reserve(npix));
-  HIP_TRY(ms->wf_ctl.reserve(WC_WORDS));
-  WfParams Wp{};
-  Wp.R = P;
-  Wp.pix = (PixState *)ms->wf_pix.get(), Wp.ray = (RayRec *)ms->wf_ray.get(), Wp.hit = (HitRec *)ms->wf_hit.get();
-  Wp.q_trav = ms->wf_qtrav, Wp.q_gen = ms->wf_qgen, Wp.ctl = ms->wf_ctl;
-  Wp.npix = (uint32_t)npix;
-
-  constexpr int NTS = 256;  // GEN / SHADE workgroups
-  size_t lds_s = (size_t)8 * NTS * sizeof(unsigned long long);
-  uint32_t flat_blocks = (uint32_t)((npix + NTS - 1) / NTS);
-  uint32_t stage_blocks = flat_blocks < (uint32_t)g_cus * 8 ? flat_blocks : (uint32_t)g_cus * 8;
-  constexpr int NTT = 768;  // TRAV workgroups (12 waves; two per CU = 6 waves/SIMD at <= 80 VGPRs), scene staged in LDS when it fits
-  size_t scene_bytes = (size_t)P.n_ops * sizeof(DevOp) + (size_t)P.n_spheres * sizeof(DevSphere);
-  bool in_lds = scene_bytes <= g_lds_max;
-  size_t lds_t = in_lds ? scene_bytes : 0;
-  uint32_t per_cu = in_lds ? (uint32_t)(g_lds_max / (scene_bytes ? scene_bytes : 1)) : 2;
-  if (per_cu > 2) per_cu = 2;
-  if (per_cu < 1) per_cu = 1;
-  uint32_t trav_blocks = (uint32_t)g_cus * per_cu;
-  {
-    uint32_t need = (uint32_t)((npix + NTT - 1) / NTT);
-    if (trav_blocks > need) trav_blocks = need;
-  }
-  if (in_lds) {
-    HIP_TRY(hipFuncSetAttribute((const void *)wf_trav<NTT, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-    HIP_TRY(hipFuncSetAttribute((const void *)wf_trav<NTT, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t));
-  }
-  auto trav = [&]() -> int {
-    if (in_lds) {
-      if (want_stats) hipLaunchKernelGGL((wf_trav<NTT, true, true>), dim3(trav_blocks), dim3(NTT), lds_t, stream, Wp);
-      else hipLaunchKernelGGL((wf_trav<NTT, true, false>), dim3(trav_blocks), dim3(NTT), lds_t, stream, Wp);
-    } else {
-      if (want_stats) hipLaunchKernelGGL((wf_trav<NTT, false, true>), dim3(trav_blocks), dim3(NTT), 0, stream, Wp);
-      else hipLaunchKernelGGL((wf_trav<NTT, false, false>), dim3(trav_blocks), dim3(NTT), 0, stream, Wp);
-    }
-    return RL_OK;
-  };
-  hipLaunchKernelGGL(wf_init, dim3(flat_blocks), dim3(NTS), 0, stream, Wp);
-  hipLaunchKernelGGL((wf_gen<NTS>), dim3(stage_blocks), dim3(NTS), lds_s, stream, Wp);
-  HIP_TRY(hipGetLastError());
-  const int CHUNK = 64;
-  uint32_t finished = 0;
-  for (long pass = 0; pass < (1l << 40); pass += CHUNK) {
-    for (int k = 0; k < CHUNK; k++) {
-      hipLaunchKernelGGL(wf_begin_pass, dim3(1), dim3(1), 0, stream, Wp);
-      int rc = trav();
-      if (rc != RL_OK) return rc;
-      hipLaunchKernelGGL((wf_shade<NTS>), dim3(stage_blocks), dim3(NTS), lds_s, stream, Wp);
-      hipLaunchKernelGGL((wf_gen<NTS>), dim3(stage_blocks), dim3(NTS), lds_s, stream, Wp);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&finished, ms->wf_ctl + WC_FINISHED, sizeof finished, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (std::getenv("RL_WF_DEBUG")) std::fprintf(stderr, "[wf] passes %ld finished %u / %zu\n", pass + CHUNK, finished, npix);
-    if (finished >= npix) break;
-  }
-  hipLaunchKernelGGL(wf_finish, dim3(flat_blocks), dim3(NTS), 0, stream, Wp);
-  HIP_TRY(hipGetLastError());
-  return RL_OK;
-}
-
-#endif
-
-#ifdef RL_EXPERIMENTAL
-// Wavefront form of the general fast traversal (rl_rtiow_wfg.h): init, then PASSES of wfg_logic + wfg_trav until every pixel has finished.
-// The pass chain is enqueued in chunks and the finished-pixel counter is polled once per chunk (one chunk ahead of the one being waited
-// for), so this render returns when the frame is complete: the call is synchronous on `stream`.
-static int render_wfg(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream, bool trans) {
-  rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only; the scene program is immutable
-  const size_t npix = (size_t)nrows * P.cam.image_width, nslots = P.n_slots;
-  HIP_TRY(ms->d_wfg_pix.reserve(npix * sizeof(WfgPix)));
-  HIP_TRY(ms->d_wfg_ray.reserve(npix * sizeof(WfgRay)));
-  HIP_TRY(ms->d_wfg_q0.reserve(nslots));
-  HIP_TRY(ms->d_wfg_q1.reserve(nslots));
-  HIP_TRY(ms->d_wfg_qs.reserve(nslots));
-  HIP_TRY(ms->d_wfg_ctl.reserve(WFG_CTL_WORDS));
-  HIP_TRY(ms->h_wfg.reserve(16, hipHostMallocDefault));
-  WfgParams Q{};
-  Q.pix = (WfgPix *)ms->d_wfg_pix.get(), Q.ray = (WfgRay *)ms->d_wfg_ray.get(), Q.queue[0] = ms->d_wfg_q0, Q.queue[1] = ms->d_wfg_q1, Q.slow_queue = ms->d_wfg_qs, Q.ctl = ms->d_wfg_ctl;
-  P.sample_begin = 0, P.sample_end = P.cam.samples_per_pixel, P.resume = 0, P.pos_state = nullptr, P.tile_order = nullptr, P.tile_cost = nullptr;
-  if (!g_sw.tune_set) P.tune[0] = 4, P.tune[3] = FASTG_STEP_BUDGET;
-  hipLaunchKernelGGL(wfg_init, dim3((unsigned)((nslots + 255) / 256)), dim3(256), 0, stream, P, Q);
-  HIP_TRY(hipGetLastError());
-  constexpr int LNT = 256;                         // wfg_logic: blocks of one wave per SIMD, 3 (2 with transcendental textures) per CU, rings in LDS
-  const size_t llds = (size_t)16 * LNT * sizeof(unsigned long long);
-  constexpr int TNT = 256, TSD = 20;               // wfg_trav: 20-entry stacks in LDS, register budget of `twpe` waves per SIMD
-  const size_t tlds = (size_t)TSD * TNT * sizeof(uint32_t);
-  const int twpe = (g_sw.tune_set && (g_sw.tune[2] == 4 || g_sw.tune[2] == 5 || g_sw.tune[2] == 8)) ? (int)g_sw.tune[2] : 6;  // A/B: RL_TUNE third field
-  const uint32_t lblocks = (uint32_t)g_cus * (trans ? 2u : 3u), tblocks = (uint32_t)g_cus * (uint32_t)twpe;
-  const uint32_t sblocks = (uint32_t)g_cus;  // the slow queue holds a fraction of a percent of a pass's rays
-  const void *tk = twpe == 4 ? (const void *)wfg_trav<TNT, TSD, 4> : twpe == 5 ? (const void *)wfg_trav<TNT, TSD, 5> : twpe == 8 ? (const void *)wfg_trav<TNT, TSD, 8> : (const void *)wfg_trav<TNT, TSD, 6>;
-  if (ensure_lds_attr(trans ? (const void *)wfg_logic<LNT, true, false> : (const void *)wfg_logic<LNT, false, false>, llds) != 0 ||
-      ensure_lds_attr(trans ? (const void *)wfg_logic<LNT, true, true> : (const void *)wfg_logic<LNT, false, true>, llds) != 0 || ensure_lds_attr(tk, tlds) != 0)
-    return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-  const int CHUNK = 16;
-  volatile uint32_t *h_done = (volatile uint32_t *)ms->h_wfg;
-  uint32_t pass = 0;
-  for (long chunk = 0; chunk < (1l << 36); chunk++) {
-    for (int k = 0; k < CHUNK; k++, pass++) {
-      Q.in = pass & 1u;
-      if (trans) {
-        hipLaunchKernelGGL((wfg_logic<LNT, true, false>), dim3(lblocks), dim3(LNT), llds, stream, P, Q);
-        hipLaunchKernelGGL((wfg_logic<LNT, true, true>), dim3(sblocks), dim3(LNT), llds, stream, P, Q);
-      } else {
-        hipLaunchKernelGGL((wfg_logic<LNT, false, false>), dim3(lblocks), dim3(LNT), llds, stream, P, Q);
-        hipLaunchKernelGGL((wfg_logic<LNT, false, true>), dim3(sblocks), dim3(LNT), llds, stream, P, Q);
-      }
-      if (twpe == 4) hipLaunchKernelGGL((wfg_trav<TNT, TSD, 4>), dim3(tblocks), dim3(TNT), tlds, stream, P, Q);
-      else if (twpe == 5) hipLaunchKernelGGL((wfg_trav<TNT, TSD, 5>), dim3(tblocks), dim3(TNT), tlds, stream, P, Q);
-      else if (twpe == 8) hipLaunchKernelGGL((wfg_trav<TNT, TSD, 8>), dim3(tblocks), dim3(TNT), tlds, stream, P, Q);
-      else hipLaunchKernelGGL((wfg_trav<TNT, TSD, 6>), dim3(tblocks), dim3(TNT), tlds, stream, P, Q);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync((void *)h_done, ms->d_wfg_ctl + WFG_DONE, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    if (*h_done >= npix) break;
-  }
-  return RL_OK;
-}
-
-#endif
-
 // The parameter block of one render (what every RTIOW kernel receives): scene pointers, derived camera, ChaCha key, shard geometry.
 static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, uint32_t nrows, void *d_out,
                              bool want_stats, RtiowParams &P, uint64_t &slots) {
@@ -749,9 +592,6 @@ static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, 
   P.cops = scene->d_cops, P.n_cops = (uint32_t)H.cops.size(), P.centry0 = H.centry0, P.movbits = scene->d_movbits;
   P.fast_nodes = scene->d_fast_nodes, P.n_fast_inner = (uint32_t)H.fast_nodes.size(), P.fast_root = H.fast_root;
   P.fg_nodes = scene->d_fg_nodes, P.fg_items = scene->d_fg_items, P.fg_spheres = scene->d_fg_spheres, P.fg_material = scene->d_fg_material, P.fg_root = H.fg.qroot, P.fg_rsafe2 = H.fg.r_safe * H.fg.r_safe * 0.9999f;  // binary32 evaluation on the device: keep a margin
-#ifdef RL_EXPERIMENTAL
-  P.fg_onodes = scene->d_fg_onodes, P.fg_oroot = H.fg.oroot;
-#endif
   P.fg_seg_roots = scene->d_fg_seg_roots, P.fg_media = scene->d_fg_media, P.fg_n_seg = (uint32_t)H.fg.stage_roots.size();
   P.fg_top = 0;  // (set by the launch that stages it: fastg_lds)
   P.fg_center[0] = H.fg.center[0], P.fg_center[1] = H.fg.center[1], P.fg_center[2] = H.fg.center[2];
@@ -777,40 +617,30 @@ static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, 
 struct RtiowChoice {
   int variant = 0;
   bool general = false;
-  size_t compact_bytes = 0, fast_bytes = 0, scene_bytes = 0;
+  size_t compact_bytes = 0, fast_bytes = 0;
   bool fits_fast = false;
 };
 static int choose_rtiow_variant(const rl_scene *scene, const rl_rtiow_camera *cam, const RtiowParams &P, uint32_t nrows, bool want_stats, RtiowChoice &out) {
   const RtiowProgram &rt = scene->rt();
   const HostRtiow &H = *scene->hrt;
   const uint32_t W = cam->image_width, n_cops = P.n_cops;
-  const size_t scene_bytes = (size_t)P.n_ops * sizeof(DevOp) + (size_t)P.n_spheres * sizeof(DevSphere);
   // ---- kernel variant.  The PRODUCT library carries, for sphere-only worlds, the four layouts the automatic choice below can reach
   // (1029 fast traversal / 1027 guarded compact ops / 1025 linked ops in LDS / 1024 scene through L2), the cooperative kernel (1033) and
   // the nested-loop all-primitives kernel (2: the A/B reference the tests compare against); for general worlds 1031 (fast traversal) and
-  // 4 (reference order).  Every other instantiation (wave256 / 512 / 768, whole-scene-in-LDS layouts, v1, other register budgets,
-  // pool / wave2 / wavefront) is A/B material and lives in librl_render_exp.so (make exp).
+  // 4 (reference order).  The variants that were measured and lost (v1, wavefront, pool, pool256, wave2, wave256 / 512 / 768, the
+  // wavefront form of the general fast traversal) were retired; their numbers still get an explicit answer.
   int variant = g_sw.rtiow_variant;
   const bool general = rt.has_planars || rt.has_instances || rt.has_images || rt.has_noise || rt.has_media;
   // a ConstantMedium (RL_H_MEDIUM) draws from the pixel's RNG where the reference's fold reaches it: the reference-order kernels evaluate
   // it as a scope of the threaded program (wave-scheduled) or by recursion (RL_RTIOW_KERNEL=general); the fast traversal walks one tree per
   // program segment between two media (rl_rtiow_fastgen.h MEDIA) — counter-free renders only, as for every fast traversal
   if (rt.has_media && variant != 2 && variant != 0 && variant != 1031) variant = 4;
-#ifndef RL_EXPERIMENTAL
-  if (variant == 1 || variant == 3 || variant == 5 || variant == 6 || variant == 7 || variant == 256 || variant == 512 || variant == 768 || variant == 1035)
-    return set_err(RL_E_UNSUPPORTED, "this kernel variant is A/B material and lives in librl_render_exp.so only (make -C rendering-learning_amd/csrc exp)");
-#endif
+  for (int retired : {1, 3, 5, 6, 7, 256, 512, 768, 1035})
+    if (variant == retired) return set_err(RL_E_UNSUPPORTED, "this kernel variant was retired: it was measured and lost (DESIGN.md §3.5), and its code is no longer in the library");
   // 1031 = the FAST traversal for general scenes (rl_rtiow_fastgen.h): counter-free renders only, like 1029
   const bool fits_fastg = general && H.fg.ok && (!want_stats) && g_sw.fast_traversal;
   if (variant == 2) variant = 2;               // the nested-loop all-primitives kernel (A/B reference)
-  else if ((variant == 0 || variant == 1031 || variant == 1035) && fits_fastg) {
-    // 1035 = the same traversal in WAVEFRONT form (experimental/rl_rtiow_wfg.h): measured, slower, experimental library only
-    bool wf = false;
-#ifdef RL_EXPERIMENTAL
-    wf = (variant == 1035 || (variant == 0 && g_sw.wavefront == 1)) && (uint64_t)nrows * W < 0xFFFF0000ull && !rt.has_media;
-#endif
-    variant = wf ? 1035 : 1031;
-  }
+  else if ((variant == 0 || variant == 1031) && fits_fastg) variant = 1031;
   else if (general || variant == 4 || variant == 1031) variant = 4;  // wave-scheduled all-primitives kernel (scene read from HBM/L2)
   const size_t compact_bytes = ((size_t)n_cops * sizeof(CompactOp) + (((size_t)P.n_spheres + 31) / 32 + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
   bool fits_compact = n_cops != 0 && (size_t)16 * 1024 * sizeof(unsigned long long) + compact_bytes <= g_lds_max;
@@ -836,8 +666,6 @@ static int choose_rtiow_variant(const rl_scene *scene, const rl_rtiow_camera *ca
   if (variant == 1033 && (general || !fits_fast || want_stats)) variant = 0;  // cooperative kernel: the fast structure's scenes, counter-free renders
   if (variant == 1027 && (general || !fits_compact)) variant = 0;
   if (variant == 1025 && (general || !fits_ops)) variant = 0;
-  if (variant == 7 && (general || (size_t)8 * 1024 * sizeof(unsigned long long) + scene_bytes > g_lds_max)) variant = 0;  // two-context kernel needs the scene in LDS
-  if ((variant == 5 || variant == 6) && (general || (size_t)(variant == 5 ? 512 : 256) * 192 + scene_bytes > g_lds_max)) variant = 0;  // pool kernel needs the scene in LDS
   if (variant == 0 && !general) {
     // automatic: 4 waves per SIMD (1024 lanes per CU, 128 KB of ChaCha rings) with, in LDS next to the rings, the fast tree / the
     // guarded compact ops / the linked ops — whichever fits first — and otherwise the whole scene read through L2
@@ -850,7 +678,7 @@ static int choose_rtiow_variant(const rl_scene *scene, const rl_rtiow_camera *ca
   }
   // 1029 keeps a path's remaining depth in 22 bits (rl_rtiow_wave.h, the self-test skip): deeper paths take the next layout that fits
   if (variant == 1029 && cam->max_depth > FAST_DEPTH_MASK) variant = fits_compact ? 1027 : fits_ops ? 1025 : 1024;
-  out.variant = variant, out.general = general, out.compact_bytes = compact_bytes, out.fast_bytes = fast_bytes, out.scene_bytes = scene_bytes, out.fits_fast = fits_fast;
+  out.variant = variant, out.general = general, out.compact_bytes = compact_bytes, out.fast_bytes = fast_bytes, out.fits_fast = fits_fast;
   return RL_OK;
 }
 
@@ -885,7 +713,6 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
                         hipStream_t stream, bool want_stats) {
   const RtiowProgram &rt = scene->rt();
   const HostRtiow &H = *scene->hrt;
-  (void)H;  // (experimental builds read more of it)
   uint32_t H_ = cam->image_height, W = cam->image_width;
   uint32_t nrows = row_first < H_ ? (H_ - row_first + row_step - 1) / row_step : 0;
   RtiowParams P;
@@ -905,9 +732,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     P.work_counter = scene->d_progress;
     HIP_TRY(hipMemsetAsync(scene->d_progress, 0, 8, stream));
   }
-  size_t scene_bytes = (size_t)P.n_ops * sizeof(DevOp) + (size_t)P.n_spheres * sizeof(DevSphere);
-  auto launch = [&](auto kern, int nt, size_t rng_bytes, bool lds_scene) -> int {
-    size_t lds = rng_bytes + (lds_scene ? scene_bytes : 0);
+  auto launch = [&](auto kern, int nt, size_t lds) -> int {
     uint32_t blocks = (uint32_t)((slots + nt - 1) / nt);
     uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));  // persistent lanes: as many workgroups as stay resident
     if (per_cu < 1) per_cu = 1;
@@ -965,11 +790,6 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     if (mode == 2) {
       if (ensure_lds_attr((const void *)rtiow_coop_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
       hipLaunchKernelGGL((rtiow_coop_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-#ifdef RL_EXPERIMENTAL
-    } else if (mode == 1) {  // L2 boxes at the register budget of two waves per SIMD
-      if (ensure_lds_attr((const void *)rtiow_coop_kernel<NW, false, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_kernel<NW, false, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-#endif
     } else {
       if (ensure_lds_attr((const void *)rtiow_coop_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
       hipLaunchKernelGGL((rtiow_coop_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
@@ -990,17 +810,8 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
       constexpr int NT = 256;
       size_t rb = (size_t)8 * NT * sizeof(unsigned long long);
       // register budget of two waves per SIMD (256 registers instead of 256 + 151): cornell_smoke 309 -> 493 Mrays/s, final_scene 170 -> 219
-      // (three waves: 390 / 182).  RL_GENERAL_REGS=256|768 selects the others (experimental library).
-#ifdef RL_EXPERIMENTAL
-      if (g_sw.general_regs == 768) rc = want_stats ? launch(rtiow_general_kernel<NT, true, 768>, NT, rb, false) : launch(rtiow_general_kernel<NT, false, 768>, NT, rb, false);
-      else if (g_sw.general_regs == 256) rc = want_stats ? launch(rtiow_general_kernel<NT, true>, NT, rb, false) : launch(rtiow_general_kernel<NT, false>, NT, rb, false);
-      else
-#endif
-        rc = want_stats ? launch(rtiow_general_kernel<NT, true, 512>, NT, rb, false) : launch(rtiow_general_kernel<NT, false, 512>, NT, rb, false);
-#ifdef RL_EXPERIMENTAL
-    } else if (variant == 1035) {
-      rc = render_wfg(scene, P, nrows, stream, rt.has_noise || rt.has_sphere_uv);
-#endif
+      // (three waves: 390 / 182).
+      rc = want_stats ? launch(rtiow_general_kernel<NT, true, 512>, NT, rb) : launch(rtiow_general_kernel<NT, false, 512>, NT, rb);
     } else if (variant == 1031) {  // rings + the traversal stacks in LDS
       // four steps per scheduling round (a step is an Infinity Cache / L2 round trip here, not an LDS one: lanes that fall out of TRAV
       // should not wait 24 of them): cfg 5 +6.6 %, cfg 4 +0.7 % against the sphere kernel's 24
@@ -1018,84 +829,37 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
         constexpr int NT = 256, SD = 40;
         size_t rb = fastg_lds(NT, SD);
         if (rb < 90000) rb = 90000;  // one workgroup per CU
-        rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, true, false, true>, NT, rb);
+        rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, true, true>, NT, rb);
       } else if (media) {  // several stages (media, unbounded Planes): the boundary walks and the Isotropic phase function need the 256-register budget
         constexpr int NT = 512, SD = 40;
         size_t rb = fastg_lds(NT, SD);
-        rc = trans ? launch_ptr(rtiow_fast_general_kernel<NT, SD, true, false, true>, NT, rb) : launch_ptr(rtiow_fast_general_kernel<NT, SD, false, false, true>, NT, rb);
+        rc = trans ? launch_ptr(rtiow_fast_general_kernel<NT, SD, true, true>, NT, rb) : launch_ptr(rtiow_fast_general_kernel<NT, SD, false, true>, NT, rb);
       } else if (trans) {  // 512 lanes per CU (the transcendental texture code needs 256 VGPRs), 40-entry stacks
         constexpr int NT = 512, SD = 40;
         size_t rb = fastg_lds(NT, SD);
         rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, true>, NT, rb);
-#ifdef RL_EXPERIMENTAL
-      } else if (g_sw.fastg512) {
-        constexpr int NT = 512, SD = 40;
-        size_t rb = fastg_lds(NT, SD);
-        rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, false>, NT, rb);
-#endif
       } else {  // 768 lanes per CU (3 waves per SIMD hide more of the node-fetch latency), 20-entry stacks: 208 B of LDS per lane, and the
         // 4 KB that leaves of 160 KB hold the top 32 nodes of the tree (cfg 4 +1.1 %, cfg 5 +0.4 %; 128 nodes with 16-entry stacks: the same)
         constexpr int NT = 768, SD = 20;
         size_t rb = fastg_lds(NT, SD);
-#ifdef RL_EXPERIMENTAL  // eight-wide quantised nodes (FastNodeO): cow scene 6.1 -> 3.8 steps per ray but -3.5 %, cfg 5 16.5 -> 13.9 steps, +10 % LEAF visits, -15 %
-        if (!H.fg.onodes.empty() && g_sw.fastg_octo != 0) rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, false, true>, NT, rb);
-        else
-#endif
-          rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, false>, NT, rb);
+        rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, false>, NT, rb);
       }
     } else if (variant == 4) {
       // 512 lanes per CU (2 waves per SIMD): the kernel needs ~200 VGPRs (~260 with the sin / Perlin / acos / atan2 code of
       // scenes that have Noise textures or Image textures on spheres).  At 768 lanes (168 VGPRs) the spills land in the TRAV
-      // loop and cost 2.3x (measured, cfg 4: 1101 vs 465 Mrays/s; RL_GENERAL_NT=768 in the experimental library).
+      // loop and cost 2.3x (measured, cfg 4: 1101 vs 465 Mrays/s).
       bool trans = rt.has_noise || rt.has_sphere_uv;
       size_t rb = (size_t)16 * 512 * sizeof(unsigned long long);
       if (rt.has_media) {  // + the parked HitRecord of a medium scope: 96 B of LDS per lane
         size_t mb = (size_t)512 * (16 + MEDIA_SAVE_WORDS) * sizeof(unsigned long long);
-        if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<512, true, true, true>, 512, mb, false) : launch(rtiow_wave_general_kernel<512, true, false, true>, 512, mb, false);
-        else rc = want_stats ? launch(rtiow_wave_general_kernel<512, false, true, true>, 512, mb, false) : launch(rtiow_wave_general_kernel<512, false, false, true>, 512, mb, false);
-#ifdef RL_EXPERIMENTAL
-      } else if (g_sw.general_nt == 768) {
-        size_t rb7 = (size_t)16 * 768 * sizeof(unsigned long long);
-        if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<768, true, true>, 768, rb7, false) : launch(rtiow_wave_general_kernel<768, true, false>, 768, rb7, false);
-        else rc = want_stats ? launch(rtiow_wave_general_kernel<768, false, true>, 768, rb7, false) : launch(rtiow_wave_general_kernel<768, false, false>, 768, rb7, false);
-#endif
-      } else if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<512, true, true>, 512, rb, false) : launch(rtiow_wave_general_kernel<512, true, false>, 512, rb, false);
-      else rc = want_stats ? launch(rtiow_wave_general_kernel<512, false, true>, 512, rb, false) : launch(rtiow_wave_general_kernel<512, false, false>, 512, rb, false);
-#ifdef RL_EXPERIMENTAL
-    } else if (variant == 5) {
-      constexpr int NT = 512;
-      rc = want_stats ? launch(rtiow_pool_kernel<NT, true>, NT, (size_t)NT * 192, true) : launch(rtiow_pool_kernel<NT, false>, NT, (size_t)NT * 192, true);
-    } else if (variant == 7) {
-      constexpr int NT = 512;
-      size_t rb = (size_t)8 * 2 * NT * sizeof(unsigned long long);
-      rc = want_stats ? launch(rtiow_wave2_kernel<NT, true, true>, NT, rb, true) : launch(rtiow_wave2_kernel<NT, true, false>, NT, rb, true);
-    } else if (variant == 6) {
-      constexpr int NT = 256;
-      rc = want_stats ? launch(rtiow_pool_kernel<NT, true>, NT, (size_t)NT * 192, true) : launch(rtiow_pool_kernel<NT, false>, NT, (size_t)NT * 192, true);
-    } else if (variant == 1) {  // the first correct kernel: nested loops, exact divisions
-      constexpr int NT = 1024;
-      size_t rb = (size_t)8 * NT * sizeof(unsigned long long);
-      bool in_lds = rb + scene_bytes <= g_lds_max;
-      if (in_lds) rc = want_stats ? launch(rtiow_spheres_kernel<NT, true, true>, NT, rb, true) : launch(rtiow_spheres_kernel<NT, true, false>, NT, rb, true);
-      else rc = want_stats ? launch(rtiow_spheres_kernel<NT, false, true>, NT, rb, false) : launch(rtiow_spheres_kernel<NT, false, false>, NT, rb, false);
-#define RL_LAUNCH_WAVE(NT)                                                                                              \
-  {                                                                                                                     \
-    size_t rb = (size_t)16 * NT * sizeof(unsigned long long);                                                           \
-    bool in_lds = rb + scene_bytes <= g_lds_max;                                                                        \
-    if (in_lds) rc = want_stats ? launch(rtiow_wave_kernel<NT, 1, true>, NT, rb, true) : launch(rtiow_wave_kernel<NT, 1, false>, NT, rb, true); \
-    else rc = want_stats ? launch(rtiow_wave_kernel<NT, 0, true>, NT, rb, false) : launch(rtiow_wave_kernel<NT, 0, false>, NT, rb, false);   \
-  }
-    } else if (variant == 768) RL_LAUNCH_WAVE(768)
-    else if (variant == 256) RL_LAUNCH_WAVE(256)
-    else if (variant == 512) RL_LAUNCH_WAVE(512)
-#undef RL_LAUNCH_WAVE
-#else
-    }
-#endif
-    else if (variant == 1025) {  // 4 waves per SIMD: rings + linked ops in LDS, spheres read from L2
+        if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<512, true, true, true>, 512, mb) : launch(rtiow_wave_general_kernel<512, true, false, true>, 512, mb);
+        else rc = want_stats ? launch(rtiow_wave_general_kernel<512, false, true, true>, 512, mb) : launch(rtiow_wave_general_kernel<512, false, false, true>, 512, mb);
+      } else if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<512, true, true>, 512, rb) : launch(rtiow_wave_general_kernel<512, true, false>, 512, rb);
+      else rc = want_stats ? launch(rtiow_wave_general_kernel<512, false, true>, 512, rb) : launch(rtiow_wave_general_kernel<512, false, false>, 512, rb);
+    } else if (variant == 1025) {  // 4 waves per SIMD: rings + linked ops in LDS, spheres read from L2
       constexpr int NT = 1024;
       size_t rb = (size_t)16 * NT * sizeof(unsigned long long) + (size_t)P.n_ops * sizeof(DevOp);
-      rc = want_stats ? launch(rtiow_wave_kernel<NT, 2, true>, NT, rb, false) : launch(rtiow_wave_kernel<NT, 2, false>, NT, rb, false);
+      rc = want_stats ? launch(rtiow_wave_kernel<NT, 2, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 2, false>, NT, rb);
     } else if (variant == 1033) {  // A/B: EVERY pixel through the cooperative one-wave-per-pixel kernel (rl_rtiow_coop.h)
       rl_scene *ms = const_cast<rl_scene *>(scene);
       const size_t npix = (size_t)nrows * W;
@@ -1108,19 +872,18 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
       // leave a TRAV round when fewer than a quarter of the lanes it started with are still walking (the counting kernels: 3/8): with
       // pair nodes and inline misses the walks are short and uneven — +2.1 % (6596 -> 6734 Mrays/s; 24,2: 6740; 24,1: 6586; tools: RL_TUNE)
       if (!g_sw.tune_set) P.tune[1] = 4, P.tune[2] = 4;
-      if (steal) rc = launch(rtiow_wave_kernel<NT, 4, false, true>, NT, rb, false);
-#ifdef RL_EXPERIMENTAL  // <.., 4, true> only under rl_debug_fast_stats (tools/sched.py): scheduler occupancy of the fast kernel; its box / sphere counts are its own
-      else if (want_stats) rc = launch(rtiow_wave_kernel<NT, 4, true>, NT, rb, false);
-#endif
-      else rc = launch(rtiow_wave_kernel<NT, 4, false>, NT, rb, false);
+      if (steal) rc = launch(rtiow_wave_kernel<NT, 4, false, true>, NT, rb);
+      // counting only under rl_debug_fast_stats (verify build, tools/sched.py): scheduler occupancy of the fast kernel; its box / sphere counts are its own
+      else if (want_stats && FAST_STATS_KERNEL) rc = launch(rtiow_wave_kernel<NT, 4, FAST_STATS_KERNEL>, NT, rb);
+      else rc = launch(rtiow_wave_kernel<NT, 4, false>, NT, rb);
     } else if (variant == 1027) {  // 4 waves per SIMD: rings + compact guarded ops in LDS, spheres read from L2
       constexpr int NT = 1024;
       size_t rb = (size_t)16 * NT * sizeof(unsigned long long) + compact_bytes;
-      rc = want_stats ? launch(rtiow_wave_kernel<NT, 3, true>, NT, rb, false) : launch(rtiow_wave_kernel<NT, 3, false>, NT, rb, false);
+      rc = want_stats ? launch(rtiow_wave_kernel<NT, 3, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 3, false>, NT, rb);
     } else {  // 1024: everything through L2 (sphere-only worlds too large for LDS)
       constexpr int NT = 1024;
       size_t rb = (size_t)16 * NT * sizeof(unsigned long long);
-      rc = want_stats ? launch(rtiow_wave_kernel<NT, 0, true>, NT, rb, false) : launch(rtiow_wave_kernel<NT, 0, false>, NT, rb, false);
+      rc = want_stats ? launch(rtiow_wave_kernel<NT, 0, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 0, false>, NT, rb);
     }
     return rc;
   };
@@ -1132,14 +895,10 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
   // with their exact sums and ChaCha word positions: results are bit-identical to a single launch.
   const bool lpt_enabled = g_sw.lpt;
   const uint32_t lpt_first = 8;  // (round 3: 2 / 4 / 16 probe samples measure 6727 / 6752 / 6710 Mrays/s against 6711 — flat)
-  bool lpt = lpt_enabled && variant != 1035 && (variant >= 256 || variant == 4 || variant == 1031 || variant == 5 || variant == 6 || variant == 7) && cam->samples_per_pixel >= 64;
+  bool lpt = lpt_enabled && (variant >= 256 || variant == 4) && cam->samples_per_pixel >= 64;
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev0, stream));
   int rc = RL_OK;
-  if (variant == 3) {
-#ifdef RL_EXPERIMENTAL
-    rc = render_wavefront(scene, P, nrows, stream, want_stats);
-#endif
-  } else if (!lpt) rc = launch_variant();
+  if (!lpt) rc = launch_variant();
   else {
     rl_scene *ms = const_cast<rl_scene *>(scene);  // scratch buffers only; the scene program itself is immutable
     size_t npix = (size_t)nrows * W, ntiles = (size_t)(slots >> 6);
@@ -1168,19 +927,6 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
       P.steal_state = ms->d_steal_state, P.steal_n = ms->d_steal_n, P.steal_counter = (uint32_t *)(scene->d_scratch + 256);
       P.coop_leaf_boxes = scene->d_fast_leaf_boxes;
       steal = true;
-    }
-    if (variant == 1029) {
-      // latency modes (A/B only, default off): RL_THIN=<permille of the tiles> renders the most expensive tiles
-      // 64 >> RL_THIN_SHIFT pixels per wave, RL_PRIO=<permille> raises the issue priority of the waves that hold them.  Measured on the
-      // emulated 1/8 shard: 271 - 283 ms against 279 at best, slower when more than ~1 % of the tiles are thinned: the longest sample
-      // chain's time is per-ray LATENCY (9.6 us for a pixel alone on the GPU, tools/lone_ray.py), which neither shortens
-#ifdef RL_EXPERIMENTAL
-      P.thin_tiles = (uint32_t)((double)ntiles * g_sw.thin_permille / 1000.0);
-      P.thin_shift = (uint32_t)g_sw.thin_shift;
-      P.prio_tiles = (uint32_t)((double)ntiles * g_sw.prio_permille / 1000.0);  // A/B
-      uint64_t total = slots + (((uint64_t)P.thin_tiles * 64u) << P.thin_shift);
-      if (total >= 0xFFFF0000ull) P.thin_tiles = 0;
-#endif
     }
     rc = launch_variant();
   }
@@ -1214,7 +960,6 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
   // pixels x samples of parallelism), and the reference-order wave-scheduled general kernel for everything else (counting renders too)
   int variant = choice.variant;
   if (variant == 1033) variant = 1029;
-  if (variant == 1035) variant = 1031;
   if ((variant == 1029 && want_stats) || (variant != 1029 && variant != 1031)) variant = 4;
   const uint32_t S = cam->samples_per_pixel;
   const uint64_t n_vals = (uint64_t)nrows * W * 3u;
@@ -1741,13 +1486,7 @@ int rl_debug_set_status_gap(unsigned device_us, unsigned host_us) {
   g_status_gap_dev_us = std::min(device_us, 20000u), g_status_gap_host_us = std::min(host_us, 20000u);
   return RL_OK;
 }
-void rl_debug_fast_stats(int on) {  // the instrumented fast kernel <1024, 4, true> exists in the experimental library only
-#ifdef RL_EXPERIMENTAL
-  g_fast_debug_stats = on != 0;
-#else
-  (void)on;
-#endif
-}
+void rl_debug_fast_stats(int on) { g_fast_debug_stats = FAST_STATS_KERNEL && on != 0; }
 #ifdef RL_FASTG_VERIFY
 int rl_debug_fastg_verify(unsigned int *count, double *log768) {
   HIP_TRY(hipMemcpyFromSymbol(count, HIP_SYMBOL(rl::g_vcount), 4));
@@ -1761,13 +1500,6 @@ int rl_debug_fastg_counts(unsigned long long *out4) {
 #endif
 // rays of the render rl_render_status last waited for that the fast traversal re-traced in the reference's order
 unsigned long long rl_debug_slow_traces(void) { return g_last_slow_traces; }
-int rl_debug_has_experimental(void) {
-#ifdef RL_EXPERIMENTAL
-  return 1;
-#else
-  return 0;
-#endif
-}
 
 // Not part of the ABI (tests): the device allocations the library owns right now, out[0] their number, out[1] their bytes (rl_devbuf.h)
 void rl_debug_live_buffers(unsigned long long out[2]) { out[0] = rl::g_live_buffers.load(), out[1] = rl::g_live_bytes.load(); }
@@ -2038,12 +1770,7 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
     F.n_tris = P.n_tris, F.max_reflection_depth = rc_.max_reflection_depth;
     // register budget of three waves per SIMD (168 VGPRs; ~165 of the kernel's binary64 temporaries then live in scratch, at points that
     // run once per ray): measured 13.3 / 14.0 / 19.2 ms for 3 / 2 / 1 waves on the mirror scene at 1080p, 2.7 / 2.9 / 4.2 ms on the teapot
-    // forced through this kernel.  RL_RTC_FULL_REGS=256|512 selects the other budgets (A/B).
-#ifdef RL_EXPERIMENTAL  // (the other register budgets exist for the frame kernels only: a list call takes the product flavour)
-    if (!list && g_sw.rtc_full_regs == 512) { blocks = grid_for((const void *)rtc_full_kernel<NT, 512>, 0); hipLaunchKernelGGL((rtc_full_kernel<NT, 512>), dim3(blocks), dim3(NT), 0, stream, F); }
-    else if (!list && g_sw.rtc_full_regs == 256) { blocks = grid_for((const void *)rtc_full_kernel<NT, 256>, 0); hipLaunchKernelGGL((rtc_full_kernel<NT, 256>), dim3(blocks), dim3(NT), 0, stream, F); }
-    else
-#endif
+    // forced through this kernel.
     if (list) {
       blocks = grid_for((const void *)rtc_full_pixels_kernel<NT, 768>, 0);
       hipLaunchKernelGGL((rtc_full_pixels_kernel<NT, 768>), dim3(blocks), dim3(NT), 0, stream, F, d_xs, d_ys, n_list);
@@ -2053,14 +1780,6 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
     }
   // (241 VGPRs -> two waves per SIMD.  Measured in round 3 with the register budgets of three / four waves (68 / 128 spilled VGPRs): AA 8 19.5 -> 21.1 /
   // 22.5 ms, AA 1 0.547 -> 0.518 / 0.517 ms: the binary64 Moeller-Trumbore + Phong temporaries in scratch cost more than the extra waves hide.)
-#ifdef RL_EXPERIMENTAL
-  } else if (!list && lds_scene && g_sw.rtc_regs == 768) {
-    blocks = grid_for((const void *)rtc_kernel<NT, true, 768>, lds);
-    hipLaunchKernelGGL((rtc_kernel<NT, true, 768>), dim3(blocks), dim3(NT), lds, stream, P);
-  } else if (!list && lds_scene && g_sw.rtc_regs == 1024) {
-    blocks = grid_for((const void *)rtc_kernel<NT, true, 1024>, lds);
-    hipLaunchKernelGGL((rtc_kernel<NT, true, 1024>), dim3(blocks), dim3(NT), lds, stream, P);
-#endif
   } else if (list && lds_scene) {
     blocks = grid_for((const void *)rtc_pixels_kernel<NT, true>, lds);
     hipLaunchKernelGGL((rtc_pixels_kernel<NT, true>), dim3(blocks), dim3(NT), lds, stream, P, d_xs, d_ys, n_list);

@@ -246,20 +246,18 @@ __device__ __forceinline__ double rtc_traverse(const RtcParams &P, const DevOp *
   return atten;
 }
 
-// REGS_FOR: the workgroup size the register budget is computed for (NT: one wave per SIMD and up to 512 registers, 2 NT / 3 NT / 4 NT: the
-// budget of two / three / four waves per SIMD)
 // LIST (rl_rtc_render_pixels*): the grid-stride index picks element idx of the caller's pixel list, (xs[idx], ys[idx]) of the
 // whole frame, instead of pixel (idx / W, idx % W) of the shard; the colour goes to out[idx] either way.  An element outside the image is
 // written as zeros and traces nothing.  Everything after ray generation is the frame's code.
-template <int NT, bool LDS_SCENE, int REGS_FOR = NT>
-__global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtc_kernel(RtcParams P) {
+template <int NT, bool LDS_SCENE>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtc_kernel(RtcParams P) {
   constexpr bool LIST = false;
   const uint32_t *const xs = nullptr, *const ys = nullptr;
   const uint64_t n_list = 0;
 #include "rl_rtc_render_body.inc"
 }
-template <int NT, bool LDS_SCENE, int REGS_FOR = NT>
-__global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtc_pixels_kernel(RtcParams P, const uint32_t *xs, const uint32_t *ys, uint64_t n_list) {
+template <int NT, bool LDS_SCENE>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtc_pixels_kernel(RtcParams P, const uint32_t *xs, const uint32_t *ys, uint64_t n_list) {
   constexpr bool LIST = true;
 #include "rl_rtc_render_body.inc"
 }

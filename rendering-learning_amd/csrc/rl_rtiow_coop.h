@@ -256,7 +256,7 @@ __device__ __forceinline__ void rtiow_coop_body(const RtiowParams &P, const floa
           color = color + thr * background;
           break;
         }
-        // ---- the HitRecord of the winner and Material::scatter, as in rl_rtiow_kernel.h (same arithmetic as at test time)
+        // ---- the HitRecord of the winner and Material::scatter, as in the wave kernel's SHADE (same arithmetic as at test time)
         uint32_t si = hit_prim & SPH_INDEX;
         const DevSphere &s = spheres[si];
         D3 c0v = ld3(s.c0);

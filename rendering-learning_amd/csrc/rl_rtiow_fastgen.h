@@ -165,7 +165,6 @@ __device__ __forceinline__ void fastg_sphere_hit(const DevSphere &s, uint32_t pa
 // and spheres behind 4 MB of L2 per XCD) +6 ... 8 %.  Also measured, and dropped: a 10-bit lower bound of the entry distance in every stack
 // entry, so that pop() can skip entries that have fallen behind the closest hit (cfg 4 -10 %, cfg 5 -6 %: the skipped visits are worth less
 // than the dependent LDS round trips of the skipping loop).
-// OCTO: the eight-wide nodes with quantised boxes (FastNodeO) instead of the four-wide ones (FastNodeQ)
 // MEDIA (round 3): scenes with ConstantMedium objects (constant_medium.rs:27-80, deterministic variant: include/rl_render.h rl_medium).  The
 // reference evaluates a medium where its fold reaches it, with ray_t.max = the closest hit found by everything BEFORE it in the program,
 // and draws the free path from the RNG only if the ray's stretch inside the boundary, clamped to that closest hit, is non-empty.  So the
@@ -175,14 +174,14 @@ __device__ __forceinline__ void fastg_sphere_hit(const DevSphere &s, uint32_t pa
 // never decide whether it draws: a ray that misses a box inside [t_min, closest] has an empty stretch inside the boundary, too.)  An
 // order-sensitive ray rewinds the ring to the word position the ray started at and is re-traced by the reference's fold WITH its media.
 // INDEP: the sample-parallel mode, as in rtiow_wave_indep_kernel (rl_rtiow_wave.h; the body is included into both kernels for the same reason)
-template <int NT, int SD, bool TRANS, bool OCTO = false, bool MEDIA = false>
+template <int NT, int SD, bool TRANS, bool MEDIA = false>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_kernel(const RtiowParams *__restrict__ Pp) {
   constexpr bool INDEP = false, RAYS = false, PIXELS = false;
 #include "rl_rtiow_fastgen_body.inc"
 }
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_indep_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = true, OCTO = false, RAYS = false, PIXELS = false;
+  constexpr bool INDEP = true, RAYS = false, PIXELS = false;
 #include "rl_rtiow_fastgen_body.inc"
 }
 // RAYS (rl_rtiow_ray_color_rays*): Camera::ray_color for a buffer of rays, each with its own RNG cursor.  GEN claims rays
@@ -190,14 +189,14 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_indep_k
 // treatment of start_ray, the exact re-trace — is the body's own.  P.cam carries the call's background and max_depth, P.key its seed.
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_rays_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = false, OCTO = false, RAYS = true, PIXELS = false;
+  constexpr bool INDEP = false, RAYS = true, PIXELS = false;
 #include "rl_rtiow_fastgen_body.inc"
 }
 // PIXELS (rl_rtiow_render_pixels*): GEN claims elements of the caller's (x, y) list instead of tile slots and stores a pixel's
 // sums at its element index; everything behind the claim is the body's own, so a listed pixel is the frame's pixel bit for bit.
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_pixels_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = false, OCTO = false, RAYS = false, PIXELS = true;
+  constexpr bool INDEP = false, RAYS = false, PIXELS = true;
 #include "rl_rtiow_fastgen_body.inc"
 }
 

@@ -3,10 +3,11 @@
 // aabb.rs:123-152), the materials (material.rs) and textures (texture.rs), ChaCha8 stream RNG
 // (rand_chacha 0.3.1 as used at camera.rs:161-170).
 //
+// This header holds what every RTIOW kernel shares: the parameter block, the ChaCha8 block function and
+// per-lane RNG, the exact AABB and sphere tests, Perlin noise and the textures.  The kernels themselves are
+// in rl_rtiow_general.h, rl_rtiow_wave.h, rl_rtiow_wave_general.h, rl_rtiow_fastgen.h and rl_rtiow_coop.h.
 // Parallel unit = the pixel: samples of one pixel are sequentially dependent (set_stream keeps the
-// ChaCha word position), pixels are independent.  One lane owns one pixel at a time and claims the
-// next from a global counter when done (persistent lanes).  The scene program (rl_program.h) and the
-// sphere table are staged in LDS once per workgroup; traversal is stackless.
+// ChaCha word position), pixels are independent.
 #pragma once
 #ifndef RL_KERNEL_ALIGN
 // Every big kernel starts on a 64 KB boundary of the code object.  Measured (round 3): the stealing instantiation of rtiow_wave_kernel (77 KB of
@@ -45,10 +46,6 @@ struct RtiowParams {
   const uint32_t *fg_material;   // [item] material index
   const FastItem *fg_items;
   uint32_t fg_root;
-#ifdef RL_EXPERIMENTAL
-  const FastNodeO *fg_onodes;  // eight-wide quantised form (FastNodeO) and its root entry (A/B)
-  uint32_t fg_oroot;
-#endif
   float fg_center[3], fg_rsafe2;  // r_safe squared
   float fg_radius, fg_pad_k;      // far-origin rays: box growth = fg_pad_k * (distance + fg_radius)^2 (rl_rtiow_fastgen.h start_ray)
   rl_rtiow_camera cam;
@@ -64,14 +61,11 @@ struct RtiowParams {
   uint32_t *tile_cost;                         // per-tile ray count accumulated at pixel end, or null
   double k8u;                 // 8 * 2^-53, passed as a kernel argument so it lives in SGPRs (one v_fma instead of v_mov + v_fmac with a literal)
   uint32_t tune[4];           // wave kernel: [0] max TRAV steps per scheduling round, [1] leave-TRAV population floor in 1/16ths
-  uint32_t thin_tiles;        // fast wave kernel, resume launch: the first thin_tiles tiles of tile_order are handed out 64 >> thin_shift pixels per wave
-  uint32_t thin_shift;        // 2 (16 pixels per wave) .. 6 (one pixel per wave)
-  uint32_t prio_tiles;
   // work stealing on small shards (rl_rtiow_wave.h STEAL instantiation): a wave whose lanes have all run out of pixels takes over pixels
   // other lanes are still rendering, at a sample boundary, and continues them with the cooperative one-wave-per-pixel body.
   // steal_state[pix]: 0 queued / running, 1 take-over requested, 2 released (P.out, pos_state and steal_n hold the state), 3 finished
   uint32_t *steal_state, *steal_n, *steal_counter;
-  const float *coop_leaf_boxes;        // fast wave kernel, resume launch (A/B): a wave holding a pixel of the first prio_tiles tiles runs at s_setprio 3
+  const float *coop_leaf_boxes;  // ... the spheres' padded leaf boxes, which that body scans (rl_rtiow_coop.h)
   uint32_t *pix_rays;         // debug (tools/): per-pixel ray counts, accumulated at pixel end by the counting wave kernel, or null
   unsigned long long *stats;  // [0]=rays [1]=node_tests [2]=sphere_tests [3]=planar [4]=instance [5]=rng_words [6]=flagged
   // (appended last: the by-value kernels' kernarg offsets of everything above stay where they were)
@@ -371,199 +365,6 @@ __device__ __forceinline__ D3 texture_value(const RtiowParams &P, uint32_t tex, 
     return D3{(double)px[0], (double)px[1], (double)px[2]};
   }
   return D3{0.0, 0.0, 0.0};
-}
-
-struct Counters {
-  unsigned long long rays, nodes, spheres, planars, instances, flagged;
-};
-
-// ================================================================= the kernel
-// LDS_SCENE: ops + spheres staged in LDS (they fit); otherwise read through L1/L2 from HBM.
-template <int NT, bool LDS_SCENE, bool STATS>
-__global__ void __launch_bounds__(NT) rtiow_spheres_kernel(RtiowParams P) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int tid = threadIdx.x;
-  unsigned long long *s_rng = (unsigned long long *)smem;  // [8][NT]
-  const DevOp *ops = P.ops;
-  const DevSphere *spheres = P.spheres;
-  if (LDS_SCENE) {
-    DevOp *s_ops = (DevOp *)(smem + (size_t)8 * NT * sizeof(unsigned long long));
-    DevSphere *s_sph = (DevSphere *)(s_ops + P.n_ops);
-    // 16-byte cooperative copy
-    const uint4 *g = (const uint4 *)P.ops;
-    uint4 *l = (uint4 *)s_ops;
-    for (uint32_t i = tid; i < P.n_ops * 4u; i += NT) l[i] = g[i];
-    g = (const uint4 *)P.spheres;
-    l = (uint4 *)s_sph;
-    for (uint32_t i = tid; i < P.n_spheres * 4u; i += NT) l[i] = g[i];
-    __syncthreads();
-    ops = s_ops;
-    spheres = s_sph;
-  }
-  RngCtx<NT> rc{P.key, s_rng, tid};
-  const rl_rtiow_camera &cam = P.cam;
-  const uint32_t W = cam.image_width;
-  const uint64_t WH = (uint64_t)cam.image_width * (uint64_t)cam.image_height;
-  const D3 p00 = ld3(cam.pixel_00), du = ld3(cam.pixel_du), dv = ld3(cam.pixel_dv);
-  const D3 lookfrom = ld3(cam.lookfrom), ddu = ld3(cam.defocus_disk_u), ddv = ld3(cam.defocus_disk_v);
-  const D3 background = ld3(cam.background);
-  const double INF = __longlong_as_double(0x7FF0000000000000ll);
-  Counters cnt{0, 0, 0, 0, 0, 0};
-  unsigned long long words = 0;
-
-  for (;;) {
-    uint32_t slot = wave_claim(P.work_counter);
-    if (slot >= P.n_slots) break;
-    // 8x8 tiles over (x, virtual row)
-    uint32_t tile = slot >> 6, in = slot & 63u;
-    uint32_t x = (tile % P.tiles_x) * 8u + (in & 7u);
-    uint32_t r = (tile / P.tiles_x) * 8u + (in >> 3);
-    if (x >= W || r >= P.nrows) continue;
-    uint32_t y = P.row_first + r * P.row_step;
-
-    Rng rng{0ull, 0u, 0xFFFFFFFFu};
-    D3 sum = d3(0.0, 0.0, 0.0);
-    for (uint32_t n = 0; n < cam.samples_per_pixel; n++) {
-      uint64_t sample_index = (uint64_t)n + P.first_sample;
-      rng.stream = sample_index * WH + (uint64_t)x * (uint64_t)W + (uint64_t)y;  // camera.rs:167-169 (x*W, sic)
-      rng.buf_ctr = 0xFFFFFFFFu;                                                   // new stream: block must be regenerated
-      // get_ray camera.rs:203-216
-      D3 pixel_center = (p00 + du * (double)x) + dv * (double)y;
-      double px = -0.5 + rc.gen_f64(rng);
-      double py = -0.5 + rc.gen_f64(rng);
-      D3 pixel_sample = pixel_center + (du * px + dv * py);
-      D3 o;
-      if (cam.defocus_angle <= 0.0) o = lookfrom;
-      else {
-        double a, b;
-        rc.unit_disc(rng, a, b);
-        o = (lookfrom + ddu * a) + ddv * b;
-      }
-      D3 d = pixel_sample - o;
-      double time = rc.gen_f64(rng);
-
-      // ray_color camera.rs:232-260 in throughput form (colour-only reassociation, <= a few ulps)
-      D3 thr = d3(1.0, 1.0, 1.0);
-      D3 color = d3(0.0, 0.0, 0.0);
-      for (uint32_t depth = cam.max_depth; depth > 0; depth--) {
-        cnt.rays++;
-        // ---- world.hit(r, [1e-10, inf]) : threaded traversal in the reference's DFS order
-        Hit h{INF, NONE};
-        uint32_t pc = 0;
-        for (;;) {
-          const DevOp &op = ops[pc];
-          uint32_t code = op.code & 0xFFu;
-          if (code == OP_END) break;
-          if (code == OP_SPHERE) {
-            if (STATS) cnt.spheres++;
-            uint32_t a = op.a;
-            if (sphere_hit(spheres[a & SPH_INDEX], a, o, d, time, 1e-10, h)) cnt.flagged++;
-            pc++;
-            continue;
-          }
-          // OP_BOX / OP_BOX_SPH
-          if (STATS) cnt.nodes++;
-          uint32_t skip = op.skip;
-          if (!aabb_hit(op.box, o, d, 1e-10, h.t)) {
-            pc = skip;
-            continue;
-          }
-          if (code == OP_BOX) {
-            pc++;
-            continue;
-          }
-          uint32_t a = op.a, b = op.b;
-          if (STATS) cnt.spheres++;
-          if (sphere_hit(spheres[a & SPH_INDEX], a, o, d, time, 1e-10, h)) cnt.flagged++;
-          if (b != NONE) {
-            if (STATS) cnt.spheres++;
-            if (sphere_hit(spheres[b & SPH_INDEX], b, o, d, time, 1e-10, h)) cnt.flagged++;
-          }
-          pc = skip;
-        }
-        if (h.prim == NONE) {  // miss -> background
-          color = color + thr * background;
-          break;
-        }
-        // rebuild the HitRecord of the winning sphere (same arithmetic as at test time)
-        uint32_t si = h.prim & SPH_INDEX;
-        const DevSphere &s = spheres[si];
-        D3 c0 = ld3(s.c0);
-        D3 center = (h.prim & SPH_MOVING) ? c0 + ld3(s.dc) * time : c0;
-        D3 p = o + d * h.t;
-        D3 outward = (p - center) * s.inv_r;
-        bool front = dot(d, outward) <= 0.0;  // hittable/mod.rs:32-38
-        D3 normal = front ? outward : -outward;
-        const DevMaterial &m = P.materials[P.sphere_material[si]];
-        uint32_t kind = m.kind;
-        D3 nd;
-        if (kind == RL_MAT_LAMBERTIAN) {  // material.rs:74-92
-          D3 dir = normal + rc.unit_sphere(rng);
-          bool near_zero = approx_eq_eps(dir.x, 0.0, 1e-8) && approx_eq_eps(dir.y, 0.0, 1e-8) && approx_eq_eps(dir.z, 0.0, 1e-8);
-          nd = near_zero ? normal : dir;
-          thr = thr * texture_value(P, m.texture, 0.0, 0.0, p);
-        } else if (kind == RL_MAT_METAL) {  // material.rs:105-122
-          D3 reflected = d - normal * (2.0 * dot(d, normal));
-          nd = normalize(reflected) + rc.unit_sphere(rng) * m.fuzz;
-          if (!(dot(nd, normal) > 0.0)) break;  // absorbed: emitted (0) only
-          thr = thr * ld3(m.albedo);
-        } else if (kind == RL_MAT_DIELECTRIC) {  // material.rs:139-165
-          double ri = front ? 1.0 / m.ior : m.ior;
-          double m2 = len2(d);
-          D3 ud;
-          if (approx_eq_eps(m2, 0.0, 1e-16)) {  // "How did the incident ray have magnitude 0?"
-            cnt.flagged++;
-            ud = d;
-          } else
-            ud = normalize(d);
-          double cos_theta = fmin(dot(-ud, normal), 1.0);
-          double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
-          bool reflect = ri * sin_theta > 1.0;
-          if (!reflect) {  // Schlick, material.rs:173-176; short-circuit: the draw happens only here
-            double q = (1.0 - ri) / (1.0 + ri);
-            double r0 = q * q;
-            double xx = 1.0 - cos_theta;
-            double x2 = xx * xx;
-            double refl = r0 + (1.0 - r0) * (xx * (x2 * x2));
-            reflect = refl > rc.gen_f64(rng);
-          }
-          if (reflect) nd = ud - normal * (2.0 * dot(ud, normal));
-          else {  // vec3.rs:224-230
-            D3 perp = (ud + normal * cos_theta) * ri;
-            D3 par = normal * (-sqrt(fabs(1.0 - len2(perp))));
-            nd = perp + par;
-          }
-          // attenuation (1,1,1): thr unchanged (x * 1.0 == x)
-        } else if (kind == RL_MAT_DIFFUSE_LIGHT) {  // material.rs:182-195: emitted, no scatter
-          color = color + thr * texture_value(P, m.texture, 0.0, 0.0, p);
-          break;
-        } else {  // Flat
-          break;
-        }
-        o = p;
-        d = nd;
-      }
-      sum = sum + color;  // camera.rs:174: sequential fold in sample order
-    }
-    words += rng.pos;
-    double *outp = P.out + ((size_t)r * W + x) * 3;
-    outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
-  }
-
-  // counters: one atomic per wave per counter
-  unsigned long long v;
-  v = wave_sum(cnt.rays);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[0], v);
-  v = wave_sum(cnt.flagged);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
-  if (STATS) {
-    v = wave_sum(cnt.nodes);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[1], v);
-    v = wave_sum(cnt.spheres);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
-    v = wave_sum(words);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[5], v);
-  }
 }
 
 }  // namespace rl

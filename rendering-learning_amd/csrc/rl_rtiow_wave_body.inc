@@ -84,7 +84,7 @@
   uint32_t px = 0, pr = 0, n = spp;  // n == spp: no pixel owned yet
   uint32_t n_end = spp;              // INDEP: end of the lane's sample group
   uint32_t ptile = 0, pix_rays = 0;
-  bool have_pixel = false, thin_pix = false;
+  bool have_pixel = false;
   D3 sum = d3(0.0, 0.0, 0.0);
   D3 o = d3(0.0, 0.0, 0.0), d = d3(0.0, 0.0, 1.0), thr = d3(1.0, 1.0, 1.0);
   RayAux ra = ray_aux(o, d);
@@ -279,12 +279,6 @@
     int n_leaf = __popcll(__ballot(state == ST_LEAF));
     int n_shade2 = SPLIT_SHADE && LDS_SCENE == 4 ? __popcll(__ballot(state == ST_SHADE2)) : 0;
     int n_leaf2 = SPLIT_LEAF && LDS_SCENE == 4 ? __popcll(__ballot(state == ST_LEAF2)) : 0;
-    if (LATENCY_MODES && LDS_SCENE == 4 && P.thin_tiles != 0u) {  // parked lanes wake up when no lane of the wave holds a thin pixel any more
-      if (__ballot(state == ST_PARK) != 0ull && __ballot(have_pixel && thin_pix) == 0ull) {
-        if (state == ST_PARK) state = ST_GEN;
-        n_gen = __popcll(__ballot(state == ST_GEN));
-      }
-    }
     if ((n_trav | n_shade | n_fill | n_gen | n_leaf | n_shade2 | n_leaf2) == 0) break;
     uint32_t pick = ST_TRAV;
     // (A/B, RL_TUNE third field w: TRAV competes with n_trav * w / 4 — a TRAV step costs a tenth of a LEAF or SHADE block, so running it for
@@ -484,27 +478,7 @@
             have_pixel = false;
           }
           uint32_t slot = wave_claim(P.work_counter);
-          // THIN tiles (latency mode, LDS_SCENE = 4, cost-sorted resume launch of a small shard): the P.thin_tiles most expensive tiles
-          // hand out their 64 pixels over 1 << thin_shift wave-claims of 64 slots (16 … 1 pixels each); a lane that draws an empty slot
-          // parks until its wave's thin pixels are done.  A wave then serialises 16 sample chains instead of 64: the longest chains
-          // of the frame (the shard's critical path, DESIGN.md §6) see a quarter of the state divergence.
-          const uint32_t sh = P.thin_shift;  // a thin tile's 64 pixels go out over 1 << sh wave-claims, 64 >> sh pixels each
-          const uint32_t thin_slots = LATENCY_MODES && LDS_SCENE == 4 ? (P.thin_tiles * 64u) << sh : 0u;
-          thin_pix = false;
-          bool parked = false;
-          if (slot < thin_slots) {
-            const uint32_t sub = slot & ((64u << sh) - 1u), l = sub & 63u;
-            parked = (l & ((1u << sh) - 1u)) != 0u;
-            thin_pix = !parked;
-            slot = (slot >> (6u + sh)) * 64u + (sub >> 6) * (64u >> sh) + (l >> sh);
-          } else if (LATENCY_MODES) {
-            slot -= thin_slots - (LDS_SCENE == 4 ? P.thin_tiles * 64u : 0u);
-            if (LDS_SCENE == 4 && P.prio_tiles != 0u) thin_pix = (slot >> 6) < P.prio_tiles;
-          }
-          if (parked) {
-            state = ST_PARK;
-            active = false;
-          } else if (slot >= P.n_slots) {
+          if (slot >= P.n_slots) {
             state = ST_DONE;
             active = false;
           } else {
@@ -590,10 +564,6 @@
           // the pixel's entry word: read and used up here, so that it is not held across blocks (the kernel sits at 128 VGPRs)
           start_ray(LDS_SCENE == 4 && P.pixel_entry ? P.pixel_entry[(size_t)pr * W + px] : fast_root_word);
         }
-      }
-      if (LATENCY_MODES && LDS_SCENE == 4 && P.prio_tiles != 0u) {  // A/B: issue priority for the waves that hold the frame's longest sample chains
-        if (__ballot(have_pixel && thin_pix) != 0ull) __builtin_amdgcn_s_setprio(3);
-        else __builtin_amdgcn_s_setprio(0);
       }
     } else if (SPLIT_SHADE && pick == ST_SHADE2) {
       if (state == ST_SHADE2) shade(std::integral_constant<int, 2>{});

@@ -43,11 +43,6 @@ struct HostRtc {
   RtcProgram rc;
   std::vector<RtcGuard> guards;
 };
-// wavefront (v3) work buffers of the experimental library: per-pixel state, ray and hit records, queues, control words
-struct ExpBuffers {
-  DevBuf<unsigned char> wf_pix, wf_ray, wf_hit;
-  DevBuf<uint32_t> wf_qtrav, wf_qgen, wf_ctl;
-};
 
 }  // namespace rl
 
@@ -73,7 +68,6 @@ struct rl_scene {
   rl::DevBuf<uint32_t> d_coop_pixels;  // cooperative kernel: pixel list (scratch, grown on demand)
   rl::DevBuf<uint32_t> d_steal_state, d_steal_n;  // work stealing on small shards (RtiowParams::steal_state)
   rl::DevBuf<rl::FastNodeQ> d_fg_nodes;
-  rl::DevBuf<rl::FastNodeO> d_fg_onodes;
   rl::DevBuf<uint32_t> d_fg_seg_roots;
   rl::DevBuf<rl::FastMedium> d_fg_media;
   rl::DevBuf<rl::FastItem> d_fg_items;
@@ -128,10 +122,6 @@ struct rl_scene {
   rl::DevBuf<double> d_shard;
   rl::Event ev_gather_read;  // replica 0: recorded behind the de-interleave kernel that reads the gather slots
   bool ev_gather_read_valid = false;
-  // wavefront form (rl_rtiow_wfg.h): per-pixel records, ray records, the two queues, control words, the polled word in pinned memory
-  rl::DevBuf<unsigned char> d_wfg_pix, d_wfg_ray;
-  rl::DevBuf<uint32_t> d_wfg_q0, d_wfg_q1, d_wfg_qs, d_wfg_ctl;
-  rl::PinnedBuf<uint32_t> h_wfg;
   // rl_rtiow_render_progress (opt-in: its first call switches it on for the renders that follow): the kernels' work counters then live
   // in two words of pinned HOST memory the device reaches over PCIe — [0] the first (or only) launch of a render, [1] the cost-sorted
   // resume launch — so that the host reads them with plain loads while the kernels run; `progress_total` = slots of the render enqueued last
@@ -143,7 +133,6 @@ struct rl_scene {
   unsigned params_slot = 0;
   rl::DevBuf<uint32_t> d_pix_rays;  // debug (tools/): per-pixel ray counts of the last counting render
   rl::DevBuf<double> d_indep;       // sample-parallel mode: the pass buffer [samples of a pass][shard pixels][3] (rl_rtiow_render_independent*)
-  rl::ExpBuffers exp;               // experimental kernels' work buffers (used by RL_EXPERIMENTAL builds only)
   // per-scene scratch: [0] work counter (u32), [64..] 8 x u64 stats, [128..] scheduler debug counters.  Declared LAST, so released FIRST:
   // every scene has it, and its hipFree waits for the device's work in flight before the events and the pinned memory above go.
   rl::DevBuf<unsigned char> d_scratch;

@@ -9,7 +9,7 @@ import pytest
 
 import os
 
-# librl_host.so is linked against the PRODUCT library; with RL_RENDER_LIB pointing the Python binding at another build (experimental /
+# librl_host.so is linked against the PRODUCT library; with RL_RENDER_LIB pointing the Python binding at another build (the
 # verification library) the process would hold two copies of the C ABI, one of them uninitialised: these tests belong to the product build
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(bool(os.environ.get("RL_RENDER_LIB")), reason="the C++ host mirror links librl_render.so (the product library)")]
 

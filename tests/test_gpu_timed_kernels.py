@@ -58,6 +58,27 @@ def test_timed_sphere_kernels_equal_counting_kernels_and_oracle(rl, oracle, vari
         rl.api.set_rtiow_variant(0)
 
 
+def test_retired_variants_are_refused_and_the_automatic_choice_is_untouched(rl):
+    """The kernel variants that were measured, lost and removed answer RL_E_UNSUPPORTED instead of falling through to
+    the automatic choice, and asking for one leaves nothing behind: after the reset the frame has the bits it had before."""
+    world = rl.World.golden_test_scene()
+    p = world.params
+    p.aspect_ratio, p.image_width, p.samples_per_pixel, p.max_depth = 1.0, 16, 1, 4
+    cam = rl.Camera(p)
+    assert (cam.c.image_width, cam.c.image_height) == (16, 16)
+    before = cam.render(world).data
+    try:
+        for variant in (1, 3, 5, 6, 7, 256, 512, 768, 1035):
+            rl.api.set_rtiow_variant(variant)
+            with pytest.raises(rl.api.RLError) as err:
+                cam.render(world)
+            assert err.value.code == rl.api.RL_E_UNSUPPORTED, variant
+            assert "retired" in str(err.value) and "DESIGN.md" in str(err.value), variant
+    finally:
+        rl.api.set_rtiow_variant(0)
+    assert np.array_equal(cam.render(world).data, before)
+
+
 def test_timed_kernel_row_shards_and_resume(rl, oracle):
     world = rl.World.bouncing_spheres(1)
     p = world.params

@@ -18,4 +18,4 @@ for i in range(2):
     e0,e1=torch.cuda.Event(enable_timing=True),torch.cuda.Event(enable_timing=True)
     e0.record(s); cam.render_device(w, buf.data_ptr(), stream=s.cuda_stream); e1.record(s)
     st=rl.api.render_status(w); torch.cuda.synchronize()
-print(name, sys.argv[1:], os.environ.get("RL_GENERAL_REGS",""), os.environ.get("RL_RTIOW_KERNEL","default"), os.environ.get("RL_FAST",""), os.environ.get("RL_LPT",""), "ms", round(e0.elapsed_time(e1),1), "rays", st["rays"], "Mrays/s", round(st["rays"]/e0.elapsed_time(e1)/1e3,1))
+print(name, sys.argv[1:], os.environ.get("RL_RTIOW_KERNEL","default"), os.environ.get("RL_FAST",""), os.environ.get("RL_LPT",""), "ms", round(e0.elapsed_time(e1),1), "rays", st["rays"], "Mrays/s", round(st["rays"]/e0.elapsed_time(e1)/1e3,1))

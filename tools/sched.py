@@ -1,4 +1,8 @@
-"""Prints the wave scheduler's block executions / average population per state (STATS launch)."""
+"""Prints the wave scheduler's block executions / average population per state (STATS launch).
+usage: [RL_RENDER_LIB=.../librl_render_verify.so] [RL_SCHED_FAST=0] tools/sched.py [image width] [samples per pixel]
+The instrumented fast sphere kernel (rl_debug_fast_stats) exists in the verify build only (make -C rendering-learning_amd/csrc verify): there
+every ray is also re-traced in the reference's order, so its TRAV / LEAF cycle shares include that re-trace; executions and populations do
+not.  With the product library rl_debug_fast_stats does nothing and the counting kernel's scheduler is printed."""
 import ctypes as C, importlib, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 rl = importlib.import_module("rendering-learning_amd")
