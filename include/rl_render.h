@@ -466,6 +466,29 @@ int rl_rtc_render_pixels_device(const rl_scene *, const rl_rtc_camera *, uint32_
                                 uint64_t n, void *d_out_rgb, void *hip_stream, rl_stats *opt_stats);
 
 /* =====================================================================
+ *  Second moments: sum of the squared sample colours beside the sum, for adaptive sampling
+ * =====================================================================
+ * The chained RTIOW renders once more, with a second output.  out_rgb_sum is exactly what the matching plain call writes
+ * (rl_rtiow_render_rows / _device, rl_rtiow_render_pixels / _device: same bits, same layout).  out_rgb_sq has the same layout and holds,
+ * per pixel and channel, with c_n the colour sample n adds to the sum (0 for a path that contributes nothing):
+ *     sq = 0.0;  for n ascending:  sq = sq + (c_n * c_n)
+ * in f64, the product rounded before the add (no FMA).  With both, (sq - sum^2 / S) / (S - 1) / S estimates the variance of the pixel's mean.
+ * Second moments of calls that continue each other (first_sample) add, as the sums do.  The _rows form always counts, as
+ * rl_rtiow_render_rows does; the list form counts when opt_stats is given, as rl_rtiow_render_pixels does.
+ * Status codes, opt_stats (a counting call takes the reference-order kernel: all seven counters, as the plain call's), rl_render_status,
+ * rl_rtiow_render_progress and concurrency are those of the plain calls; a NULL out_rgb_sq is RL_E_INVALID; in the _device list form an
+ * element outside the image writes zeros to BOTH buffers.  There is no CPU fallback: without a device RL_E_NO_DEVICE, outputs untouched.
+ * Not offered: the independent-sample renders, the multi-GPU renders, rgb8 output, and the RTC family (its AA grid is deterministic). */
+int rl_rtiow_render_moments_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                 double *out_rgb_sum, double *out_rgb_sq, rl_stats *opt_stats);
+int rl_rtiow_render_moments_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                   void *d_out_rgb_sum, void *d_out_rgb_sq, void *hip_stream, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_moments(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys,
+                                   uint64_t n, double *out_rgb_sum /* [n][3] */, double *out_rgb_sq /* [n][3] */, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_moments_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs, const void *d_ys,
+                                          uint64_t n, void *d_out_rgb_sum, void *d_out_rgb_sq, void *hip_stream, rl_stats *opt_stats);
+
+/* =====================================================================
  *  Batched ray queries: the reference's per-ray primitives on the device
  * =====================================================================
  *   rl_rtiow_hit_rays*      <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval) -> Option<(&Material, HitRecord)>

@@ -210,7 +210,8 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtiow_hit_rays_seeded", "rl_rtiow_hit_rays_seeded_device",
                   "rl_rtc_prepare_rays", "rl_rtc_prepare_rays_device", "rl_rtc_shade_hits", "rl_rtc_shade_hits_device",
                   "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device",
-                  "rl_rtiow_render_pixels", "rl_rtiow_render_pixels_device", "rl_rtc_render_pixels", "rl_rtc_render_pixels_device"]
+                  "rl_rtiow_render_pixels", "rl_rtiow_render_pixels_device", "rl_rtc_render_pixels", "rl_rtc_render_pixels_device",
+                  "rl_rtiow_render_moments_rows", "rl_rtiow_render_moments_device", "rl_rtiow_render_pixels_moments", "rl_rtiow_render_pixels_moments_device"]
 
 
 def _material_query_argtypes(L):
@@ -246,6 +247,16 @@ def _render_pixels_argtypes(L):
     L.rl_rtc_render_pixels.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
     L.rl_rtc_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                               C.POINTER(Stats)]
+
+
+def _render_moments_argtypes(L):
+    L.rl_rtiow_render_moments_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtiow_render_moments_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(Stats)]
+    L.rl_rtiow_render_pixels_moments.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(Stats)]
+    L.rl_rtiow_render_pixels_moments_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.POINTER(Stats)]
 
 
 def _pixel_list(xs, ys):
@@ -316,6 +327,8 @@ def render_lib():
             _seeded_hit_query_argtypes(L)
         if hasattr(L, "rl_rtiow_render_pixels"):  # (likewise)
             _render_pixels_argtypes(L)
+        if hasattr(L, "rl_rtiow_render_moments_rows"):  # (likewise)
+            _render_moments_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -1036,6 +1049,30 @@ class Canvas:  # camera.rs:263-296; data = SUMS over samples, [H, W, 3] f64
         return Canvas(s.value, w.value, h.value, data)
 
 
+@dataclass
+class Moments:
+    """First and second moments of a chained render (Camera.render_moments): per pixel and channel the sum of the sample colours (what
+    Canvas.data holds) and the sum of their squares, sq = sq + c_n * c_n in sample order.  With a row shard both arrays hold the shard's rows."""
+    samples: int
+    sums: np.ndarray = field(repr=False)  # [H, W, 3] f64
+    sq: np.ndarray = field(repr=False)    # [H, W, 3] f64
+
+    def merge(self, other):  # as Canvas.merge: the moments of renders that continue each other (first_sample) add
+        assert self.sums.shape == other.sums.shape and self.sq.shape == other.sq.shape
+        return Moments(self.samples + other.samples, self.sums + other.sums, self.sq + other.sq)
+
+    def canvas(self) -> Canvas:
+        return Canvas(self.samples, self.sums.shape[1], self.sums.shape[0], self.sums)
+
+    def variance_of_mean(self) -> np.ndarray:
+        """An ESTIMATE of the variance of each pixel mean: the unbiased sample variance over n, (sq - sums^2 / n) / (n - 1) / n, clipped at 0
+        (round-off can take the difference of the two large terms below it).  Plain numpy on the host; needs n >= 2."""
+        n = self.samples
+        if n < 2:
+            raise ValueError(f"variance_of_mean needs at least 2 samples, got {n}")
+        return np.maximum((self.sq - self.sums * self.sums / n) / (n - 1) / n, 0.0)
+
+
 class Camera:
     def __init__(self, params: CameraParams):  # Camera::new camera.rs:72
         self.params = params
@@ -1191,6 +1228,56 @@ class Camera:
         st = Stats() if stats is not None else None
         rc = render_lib().rl_rtiow_render_pixels_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
                                                         C.c_void_p(d_out), C.c_void_p(stream), C.byref(st) if st is not None else None)
+        _check(rc)
+        if stats is not None:
+            stats.update(st.as_dict())
+
+    # ---- renders with second moments (include/rl_render.h rl_rtiow_render_moments*, rl_rtiow_render_pixels_moments*): the sums of the plain
+    # call, bit for bit, and beside them the sums of the squared sample colours — what an adaptive pass picks its pixels by
+    def render_moments(self, world: World, first_sample=0, row_first=0, row_step=1, stats=None, allow_degenerate=False) -> Moments:
+        """render_rows(world, row_first, row_step, first_sample) with the second moments: Moments.sums is that call's array."""
+        nrows = rows_for(self.c.image_height, row_first, row_step)
+        sums = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
+        sq = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
+        st = Stats()
+        rc = render_lib().rl_rtiow_render_moments_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, sums.ctypes.data, sq.ctypes.data,
+                                                       C.byref(st))
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+        return Moments(self.params.samples_per_pixel, sums, sq)
+
+    def render_moments_device(self, world: World, d_sums, d_sq, stream=0, row_first=0, row_step=1, first_sample=0, stats=None):
+        """Both outputs stay in HBM: d_sums, d_sq = device pointers of nrows*W*3 f64 each.  Async unless stats is a dict."""
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_moments_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.c_void_p(d_sums),
+                                                         C.c_void_p(d_sq), C.c_void_p(stream), C.byref(st) if st is not None else None)
+        _check(rc)
+        if stats is not None:
+            stats.update(st.as_dict())
+
+    def render_pixels_moments(self, world: World, xs, ys, first_sample=0, stats=None, allow_degenerate=False):
+        """(sums [n, 3], sq [n, 3]) of pixels (xs[i], ys[i]): render_pixels' sums and the second moments, each what render_moments holds at
+        [ys[i], xs[i]].  The list rules are render_pixels'."""
+        xs, ys = _pixel_list(xs, ys)
+        sums = np.empty((xs.size, 3), dtype=np.float64)
+        sq = np.empty((xs.size, 3), dtype=np.float64)
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_pixels_moments(world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, sums.ctypes.data,
+                                                         sq.ctypes.data, C.byref(st) if st is not None else None)
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+        return sums, sq
+
+    def render_pixels_moments_device(self, world: World, d_xs, d_ys, n, d_sums, d_sq, stream=0, first_sample=0, stats=None):
+        """d_xs / d_ys: device pointers of n uint32; d_sums, d_sq: of n*3 f64 each.  Async unless stats is a dict; an element outside the image
+        is written as zeros in both."""
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_pixels_moments_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
+                                                                C.c_void_p(d_sums), C.c_void_p(d_sq), C.c_void_p(stream), C.byref(st) if st is not None else None)
         _check(rc)
         if stats is not None:
             stats.update(st.as_dict())

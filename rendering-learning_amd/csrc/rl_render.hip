@@ -682,6 +682,16 @@ static int choose_rtiow_variant(const rl_scene *scene, const rl_rtiow_camera *ca
   return RL_OK;
 }
 
+// Where a MOMENTS frame (rl_rtiow_render_moments*) goes.  The flavour exists in the counter-free wave kernel (1029 / 1027 /
+// 1025 / 1024), the cooperative kernel (1033), the fast general kernel (1031) and the reference-order wave general kernel (4, counting or
+// not).  Every pixel is the same bits through every kernel, so a call whose scene, counters or forced variant would land anywhere else —
+// the nested-loop kernel (2), a counting layout of the wave kernel — takes variant 4; the cost-sorted resume launch of a small shard runs
+// without work stealing; the fast general kernel runs in its two-waves-per-SIMD form whatever the frame's size.
+static void route_moments_variant(RtiowChoice &choice, bool want_stats) {
+  const int v = choice.variant;
+  if (v == 2 || (want_stats && v != 4)) choice.variant = 4;
+}
+
 // Variant 1029 only: the per-pixel entry table of this render's camera and rows (rl_pixel_entry.h), built on `stream` ahead of the render
 // kernels into the scene's own buffer (grown on demand, like d_pos).  Nothing is kept from call to call: the camera may differ.
 static int build_pixel_entry(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream) {
@@ -710,7 +720,7 @@ static int stage_params(const rl_scene *scene, const RtiowParams &P, hipStream_t
 
 namespace rl {
 int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, void *d_out,
-                        hipStream_t stream, bool want_stats) {
+                        hipStream_t stream, bool want_stats, void *d_out_sq) {
   const RtiowProgram &rt = scene->rt();
   const HostRtiow &H = *scene->hrt;
   uint32_t H_ = cam->image_height, W = cam->image_width;
@@ -721,6 +731,8 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     int rcp = fill_rtiow_params(scene, cam, first_sample, row_first, row_step, nrows, d_out, want_stats, P, slots);
     if (rcp != RL_OK) return rcp;
   }
+  const bool moments = d_out_sq != nullptr;  // the MOMENTS instantiations: second moments beside the sums, same layout
+  P.out_sq = (double *)d_out_sq;
 
   {
     int rco = order_after_previous(scene, stream);
@@ -765,6 +777,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     int rcv = choose_rtiow_variant(scene, cam, P, nrows, want_stats, choice);
     if (rcv != RL_OK) return rcv;
   }
+  if (moments) route_moments_variant(choice, want_stats);
   const int variant = choice.variant;
   const size_t compact_bytes = choice.compact_bytes, fast_bytes = choice.fast_bytes;
   if (variant == 1029) {
@@ -787,7 +800,13 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     // the lowest latency (boxes in registers: 3.3 us per ray, two waves per SIMD) while every pixel gets a wave at once; the register
     // budget of four waves per SIMD (boxes from L2: 4.0 us per ray, +25 % throughput) for larger frames.  RL_COOP_MODE forces one (A/B).
     int mode = g_sw.coop_mode >= 0 ? g_sw.coop_mode : (n_pixels <= (uint32_t)g_cus * 8u ? 2 : 0);
-    if (mode == 2) {
+    if (moments && mode == 2) {
+      if (ensure_lds_attr((const void *)rtiow_coop_moments_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
+      hipLaunchKernelGGL((rtiow_coop_moments_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
+    } else if (moments) {
+      if (ensure_lds_attr((const void *)rtiow_coop_moments_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
+      hipLaunchKernelGGL((rtiow_coop_moments_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
+    } else if (mode == 2) {
       if (ensure_lds_attr((const void *)rtiow_coop_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
       hipLaunchKernelGGL((rtiow_coop_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
     } else {
@@ -824,8 +843,19 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
       // at 1000x1000: the one-wave form's throughput ends at ~810 Mrays/s).  Measured and not taken: the same for the other flavours (quads.rs -17 %, flat_world.rs -24 %, cornell_smoke.rs at
       // 600x600 -30 %: they spill little, and lose the second wave's latency hiding).  RL_FASTG_NT256=1 / 0 forces it on / off (A/B).
       const bool media = H.fg.stage_roots.size() > 1;
-      const bool one_wave = trans && media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : (uint64_t)nrows * W <= (uint64_t)g_cus * 1536u);
-      if (one_wave) {
+      const bool one_wave = !moments && trans && media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : (uint64_t)nrows * W <= (uint64_t)g_cus * 1536u);
+      if (moments) {  // the same four flavours and LDS layouts as below
+        if (media || trans) {
+          constexpr int NT = 512, SD = 40;
+          size_t rb = fastg_lds(NT, SD);
+          if (media) rc = trans ? launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, true, true>, NT, rb) : launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, false, true>, NT, rb);
+          else rc = launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, true, false>, NT, rb);
+        } else {
+          constexpr int NT = 768, SD = 20;
+          size_t rb = fastg_lds(NT, SD);
+          rc = launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, false, false>, NT, rb);
+        }
+      } else if (one_wave) {
         constexpr int NT = 256, SD = 40;
         size_t rb = fastg_lds(NT, SD);
         if (rb < 90000) rb = 90000;  // one workgroup per CU
@@ -850,7 +880,14 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
       // loop and cost 2.3x (measured, cfg 4: 1101 vs 465 Mrays/s).
       bool trans = rt.has_noise || rt.has_sphere_uv;
       size_t rb = (size_t)16 * 512 * sizeof(unsigned long long);
-      if (rt.has_media) {  // + the parked HitRecord of a medium scope: 96 B of LDS per lane
+      if (moments) {
+        size_t mb = (size_t)512 * (16 + MEDIA_SAVE_WORDS) * sizeof(unsigned long long);
+        if (rt.has_media) {
+          if (trans) rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, true, true, true>, 512, mb) : launch(rtiow_wave_general_moments_kernel<512, true, false, true>, 512, mb);
+          else rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, false, true, true>, 512, mb) : launch(rtiow_wave_general_moments_kernel<512, false, false, true>, 512, mb);
+        } else if (trans) rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, true, true, false>, 512, rb) : launch(rtiow_wave_general_moments_kernel<512, true, false, false>, 512, rb);
+        else rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, false, true, false>, 512, rb) : launch(rtiow_wave_general_moments_kernel<512, false, false, false>, 512, rb);
+      } else if (rt.has_media) {  // + the parked HitRecord of a medium scope: 96 B of LDS per lane
         size_t mb = (size_t)512 * (16 + MEDIA_SAVE_WORDS) * sizeof(unsigned long long);
         if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<512, true, true, true>, 512, mb) : launch(rtiow_wave_general_kernel<512, true, false, true>, 512, mb);
         else rc = want_stats ? launch(rtiow_wave_general_kernel<512, false, true, true>, 512, mb) : launch(rtiow_wave_general_kernel<512, false, false, true>, 512, mb);
@@ -859,7 +896,8 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     } else if (variant == 1025) {  // 4 waves per SIMD: rings + linked ops in LDS, spheres read from L2
       constexpr int NT = 1024;
       size_t rb = (size_t)16 * NT * sizeof(unsigned long long) + (size_t)P.n_ops * sizeof(DevOp);
-      rc = want_stats ? launch(rtiow_wave_kernel<NT, 2, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 2, false>, NT, rb);
+      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 2>, NT, rb);  // (never counting: route_moments_variant)
+      else rc = want_stats ? launch(rtiow_wave_kernel<NT, 2, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 2, false>, NT, rb);
     } else if (variant == 1033) {  // A/B: EVERY pixel through the cooperative one-wave-per-pixel kernel (rl_rtiow_coop.h)
       rl_scene *ms = const_cast<rl_scene *>(scene);
       const size_t npix = (size_t)nrows * W;
@@ -872,18 +910,21 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
       // leave a TRAV round when fewer than a quarter of the lanes it started with are still walking (the counting kernels: 3/8): with
       // pair nodes and inline misses the walks are short and uneven — +2.1 % (6596 -> 6734 Mrays/s; 24,2: 6740; 24,1: 6586; tools: RL_TUNE)
       if (!g_sw.tune_set) P.tune[1] = 4, P.tune[2] = 4;
-      if (steal) rc = launch(rtiow_wave_kernel<NT, 4, false, true>, NT, rb);
+      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 4>, NT, rb);
+      else if (steal) rc = launch(rtiow_wave_kernel<NT, 4, false, true>, NT, rb);
       // counting only under rl_debug_fast_stats (verify build, tools/sched.py): scheduler occupancy of the fast kernel; its box / sphere counts are its own
       else if (want_stats && FAST_STATS_KERNEL) rc = launch(rtiow_wave_kernel<NT, 4, FAST_STATS_KERNEL>, NT, rb);
       else rc = launch(rtiow_wave_kernel<NT, 4, false>, NT, rb);
     } else if (variant == 1027) {  // 4 waves per SIMD: rings + compact guarded ops in LDS, spheres read from L2
       constexpr int NT = 1024;
       size_t rb = (size_t)16 * NT * sizeof(unsigned long long) + compact_bytes;
-      rc = want_stats ? launch(rtiow_wave_kernel<NT, 3, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 3, false>, NT, rb);
+      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 3>, NT, rb);
+      else rc = want_stats ? launch(rtiow_wave_kernel<NT, 3, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 3, false>, NT, rb);
     } else {  // 1024: everything through L2 (sphere-only worlds too large for LDS)
       constexpr int NT = 1024;
       size_t rb = (size_t)16 * NT * sizeof(unsigned long long);
-      rc = want_stats ? launch(rtiow_wave_kernel<NT, 0, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 0, false>, NT, rb);
+      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 0>, NT, rb);
+      else rc = want_stats ? launch(rtiow_wave_kernel<NT, 0, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 0, false>, NT, rb);
     }
     return rc;
   };
@@ -918,7 +959,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     if (scene->progress_on) P.work_counter = scene->d_progress + 1;  // the resume launch counts in the second host-visible word
     P.sample_begin = lpt_first, P.sample_end = cam->samples_per_pixel, P.resume = 1;
     P.tile_order = ms->d_tile_order, P.tile_cost = nullptr;
-    if (variant == 1029 && !want_stats && g_sw.steal_max_fill > 0.0 && (double)npix <= g_sw.steal_max_fill * (double)g_cus * 1024.0) {
+    if (variant == 1029 && !want_stats && !moments && g_sw.steal_max_fill > 0.0 && (double)npix <= g_sw.steal_max_fill * (double)g_cus * 1024.0) {
       // small shard: waves that run out of pixels take over pixels other lanes are still rendering (rl_rtiow_coop.h rtiow_steal_loop)
       HIP_TRY(ms->d_steal_state.reserve(npix));
       HIP_TRY(ms->d_steal_n.reserve(npix));
@@ -1066,7 +1107,9 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
 }
 }  // namespace rl
 
-// Which kernel renders a pixel LIST (rl_rtiow_render_pixels*).  The list kernels are the cooperative one-wave-per-pixel
+// Which kernel renders a pixel LIST (rl_rtiow_render_pixels*; with second moments, rl_rtiow_render_pixels_moments*, §3.14: all
+// three list kernels have the MOMENTS flavour, so a moments list goes where the plain list goes — except that the fast general kernel runs in
+// its two-waves-per-SIMD form whatever the list's length).  The list kernels are the cooperative one-wave-per-pixel
 // kernel (sphere-only scenes that have the fast structure, counter-free), the fast general kernel (general scenes with a fast tree,
 // counter-free) and the reference-order wave-scheduled general kernel (every counting call, and every scene the other two do not take).
 // rl_debug_set_fast_traversal(0) / rl_debug_set_coop(0) send the counter-free calls to the reference-order kernel (tests, A/B).
@@ -1093,7 +1136,7 @@ namespace rl {
 // The launch half of rl_rtiow_render_pixels*: n list elements (d_xs[i], d_ys[i]) of the whole frame -> d_out[i], all on `stream`.
 // want_stats: a counting call (reference-order kernel); timed: the caller reads the stats words synchronously (ev0 / ev1 bracket the kernel)
 int rtiow_render_pixels_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const uint32_t *d_xs, const uint32_t *d_ys, uint64_t n,
-                               void *d_out, hipStream_t stream, bool want_stats, bool timed) {
+                               void *d_out, hipStream_t stream, bool want_stats, bool timed, void *d_out_sq) {
   const RtiowProgram &rt = scene->rt();
   const HostRtiow &H = *scene->hrt;
   if (n >= PIXEL_LIST_MAX_N) return set_err(RL_E_INVALID, "image too large");  // the u32 work counter (the entry points have checked already)
@@ -1104,6 +1147,8 @@ int rtiow_render_pixels_launch(const rl_scene *scene, const rl_rtiow_camera *cam
     if (rcp != RL_OK) return rcp;
   }
   P.n_slots = (uint32_t)n, P.pix_xs = d_xs, P.pix_ys = d_ys;
+  const bool moments = d_out_sq != nullptr;  // the MOMENTS instantiations: second moments beside the sums, compact as they are
+  P.out_sq = (double *)d_out_sq;
   P.pix_rays = nullptr, P.pos_state = nullptr, P.tile_order = nullptr, P.tile_cost = nullptr, P.resume = 0;
   P.sample_begin = 0, P.sample_end = cam->samples_per_pixel;
   PixelsKernel which;
@@ -1164,7 +1209,13 @@ int rtiow_render_pixels_launch(const rl_scene *scene, const rl_rtiow_camera *cam
     const uint32_t cap = (uint32_t)g_cus * (16 / NW);  // 4 waves per SIMD at 128 VGPRs
     if (blocks > cap) blocks = cap;
     const int mode = g_sw.coop_mode >= 0 ? g_sw.coop_mode : (n <= (uint64_t)g_cus * 8u ? 2 : 0);
-    if (mode == 2) {
+    if (moments && mode == 2) {
+      if (ensure_lds_attr((const void *)rtiow_coop_pixels_moments_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
+      hipLaunchKernelGGL((rtiow_coop_pixels_moments_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
+    } else if (moments) {
+      if (ensure_lds_attr((const void *)rtiow_coop_pixels_moments_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
+      hipLaunchKernelGGL((rtiow_coop_pixels_moments_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
+    } else if (mode == 2) {
       if (ensure_lds_attr((const void *)rtiow_coop_pixels_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
       hipLaunchKernelGGL((rtiow_coop_pixels_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
     } else {
@@ -1175,20 +1226,30 @@ int rtiow_render_pixels_launch(const rl_scene *scene, const rl_rtiow_camera *cam
   } else if (which == PIXELS_FAST_GENERAL) {  // the flavours and LDS layout of the frame's variant 1031 (rtiow_render_launch)
     if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
     const bool media = H.fg.stage_roots.size() > 1;
-    const bool one_wave = trans && media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : n <= (uint64_t)g_cus * 1536u);
+    const bool one_wave = !moments && trans && media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : n <= (uint64_t)g_cus * 1536u);
     const int SD = (media || trans) ? 40 : 20, nt = one_wave ? 256 : (media || trans) ? 512 : 768;
     const size_t base = (size_t)nt * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));
     const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
     P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(H.fg.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
     size_t lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
     if (one_wave && lds < 90000) lds = 90000;  // one workgroup per CU
-    if (one_wave) rc = launch_ptr(rtiow_fast_general_pixels_kernel<256, 40, true, true>, nt, lds);
+    if (moments) {
+      if (media) rc = trans ? launch_ptr(rtiow_fast_general_pixels_moments_kernel<512, 40, true, true>, nt, lds) : launch_ptr(rtiow_fast_general_pixels_moments_kernel<512, 40, false, true>, nt, lds);
+      else if (trans) rc = launch_ptr(rtiow_fast_general_pixels_moments_kernel<512, 40, true, false>, nt, lds);
+      else rc = launch_ptr(rtiow_fast_general_pixels_moments_kernel<768, 20, false, false>, nt, lds);
+    } else if (one_wave) rc = launch_ptr(rtiow_fast_general_pixels_kernel<256, 40, true, true>, nt, lds);
     else if (media) rc = trans ? launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, true, true>, nt, lds) : launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, false, true>, nt, lds);
     else if (trans) rc = launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, true, false>, nt, lds);
     else rc = launch_ptr(rtiow_fast_general_pixels_kernel<768, 20, false, false>, nt, lds);
   } else {  // reference order: 512 lanes per CU, rings (and a medium scope's parked HitRecord) in LDS, as the frame's variant 4
     const size_t lds = (size_t)512 * (16 + (rt.has_media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long);
-    if (rt.has_media) {
+    if (moments) {
+      if (rt.has_media) {
+        if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, true, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, true, false, true>, 512, lds);
+        else rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, false, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, false, false, true>, 512, lds);
+      } else if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, true, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, true, false, false>, 512, lds);
+      else rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, false, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, false, false, false>, 512, lds);
+    } else if (rt.has_media) {
       if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, true, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, true, false, true>, 512, lds);
       else rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, false, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, false, false, true>, 512, lds);
     } else if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, true, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, true, false, false>, 512, lds);
@@ -1222,10 +1283,12 @@ int rl_rtiow_render_independent_device(const rl_scene *scene, const rl_rtiow_cam
 
 // Pixel-list renders (include/rl_render.h "Pixel-list renders").  counting: the caller gave opt_stats (reference-order
 // kernel, all seven counters); sync_st: filled synchronously (the host form always; rays and flagged only when !counting); null: asynchronous.
+// d_out_sq: the moments forms' second buffer; null: a plain list render.
 static int rtiow_render_pixels_impl(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const void *d_xs, const void *d_ys, uint64_t n,
-                                    void *d_out, hipStream_t stream, bool counting, rl_stats *sync_st) {
+                                    void *d_out, hipStream_t stream, bool counting, rl_stats *sync_st, void *d_out_sq = nullptr) {
   return render_run(scene, stream, sync_st, [&] {
-    return rl::rtiow_render_pixels_launch(scene, cam, first_sample, (const uint32_t *)d_xs, (const uint32_t *)d_ys, n, d_out, stream, counting, sync_st != nullptr);
+    return rl::rtiow_render_pixels_launch(scene, cam, first_sample, (const uint32_t *)d_xs, (const uint32_t *)d_ys, n, d_out, stream, counting, sync_st != nullptr,
+                                          d_out_sq);
   });
 }
 
@@ -1237,6 +1300,27 @@ int rl_rtiow_render_pixels_device(const rl_scene *scene, const rl_rtiow_camera *
   rc = list_length_check(n, st, done);
   if (done) return rc;
   return rtiow_render_pixels_impl(scene, cam, first_sample, d_xs, d_ys, n, d_out, (hipStream_t)hip_stream, st != nullptr, st);
+}
+
+// Renders with second moments (include/rl_render.h "Second moments"): the plain calls' checks, run and status, with the
+// second buffer handed to the launch, which then takes the MOMENTS instantiations.
+int rl_rtiow_render_moments_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                   void *d_out, void *d_out_sq, void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), d_out && d_out_sq && row_step != 0, row_first, "empty image", st, done);
+  if (done) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  return render_run(scene, stream, st, [&] { return rl::rtiow_render_launch(scene, cam, first_sample, row_first, row_step, d_out, stream, st != nullptr, d_out_sq); });
+}
+
+int rl_rtiow_render_pixels_moments_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const void *d_xs, const void *d_ys, uint64_t n,
+                                          void *d_out, void *d_out_sq, void *hip_stream, rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), d_out_sq && (n == 0 || (d_xs && d_ys && d_out)), 0, "empty image", st, done);
+  if (done) return rc;
+  rc = list_length_check(n, st, done);
+  if (done) return rc;
+  return rtiow_render_pixels_impl(scene, cam, first_sample, d_xs, d_ys, n, d_out, (hipStream_t)hip_stream, st != nullptr, st, d_out_sq);
 }
 
 // Completion + status of the last ASYNCHRONOUS render of this scene (rl_*_render_device / rl_*_render_multi_device with
@@ -1570,6 +1654,36 @@ int rl_rtiow_render_pixels(const rl_scene *scene, const rl_rtiow_camera *cam, ui
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;
   return q.finish(rtiow_render_pixels_impl(scene, cam, first_sample, d_xy, d_xy + (size_t)n * sizeof(uint32_t), n, d_out, q.stream, st != nullptr, &local), st, local);
+}
+
+int rl_rtiow_render_moments_rows(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, double *out,
+                                 double *out_sq, rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), out && out_sq && row_step != 0, row_first, nullptr, st, done);
+  if (done) return rc;
+  HostStaging q(scene);
+  const size_t bytes = frame_of(cam).rows_bytes(row_first, row_step);
+  void *d_out = q.out(out, bytes), *d_out_sq = q.out(out_sq, bytes);
+  if (q.rc != RL_OK) return q.rc;
+  rl_stats local;
+  return q.finish(rl_rtiow_render_moments_device(scene, cam, first_sample, row_first, row_step, d_out, d_out_sq, q.stream, &local), st, local);
+}
+
+int rl_rtiow_render_pixels_moments(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys, uint64_t n,
+                                   double *out, double *out_sq, rl_stats *st) {
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), out_sq && (n == 0 || (xs && ys && out)), 0, "empty image", st, done);
+  if (done) return rc;
+  rc = list_length_check(n, st, done);
+  if (done) return rc;
+  if ((rc = pixel_list_check(frame_of(cam), xs, ys, n)) != RL_OK) return rc;
+  HostStaging q(scene);
+  const unsigned char *d_xy = (const unsigned char *)q.in({{xs, (size_t)n * sizeof(uint32_t)}, {ys, (size_t)n * sizeof(uint32_t)}});
+  void *d_out = q.out(out, (size_t)n * 3 * sizeof(double)), *d_out_sq = q.out(out_sq, (size_t)n * 3 * sizeof(double));
+  if (q.rc != RL_OK) return q.rc;
+  rl_stats local;
+  return q.finish(rtiow_render_pixels_impl(scene, cam, first_sample, d_xy, d_xy + (size_t)n * sizeof(uint32_t), n, d_out, q.stream, st != nullptr, &local, d_out_sq), st,
+                  local);
 }
 
 int rl_rtiow_encode_rgb8_device(const void *d_rgb_sum, uint64_t n_pixels, uint32_t samples, void *d_rgb8, void *hip_stream) {

@@ -91,7 +91,9 @@ struct WaveRng {
   }
 };
 
-template <int NT, bool BOXES_IN_REGS, class Source, class Cand>
+// MOMENTS (rl_rtiow_render_moments* / rl_rtiow_render_pixels_moments*): the pixel also carries sq, per channel the sum of the
+// squared sample colours (each product rounded, then added, in sample order), which the source's next / finish load and store beside sum
+template <int NT, bool BOXES_IN_REGS, bool MOMENTS = false, class Source, class Cand>
 __device__ __forceinline__ void rtiow_coop_body(const RtiowParams &P, const float *leaf_boxes, uint32_t max_cand, unsigned long long *s_rng, Cand cand_at, Source src) {
   const int tid = threadIdx.x, lane = tid & 63;
   const DevOp *ops = P.ops;
@@ -119,8 +121,11 @@ __device__ __forceinline__ void rtiow_coop_body(const RtiowParams &P, const floa
 
   for (;;) {
     uint32_t pix = 0, n_begin = 0, pos0 = 0;
-    D3 sum = d3(0.0, 0.0, 0.0);
-    if (!src.next(P, lane, pix, sum, pos0, n_begin)) break;
+    D3 sum = d3(0.0, 0.0, 0.0), sq = d3(0.0, 0.0, 0.0);
+    bool more;
+    if constexpr (MOMENTS) more = src.next(P, lane, pix, sum, sq, pos0, n_begin);
+    else more = src.next(P, lane, pix, sum, pos0, n_begin);
+    if (!more) break;
     uint32_t x, y;
     src.locate(P, pix, x, y);
     WaveRng<NT> rng{P.key, s_rng, tid, 0ull, pos0, 0xFFFFFFFFu};
@@ -314,8 +319,10 @@ __device__ __forceinline__ void rtiow_coop_body(const RtiowParams &P, const floa
         d = nd;
       }
       sum = sum + color;
+      if constexpr (MOMENTS) sq = sq + color * color;
     }
-    src.finish(P, lane, pix, sum, rng.pos);
+    if constexpr (MOMENTS) src.finish(P, lane, pix, sum, sq, rng.pos);
+    else src.finish(P, lane, pix, sum, rng.pos);
   }
   // every lane of a wave counted the same rays: lane 0 reports
   if (lane == 0) {
@@ -351,12 +358,29 @@ struct CoopListSource {
     }
     return true;
   }
+  // MOMENTS: the second moments from and to P.out_sq, wherever the sums come from and go to P.out
+  __device__ __forceinline__ bool next(const RtiowParams &P, int lane, uint32_t &pix, D3 &sum, D3 &sq, uint32_t &pos, uint32_t &n_begin) const {
+    if (!next(P, lane, pix, sum, pos, n_begin)) return false;
+    sq = d3(0.0, 0.0, 0.0);
+    if (P.resume) {
+      const double *inq = P.out_sq + (size_t)pix * 3;
+      sq = d3(inq[0], inq[1], inq[2]);
+    }
+    return true;
+  }
   __device__ __forceinline__ void locate(const RtiowParams &P, uint32_t pix, uint32_t &x, uint32_t &y) const { virtual_index_pixel(P, pix, x, y); }
   __device__ __forceinline__ void finish(const RtiowParams &P, int lane, uint32_t pix, D3 sum, uint32_t pos) const {
     if (lane == 0) {
       double *outp = P.out + (size_t)pix * 3;
       outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
       if (P.pos_state) P.pos_state[pix] = pos;
+    }
+  }
+  __device__ __forceinline__ void finish(const RtiowParams &P, int lane, uint32_t pix, D3 sum, D3 sq, uint32_t pos) const {
+    finish(P, lane, pix, sum, pos);
+    if (lane == 0) {
+      double *outq = P.out_sq + (size_t)pix * 3;
+      outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
     }
   }
 };
@@ -376,6 +400,15 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_coop_kernel(Rt
   uint32_t *s_cand = (uint32_t *)(smem + (size_t)8 * NT * sizeof(unsigned long long)) + (size_t)(threadIdx.x >> 6) * C.max_cand;
   rtiow_coop_body<NT, BOXES_IN_REGS>(P, C.leaf_boxes, C.max_cand, s_rng, CoopLinearCand{s_cand}, CoopListSource{C.pixels, C.n_pixels, C.counter});
 }
+// the same with second moments (MOMENTS)
+template <int NW, bool BOXES_IN_REGS, int REGS_FOR>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_coop_moments_kernel(RtiowParams P, CoopParams C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NT = NW * 64;
+  unsigned long long *s_rng = (unsigned long long *)smem;
+  uint32_t *s_cand = (uint32_t *)(smem + (size_t)8 * NT * sizeof(unsigned long long)) + (size_t)(threadIdx.x >> 6) * C.max_cand;
+  rtiow_coop_body<NT, BOXES_IN_REGS, true>(P, C.leaf_boxes, C.max_cand, s_rng, CoopLinearCand{s_cand}, CoopListSource{C.pixels, C.n_pixels, C.counter});
+}
 
 // Work source of rl_rtiow_render_pixels* (DESIGN.md §3.13): the elements of the caller's (x, y) list, one wave per element.  The work item is
 // the element's INDEX, which is also where its sums go (compact output); an element outside the image (the _device form) is written as
@@ -384,7 +417,8 @@ struct CoopPixelListSource {
   const uint32_t *xs, *ys;
   uint32_t n_pixels;
   uint32_t *counter;
-  __device__ __forceinline__ bool next(const RtiowParams &P, int lane, uint32_t &pix, D3 &sum, uint32_t &pos, uint32_t &n_begin) const {
+  template <bool MOMENTS>
+  __device__ __forceinline__ bool next_element(const RtiowParams &P, int lane, uint32_t &pix, D3 &sum, uint32_t &pos, uint32_t &n_begin) const {
     for (;;) {
       uint32_t idx = 0;
       if (lane == 0) idx = atomicAdd(counter, 1u);
@@ -394,6 +428,10 @@ struct CoopPixelListSource {
         if (lane == 0) {
           double *outp = P.out + (size_t)idx * 3;
           outp[0] = 0.0, outp[1] = 0.0, outp[2] = 0.0;
+          if (MOMENTS) {  // zeros to both outputs
+            double *outq = P.out_sq + (size_t)idx * 3;
+            outq[0] = 0.0, outq[1] = 0.0, outq[2] = 0.0;
+          }
         }
         continue;
       }
@@ -402,11 +440,25 @@ struct CoopPixelListSource {
       return true;
     }
   }
+  __device__ __forceinline__ bool next(const RtiowParams &P, int lane, uint32_t &pix, D3 &sum, uint32_t &pos, uint32_t &n_begin) const {
+    return next_element<false>(P, lane, pix, sum, pos, n_begin);
+  }
+  __device__ __forceinline__ bool next(const RtiowParams &P, int lane, uint32_t &pix, D3 &sum, D3 &sq, uint32_t &pos, uint32_t &n_begin) const {
+    sq = d3(0.0, 0.0, 0.0);
+    return next_element<true>(P, lane, pix, sum, pos, n_begin);
+  }
   __device__ __forceinline__ void locate(const RtiowParams &, uint32_t pix, uint32_t &x, uint32_t &y) const { x = xs[pix], y = ys[pix]; }
   __device__ __forceinline__ void finish(const RtiowParams &P, int lane, uint32_t pix, D3 sum, uint32_t) const {
     if (lane == 0) {
       double *outp = P.out + (size_t)pix * 3;
       outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+    }
+  }
+  __device__ __forceinline__ void finish(const RtiowParams &P, int lane, uint32_t pix, D3 sum, D3 sq, uint32_t pos) const {
+    finish(P, lane, pix, sum, pos);
+    if (lane == 0) {
+      double *outq = P.out_sq + (size_t)pix * 3;
+      outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
     }
   }
 };
@@ -418,6 +470,14 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_coop_pixels_ke
   unsigned long long *s_rng = (unsigned long long *)smem;
   uint32_t *s_cand = (uint32_t *)(smem + (size_t)8 * NT * sizeof(unsigned long long)) + (size_t)(threadIdx.x >> 6) * C.max_cand;
   rtiow_coop_body<NT, BOXES_IN_REGS>(P, C.leaf_boxes, C.max_cand, s_rng, CoopLinearCand{s_cand}, CoopPixelListSource{P.pix_xs, P.pix_ys, C.n_pixels, C.counter});
+}
+template <int NW, bool BOXES_IN_REGS, int REGS_FOR>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_coop_pixels_moments_kernel(RtiowParams P, CoopParams C) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int NT = NW * 64;
+  unsigned long long *s_rng = (unsigned long long *)smem;
+  uint32_t *s_cand = (uint32_t *)(smem + (size_t)8 * NT * sizeof(unsigned long long)) + (size_t)(threadIdx.x >> 6) * C.max_cand;
+  rtiow_coop_body<NT, BOXES_IN_REGS, true>(P, C.leaf_boxes, C.max_cand, s_rng, CoopLinearCand{s_cand}, CoopPixelListSource{P.pix_xs, P.pix_ys, C.n_pixels, C.counter});
 }
 
 // ---- work stealing (the STEAL instantiation of rtiow_wave_kernel, small shards): see RtiowParams::steal_state

@@ -176,12 +176,12 @@ __device__ __forceinline__ void fastg_sphere_hit(const DevSphere &s, uint32_t pa
 // INDEP: the sample-parallel mode, as in rtiow_wave_indep_kernel (rl_rtiow_wave.h; the body is included into both kernels for the same reason)
 template <int NT, int SD, bool TRANS, bool MEDIA = false>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = false, RAYS = false, PIXELS = false;
+  constexpr bool INDEP = false, RAYS = false, PIXELS = false, MOMENTS = never_v<NT>;
 #include "rl_rtiow_fastgen_body.inc"
 }
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_indep_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = true, RAYS = false, PIXELS = false;
+  constexpr bool INDEP = true, RAYS = false, PIXELS = false, MOMENTS = never_v<NT>;
 #include "rl_rtiow_fastgen_body.inc"
 }
 // RAYS (rl_rtiow_ray_color_rays*): Camera::ray_color for a buffer of rays, each with its own RNG cursor.  GEN claims rays
@@ -189,14 +189,26 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_indep_k
 // treatment of start_ray, the exact re-trace — is the body's own.  P.cam carries the call's background and max_depth, P.key its seed.
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_rays_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = false, RAYS = true, PIXELS = false;
+  constexpr bool INDEP = false, RAYS = true, PIXELS = false, MOMENTS = never_v<NT>;
 #include "rl_rtiow_fastgen_body.inc"
 }
 // PIXELS (rl_rtiow_render_pixels*): GEN claims elements of the caller's (x, y) list instead of tile slots and stores a pixel's
 // sums at its element index; everything behind the claim is the body's own, so a listed pixel is the frame's pixel bit for bit.
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_pixels_kernel(const RtiowParams *__restrict__ Pp) {
-  constexpr bool INDEP = false, RAYS = false, PIXELS = true;
+  constexpr bool INDEP = false, RAYS = false, PIXELS = true, MOMENTS = never_v<NT>;
+#include "rl_rtiow_fastgen_body.inc"
+}
+// MOMENTS (rl_rtiow_render_moments* / rl_rtiow_render_pixels_moments*): the frame and the list kernel once more, keeping the
+// sum of the squared sample colours (P.out_sq) beside the sum — stored, resumed and zeroed wherever the sum is.
+template <int NT, int SD, bool TRANS, bool MEDIA>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_moments_kernel(const RtiowParams *__restrict__ Pp) {
+  constexpr bool INDEP = false, RAYS = false, PIXELS = false, MOMENTS = true;
+#include "rl_rtiow_fastgen_body.inc"
+}
+template <int NT, int SD, bool TRANS, bool MEDIA>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_pixels_moments_kernel(const RtiowParams *__restrict__ Pp) {
+  constexpr bool INDEP = false, RAYS = false, PIXELS = true, MOMENTS = true;
 #include "rl_rtiow_fastgen_body.inc"
 }
 

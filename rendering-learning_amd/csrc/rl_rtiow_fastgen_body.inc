@@ -1,5 +1,6 @@
   // The body of rtiow_fast_general_kernel / rtiow_fast_general_indep_kernel / rtiow_fast_general_rays_kernel / rtiow_fast_general_pixels_kernel
-  // (rl_rtiow_fastgen.h): included inside all four, with INDEP, RAYS, PIXELS (and the kernel's template parameters) in scope.
+  // and the two _moments_ kernels (rl_rtiow_fastgen.h): included inside all six, with INDEP, RAYS, PIXELS, MOMENTS (and the kernel's template
+  // parameters) in scope.
   // the parameter block is read from memory where it is needed (uniform addresses: scalar loads through the constant cache) instead of
   // arriving by value: by value every field that is live anywhere is loaded at kernel entry and pins SGPRs for the kernel's life time
   const RtiowParams &P = *Pp;
@@ -31,6 +32,7 @@
   uint32_t ptile = 0, pix_rays = 0;
   bool have_pixel = false;
   D3 sum = d3(0.0, 0.0, 0.0);
+  D3 sq = d3(0.0, 0.0, 0.0);  // MOMENTS: per channel the sum of the squared sample colours (each product rounded, then added), beside sum
   D3 wo = d3(0.0, 0.0, 0.0), wd = d3(0.0, 0.0, 1.0);
   D3 thr = d3(1.0, 1.0, 1.0);
   RayAux32 ra32 = ray_aux32_direct(wo, wd);
@@ -61,7 +63,11 @@
       if (!amb && best == NONE) {  // a miss needs no SHADE visit: background (camera.rs:257), sample done
 #endif
         if (MEDIA) c_flag += ray_flags;
-        sum = sum + thr * ld3(cam.background);
+        if constexpr (MOMENTS) {
+          const D3 c = thr * ld3(cam.background);
+          sum = sum + c;
+          sq = sq + c * c;
+        } else sum = sum + thr * ld3(cam.background);
         n++;
         state = ST_GEN;
       } else state = ST_SHADE;
@@ -336,6 +342,10 @@
             if (have_pixel) {
               double *outp = P.out + (size_t)q_idx * 3;
               outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+              if (MOMENTS) {
+                double *outq = P.out_sq + (size_t)q_idx * 3;
+                outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
+              }
               have_pixel = false;
             }
             const uint32_t slot = wave_claim(P.work_counter);  // 64 consecutive list elements per wave claim
@@ -347,12 +357,17 @@
               if (px >= W || pr >= cam.image_height) {  // not a pixel of the image (the _device form): zeros, nothing traced
                 double *outp = P.out + (size_t)slot * 3;
                 outp[0] = 0.0, outp[1] = 0.0, outp[2] = 0.0;
+                if (MOMENTS) {
+                  double *outq = P.out_sq + (size_t)slot * 3;
+                  outq[0] = 0.0, outq[1] = 0.0, outq[2] = 0.0;
+                }
               } else {
                 have_pixel = true;
                 n = s_begin;
                 pix_rays = 0;
                 rng.pos = 0, rng.nres = 0;
                 sum = d3(0.0, 0.0, 0.0);
+                if (MOMENTS) sq = d3(0.0, 0.0, 0.0);
                 active = n < spp;
               }
             }
@@ -362,6 +377,10 @@
             size_t pix = (size_t)pr * W + px;
             double *outp = P.out + pix * 3;
             outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+            if (MOMENTS) {
+              double *outq = P.out_sq + pix * 3;
+              outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
+            }
             if (P.pos_state) P.pos_state[pix] = rng.pos;
             if (P.tile_cost) atomicAdd(&P.tile_cost[ptile], pix_rays);
             have_pixel = false;
@@ -388,10 +407,15 @@
                 size_t pix = (size_t)pr * W + px;
                 const double *inp = P.out + pix * 3;
                 sum = d3(inp[0], inp[1], inp[2]);
+                if (MOMENTS) {
+                  const double *inq = P.out_sq + pix * 3;
+                  sq = d3(inq[0], inq[1], inq[2]);
+                }
                 rng.pos = P.pos_state[pix];
               } else {
                 rng.pos = 0;
                 sum = d3(0.0, 0.0, 0.0);
+                if (MOMENTS) sq = d3(0.0, 0.0, 0.0);
               }
               rng.nres = 0;
               if (n >= (INDEP ? n_end : spp)) active = false;
@@ -536,7 +560,11 @@
 #endif
         D3 p = rec.p;
         if (!rec.any) {
-          sum = sum + thr * ld3(cam.background);
+          if constexpr (MOMENTS) {
+            const D3 c = thr * ld3(cam.background);
+            sum = sum + c;
+            sq = sq + c * c;
+          } else sum = sum + thr * ld3(cam.background);
           path_done = true;
         } else {
           const DevMaterial &m = P.materials[rec.mat];
@@ -588,7 +616,11 @@
               nd = perp + par;
             }
           } else if (kind == RL_MAT_DIFFUSE_LIGHT) {
-            sum = sum + thr * texc;
+            if constexpr (MOMENTS) {
+              const D3 c = thr * texc;
+              sum = sum + c;
+              sq = sq + c * c;
+            } else sum = sum + thr * texc;
             path_done = true;
           } else {
             path_done = true;

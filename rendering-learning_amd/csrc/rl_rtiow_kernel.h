@@ -90,7 +90,20 @@ struct RtiowParams {
   // pixel-list mode (PIXELS instantiations, rl_rtiow_render_pixels*): a slot is element i of the caller's list, pixel (pix_xs[i], pix_ys[i]) of
   // the whole frame (row_first = 0, row_step = 1); its sums go to out[i], never to out[y * W + x].  n_slots = the list's length.
   const uint32_t *pix_xs, *pix_ys;
+  // second moments (MOMENTS instantiations, rl_rtiow_render_moments* / rl_rtiow_render_pixels_moments*): per channel the
+  // sum of the squared sample colours, laid out as `out` and stored / re-loaded wherever `out` is.  Read by no other instantiation.
+  // (appended last, as everything since `stats`: the by-value kernels' kernarg offsets of everything above stay where they were)
+  double *out_sq;
 };
+
+// MOMENTS, the compile-time flavour of the chained render kernels that keeps second moments (P.out_sq), is `false` in every kernel without
+// it — spelled as a value that DEPENDS on a template parameter.  The bodies add a sample's colour under `if constexpr (MOMENTS) { name it,
+// add it, add its square } else { the statement the kernel has always had }`, and only a dependent condition makes the first branch a
+// discarded statement: nothing in it is instantiated, and the lambdas it stands in do not capture sq.  Measured with a plain `false` (and
+// with the colour named in both flavours): the headline kernel <1024, 4, false> came out with another register assignment (or three
+// instructions shorter), rtiow_fast_general_rays_kernel<768, 20, false, false> with one more spilled VGPR — and they stay exactly what they were.
+template <int>
+constexpr bool never_v = false;
 
 // RAYS: the path's colour, the cursor behind it and its ray count to the ray's own index
 __device__ __forceinline__ void rtiow_rays_store(const RtiowParams &P, uint64_t idx, const D3 &c, uint64_t stream, uint32_t pos, uint32_t rays) {

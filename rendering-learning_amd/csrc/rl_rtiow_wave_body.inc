@@ -1,5 +1,5 @@
-  // The body of rtiow_wave_kernel / rtiow_wave_indep_kernel (rl_rtiow_wave.h): included inside both kernels, with INDEP (and the
-  // kernel's template parameters) in scope.
+  // The body of rtiow_wave_kernel / rtiow_wave_indep_kernel / rtiow_wave_moments_kernel (rl_rtiow_wave.h): included inside all three, with
+  // INDEP and MOMENTS (and the kernel's template parameters) in scope.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   // LDS layout: [linked ops][spheres][ChaCha rings 16 x NT u64]; with the scene in HBM the rings start at 0
@@ -86,6 +86,7 @@
   uint32_t ptile = 0, pix_rays = 0;
   bool have_pixel = false;
   D3 sum = d3(0.0, 0.0, 0.0);
+  D3 sq = d3(0.0, 0.0, 0.0);  // MOMENTS: per channel the sum of the squared sample colours (each product rounded, then added), beside sum
   D3 o = d3(0.0, 0.0, 0.0), d = d3(0.0, 0.0, 1.0), thr = d3(1.0, 1.0, 1.0);
   RayAux ra = ray_aux(o, d);
   RayAux32 ra32 = ray_aux32(ra);
@@ -139,7 +140,11 @@
 #endif
       if (amb) pc = FAST_SLOW, state = ST_LEAF;
       else if (hit_prim == NONE) {  // a miss needs no SHADE visit: background (camera.rs:257), sample done (+10 %)
-        sum = sum + thr * ld3(P.cam.background);
+        if constexpr (MOMENTS) {
+          const D3 c = thr * ld3(P.cam.background);
+          sum = sum + c;
+          sq = sq + c * c;
+        } else sum = sum + thr * ld3(P.cam.background);
         n++;
         state = ST_GEN;
       } else state = shade_state();
@@ -175,7 +180,11 @@
         D3 nd = d;
         D3 p = o;
         if (MODE != 2 && hit_prim == NONE) {  // miss -> background (camera.rs:257)
-          sum = sum + thr * ld3(cam.background);
+          if constexpr (MOMENTS) {
+            const D3 c = thr * ld3(cam.background);
+            sum = sum + c;
+            sq = sq + c * c;
+          } else sum = sum + thr * ld3(cam.background);
           path_done = true;
         } else {
           uint32_t si = hit_prim & SPH_INDEX;
@@ -235,7 +244,11 @@
               nd = perp + par;
             }
           } else if (MODE != 2 && kind == RL_MAT_DIFFUSE_LIGHT) {
-            sum = sum + thr * (solid ? ld3(m.albedo) : texture_value(P, m.texture, 0.0, 0.0, p));
+            if constexpr (MOMENTS) {
+              const D3 c = thr * (solid ? ld3(m.albedo) : texture_value(P, m.texture, 0.0, 0.0, p));
+              sum = sum + c;
+              sq = sq + c * c;
+            } else sum = sum + thr * (solid ? ld3(m.albedo) : texture_value(P, m.texture, 0.0, 0.0, p));
             path_done = true;
           } else {
             path_done = true;  // Flat
@@ -470,6 +483,10 @@
             size_t pix = (size_t)pr * W + px;
             double *outp = P.out + pix * 3;
             outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+            if (MOMENTS) {
+              double *outq = P.out_sq + pix * 3;
+              outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
+            }
             if (STEAL && P.steal_state) atomicExch(&P.steal_state[pix], 3u);  // finished: a request that arrives now finds nothing to take
             if (P.pos_state) P.pos_state[pix] = rng.pos;               // resumable: the next launch continues this pixel
             if (P.tile_cost) atomicAdd(&P.tile_cost[ptile], pix_rays);  // cost estimate for the LPT order of the next launch
@@ -503,10 +520,15 @@
                 size_t pix = (size_t)pr * W + px;
                 const double *inp = P.out + pix * 3;
                 sum = d3(inp[0], inp[1], inp[2]);
+                if (MOMENTS) {
+                  const double *inq = P.out_sq + pix * 3;
+                  sq = d3(inq[0], inq[1], inq[2]);
+                }
                 rng.pos = P.pos_state[pix];
               } else {
                 rng.pos = 0;
                 sum = d3(0.0, 0.0, 0.0);
+                if (MOMENTS) sq = d3(0.0, 0.0, 0.0);
               }
               rng.nres = 0;
               if (n >= (INDEP ? n_end : spp)) active = false;

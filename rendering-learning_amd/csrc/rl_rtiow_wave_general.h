@@ -28,19 +28,19 @@ static const int MEDIA_SAVE_WORDS = 12;  // parked Rec: t, p, normal, u, v, w, {
 // INDEP: the sample-parallel mode, as in rtiow_wave_indep_kernel (rl_rtiow_wave.h; the body is included into both kernels for the same reason); rng_words are counted at every sample end
 template <int NT, bool TRANS, bool STATS, bool MEDIA = false>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_kernel(RtiowParams P) {
-  constexpr bool INDEP = false, RAYS = false, PIXELS = false;
+  constexpr bool INDEP = false, RAYS = false, PIXELS = false, MOMENTS = never_v<NT>;
 #include "rl_rtiow_wave_general_body.inc"
 }
 template <int NT, bool TRANS, bool STATS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_indep_kernel(RtiowParams P) {
-  constexpr bool INDEP = true, RAYS = false, PIXELS = false;
+  constexpr bool INDEP = true, RAYS = false, PIXELS = false, MOMENTS = never_v<NT>;
 #include "rl_rtiow_wave_general_body.inc"
 }
 // RAYS (rl_rtiow_ray_color_rays*): the reference-order form of the ray-buffer path query — counting calls, scenes without a
 // fast tree, RL_FAST=0.  A slot is one ray with its own RNG cursor; rng_words counts the words each path consumed.
 template <int NT, bool TRANS, bool STATS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_rays_kernel(RtiowParams P) {
-  constexpr bool INDEP = false, RAYS = true, PIXELS = false;
+  constexpr bool INDEP = false, RAYS = true, PIXELS = false, MOMENTS = never_v<NT>;
 #include "rl_rtiow_wave_general_body.inc"
 }
 // PIXELS (rl_rtiow_render_pixels*): a slot is one element of the caller's (x, y) list; the lane reads the pair once, runs the
@@ -49,7 +49,20 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_rays_ke
 // counter-free calls that have no fast path.
 template <int NT, bool TRANS, bool STATS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_pixels_kernel(RtiowParams P) {
-  constexpr bool INDEP = false, RAYS = false, PIXELS = true;
+  constexpr bool INDEP = false, RAYS = false, PIXELS = true, MOMENTS = never_v<NT>;
+#include "rl_rtiow_wave_general_body.inc"
+}
+// MOMENTS (rl_rtiow_render_moments* / rl_rtiow_render_pixels_moments*): the frame and the list kernel once more, keeping the
+// sum of the squared sample colours (P.out_sq) beside the sum.  The reference-order form: every counting moments call, every scene without
+// a fast tree, and every moments call that would otherwise land in a kernel that has no MOMENTS flavour.
+template <int NT, bool TRANS, bool STATS, bool MEDIA>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_moments_kernel(RtiowParams P) {
+  constexpr bool INDEP = false, RAYS = false, PIXELS = false, MOMENTS = true;
+#include "rl_rtiow_wave_general_body.inc"
+}
+template <int NT, bool TRANS, bool STATS, bool MEDIA>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_pixels_moments_kernel(RtiowParams P) {
+  constexpr bool INDEP = false, RAYS = false, PIXELS = true, MOMENTS = true;
 #include "rl_rtiow_wave_general_body.inc"
 }
 

@@ -1,5 +1,6 @@
   // The body of rtiow_wave_general_kernel / rtiow_wave_general_indep_kernel / rtiow_wave_general_rays_kernel / rtiow_wave_general_pixels_kernel
-  // (rl_rtiow_wave_general.h): included inside all four, with INDEP, RAYS, PIXELS (and the kernel's template parameters) in scope.
+  // and the two _moments_ kernels (rl_rtiow_wave_general.h): included inside all six, with INDEP, RAYS, PIXELS, MOMENTS (and the kernel's
+  // template parameters) in scope.
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   unsigned long long *s_rng = (unsigned long long *)smem;  // [16][NT]
@@ -20,6 +21,7 @@
   uint32_t ptile = 0, pix_rays = 0;
   bool have_pixel = false;
   D3 sum = d3(0.0, 0.0, 0.0);
+  D3 sq = d3(0.0, 0.0, 0.0);  // MOMENTS: per channel the sum of the squared sample colours (each product rounded, then added), beside sum
   D3 wo = d3(0.0, 0.0, 0.0), wd = d3(0.0, 0.0, 1.0);  // world ray
   D3 o = wo, d = wd;                                    // ray in the current instance scope
   D3 thr = d3(1.0, 1.0, 1.0);
@@ -233,6 +235,10 @@
             if (have_pixel) {
               double *outp = P.out + (size_t)q_idx * 3;
               outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+              if (MOMENTS) {
+                double *outq = P.out_sq + (size_t)q_idx * 3;
+                outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
+              }
               if (STATS) c_words += rng.pos;
               have_pixel = false;
             }
@@ -245,12 +251,17 @@
               if (px >= W || pr >= cam.image_height) {  // not a pixel of the image (the _device form): zeros, nothing traced
                 double *outp = P.out + (size_t)slot * 3;
                 outp[0] = 0.0, outp[1] = 0.0, outp[2] = 0.0;
+                if (MOMENTS) {
+                  double *outq = P.out_sq + (size_t)slot * 3;
+                  outq[0] = 0.0, outq[1] = 0.0, outq[2] = 0.0;
+                }
               } else {
                 have_pixel = true;
                 n = s_begin;
                 pix_rays = 0;
                 rng.pos = 0, rng.nres = 0;
                 sum = d3(0.0, 0.0, 0.0);
+                if (MOMENTS) sq = d3(0.0, 0.0, 0.0);
                 active = n < spp;
               }
             }
@@ -260,6 +271,10 @@
             size_t pix = (size_t)pr * W + px;
             double *outp = P.out + pix * 3;
             outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
+            if (MOMENTS) {
+              double *outq = P.out_sq + pix * 3;
+              outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
+            }
             if (P.pos_state) P.pos_state[pix] = rng.pos;
             if (P.tile_cost) atomicAdd(&P.tile_cost[ptile], pix_rays);
             if (STATS && !P.tile_cost) c_words += rng.pos;
@@ -287,10 +302,15 @@
                 size_t pix = (size_t)pr * W + px;
                 const double *inp = P.out + pix * 3;
                 sum = d3(inp[0], inp[1], inp[2]);
+                if (MOMENTS) {
+                  const double *inq = P.out_sq + pix * 3;
+                  sq = d3(inq[0], inq[1], inq[2]);
+                }
                 rng.pos = P.pos_state[pix];
               } else {
                 rng.pos = 0;
                 sum = d3(0.0, 0.0, 0.0);
+                if (MOMENTS) sq = d3(0.0, 0.0, 0.0);
               }
               rng.nres = 0;
               if (n >= (INDEP ? n_end : spp)) active = false;
@@ -333,7 +353,11 @@
         D3 nd = wd;
         D3 p = rec.p;
         if (!rec.any) {
-          sum = sum + thr * ld3(cam.background);
+          if constexpr (MOMENTS) {
+            const D3 c = thr * ld3(cam.background);
+            sum = sum + c;
+            sq = sq + c * c;
+          } else sum = sum + thr * ld3(cam.background);
           path_done = true;
         } else {
           const DevMaterial &m = P.materials[rec.mat];
@@ -387,7 +411,11 @@
               nd = perp + par;
             }
           } else if (kind == RL_MAT_DIFFUSE_LIGHT) {
-            sum = sum + thr * texc;
+            if constexpr (MOMENTS) {
+              const D3 c = thr * texc;
+              sum = sum + c;
+              sq = sq + c * c;
+            } else sum = sum + thr * texc;
             path_done = true;
           } else {
             path_done = true;

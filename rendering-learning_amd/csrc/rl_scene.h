@@ -149,13 +149,14 @@ void drop_multi_state();  // rl_multi.hip: RCCL communicators + the emulation fl
 
 // Launch-only halves of the render entry points (rl_render.hip): enqueue everything on `stream`, never synchronise.  The caller finishes
 // the render, holding scene->mu since the launch, with collect_stats (want_stats; synchronises the stream) or post_status.
+// d_out_sq (rl_rtiow_render_moments*, rl_rtiow_render_pixels_moments*): the second moments' buffer, laid out as d_out; null: a plain render
 int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, void *d_out,
-                        hipStream_t stream, bool want_stats);
+                        hipStream_t stream, bool want_stats, void *d_out_sq = nullptr);
 int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, uint32_t row_first, uint32_t row_step, void *d_out, hipStream_t stream,
                       bool want_stats, const uint32_t *d_xs = nullptr, const uint32_t *d_ys = nullptr, uint64_t n_list = 0);
 // pixel-list renders (rl_*_render_pixels*): n elements (d_xs[i], d_ys[i]) of the whole frame -> d_out[i]
 int rtiow_render_pixels_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const uint32_t *d_xs, const uint32_t *d_ys, uint64_t n,
-                               void *d_out, hipStream_t stream, bool want_stats, bool timed);
+                               void *d_out, hipStream_t stream, bool want_stats, bool timed, void *d_out_sq = nullptr);
 int rtc_render_pixels_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, const uint32_t *d_xs, const uint32_t *d_ys, uint64_t n, void *d_out,
                              hipStream_t stream, bool want_stats);
 int collect_stats(const rl_scene *scene, hipStream_t stream, rl_stats *st);  // RL_OK / RL_E_DEGENERATE / RL_E_DEVICE

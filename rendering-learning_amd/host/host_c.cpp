@@ -571,6 +571,23 @@ int rlh_render_pixels_probe(int family, uint64_t width, uint64_t spp_or_aa, cons
     return -1;
   }
 }
+// Renders with second moments through the C++ mirror: golden_test_scene at image_width = width, samples_per_pixel = spp.  n = 0:
+// rtiow::Camera::render_moments, sums and sq = W * H * 3 doubles each; n > 0: render_pixels_moments of the list, n * 3 doubles each.
+// 0 or -1 (rlh_last_error).
+int rlh_render_moments_probe(uint64_t width, uint64_t spp, const uint32_t *xs, const uint32_t *ys, uint64_t n, double *sums, double *sq) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    s.params.image_width = (size_t)width, s.params.samples_per_pixel = (size_t)spp;
+    rtiow::Camera cam(s.params);
+    rtiow::Camera::Moments m = n ? cam.render_pixels_moments(*s.world, xs, ys, (size_t)n) : cam.render_moments(*s.world);
+    std::memcpy(sums, m.sums.data(), m.sums.size() * sizeof(double));
+    std::memcpy(sq, m.sq.data(), m.sq.size() * sizeof(double));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
 // which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
 // b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,

@@ -52,6 +52,33 @@ std::vector<double> Camera::render_pixels(const Hittable &world, const uint32_t 
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_pixels: ") + rl_last_error());
   return out;
 }
+Camera::Moments Camera::render_moments(const Hittable &world, uint64_t first_sample) const {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  rl_rtiow_camera cam = derived();
+  const size_t n = params.image_width * image_height * 3;
+  Moments m{params.samples_per_pixel, std::vector<double>(n), std::vector<double>(n)};
+  int rc = rl_rtiow_render_moments_rows(sc, &cam, first_sample, 0, 1, m.sums.data(), m.sq.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_moments_rows: ") + rl_last_error());
+  return m;
+}
+Camera::Moments Camera::render_pixels_moments(const Hittable &world, const uint32_t *xs, const uint32_t *ys, size_t n, uint64_t first_sample) const {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  rl_rtiow_camera cam = derived();
+  Moments m{params.samples_per_pixel, std::vector<double>(n * 3), std::vector<double>(n * 3)};
+  int rc = rl_rtiow_render_pixels_moments(sc, &cam, first_sample, xs, ys, n, m.sums.data(), m.sq.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_pixels_moments: ") + rl_last_error());
+  return m;
+}
 Canvas Camera::render_independent(const Hittable &world) const { return render_independent_impl(*this, world, nullptr); }
 Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
   return render_independent_impl(*this, world, &checkpoint);

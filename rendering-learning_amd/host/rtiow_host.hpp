@@ -799,6 +799,15 @@ struct Camera {
   // the pixels of the caller's choosing (rl_rtiow_render_pixels): out[3 i ..] = the sums _render(first_sample, world) leaves at pixel
   // (xs[i], ys[i]), bit for bit, for any list (unsorted, duplicates); a pixel outside the image throws
   std::vector<double> render_pixels(const Hittable &world, const uint32_t *xs, const uint32_t *ys, size_t n, uint64_t first_sample = 0) const;
+  // renders with second moments (rl_rtiow_render_moments_rows, rl_rtiow_render_pixels_moments): `sums` is what _render(first_sample, world) /
+  // render_pixels leaves, bit for bit; `sq` holds, laid out the same way, per channel the sum of the squared sample colours (sq = sq + c * c
+  // in sample order).  (sq - sums^2 / n) / (n - 1) / n estimates the variance of a pixel's mean: what an adaptive pass picks its pixels by.
+  struct Moments {
+    size_t samples;
+    std::vector<double> sums, sq;  // [H][W][3] (render_moments) / [n][3] (render_pixels_moments)
+  };
+  Moments render_moments(const Hittable &world, uint64_t first_sample = 0) const;
+  Moments render_pixels_moments(const Hittable &world, const uint32_t *xs, const uint32_t *ys, size_t n, uint64_t first_sample = 0) const;
   // Camera::get_ray(&mut rng, x, y) (camera.rs:203-216) for a batch of pixels, on the GPU (rl_rtiow_camera_rays): rng_i as for
   // ray_color_rays with seed = params.seed; cursors[i] is advanced behind the draws.  _render's stream of sample s at pixel (x, y) is
   // s * W * H + x * W + y (camera.rs:161-170).
