@@ -5,13 +5,15 @@
 //                                every element, the draws taken from the element's own cursor
 //   rtiow_texture_values_kernel  Texture::value(u, v, &p) (texture.rs) for a buffer of (texture id, uv, p)
 //
-// The material arithmetic is the renders' SHADE block (rl_rtiow_wave_general_body.inc, rl_rtiow_fastgen_body.inc) restated here,
-// expression for expression: a host loop of rl_rtiow_hit_rays + rl_rtiow_scatter_rays reproduces rl_rtiow_ray_color_rays bit for bit
-// (tests/test_gpu_material_query.py), and the render kernels carry none of this code.  One element per lane, grid-stride over the batch;
+// The material arithmetic is material_texture + material_scatter (rl_rtiow_scatter.h), the same inlined statement the general renders' SHADE
+// blocks use: a host loop of rl_rtiow_hit_rays + rl_rtiow_scatter_rays reproduces rl_rtiow_ray_color_rays bit for bit
+// (tests/test_gpu_material_query.py).  What is this kernel's own is the record packing, the cursors and the lazy stream start; the render
+// kernels carry none of that.  One element per lane, grid-stride over the batch;
 // the lane's ChaCha8 blocks live in a Ring column (ODD: a cursor may stand at any word), regenerated for every element that draws.
 // Records move as whole 8-byte words.  MATERIAL_QUERY_MAX_BLOCKS_PER_CU bounds the grid: a batch beyond it puts several elements, each
 // on its own stream, through one lane.
 #pragma once
+#include "rl_rtiow_scatter.h"
 #include "rl_rtiow_wave.h"
 
 namespace rl {
@@ -33,6 +35,26 @@ struct MaterialQuery {
   const double *uv;  // [n][2]
   const double *p;   // [n][3]
   double *rgb;       // [n][3]
+};
+
+// The query's draws for material_scatter: the element's two blocks are generated just before its first draw, so an element that draws
+// nothing generates none
+template <class RingT>
+struct LazyDraws {
+  RingT &rng;
+  uint64_t stream;
+  bool started;
+  __device__ __forceinline__ void start() {
+    if (!started) rng.reset_stream(stream), started = true;
+  }
+  __device__ __forceinline__ D3 unit_sphere() {
+    start();
+    return rng.unit_sphere();
+  }
+  __device__ __forceinline__ double gen_f64() {
+    start();
+    return rng.gen_f64();
+  }
 };
 
 // P: the scene's material / texture / image / Perlin tables, key (expanded from the call's seed) and stats ([0] elements with a hit,
@@ -64,64 +86,18 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_scatter_rays_kernel(
     const bool front = (uint32_t)(hw9 >> 32) != 0u;
     const D3 p = d3(h[1], h[2], h[3]);
     const DevMaterial &m = P.materials[mat];
-    const uint32_t kind = m.kind;
-    // texture first (it draws no random numbers): acos / atan2 are the caller's already (hit.u, hit.v), sin and Perlin for Noise are
-    // register-hungry, so they run before the scatter temporaries are live
-    D3 texc = d3(0.0, 0.0, 0.0);
-    if (kind == RL_MAT_LAMBERTIAN || kind == RL_MAT_DIFFUSE_LIGHT || kind == RL_MAT_ISOTROPIC) texc = texture_value<2>(P, m.texture, h[7], h[8], p);
+    // (acos / atan2 are the caller's already: hit.u, hit.v)
+    const D3 texc = material_texture<true>(m, [&](uint32_t tex) { return texture_value<2>(P, tex, h[7], h[8], p); });
     const D3 normal = d3(h[4], h[5], h[6]);
     const double *r = (const double *)(Q.rays + idx);
     const D3 wd = d3(r[3], r[4], r[5]);
     const double time = r[6];
     rng.stream = stream, rng.pos = (uint32_t)word_pos, rng.nres = 0;
-    D3 att = d3(0.0, 0.0, 0.0), emitted = d3(0.0, 0.0, 0.0), nd = d3(0.0, 0.0, 0.0);
-    bool some = false;
-    if (kind == RL_MAT_ISOTROPIC) {  // material.rs:201-214: Vec3::random_unit_vector, attenuation = texture.value(uv, p)
-      rng.reset_stream(stream);
-      nd = rng.unit_sphere();
-      att = texc, some = true;
-    } else if (kind == RL_MAT_LAMBERTIAN) {
-      rng.reset_stream(stream);
-      D3 dir = normal + rng.unit_sphere();
-      bool near_zero = approx_eq_eps(dir.x, 0.0, 1e-8) && approx_eq_eps(dir.y, 0.0, 1e-8) && approx_eq_eps(dir.z, 0.0, 1e-8);
-      nd = near_zero ? normal : dir;
-      att = texc, some = true;
-    } else if (kind == RL_MAT_METAL) {
-      rng.reset_stream(stream);
-      D3 reflected = wd - normal * (2.0 * dot(wd, normal));
-      nd = normalize(reflected) + rng.unit_sphere() * m.fuzz;
-      if (dot(nd, normal) > 0.0) att = ld3(m.albedo), some = true;  // (an absorbed reflection has consumed its draws all the same)
-    } else if (kind == RL_MAT_DIELECTRIC) {
-      double ri = front ? 1.0 / m.ior : m.ior;
-      double m2 = len2(wd);
-      D3 ud;
-      if (approx_eq_eps(m2, 0.0, 1e-16)) {  // material.rs:150-151 would panic: flagged, and on with the renders' value
-        c_flag++;
-        ud = wd;
-      } else
-        ud = normalize(wd);
-      double cos_theta = fmin(dot(-ud, normal), 1.0);
-      double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
-      bool reflect = ri * sin_theta > 1.0;
-      if (!reflect) {
-        double q = (1.0 - ri) / (1.0 + ri);
-        double r0 = q * q;
-        double xx = 1.0 - cos_theta;
-        double x2 = xx * xx;
-        double refl = r0 + (1.0 - r0) * (xx * (x2 * x2));
-        rng.reset_stream(stream);
-        reflect = refl > rng.gen_f64();
-      }
-      if (reflect) nd = ud - normal * (2.0 * dot(ud, normal));
-      else {
-        D3 perp = (ud + normal * cos_theta) * ri;
-        D3 par = normal * (-sqrt(fabs(1.0 - len2(perp))));
-        nd = perp + par;
-      }
-      att = d3(1.0, 1.0, 1.0), some = true;
-    } else if (kind == RL_MAT_DIFFUSE_LIGHT) {
-      emitted = texc;
-    }
+    LazyDraws<decltype(rng)> draws{rng, stream, false};
+    const Scatter s = material_scatter<true>(m, wd, normal, front, [&] { return texc; }, draws);  // (an absorbed reflection has consumed its draws all the same)
+    if (s.flagged) c_flag++;  // on with the renders' value
+    const bool some = s.what == SCATTER_RAY;
+    const D3 att = s.att, emitted = s.emitted, nd = s.dir;  // (att, emitted: zeros unless a ray was scattered / light emitted; nd is written only if `some`)
     c_words += rng.pos - (uint32_t)word_pos;
     out[0] = att.x, out[1] = att.y, out[2] = att.z;
     out[3] = emitted.x, out[4] = emitted.y, out[5] = emitted.z;

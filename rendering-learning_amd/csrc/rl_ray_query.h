@@ -56,9 +56,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_kernel(Rtio
     const D3 o = ld3(ray.origin), d = ld3(ray.dir);
     const double time = ray.time;
     c_rays++;
-    Rec rec;
-    rec.t = Q.tmax, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
-    rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+    Rec rec = rec_none(Q.tmax);
     GenCounters gc{0, 0, 0, 0, 0};
     auto draw = []() { return 0.0; };  // media are rejected on the host (a bare ray has no RNG stream to draw from)
     general_trace<STATS, false, true>(P, ops, 0u, NONE, o, d, o, d, time, Q.tmin, rec, gc, draw);
@@ -111,9 +109,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_seeded_kern
     const double time = ray.time;
     c_rays++;
     rng.stream = stream, rng.pos = (uint32_t)word_pos, rng.nres = 0;
-    Rec rec;
-    rec.t = Q.tmax, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
-    rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+    Rec rec = rec_none(Q.tmax);
     GenCounters gc{0, 0, 0, 0, 0};
     auto draw = [&]() {
       if (rng.nres == 0u) rng.reset_stream(stream);  // the ray's first draw: blocks pos / 16 and the next one
@@ -260,9 +256,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_fast_kernel
       if (nh >= 2) push(c1);
       e = nh ? c0 : pop();
     }
-    Rec rec;
-    rec.t = Q.tmax, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
-    rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+    Rec rec = rec_none(Q.tmax);
     uint32_t hit_flags = 0;
     if (!amb && best != NONE) {  // the winner's HitRecord: the same test once more with ray_t.max = its root, then the POP chain
       const FastItem it = items[best];
@@ -290,25 +284,10 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_fast_kernel
         if (planar_hit_rec(P.planars[it.payload], it.op_pc, o, d, rec)) hit_flags++;
       }
       if (!amb && !rec.any) amb = true;  // (cannot happen: the same arithmetic found this root)
-      uint32_t push_pc = amb ? NONE : it.chain;
-#pragma unroll 1
-      while (push_pc != NONE) {
-        const DevOp &op = ops[push_pc];
-        if ((op.code & 0xFFu) == OP_PUSH_TRANSLATE) rec.p = rec.p + ld3(P.translates[op.a].offset);
-        else {
-          const rl_transform &t = P.transforms[op.a];
-          rec.p = mat3_mul(t.m, rec.p);
-          D3 wn = mat3_mul(t.inv_t, rec.normal);
-          double m = len2(wn);
-          if (approx_eq_eps(m, 0.0, 1e-16)) hit_flags++;
-          else rec.normal = normalize(wn);
-        }
-        push_pc = op.b;
-      }
+      hit_flags += pop_rec_chain(P, ops, amb ? NONE : it.chain, rec);
     }
     if (amb) {  // the reference's own fold decides
-      rec.t = Q.tmax, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
-      rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+      rec = rec_none(Q.tmax);
       GenCounters gc{0, 0, 0, 0, 0};
       auto draw = []() { return 0.0; };
       general_trace<false, false, true>(P, ops, 0u, NONE, wo, wd, wo, wd, time, 1e-10, rec, gc, draw);

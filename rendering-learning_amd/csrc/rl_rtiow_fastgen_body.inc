@@ -453,6 +453,11 @@
       if (state == ST_SHADE) {
         bool path_done = false;
         D3 nd = wd;
+        // This SHADE block keeps its own text of what the other kernels share — the empty record (rec_none), the two POP chains
+        // (pop_rec_chain; general_slow_trace's POP likewise) and Material::scatter (rl_rtiow_scatter.h) — because this is the kernel
+        // of the cow and stress configs and each shared form measured slower there than the parent's slowest run: scatter + 1.2 %,
+        // the POP + 0.2 %, rec_none + 0.1 % in one run of two (profiles/scatter_refactor.txt).  tests/test_gpu_scatter_forms.py and
+        // test_gpu_fuzz_general.py hold this text and the shared one together, bit for bit.
         Rec rec;
         rec.t = INF, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
         rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
@@ -543,9 +548,7 @@
         }
 #ifdef RL_FASTG_VERIFY
         {
-          Rec r2;
-          r2.t = INF, r2.any = false, r2.pc = 0, r2.mat = 0, r2.u = 0.0, r2.v = 0.0, r2.w = 0.0, r2.uv3 = false, r2.front = true;
-          r2.p = d3(0.0, 0.0, 0.0), r2.normal = d3(0.0, 0.0, 0.0);
+          Rec r2 = rec_none(INF);
           general_slow_trace<TRANS>(P, ops, wo, wd, time, r2);
           bool same = rec.any == r2.any && (!rec.any || (rec.t == r2.t && rec.pc == r2.pc && rec.p.x == r2.p.x && rec.normal.y == r2.normal.y));
           if (!same) {

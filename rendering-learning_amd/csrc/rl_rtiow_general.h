@@ -11,7 +11,8 @@
 // the world ray — the same arithmetic as the first time, so bit-identical — which keeps traversal
 // stackless.
 #pragma once
-#include "rl_rtiow_wave.h"  // RayAux / aabb_fast (filtered AABB test with exact fallback)
+#include "rl_rtiow_scatter.h"  // Material::scatter, the one statement
+#include "rl_rtiow_wave.h"     // RayAux / aabb_fast (filtered AABB test with exact fallback)
 
 namespace rl {
 
@@ -35,6 +36,14 @@ struct Rec {  // hittable/mod.rs:24-30 HitRecord + the material id
   uint32_t pc;  // op where it was found (instance scope test)
   bool front, any, uv3;
 };
+
+// no hit yet, ray_t.max = tmax: what every trace starts from
+__device__ __forceinline__ Rec rec_none(double tmax) {
+  Rec rec;
+  rec.t = tmax, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
+  rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+  return rec;
+}
 
 __device__ __forceinline__ void face_normal(D3 d, D3 outward, D3 &normal, bool &front) {  // hittable/mod.rs:32-38
   front = dot(d, outward) <= 0.0;
@@ -132,6 +141,35 @@ __device__ __forceinline__ void replay_chain(const RtiowParams &P, const DevOp *
       o = no, d = nd;
     }
   }
+}
+
+// One POP: the hit record found inside a Translate (translate.rs:18) / Transform (transform.rs:152-161) scope, back in its parent's space
+// (p, normal; t and face are NOT recomputed).  `a`: the instance's index (a PUSH op and its POP carry the same).  Returns the flag:
+// "Instance normal couldn't be normalized" would have panicked, and the normal stays as it was.
+__device__ __forceinline__ bool pop_rec(const RtiowParams &P, bool translate, uint32_t a, Rec &rec) {
+  if (translate) {
+    rec.p = rec.p + ld3(P.translates[a].offset);
+    return false;
+  }
+  const rl_transform &t = P.transforms[a];
+  rec.p = mat3_mul(t.m, rec.p);
+  D3 wn = mat3_mul(t.inv_t, rec.normal);
+  double m = len2(wn);
+  if (approx_eq_eps(m, 0.0, 1e-16)) return true;
+  rec.normal = normalize(wn);
+  return false;
+}
+
+// The POPs of the chain of PUSH ops that ends at `push_pc`, innermost first, as the reference's recursion unwinds; returns the flags
+__device__ __forceinline__ uint32_t pop_rec_chain(const RtiowParams &P, const DevOp *ops, uint32_t push_pc, Rec &rec) {
+  uint32_t flags = 0;
+#pragma unroll 1
+  while (push_pc != NONE) {
+    const DevOp &op = ops[push_pc];
+    if (pop_rec(P, (op.code & 0xFFu) == OP_PUSH_TRANSLATE, op.a, rec)) flags++;
+    push_pc = op.b;
+  }
+  return flags;
 }
 
 struct GenCounters {
@@ -252,22 +290,21 @@ __device__ __forceinline__ void general_trace(const RtiowParams &P, const DevOp 
     }
     // POP: op.b = pc of the matching PUSH, whose .b is the parent PUSH
     uint32_t push_pc = op.b;
-    if (rec.any && rec.pc > push_pc) {  // the current closest hit was found inside this instance
-      if (code == OP_POP_TRANSLATE) rec.p = rec.p + ld3(P.translates[op.a].offset);  // translate.rs:18
-      else {                                                                              // transform.rs:152-161
-        const rl_transform &t = P.transforms[op.a];
-        rec.p = mat3_mul(t.m, rec.p);
-        D3 wn = mat3_mul(t.inv_t, rec.normal);
-        double m = len2(wn);
-        if (approx_eq_eps(m, 0.0, 1e-16)) gc.flagged++;  // "Instance normal couldn't be normalized"
-        else rec.normal = normalize(wn);
-      }
-    }
+    if (rec.any && rec.pc > push_pc && pop_rec(P, code == OP_POP_TRANSLATE, op.a, rec)) gc.flagged++;  // the closest hit was found inside this instance
     replay_chain(P, ops, ops[push_pc].b, wo, wd, o, d);
     ra = ray_aux(o, d);
     pc++;
   }
 }
+
+// the general kernel's draws for material_scatter
+template <int NT>
+struct RngDraws {
+  const RngCtx<NT> &rc;
+  Rng &rng;
+  __device__ __forceinline__ D3 unit_sphere() { return rc.unit_sphere(rng); }
+  __device__ __forceinline__ double gen_f64() { return rc.gen_f64(rng); }
+};
 
 // REGS_FOR: the workgroup size the register budget is computed for (2 NT: two waves per SIMD, what the launcher uses)
 template <int NT, bool STATS, int REGS_FOR>
@@ -317,9 +354,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_general_kernel
       D3 color = d3(0.0, 0.0, 0.0);
       for (uint32_t depth = cam.max_depth; depth > 0; depth--) {
         c_rays++;
-        Rec rec;
-        rec.t = INF, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
-        rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+        Rec rec = rec_none(INF);
         {
           GenCounters gc{0, 0, 0, 0, 0};
           auto draw = [&]() { return rc.gen_f64(rng); };
@@ -331,64 +366,19 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtiow_general_kernel
           break;
         }
         const DevMaterial &m = P.materials[rec.mat];
-          // texture first (it draws no random numbers): the transcendental code in here (acos / atan2 for sphere UVs, sin and
-          // Perlin for Noise) is register-hungry, so it runs before the scatter temporaries are live
-          D3 texc = d3(0.0, 0.0, 0.0);
-          if (m.kind == RL_MAT_LAMBERTIAN || m.kind == RL_MAT_DIFFUSE_LIGHT) {
-            double tu, tv;
-            rec_uv(rec, tu, tv);
-            texc = texture_value<2>(P, m.texture, tu, tv, rec.p);
-          }
-        uint32_t kind = m.kind;
-        D3 normal = rec.normal, p = rec.p;
-        D3 nd;
-        if (kind == RL_MAT_ISOTROPIC) {  // material.rs:201-214: Vec3::random_unit_vector, attenuation = texture.value(uv, p)
-          nd = rc.unit_sphere(rng);
-          thr = thr * texture_value<2>(P, m.texture, rec.u, rec.v, rec.p);
-        } else if (kind == RL_MAT_LAMBERTIAN) {
-          D3 dir = normal + rc.unit_sphere(rng);
-          bool near_zero = approx_eq_eps(dir.x, 0.0, 1e-8) && approx_eq_eps(dir.y, 0.0, 1e-8) && approx_eq_eps(dir.z, 0.0, 1e-8);
-          nd = near_zero ? normal : dir;
-          thr = thr * texc;
-        } else if (kind == RL_MAT_METAL) {
-          D3 reflected = wd - normal * (2.0 * dot(wd, normal));
-          nd = normalize(reflected) + rc.unit_sphere(rng) * m.fuzz;
-          if (!(dot(nd, normal) > 0.0)) break;
-          thr = thr * ld3(m.albedo);
-        } else if (kind == RL_MAT_DIELECTRIC) {
-          double ri = rec.front ? 1.0 / m.ior : m.ior;
-          double m2 = len2(wd);
-          D3 ud;
-          if (approx_eq_eps(m2, 0.0, 1e-16)) {
-            c_flag++;
-            ud = wd;
-          } else
-            ud = normalize(wd);
-          double cos_theta = fmin(dot(-ud, normal), 1.0);
-          double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
-          bool reflect = ri * sin_theta > 1.0;
-          if (!reflect) {
-            double q = (1.0 - ri) / (1.0 + ri);
-            double r0 = q * q;
-            double xx = 1.0 - cos_theta;
-            double x2 = xx * xx;
-            double refl = r0 + (1.0 - r0) * (xx * (x2 * x2));
-            reflect = refl > rc.gen_f64(rng);
-          }
-          if (reflect) nd = ud - normal * (2.0 * dot(ud, normal));
-          else {
-            D3 perp = (ud + normal * cos_theta) * ri;
-            D3 par = normal * (-sqrt(fabs(1.0 - len2(perp))));
-            nd = perp + par;
-          }
-        } else if (kind == RL_MAT_DIFFUSE_LIGHT) {
-          color = color + thr * texc;
-          break;
-        } else {
-          break;
-        }
-        wo = p;
-        wd = nd;
+        const D3 texc = material_texture<true>(m, [&](uint32_t tex) {
+          double tu, tv;
+          rec_uv(rec, tu, tv);
+          return texture_value<2>(P, tex, tu, tv, rec.p);
+        });
+        RngDraws<NT> draws{rc, rng};
+        const Scatter s = material_scatter<true>(m, wd, rec.normal, rec.front, [&] { return texc; }, draws);
+        if (s.flagged) c_flag++;
+        if (s.what == SCATTER_EMITTED) color = color + thr * s.emitted;
+        if (s.what != SCATTER_RAY) break;
+        thr = thr * s.att;
+        wo = rec.p;
+        wd = s.dir;
       }
       sum = sum + color;
     }

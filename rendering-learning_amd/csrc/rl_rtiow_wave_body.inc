@@ -174,6 +174,7 @@
 
   // SHADE: miss -> background; hit -> rebuild the HitRecord, scatter, next ray.  MODE 0 = every material (reference-order kernels),
   // 1 = everything but Metal / Dielectric, 2 = Metal / Dielectric only (ST_SHADE2): the fast kernel's two halves
+  // (the generic statement of Material::scatter is rl_rtiow_scatter.h; this one stays its own: flattened sphere records, hoisted us / vn, the SHADE2 split)
   auto shade = [&](auto mode) {
     constexpr int MODE = decltype(mode)::value;
         bool path_done = false;

@@ -27,9 +27,7 @@
   D3 thr = d3(1.0, 1.0, 1.0);
   RayAux ra = ray_aux(o, d);
   double time = 0.0;
-  Rec rec;
-  rec.t = INF, rec.any = false, rec.pc = 0, rec.mat = 0, rec.u = 0.0, rec.v = 0.0, rec.w = 0.0, rec.uv3 = false, rec.front = true;
-  rec.p = d3(0.0, 0.0, 0.0), rec.normal = d3(0.0, 0.0, 0.0);
+  Rec rec = rec_none(INF);
   uint32_t pc = 0, depth = 0;
   uint32_t c_rays = 0, c_flag = 0;
   unsigned long long c_nodes = 0, c_sph = 0, c_pl = 0, c_inst = 0, c_words = 0;
@@ -168,17 +166,7 @@
           o = no, d = nd;
         } else {  // POP: op.b = the matching PUSH, whose .b is the parent PUSH
           uint32_t push_pc = op.b;
-          if (rec.any && rec.pc > push_pc) {
-            if (kind == OP_POP_TRANSLATE) rec.p = rec.p + ld3(P.translates[op.a].offset);
-            else {
-              const rl_transform &t = P.transforms[op.a];
-              rec.p = mat3_mul(t.m, rec.p);
-              D3 wn = mat3_mul(t.inv_t, rec.normal);
-              double m = len2(wn);
-              if (approx_eq_eps(m, 0.0, 1e-16)) c_flag++;
-              else rec.normal = normalize(wn);
-            }
-          }
+          if (rec.any && rec.pc > push_pc && pop_rec(P, kind == OP_POP_TRANSLATE, op.a, rec)) c_flag++;
           replay_chain(P, ops, ops[push_pc].b, wo, wd, o, d);
         }
         ra = ray_aux(o, d);
@@ -361,63 +349,22 @@
           path_done = true;
         } else {
           const DevMaterial &m = P.materials[rec.mat];
-          // texture first (it draws no random numbers): the transcendental code in here (acos / atan2 for sphere UVs, sin and
-          // Perlin for Noise) is register-hungry, so it runs before the scatter temporaries are live
-          D3 texc = d3(0.0, 0.0, 0.0);
-          if (m.kind == RL_MAT_LAMBERTIAN || m.kind == RL_MAT_DIFFUSE_LIGHT || (MEDIA && m.kind == RL_MAT_ISOTROPIC)) {
+          const D3 texc = material_texture<MEDIA>(m, [&](uint32_t tex) {
             double tu, tv;
             rec_uv<TRANS>(rec, tu, tv);
-            texc = texture_value<(TRANS ? 2 : 1)>(P, m.texture, tu, tv, rec.p);
-          }
-          uint32_t kind = m.kind;
-          D3 normal = rec.normal;
-          if (MEDIA && kind == RL_MAT_ISOTROPIC) {  // material.rs:201-214: Vec3::random_unit_vector, attenuation = texture.value(uv, p)
-            nd = rng.unit_sphere();
-            thr = thr * texc;
-          } else if (kind == RL_MAT_LAMBERTIAN) {
-            D3 dir = normal + rng.unit_sphere();
-            bool near_zero = approx_eq_eps(dir.x, 0.0, 1e-8) && approx_eq_eps(dir.y, 0.0, 1e-8) && approx_eq_eps(dir.z, 0.0, 1e-8);
-            nd = near_zero ? normal : dir;
-            thr = thr * texc;
-          } else if (kind == RL_MAT_METAL) {
-            D3 reflected = wd - normal * (2.0 * dot(wd, normal));
-            nd = normalize(reflected) + rng.unit_sphere() * m.fuzz;
-            if (!(dot(nd, normal) > 0.0)) path_done = true;
-            else thr = thr * ld3(m.albedo);
-          } else if (kind == RL_MAT_DIELECTRIC) {
-            double ri = rec.front ? 1.0 / m.ior : m.ior;
-            double m2 = len2(wd);
-            D3 ud;
-            if (approx_eq_eps(m2, 0.0, 1e-16)) {
-              c_flag++;
-              ud = wd;
-            } else
-              ud = normalize(wd);
-            double cos_theta = fmin(dot(-ud, normal), 1.0);
-            double sin_theta = sqrt(1.0 - cos_theta * cos_theta);
-            bool reflect = ri * sin_theta > 1.0;
-            if (!reflect) {
-              double q = (1.0 - ri) / (1.0 + ri);
-              double r0 = q * q;
-              double xx = 1.0 - cos_theta;
-              double x2 = xx * xx;
-              double refl = r0 + (1.0 - r0) * (xx * (x2 * x2));
-              reflect = refl > rng.gen_f64();
+            return texture_value<(TRANS ? 2 : 1)>(P, tex, tu, tv, rec.p);
+          });
+          const Scatter s = material_scatter<MEDIA>(m, wd, rec.normal, rec.front, [&] { return texc; }, rng);
+          if (s.flagged) c_flag++;
+          if (s.what == SCATTER_RAY) thr = thr * s.att, nd = s.dir;
+          else {
+            if (s.what == SCATTER_EMITTED) {
+              if constexpr (MOMENTS) {
+                const D3 c = thr * s.emitted;
+                sum = sum + c;
+                sq = sq + c * c;
+              } else sum = sum + thr * s.emitted;
             }
-            if (reflect) nd = ud - normal * (2.0 * dot(ud, normal));
-            else {
-              D3 perp = (ud + normal * cos_theta) * ri;
-              D3 par = normal * (-sqrt(fabs(1.0 - len2(perp))));
-              nd = perp + par;
-            }
-          } else if (kind == RL_MAT_DIFFUSE_LIGHT) {
-            if constexpr (MOMENTS) {
-              const D3 c = thr * texc;
-              sum = sum + c;
-              sq = sq + c * c;
-            } else sum = sum + thr * texc;
-            path_done = true;
-          } else {
             path_done = true;
           }
         }
