@@ -489,6 +489,45 @@ int rl_rtiow_render_pixels_moments_device(const rl_scene *, const rl_rtiow_camer
                                           uint64_t n, void *d_out_rgb_sum, void *d_out_rgb_sq, void *hip_stream, rl_stats *opt_stats);
 
 /* =====================================================================
+ *  Adaptive renders: every pixel stops, inside the launch, once its variance estimate is below the caller's bound
+ * =====================================================================
+ * rl_rtiow_render_moments_rows / _device once more, with a stopping rule.  A pixel is rendered exactly as the chained render renders it
+ * (streams, the word position carried from sample to sample, sum and sq as "Second moments" defines them; first_sample only shifts the
+ * streams).  Let n be the number of samples OF THIS CALL accumulated so far.  At a checkpoint n = min_samples + k * check_every (k >= 0)
+ * with n < cam->samples_per_pixel the pixel's three channels c are tested, in binary64, every operation rounded on its own (no FMA), in
+ * exactly this order:
+ *     nd  = (double)n
+ *     s2  = sum_c * sum_c
+ *     lhs = (nd * sq_c) - s2
+ *     rhs = (nd - 1.0) * ((abs_variance * (nd * nd)) + (rel_variance * s2))
+ *     ok_c = lhs <= rhs
+ * and the pixel stops at the first checkpoint where ok_r && ok_g && ok_b; otherwise it runs to samples_per_pixel.  A NaN in any term
+ * makes ok_c false: the pixel runs on.  Algebraically the rule is  variance of the mean <= abs_variance + rel_variance * mean^2,
+ * multiplied through by n^2 (n - 1): no division, so that a host can reproduce every count to the bit.
+ * Outputs per pixel, laid out as the plain call's pixels: out_rgb_sum and out_rgb_sq (3 f64 each), out_count (one uint32: the samples
+ * taken).  For every pixel sum and sq are bit for bit what rl_rtiow_render_moments_rows writes for it when the camera's
+ * samples_per_pixel equals the pixel's count: a prefix of a chain is the chain of a shorter render.  min_samples >= samples_per_pixel
+ * never reaches a checkpoint: the moments call's bytes, and count == samples_per_pixel everywhere.
+ * RL_E_INVALID, outputs untouched: a NULL rule, a NULL output, min_samples < 2, check_every == 0, a negative or NaN bound.  Everything
+ * else follows the moments calls: _rows always counts, _device is asynchronous unless opt_stats is given; a counting call takes the
+ * reference-order kernel and its seven counters are the reference's for exactly the samples rendered (each pixel's count);
+ * rl_render_status, rl_rtiow_render_progress and per-scene serialisation as for the plain renders; no CPU fallback (RL_E_NO_DEVICE,
+ * outputs untouched).
+ * Not offered: pixel-list forms, the independent-sample renders, the multi-GPU renders, rgb8 output, the RTC family; the cooperative
+ * one-wave-per-pixel kernel has no adaptive mode (its small frames run in the wave-scheduled kernel: same bits). */
+typedef struct rl_rtiow_adaptive {
+  uint32_t min_samples;  /* >= 2: the first checkpoint                                   */
+  uint32_t check_every;  /* >= 1: checkpoints at n = min_samples + k * check_every, k >= 0 */
+  double abs_variance;   /* >= 0                                                          */
+  double rel_variance;   /* >= 0                                                          */
+} rl_rtiow_adaptive;
+int rl_rtiow_render_adaptive_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                  const rl_rtiow_adaptive *rule, double *out_rgb_sum, double *out_rgb_sq, uint32_t *out_count, rl_stats *opt_stats);
+int rl_rtiow_render_adaptive_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                    const rl_rtiow_adaptive *rule, void *d_out_rgb_sum, void *d_out_rgb_sq, void *d_out_count, void *hip_stream,
+                                    rl_stats *opt_stats);
+
+/* =====================================================================
  *  Batched ray queries: the reference's per-ray primitives on the device
  * =====================================================================
  *   rl_rtiow_hit_rays*      <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval) -> Option<(&Material, HitRecord)>

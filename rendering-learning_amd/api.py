@@ -211,7 +211,8 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtc_prepare_rays", "rl_rtc_prepare_rays_device", "rl_rtc_shade_hits", "rl_rtc_shade_hits_device",
                   "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device",
                   "rl_rtiow_render_pixels", "rl_rtiow_render_pixels_device", "rl_rtc_render_pixels", "rl_rtc_render_pixels_device",
-                  "rl_rtiow_render_moments_rows", "rl_rtiow_render_moments_device", "rl_rtiow_render_pixels_moments", "rl_rtiow_render_pixels_moments_device"]
+                  "rl_rtiow_render_moments_rows", "rl_rtiow_render_moments_device", "rl_rtiow_render_pixels_moments", "rl_rtiow_render_pixels_moments_device",
+                  "rl_rtiow_render_adaptive_rows", "rl_rtiow_render_adaptive_device"]
 
 
 def _material_query_argtypes(L):
@@ -257,6 +258,17 @@ def _render_moments_argtypes(L):
                                                  C.POINTER(Stats)]
     L.rl_rtiow_render_pixels_moments_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                         C.c_void_p, C.POINTER(Stats)]
+
+
+class RtiowAdaptive(C.Structure):  # rl_rtiow_adaptive
+    _fields_ = [("min_samples", C.c_uint32), ("check_every", C.c_uint32), ("abs_variance", C.c_double), ("rel_variance", C.c_double)]
+
+
+def _render_adaptive_argtypes(L):
+    L.rl_rtiow_render_adaptive_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowAdaptive), C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+    L.rl_rtiow_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowAdaptive), C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
 
 
 def _pixel_list(xs, ys):
@@ -329,6 +341,8 @@ def render_lib():
             _render_pixels_argtypes(L)
         if hasattr(L, "rl_rtiow_render_moments_rows"):  # (likewise)
             _render_moments_argtypes(L)
+        if hasattr(L, "rl_rtiow_render_adaptive_rows"):  # (likewise)
+            _render_adaptive_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -394,6 +408,12 @@ def set_fast_traversal(on):
 def set_coop(on):
     """Tests / tools: counter-free renders of SMALL frames of sphere scenes use the cooperative one-wave-per-pixel kernel unless switched off."""
     render_lib().rl_debug_set_coop(int(bool(on)))
+
+
+def set_lpt(on):
+    """rl_debug_set_lpt: the cost-sorted two-launch render of the wave kernels (samples [0, 8), sort, resume; 64 spp and more) on / off.
+    Same bits either way; tests take both paths."""
+    render_lib().rl_debug_set_lpt(int(bool(on)))
 
 
 def set_coop_pixels_max(n):
@@ -1073,6 +1093,26 @@ class Moments:
         return np.maximum((self.sq - self.sums * self.sums / n) / (n - 1) / n, 0.0)
 
 
+@dataclass
+class Adaptive:
+    """The outputs of an adaptive render (Camera.render_adaptive): per pixel the number of samples it took before the stopping rule
+    (include/rl_render.h "Adaptive renders") let it stop, and the sums and second moments of exactly those samples — what Moments holds for a
+    render of that many samples.  With a row shard the arrays hold the shard's rows."""
+    sums: np.ndarray = field(repr=False)    # [H, W, 3] f64
+    sq: np.ndarray = field(repr=False)      # [H, W, 3] f64
+    counts: np.ndarray = field(repr=False)  # [H, W] uint32
+
+    def mean(self) -> np.ndarray:
+        return self.sums / self.counts[..., None]
+
+    def variance_of_mean(self) -> np.ndarray:
+        """Moments.variance_of_mean with every pixel's own n: (sq - sums^2 / n) / (n - 1) / n, clipped at 0.  Needs n >= 2 everywhere."""
+        n = self.counts[..., None].astype(np.float64)
+        if (self.counts < 2).any():
+            raise ValueError("variance_of_mean needs at least 2 samples in every pixel")
+        return np.maximum((self.sq - self.sums * self.sums / n) / (n - 1) / n, 0.0)
+
+
 class Camera:
     def __init__(self, params: CameraParams):  # Camera::new camera.rs:72
         self.params = params
@@ -1278,6 +1318,37 @@ class Camera:
         st = Stats() if stats is not None else None
         rc = render_lib().rl_rtiow_render_pixels_moments_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
                                                                 C.c_void_p(d_sums), C.c_void_p(d_sq), C.c_void_p(stream), C.byref(st) if st is not None else None)
+        _check(rc)
+        if stats is not None:
+            stats.update(st.as_dict())
+
+    # ---- adaptive renders (include/rl_render.h rl_rtiow_render_adaptive*): render_moments with a stopping rule evaluated inside the launch.
+    # A pixel stops at the first checkpoint n = min_samples + k * check_every (n < samples_per_pixel) at which, in every channel,
+    # n * sq - sum^2 <= (n - 1) * (abs_variance * n^2 + rel_variance * sum^2): variance of the mean <= abs_variance + rel_variance * mean^2
+    def render_adaptive(self, world: World, min_samples, check_every, abs_variance=0.0, rel_variance=0.0, first_sample=0, row_first=0, row_step=1, stats=None,
+                        allow_degenerate=False) -> Adaptive:
+        """Every pixel's sums and sq are render_moments' for a camera of counts[pixel] samples, bit for bit."""
+        nrows = rows_for(self.c.image_height, row_first, row_step)
+        sums = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
+        sq = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
+        counts = np.empty((nrows, self.c.image_width), dtype=np.uint32)
+        rule = RtiowAdaptive(min_samples, check_every, abs_variance, rel_variance)
+        st = Stats()
+        rc = render_lib().rl_rtiow_render_adaptive_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(rule), sums.ctypes.data,
+                                                        sq.ctypes.data, counts.ctypes.data, C.byref(st))
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+        return Adaptive(sums, sq, counts)
+
+    def render_adaptive_device(self, world: World, min_samples, check_every, d_sums, d_sq, d_counts, abs_variance=0.0, rel_variance=0.0, stream=0, row_first=0,
+                               row_step=1, first_sample=0, stats=None):
+        """All three outputs stay in HBM: d_sums, d_sq = device pointers of nrows*W*3 f64 each, d_counts of nrows*W uint32.  Async unless stats is a dict."""
+        rule = RtiowAdaptive(min_samples, check_every, abs_variance, rel_variance)
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_adaptive_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(rule), C.c_void_p(d_sums),
+                                                          C.c_void_p(d_sq), C.c_void_p(d_counts), C.c_void_p(stream), C.byref(st) if st is not None else None)
         _check(rc)
         if stats is not None:
             stats.update(st.as_dict())

@@ -692,6 +692,14 @@ static void route_moments_variant(RtiowChoice &choice, bool want_stats) {
   if (v == 2 || (want_stats && v != 4)) choice.variant = 4;
 }
 
+// Where an ADAPTIVE frame (rl_rtiow_render_adaptive*) goes: where the moments frame goes (the stopping rule is a runtime
+// mode of the MOMENTS wave, fast general and reference-order kernels), except that the cooperative one-wave-per-pixel kernel has no such
+// mode: its small frames, and a forced 1033, take the fast layout of the wave kernel (every scene of 1033 has it; paths deeper than its
+// depth field take the reference-order kernel).  Never work stealing: no moments call steals.
+static void route_adaptive_variant(RtiowChoice &choice, const rl_rtiow_camera *cam) {
+  if (choice.variant == 1033) choice.variant = cam->max_depth > FAST_DEPTH_MASK ? 4 : 1029;
+}
+
 // Variant 1029 only: the per-pixel entry table of this render's camera and rows (rl_pixel_entry.h), built on `stream` ahead of the render
 // kernels into the scene's own buffer (grown on demand, like d_pos).  Nothing is kept from call to call: the camera may differ.
 static int build_pixel_entry(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream) {
@@ -720,7 +728,7 @@ static int stage_params(const rl_scene *scene, const RtiowParams &P, hipStream_t
 
 namespace rl {
 int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, void *d_out,
-                        hipStream_t stream, bool want_stats, void *d_out_sq) {
+                        hipStream_t stream, bool want_stats, void *d_out_sq, const rl_rtiow_adaptive *rule, void *d_out_count) {
   const RtiowProgram &rt = scene->rt();
   const HostRtiow &H = *scene->hrt;
   uint32_t H_ = cam->image_height, W = cam->image_width;
@@ -733,6 +741,8 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
   }
   const bool moments = d_out_sq != nullptr;  // the MOMENTS instantiations: second moments beside the sums, same layout
   P.out_sq = (double *)d_out_sq;
+  const bool adaptive = moments && rule && d_out_count;  // the MOMENTS frame kernels' runtime mode: pixels stop by the rule, counts beside the moments
+  if (adaptive) P.out_count = (uint32_t *)d_out_count, P.adapt = *rule, P.adapt_total = cam->samples_per_pixel;
 
   {
     int rco = order_after_previous(scene, stream);
@@ -778,6 +788,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     if (rcv != RL_OK) return rcv;
   }
   if (moments) route_moments_variant(choice, want_stats);
+  if (adaptive) route_adaptive_variant(choice, cam);
   const int variant = choice.variant;
   const size_t compact_bytes = choice.compact_bytes, fast_bytes = choice.fast_bytes;
   if (variant == 1029) {
@@ -1313,6 +1324,23 @@ int rl_rtiow_render_moments_device(const rl_scene *scene, const rl_rtiow_camera 
   return render_run(scene, stream, st, [&] { return rl::rtiow_render_launch(scene, cam, first_sample, row_first, row_step, d_out, stream, st != nullptr, d_out_sq); });
 }
 
+// Adaptive renders (include/rl_render.h "Adaptive renders"): the moments call with a stopping rule and a third buffer, the
+// per-pixel sample counts.  What the rule itself can be wrong by is refused first, device or not.
+static bool adaptive_rule_ok(const rl_rtiow_adaptive *rule) {
+  return rule && rule->min_samples >= 2 && rule->check_every >= 1 && rule->abs_variance >= 0.0 && rule->rel_variance >= 0.0;  // (a NaN bound compares false)
+}
+int rl_rtiow_render_adaptive_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                    const rl_rtiow_adaptive *rule, void *d_out, void *d_out_sq, void *d_out_count, void *hip_stream, rl_stats *st) {
+  if (!adaptive_rule_ok(rule) || !d_out || !d_out_sq || !d_out_count) return set_err(RL_E_INVALID, "bad argument");
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), row_step != 0, row_first, "empty image", st, done);
+  if (done) return rc;
+  hipStream_t stream = (hipStream_t)hip_stream;
+  return render_run(scene, stream, st, [&] {
+    return rl::rtiow_render_launch(scene, cam, first_sample, row_first, row_step, d_out, stream, st != nullptr, d_out_sq, rule, d_out_count);
+  });
+}
+
 int rl_rtiow_render_pixels_moments_device(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const void *d_xs, const void *d_ys, uint64_t n,
                                           void *d_out, void *d_out_sq, void *hip_stream, rl_stats *st) {
   bool done;
@@ -1667,6 +1695,20 @@ int rl_rtiow_render_moments_rows(const rl_scene *scene, const rl_rtiow_camera *c
   if (q.rc != RL_OK) return q.rc;
   rl_stats local;
   return q.finish(rl_rtiow_render_moments_device(scene, cam, first_sample, row_first, row_step, d_out, d_out_sq, q.stream, &local), st, local);
+}
+
+int rl_rtiow_render_adaptive_rows(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                  const rl_rtiow_adaptive *rule, double *out, double *out_sq, uint32_t *out_count, rl_stats *st) {
+  if (!adaptive_rule_ok(rule) || !out || !out_sq || !out_count) return set_err(RL_E_INVALID, "bad argument");
+  bool done;
+  int rc = render_check(scene, 1, frame_of(cam), row_step != 0, row_first, nullptr, st, done);
+  if (done) return rc;
+  HostStaging q(scene);
+  const size_t bytes = frame_of(cam).rows_bytes(row_first, row_step);
+  void *d_out = q.out(out, bytes), *d_out_sq = q.out(out_sq, bytes), *d_out_count = q.out(out_count, bytes / (3 * sizeof(double)) * sizeof(uint32_t));
+  if (q.rc != RL_OK) return q.rc;
+  rl_stats local;
+  return q.finish(rl_rtiow_render_adaptive_device(scene, cam, first_sample, row_first, row_step, rule, d_out, d_out_sq, d_out_count, q.stream, &local), st, local);
 }
 
 int rl_rtiow_render_pixels_moments(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys, uint64_t n,

@@ -200,7 +200,8 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_pixels_
 #include "rl_rtiow_fastgen_body.inc"
 }
 // MOMENTS (rl_rtiow_render_moments* / rl_rtiow_render_pixels_moments*): the frame and the list kernel once more, keeping the
-// sum of the squared sample colours (P.out_sq) beside the sum — stored, resumed and zeroed wherever the sum is.
+// sum of the squared sample colours (P.out_sq) beside the sum — stored, resumed and zeroed wherever the sum is.  With P.out_count set
+// (rl_rtiow_render_adaptive*) a pixel of the frame kernel also ends at the first checkpoint rtiow_adaptive_stop accepts.
 template <int NT, int SD, bool TRANS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_fast_general_moments_kernel(const RtiowParams *__restrict__ Pp) {
   constexpr bool INDEP = false, RAYS = false, PIXELS = false, MOMENTS = true;

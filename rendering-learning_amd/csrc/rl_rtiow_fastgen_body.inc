@@ -337,6 +337,10 @@
           if (n >= n_end) have_pixel = false;
           else rng.pos = 0, rng.nres = 0, sum = d3(0.0, 0.0, 0.0);
         }
+        // adaptive renders (P.out_count, the MOMENTS frame kernel only): the pixel is also finished at the first checkpoint where its variance
+        // estimate is below the caller's bound
+        bool stop = false;
+        if constexpr (MOMENTS && !PIXELS) stop = P.out_count && have_pixel && rtiow_adaptive_stop(P.adapt, P.adapt_total, n, sum, sq);
         if constexpr (PIXELS) {  // a work item is element q_idx of the caller's pixel list: (x, y) read once, compact output, no tiles / resume
           if (n >= spp) {
             if (have_pixel) {
@@ -372,18 +376,21 @@
               }
             }
           }
-        } else if (n >= (INDEP ? n_end : spp)) {
+        } else if (stop || n >= (INDEP ? n_end : spp)) {
           if (have_pixel) {
             size_t pix = (size_t)pr * W + px;
             double *outp = P.out + pix * 3;
             outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
-            if (MOMENTS) {
+            if constexpr (MOMENTS) {
               double *outq = P.out_sq + pix * 3;
               outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
+              // its sample count: n where it stopped; the call's total otherwise — also from the first of two launches, whose resume launch tells by that which pixels to continue
+              if (P.out_count) P.out_count[pix] = stop ? n : P.adapt_total;
             }
             if (P.pos_state) P.pos_state[pix] = rng.pos;
             if (P.tile_cost) atomicAdd(&P.tile_cost[ptile], pix_rays);
             have_pixel = false;
+            if (stop) n = spp;  // (a lane whose next slot lies outside the image claims again at its next visit)
           }
           uint32_t slot = wave_claim(P.work_counter);
           if (slot >= P.n_slots) {
@@ -407,9 +414,10 @@
                 size_t pix = (size_t)pr * W + px;
                 const double *inp = P.out + pix * 3;
                 sum = d3(inp[0], inp[1], inp[2]);
-                if (MOMENTS) {
+                if constexpr (MOMENTS) {
                   const double *inq = P.out_sq + pix * 3;
                   sq = d3(inq[0], inq[1], inq[2]);
+                  if (P.out_count && P.out_count[pix] != P.adapt_total) have_pixel = false, n = spp;  // stopped in the first launch: not resumed
                 }
                 rng.pos = P.pos_state[pix];
               } else {

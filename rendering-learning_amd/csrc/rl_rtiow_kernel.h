@@ -94,6 +94,13 @@ struct RtiowParams {
   // sum of the squared sample colours, laid out as `out` and stored / re-loaded wherever `out` is.  Read by no other instantiation.
   // (appended last, as everything since `stats`: the by-value kernels' kernarg offsets of everything above stay where they were)
   double *out_sq;
+  // adaptive renders (rl_rtiow_render_adaptive*; a runtime mode of the MOMENTS frame kernels): out_count non-null = a pixel
+  // stops at the first checkpoint of `adapt` that rtiow_adaptive_stop (rl_rtiow_adaptive.h) accepts, and its sample count goes to
+  // out_count[pix], laid out as the pixels of `out`.  adapt_total = the call's samples_per_pixel, whatever [sample_begin, sample_end) this
+  // launch renders.  Null: today's moments render.  Read by no other instantiation.
+  uint32_t *out_count;
+  rl_rtiow_adaptive adapt;
+  uint32_t adapt_total;
 };
 
 // MOMENTS, the compile-time flavour of the chained render kernels that keeps second moments (P.out_sq), is `false` in every kernel without

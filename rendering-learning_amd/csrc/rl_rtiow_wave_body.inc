@@ -479,14 +479,20 @@
           if (n >= n_end) have_pixel = false;
           else rng.pos = 0, rng.nres = 0, sum = d3(0.0, 0.0, 0.0);
         }
-        if (n >= (INDEP ? n_end : spp)) {  // pixel finished (or none yet): write it out, claim the next slot
+        // adaptive renders (P.out_count, MOMENTS only): the pixel is also finished at the first checkpoint where its variance estimate is below the caller's bound
+        bool stop = false;
+        if constexpr (MOMENTS) stop = P.out_count && have_pixel && rtiow_adaptive_stop(P.adapt, P.adapt_total, n, sum, sq);
+        if (stop || n >= (INDEP ? n_end : spp)) {  // pixel finished (or none yet): write it out, claim the next slot
           if (have_pixel) {
             size_t pix = (size_t)pr * W + px;
             double *outp = P.out + pix * 3;
             outp[0] = sum.x, outp[1] = sum.y, outp[2] = sum.z;
-            if (MOMENTS) {
+            if constexpr (MOMENTS) {
               double *outq = P.out_sq + pix * 3;
               outq[0] = sq.x, outq[1] = sq.y, outq[2] = sq.z;
+              // its sample count: n where it stopped; the call's total otherwise — also from the first of two launches, whose resume launch tells by that which pixels to continue
+              if (P.out_count) P.out_count[pix] = stop ? n : P.adapt_total;
+              if (stop) n = spp;  // (a lane whose next slot lies outside the image claims again at its next visit)
             }
             if (STEAL && P.steal_state) atomicExch(&P.steal_state[pix], 3u);  // finished: a request that arrives now finds nothing to take
             if (P.pos_state) P.pos_state[pix] = rng.pos;               // resumable: the next launch continues this pixel
@@ -521,9 +527,10 @@
                 size_t pix = (size_t)pr * W + px;
                 const double *inp = P.out + pix * 3;
                 sum = d3(inp[0], inp[1], inp[2]);
-                if (MOMENTS) {
+                if constexpr (MOMENTS) {
                   const double *inq = P.out_sq + pix * 3;
                   sq = d3(inq[0], inq[1], inq[2]);
+                  if (P.out_count && P.out_count[pix] != P.adapt_total) have_pixel = false, n = spp;  // stopped in the first launch: not resumed
                 }
                 rng.pos = P.pos_state[pix];
               } else {

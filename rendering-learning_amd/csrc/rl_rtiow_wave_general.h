@@ -54,7 +54,8 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_pixels_
 }
 // MOMENTS (rl_rtiow_render_moments* / rl_rtiow_render_pixels_moments*): the frame and the list kernel once more, keeping the
 // sum of the squared sample colours (P.out_sq) beside the sum.  The reference-order form: every counting moments call, every scene without
-// a fast tree, and every moments call that would otherwise land in a kernel that has no MOMENTS flavour.
+// a fast tree, and every moments call that would otherwise land in a kernel that has no MOMENTS flavour.  With P.out_count set
+// (rl_rtiow_render_adaptive*) a pixel of the frame kernel also ends at the first checkpoint rtiow_adaptive_stop accepts.
 template <int NT, bool TRANS, bool STATS, bool MEDIA>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_wave_general_moments_kernel(RtiowParams P) {
   constexpr bool INDEP = false, RAYS = false, PIXELS = false, MOMENTS = true;

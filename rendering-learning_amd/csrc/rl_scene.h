@@ -150,8 +150,9 @@ void drop_multi_state();  // rl_multi.hip: RCCL communicators + the emulation fl
 // Launch-only halves of the render entry points (rl_render.hip): enqueue everything on `stream`, never synchronise.  The caller finishes
 // the render, holding scene->mu since the launch, with collect_stats (want_stats; synchronises the stream) or post_status.
 // d_out_sq (rl_rtiow_render_moments*, rl_rtiow_render_pixels_moments*): the second moments' buffer, laid out as d_out; null: a plain render
+// rule, d_out_count (rl_rtiow_render_adaptive*, with d_out_sq): the stopping rule and the per-pixel sample counts; null: every pixel takes all its samples
 int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, void *d_out,
-                        hipStream_t stream, bool want_stats, void *d_out_sq = nullptr);
+                        hipStream_t stream, bool want_stats, void *d_out_sq = nullptr, const rl_rtiow_adaptive *rule = nullptr, void *d_out_count = nullptr);
 int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, uint32_t row_first, uint32_t row_step, void *d_out, hipStream_t stream,
                       bool want_stats, const uint32_t *d_xs = nullptr, const uint32_t *d_ys = nullptr, uint64_t n_list = 0);
 // pixel-list renders (rl_*_render_pixels*): n elements (d_xs[i], d_ys[i]) of the whole frame -> d_out[i]

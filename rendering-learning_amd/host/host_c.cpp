@@ -588,6 +588,24 @@ int rlh_render_moments_probe(uint64_t width, uint64_t spp, const uint32_t *xs, c
     return -1;
   }
 }
+// An adaptive render through the C++ mirror: golden_test_scene at image_width = width, samples_per_pixel = spp, rtiow::Camera::render_adaptive
+// with the given rule.  sums and sq = W * H * 3 doubles each, counts = W * H uint32.  0 or -1 (rlh_last_error).
+int rlh_render_adaptive_probe(uint64_t width, uint64_t spp, uint32_t min_samples, uint32_t check_every, double abs_variance, double rel_variance, double *sums,
+                              double *sq, uint32_t *counts) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    s.params.image_width = (size_t)width, s.params.samples_per_pixel = (size_t)spp;
+    rtiow::Camera cam(s.params);
+    rtiow::Camera::Adaptive a = cam.render_adaptive(*s.world, rl_rtiow_adaptive{min_samples, check_every, abs_variance, rel_variance});
+    std::memcpy(sums, a.sums.data(), a.sums.size() * sizeof(double));
+    std::memcpy(sq, a.sq.data(), a.sq.size() * sizeof(double));
+    std::memcpy(counts, a.counts.data(), a.counts.size() * sizeof(uint32_t));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
 // which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
 // b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,

@@ -79,6 +79,20 @@ Camera::Moments Camera::render_pixels_moments(const Hittable &world, const uint3
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_pixels_moments: ") + rl_last_error());
   return m;
 }
+Camera::Adaptive Camera::render_adaptive(const Hittable &world, const rl_rtiow_adaptive &rule, uint64_t first_sample) const {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  rl_rtiow_camera cam = derived();
+  const size_t n = params.image_width * image_height;
+  Adaptive a{std::vector<double>(n * 3), std::vector<double>(n * 3), std::vector<uint32_t>(n)};
+  int rc = rl_rtiow_render_adaptive_rows(sc, &cam, first_sample, 0, 1, &rule, a.sums.data(), a.sq.data(), a.counts.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_adaptive_rows: ") + rl_last_error());
+  return a;
+}
 Canvas Camera::render_independent(const Hittable &world) const { return render_independent_impl(*this, world, nullptr); }
 Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
   return render_independent_impl(*this, world, &checkpoint);

@@ -808,6 +808,14 @@ struct Camera {
   };
   Moments render_moments(const Hittable &world, uint64_t first_sample = 0) const;
   Moments render_pixels_moments(const Hittable &world, const uint32_t *xs, const uint32_t *ys, size_t n, uint64_t first_sample = 0) const;
+  // an adaptive render (rl_rtiow_render_adaptive_rows): render_moments in which every pixel stops, inside the launch, at the first
+  // checkpoint of `rule` where its variance estimate is below the rule's bound; counts[pixel] = the samples it took, and its sums and sq are
+  // render_moments' for a camera of that many samples, bit for bit
+  struct Adaptive {
+    std::vector<double> sums, sq;   // [H][W][3]
+    std::vector<uint32_t> counts;   // [H][W]
+  };
+  Adaptive render_adaptive(const Hittable &world, const rl_rtiow_adaptive &rule, uint64_t first_sample = 0) const;
   // Camera::get_ray(&mut rng, x, y) (camera.rs:203-216) for a batch of pixels, on the GPU (rl_rtiow_camera_rays): rng_i as for
   // ray_color_rays with seed = params.seed; cursors[i] is advanced behind the draws.  _render's stream of sample s at pixel (x, y) is
   // s * W * H + x * W + y (camera.rs:161-170).
