@@ -528,6 +528,66 @@ int rl_rtiow_render_adaptive_device(const rl_scene *, const rl_rtiow_camera *, u
                                     rl_stats *opt_stats);
 
 /* =====================================================================
+ *  Feature renders: first-hit albedo, normal and depth sums, the guide buffers of a denoiser
+ * =====================================================================
+ * One launch traces cam->samples_per_pixel jittered camera rays per pixel to their FIRST hit and keeps four sums.  Let the pixel be
+ * (x, y) of the camera's whole frame, F = first_sample, S = cam->samples_per_pixel, W x H the frame.  For s = F, F+1, .., F+S-1, in
+ * this order:
+ *     rng  = ChaCha8Rng::seed_from_u64(cam->seed), set_stream(s*W*H + x*W + y), word position 0
+ *     ray  = Camera::get_ray(&mut rng, x, y)                 -- what rl_rtiow_camera_rays returns for that cursor
+ *     hit  = world.hit(&ray, &Interval{1e-10, +inf}), media drawing from rng
+ *                                                            -- what rl_rtiow_hit_rays_seeded returns for (ray, cursor behind get_ray)
+ *     if hit.hit:  m = materials[hit.material]
+ *                  a = Lambertian, Isotropic, DiffuseLight: textures[m.texture].value(hit.u, hit.v, &hit.p)
+ *                      Metal: m.albedo        Dielectric: (1, 1, 1)        Flat / any other kind: (0, 0, 0)
+ *                  nrm = hit.normal;  d = hit.t;  k = 1
+ *     else:        a = cam->background;  nrm = (0, 0, 0);  d = 0.0;  k = 0
+ *     albedo_sum = albedo_sum + a;  normal_sum = normal_sum + nrm;  depth_sum = depth_sum + d;  hit_count += k
+ * All four sums start at +0.0 / 0; binary64, every add rounded on its own (no FMA).  So the host composition of rl_rtiow_camera_rays,
+ * rl_rtiow_hit_rays_seeded and rl_rtiow_texture_values with a left-to-right fold reproduces every output bit for bit.
+ * What follows from the definition:
+ *  - Same camera rays as the beauty image: these are the camera rays of rl_rtiow_render_independent* sample for sample, and of the first
+ *    sample of every chained render.
+ *  - Every first vertex is covered by `a`, the factor the first vertex puts on the path: attenuation where it scatters (a Metal's albedo
+ *    whether or not the fuzzed reflection is absorbed), emission where it emits, background where it misses.  beauty / albedo is defined
+ *    wherever the beauty is nonzero.
+ *  - Normal and depth are the reference's record fields: a ConstantMedium gives normal (1, 0, 0); t is the ray parameter and `dir` is
+ *    not normalised.
+ *  - A pixel's values depend on nothing but the pixel, F, S, the camera and the scene: row shards and pixel lists give the frame's bits.
+ *  - cam->max_depth is not read.
+ *  - Sums of calls that continue each other (first_sample) add; the added result is not promised to be bit-equal to one longer call.
+ * Layout is that of the plain calls: compact shard rows for _rows and _device ([nrows][W]), out[i] for the lists.  Each pointer of
+ * rl_rtiow_features is optional; an output that is not asked for is not written, and the others have the same bits.  The plain forms
+ * take host pointers in the struct, the _device forms device pointers and a hipStream_t; those are asynchronous unless opt_stats is given.
+ * Errors.  A NULL struct or one whose four pointers are all NULL: RL_E_INVALID, before anything else is looked at (so also without a
+ * device), outputs untouched; then, without a device, RL_E_NO_DEVICE (no CPU fallback), outputs untouched; then the plain calls' own
+ * rules (a NULL scene or camera, row_step 0, an RTC scene, an empty image: RL_E_INVALID).  Pixel lists follow rl_rtiow_render_pixels*:
+ * unsorted, duplicates allowed, n = 0 is RL_OK, the host form refuses a pixel outside the image, the _device form writes zeros to every
+ * given output for such an element and traces nothing; n >= 0xFFFF0000: RL_E_INVALID; under rl_init_multi device 0's replica.  A reached
+ * panic site sets flagged and returns RL_E_DEGENERATE with every output written.
+ * Stats.  With opt_stats all seven counters are the reference's for exactly these S * pixels rays, the nested boundary traces of media
+ * included (reference-order trace); rng_words = the words get_ray and the media consumed.  Without it the call is counter-free, may take
+ * the fast walk and gives the same bits.  _rows always counts, as rl_rtiow_render_rows does.  rl_render_status covers the asynchronous
+ * forms, each call counting once, rays = S * pixels.  Per-scene serialisation as for every render; rl_rtiow_render_progress reports
+ * nothing for these calls, as for the independent renders.
+ * Not offered: multi-GPU forms, rgb8 output, the RTC family (rl_rtc_prepare_rays on pixel-centre rays already returns point, normal, t
+ * and object colour in one call), and features of a chained render's later samples (their camera rays depend on the path before them). */
+typedef struct rl_rtiow_features { /* each pointer optional; all NULL: RL_E_INVALID */
+  double *albedo_sum;  /* [n][3] */
+  double *normal_sum;  /* [n][3] */
+  double *depth_sum;   /* [n]    */
+  uint32_t *hit_count; /* [n]    */
+} rl_rtiow_features;
+int rl_rtiow_render_features_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                  const rl_rtiow_features *out, rl_stats *opt_stats);
+int rl_rtiow_render_features_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                    const rl_rtiow_features *d_out, void *hip_stream, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_features(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys,
+                                    uint64_t n, const rl_rtiow_features *out, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_features_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs, const void *d_ys,
+                                           uint64_t n, const rl_rtiow_features *d_out, void *hip_stream, rl_stats *opt_stats);
+
+/* =====================================================================
  *  Batched ray queries: the reference's per-ray primitives on the device
  * =====================================================================
  *   rl_rtiow_hit_rays*      <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval) -> Option<(&Material, HitRecord)>

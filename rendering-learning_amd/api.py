@@ -18,6 +18,7 @@ import ctypes as C
 import os
 import threading
 from dataclasses import dataclass, field
+from typing import Optional
 
 import numpy as np
 
@@ -212,7 +213,9 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device",
                   "rl_rtiow_render_pixels", "rl_rtiow_render_pixels_device", "rl_rtc_render_pixels", "rl_rtc_render_pixels_device",
                   "rl_rtiow_render_moments_rows", "rl_rtiow_render_moments_device", "rl_rtiow_render_pixels_moments", "rl_rtiow_render_pixels_moments_device",
-                  "rl_rtiow_render_adaptive_rows", "rl_rtiow_render_adaptive_device"]
+                  "rl_rtiow_render_adaptive_rows", "rl_rtiow_render_adaptive_device",
+                  "rl_rtiow_render_features_rows", "rl_rtiow_render_features_device", "rl_rtiow_render_pixels_features",
+                  "rl_rtiow_render_pixels_features_device"]
 
 
 def _material_query_argtypes(L):
@@ -269,6 +272,23 @@ def _render_adaptive_argtypes(L):
                                                 C.c_void_p, C.c_void_p, C.POINTER(Stats)]
     L.rl_rtiow_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowAdaptive), C.c_void_p,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
+
+
+class RtiowFeatures(C.Structure):  # rl_rtiow_features: each pointer optional (None), all None is refused
+    _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p)]
+
+
+FEATURE_OUTPUTS = ("albedo_sum", "normal_sum", "depth_sum", "hit_count")
+
+
+def _render_features_argtypes(L):
+    L.rl_rtiow_render_features_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowFeatures), C.POINTER(Stats)]
+    L.rl_rtiow_render_features_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowFeatures), C.c_void_p,
+                                                  C.POINTER(Stats)]
+    L.rl_rtiow_render_pixels_features.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RtiowFeatures),
+                                                  C.POINTER(Stats)]
+    L.rl_rtiow_render_pixels_features_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                         C.POINTER(RtiowFeatures), C.c_void_p, C.POINTER(Stats)]
 
 
 def _pixel_list(xs, ys):
@@ -343,6 +363,8 @@ def render_lib():
             _render_moments_argtypes(L)
         if hasattr(L, "rl_rtiow_render_adaptive_rows"):  # (likewise)
             _render_adaptive_argtypes(L)
+        if hasattr(L, "rl_rtiow_render_features_rows"):  # (likewise)
+            _render_features_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -569,13 +591,13 @@ def set_query_pass_cap(rays):
 
 
 def last_query():
-    """rl_debug_last_query: which kernel served the most recent hit_rays* / ray_color_rays* call ("fast" / "reference") and, for a synchronous call, how
-    many of its rays the fast walk re-traced in the reference's order."""
+    """rl_debug_last_query: which kernel served the most recent hit_rays* / ray_color_rays* call ("fast" / "reference") or render_features* call
+    ("features_fast" / "features_reference") and, for a synchronous call, how many of its rays the fast walk re-traced in the reference's order."""
     out = (C.c_uint64 * 2)()
     L = render_lib()
     L.rl_debug_last_query.argtypes = [C.c_void_p]
     _check(L.rl_debug_last_query(out))
-    return {"kernel": {1: "reference", 2: "fast"}.get(int(out[0]), "none"), "retraced": int(out[1])}
+    return {"kernel": {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast"}.get(int(out[0]), "none"), "retraced": int(out[1])}
 
 
 def material_query_max_lanes():
@@ -585,6 +607,15 @@ def material_query_max_lanes():
     L.rl_debug_material_query_lanes.restype = C.c_uint64
     L.rl_debug_material_query_lanes.argtypes = []
     return int(L.rl_debug_material_query_lanes())
+
+
+def features_max_lanes():
+    """rl_debug_features_lanes: the most lanes one render_features* launch has on the current device; a frame or list with more pixels puts
+    several pixels through one lane."""
+    L = render_lib()
+    L.rl_debug_features_lanes.restype = C.c_uint64
+    L.rl_debug_features_lanes.argtypes = []
+    return int(L.rl_debug_features_lanes())
 
 
 def _records_arg(a, dtype, n, what):
@@ -1113,6 +1144,56 @@ class Adaptive:
         return np.maximum((self.sq - self.sums * self.sums / n) / (n - 1) / n, 0.0)
 
 
+@dataclass
+class Features:
+    """The outputs of a feature render (Camera.render_features; include/rl_render.h "Feature renders"): per pixel, over the `samples` jittered
+    camera rays, the sums of the first hit's colour factor (background where the ray misses), normal and ray parameter t, and the number of
+    rays that hit.  An output that was not asked for (want=) is None.  With a row shard the arrays hold the shard's rows; a list render
+    holds [n, ...] arrays."""
+    samples: int
+    albedo_sum: Optional[np.ndarray] = field(default=None, repr=False)  # [H, W, 3] f64
+    normal_sum: Optional[np.ndarray] = field(default=None, repr=False)  # [H, W, 3] f64
+    depth_sum: Optional[np.ndarray] = field(default=None, repr=False)   # [H, W] f64
+    hit_count: Optional[np.ndarray] = field(default=None, repr=False)   # [H, W] uint32
+
+    def albedo(self) -> np.ndarray:  # as Canvas.pixel_data: c * (1/samples)
+        return self.albedo_sum * (1.0 / self.samples)
+
+    def normal(self) -> np.ndarray:
+        """normal_sum normalised; zeros where it is zero (no ray hit, or the normals cancelled)."""
+        n = np.sqrt((self.normal_sum * self.normal_sum).sum(axis=-1, keepdims=True))
+        return np.divide(self.normal_sum, n, out=np.zeros_like(self.normal_sum), where=n != 0.0)
+
+    def depth(self) -> np.ndarray:
+        """depth_sum / hit_count: the mean t of the rays that hit; inf where none did."""
+        k = self.hit_count.astype(np.float64)
+        return np.divide(self.depth_sum, k, out=np.full_like(self.depth_sum, np.inf), where=k != 0.0)
+
+    def coverage(self) -> np.ndarray:
+        return self.hit_count / self.samples
+
+    def merge(self, other):  # as Moments.merge: the sums of renders that continue each other (first_sample) add
+        def add(a, b):
+            assert (a is None) == (b is None) and (a is None or a.shape == b.shape)
+            return None if a is None else a + b
+        return Features(self.samples + other.samples, *(add(getattr(self, k), getattr(other, k)) for k in FEATURE_OUTPUTS))
+
+
+def _features_want(want):
+    want = FEATURE_OUTPUTS if want is None else tuple(want)
+    for k in want:
+        if k not in FEATURE_OUTPUTS:
+            raise ValueError(f"want holds {k!r}; the outputs are {FEATURE_OUTPUTS}")
+    return want
+
+
+def _features_host(want, shape):
+    """(Features arrays by name, the ctypes struct over them) for `want` at pixel shape `shape`."""
+    arrays = {k: np.empty(shape + ((3,) if k in ("albedo_sum", "normal_sum") else ()), dtype=np.uint32 if k == "hit_count" else np.float64)
+              for k in _features_want(want)}
+    return arrays, RtiowFeatures(**{k: a.ctypes.data for k, a in arrays.items()})
+
+
 class Camera:
     def __init__(self, params: CameraParams):  # Camera::new camera.rs:72
         self.params = params
@@ -1352,6 +1433,58 @@ class Camera:
         _check(rc)
         if stats is not None:
             stats.update(st.as_dict())
+
+
+    # ---- feature renders (include/rl_render.h rl_rtiow_render_features*): per pixel the sums of the first hit's colour factor, normal and
+    # depth over the S jittered camera rays of render_independent, and the number of rays that hit; want= a subset of FEATURE_OUTPUTS
+    def render_features(self, world: World, first_sample=0, row_first=0, row_step=1, want=None, stats=None, allow_degenerate=False) -> Features:
+        """Compact shard rows.  Always a counting call (reference-order trace), as render_rows."""
+        nrows = rows_for(self.c.image_height, row_first, row_step)
+        arrays, f = _features_host(want, (nrows, self.c.image_width))
+        st = Stats()
+        rc = render_lib().rl_rtiow_render_features_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f), C.byref(st))
+        _finish_query(rc, st, stats, allow_degenerate)
+        return Features(self.params.samples_per_pixel, **arrays)
+
+    def render_features_device(self, world: World, stream=0, row_first=0, row_step=1, first_sample=0, stats=None, allow_degenerate=False, *, d_albedo_sum=0,
+                               d_normal_sum=0, d_depth_sum=0, d_hit_count=0):
+        """Outputs stay in HBM: device pointers of nrows*W*3 f64 (albedo, normal), nrows*W f64 (depth), nrows*W uint32 (hit count); 0 = not
+        wanted.  Async unless stats is a dict."""
+        f = RtiowFeatures(d_albedo_sum or None, d_normal_sum or None, d_depth_sum or None, d_hit_count or None)
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_features_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f), C.c_void_p(stream),
+                                                          C.byref(st) if st is not None else None)
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+
+    def render_pixels_features(self, world: World, xs, ys, first_sample=0, want=None, stats=None, allow_degenerate=False) -> Features:
+        """Features of pixels (xs[i], ys[i]), [n, ...]: what render_features(world, first_sample) holds at [ys[i], xs[i]].  The list rules
+        are render_pixels'.  stats (a dict): a counting call; without it the call is counter-free and may take the fast walk."""
+        xs, ys = _pixel_list(xs, ys)
+        arrays, f = _features_host(want, (xs.size,))
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_pixels_features(world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, C.byref(f),
+                                                          C.byref(st) if st is not None else None)
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
+        return Features(self.params.samples_per_pixel, **arrays)
+
+    def render_pixels_features_device(self, world: World, d_xs, d_ys, n, stream=0, first_sample=0, stats=None, allow_degenerate=False, *, d_albedo_sum=0,
+                                      d_normal_sum=0, d_depth_sum=0, d_hit_count=0):
+        """d_xs / d_ys: device pointers of n uint32; outputs as render_features_device with n pixels.  Async unless stats is a dict; an element
+        outside the image is written as zeros in every given output."""
+        f = RtiowFeatures(d_albedo_sum or None, d_normal_sum or None, d_depth_sum or None, d_hit_count or None)
+        st = Stats() if stats is not None else None
+        rc = render_lib().rl_rtiow_render_pixels_features_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
+                                                                 C.byref(f), C.c_void_p(stream), C.byref(st) if st is not None else None)
+        _check(rc, allow_degenerate)
+        if stats is not None:
+            stats.update(st.as_dict())
+            stats["rc"] = rc
 
 
 def _take_string(ptr, n):

@@ -105,7 +105,7 @@ class HostStaging {
     if (scene) rc = scene_context(scene, c);
     else if ((rc = rl::use_context(0)) == RL_OK) c = &rl::context(0);
     if (rc == RL_OK) stream = c->stream;
-    bufs_.reserve(4), back_.reserve(4);  // what the largest form stages: one host allocation each, whatever the call
+    bufs_.reserve(5), back_.reserve(4);  // what the largest form stages: one host allocation each, whatever the call
   }
   // host arrays uploaded back to back into one allocation
   void *in(std::initializer_list<std::pair<const void *, size_t>> parts) {

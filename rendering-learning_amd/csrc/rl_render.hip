@@ -29,6 +29,7 @@
 #include "rl_ray_query.h"
 #include "rl_material_query.h"
 #include "rl_rtc_shade_query.h"
+#include "rl_rtiow_features.h"
 
 using namespace rl;
 
@@ -2041,3 +2042,4 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 
 // the batched queries' host layer (22 entry points); last, so that its kernels keep their order of first use
 #include "rl_query_api.h"
+#include "rl_features_api.h"

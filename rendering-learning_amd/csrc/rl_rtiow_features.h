@@ -1,0 +1,287 @@
+// Feature renders (include/rl_render.h "Feature renders", rl_rtiow_render_features*): per pixel the sums over S jittered
+// camera rays of the first hit's colour factor, normal and depth, and the number of rays that hit — the guide buffers of a denoiser.
+//
+//   rtiow_features_kernel<NT, STATS, FAST, SD>   one pixel per lane, grid-stride over the frame's or the list's slots; a per-lane loop over
+//                                                the samples F .. F + S - 1 in ascending order, every add rounded on its own.
+//
+// Per sample the kernel joins three texts the library already has, expression for expression, so that the host composition of
+// rl_rtiow_camera_rays, rl_rtiow_hit_rays_seeded and rl_rtiow_texture_values gives the same bits (tests/test_gpu_render_features.py):
+//   1. the stream start and the camera arithmetic of rtiow_camera_rays_kernel (rl_ray_query.h): Ring in an LDS column, reset_stream at word 0
+//   2. the closest-hit trace
+//        FAST = false  general_trace<STATS, true, true>, media drawing from the sample's ring (rtiow_hit_rays_seeded_kernel)
+//        FAST = true   the flat four-wide SAH walk of rtiow_hit_rays_fast_kernel with tmax = +inf: LDS stack, tree top in LDS, every
+//                      order-sensitive ray re-traced by general_trace — the same record, bit for bit
+//   3. rec_uv + material_texture / texture_value<2> as rtiow_scatter_rays_kernel (rl_material_query.h) calls them
+// The walk of FAST is a SECOND COPY of rtiow_hit_rays_fast_kernel's per-ray text (features_fast_trace below), not a function shared with
+// it: factored into one function for both, the query kernel came out at 274 VGPRs + 18 AGPRs instead of 247; as it is,
+// it stays the code object it was.  What the copy leaves out is the finite-tmax tie test (tmax is +inf here).  A change to one walk belongs in the other; the tests hold the two against each other through the host composition.
+//
+// The kernel takes its own parameter struct beside RtiowParams, as the ray queries take RayQuery: RtiowParams does not grow.
+// LDS (dynamic): [16][NT] u64 ChaCha ring; FAST: + [SD][NT] u32 stack + P.fg_top FastNodeQ.
+// stats: [0] rays = samples traced, [5] words drawn (get_ray + media), [6] flagged, [7] rays the fast walk re-traced; STATS: [1..4].
+#pragma once
+#include "rl_material_query.h"
+#include "rl_ray_query.h"
+
+namespace rl {
+
+struct FeaturesQuery {
+  unsigned long long n;     // slots: nrows * W of the shard, or the list's length
+  const uint32_t *xs, *ys;  // pixel list (null: the shard's rows, slot = r * W + x, y = row_first + r * row_step)
+  double *albedo_sum;       // [n][3] or null
+  double *normal_sum;       // [n][3] or null
+  double *depth_sum;        // [n]    or null
+  uint32_t *hit_count;      // [n]    or null
+};
+
+// rtiow_hit_rays_fast_kernel's walk for one world ray (wo, wd, time) with Interval{1e-10, +inf}: -> rec; `slow`: the ray was re-traced in
+// the reference's order; returns the flags (panic sites reached).
+template <int NT, int SD>
+__device__ __forceinline__ uint32_t features_fast_trace(const RtiowParams &P, const DevOp *ops, uint32_t *s_stack, const uint4 *s_top, int tid, D3 wo, D3 wd,
+                                                        double time, Rec &rec, bool &slow) {
+  const FastNodeQ *nodes = P.fg_nodes;
+  const FastItem *items = P.fg_items;
+  const uint32_t top = P.fg_top;
+  const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  const float FINF = __int_as_float(0x7F800000);
+  double closest = INF;
+  uint32_t best = NONE, sp = 0, steps = 0;
+  const RayAux32 ra32 = ray_aux32_direct(wo, wd);
+  bool amb = !(ra32.slack < FINF);  // outside the binary32 filter's range: the reference's order
+  float grow = 0.0f;
+  const float fx = (float)wo.x - P.fg_center[0], fy = (float)wo.y - P.fg_center[1], fz = (float)wo.z - P.fg_center[2];
+  const float far2 = fmaf(fx, fx, fmaf(fy, fy, fz * fz));
+  const bool unsafe = !(far2 <= P.fg_rsafe2);
+  if (unsafe) {  // start_ray of rl_rtiow_fastgen_body.inc: boxes widened, no pruning by the closest hit
+    const float L = sqrtf(far2) + P.fg_radius;
+    grow = P.fg_pad_k * L * L * fmaxf(fmaxf(fabsf(ra32.invx), fabsf(ra32.invy)), fabsf(ra32.invz));
+    if (!(grow < FINF)) amb = true;
+  }
+  auto pop = [&]() -> uint32_t {
+    if (sp == 0) return NONE;
+    sp--;
+    return s_stack[(size_t)sp * NT + tid];
+  };
+  auto push = [&](uint32_t e) {
+    if (sp < (uint32_t)SD) s_stack[(size_t)sp * NT + tid] = e, sp++;
+    else amb = true;  // more pending children than the stack holds: the reference's order decides
+  };
+  uint32_t seg = 0;
+  uint32_t e = amb ? NONE : (P.fg_n_seg > 1u ? P.fg_seg_roots[0] : P.fg_root);
+#pragma unroll 1
+  for (;;) {
+    while (e == NONE && !amb && seg + 1u < P.fg_n_seg) e = P.fg_seg_roots[++seg];
+    if (e == NONE || amb) break;
+    if (++steps > FASTG_STEP_BUDGET) {
+      amb = true;
+      break;
+    }
+    if (e & FASTG_LEAF) {
+      const uint32_t item = e & ~FASTG_LEAF;
+      const FastItem it = items[item];
+      const DevSphere isph = P.fg_spheres[item];
+      D3 o, d;
+      replay_chain(P, ops, it.chain, wo, wd, o, d);
+      float oimax = ra32.oimax();
+      if (it.chain != NONE)
+        oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
+                      fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
+      if (!(oimax < FINF)) oimax = FINF;
+      if (it.kind == 0) fastg_sphere_hit(isph, it.payload, o, d, time, oimax, item, closest, best, amb);
+      else fastg_planar_hit(P.planars[it.payload], o, d, oimax, item, closest, best, amb);
+      e = pop();
+      continue;
+    }
+    const float c32 = unsafe ? FINF : (float)closest;
+    auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) {
+      float t0x = fmaf(b0, ra32.invx, -ra32.oix), t1x = fmaf(b1, ra32.invx, -ra32.oix);
+      float t0y = fmaf(b2, ra32.invy, -ra32.oiy), t1y = fmaf(b3, ra32.invy, -ra32.oiy);
+      float t0z = fmaf(b4, ra32.invz, -ra32.oiz), t1z = fmaf(b5, ra32.invz, -ra32.oiz);
+      tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)) - grow, 1e-10f);
+      float tmax = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)) + grow, c32);
+      float diff = tmax - tmin;
+      float thresh = fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
+      return diff < -thresh;
+    };
+    const Float4 *nd = e < top ? (const Float4 *)(s_top + e * 8u) : (const Float4 *)(nodes + e);
+    const Float4 lx = nd[0], ly = nd[1], lz = nd[2], hx = nd[3], hy = nd[4], hz = nd[5];
+    const uint4 ch = *(const uint4 *)(nd + 6);
+    float k0, k1, k2, k3;
+    const bool h0 = !missed(lx.x, hx.x, ly.x, hy.x, lz.x, hz.x, k0) && ch.x != NONE;
+    const bool h1 = !missed(lx.y, hx.y, ly.y, hy.y, lz.y, hz.y, k1) && ch.y != NONE;
+    const bool h2 = !missed(lx.z, hx.z, ly.z, hy.z, lz.z, hz.z, k2) && ch.z != NONE;
+    const bool h3 = !missed(lx.w, hx.w, ly.w, hy.w, lz.w, hz.w, k3) && ch.w != NONE;
+    const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
+    k0 = h0 ? k0 : FINF, k1 = h1 ? k1 : FINF, k2 = h2 ? k2 : FINF, k3 = h3 ? k3 : FINF;
+    uint32_t c0 = ch.x, c1 = ch.y, c2 = ch.z, c3 = ch.w;
+    uint32_t u0 = (__float_as_uint(k0) & ~1u) | (h0 ? 0u : 1u), u1 = (__float_as_uint(k1) & ~1u) | (h1 ? 0u : 1u);
+    uint32_t u2 = (__float_as_uint(k2) & ~1u) | (h2 ? 0u : 1u), u3 = (__float_as_uint(k3) & ~1u) | (h3 ? 0u : 1u);
+    auto cex = [&](uint32_t &ka, uint32_t &kb, uint32_t &ca, uint32_t &cb) {  // keys are non-negative floats: integer order = float order
+      const bool sw = kb < ka;
+      const uint32_t tk = sw ? kb : ka, tc = sw ? cb : ca;
+      kb = sw ? ka : kb, cb = sw ? ca : cb;
+      ka = tk, ca = tc;
+    };
+    cex(u0, u1, c0, c1), cex(u2, u3, c2, c3), cex(u0, u2, c0, c2), cex(u1, u3, c1, c3), cex(u1, u2, c1, c2);
+    if (nh >= 4) push(c3);
+    if (nh >= 3) push(c2);
+    if (nh >= 2) push(c1);
+    e = nh ? c0 : pop();
+  }
+  rec = rec_none(INF);
+  uint32_t hit_flags = 0;
+  if (!amb && best != NONE) {  // the winner's HitRecord: the same test once more with ray_t.max = its root, then the POP chain
+    const FastItem it = items[best];
+    const DevSphere sph = P.fg_spheres[best];
+    const uint32_t wmat = P.fg_material[best];
+    D3 o, d;
+    replay_chain(P, ops, it.chain, wo, wd, o, d);
+    float oimax = ra32.oimax();
+    if (it.chain != NONE)
+      oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
+                    fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
+    if (!(oimax < FINF)) oimax = FINF;
+    rec.t = closest;
+    if (it.kind == 0) {
+      if (sphere_hit_rec(sph, it.payload | SPH_UV, wmat, it.op_pc, o, d, time, rec)) hit_flags++;
+      D3 c0 = ld3(sph.c0);
+      D3 center = (it.payload & SPH_MOVING) ? c0 + ld3(sph.dc) * time : c0;
+      D3 oc = o - center;
+      double half_b = dot(oc, d), sq = sph.r2 * sph.inv_r * fabs(dot(d, rec.normal)), a = len2(d);
+      double other = 2.0 * sq * (double)__builtin_amdgcn_rcpf((float)a);
+      if (fast_hit_is_order_sensitive(oc, d, closest, sph.r2 * sph.inv_r, half_b, sq, closest, fabs(closest) + other, oimax)) amb = true;
+    } else {
+      if (planar_hit_rec(P.planars[it.payload], it.op_pc, o, d, rec)) hit_flags++;
+    }
+    if (!amb && !rec.any) amb = true;  // (cannot happen: the same arithmetic found this root)
+    hit_flags += pop_rec_chain(P, ops, amb ? NONE : it.chain, rec);
+  }
+  slow = amb;
+  if (amb) {  // the reference's own fold decides
+    rec = rec_none(INF);
+    GenCounters gc{0, 0, 0, 0, 0};
+    auto draw = []() { return 0.0; };
+    general_trace<false, false, true>(P, ops, 0u, NONE, wo, wd, wo, wd, time, 1e-10, rec, gc, draw);
+    return (uint32_t)gc.flagged;
+  }
+  return hit_flags;
+}
+
+// P: the scene's tables (hit_query_params + materials, textures, images, Perlin), cam, key, first_sample, row_first / row_step / nrows,
+// stats; FAST: also the query tree (fg_*, fg_top).
+// Register budget: FAST is compiled for two workgroups per SIMD row (launch bounds 2 NT: 256 VGPRs, which its LDS allows too); left to
+// itself it takes 315 and runs one wave per SIMD, measured 1.4x - 1.5x slower.  The reference-order instantiations
+// carry general_trace with media and the counters at 350 - 376 registers: one wave per SIMD, as rtiow_hit_rays_seeded_kernel.
+template <int NT, bool STATS, bool FAST, int SD>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_features_kernel(RtiowParams P, FeaturesQuery Q) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  unsigned long long *s_rng = (unsigned long long *)smem;                               // [16][NT]
+  uint32_t *s_stack = (uint32_t *)(smem + (size_t)16 * NT * sizeof(unsigned long long));  // FAST: [SD][NT]
+  uint4 *s_top = (uint4 *)(s_stack + (size_t)NT * SD);                                  // FAST: [fg_top] FastNodeQ
+  const DevOp *ops = P.ops;
+  if (FAST && P.fg_top) {
+    for (uint32_t i = (uint32_t)tid; i < P.fg_top * 8u; i += (uint32_t)NT) s_top[i] = ((const uint4 *)P.fg_nodes)[i];
+    __syncthreads();
+  }
+  const rl_rtiow_camera &cam = P.cam;
+  const uint32_t W = cam.image_width, H = cam.image_height, S = cam.samples_per_pixel;
+  const uint64_t WH = (uint64_t)W * (uint64_t)H;
+  const D3 background = ld3(cam.background);
+  const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  Ring<NT, true, true> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
+  unsigned long long c_rays = 0, c_nodes = 0, c_sph = 0, c_pl = 0, c_inst = 0, c_flag = 0, c_words = 0, c_slow = 0;
+  for (unsigned long long idx = (unsigned long long)blockIdx.x * NT + tid; idx < Q.n; idx += (unsigned long long)gridDim.x * NT) {
+    uint32_t px, y;
+    if (Q.xs) px = Q.xs[idx], y = Q.ys[idx];
+    else px = (uint32_t)(idx % W), y = P.row_first + (uint32_t)(idx / W) * P.row_step;
+    D3 albedo = d3(0.0, 0.0, 0.0), normal = d3(0.0, 0.0, 0.0);
+    double depth = 0.0;
+    uint32_t hits = 0;
+    const bool inside = px < W && y < H;  // (a list element outside the image, device form: zeros, nothing traced)
+#pragma unroll 1
+    for (uint32_t n = 0; inside && n < S; n++) {
+      const uint64_t sample_index = (uint64_t)n + P.first_sample;
+      rng.pos = 0u, rng.nres = 0;
+      rng.reset_stream(sample_index * WH + (uint64_t)px * (uint64_t)W + (uint64_t)y);
+      // 1. Camera::get_ray (rtiow_camera_rays_kernel)
+      D3 p00 = ld3(cam.pixel_00), du = ld3(cam.pixel_du), dv = ld3(cam.pixel_dv);
+      D3 pixel_center = (p00 + du * (double)px) + dv * (double)y;
+      double sx = -0.5 + rng.gen_f64();
+      double sy = -0.5 + rng.gen_f64();
+      D3 pixel_sample = pixel_center + (du * sx + dv * sy);
+      D3 wo;
+      if (cam.defocus_angle <= 0.0) wo = ld3(cam.lookfrom);
+      else {
+        double a, b;
+        rng.unit_disc(a, b);
+        wo = (ld3(cam.lookfrom) + ld3(cam.defocus_disk_u) * a) + ld3(cam.defocus_disk_v) * b;
+      }
+      const D3 wd = pixel_sample - wo;
+      const double time = rng.gen_f64();
+      // 2. world.hit(&ray, &Interval{1e-10, +inf})
+      c_rays++;
+      Rec rec;
+      if (FAST) {
+        bool slow;
+        c_flag += features_fast_trace<NT, SD>(P, ops, s_stack, s_top, tid, wo, wd, time, rec, slow);
+        if (slow) c_slow++;
+      } else {
+        rec = rec_none(INF);
+        GenCounters gc{0, 0, 0, 0, 0};
+        auto draw = [&]() { return rng.gen_f64(); };
+        general_trace<STATS, true, true>(P, ops, 0u, NONE, wo, wd, wo, wd, time, 1e-10, rec, gc, draw);
+        c_nodes += gc.nodes, c_sph += gc.spheres, c_pl += gc.planars, c_inst += gc.instances, c_flag += gc.flagged;
+      }
+      c_words += rng.pos;
+      // 3. the factor the first vertex puts on the path, its normal and its ray parameter
+      D3 a = background, nrm = d3(0.0, 0.0, 0.0);
+      double dpt = 0.0;
+      if (rec.any) {
+        const DevMaterial &m = P.materials[rec.mat];
+        a = material_texture<true>(m, [&](uint32_t tex) {
+          double tu, tv;
+          rec_uv(rec, tu, tv);
+          return texture_value<2>(P, tex, tu, tv, rec.p);
+        });
+        if (m.kind == RL_MAT_METAL) a = ld3(m.albedo);
+        else if (m.kind == RL_MAT_DIELECTRIC) a = d3(1.0, 1.0, 1.0);
+        nrm = rec.normal, dpt = rec.t, hits++;
+      }
+      albedo = albedo + a, normal = normal + nrm, depth = depth + dpt;
+    }
+    if (Q.albedo_sum) {
+      double *o = Q.albedo_sum + idx * 3;
+      o[0] = albedo.x, o[1] = albedo.y, o[2] = albedo.z;
+    }
+    if (Q.normal_sum) {
+      double *o = Q.normal_sum + idx * 3;
+      o[0] = normal.x, o[1] = normal.y, o[2] = normal.z;
+    }
+    if (Q.depth_sum) Q.depth_sum[idx] = depth;
+    if (Q.hit_count) Q.hit_count[idx] = hits;
+  }
+  unsigned long long v;
+  v = wave_sum(c_rays);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[0], v);
+  v = wave_sum(c_words);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[5], v);
+  v = wave_sum(c_flag);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
+  if (FAST) {
+    v = wave_sum(c_slow);
+    if ((tid & 63) == 0 && v) atomicAdd(&P.stats[7], v);
+  }
+  if (STATS) {
+    v = wave_sum(c_nodes);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[1], v);
+    v = wave_sum(c_sph);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
+    v = wave_sum(c_pl);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[3], v);
+    v = wave_sum(c_inst);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[4], v);
+  }
+}
+
+}  // namespace rl

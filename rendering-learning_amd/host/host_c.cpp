@@ -606,6 +606,25 @@ int rlh_render_adaptive_probe(uint64_t width, uint64_t spp, uint32_t min_samples
     return -1;
   }
 }
+// A feature render through the C++ mirror: golden_test_scene at image_width = width, samples_per_pixel = spp, rtiow::Camera::render_features
+// from sample first_sample on.  albedo_sum and normal_sum = W * H * 3 doubles each, depth_sum = W * H doubles, hit_count = W * H uint32.
+// 0 or -1 (rlh_last_error).
+int rlh_render_features_probe(uint64_t width, uint64_t spp, uint64_t first_sample, double *albedo_sum, double *normal_sum, double *depth_sum, uint32_t *hit_count) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    s.params.image_width = (size_t)width, s.params.samples_per_pixel = (size_t)spp;
+    rtiow::Camera cam(s.params);
+    rtiow::Camera::Features f = cam.render_features(*s.world, first_sample);
+    std::memcpy(albedo_sum, f.albedo_sum.data(), f.albedo_sum.size() * sizeof(double));
+    std::memcpy(normal_sum, f.normal_sum.data(), f.normal_sum.size() * sizeof(double));
+    std::memcpy(depth_sum, f.depth_sum.data(), f.depth_sum.size() * sizeof(double));
+    std::memcpy(hit_count, f.hit_count.data(), f.hit_count.size() * sizeof(uint32_t));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
 // which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
 // b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,

@@ -93,6 +93,21 @@ Camera::Adaptive Camera::render_adaptive(const Hittable &world, const rl_rtiow_a
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_adaptive_rows: ") + rl_last_error());
   return a;
 }
+Camera::Features Camera::render_features(const Hittable &world, uint64_t first_sample) const {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  rl_rtiow_camera cam = derived();
+  const size_t n = params.image_width * image_height;
+  Features ft{params.samples_per_pixel, std::vector<double>(n * 3), std::vector<double>(n * 3), std::vector<double>(n), std::vector<uint32_t>(n)};
+  const rl_rtiow_features out{ft.albedo_sum.data(), ft.normal_sum.data(), ft.depth_sum.data(), ft.hit_count.data()};
+  int rc = rl_rtiow_render_features_rows(sc, &cam, first_sample, 0, 1, &out, nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_features_rows: ") + rl_last_error());
+  return ft;
+}
 Canvas Camera::render_independent(const Hittable &world) const { return render_independent_impl(*this, world, nullptr); }
 Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
   return render_independent_impl(*this, world, &checkpoint);

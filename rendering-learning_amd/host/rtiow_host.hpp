@@ -816,6 +816,16 @@ struct Camera {
     std::vector<uint32_t> counts;   // [H][W]
   };
   Adaptive render_adaptive(const Hittable &world, const rl_rtiow_adaptive &rule, uint64_t first_sample = 0) const;
+  // a feature render (rl_rtiow_render_features_rows): per pixel, over the samples_per_pixel jittered camera rays of render_independent
+  // (samples first_sample ..), the sums of the first hit's colour factor (the background where the ray misses), normal and ray parameter t,
+  // and the number of rays that hit — the guide buffers of a denoiser.  max_depth is not read.
+  struct Features {
+    size_t samples;
+    std::vector<double> albedo_sum, normal_sum;  // [H][W][3]
+    std::vector<double> depth_sum;               // [H][W]
+    std::vector<uint32_t> hit_count;             // [H][W]
+  };
+  Features render_features(const Hittable &world, uint64_t first_sample = 0) const;
   // Camera::get_ray(&mut rng, x, y) (camera.rs:203-216) for a batch of pixels, on the GPU (rl_rtiow_camera_rays): rng_i as for
   // ray_color_rays with seed = params.seed; cursors[i] is advanced behind the draws.  _render's stream of sample s at pixel (x, y) is
   // s * W * H + x * W + y (camera.rs:161-170).
