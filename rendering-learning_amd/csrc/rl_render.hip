@@ -1619,7 +1619,7 @@ void rl_debug_live_buffers(unsigned long long out[2]) { out[0] = rl::g_live_buff
 
 // Not part of the ABI (tools only): scheduler occupancy counters of the last STATS launch, 32 x u64 ([3s .. 3s+2] per state; [24]: the
 // fast kernel's skipped self tests, rl_rtiow_wave.h fast_self_miss; [25 .. 28]: the camera rays' TRAV lane-steps, LEAF visits, number, and
-// LEAF visits that ended at disc < 0).
+// LEAF visits that ended at disc < 0; [29]: the scheduling decisions that chose TRAV — [3] counts its steps).
 int rl_debug_sched(const rl_scene *scene, unsigned long long *out32) {
   if (!scene || !out32) return RL_E_INVALID;
   HIP_TRY(hipMemcpy(out32, scene->d_scratch + 128, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));

@@ -40,6 +40,8 @@ namespace rl {
 #ifndef RL_COOP_GEN
 #define RL_COOP_GEN 1
 #endif
+// tools/wave_codegen.py finds the scheduler loop's header, its blocks and the TRAV step in a kernel's assembly by these comment lines (no code)
+#define RL_CG_MARK(name) asm volatile("; rl_cg " name)
 enum : uint32_t { ST_GEN = 0, ST_TRAV = 1, ST_SHADE = 2, ST_FILL = 3, ST_DONE = 4, ST_LEAF = 5, ST_SHADE2 = 6, ST_LEAF2 = 8 };
 
 // two-block ChaCha ring in LDS: 16 u64 slots per lane, slot-major ([slot][lane]) => conflict-free

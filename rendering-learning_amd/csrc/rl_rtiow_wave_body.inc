@@ -282,7 +282,9 @@
   };
 
   unsigned long long sc_exec[7] = {0, 0, 0, 0, 0, 0, 0}, sc_pop[7] = {0, 0, 0, 0, 0, 0, 0}, sc_cyc[7] = {0, 0, 0, 0, 0, 0, 0};
+  unsigned long long sc_trav_picks = 0;  // STATS: scheduling decisions that chose TRAV (sc_exec[ST_TRAV] counts its steps)
   for (;;) {
+    RL_CG_MARK("HEAD");
     // a finished traversal goes to SHADE; lanes reading from their newest ChaCha block top the ring up first
     if ((state == ST_SHADE || (SPLIT_SHADE && LDS_SCENE == 4 && state == ST_SHADE2)) && rng.low()) state = ST_FILL;
     // ---- wave scheduler: run the state with the most lanes in it (ties -> TRAV, SHADE, FILL, GEN)
@@ -305,6 +307,20 @@
     if (SPLIT_SHADE && LDS_SCENE == 4 && n_shade2 > best) pick = ST_SHADE2, best = n_shade2;
     if (SPLIT_LEAF && LDS_SCENE == 4 && n_leaf2 > best) pick = ST_LEAF2, best = n_leaf2;
 
+    // The blocks are separate `if`s, each on its own opaque copy of the wave-uniform pick, and not an else-if chain.  A chain (or the
+    // switch it becomes) is ONE region with several uniform branches around divergent code, and the compiler linearises such a region:
+    // flow blocks with a "not run yet" flag after every block, and in each of them a merge of every variable the block may write with
+    // an undefined value.  The register allocator answers those merges with a second copy of the lane state: 117 v_mov on a TRAV
+    // pick's way round the loop, for o, d, thr, time and the ray constants that TRAV never writes, and about as many around the other
+    // blocks.  A lone `if` with one uniform branch is left as the scalar branch it is, its join merges old and new value only, and the
+    // lane state stays in place: 13 v_mov on that path (tools/wave_codegen.py, DESIGN.md section 3.1).  The tests that follow a block
+    // that ran cost two scalar instructions each.  (The opaque copy is not what keeps the chain away — without it the separate `if`s
+    // compile to the same paths — but with it the headline kernel spills 71 SGPRs instead of 75: the measured form.)
+    auto picked = [&](uint32_t s) {
+      uint32_t p = pick;
+      asm volatile("" : "+s"(p));
+      return p == s;
+    };
     unsigned long long t_begin = 0;
     if (STATS) {  // debug (tools/sched.py): block executions, lanes served and shader cycles per state, per wave
       t_begin = __builtin_readcyclecounter();
@@ -314,7 +330,9 @@
           if (pick == (uint32_t)k) sc_exec[k]++, sc_pop[k] += (unsigned)best;
       }
     }
-    if (pick == ST_TRAV) {
+    if (picked(ST_TRAV)) {
+      RL_CG_MARK("TRAV_B");
+      if (STATS) sc_trav_picks++;
       // several steps per scheduling decision while the population stays near its starting size
       int floor_n = ((LDS_SCENE == 4 ? n_trav : best) * (int)P.tune[1]) >> 4;
       auto trav_step = [&]() {
@@ -322,6 +340,7 @@
           int np = __popcll(__ballot(state == ST_TRAV));
           sc_exec[ST_TRAV]++, sc_pop[ST_TRAV] += (unsigned)np;
         }
+        RL_CG_MARK("STEP_B");
         if (state == ST_TRAV) {
           // one LDS round trip: the whole 64-B linked op {box, w_hit, w_miss}; every op stepped here is a box op,
           // the successor words already carry the state the lane enters there (rl_render.hip link_ops)
@@ -392,13 +411,17 @@
             state = w >> 29;
           }
         }
+        RL_CG_MARK("STEP_E");
       };
       for (int it = 0; it < (int)P.tune[0]; it += 2) {  // two steps per population check
         trav_step();
         trav_step();
         if (__popcll(__ballot(state == ST_TRAV)) < floor_n) break;
       }
-    } else if (pick == ST_LEAF) {
+      RL_CG_MARK("TRAV_E");
+    }
+    if (picked(ST_LEAF)) {
+      RL_CG_MARK("LEAF_B");
       if (LDS_SCENE == 4) {
         if (state == ST_LEAF) {
           if (__builtin_expect(pc == FAST_SLOW, 0)) {  // rare: the answer may depend on the visiting order -> the reference's own fold
@@ -443,19 +466,34 @@
         pc = w & 0x1FFFFFFFu;
         state = w >> 29;
       }
-    } else if (SPLIT_LEAF && LDS_SCENE == 4 && pick == ST_LEAF2) {
+      RL_CG_MARK("LEAF_E");
+    }
+    if (SPLIT_LEAF && LDS_SCENE == 4 && picked(ST_LEAF2)) {
       if (state == ST_LEAF2) {
         const uint32_t sidx = pc - P.n_fast_inner;
         const uint32_t payload = sidx | (((s_bits[sidx >> 5] >> (sidx & 31u)) & 1u) ? SPH_MOVING : 0u);
         fast_sphere_hit(spheres[sidx], payload, o, d, time, ra32.oimax(), closest, hit_prim, amb);
         fast_go(fast_pop());
       }
-    } else if (pick == ST_FILL) {
+    }
+    if (picked(ST_SHADE)) {  // (placed here, not last: behind GEN the allocator spills two VGPRs in SHADE's inline ring refill)
+      RL_CG_MARK("SHADE_B");
+      if (state == ST_SHADE) {
+        if (SPLIT_SHADE && LDS_SCENE == 4) shade(std::integral_constant<int, 1>{});
+        else shade(std::integral_constant<int, 0>{});
+      }
+      RL_CG_MARK("SHADE_E");
+    }
+    if (picked(ST_FILL)) {
+      RL_CG_MARK("FILL_B");
       if (state == ST_FILL) {
         rng.top_up();
         state = shade_state();
       }
-    } else if (pick == ST_GEN) {
+      RL_CG_MARK("FILL_E");
+    }
+    if (picked(ST_GEN)) {
+      RL_CG_MARK("GEN_B");
       bool active = false;
       if (state == ST_GEN) {
         active = true;
@@ -595,13 +633,10 @@
           start_ray(LDS_SCENE == 4 && P.pixel_entry ? P.pixel_entry[(size_t)pr * W + px] : fast_root_word);
         }
       }
-    } else if (SPLIT_SHADE && pick == ST_SHADE2) {
+      RL_CG_MARK("GEN_E");
+    }
+    if (SPLIT_SHADE && picked(ST_SHADE2)) {
       if (state == ST_SHADE2) shade(std::integral_constant<int, 2>{});
-    } else {  // ST_SHADE
-      if (state == ST_SHADE) {
-        if (SPLIT_SHADE && LDS_SCENE == 4) shade(std::integral_constant<int, 1>{});
-        else shade(std::integral_constant<int, 0>{});
-      }
     }
     if (STATS) {
       unsigned long long dt = __builtin_readcyclecounter() - t_begin;
@@ -618,6 +653,7 @@
       atomicAdd(&sched[3 * s + 1], sc_pop[s]);
       atomicAdd(&sched[3 * s + 2], sc_cyc[s]);
     }
+    atomicAdd(&sched[29], sc_trav_picks);  // rl_debug_sched out[29]
   }
 
   if (STEAL && LDS_SCENE == 4 && P.steal_state) {

@@ -28,6 +28,9 @@ if out[27]:  # census of the fast kernel's camera rays (remaining depth still ma
           f"LEAF visits {out[26]} of {leaf} ({100 * out[26] / max(leaf, 1):.1f} %, {out[26] / out[27]:.3f} per camera ray)")
     # of those, the visits that end at the discriminant test: the ray passed the sphere's box, not the sphere
     print(f"camera LEAF visits with disc < 0: {out[28]} ({out[28] / out[27]:.3f} per camera ray, {100 * out[28] / max(leaf, 1):.1f} % of all LEAF visits)")
+if out[29]:  # scheduling decisions that chose TRAV: what a per-pick cost (the way round the loop, tools/wave_codegen.py) weighs against the steps
+    steps = out[3 * 1]
+    print(f"TRAV picks {out[29]} ({steps / out[29]:.2f} steps per pick, {out[29] / st['rays']:.4f} picks per ray)")
 tot = sum(out[3 * k + 2] for k in names)
 for k, nm in names.items():
     ex, pop, cyc = out[3 * k], out[3 * k + 1], out[3 * k + 2]
