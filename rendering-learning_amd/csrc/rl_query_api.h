@@ -1,7 +1,7 @@
 // The host side of the batched queries (include/rl_render.h rl_*_rays*, rl_rtiow_texture_values*, rl_rtc_lighting*; DESIGN.md §3.8 - §3.12;
 // kernels: rl_ray_query.h, rl_material_query.h, rl_rtc_shade_query.h and the *_rays_kernel forms of the render kernels): 12 queries, each in a
 // host-buffer and a _device form.  Not a translation unit of its own: rl_render.hip includes it once, at its end, and it uses that file's
-// statics (g_sw, g_cus, g_lds_max, ensure_lds_attr, fill_rtiow_params, stage_params, chacha_key_from_seed).
+// statics (g_sw, g_cus, g_lds_max, ensure_lds_attr, fill_rtiow_params, chacha_key_from_seed) and the launch half of rl_rtiow_launch.h.
 //
 // Every entry point is made of three moves, each of which exists once:
 //   query_check   — library ready, scene family, the empty batch, null buffers, the batch bound; what is particular to a call follows it
@@ -270,7 +270,7 @@ static int cursors_check(const rl_rng_cursor *cursors, uint64_t n) {
   return RL_OK;
 }
 
-// The same flavour choice as rtiow_render_indep_launch without the LDS sphere kernels: the counter-free general fast kernel wherever the
+// The kernel families of rtiow_render_indep_launch without the LDS sphere kernels: the counter-free general fast kernel wherever the
 // scene has a world-space SAH tree (sphere-only scenes: the queries' own, HostRtiow::qfg), the reference-order wave-scheduled kernel for
 // counting calls, scenes without one and RL_FAST=0.  sync_st as in rtiow_hit_rays_impl.
 static int rtiow_ray_color_impl(const rl_scene *scene, const void *d_rays, const void *d_cursors, uint64_t n, uint64_t seed, uint32_t max_depth,
@@ -292,61 +292,19 @@ static int rtiow_ray_color_impl(const rl_scene *scene, const void *d_rays, const
   P.q_out_cursors = (rl_rng_cursor *)d_out_cursors, P.q_ray_counts = (uint32_t *)d_counts;
   const bool fast = !counting && QF.ok && g_sw.fast_traversal;
   const bool trans = rt.has_noise || rt.has_sphere_uv;
-  const bool fg_media = QF.stage_roots.size() > 1;
+  ValueKernel kern = nullptr;       // reference order: parameter block by value
+  PointerKernel kern_ptr = nullptr;  // fast: by pointer, each pass its own stream-ordered copy
   int nt = 512;
   size_t lds = 0;
-  if (fast) {
-    if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
-    const int SD = (fg_media || trans) ? 40 : 20;
-    nt = (fg_media || trans) ? 512 : 768;
-    const size_t base = (size_t)nt * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));
-    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
-    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(QF.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
-    lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
+  if (fast) {  // never the one-wave-per-SIMD form: the rays flavour has none
+    const bool media = QF.stage_roots.size() > 1;
+    const FastgLayout lay = fastg_prepare(QF, trans, media, false, P);
+    kern_ptr = fast_general_kernel(Mode::RAYS, trans, media, false), nt = lay.nt, lds = lay.lds;
   } else {
-    lds = (size_t)512 * (16 + (rt.has_media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long);
+    kern = wave_general_kernel(Mode::RAYS, trans, counting, rt.has_media), lds = wave_general_lds(rt.has_media);
   }
-  uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));  // persistent lanes: as many workgroups as stay resident
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu * (uint32_t)nt > 2048) per_cu = 2048 / (uint32_t)nt;
-  auto blocks_of = [&](const void *kern, uint32_t &blocks) -> int {
-    blocks = (uint32_t)(((uint64_t)P.n_slots + nt - 1) / nt);
-    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
-    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;
-    if (ensure_lds_attr(kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    return RL_OK;
-  };
-  auto launch = [&](void (*kern)(RtiowParams)) -> int {
-    uint32_t blocks = 0;
-    int rcb = blocks_of((const void *)kern, blocks);
-    if (rcb != RL_OK) return rcb;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
-  auto launch_ptr = [&](void (*kern)(const RtiowParams *)) -> int {  // by pointer: each pass its own stream-ordered copy (two slots)
-    uint32_t blocks = 0;
-    int rcb = blocks_of((const void *)kern, blocks);
-    if (rcb != RL_OK) return rcb;
-    const RtiowParams *slot = nullptr;
-    int rcs = stage_params(scene, P, stream, slot);
-    if (rcs != RL_OK) return rcs;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
   auto launch_pass = [&]() -> int {
-    if (fast) {
-      if (fg_media) return trans ? launch_ptr(rtiow_fast_general_rays_kernel<512, 40, true, true>) : launch_ptr(rtiow_fast_general_rays_kernel<512, 40, false, true>);
-      if (trans) return launch_ptr(rtiow_fast_general_rays_kernel<512, 40, true, false>);
-      return launch_ptr(rtiow_fast_general_rays_kernel<768, 20, false, false>);
-    }
-    if (rt.has_media) {
-      if (trans) return counting ? launch(rtiow_wave_general_rays_kernel<512, true, true, true>) : launch(rtiow_wave_general_rays_kernel<512, true, false, true>);
-      return counting ? launch(rtiow_wave_general_rays_kernel<512, false, true, true>) : launch(rtiow_wave_general_rays_kernel<512, false, false, true>);
-    }
-    if (trans) return counting ? launch(rtiow_wave_general_rays_kernel<512, true, true, false>) : launch(rtiow_wave_general_rays_kernel<512, true, false, false>);
-    return counting ? launch(rtiow_wave_general_rays_kernel<512, false, true, false>) : launch(rtiow_wave_general_rays_kernel<512, false, false, false>);
+    return kern_ptr ? launch_persistent(kern_ptr, nt, lds, P.n_slots, P, scene, stream) : launch_persistent(kern, nt, lds, P.n_slots, P, scene, stream);
   };
   // rays per pass: below the u32 work counter's end, with room for every resident lane's last claim (which overshoots)
   uint64_t per_pass = 0xFF000000ull;

@@ -594,7 +594,7 @@ static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, 
   P.fast_nodes = scene->d_fast_nodes, P.n_fast_inner = (uint32_t)H.fast_nodes.size(), P.fast_root = H.fast_root;
   P.fg_nodes = scene->d_fg_nodes, P.fg_items = scene->d_fg_items, P.fg_spheres = scene->d_fg_spheres, P.fg_material = scene->d_fg_material, P.fg_root = H.fg.qroot, P.fg_rsafe2 = H.fg.r_safe * H.fg.r_safe * 0.9999f;  // binary32 evaluation on the device: keep a margin
   P.fg_seg_roots = scene->d_fg_seg_roots, P.fg_media = scene->d_fg_media, P.fg_n_seg = (uint32_t)H.fg.stage_roots.size();
-  P.fg_top = 0;  // (set by the launch that stages it: fastg_lds)
+  P.fg_top = 0;  // (set by the launch that stages it: fastg_prepare)
   P.fg_center[0] = H.fg.center[0], P.fg_center[1] = H.fg.center[1], P.fg_center[2] = H.fg.center[2];
   P.fg_radius = H.fg.radius, P.fg_pad_k = H.fg.pad_k;
   P.cam = *cam;
@@ -727,6 +727,8 @@ static int stage_params(const rl_scene *scene, const RtiowParams &P, hipStream_t
   return RL_OK;
 }
 
+#include "rl_rtiow_launch.h"  // kernel tables, fastg_prepare, wave_general_lds, persistent_blocks, launch_persistent, coop_launch
+
 namespace rl {
 int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint64_t first_sample, uint32_t row_first, uint32_t row_step, void *d_out,
                         hipStream_t stream, bool want_stats, void *d_out_sq, const rl_rtiow_adaptive *rule, void *d_out_count) {
@@ -755,34 +757,6 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     P.work_counter = scene->d_progress;
     HIP_TRY(hipMemsetAsync(scene->d_progress, 0, 8, stream));
   }
-  auto launch = [&](auto kern, int nt, size_t lds) -> int {
-    uint32_t blocks = (uint32_t)((slots + nt - 1) / nt);
-    uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));  // persistent lanes: as many workgroups as stay resident
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu * nt > 2048) per_cu = 2048 / nt;
-    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
-    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;  // A/B only
-    if (ensure_lds_attr((const void *)kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
-  auto launch_ptr = [&](auto kern, int nt, size_t rng_bytes) -> int {  // kernels that take the parameter block by pointer (device copy)
-    const RtiowParams *slot = nullptr;
-    int rcs = stage_params(scene, P, stream, slot);
-    if (rcs != RL_OK) return rcs;
-    size_t lds = rng_bytes;
-    uint32_t blocks = (uint32_t)((slots + nt - 1) / nt);
-    uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu * nt > 2048) per_cu = 2048 / nt;
-    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
-    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;
-    if (ensure_lds_attr((const void *)kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
   RtiowChoice choice;
   {
     int rcv = choose_rtiow_variant(scene, cam, P, nrows, want_stats, choice);
@@ -797,148 +771,41 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
     if (rce != RL_OK) return rce;
   }
   bool steal = false;  // set for the resume launch of a small shard (variant 1029)
-  auto launch_coop = [&](const uint32_t *d_pixels, uint32_t n_pixels) -> int {
-    constexpr int NW = 4;
-    CoopParams C{};
-    C.pixels = d_pixels, C.n_pixels = n_pixels, C.leaf_boxes = scene->d_fast_leaf_boxes;
-    C.counter = (uint32_t *)(scene->d_scratch + 256);
-    C.max_cand = 128;
-    HIP_TRY(hipMemsetAsync(C.counter, 0, 4, stream));
-    size_t lds = (size_t)8 * NW * 64 * sizeof(unsigned long long) + (size_t)NW * C.max_cand * sizeof(uint32_t);
-    uint32_t blocks = (n_pixels + NW - 1) / NW;
-    uint32_t cap = (uint32_t)g_cus * (16 / NW);  // 4 waves per SIMD at 128 VGPRs
-    if (blocks > cap) blocks = cap;
-    if (blocks == 0) return RL_OK;
-    // the lowest latency (boxes in registers: 3.3 us per ray, two waves per SIMD) while every pixel gets a wave at once; the register
-    // budget of four waves per SIMD (boxes from L2: 4.0 us per ray, +25 % throughput) for larger frames.  RL_COOP_MODE forces one (A/B).
-    int mode = g_sw.coop_mode >= 0 ? g_sw.coop_mode : (n_pixels <= (uint32_t)g_cus * 8u ? 2 : 0);
-    if (moments && mode == 2) {
-      if (ensure_lds_attr((const void *)rtiow_coop_moments_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_moments_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    } else if (moments) {
-      if (ensure_lds_attr((const void *)rtiow_coop_moments_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_moments_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    } else if (mode == 2) {
-      if (ensure_lds_attr((const void *)rtiow_coop_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    } else {
-      if (ensure_lds_attr((const void *)rtiow_coop_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    }
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
-  // LDS of a fast general launch: rings + stacks, and the tree's top in what is left (P.fg_top nodes, breadth first: FastGeneral::top_nodes)
-  auto fastg_lds = [&](int NT, int SD) -> size_t {
-    const size_t base = (size_t)NT * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));
-    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
-    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(H.fg.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
-    return base + (size_t)P.fg_top * sizeof(FastNodeQ);
-  };
+  const Mode mode = moments ? Mode::MOMENTS : Mode::FRAME;
+  const bool trans = rt.has_noise || rt.has_sphere_uv;
   auto launch_variant = [&]() -> int {
-    int rc;
     if (variant == 2) {
       constexpr int NT = 256;
-      size_t rb = (size_t)8 * NT * sizeof(unsigned long long);
       // register budget of two waves per SIMD (256 registers instead of 256 + 151): cornell_smoke 309 -> 493 Mrays/s, final_scene 170 -> 219
       // (three waves: 390 / 182).
-      rc = want_stats ? launch(rtiow_general_kernel<NT, true, 512>, NT, rb) : launch(rtiow_general_kernel<NT, false, 512>, NT, rb);
-    } else if (variant == 1031) {  // rings + the traversal stacks in LDS
-      // four steps per scheduling round (a step is an Infinity Cache / L2 round trip here, not an LDS one: lanes that fall out of TRAV
-      // should not wait 24 of them): cfg 5 +6.6 %, cfg 4 +0.7 % against the sphere kernel's 24
-      if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
-      bool trans = rt.has_noise || rt.has_sphere_uv;
-      // The flavour with both the media code and the Perlin / acos / atan2 code spills 126 VGPRs at 256 registers.  For small frames (at most
-      // three pixels per lane of the 512-lane form: the frame's time is per-ray latency, and scratch round trips are part of it) it
-      // runs as ONE wave per SIMD with the 512-register budget instead (what would spill lives in AGPRs): final_scene.rs at 400x400 442 ->
-      // 522 Mrays/s, at 560x560 664 -> 782, at 640x640 786 -> 811; from 720x720 on the two-wave form wins (975 against 818; 1100 against 810
-      // at 1000x1000: the one-wave form's throughput ends at ~810 Mrays/s).  Measured and not taken: the same for the other flavours (quads.rs -17 %, flat_world.rs -24 %, cornell_smoke.rs at
-      // 600x600 -30 %: they spill little, and lose the second wave's latency hiding).  RL_FASTG_NT256=1 / 0 forces it on / off (A/B).
+      const ValueKernel kern = want_stats ? rtiow_general_kernel<NT, true, 512> : rtiow_general_kernel<NT, false, 512>;
+      return launch_persistent(kern, NT, (size_t)8 * NT * sizeof(unsigned long long), slots, P, scene, stream);
+    }
+    if (variant == 1031) {  // rings + the traversal stacks in LDS; a moments frame in the two-waves-per-SIMD form whatever its size
       const bool media = H.fg.stage_roots.size() > 1;
-      const bool one_wave = !moments && trans && media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : (uint64_t)nrows * W <= (uint64_t)g_cus * 1536u);
-      if (moments) {  // the same four flavours and LDS layouts as below
-        if (media || trans) {
-          constexpr int NT = 512, SD = 40;
-          size_t rb = fastg_lds(NT, SD);
-          if (media) rc = trans ? launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, true, true>, NT, rb) : launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, false, true>, NT, rb);
-          else rc = launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, true, false>, NT, rb);
-        } else {
-          constexpr int NT = 768, SD = 20;
-          size_t rb = fastg_lds(NT, SD);
-          rc = launch_ptr(rtiow_fast_general_moments_kernel<NT, SD, false, false>, NT, rb);
-        }
-      } else if (one_wave) {
-        constexpr int NT = 256, SD = 40;
-        size_t rb = fastg_lds(NT, SD);
-        if (rb < 90000) rb = 90000;  // one workgroup per CU
-        rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, true, true>, NT, rb);
-      } else if (media) {  // several stages (media, unbounded Planes): the boundary walks and the Isotropic phase function need the 256-register budget
-        constexpr int NT = 512, SD = 40;
-        size_t rb = fastg_lds(NT, SD);
-        rc = trans ? launch_ptr(rtiow_fast_general_kernel<NT, SD, true, true>, NT, rb) : launch_ptr(rtiow_fast_general_kernel<NT, SD, false, true>, NT, rb);
-      } else if (trans) {  // 512 lanes per CU (the transcendental texture code needs 256 VGPRs), 40-entry stacks
-        constexpr int NT = 512, SD = 40;
-        size_t rb = fastg_lds(NT, SD);
-        rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, true>, NT, rb);
-      } else {  // 768 lanes per CU (3 waves per SIMD hide more of the node-fetch latency), 20-entry stacks: 208 B of LDS per lane, and the
-        // 4 KB that leaves of 160 KB hold the top 32 nodes of the tree (cfg 4 +1.1 %, cfg 5 +0.4 %; 128 nodes with 16-entry stacks: the same)
-        constexpr int NT = 768, SD = 20;
-        size_t rb = fastg_lds(NT, SD);
-        rc = launch_ptr(rtiow_fast_general_kernel<NT, SD, false>, NT, rb);
-      }
-    } else if (variant == 4) {
-      // 512 lanes per CU (2 waves per SIMD): the kernel needs ~200 VGPRs (~260 with the sin / Perlin / acos / atan2 code of
-      // scenes that have Noise textures or Image textures on spheres).  At 768 lanes (168 VGPRs) the spills land in the TRAV
-      // loop and cost 2.3x (measured, cfg 4: 1101 vs 465 Mrays/s).
-      bool trans = rt.has_noise || rt.has_sphere_uv;
-      size_t rb = (size_t)16 * 512 * sizeof(unsigned long long);
-      if (moments) {
-        size_t mb = (size_t)512 * (16 + MEDIA_SAVE_WORDS) * sizeof(unsigned long long);
-        if (rt.has_media) {
-          if (trans) rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, true, true, true>, 512, mb) : launch(rtiow_wave_general_moments_kernel<512, true, false, true>, 512, mb);
-          else rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, false, true, true>, 512, mb) : launch(rtiow_wave_general_moments_kernel<512, false, false, true>, 512, mb);
-        } else if (trans) rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, true, true, false>, 512, rb) : launch(rtiow_wave_general_moments_kernel<512, true, false, false>, 512, rb);
-        else rc = want_stats ? launch(rtiow_wave_general_moments_kernel<512, false, true, false>, 512, rb) : launch(rtiow_wave_general_moments_kernel<512, false, false, false>, 512, rb);
-      } else if (rt.has_media) {  // + the parked HitRecord of a medium scope: 96 B of LDS per lane
-        size_t mb = (size_t)512 * (16 + MEDIA_SAVE_WORDS) * sizeof(unsigned long long);
-        if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<512, true, true, true>, 512, mb) : launch(rtiow_wave_general_kernel<512, true, false, true>, 512, mb);
-        else rc = want_stats ? launch(rtiow_wave_general_kernel<512, false, true, true>, 512, mb) : launch(rtiow_wave_general_kernel<512, false, false, true>, 512, mb);
-      } else if (trans) rc = want_stats ? launch(rtiow_wave_general_kernel<512, true, true>, 512, rb) : launch(rtiow_wave_general_kernel<512, true, false>, 512, rb);
-      else rc = want_stats ? launch(rtiow_wave_general_kernel<512, false, true>, 512, rb) : launch(rtiow_wave_general_kernel<512, false, false>, 512, rb);
-    } else if (variant == 1025) {  // 4 waves per SIMD: rings + linked ops in LDS, spheres read from L2
-      constexpr int NT = 1024;
-      size_t rb = (size_t)16 * NT * sizeof(unsigned long long) + (size_t)P.n_ops * sizeof(DevOp);
-      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 2>, NT, rb);  // (never counting: route_moments_variant)
-      else rc = want_stats ? launch(rtiow_wave_kernel<NT, 2, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 2, false>, NT, rb);
-    } else if (variant == 1033) {  // A/B: EVERY pixel through the cooperative one-wave-per-pixel kernel (rl_rtiow_coop.h)
+      const bool one_wave = !moments && fastg_one_wave(trans, media, (uint64_t)nrows * W);
+      const FastgLayout lay = fastg_prepare(H.fg, trans, media, one_wave, P);
+      return launch_persistent(fast_general_kernel(mode, trans, media, one_wave), lay.nt, lay.lds, slots, P, scene, stream);
+    }
+    if (variant == 4) return launch_persistent(wave_general_kernel(mode, trans, want_stats, rt.has_media), 512, wave_general_lds(rt.has_media), slots, P, scene, stream);
+    if (variant == 1033) {  // A/B: EVERY pixel through the cooperative one-wave-per-pixel kernel (rl_rtiow_coop.h)
       rl_scene *ms = const_cast<rl_scene *>(scene);
       const size_t npix = (size_t)nrows * W;
       HIP_TRY(ms->d_coop_pixels.reserve(npix));
       hipLaunchKernelGGL(iota_u32, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, ms->d_coop_pixels, (uint32_t)npix);
-      rc = launch_coop(ms->d_coop_pixels, (uint32_t)npix);
-    } else if (variant == 1029) {  // 4 waves per SIMD: rings + fast traversal nodes in LDS, spheres read from L2; never a counting render
-      constexpr int NT = 1024;
-      size_t rb = (size_t)16 * NT * sizeof(unsigned long long) + fast_bytes;
-      // leave a TRAV round when fewer than a quarter of the lanes it started with are still walking (the counting kernels: 3/8): with
-      // pair nodes and inline misses the walks are short and uneven — +2.1 % (6596 -> 6734 Mrays/s; 24,2: 6740; 24,1: 6586; tools: RL_TUNE)
-      if (!g_sw.tune_set) P.tune[1] = 4, P.tune[2] = 4;
-      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 4>, NT, rb);
-      else if (steal) rc = launch(rtiow_wave_kernel<NT, 4, false, true>, NT, rb);
-      // counting only under rl_debug_fast_stats (verify build, tools/sched.py): scheduler occupancy of the fast kernel; its box / sphere counts are its own
-      else if (want_stats && FAST_STATS_KERNEL) rc = launch(rtiow_wave_kernel<NT, 4, FAST_STATS_KERNEL>, NT, rb);
-      else rc = launch(rtiow_wave_kernel<NT, 4, false>, NT, rb);
-    } else if (variant == 1027) {  // 4 waves per SIMD: rings + compact guarded ops in LDS, spheres read from L2
-      constexpr int NT = 1024;
-      size_t rb = (size_t)16 * NT * sizeof(unsigned long long) + compact_bytes;
-      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 3>, NT, rb);
-      else rc = want_stats ? launch(rtiow_wave_kernel<NT, 3, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 3, false>, NT, rb);
-    } else {  // 1024: everything through L2 (sphere-only worlds too large for LDS)
-      constexpr int NT = 1024;
-      size_t rb = (size_t)16 * NT * sizeof(unsigned long long);
-      if (moments) rc = launch(rtiow_wave_moments_kernel<NT, 0>, NT, rb);
-      else rc = want_stats ? launch(rtiow_wave_kernel<NT, 0, true>, NT, rb) : launch(rtiow_wave_kernel<NT, 0, false>, NT, rb);
+      CoopParams C{};
+      C.pixels = ms->d_coop_pixels, C.leaf_boxes = scene->d_fast_leaf_boxes, C.counter = (uint32_t *)(scene->d_scratch + 256);
+      HIP_TRY(hipMemsetAsync(C.counter, 0, 4, stream));
+      return coop_launch(P, C, (uint32_t)npix, moments, false, stream);
     }
-    return rc;
+    // the wave kernel, 4 waves per SIMD: the rings and, in LDS next to them, the fast traversal nodes (1029; never a counting render) / the
+    // compact guarded ops (1027) / the linked ops (1025) / nothing: everything through L2 (1024: sphere-only worlds too large for LDS)
+    const int lds_scene = variant == 1029 ? 4 : variant == 1027 ? 3 : variant == 1025 ? 2 : 0;
+    const size_t scene_bytes = lds_scene == 4 ? fast_bytes : lds_scene == 3 ? compact_bytes : lds_scene == 2 ? (size_t)P.n_ops * sizeof(DevOp) : 0;
+    // leave a TRAV round when fewer than a quarter of the lanes it started with are still walking (the counting kernels: 3/8): with
+    // pair nodes and inline misses the walks are short and uneven — +2.1 % (6596 -> 6734 Mrays/s; 24,2: 6740; 24,1: 6586; tools: RL_TUNE)
+    if (lds_scene == 4 && !g_sw.tune_set) P.tune[1] = 4, P.tune[2] = 4;
+    return launch_persistent(wave_kernel(mode, lds_scene, want_stats, steal), 1024, (size_t)16 * 1024 * sizeof(unsigned long long) + scene_bytes, slots, P, scene, stream);
   };
   P.sample_begin = 0, P.sample_end = cam->samples_per_pixel, P.resume = 0;
   P.pos_state = nullptr, P.tile_order = nullptr, P.tile_cost = nullptr;
@@ -1036,68 +903,22 @@ int rtiow_render_indep_launch(const rl_scene *scene, const rl_rtiow_camera *cam,
   }
   HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 512, stream));  // work counter and stats: once per render
   const bool trans = rt.has_noise || rt.has_sphere_uv;
-  const bool fg_media = H.fg.stage_roots.size() > 1;
-  const bool one_wave = variant == 1031 && trans && fg_media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : (uint64_t)nrows * W <= (uint64_t)g_cus * 1536u);
+  ValueKernel kern = nullptr;       // variants 1029 and 4: parameter block by value
+  PointerKernel kern_ptr = nullptr;  // variant 1031: by pointer, each pass its own stream-ordered copy
   int nt = 512;
   size_t lds = 0;
   if (variant == 1029) {
-    nt = 1024, lds = (size_t)16 * 1024 * sizeof(unsigned long long) + choice.fast_bytes;
+    kern = wave_kernel(Mode::INDEP, 4, false, false), nt = 1024, lds = (size_t)16 * 1024 * sizeof(unsigned long long) + choice.fast_bytes;
     if (!g_sw.tune_set) P.tune[1] = 4, P.tune[2] = 4;
   } else if (variant == 1031) {
-    if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
-    const int SD = (one_wave || fg_media || trans) ? 40 : 20;
-    nt = one_wave ? 256 : (fg_media || trans) ? 512 : 768;
-    const size_t base = (size_t)nt * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));  // as in rtiow_render_launch's fastg_lds
-    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
-    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(H.fg.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
-    lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
-    if (one_wave && lds < 90000) lds = 90000;  // one workgroup per CU
+    const bool media = H.fg.stage_roots.size() > 1, one_wave = fastg_one_wave(trans, media, (uint64_t)nrows * W);
+    const FastgLayout lay = fastg_prepare(H.fg, trans, media, one_wave, P);
+    kern_ptr = fast_general_kernel(Mode::INDEP, trans, media, one_wave), nt = lay.nt, lds = lay.lds;
   } else {
-    lds = (size_t)512 * (16 + (rt.has_media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long);
+    kern = wave_general_kernel(Mode::INDEP, trans, want_stats, rt.has_media), lds = wave_general_lds(rt.has_media);
   }
-  uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));  // persistent lanes: as many workgroups as stay resident
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu * (uint32_t)nt > 2048) per_cu = 2048 / (uint32_t)nt;
-  auto blocks_of = [&](const void *kern, uint32_t &blocks) -> int {
-    blocks = (uint32_t)(((uint64_t)P.n_slots + nt - 1) / nt);
-    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
-    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;
-    if (ensure_lds_attr(kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    return RL_OK;
-  };
-  auto launch = [&](void (*kern)(RtiowParams)) -> int {  // parameter block by value
-    uint32_t blocks = 0;
-    int rcb = blocks_of((const void *)kern, blocks);
-    if (rcb != RL_OK) return rcb;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
-  auto launch_ptr = [&](void (*kern)(const RtiowParams *)) -> int {  // by pointer: each pass its own stream-ordered copy (two slots)
-    uint32_t blocks = 0;
-    int rcb = blocks_of((const void *)kern, blocks);
-    if (rcb != RL_OK) return rcb;
-    const RtiowParams *slot = nullptr;
-    int rcs = stage_params(scene, P, stream, slot);
-    if (rcs != RL_OK) return rcs;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
   auto launch_pass = [&]() -> int {
-    if (variant == 1029) return launch(rtiow_wave_indep_kernel<1024, 4, false>);
-    if (variant == 1031) {
-      if (one_wave) return launch_ptr(rtiow_fast_general_indep_kernel<256, 40, true, true>);
-      if (fg_media) return trans ? launch_ptr(rtiow_fast_general_indep_kernel<512, 40, true, true>) : launch_ptr(rtiow_fast_general_indep_kernel<512, 40, false, true>);
-      if (trans) return launch_ptr(rtiow_fast_general_indep_kernel<512, 40, true, false>);
-      return launch_ptr(rtiow_fast_general_indep_kernel<768, 20, false, false>);
-    }
-    if (rt.has_media) {
-      if (trans) return want_stats ? launch(rtiow_wave_general_indep_kernel<512, true, true, true>) : launch(rtiow_wave_general_indep_kernel<512, true, false, true>);
-      return want_stats ? launch(rtiow_wave_general_indep_kernel<512, false, true, true>) : launch(rtiow_wave_general_indep_kernel<512, false, false, true>);
-    }
-    if (trans) return want_stats ? launch(rtiow_wave_general_indep_kernel<512, true, true, false>) : launch(rtiow_wave_general_indep_kernel<512, true, false, false>);
-    return want_stats ? launch(rtiow_wave_general_indep_kernel<512, false, true, false>) : launch(rtiow_wave_general_indep_kernel<512, false, false, false>);
+    return kern_ptr ? launch_persistent(kern_ptr, nt, lds, P.n_slots, P, scene, stream) : launch_persistent(kern, nt, lds, P.n_slots, P, scene, stream);
   };
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev0, stream));
   int rc = RL_OK;
@@ -1179,93 +1000,21 @@ int rtiow_render_pixels_launch(const rl_scene *scene, const rl_rtiow_camera *cam
     P.work_counter = scene->d_progress, coop_counter = scene->d_progress;
     HIP_TRY(hipMemsetAsync(scene->d_progress, 0, 8, stream));
   }
-  // persistent lanes: as many workgroups as stay resident, at most one lane per list element
-  auto blocks_of = [&](const void *kern, int nt, size_t lds, uint32_t &blocks) -> int {
-    uint32_t per_cu = (uint32_t)(g_lds_max / (lds ? lds : 1));
-    if (per_cu < 1) per_cu = 1;
-    if (per_cu * (uint32_t)nt > 2048) per_cu = 2048 / (uint32_t)nt;
-    blocks = (uint32_t)((n + nt - 1) / nt);
-    if (blocks > (uint32_t)g_cus * per_cu) blocks = (uint32_t)g_cus * per_cu;
-    if (g_sw.blocks_cap >= 1 && g_sw.blocks_cap < blocks) blocks = g_sw.blocks_cap;  // A/B only
-    if (ensure_lds_attr(kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
-    return RL_OK;
-  };
-  auto launch = [&](void (*kern)(RtiowParams), int nt, size_t lds) -> int {  // parameter block by value
-    uint32_t blocks = 0;
-    int rcb = blocks_of((const void *)kern, nt, lds, blocks);
-    if (rcb != RL_OK) return rcb;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
-  auto launch_ptr = [&](void (*kern)(const RtiowParams *), int nt, size_t lds) -> int {  // by pointer: a stream-ordered device copy
-    uint32_t blocks = 0;
-    int rcb = blocks_of((const void *)kern, nt, lds, blocks);
-    if (rcb != RL_OK) return rcb;
-    const RtiowParams *slot = nullptr;
-    int rcs = stage_params(scene, P, stream, slot);
-    if (rcs != RL_OK) return rcs;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
-    HIP_TRY(hipGetLastError());
-    return RL_OK;
-  };
+  const Mode mode = moments ? Mode::PIXELS_MOMENTS : Mode::PIXELS;
   const bool trans = rt.has_noise || rt.has_sphere_uv;
   if (timed) HIP_TRY(hipEventRecord(scene->ev0, stream));
   int rc = RL_OK;
-  if (which == PIXELS_COOP) {  // one wave per element; the two register modes by list length, as the frame path's launch_coop
-    constexpr int NW = 4;
+  if (which == PIXELS_COOP) {  // one wave per element
     CoopParams C{};
-    C.pixels = nullptr, C.n_pixels = (uint32_t)n, C.leaf_boxes = scene->d_fast_leaf_boxes, C.counter = coop_counter, C.max_cand = 128;
-    const size_t lds = (size_t)8 * NW * 64 * sizeof(unsigned long long) + (size_t)NW * C.max_cand * sizeof(uint32_t);
-    uint32_t blocks = (uint32_t)((n + NW - 1) / NW);
-    const uint32_t cap = (uint32_t)g_cus * (16 / NW);  // 4 waves per SIMD at 128 VGPRs
-    if (blocks > cap) blocks = cap;
-    const int mode = g_sw.coop_mode >= 0 ? g_sw.coop_mode : (n <= (uint64_t)g_cus * 8u ? 2 : 0);
-    if (moments && mode == 2) {
-      if (ensure_lds_attr((const void *)rtiow_coop_pixels_moments_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_pixels_moments_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    } else if (moments) {
-      if (ensure_lds_attr((const void *)rtiow_coop_pixels_moments_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_pixels_moments_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    } else if (mode == 2) {
-      if (ensure_lds_attr((const void *)rtiow_coop_pixels_kernel<NW, true, NW * 64>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_pixels_kernel<NW, true, NW * 64>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    } else {
-      if (ensure_lds_attr((const void *)rtiow_coop_pixels_kernel<NW, false, 1024>, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
-      hipLaunchKernelGGL((rtiow_coop_pixels_kernel<NW, false, 1024>), dim3(blocks), dim3(NW * 64), lds, stream, P, C);
-    }
-    HIP_TRY(hipGetLastError());
-  } else if (which == PIXELS_FAST_GENERAL) {  // the flavours and LDS layout of the frame's variant 1031 (rtiow_render_launch)
-    if (!g_sw.tune_set) P.tune[0] = 4, P.tune[2] = 4, P.tune[3] = FASTG_STEP_BUDGET;
+    C.pixels = nullptr, C.leaf_boxes = scene->d_fast_leaf_boxes, C.counter = coop_counter;
+    rc = coop_launch(P, C, n, moments, true, stream);
+  } else if (which == PIXELS_FAST_GENERAL) {  // a moments list in the two-waves-per-SIMD form whatever its length
     const bool media = H.fg.stage_roots.size() > 1;
-    const bool one_wave = !moments && trans && media && (g_sw.fastg_nt256 >= 0 ? g_sw.fastg_nt256 != 0 : n <= (uint64_t)g_cus * 1536u);
-    const int SD = (media || trans) ? 40 : 20, nt = one_wave ? 256 : (media || trans) ? 512 : 768;
-    const size_t base = (size_t)nt * (16 * sizeof(unsigned long long) + (size_t)SD * sizeof(uint32_t));
-    const size_t room = g_lds_max > base ? (g_lds_max - base) / sizeof(FastNodeQ) : 0;
-    P.fg_top = g_sw.fastg_top ? (uint32_t)std::min<size_t>(H.fg.top_nodes, std::min<size_t>(room, g_sw.fastg_top_max)) : 0u;
-    size_t lds = base + (size_t)P.fg_top * sizeof(FastNodeQ);
-    if (one_wave && lds < 90000) lds = 90000;  // one workgroup per CU
-    if (moments) {
-      if (media) rc = trans ? launch_ptr(rtiow_fast_general_pixels_moments_kernel<512, 40, true, true>, nt, lds) : launch_ptr(rtiow_fast_general_pixels_moments_kernel<512, 40, false, true>, nt, lds);
-      else if (trans) rc = launch_ptr(rtiow_fast_general_pixels_moments_kernel<512, 40, true, false>, nt, lds);
-      else rc = launch_ptr(rtiow_fast_general_pixels_moments_kernel<768, 20, false, false>, nt, lds);
-    } else if (one_wave) rc = launch_ptr(rtiow_fast_general_pixels_kernel<256, 40, true, true>, nt, lds);
-    else if (media) rc = trans ? launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, true, true>, nt, lds) : launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, false, true>, nt, lds);
-    else if (trans) rc = launch_ptr(rtiow_fast_general_pixels_kernel<512, 40, true, false>, nt, lds);
-    else rc = launch_ptr(rtiow_fast_general_pixels_kernel<768, 20, false, false>, nt, lds);
-  } else {  // reference order: 512 lanes per CU, rings (and a medium scope's parked HitRecord) in LDS, as the frame's variant 4
-    const size_t lds = (size_t)512 * (16 + (rt.has_media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long);
-    if (moments) {
-      if (rt.has_media) {
-        if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, true, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, true, false, true>, 512, lds);
-        else rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, false, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, false, false, true>, 512, lds);
-      } else if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, true, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, true, false, false>, 512, lds);
-      else rc = want_stats ? launch(rtiow_wave_general_pixels_moments_kernel<512, false, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_moments_kernel<512, false, false, false>, 512, lds);
-    } else if (rt.has_media) {
-      if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, true, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, true, false, true>, 512, lds);
-      else rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, false, true, true>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, false, false, true>, 512, lds);
-    } else if (trans) rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, true, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, true, false, false>, 512, lds);
-    else rc = want_stats ? launch(rtiow_wave_general_pixels_kernel<512, false, true, false>, 512, lds) : launch(rtiow_wave_general_pixels_kernel<512, false, false, false>, 512, lds);
+    const bool one_wave = !moments && fastg_one_wave(trans, media, n);
+    const FastgLayout lay = fastg_prepare(H.fg, trans, media, one_wave, P);
+    rc = launch_persistent(fast_general_kernel(mode, trans, media, one_wave), lay.nt, lay.lds, n, P, scene, stream);
+  } else {  // reference order
+    rc = launch_persistent(wave_general_kernel(mode, trans, want_stats, rt.has_media), 512, wave_general_lds(rt.has_media), n, P, scene, stream);
   }
   if (timed) HIP_TRY(hipEventRecord(scene->ev1, stream));
   return rc;  // the caller ends the render with collect_stats / post_status, which record ev_last behind the stats copy
