@@ -588,6 +588,52 @@ int rl_rtiow_render_pixels_features_device(const rl_scene *, const rl_rtiow_came
                                            uint64_t n, const rl_rtiow_features *d_out, void *hip_stream, rl_stats *opt_stats);
 
 /* =====================================================================
+ *  Denoising: an edge-avoiding a-trous filter for noisy and adaptive renders
+ * =====================================================================
+ * What consumes the mean and variance of the moments and adaptive renders and the guide buffers of the feature renders.  It needs no scene.
+ * One pass.  All images are row-major f64: color [H][W][3], variance [H][W][3] (the variance of each pixel mean, >= 0), guides [H][W][G]
+ * with 0 <= G <= 8 (G = n_guides).  Parameters: color_sigma2 >= 0, variance_floor > 0, guide_inv_sigma[G] >= 0 where 0 switches a guide
+ * off, step >= 1.  Let h = [1/16, 1/4, 3/8, 1/4, 1/16].  For pixel p = (x, y), visit the 25 taps q = (x + i*step, y + j*step) with
+ * j = -2..2 outer and i = -2..2 inner.  Skip taps outside the image.  Every operation is rounded separately and sums run left to right:
+ *     vsum(r) = (var_r[0] + var_r[1]) + var_r[2]
+ *     d       = color_p - color_q ;  d2 = (d0*d0 + d1*d1) + d2*d2
+ *     D       = color_sigma2 * (vsum(p) + vsum(q)) + variance_floor
+ *     xg      = 0 ; for k in 0..G-1: e = (guide_p[k] - guide_q[k]) * guide_inv_sigma[k] ; xg = xg + e*e
+ *     w       = ((h[j+2]*h[i+2]) * D) / ((D + d2) * (1.0 + xg))
+ *     sw      = sw + w ;  ac[c] = ac[c] + w * color_q[c] ;  av[c] = av[c] + (w*w) * var_q[c]
+ *     out_color[c] = ac[c] / sw ;  out_variance[c] = av[c] / (sw*sw)
+ * sw, ac and av start at +0.0.  Binary64 throughout, + - * / only, no FMA, no libm call: the weights are Cauchy-type, 1 / (1 + x), in
+ * place of the usual exp(-x), so a host that follows the statement gets every output bit (tests/atrous_model.py does).  One division per tap.
+ * What follows from the definition:
+ *  - The centre tap always has w = (9/64 * D) / (D * 1) > 0, so sw > 0 for every pixel of every image, a 1 x 1 image included.
+ *  - Non-finite inputs give non-finite outputs in the pixels whose footprint (the 25 taps) they touch, and in no other pixel.  No input is
+ *    scanned.
+ *  - A guide with guide_inv_sigma[k] = 0 leaves every bit as the call without that channel has it (finite guides: e = +-0, xg + 0 = xg).
+ *  - A pass is not in place: every pixel reads its neighbours' inputs.
+ * rl_denoise_atrous_pass_device enqueues ONE pass on the caller's stream and returns: asynchronous, device pointers, owns no device memory.
+ * rl_denoise_atrous takes host arrays, stages them and runs `iterations` passes with step = 1, 2, .., 2^(iterations-1), each reading the
+ * colour and variance the one before wrote (the guides stay), ping-ponging between two staged pairs, and copies the last pass's outputs
+ * back; iterations = 0 copies the inputs through.  d_out_variance / out_variance may be NULL (the colour bytes are the same); d_guides /
+ * guides may be NULL when n_guides = 0 and is not read then.  guide_inv_sigma[k] for k >= n_guides is not read.
+ * Errors.  RL_E_INVALID, before the device is looked at (so also without one), nothing written: NULL params, colour, variance or colour
+ * output; NULL guides with n_guides > 0; n_guides > 8; reserved != 0; variance_floor not > 0; a non-finite or negative color_sigma2,
+ * variance_floor or guide_inv_sigma[k < n_guides]; step = 0 or step > 1 << 20; iterations > 12; an output pointer equal to an input
+ * pointer or to the other output; width * height >= 0xFFFF0000.  Then, without a device, RL_E_NO_DEVICE (no CPU fallback).  Then a
+ * zero-area image: RL_OK, nothing read or written.  The device form runs on the current device; the host form on the library's device 0.
+ * Not offered: f32 images, temporal accumulation, a variance pre-filter, multi-GPU forms, rgb8 output. */
+typedef struct rl_atrous_params {
+  double color_sigma2;       /* >= 0: how many variances of colour difference halve a tap's weight */
+  double variance_floor;     /* > 0: keeps D positive where both variances are 0 */
+  uint32_t n_guides;         /* G, 0 .. 8 */
+  uint32_t reserved;         /* 0 */
+  double guide_inv_sigma[8]; /* 1 / sigma of guide channel k; 0: that guide is off */
+} rl_atrous_params;          /* 88 bytes */
+int rl_denoise_atrous_pass_device(uint32_t width, uint32_t height, uint32_t step, const rl_atrous_params *, const void *d_color,
+                                  const void *d_variance, const void *d_guides, void *d_out_color, void *d_out_variance, void *hip_stream);
+int rl_denoise_atrous(uint32_t width, uint32_t height, uint32_t iterations, const rl_atrous_params *, const double *color,
+                      const double *variance, const double *guides, double *out_color, double *out_variance);
+
+/* =====================================================================
  *  Batched ray queries: the reference's per-ray primitives on the device
  * =====================================================================
  *   rl_rtiow_hit_rays*      <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval) -> Option<(&Material, HitRecord)>

@@ -4,5 +4,5 @@ Product = csrc/ (hand-written HIP for gfx950 behind the C ABI of include/rl_rend
 mirror of the reference's scene-building API).  `api` is the ctypes plumbing used by tests and bench.
 """
 from . import api  # noqa: F401
-from .api import (Adaptive, Camera, CameraParams, Canvas, Features, Moments, RLError, RtcWorld, World, canvas_ppm, init, output_ppm,  # noqa: F401
-                  rtc_camera)
+from .api import (Adaptive, AtrousParams, Camera, CameraParams, Canvas, Features, Moments, RLError, RtcWorld, World, atrous_params, canvas_ppm,  # noqa: F401
+                  denoise_atrous, denoise_atrous_pass_device, denoise_render, init, output_ppm, rtc_camera)

@@ -215,7 +215,8 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtiow_render_moments_rows", "rl_rtiow_render_moments_device", "rl_rtiow_render_pixels_moments", "rl_rtiow_render_pixels_moments_device",
                   "rl_rtiow_render_adaptive_rows", "rl_rtiow_render_adaptive_device",
                   "rl_rtiow_render_features_rows", "rl_rtiow_render_features_device", "rl_rtiow_render_pixels_features",
-                  "rl_rtiow_render_pixels_features_device"]
+                  "rl_rtiow_render_pixels_features_device",
+                  "rl_denoise_atrous_pass_device", "rl_denoise_atrous"]
 
 
 def _material_query_argtypes(L):
@@ -289,6 +290,17 @@ def _render_features_argtypes(L):
                                                   C.POINTER(Stats)]
     L.rl_rtiow_render_pixels_features_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
                                                          C.POINTER(RtiowFeatures), C.c_void_p, C.POINTER(Stats)]
+
+
+class AtrousParams(C.Structure):  # rl_atrous_params
+    _fields_ = [("color_sigma2", C.c_double), ("variance_floor", C.c_double), ("n_guides", C.c_uint32), ("reserved", C.c_uint32),
+                ("guide_inv_sigma", C.c_double * 8)]
+
+
+def _denoise_argtypes(L):
+    L.rl_denoise_atrous_pass_device.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]
+    L.rl_denoise_atrous.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 def _pixel_list(xs, ys):
@@ -365,6 +377,8 @@ def render_lib():
             _render_adaptive_argtypes(L)
         if hasattr(L, "rl_rtiow_render_features_rows"):  # (likewise)
             _render_features_argtypes(L)
+        if hasattr(L, "rl_denoise_atrous"):  # (likewise)
+            _denoise_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -598,6 +612,17 @@ def last_query():
     L.rl_debug_last_query.argtypes = [C.c_void_p]
     _check(L.rl_debug_last_query(out))
     return {"kernel": {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast"}.get(int(out[0]), "none"), "retraced": int(out[1])}
+
+
+def set_denoise_route(route):
+    """rl_debug_set_denoise_route: which route serves a denoising pass.  -1: the default (LDS, the faster one at every step measured);
+    0: every tap read from the images; 1: one lattice's tile and halo staged in LDS.  Same bytes either way; tests compare them, tools/denoise_ab.py times them."""
+    render_lib().rl_debug_set_denoise_route(int(route))
+
+
+def last_denoise_route():
+    """rl_debug_last_denoise_route: "images" / "lds" for the most recent denoising pass, "none" before the first."""
+    return {0: "images", 1: "lds"}.get(int(render_lib().rl_debug_last_denoise_route()), "none")
 
 
 def material_query_max_lanes():
@@ -1144,6 +1169,9 @@ class Adaptive:
         return np.maximum((self.sq - self.sums * self.sums / n) / (n - 1) / n, 0.0)
 
 
+GUIDE_KINDS = ("albedo", "normal", "depth", "coverage")  # Features.guides: 3 + 3 + 1 + 1 channels
+
+
 @dataclass
 class Features:
     """The outputs of a feature render (Camera.render_features; include/rl_render.h "Feature renders"): per pixel, over the `samples` jittered
@@ -1171,6 +1199,19 @@ class Features:
 
     def coverage(self) -> np.ndarray:
         return self.hit_count / self.samples
+
+    def guides(self, want=GUIDE_KINDS) -> np.ndarray:
+        """The guide image [H, W, G] denoise_atrous takes, channels in the order of `want`: albedo (3), normal (3), depth (1), coverage (1).
+        Depth here is depth_sum / max(hit_count, 1): 0 where no ray hit, never inf (an inf guide would make the filter's output NaN);
+        coverage tells those pixels apart."""
+        make = {"albedo": self.albedo, "normal": self.normal, "depth": lambda: (self.depth_sum / np.maximum(self.hit_count, 1))[..., None],
+                "coverage": lambda: self.coverage()[..., None]}
+        for k in want:
+            if k not in make:
+                raise ValueError(f"want holds {k!r}; the guides are {GUIDE_KINDS}")
+        if not want:
+            raise ValueError("no guide asked for")
+        return np.ascontiguousarray(np.concatenate([make[k]() for k in want], axis=-1), dtype=np.float64)
 
     def merge(self, other):  # as Moments.merge: the sums of renders that continue each other (first_sample) add
         def add(a, b):
@@ -1485,6 +1526,91 @@ class Camera:
         if stats is not None:
             stats.update(st.as_dict())
             stats["rc"] = rc
+
+
+# ---- denoising (include/rl_render.h "Denoising", rl_denoise_atrous*).  The default sigmas below are UNMEASURED defaults:
+# plausible for unit-scale colours and the guides of Features.guides(), tuned on nothing.
+DENOISE_COLOR_SIGMA = 2.0        # color_sigma2 = 4: a tap whose squared colour difference is 4 (summed) variances has half weight
+DENOISE_VARIANCE_FLOOR = 1e-8
+DENOISE_GUIDE_SIGMA = {"albedo": 0.1, "normal": 0.25, "depth": 1.0, "coverage": 0.25}  # per channel of that kind; depth in scene units of t
+
+
+def atrous_params(n_guides=0, color_sigma=DENOISE_COLOR_SIGMA, guide_sigma=None, variance_floor=DENOISE_VARIANCE_FLOOR, guide_inv_sigma=None) -> AtrousParams:
+    """The rl_atrous_params of a call: color_sigma2 = color_sigma * color_sigma; guide_inv_sigma[k] = 1 / guide_sigma[k], guide_sigma one number
+    for all or one per channel, None / inf switching the channel off (default: every guide at sigma 1); guide_inv_sigma= gives the
+    reciprocals themselves (0 = off) and wins.  Range errors are the library's to refuse (RL_E_INVALID); a wrong length is a ValueError."""
+    n_guides = int(n_guides)
+    if guide_inv_sigma is None:
+        gs = 1.0 if guide_sigma is None else guide_sigma
+        gs = [gs] * n_guides if np.ndim(gs) == 0 else list(gs)
+        guide_inv_sigma = [0.0 if g is None or g == float("inf") else 1.0 / float(g) for g in gs]
+    inv = [float(guide_inv_sigma)] * n_guides if np.ndim(guide_inv_sigma) == 0 else [float(v) for v in guide_inv_sigma]
+    if len(inv) != n_guides:
+        raise ValueError(f"{len(inv)} guide sigmas for {n_guides} guide channels")
+    return AtrousParams(float(color_sigma) * float(color_sigma), float(variance_floor), n_guides, 0, (C.c_double * 8)(*inv[:8]))  # n_guides > 8: the library refuses it
+
+
+def _denoise_images(color, variance, guides):
+    color, variance = np.ascontiguousarray(color, dtype=np.float64), np.ascontiguousarray(variance, dtype=np.float64)
+    if color.ndim != 3 or color.shape[2] != 3 or variance.shape != color.shape:
+        raise ValueError(f"color and variance must both be [H, W, 3] (got {color.shape} and {variance.shape})")
+    if guides is not None:
+        guides = np.ascontiguousarray(guides, dtype=np.float64)
+        if guides.ndim != 3 or guides.shape[:2] != color.shape[:2]:
+            raise ValueError(f"guides must be [H, W, G] beside a colour image of {color.shape} (got {guides.shape})")
+        if guides.shape[2] == 0:
+            guides = None
+    return color, variance, guides
+
+
+def denoise_atrous(color, variance, guides=None, iterations=5, color_sigma=DENOISE_COLOR_SIGMA, guide_sigma=None, variance_floor=DENOISE_VARIANCE_FLOOR,
+                   guide_inv_sigma=None, out_variance=True, params: AtrousParams = None):
+    """rl_denoise_atrous: `iterations` passes of the edge-avoiding a-trous filter (step 1, 2, 4, ..) over color [H, W, 3] with the variance
+    of each pixel mean [H, W, 3] and optional guides [H, W, G <= 8] -> (color, variance), both [H, W, 3] f64; out_variance=False: (color,
+    None).  The sigmas go through atrous_params (params= gives the struct itself)."""
+    color, variance, guides = _denoise_images(color, variance, guides)
+    H, W = color.shape[:2]
+    G = 0 if guides is None else guides.shape[2]
+    p = params if params is not None else atrous_params(G, color_sigma, guide_sigma, variance_floor, guide_inv_sigma)
+    if p.n_guides != G:
+        raise ValueError(f"params has n_guides = {p.n_guides}, the guide image {G} channels")
+    out_c = np.empty_like(color)
+    out_v = np.empty_like(color) if out_variance else None
+    _check(render_lib().rl_denoise_atrous(W, H, int(iterations), C.byref(p), color.ctypes.data, variance.ctypes.data, None if guides is None else guides.ctypes.data,
+                                          out_c.ctypes.data, None if out_v is None else out_v.ctypes.data))
+    return out_c, out_v
+
+
+def denoise_atrous_pass_device(width, height, step, params: AtrousParams, d_color, d_variance, d_guides, d_out_color, d_out_variance=0, stream=0):
+    """rl_denoise_atrous_pass_device: one pass on `stream` over device images (pointers; d_guides 0 with no guides, d_out_variance 0 = not
+    wanted).  Asynchronous; the outputs must not be the inputs."""
+    _check(render_lib().rl_denoise_atrous_pass_device(int(width), int(height), int(step), C.byref(params), C.c_void_p(d_color or None), C.c_void_p(d_variance or None),
+                                                      C.c_void_p(d_guides or None), C.c_void_p(d_out_color or None), C.c_void_p(d_out_variance or None),
+                                                      C.c_void_p(stream)))
+
+
+def _denoise_render_inputs(estimate, features, guide_sigma, want):
+    """What denoise_render hands to denoise_atrous: (colour, variance, guides, per-channel guide sigmas, the albedo it divided by)."""
+    mean = estimate.mean() if isinstance(estimate, Adaptive) else estimate.sums * (1.0 / estimate.samples)
+    var = estimate.variance_of_mean()
+    albedo = features.albedo()
+    if albedo.shape != mean.shape:
+        raise ValueError(f"the estimate is {mean.shape}, the features' albedo {albedo.shape}")
+    a = np.where(albedo > 0.0, albedo, 1.0)
+    sig = dict(DENOISE_GUIDE_SIGMA, **(guide_sigma or {}))
+    per_channel = [s for k in want for s in [sig[k]] * (3 if k in ("albedo", "normal") else 1)]
+    return mean / a, var / (a * a), features.guides(want), per_channel, a
+
+
+def denoise_render(estimate, features: Features, iterations=5, color_sigma=DENOISE_COLOR_SIGMA, guide_sigma=None, variance_floor=DENOISE_VARIANCE_FLOOR,
+                   want=GUIDE_KINDS):
+    """A Moments or Adaptive render denoised with the guides of a Features render of the same camera -> (color, variance) of the pixel MEANS,
+    [H, W, 3] f64.  Plain numpy around one denoise_atrous: mean and variance of the mean are divided by the albedo and its square where
+    the albedo is > 0 (so that texture detail is not what the filter sees as noise), filtered with features.guides(want), and multiplied
+    back.  guide_sigma: {kind: sigma} over DENOISE_GUIDE_SIGMA's unmeasured defaults."""
+    color, variance, guides, per_channel, a = _denoise_render_inputs(estimate, features, guide_sigma, want)
+    color, variance = denoise_atrous(color, variance, guides, iterations, color_sigma, per_channel, variance_floor)
+    return color * a, variance * (a * a)
 
 
 def _take_string(ptr, n):

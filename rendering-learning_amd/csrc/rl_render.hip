@@ -1792,3 +1792,4 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 // the batched queries' host layer (22 entry points); last, so that its kernels keep their order of first use
 #include "rl_query_api.h"
 #include "rl_features_api.h"
+#include "rl_denoise.h"

@@ -625,6 +625,23 @@ int rlh_render_features_probe(uint64_t width, uint64_t spp, uint64_t first_sampl
     return -1;
   }
 }
+// rtiow::denoise_atrous through the C++ mirror: color, variance and the two outputs = width * height * 3 doubles, guides = width * height *
+// params->n_guides doubles.  0 or -1 (rlh_last_error).
+int rlh_denoise_atrous_probe(uint64_t width, uint64_t height, uint32_t iterations, const rl_atrous_params *params, const double *color, const double *variance,
+                             const double *guides, double *out_color, double *out_variance) {
+  try {
+    const size_t n = (size_t)width * height;
+    rtiow::Denoised d = rtiow::denoise_atrous((size_t)width, (size_t)height, iterations, *params, std::vector<double>(color, color + n * 3),
+                                              std::vector<double>(variance, variance + n * 3),
+                                              std::vector<double>(guides, guides + (params->n_guides ? n * params->n_guides : 0)));
+    std::memcpy(out_color, d.color.data(), d.color.size() * sizeof(double));
+    std::memcpy(out_variance, d.variance.data(), d.variance.size() * sizeof(double));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
 // which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
 // b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,

@@ -108,6 +108,17 @@ Camera::Features Camera::render_features(const Hittable &world, uint64_t first_s
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_features_rows: ") + rl_last_error());
   return ft;
 }
+Denoised denoise_atrous(size_t width, size_t height, uint32_t iterations, const rl_atrous_params &params, const std::vector<double> &color,
+                        const std::vector<double> &variance, const std::vector<double> &guides) {
+  const size_t n = width * height;
+  if (width > UINT32_MAX || height > UINT32_MAX || color.size() != n * 3 || variance.size() != n * 3 || guides.size() != n * params.n_guides)
+    throw std::runtime_error("denoise_atrous: size mismatch");
+  Denoised d{std::vector<double>(n * 3), std::vector<double>(n * 3)};
+  int rc = rl_denoise_atrous((uint32_t)width, (uint32_t)height, iterations, &params, color.data(), variance.data(), params.n_guides ? guides.data() : nullptr,
+                             d.color.data(), d.variance.data());
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_denoise_atrous: ") + rl_last_error());
+  return d;
+}
 Canvas Camera::render_independent(const Hittable &world) const { return render_independent_impl(*this, world, nullptr); }
 Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
   return render_independent_impl(*this, world, &checkpoint);

@@ -832,6 +832,16 @@ struct Camera {
   std::vector<rl_ray> get_rays(const uint32_t *px, const uint32_t *py, rl_rng_cursor *cursors, size_t n) const;
 };
 
+// ---------------------------------------------------------------- denoising (rl_denoise_atrous; defined in host_render.cpp)
+// `iterations` passes (step 1, 2, 4, ..) of the edge-avoiding a-trous filter of include/rl_render.h "Denoising" over color [H][W][3] with
+// the variance of each pixel mean [H][W][3] and guides [H][W][params.n_guides] (empty with no guides), e.g. a Moments' or Adaptive's mean
+// and variance beside a Features' albedo, normal and depth.  Throws what the library refuses (a size mismatch included).
+struct Denoised {
+  std::vector<double> color, variance;  // [H][W][3]
+};
+Denoised denoise_atrous(size_t width, size_t height, uint32_t iterations, const rl_atrous_params &params, const std::vector<double> &color,
+                        const std::vector<double> &variance, const std::vector<double> &guides = {});
+
 // ---------------------------------------------------------------- color.rs / output.rs
 namespace srgb {  // color.rs:114-136
 inline double srgb_to_linear(double u) { return u <= 0.04045 ? u / 12.92 : std::pow((u + 0.055) / (1.0 + 0.055), 2.4); }
