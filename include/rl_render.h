@@ -592,7 +592,7 @@ int rl_rtiow_render_pixels_features_device(const rl_scene *, const rl_rtiow_came
  * =====================================================================
  * What consumes the mean and variance of the moments and adaptive renders and the guide buffers of the feature renders.  It needs no scene.
  * One pass.  All images are row-major f64: color [H][W][3], variance [H][W][3] (the variance of each pixel mean, >= 0), guides [H][W][G]
- * with 0 <= G <= 8 (G = n_guides).  Parameters: color_sigma2 >= 0, variance_floor > 0, guide_inv_sigma[G] >= 0 where 0 switches a guide
+ * with 0 <= G <= 8 (G = n_guides).  Parameters: color_sigma2 >= 0, variance_floor >= DBL_MIN, guide_inv_sigma[G] >= 0 where 0 switches a guide
  * off, step >= 1.  Let h = [1/16, 1/4, 3/8, 1/4, 1/16].  For pixel p = (x, y), visit the 25 taps q = (x + i*step, y + j*step) with
  * j = -2..2 outer and i = -2..2 inner.  Skip taps outside the image.  Every operation is rounded separately and sums run left to right:
  *     vsum(r) = (var_r[0] + var_r[1]) + var_r[2]
@@ -605,7 +605,14 @@ int rl_rtiow_render_pixels_features_device(const rl_scene *, const rl_rtiow_came
  * sw, ac and av start at +0.0.  Binary64 throughout, + - * / only, no FMA, no libm call: the weights are Cauchy-type, 1 / (1 + x), in
  * place of the usual exp(-x), so a host that follows the statement gets every output bit (tests/atrous_model.py does).  One division per tap.
  * What follows from the definition:
- *  - The centre tap always has w = (9/64 * D) / (D * 1) > 0, so sw > 0 for every pixel of every image, a 1 x 1 image included.
+ *  - variance_floor is finite and a normal number (>= DBL_MIN), so D >= DBL_MIN wherever it is finite; there the centre tap has
+ *    w = (9/64 * D) / (D * 1) > 0, so sw > 0 wherever D is finite, a 1 x 1 image included.  (A subnormal floor is refused because it
+ *    breaks this: with 5e-324 on a flat image without variance, 9/64 * D rounds to 0, sw = 0 and every output is 0 / 0.)
+ *  - With finite inputs and color_sigma2 * (vsum(p) + vsum(q)) + variance_floor finite for every pair of a pixel and a tap, every output
+ *    is finite: an overflowing d2 or xg only takes that tap's w to 0.  (Two provisos at the very edge of the range: a guide difference that
+ *    itself overflows under guide_inv_sigma[k] = 0 is inf * 0, and colours within a few ulps of DBL_MAX can round ac up to inf.)
+ *  - Where D overflows to +inf (finite variances whose scaled sum exceeds DBL_MAX), that tap's w is inf / inf = NaN, and sw and every
+ *    output of that pixel are NaN.  No input is scanned for this either.
  *  - Non-finite inputs give non-finite outputs in the pixels whose footprint (the 25 taps) they touch, and in no other pixel.  No input is
  *    scanned.
  *  - A guide with guide_inv_sigma[k] = 0 leaves every bit as the call without that channel has it (finite guides: e = +-0, xg + 0 = xg).
@@ -616,14 +623,14 @@ int rl_rtiow_render_pixels_features_device(const rl_scene *, const rl_rtiow_came
  * back; iterations = 0 copies the inputs through.  d_out_variance / out_variance may be NULL (the colour bytes are the same); d_guides /
  * guides may be NULL when n_guides = 0 and is not read then.  guide_inv_sigma[k] for k >= n_guides is not read.
  * Errors.  RL_E_INVALID, before the device is looked at (so also without one), nothing written: NULL params, colour, variance or colour
- * output; NULL guides with n_guides > 0; n_guides > 8; reserved != 0; variance_floor not > 0; a non-finite or negative color_sigma2,
+ * output; NULL guides with n_guides > 0; n_guides > 8; reserved != 0; variance_floor not finite and a normal number (below DBL_MIN: 0, subnormal); a non-finite or negative color_sigma2,
  * variance_floor or guide_inv_sigma[k < n_guides]; step = 0 or step > 1 << 20; iterations > 12; an output pointer equal to an input
  * pointer or to the other output; width * height >= 0xFFFF0000.  Then, without a device, RL_E_NO_DEVICE (no CPU fallback).  Then a
  * zero-area image: RL_OK, nothing read or written.  The device form runs on the current device; the host form on the library's device 0.
  * Not offered: f32 images, temporal accumulation, a variance pre-filter, multi-GPU forms, rgb8 output. */
 typedef struct rl_atrous_params {
   double color_sigma2;       /* >= 0: how many variances of colour difference halve a tap's weight */
-  double variance_floor;     /* > 0: keeps D positive where both variances are 0 */
+  double variance_floor;     /* finite and a normal number, >= DBL_MIN: keeps D positive where both variances are 0 */
   uint32_t n_guides;         /* G, 0 .. 8 */
   uint32_t reserved;         /* 0 */
   double guide_inv_sigma[8]; /* 1 / sigma of guide channel k; 0: that guide is off */

@@ -625,6 +625,25 @@ def last_denoise_route():
     return {0: "images", 1: "lds"}.get(int(render_lib().rl_debug_last_denoise_route()), "none")
 
 
+def set_denoise_blocks(max_blocks):
+    """rl_debug_set_denoise_blocks: the most workgroups a denoising pass launches; 0: the default, the CU-derived cap of the route.  With
+    fewer workgroups than tiles a workgroup takes several tiles in turn; tests force that on tiny images."""
+    L = render_lib()
+    L.rl_debug_set_denoise_blocks.argtypes = [C.c_uint32]
+    L.rl_debug_set_denoise_blocks.restype = None
+    L.rl_debug_set_denoise_blocks(int(max_blocks))
+
+
+def last_denoise_launch():
+    """rl_debug_last_denoise_launch: {"tiles", "blocks"} of the most recent denoising pass: its tiles and the workgroups that shared them."""
+    out = (C.c_uint64 * 2)()
+    L = render_lib()
+    L.rl_debug_last_denoise_launch.argtypes = [C.c_void_p]
+    L.rl_debug_last_denoise_launch.restype = None
+    L.rl_debug_last_denoise_launch(out)
+    return {"tiles": int(out[0]), "blocks": int(out[1])}
+
+
 def material_query_max_lanes():
     """rl_debug_material_query_lanes: the most lanes one scatter_rays* / texture_values* launch has on the current device (the grid cap,
     csrc/rl_material_query.h MATERIAL_QUERY_MAX_BLOCKS_PER_CU workgroups per CU); a larger batch puts several elements through one lane."""

@@ -3,7 +3,7 @@
 // g_cus, g_lds_max, set_err, HIP_TRY) and the staging of rl_host_api.h.  It needs no scene.
 //
 // One pass.  Images are row-major f64: color [H][W][3], variance [H][W][3] (the variance of each pixel mean, >= 0), guides [H][W][G],
-// 0 <= G <= 8.  Parameters: color_sigma2 >= 0, variance_floor > 0, guide_inv_sigma[G] >= 0 (0 switches a guide off), step >= 1.
+// 0 <= G <= 8.  Parameters: color_sigma2 >= 0, variance_floor >= DBL_MIN, guide_inv_sigma[G] >= 0 (0 switches a guide off), step >= 1.
 // Let h = [1/16, 1/4, 3/8, 1/4, 1/16].  For pixel p = (x, y), visit the 25 taps q = (x + i*step, y + j*step) with j = -2..2 outer and
 // i = -2..2 inner.  Skip taps outside the image.  Every operation is rounded separately (binary64, no FMA) and sums run left to right:
 //     vsum(r) = (var_r[0] + var_r[1]) + var_r[2]
@@ -14,8 +14,11 @@
 //     sw      = sw + w ;  ac[c] = ac[c] + w * color_q[c] ;  av[c] = av[c] + (w*w) * var_q[c]
 //     out_color[c] = ac[c] / sw ;  out_variance[c] = av[c] / (sw*sw)
 // sw, ac and av start at +0.0.  The weights are Cauchy-type, 1 / (1 + x), in place of exp(-x): + - * / only, so tests/atrous_model.py
-// reproduces every output bit.  The centre tap has w = (9/64 * D) / (D * 1) > 0, so sw > 0 in every pixel of every image.  A non-finite
-// input gives non-finite outputs in the pixels whose footprint touches it; no input is scanned.
+// reproduces every output bit.  variance_floor is a normal number, so wherever D is finite the centre tap has w = (9/64 * D) / (D * 1) > 0
+// and sw > 0 (a subnormal floor is refused: 9/64 * 5e-324 rounds to 0, and a flat image without variance would be 0 / 0 everywhere).  With
+// finite inputs and color_sigma2 * (vsum(p) + vsum(q)) + variance_floor finite for every pair, every output is finite: an overflowing d2 or
+// xg only takes that tap's w to 0.  Where D overflows, w is inf / inf and every output of the pixel is NaN.  A non-finite input gives
+// non-finite outputs in the pixels whose footprint touches it, and in no other; no input is scanned.
 //
 // Two routes, one arithmetic (atrous_pixel), the same bytes.  "images": a workgroup takes 32 x 8 adjacent pixels and every tap is read from
 // the images.  "lds": a workgroup takes 32 x 8 pixels of one LATTICE of the pass, the pixels (phx + u*step, phy + v*step): their taps lie
@@ -162,6 +165,11 @@ std::atomic<int> g_last_denoise_route{-1};  // rl_debug_last_denoise_route: 0 im
 // images route took 1.14 - 1.18 ms (profiles/denoise.json).
 bool atrous_route_lds() { return g_denoise_route != 0; }
 
+// rl_debug_set_denoise_blocks: 0 the default (the CU-derived cap of the route), else the most workgroups a pass launches, so that tests
+// put several tiles, or all of them, through one workgroup's grid-stride loop
+std::atomic<uint32_t> g_denoise_max_blocks{0};
+std::atomic<uint64_t> g_last_denoise_tiles{0}, g_last_denoise_blocks{0};  // rl_debug_last_denoise_launch: of the most recent pass; 0, 0 none yet
+
 bool atrous_number_ok(double v) { return std::isfinite(v) && v >= 0.0; }
 
 // The argument rules of both entry points, looked at before the device: RL_OK or RL_E_INVALID.
@@ -170,8 +178,9 @@ int atrous_check(uint32_t width, uint32_t height, const rl_atrous_params *p, con
   if (!p || !color || !variance || !out_color) return set_err(RL_E_INVALID, "bad argument");
   if (p->n_guides > ATROUS_MAX_GUIDES || p->reserved != 0) return set_err(RL_E_INVALID, "n_guides beyond 8, or reserved not 0");
   if (p->n_guides != 0 && !guides) return set_err(RL_E_INVALID, "bad argument");
-  if (!atrous_number_ok(p->color_sigma2) || !atrous_number_ok(p->variance_floor) || !(p->variance_floor > 0.0))
-    return set_err(RL_E_INVALID, "color_sigma2 must be finite and >= 0, variance_floor finite and > 0");
+  // a subnormal floor can leave the centre tap's 9/64 * D at 0 (5e-324 on a flat image without variance: sw = 0, every output 0 / 0)
+  if (!atrous_number_ok(p->color_sigma2) || !atrous_number_ok(p->variance_floor) || !(p->variance_floor >= std::numeric_limits<double>::min()))
+    return set_err(RL_E_INVALID, "color_sigma2 must be finite and >= 0, variance_floor finite and a normal number (>= DBL_MIN)");
   for (uint32_t k = 0; k < p->n_guides; k++)
     if (!atrous_number_ok(p->guide_inv_sigma[k])) return set_err(RL_E_INVALID, "guide_inv_sigma must be finite and >= 0");
   const void *ins[3] = {color, variance, p->n_guides ? guides : nullptr}, *outs[2] = {out_color, out_variance};
@@ -188,6 +197,10 @@ extern "C" {
 
 void rl_debug_set_denoise_route(int route) { g_denoise_route = route < 0 ? -1 : (route != 0); }
 int rl_debug_last_denoise_route(void) { return g_last_denoise_route.load(); }
+void rl_debug_set_denoise_blocks(uint32_t max_blocks) { g_denoise_max_blocks = max_blocks; }
+void rl_debug_last_denoise_launch(uint64_t out[2]) {
+  if (out) out[0] = g_last_denoise_tiles.load(), out[1] = g_last_denoise_blocks.load();
+}
 
 int rl_denoise_atrous_pass_device(uint32_t width, uint32_t height, uint32_t step, const rl_atrous_params *p, const void *d_color, const void *d_variance,
                                   const void *d_guides, void *d_out_color, void *d_out_variance, void *hip_stream) {
@@ -207,10 +220,13 @@ int rl_denoise_atrous_pass_device(uint32_t width, uint32_t height, uint32_t step
   const size_t lds = lds_route ? (size_t)ATROUS_LDS_PLANE * (6 + A.G) * sizeof(double) : 0;  // at most 48,384 bytes: no attribute to raise
   void (*kern)(const AtrousPass) = lds_route ? atrous_pass_kernel<true> : atrous_pass_kernel<false>;
   const uint64_t per_cu = lds_route ? std::min<size_t>(g_lds_max / lds, ATROUS_MAX_BLOCKS_PER_CU) : ATROUS_MAX_BLOCKS_PER_CU;
-  const uint64_t cap = (uint64_t)std::max(1, g_cus) * per_cu;
-  hipLaunchKernelGGL(kern, dim3((uint32_t)std::min(A.tiles, cap)), dim3(ATROUS_NT), lds, (hipStream_t)hip_stream, A);
+  const uint32_t max_blocks = g_denoise_max_blocks.load();
+  const uint64_t cap = max_blocks ? max_blocks : (uint64_t)std::max(1, g_cus) * per_cu;
+  const uint64_t blocks = std::min(A.tiles, cap);
+  hipLaunchKernelGGL(kern, dim3((uint32_t)blocks), dim3(ATROUS_NT), lds, (hipStream_t)hip_stream, A);
   HIP_TRY(hipGetLastError());
   g_last_denoise_route = lds_route ? 1 : 0;
+  g_last_denoise_tiles = A.tiles, g_last_denoise_blocks = blocks;
   return RL_OK;
 }
 

@@ -1,8 +1,9 @@
 """CPU tier: the a-trous denoiser (rl_denoise_atrous_pass_device, rl_denoise_atrous; include/rl_render.h "Denoising") is
 exported, declared, listed in api.RENDER_SYMBOLS and wired into the Python and C++ layers; rl_atrous_params is 88 bytes in the header's field
 order; every refusal of the header gives RL_E_INVALID whether or not a device is present; valid arguments fail LOUDLY (RL_E_NO_DEVICE, no CPU
-fallback) without a GPU; Features.guides on hand-made sums; and the numpy model (tests/atrous_model.py), the yardstick of the GPU tier,
-lowers the error of a synthetic noisy image."""
+fallback) without a GPU; Features.guides on hand-made sums; what denoise_render hands to the filter (_denoise_render_inputs) on hand-made
+Moments, Adaptive and Features; and the numpy model (tests/atrous_model.py), the yardstick of the GPU tier, lowers the error of a synthetic
+noisy image and shows why a variance_floor below DBL_MIN is refused."""
 import ctypes
 import os
 import re
@@ -16,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_denoise_atrous_pass_device": 10, "rl_denoise_atrous": 9}
 FIELDS = ["color_sigma2", "variance_floor", "n_guides", "reserved", "guide_inv_sigma"]
 W, H, G = 5, 4, 2
+DBL_MIN = float(np.finfo(np.float64).tiny)  # 2^-1022, the smallest normal number: the least variance_floor the library takes
 
 
 def _gpu_present():
@@ -97,6 +99,7 @@ def _bad_params(api):
         return p
     inf, nan = float("inf"), float("nan")
     return {"n_guides 9": make(n_guides=9), "reserved": make(reserved=1), "floor 0": make(variance_floor=0.0), "floor < 0": make(variance_floor=-1e-3),
+            "floor 5e-324": make(variance_floor=5e-324), "floor 2**-1023": make(variance_floor=2.0 ** -1023),  # subnormal: below DBL_MIN
             "floor nan": make(variance_floor=nan), "floor inf": make(variance_floor=inf), "sigma2 < 0": make(color_sigma2=-1.0),
             "sigma2 nan": make(color_sigma2=nan), "sigma2 inf": make(color_sigma2=inf), "inv < 0": make(inv=(1, -0.5)), "inv nan": make(inv=(0, nan)),
             "inv inf": make(inv=(1, inf))}
@@ -162,6 +165,8 @@ def test_denoise_without_a_device_fails_loudly(rl):
         assert call(out_variance=None) == api.RL_E_NO_DEVICE, name
         assert call(params=api.atrous_params(0), guides=None) == api.RL_E_NO_DEVICE, name
         assert call(width=0) == api.RL_E_NO_DEVICE and call(height=0) == api.RL_E_NO_DEVICE, name  # the device is looked at before the area
+        p_min = api.atrous_params(G, variance_floor=DBL_MIN)  # the smallest floor: accepted (the two subnormal ones of _bad_params are not)
+        assert p_min.variance_floor == 2.0 ** -1022 and call(params=p_min) == api.RL_E_NO_DEVICE, name
     assert calls["pass_device"](n=1 << 20) == api.RL_E_NO_DEVICE
     assert calls["host"](n=0) == api.RL_E_NO_DEVICE and calls["host"](n=12) == api.RL_E_NO_DEVICE
     assert all((o == 7).all() for o in outs)
@@ -225,3 +230,100 @@ def test_model_lowers_the_error_of_a_synthetic_noisy_image():
     one = np.array([[[0.5, 0.25, 2.0]]])
     c, v = M.atrous_pass(one, np.zeros((1, 1, 3)), None, 4.0, 1e-8, [], 1)
     assert (np.abs(c - one) <= 2.0 ** -52 * one).all() and not v.any()
+
+
+def test_model_needs_a_normal_variance_floor():
+    """Why variance_floor below DBL_MIN is refused.  On a flat image without variance D is the floor in every tap.  At 5e-324, the least
+    subnormal, (h*h) * D rounds to 0 for every tap (the largest, 9/64 * D, too), so sw = 0 and every output is 0 / 0.  At DBL_MIN every
+    (h*h) * D = k * 2^-1030 with k <= 36 is a subnormal held exactly, so w = h*h exactly and the filter is the plain B3 mean of a constant:
+    exactly the input where the products with the colour are exact (powers of two), the input within the roundings of the sum otherwise
+    (3 x 3 at step 1: at most 9 taps, 9 products + 8 additions on the longest path, then one division: 10 roundings; 1 x 1: two)."""
+    zero = np.zeros((3, 3, 3))
+    flat = np.broadcast_to(np.array([0.5, 0.25, 2.0]), (3, 3, 3)).copy()
+    for guides, inv in ((None, []), (np.ones((3, 3, 2)), [1.0, 3.0])):
+        c, v = M.atrous_pass(flat, zero, guides, 4.0, 5e-324, inv, 1)
+        assert np.isnan(c).all() and np.isnan(v).all()
+        c, v = M.atrous_pass(flat, zero, guides, 4.0, DBL_MIN, inv, 1)
+        assert c.tobytes() == flat.tobytes() and v.tobytes() == zero.tobytes()
+        odd = np.broadcast_to(np.array([0.3, 0.7, 1.1]), (3, 3, 3)).copy()
+        c, v = M.atrous_pass(odd, zero, guides, 4.0, DBL_MIN, inv, 1)
+        assert (np.abs(c - odd) <= 10 * 2.0 ** -53 * odd).all() and v.tobytes() == zero.tobytes()
+        c, v = M.atrous_pass(odd[:1, :1], zero[:1, :1], None if guides is None else guides[:1, :1], 4.0, DBL_MIN, inv, 1)
+        assert (np.abs(c - odd[:1, :1]) <= 2 * 2.0 ** -53 * odd[:1, :1]).all() and not v.any()
+    # finite variances that overflow D: inf / inf in the centre tap, as the header says
+    c, v = M.atrous_pass(flat, np.full((3, 3, 3), 4e307), None, 4.0, 1e-8, [], 1)  # vsum = 1.2e308 is finite, vsum(p) + vsum(q) is not
+    assert np.isnan(c).all() and np.isnan(v).all()
+
+
+def _hand_made(rl, counts=None):
+    """A 2 x 3 estimate and features: pixel (0, 0) has a zero albedo channel, (0, 1) an albedo above 1, (1, 2) was never hit.
+    counts None: a Moments of 4 samples; else an Adaptive with those per-pixel counts."""
+    api = rl.api
+    rng = np.random.default_rng(17)
+    n = np.full((2, 3), 4.0) if counts is None else np.asarray(counts, dtype=np.float64)
+    sums = rng.uniform(0.5, 3.0, (2, 3, 3)) * n[..., None]
+    sq = sums * sums / n[..., None] * rng.uniform(1.01, 1.5, (2, 3, 3))  # sq >= sums^2 / n, as any samples have it
+    sq[1, 1] = sums[1, 1] * sums[1, 1] / n[1, 1, None] * 0.5             # ... but for one pixel, where the difference is clipped at 0
+    albedo_sum = rng.uniform(0.4, 3.6, (2, 3, 3))
+    albedo_sum[0, 0, 1] = 0.0
+    albedo_sum[0, 1] = [6.0, 4.5, 8.0]
+    feats = api.Features(4, albedo_sum=albedo_sum, normal_sum=rng.standard_normal((2, 3, 3)), depth_sum=rng.uniform(1.0, 9.0, (2, 3)),
+                         hit_count=np.array([[4, 3, 1], [2, 4, 0]], dtype=np.uint32))
+    est = api.Moments(4, sums, sq) if counts is None else api.Adaptive(sums, sq, np.asarray(counts, dtype=np.uint32))
+    return est, feats, sums, sq, n
+
+
+@pytest.mark.parametrize("counts", [None, [[2, 5, 9], [3, 64, 7]]], ids=["moments", "adaptive"])
+def test_denoise_render_inputs_on_hand_made_objects(rl, counts):
+    """_denoise_render_inputs against the formulas written out: mean = sums / n and the variance of the mean (sq - sums^2 / n) / (n - 1) / n,
+    clipped at 0, with one n (Moments) or each pixel's own (Adaptive), both divided by the albedo and its square where the albedo is > 0."""
+    api = rl.api
+    est, feats, sums, sq, n = _hand_made(rl, counts)
+    color, variance, guides, sigmas, a = api._denoise_render_inputs(est, feats, None, api.GUIDE_KINDS)
+    albedo = feats.albedo_sum * 0.25
+    assert albedo[0, 0, 1] == 0.0 and (albedo[0, 1] > 1.0).all()
+    want_a = albedo.copy()
+    want_a[0, 0, 1] = 1.0
+    assert a.tobytes() == want_a.tobytes()
+    n3 = n[..., None]
+    mean = sums * 0.25 if counts is None else sums / n3
+    var = (sq - sums * sums / n3) / (n3 - 1.0) / n3
+    assert (var[1, 1] < 0.0).all() and (np.delete(var.reshape(6, 3), 4, axis=0) > 0.0).all()
+    var[1, 1] = 0.0
+    assert color.tobytes() == (mean / want_a).tobytes() and variance.tobytes() == (var / (want_a * want_a)).tobytes()
+    assert color[0, 0, 1] == mean[0, 0, 1] and variance[0, 0, 1] == var[0, 0, 1]  # albedo 0: mean and variance pass through
+    assert (color[0, 1] < mean[0, 1]).all() and (variance[0, 1] < var[0, 1]).all()  # albedo above 1 divides like any other
+    assert guides.tobytes() == feats.guides().tobytes() and guides.shape == (2, 3, 8)
+    D = api.DENOISE_GUIDE_SIGMA
+    assert sigmas == [D["albedo"]] * 3 + [D["normal"]] * 3 + [D["depth"], D["coverage"]]
+
+
+def test_denoise_render_inputs_guides_sigmas_and_refusals(rl):
+    api = rl.api
+    est, feats, *_ = _hand_made(rl)
+    D = api.DENOISE_GUIDE_SIGMA
+    width = {"albedo": 3, "normal": 3, "depth": 1, "coverage": 1}
+    for want in (("depth", "albedo"), ("coverage", "normal", "depth"), ("normal",), ("coverage", "depth", "normal", "albedo")):
+        _, _, guides, sigmas, _ = api._denoise_render_inputs(est, feats, None, want)
+        assert guides.tobytes() == feats.guides(want).tobytes()
+        assert len(sigmas) == guides.shape[2] == sum(width[k] for k in want)
+        assert sigmas == [D[k] for k in want for _ in range(width[k])], want
+    # an override changes exactly the entries of its kind
+    base = api._denoise_render_inputs(est, feats, None, api.GUIDE_KINDS)[3]
+    over = api._denoise_render_inputs(est, feats, {"normal": 0.03125}, api.GUIDE_KINDS)[3]
+    assert over[3:6] == [0.03125] * 3 and over[:3] == base[:3] and over[6:] == base[6:] and len(over) == 8
+    over = api._denoise_render_inputs(est, feats, {"normal": 0.03125}, ("depth", "normal"))[3]
+    assert over == [D["depth"]] + [0.03125] * 3
+    assert api.DENOISE_GUIDE_SIGMA == D and D["normal"] != 0.03125  # the defaults are not written to
+    # an Adaptive with a pixel of one sample has no variance estimate
+    one, feats1, *_ = _hand_made(rl, [[2, 5, 9], [3, 1, 7]])
+    with pytest.raises(ValueError):
+        api._denoise_render_inputs(one, feats1, None, api.GUIDE_KINDS)
+    with pytest.raises(ValueError):
+        api._denoise_render_inputs(api.Moments(1, est.sums, est.sq), feats, None, api.GUIDE_KINDS)
+    # an estimate and features of different shapes
+    wide = api.Features(4, albedo_sum=np.ones((2, 4, 3)), normal_sum=np.ones((2, 4, 3)), depth_sum=np.ones((2, 4)), hit_count=np.ones((2, 4), dtype=np.uint32))
+    with pytest.raises(ValueError):
+        api._denoise_render_inputs(est, wide, None, api.GUIDE_KINDS)
+    with pytest.raises(ValueError):
+        api.denoise_render(est, wide)

@@ -18,6 +18,7 @@ def _switches(rl):
     rl.init(0)
     yield
     rl.api.set_denoise_route(-1)
+    rl.api.set_denoise_blocks(0)
 
 
 def _same(a, b):
