@@ -47,6 +47,10 @@ struct alignas(16) CompactOp {  // 32 B: the wave kernel's LDS form of a box / g
   uint32_t w_hit, w_miss;  // successor words: state << 29 | op index
 };
 static_assert(sizeof(CompactOp) == 32, "CompactOp must be 32 B");
+// The wave scheduler's lane states (rl_rtiow_wave.h), here because the successor words above carry them.
+// ST_SHADE2 (fast traversal only): the specular half of SHADE — Metal and Dielectric hits — so that the many Lambertian / miss lanes
+// do not walk through normalize(), Schlick and refract() code they never need
+enum : uint32_t { ST_GEN = 0, ST_TRAV = 1, ST_SHADE = 2, ST_FILL = 3, ST_DONE = 4, ST_LEAF = 5, ST_SHADE2 = 6, ST_LEAF2 = 8 };
 
 // Node of the wave kernel's FAST traversal structure (rl_fast_bvh.cpp): a binary tree over the spheres built by the surface-area
 // heuristic, one 64-byte record per inner node holding BOTH children's boxes (binary32, rounded outwards) so that one step tests
@@ -220,7 +224,7 @@ struct alignas(16) DevTri {  // 160 B
 };
 static_assert(sizeof(DevTri) == 160, "DevTri must be 160 B");
 
-struct alignas(16) RtcGuard {  // 32 B: node of the reject-only binary32 box tree over one ROP_TRIS range (rl_render.hip build_rtc_guards)
+struct alignas(16) RtcGuard {  // 32 B: node of the reject-only binary32 box tree over one ROP_TRIS range (rl_scene_host.cpp build_rtc_guards)
   float box[6];   // x.min,x.max,y.min,y.max,z.min,z.max of the triangles below, padded outwards
   uint32_t skip;  // next node when this box is certainly missed (inner: hit -> next node in the array)
   uint32_t tri;   // leaf: the triangle to test; NONE for inner nodes
@@ -243,6 +247,9 @@ struct RtcProgram {
   std::vector<rl_rtc_pattern> patterns;
   uint32_t max_csg_depth = 0;
 };
+// Slots of the full kernel's stack of pending reflection / refraction rays (rl_rtc_full_kernel.h Pending): a world needs
+// max_reflection_depth + 1 of them, and build_host_rtc (rl_scene_host.cpp) refuses one that needs more
+static const uint32_t RTC_MAX_PENDING = 8;
 int compile_rtc(const rl_rtc_scene_desc &d, RtcProgram &out, std::string &err);
 
 }  // namespace rl

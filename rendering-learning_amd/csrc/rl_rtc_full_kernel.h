@@ -149,7 +149,7 @@ __device__ inline uint32_t rtc_intersect_all(const RtcFullParams &F, const DevOp
       };
       cnt.tris += mult * count;  // the reference tests every triangle of the group (group.rs has no acceleration structure)
       if (P.guards && op.skip != 0u) {
-        // reject-only box tree over the range (rl_render.hip build_rtc_guards; leaves in triangle order): a triangle is skipped only
+        // reject-only box tree over the range (rl_scene_host.cpp build_rtc_guards; leaves in triangle order): a triangle is skipped only
         // when the ray's LINE certainly misses its padded box — every intersection, of either sign of t, is still collected in order
         const RtcAux32 ax = rtc_aux32(o, d);
         uint32_t g = op.skip - 1u;
@@ -394,8 +394,7 @@ __device__ __forceinline__ bool rtc_are_equal(double a, double b) {  // math/uti
 
 // Pending reflection / refraction rays of one camera ray, walked depth-first: a ray with `remaining` bounces left pushes at most
 // two rays with remaining - 1, so max_reflection_depth + 1 slots are enough (rl_rtc_scene_create rejects deeper worlds with
-// RL_E_UNSUPPORTED; the reference recurses without a cap, world.rs:128-159).
-static const uint32_t RTC_MAX_PENDING = 8;
+// RL_E_UNSUPPORTED; the reference recurses without a cap, world.rs:128-159): RTC_MAX_PENDING (rl_program.h).
 struct Pending {
   D3 o, d;
   double w;

@@ -34,7 +34,7 @@ struct RtiowParams {
   const rl_medium *media;
   uint32_t n_ops, n_spheres;
   const DevMaterial *sphere_flat;  // wave kernel: per-sphere flattened material (see flatten_sphere_materials)
-  const DevOp *lops;  // wave kernel: ops with {code, skip} replaced by linked successor words (state << 29 | op index), see link_ops
+  const DevOp *lops;  // wave kernel: ops with {code, skip} replaced by linked successor words (state << 29 | op index), see rl_scene_host.cpp link_ops
   uint32_t entry0;    // linked word of op 0: where (and in which state) a new ray starts
   const CompactOp *cops;    // wave kernel LDS_SCENE = 3: guarded compact ops (n_ops originals + one guard per sphere)
   const uint32_t *movbits;  // ... one bit per sphere: Center::Moving

@@ -196,7 +196,7 @@
           D3 outward = (p - center) * s.inv_r;
           bool front = dot(d, outward) <= 0.0;
           D3 normal = front ? outward : -outward;
-          // one flattened record per sphere (rl_render.hip flatten_sphere_materials): the material with a Solid texture's
+          // one flattened record per sphere (rl_scene_host.cpp flatten_sphere_materials): the material with a Solid texture's
           // colour inlined, and for a Dielectric the constants 1/ior and Schlick's r0 of both orientations — one load
           // instead of the sphere -> material -> texture chain, same values bit for bit
           const DevMaterial &m = P.sphere_flat[si];
@@ -343,7 +343,7 @@
         RL_CG_MARK("STEP_B");
         if (state == ST_TRAV) {
           // one LDS round trip: the whole 64-B linked op {box, w_hit, w_miss}; every op stepped here is a box op,
-          // the successor words already carry the state the lane enters there (rl_render.hip link_ops)
+          // the successor words already carry the state the lane enters there (rl_scene_host.cpp link_ops)
           uint32_t w_hit, w_miss;
           bool certain, hitb;
           if (LDS_SCENE == 4) {  // one node = both children: reject-only binary32 tests, nearer child first, the other one pushed

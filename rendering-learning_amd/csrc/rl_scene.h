@@ -11,6 +11,7 @@
 
 #include "rl_devbuf.h"
 #include "rl_program.h"
+#include "rl_scene_host.h"  // HostRtiow, HostRtc: what the host side of a scene compiles to
 
 namespace rl {
 
@@ -19,29 +20,6 @@ struct DevCtx {
   int device = -1;        // HIP device ordinal
   hipStream_t stream = nullptr;  // library-owned stream (host-buffer entry points, multi-GPU renders)
   hipEvent_t ev = nullptr;       // "this device's shard has arrived" (peer-copy gather)
-};
-
-// What the host side of a scene compiles to; immutable, shared by the per-device replicas of one scene.
-struct HostRtiow {
-  RtiowProgram rt;
-  std::vector<DevOp> lops;  // linked ops (sphere-only scenes)
-  std::vector<DevMaterial> sphere_flat;
-  std::vector<CompactOp> cops;  // guarded compact ops
-  std::vector<uint32_t> movbits;
-  uint32_t entry0 = 0, centry0 = 0;
-  std::vector<FastNode> fast_nodes;  // fast traversal structure (rl_fast_bvh.cpp); fast_root == FAST_NONE: the scene does not qualify
-  uint32_t fast_root = FAST_NONE;
-  std::vector<float> fast_leaf_boxes;  // [n_spheres][8]: each sphere's padded leaf box of the fast tree (rl_rtiow_coop.h)
-  std::vector<double> fast_leaf_balls;  // [n_spheres][4]: centre and radius of a ball around each padded sphere (rl_fast_bvh.cpp fast_leaf_balls)
-  FastGeneral fg;  // fast traversal structure of a general scene (fg.ok == false: the scene does not qualify)
-  FastGeneral qfg;  // sphere-only scenes: the same structure for ray queries (rl_ray_query.h; the renders walk fast_nodes from LDS instead)
-  const FastGeneral &query_tree() const { return fg.ok ? fg : qfg; }
-  // the guard boxes' padding is rigorous for ray origins within guard_reach of guard_center (rl_render.hip link_ops)
-  double guard_center[3] = {0, 0, 0}, guard_reach = 0;
-};
-struct HostRtc {
-  RtcProgram rc;
-  std::vector<RtcGuard> guards;
 };
 
 }  // namespace rl

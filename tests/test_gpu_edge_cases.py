@@ -218,3 +218,35 @@ def test_coincident_spheres_resolve_ties_like_the_reference(rl, oracle, use_bvh)
     p = rl.CameraParams(aspect_ratio=2.0, image_width=96, samples_per_pixel=4, max_depth=8, vfov=50.0, lookfrom=(0, 0.3, 1), lookat=(0, 0, -3),
                         background=(0.6, 0.7, 0.9))
     _check(rl, oracle, world, p)
+
+
+def test_a_sphere_named_twice_renders_from_the_linked_ops(rl, oracle):
+    """A List whose first and last items are the SAME sphere record (the sphere in between them in the table is then in no list): the
+    guarded layouts need every sphere referenced exactly once, so the host compiler refuses guards (no compact ops, no fast tree) and
+    both the counting and the counter-free render walk the linked ops.  The reference tests the sphere once per mention."""
+    import ctypes as C
+    import torch
+    tex, mats = _materials(rl)
+    sph = np.zeros(4, dtype=rl.api.SPHERE)
+    sph["center0"] = [(0, 0, -3), (0, -100.5, -3), (1.2, 0, -3.5), (-1.2, 0.1, -3)]
+    sph["radius"] = [0.5, 100.0, 0.5, 0.6]
+    sph["material"] = [1, 0, 2, 2]
+    world = rl.World.from_spheres(sph, mats, tex, False)
+    d = rl.api.RtiowSceneDesc.from_address(world.desc)
+    assert d.n_list_items == 4
+    items = (C.c_uint32 * 8).from_address(d.list_items)  # rl_href {kind, index} x 4
+    assert [items[2 * k + 1] for k in range(4)] == [0, 1, 2, 3]
+    items[6], items[7] = items[0], items[1]  # the last item names sphere 0 again; sphere 3 is left out
+    r = (C.c_uint64 * 16)()
+    L = rl.api.render_lib()
+    L.rl_debug_host_structures.argtypes = [C.c_void_p, C.c_void_p]
+    assert L.rl_debug_host_structures(world.desc, r) == 0 and r[0] == 0  # no fast tree: guards were refused
+    p = rl.CameraParams(aspect_ratio=2.0, image_width=16, samples_per_pixel=4, max_depth=8, vfov=50.0, lookfrom=(0, 0.3, 1), lookat=(0, 0, -3),
+                        background=(0.6, 0.7, 0.9))
+    gs, gpu = _check(rl, oracle, world, p)
+    assert gpu.shape == (8, 16, 3) and gs["sphere_tests"] > 0
+    cam = rl.Camera(p)
+    buf = torch.zeros((8, 16, 3), dtype=torch.float64, device="cuda:0")
+    cam.render_device(world, buf.data_ptr(), stream=torch.cuda.current_stream().cuda_stream)
+    st = rl.api.render_status(world)
+    assert np.array_equal(buf.cpu().numpy(), gpu) and st["rays"] == gs["rays"] and st["flagged"] == 0

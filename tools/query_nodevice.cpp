@@ -3,7 +3,7 @@
 // return RL_E_NO_DEVICE before it touches a buffer or opt_stats — with valid buffers, with nothing to do (n = 0; an image whose row_first
 // equals its height) and with every pointer NULL.  Meant to be built with the host sanitizers (the library's host code and this file; no
 // Python involved):
-//   cd rendering-learning_amd/csrc && for f in rl_render.hip rl_multi.hip rl_bvh_build.hip rl_program.cpp rl_fast_bvh.cpp; do
+//   cd rendering-learning_amd/csrc && for f in rl_render.hip rl_multi.hip rl_bvh_build.hip rl_program.cpp rl_fast_bvh.cpp rl_scene_host.cpp; do
 //     hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -ffp-contract=off -Xarch_host -fsanitize=address,undefined -c -o /tmp/san_${f%.*}.o $f; done
 //   clang++ -std=c++17 -g -fsanitize=address,undefined -I../../include -c -o /tmp/san_main.o ../../tools/query_nodevice.cpp
 //   hipcc --offload-arch=gfx950 -fsanitize=address,undefined -o /tmp/query_nodevice /tmp/san_*.o -ldl && /tmp/query_nodevice
