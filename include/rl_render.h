@@ -627,7 +627,7 @@ int rl_rtiow_render_pixels_features_device(const rl_scene *, const rl_rtiow_came
  * variance_floor or guide_inv_sigma[k < n_guides]; step = 0 or step > 1 << 20; iterations > 12; an output pointer equal to an input
  * pointer or to the other output; width * height >= 0xFFFF0000.  Then, without a device, RL_E_NO_DEVICE (no CPU fallback).  Then a
  * zero-area image: RL_OK, nothing read or written.  The device form runs on the current device; the host form on the library's device 0.
- * Not offered: f32 images, temporal accumulation, a variance pre-filter, multi-GPU forms, rgb8 output. */
+ * Not offered: f32 images, temporal accumulation, a variance pre-filter, multi-GPU forms. */
 typedef struct rl_atrous_params {
   double color_sigma2;       /* >= 0: how many variances of colour difference halve a tap's weight */
   double variance_floor;     /* finite and a normal number, >= DBL_MIN: keeps D positive where both variances are 0 */
@@ -639,6 +639,78 @@ int rl_denoise_atrous_pass_device(uint32_t width, uint32_t height, uint32_t step
                                   const void *d_variance, const void *d_guides, void *d_out_color, void *d_out_variance, void *hip_stream);
 int rl_denoise_atrous(uint32_t width, uint32_t height, uint32_t iterations, const rl_atrous_params *, const double *color,
                       const double *variance, const double *guides, double *out_color, double *out_variance);
+
+/* From the renders' buffers to a denoised picture without leaving the device: prepare, the passes, finish.
+ * prepare turns sums, second moments and counts (moments / adaptive renders) and the feature sums into the colour, variance and guide
+ * images a pass reads; finish multiplies the filtered images back by the albedo and can encode the picture.  Binary64, every operation
+ * rounded on its own (no FMA), sums left to right, uint32 inputs converted exactly; sqrt is the correctly rounded one.  Per pixel p and
+ * channel c (tests/denoise_render_model.py is this statement in numpy; api.denoise_render computes the same bytes on the host):
+ *     n        = (double)counts[p]  if a counts image is given, else (double)samples
+ *     mean[c]  = sums[c] / n  with counts;  sums[c] * (1.0 / samples)  without (the reciprocal is one rounded division)
+ *     raw[c]   = (((sq[c] - (sums[c] * sums[c]) / n) / (n - 1.0)) / n)
+ *     var[c]   = raw[c] < 0 ? 0.0 : raw[c]                     -- a NaN stays NaN
+ *     alb[c]   = albedo_sum[c] * (1.0 / feature_samples)
+ *     a[c]     = alb[c] > 0 ? alb[c] : 1.0                     -- zero, negative and NaN albedo: the colour is left as it is
+ *     color[c] = mean[c] / a[c] ;  variance[c] = var[c] / (a[c] * a[c])
+ *     guides [H][W][G], in this fixed order, each group present iff its RL_GUIDE_* bit of `want` is set:
+ *       albedo (3):   alb[c]
+ *       normal (3):   l = sqrt((ns0*ns0 + ns1*ns1) + ns2*ns2) ;  l != 0 ? ns[c] / l : 0.0
+ *       depth (1):    depth_sum / (double)max(hit_count, 1)
+ *       coverage (1): (double)hit_count / (double)feature_samples
+ *   finish:  out_color[c] = color_f[c] * a[c] ;  out_variance[c] = variance_f[c] * (a[c] * a[c])   -- a recomputed from albedo_sum, not stored
+ *            out_rgb8[c]  = the byte of rl_rtiow_encode_rgb8_device(out_color, n, samples = 1)
+ * No input is scanned.  A pixel whose count is 0 or 1 gets the non-finite values the arithmetic gives (x / 0, 0 / 0); the passes spread
+ * them to the pixels whose 25-tap footprints touch it and no further (above).
+ * rl_denoise_prepare_device and rl_denoise_finish_device enqueue one elementwise kernel each on the caller's stream and return.  finish's
+ * outputs may be its inputs (d_out_color = d_color, d_out_variance = d_variance); d_variance is read iff d_out_variance is given; each of
+ * its three outputs is optional, one at least must be given.  d_guides may be NULL when want = 0.
+ * rl_denoise_render_device enqueues prepare, `iterations` passes at step 1, 2, 4, .. (rl_denoise_atrous_pass_device) and finish on the
+ * caller's stream and returns without waiting.  It owns no memory: two colour / variance pairs and the guide image are carved from d_work,
+ * rl_denoise_render_work_bytes(width, height, G) bytes, whose contents before and after the call mean nothing.  iterations = 0 runs prepare
+ * and finish only.  d_out_variance and d_out_rgb8 are optional, d_out_color too when one of the others is given; the last pass writes no
+ * variance when nobody wants one, and the colour bytes are the same.  rl_denoise_render takes host arrays in the struct and the outputs,
+ * stages them on the library's device 0 and waits.
+ * Errors.  RL_E_INVALID, before the device is looked at (so also without one), nothing written: a NULL struct; NULL sums, sq or
+ * albedo_sum; a pointer that a `want` bit needs is missing; `want` with bits beyond the four; reserved != 0; feature_samples = 0;
+ * counts = NULL with samples < 2; params->n_guides != G; whatever the params of a pass are refused for (above); iterations > 12;
+ * work_bytes too small (or a NULL d_work); no output at all; the two f64 outputs one buffer; width * height >= 0xFFFF0000.  Then,
+ * without a device, RL_E_NO_DEVICE (no CPU fallback).  Then a zero-area image: RL_OK, nothing read or written.
+ * rl_rtiow_render_denoised_rgb8 is the sibling of rl_rtiow_render_rgb8, one call from scene to picture: rl_rtiow_render_adaptive_device
+ * with opt_rule (rl_rtiow_render_moments_device when it is NULL), rl_rtiow_render_features_device with a copy of the camera whose
+ * samples_per_pixel is feature_samples, and rl_denoise_render_device, all on the library's stream (first_sample 0, the whole frame), then
+ * W*H*3 bytes copied back.  What rl_denoise_render_device refuses is refused before anything is rendered; after that the first non-OK
+ * code of a composed call is returned, and every rule of the scene, the camera and concurrency is the composed calls' own.  The two
+ * renders are asynchronous, so the call ends with rl_render_status(scene): RL_E_DEGENERATE, with the picture written, when a panic site
+ * was reached.  It takes no stats.
+ * Not offered: row shards, pixel lists and multi-GPU forms of the one-call render; f32 images. */
+#define RL_GUIDE_ALBEDO 1u   /* 3 channels */
+#define RL_GUIDE_NORMAL 2u   /* 3 channels */
+#define RL_GUIDE_DEPTH 4u    /* 1 channel  */
+#define RL_GUIDE_COVERAGE 8u /* 1 channel  */
+typedef struct rl_denoise_inputs { /* pointers: device in the _device forms, host in rl_denoise_render */
+  const void *sums;                /* [H][W][3] f64 */
+  const void *sq;                  /* [H][W][3] f64 */
+  const void *counts;              /* [H][W] u32 (adaptive) or NULL: every pixel took `samples` */
+  const void *albedo_sum;          /* [H][W][3] f64, required: the colour is divided by its mean */
+  const void *normal_sum;          /* [H][W][3] f64, needed iff want has RL_GUIDE_NORMAL */
+  const void *depth_sum;           /* [H][W] f64, needed iff want has RL_GUIDE_DEPTH */
+  const void *hit_count;           /* [H][W] u32, needed iff want has RL_GUIDE_DEPTH or RL_GUIDE_COVERAGE */
+  uint32_t samples;                /* read iff counts == NULL; then >= 2 */
+  uint32_t feature_samples;        /* >= 1: samples_per_pixel of the feature render */
+  uint32_t want;                   /* RL_GUIDE_* bits; G = 3*albedo + 3*normal + depth + coverage */
+  uint32_t reserved;               /* 0 */
+} rl_denoise_inputs;               /* 72 bytes */
+int rl_denoise_prepare_device(uint32_t width, uint32_t height, const rl_denoise_inputs *, void *d_color, void *d_variance, void *d_guides,
+                              void *hip_stream);
+int rl_denoise_finish_device(uint32_t width, uint32_t height, const void *d_color, const void *d_variance, const void *d_albedo_sum,
+                             uint32_t feature_samples, void *d_out_color, void *d_out_variance, void *d_out_rgb8, void *hip_stream);
+uint64_t rl_denoise_render_work_bytes(uint32_t width, uint32_t height, uint32_t n_guides); /* width * height * 8 * (12 + n_guides) */
+int rl_denoise_render_device(uint32_t width, uint32_t height, const rl_denoise_inputs *, uint32_t iterations, const rl_atrous_params *,
+                             void *d_work, uint64_t work_bytes, void *d_out_color, void *d_out_variance, void *d_out_rgb8, void *hip_stream);
+int rl_denoise_render(uint32_t width, uint32_t height, const rl_denoise_inputs *, uint32_t iterations, const rl_atrous_params *,
+                      double *out_color, double *out_variance, uint8_t *out_rgb8);
+int rl_rtiow_render_denoised_rgb8(const rl_scene *, const rl_rtiow_camera *, const rl_rtiow_adaptive *opt_rule, uint32_t feature_samples,
+                                  uint32_t want, uint32_t iterations, const rl_atrous_params *, uint8_t *out_rgb8);
 
 /* =====================================================================
  *  Batched ray queries: the reference's per-ray primitives on the device

@@ -6,3 +6,5 @@ mirror of the reference's scene-building API).  `api` is the ctypes plumbing use
 from . import api  # noqa: F401
 from .api import (Adaptive, AtrousParams, Camera, CameraParams, Canvas, Features, Moments, RLError, RtcWorld, World, atrous_params, canvas_ppm,  # noqa: F401
                   denoise_atrous, denoise_atrous_pass_device, denoise_render, init, output_ppm, rtc_camera)
+from .api import (DenoiseInputs, denoise_finish_device, denoise_inputs, denoise_prepare_device, denoise_render_device, denoise_render_gpu,  # noqa: F401
+                  denoise_render_work_bytes)

@@ -216,7 +216,9 @@ RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", 
                   "rl_rtiow_render_adaptive_rows", "rl_rtiow_render_adaptive_device",
                   "rl_rtiow_render_features_rows", "rl_rtiow_render_features_device", "rl_rtiow_render_pixels_features",
                   "rl_rtiow_render_pixels_features_device",
-                  "rl_denoise_atrous_pass_device", "rl_denoise_atrous"]
+                  "rl_denoise_atrous_pass_device", "rl_denoise_atrous",
+                  "rl_denoise_prepare_device", "rl_denoise_finish_device", "rl_denoise_render_work_bytes", "rl_denoise_render_device", "rl_denoise_render",
+                  "rl_rtiow_render_denoised_rgb8"]
 
 
 def _material_query_argtypes(L):
@@ -303,6 +305,27 @@ def _denoise_argtypes(L):
     L.rl_denoise_atrous.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
+class DenoiseInputs(C.Structure):  # rl_denoise_inputs: device pointers in the _device forms, host pointers in rl_denoise_render
+    _fields_ = [("sums", C.c_void_p), ("sq", C.c_void_p), ("counts", C.c_void_p), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p),
+                ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p), ("samples", C.c_uint32), ("feature_samples", C.c_uint32), ("want", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+GUIDE_BITS = {"albedo": 1, "normal": 2, "depth": 4, "coverage": 8}  # RL_GUIDE_*
+
+
+def _denoise_render_argtypes(L):
+    L.rl_denoise_prepare_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rl_denoise_finish_device.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rl_denoise_render_work_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    L.rl_denoise_render_work_bytes.restype = C.c_uint64
+    L.rl_denoise_render_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputs), C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_uint64, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rl_denoise_render.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputs), C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    L.rl_rtiow_render_denoised_rgb8.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.POINTER(RtiowAdaptive), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                C.POINTER(AtrousParams), C.c_void_p]
+
+
 def _pixel_list(xs, ys):
     """The (xs, ys) of a pixel-list render as two contiguous uint32 arrays; ValueError for what is not a list of pixel coordinates."""
     xs, ys = np.asarray(xs), np.asarray(ys)
@@ -379,6 +402,8 @@ def render_lib():
             _render_features_argtypes(L)
         if hasattr(L, "rl_denoise_atrous"):  # (likewise)
             _denoise_argtypes(L)
+        if hasattr(L, "rl_denoise_render_device"):  # (likewise)
+            _denoise_render_argtypes(L)
         L.rl_init_multi.argtypes = [C.c_int]
         L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
         L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
@@ -1284,6 +1309,23 @@ class Camera:
         _check(render_lib().rl_rtiow_render_rgb8(world.device(), C.byref(self.c), 0, out.ctypes.data, None), allow_degenerate=True)
         return out
 
+    def render_denoised_rgb8(self, world: World, feature_samples, rule=None, iterations=5, color_sigma=None, guide_sigma=None, variance_floor=None,
+                             want=GUIDE_KINDS, params: AtrousParams = None) -> np.ndarray:
+        """rl_rtiow_render_denoised_rgb8, one call from scene to picture: render_moments (rule=None) or render_adaptive (rule = an
+        RtiowAdaptive or its (min_samples, check_every, abs_variance, rel_variance)), render_features at `feature_samples` samples and
+        denoise_render_device composed on the library's stream -> the [H, W, 3] bytes.  Sigmas and defaults are denoise_render's."""
+        bits = guide_bits(want)
+        if params is None:
+            kinds = [k for k in GUIDE_KINDS if bits & GUIDE_BITS[k]]
+            params = atrous_params(guide_channels(bits), DENOISE_COLOR_SIGMA if color_sigma is None else color_sigma, _guide_sigmas(guide_sigma, kinds),
+                                   DENOISE_VARIANCE_FLOOR if variance_floor is None else variance_floor)
+        if rule is not None and not isinstance(rule, RtiowAdaptive):
+            rule = RtiowAdaptive(*rule)
+        out = np.empty((self.c.image_height, self.c.image_width, 3), dtype=np.uint8)
+        _check(render_lib().rl_rtiow_render_denoised_rgb8(world.device(), C.byref(self.c), None if rule is None else C.byref(rule), int(feature_samples), bits,
+                                                          int(iterations), C.byref(params), out.ctypes.data), allow_degenerate=True)
+        return out
+
     def render_from_checkpoint(self, world: World, checkpoint: Canvas) -> Canvas:  # camera.rs:136-143
         data = self._render(checkpoint.samples, world)
         return Canvas(self.params.samples_per_pixel, self.c.image_width, self.c.image_height, data).merge(checkpoint)
@@ -1630,6 +1672,115 @@ def denoise_render(estimate, features: Features, iterations=5, color_sigma=DENOI
     color, variance, guides, per_channel, a = _denoise_render_inputs(estimate, features, guide_sigma, want)
     color, variance = denoise_atrous(color, variance, guides, iterations, color_sigma, per_channel, variance_floor)
     return color * a, variance * (a * a)
+
+
+# ---- denoise_render on the device (include/rl_render.h rl_denoise_prepare_device .. rl_rtiow_render_denoised_rgb8): what
+# _denoise_render_inputs and denoise_render's last line compute in numpy, as two kernels around the passes — the same bytes
+def guide_bits(want) -> int:
+    """The RL_GUIDE_* bits of `want`: the bits themselves, or kinds of GUIDE_KINDS, which must come in GUIDE_KINDS' order (the order of the
+    guide image's channels is fixed on the device; Features.guides takes any)."""
+    if isinstance(want, (int, np.integer)):
+        return int(want)
+    want = tuple(want)
+    for k in want:
+        if k not in GUIDE_BITS:
+            raise ValueError(f"want holds {k!r}; the guides are {GUIDE_KINDS}")
+    if want != tuple(k for k in GUIDE_KINDS if k in want):
+        raise ValueError(f"want must hold each of {GUIDE_KINDS} at most once and in that order, got {want}")
+    return sum(GUIDE_BITS[k] for k in want)
+
+
+def guide_channels(want) -> int:
+    bits = guide_bits(want)
+    return 3 * bool(bits & 1) + 3 * bool(bits & 2) + bool(bits & 4) + bool(bits & 8)
+
+
+def denoise_inputs(estimate, features: Features = None, want=GUIDE_KINDS, *, samples=0, feature_samples=0) -> DenoiseInputs:
+    """The rl_denoise_inputs of a call.  estimate: a Moments or Adaptive beside a Features (host arrays, for rl_denoise_render; the struct
+    keeps them alive), or a dict of pointers {"sums", "sq", "albedo_sum"[, "counts", "normal_sum", "depth_sum", "hit_count"]} (0 / absent =
+    NULL) with samples= (read where there are no counts) and feature_samples=."""
+    bits = guide_bits(want)
+    if isinstance(estimate, dict):
+        unknown = set(estimate) - {f[0] for f in DenoiseInputs._fields_[:7]}
+        if unknown:
+            raise ValueError(f"not a pointer of rl_denoise_inputs: {sorted(unknown)}")
+        return DenoiseInputs(**{k: (int(v) or None) for k, v in estimate.items()}, samples=int(samples), feature_samples=int(feature_samples), want=bits)
+    f64 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+    u32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.uint32)
+    keep = {"sums": f64(estimate.sums), "sq": f64(estimate.sq), "counts": u32(estimate.counts) if isinstance(estimate, Adaptive) else None,
+            "albedo_sum": f64(features.albedo_sum), "normal_sum": f64(features.normal_sum), "depth_sum": f64(features.depth_sum),
+            "hit_count": u32(features.hit_count)}
+    d = DenoiseInputs(**{k: (None if a is None else a.ctypes.data) for k, a in keep.items()}, samples=0 if isinstance(estimate, Adaptive) else int(estimate.samples),
+                      feature_samples=int(features.samples), want=bits)
+    d._keep = keep
+    return d
+
+
+def denoise_prepare_device(width, height, inputs: DenoiseInputs, d_color, d_variance, d_guides=0, stream=0):
+    """rl_denoise_prepare_device: one kernel on `stream`, from the renders' device buffers to the colour, variance ([H, W, 3] f64 each) and
+    guide image ([H, W, G] f64) a pass reads.  Asynchronous."""
+    _check(render_lib().rl_denoise_prepare_device(int(width), int(height), C.byref(inputs), C.c_void_p(d_color or None), C.c_void_p(d_variance or None),
+                                                  C.c_void_p(d_guides or None), C.c_void_p(stream)))
+
+
+def denoise_finish_device(width, height, d_color, d_variance, d_albedo_sum, feature_samples, d_out_color=0, d_out_variance=0, d_out_rgb8=0, stream=0):
+    """rl_denoise_finish_device: one kernel on `stream`: the filtered images times the albedo (and its square), and / or the picture's
+    bytes; 0 = not wanted.  The outputs may be the inputs.  Asynchronous."""
+    _check(render_lib().rl_denoise_finish_device(int(width), int(height), C.c_void_p(d_color or None), C.c_void_p(d_variance or None), C.c_void_p(d_albedo_sum or None),
+                                                 int(feature_samples), C.c_void_p(d_out_color or None), C.c_void_p(d_out_variance or None),
+                                                 C.c_void_p(d_out_rgb8 or None), C.c_void_p(stream)))
+
+
+def denoise_render_work_bytes(width, height, n_guides) -> int:
+    """rl_denoise_render_work_bytes: the size of denoise_render_device's work buffer, width * height * 8 * (12 + n_guides)."""
+    return int(render_lib().rl_denoise_render_work_bytes(int(width), int(height), int(n_guides)))
+
+
+def denoise_render_device(width, height, inputs: DenoiseInputs, iterations, params: AtrousParams, d_work, work_bytes, d_out_color=0, d_out_variance=0,
+                          d_out_rgb8=0, stream=0):
+    """rl_denoise_render_device: prepare, `iterations` passes (step 1, 2, 4, ..) and finish enqueued on `stream` over device buffers; the
+    images in between live in d_work (denoise_render_work_bytes).  0 = output not wanted.  Asynchronous."""
+    _check(render_lib().rl_denoise_render_device(int(width), int(height), C.byref(inputs), int(iterations), C.byref(params), C.c_void_p(d_work or None),
+                                                 int(work_bytes), C.c_void_p(d_out_color or None), C.c_void_p(d_out_variance or None), C.c_void_p(d_out_rgb8 or None),
+                                                 C.c_void_p(stream)))
+
+
+def _guide_sigmas(guide_sigma, want):
+    sig = dict(DENOISE_GUIDE_SIGMA, **(guide_sigma or {}))
+    return [s for k in want for s in [sig[k]] * (3 if k in ("albedo", "normal") else 1)]
+
+
+def denoise_render_gpu(estimate, features: Features, iterations=5, color_sigma=DENOISE_COLOR_SIGMA, guide_sigma=None, variance_floor=DENOISE_VARIANCE_FLOOR,
+                       want=GUIDE_KINDS, rgb8=False):
+    """denoise_render with what it does in numpy around the passes done on the device too (rl_denoise_render): the same arguments,
+    defaults, ValueErrors and bytes -> (color, variance), and with rgb8=True (color, variance, [H, W, 3] uint8 picture).  `want` must be
+    in GUIDE_KINDS' order."""
+    want = tuple(want)
+    if not want:
+        raise ValueError("no guide asked for")
+    bits = guide_bits(want)
+    if isinstance(estimate, Adaptive):
+        if (estimate.counts < 2).any():
+            raise ValueError("variance_of_mean needs at least 2 samples in every pixel")
+    elif estimate.samples < 2:
+        raise ValueError(f"variance_of_mean needs at least 2 samples, got {estimate.samples}")
+    shape = estimate.sums.shape
+    needed = {"albedo_sum": shape, "normal_sum": shape if bits & 2 else None, "depth_sum": shape[:2] if bits & 4 else None,
+              "hit_count": shape[:2] if bits & 12 else None}
+    if len(shape) != 3 or shape[2] != 3 or estimate.sq.shape != shape or (isinstance(estimate, Adaptive) and estimate.counts.shape != shape[:2]):
+        raise ValueError(f"the estimate's sums must be [H, W, 3] beside sq and counts of that frame (got {shape})")
+    for k, s in needed.items():
+        a = getattr(features, k)
+        if s is not None and (a is None or a.shape != s):
+            raise ValueError(f"the estimate is {shape}, the features' {k} {None if a is None else a.shape}")
+    H, W = shape[:2]
+    d = denoise_inputs(estimate, features, bits)
+    p = atrous_params(guide_channels(bits), color_sigma, _guide_sigmas(guide_sigma, want), variance_floor)
+    color, variance = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.float64)
+    picture = np.empty(shape, dtype=np.uint8) if rgb8 else None
+    _check(render_lib().rl_denoise_render(W, H, C.byref(d), int(iterations), C.byref(p), color.ctypes.data, variance.ctypes.data,
+                                          None if picture is None else picture.ctypes.data))
+    return (color, variance, picture) if rgb8 else (color, variance)
 
 
 def _take_string(ptr, n):

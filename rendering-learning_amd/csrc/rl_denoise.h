@@ -172,17 +172,23 @@ std::atomic<uint64_t> g_last_denoise_tiles{0}, g_last_denoise_blocks{0};  // rl_
 
 bool atrous_number_ok(double v) { return std::isfinite(v) && v >= 0.0; }
 
-// The argument rules of both entry points, looked at before the device: RL_OK or RL_E_INVALID.
-int atrous_check(uint32_t width, uint32_t height, const rl_atrous_params *p, const void *color, const void *variance, const void *guides, const void *out_color,
-                 const void *out_variance) {
-  if (!p || !color || !variance || !out_color) return set_err(RL_E_INVALID, "bad argument");
+// What the struct itself must satisfy (also asked by rl_denoise_render*, rl_denoise_render.h): RL_OK or RL_E_INVALID.
+int atrous_params_check(const rl_atrous_params *p) {
   if (p->n_guides > ATROUS_MAX_GUIDES || p->reserved != 0) return set_err(RL_E_INVALID, "n_guides beyond 8, or reserved not 0");
-  if (p->n_guides != 0 && !guides) return set_err(RL_E_INVALID, "bad argument");
   // a subnormal floor can leave the centre tap's 9/64 * D at 0 (5e-324 on a flat image without variance: sw = 0, every output 0 / 0)
   if (!atrous_number_ok(p->color_sigma2) || !atrous_number_ok(p->variance_floor) || !(p->variance_floor >= std::numeric_limits<double>::min()))
     return set_err(RL_E_INVALID, "color_sigma2 must be finite and >= 0, variance_floor finite and a normal number (>= DBL_MIN)");
   for (uint32_t k = 0; k < p->n_guides; k++)
     if (!atrous_number_ok(p->guide_inv_sigma[k])) return set_err(RL_E_INVALID, "guide_inv_sigma must be finite and >= 0");
+  return RL_OK;
+}
+
+// The argument rules of both entry points, looked at before the device: RL_OK or RL_E_INVALID.
+int atrous_check(uint32_t width, uint32_t height, const rl_atrous_params *p, const void *color, const void *variance, const void *guides, const void *out_color,
+                 const void *out_variance) {
+  if (!p || !color || !variance || !out_color) return set_err(RL_E_INVALID, "bad argument");
+  if (int rc = atrous_params_check(p); rc != RL_OK) return rc;
+  if (p->n_guides != 0 && !guides) return set_err(RL_E_INVALID, "bad argument");
   const void *ins[3] = {color, variance, p->n_guides ? guides : nullptr}, *outs[2] = {out_color, out_variance};
   for (const void *o : outs)
     for (const void *i : ins)

@@ -135,14 +135,18 @@ __global__ void iota_u32(uint32_t *out, uint32_t n) {
 }
 
 // Output stages
-__global__ void encode_rtiow_rgb8(const double *sum, unsigned long long n_vals, double inv_samples, unsigned char *out) {
-  unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_vals) return;
-  double v = sum[i] * inv_samples;                                                 // camera.rs:293
+// one channel's byte; also what denoise_finish_kernel (rl_denoise_render.h) writes, with inv_samples = 1
+__device__ inline unsigned char rtiow_rgb8_of(double sum, double inv_samples) {
+  double v = sum * inv_samples;                                                    // camera.rs:293
   double s = v <= 0.0031308 ? 12.92 * v : (1.0 + 0.055) * pow(v, 1.0 / 2.4) - 0.055;  // color.rs:130-136
   double f = floor(s * 255.999);                                                   // color.rs:47-50 (as i16 saturates; NaN -> 0)
   int q = isnan(f) ? 0 : (f >= 32767.0 ? 32767 : (f <= -32768.0 ? -32768 : (int)f));
-  out[i] = (unsigned char)(q < 0 ? 0 : (q > 255 ? 255 : q));
+  return (unsigned char)(q < 0 ? 0 : (q > 255 ? 255 : q));
+}
+__global__ void encode_rtiow_rgb8(const double *sum, unsigned long long n_vals, double inv_samples, unsigned char *out) {
+  unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_vals) return;
+  out[i] = rtiow_rgb8_of(sum[i], inv_samples);
 }
 __global__ void encode_rtc_rgb8(const double *rgb, unsigned long long n_vals, unsigned char *out) {
   unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1431,3 +1435,4 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 #include "rl_query_api.h"
 #include "rl_features_api.h"
 #include "rl_denoise.h"
+#include "rl_denoise_render.h"

@@ -642,6 +642,29 @@ int rlh_denoise_atrous_probe(uint64_t width, uint64_t height, uint32_t iteration
     return -1;
   }
 }
+// rtiow::denoise_render through the C++ mirror: sums, sq, albedo_sum, normal_sum and the two outputs = width * height * 3 doubles, depth_sum
+// width * height doubles, counts (null: a Moments of `samples`; else an Adaptive) and hit_count width * height uint32; the feature arrays
+// `want` does not need may be null.  0 or -1 (rlh_last_error).
+int rlh_denoise_render_probe(uint64_t width, uint64_t height, uint32_t iterations, const rl_atrous_params *params, const double *sums, const double *sq,
+                             const uint32_t *counts, uint64_t samples, const double *albedo_sum, const double *normal_sum, const double *depth_sum,
+                             const uint32_t *hit_count, uint64_t feature_samples, uint32_t want, double *out_color, double *out_variance) {
+  try {
+    const size_t n = (size_t)width * height;
+    auto f64 = [](const double *p, size_t k) { return p ? std::vector<double>(p, p + k) : std::vector<double>(); };
+    auto u32 = [](const uint32_t *p, size_t k) { return p ? std::vector<uint32_t>(p, p + k) : std::vector<uint32_t>(); };
+    const rtiow::Camera::Features f{(size_t)feature_samples, f64(albedo_sum, n * 3), f64(normal_sum, n * 3), f64(depth_sum, n), u32(hit_count, n)};
+    rtiow::Denoised d = counts ? rtiow::denoise_render((size_t)width, (size_t)height, rtiow::Camera::Adaptive{f64(sums, n * 3), f64(sq, n * 3), u32(counts, n)}, f,
+                                                       want, iterations, *params)
+                               : rtiow::denoise_render((size_t)width, (size_t)height, rtiow::Camera::Moments{(size_t)samples, f64(sums, n * 3), f64(sq, n * 3)}, f,
+                                                       want, iterations, *params);
+    std::memcpy(out_color, d.color.data(), d.color.size() * sizeof(double));
+    std::memcpy(out_variance, d.variance.data(), d.variance.size() * sizeof(double));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // RTC shading queries through the C++ mirror on the mirror scene.  which = 0: rtc::World::prepare, a = n rl_ray, out = n rl_rtc_comps;
 // which = 1: rtc::World::shade, a = n rl_rtc_comps, out = n rl_rtc_shade; which = 2: rtc::World::shadow_attenuation, a = n points,
 // b = n light positions (3 doubles each), out = n doubles; which = 3: rtc::World::lighting, a = n rl_rtc_comps, b = n light positions,

@@ -119,6 +119,31 @@ Denoised denoise_atrous(size_t width, size_t height, uint32_t iterations, const 
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_denoise_atrous: ") + rl_last_error());
   return d;
 }
+static Denoised denoise_render_impl(size_t width, size_t height, const std::vector<double> &sums, const std::vector<double> &sq, const std::vector<uint32_t> *counts,
+                                    size_t samples, const Camera::Features &f, uint32_t want, uint32_t iterations, const rl_atrous_params &params) {
+  const size_t n = width * height;
+  const bool normal = want & RL_GUIDE_NORMAL, depth = want & RL_GUIDE_DEPTH, hits = want & (RL_GUIDE_DEPTH | RL_GUIDE_COVERAGE);
+  if (width > UINT32_MAX || height > UINT32_MAX || samples > UINT32_MAX || f.samples > UINT32_MAX || sums.size() != n * 3 || sq.size() != n * 3 ||
+      (counts && counts->size() != n) || f.albedo_sum.size() != n * 3 || (normal && f.normal_sum.size() != n * 3) || (depth && f.depth_sum.size() != n) ||
+      (hits && f.hit_count.size() != n))
+    throw std::runtime_error("denoise_render: size mismatch");
+  rl_denoise_inputs in{};
+  in.sums = sums.data(), in.sq = sq.data(), in.counts = counts ? counts->data() : nullptr, in.albedo_sum = f.albedo_sum.data();
+  in.normal_sum = normal ? f.normal_sum.data() : nullptr, in.depth_sum = depth ? f.depth_sum.data() : nullptr, in.hit_count = hits ? f.hit_count.data() : nullptr;
+  in.samples = (uint32_t)samples, in.feature_samples = (uint32_t)f.samples, in.want = want;
+  Denoised d{std::vector<double>(n * 3), std::vector<double>(n * 3)};
+  int rc = rl_denoise_render((uint32_t)width, (uint32_t)height, &in, iterations, &params, d.color.data(), d.variance.data(), nullptr);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_denoise_render: ") + rl_last_error());
+  return d;
+}
+Denoised denoise_render(size_t width, size_t height, const Camera::Moments &estimate, const Camera::Features &features, uint32_t want, uint32_t iterations,
+                        const rl_atrous_params &params) {
+  return denoise_render_impl(width, height, estimate.sums, estimate.sq, nullptr, estimate.samples, features, want, iterations, params);
+}
+Denoised denoise_render(size_t width, size_t height, const Camera::Adaptive &estimate, const Camera::Features &features, uint32_t want, uint32_t iterations,
+                        const rl_atrous_params &params) {
+  return denoise_render_impl(width, height, estimate.sums, estimate.sq, &estimate.counts, 0, features, want, iterations, params);
+}
 Canvas Camera::render_independent(const Hittable &world) const { return render_independent_impl(*this, world, nullptr); }
 Canvas Camera::render_independent_from_checkpoint(const Hittable &world, const Canvas &checkpoint) const {
   return render_independent_impl(*this, world, &checkpoint);

@@ -841,6 +841,13 @@ struct Denoised {
 };
 Denoised denoise_atrous(size_t width, size_t height, uint32_t iterations, const rl_atrous_params &params, const std::vector<double> &color,
                         const std::vector<double> &variance, const std::vector<double> &guides = {});
+// A moments or adaptive render denoised with the guides of a feature render of the same camera (rl_denoise_render): mean and variance of
+// the mean divided by the albedo, filtered with the guides `want` asks for (RL_GUIDE_* bits; params.n_guides is their channel count), and
+// multiplied back, all on the device.  Features' arrays that `want` does not need may be empty.  Throws what the library refuses.
+Denoised denoise_render(size_t width, size_t height, const Camera::Moments &estimate, const Camera::Features &features, uint32_t want, uint32_t iterations,
+                        const rl_atrous_params &params);
+Denoised denoise_render(size_t width, size_t height, const Camera::Adaptive &estimate, const Camera::Features &features, uint32_t want, uint32_t iterations,
+                        const rl_atrous_params &params);
 
 // ---------------------------------------------------------------- color.rs / output.rs
 namespace srgb {  // color.rs:114-136
