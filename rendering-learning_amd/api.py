@@ -141,6 +141,209 @@ class RtcSceneDesc(C.Structure):
                 ("patterns", C.c_void_p), ("n_patterns", C.c_uint32)]
 
 
+class RtiowAdaptive(C.Structure):  # rl_rtiow_adaptive
+    _fields_ = [("min_samples", C.c_uint32), ("check_every", C.c_uint32), ("abs_variance", C.c_double), ("rel_variance", C.c_double)]
+
+
+class RtiowFeatures(C.Structure):  # rl_rtiow_features: each pointer optional (None), all None is refused
+    _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p)]
+
+
+FEATURE_OUTPUTS = ("albedo_sum", "normal_sum", "depth_sum", "hit_count")
+
+
+class AtrousParams(C.Structure):  # rl_atrous_params
+    _fields_ = [("color_sigma2", C.c_double), ("variance_floor", C.c_double), ("n_guides", C.c_uint32), ("reserved", C.c_uint32),
+                ("guide_inv_sigma", C.c_double * 8)]
+
+
+class DenoiseInputs(C.Structure):  # rl_denoise_inputs: device pointers in the _device forms, host pointers in rl_denoise_render
+    _fields_ = [("sums", C.c_void_p), ("sq", C.c_void_p), ("counts", C.c_void_p), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p),
+                ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p), ("samples", C.c_uint32), ("feature_samples", C.c_uint32), ("want", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+GUIDE_BITS = {"albedo": 1, "normal": 2, "depth": 4, "coverage": 8}  # RL_GUIDE_*
+
+
+# ----------------------------------------------------------------------------- signatures
+# One table per library, name -> (restype, argtypes), applied once when the library is loaded (_load): the only statement of a C
+# signature on the Python side.  tests/test_binding_signatures.py compares both tables with the C text: include/rl_render.h, the
+# rl_debug_* definitions under csrc/ (no header declares them) and the rlh_* definitions in host/*.cpp.  A new entry point costs one line
+# here.  restype: None = void; a function that returns a pointer MUST say c_void_p / c_char_p (the default, c_int, would cut it to 32 bits).
+_P, _S, _I, _U, _U32, _U64, _D = C.c_void_p, C.c_char_p, C.c_int, C.c_uint, C.c_uint32, C.c_uint64, C.c_double
+_PU32, _PU64 = C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+_CAM, _RTC_CAM, _STATS = C.POINTER(RtiowCamera), C.POINTER(RtcCamera), C.POINTER(Stats)
+_ADAPTIVE, _FEATURES, _ATROUS, _DENOISE_IN = C.POINTER(RtiowAdaptive), C.POINTER(RtiowFeatures), C.POINTER(AtrousParams), C.POINTER(DenoiseInputs)
+
+RENDER_SIGNATURES = {
+    # ---- include/rl_render.h, in its order of topics
+    "rl_init": (_I, [_I]),
+    "rl_init_multi": (_I, [_I]),
+    "rl_device_count": (_I, []),
+    "rl_shutdown": (None, []),
+    "rl_last_error": (_S, []),
+    "rl_abi_version": (_I, []),
+    "rl_device_info": (_I, [_S, _I]),
+    "rl_rtiow_render_progress": (_I, [_P, _PU64, _PU64, _PU32]),
+    "rl_scene_destroy": (None, [_P]),
+    "rl_render_status": (_I, [_P, _STATS]),
+    "rl_rtiow_scene_create": (_P, [_P]),
+    "rl_bvh_build": (_I, [_P, _P, _U32, _U32, _P, _U32, _P]),
+    "rl_rtiow_render": (_I, [_P, _CAM, _U64, _P, _STATS]),
+    "rl_rtiow_render_rows": (_I, [_P, _CAM, _U64, _U32, _U32, _P, _STATS]),
+    "rl_rtiow_render_device": (_I, [_P, _CAM, _U64, _U32, _U32, _P, _P, _STATS]),
+    "rl_rtiow_render_independent_rows": (_I, [_P, _CAM, _U64, _U32, _U32, _U32, _P, _STATS]),
+    "rl_rtiow_render_independent_device": (_I, [_P, _CAM, _U64, _U32, _U32, _U32, _P, _P, _STATS]),
+    "rl_rtiow_render_multi": (_I, [_P, _CAM, _U64, _P, _STATS]),
+    "rl_rtiow_render_multi_device": (_I, [_P, _CAM, _U64, _P, _STATS]),
+    "rl_rtiow_encode_rgb8_device": (_I, [_P, _U64, _U32, _P, _P]),
+    "rl_rtiow_render_rgb8": (_I, [_P, _CAM, _U64, _P, _STATS]),
+    "rl_rtc_scene_create": (_P, [_P]),
+    "rl_rtc_render": (_I, [_P, _RTC_CAM, _U32, _P, _STATS]),
+    "rl_rtc_render_rows": (_I, [_P, _RTC_CAM, _U32, _U32, _U32, _P, _STATS]),
+    "rl_rtc_render_device": (_I, [_P, _RTC_CAM, _U32, _U32, _U32, _P, _P, _STATS]),
+    "rl_rtc_render_multi": (_I, [_P, _RTC_CAM, _U32, _P, _STATS]),
+    "rl_rtc_render_multi_device": (_I, [_P, _RTC_CAM, _U32, _P, _STATS]),
+    "rl_rtc_encode_rgb8_device": (_I, [_P, _U64, _P, _P]),
+    "rl_rtc_render_rgb8": (_I, [_P, _RTC_CAM, _U32, _P, _STATS]),
+    "rl_rtiow_hit_rays": (_I, [_P, _P, _U64, _D, _D, _P, _STATS]),
+    "rl_rtiow_hit_rays_device": (_I, [_P, _P, _U64, _D, _D, _P, _P, _STATS]),
+    "rl_rtc_intersect_rays": (_I, [_P, _P, _U64, _U32, _P, _P, _P, _STATS]),
+    "rl_rtc_intersect_rays_device": (_I, [_P, _P, _U64, _U32, _P, _P, _P, _P, _STATS]),
+    "rl_rtc_color_at_rays": (_I, [_P, _P, _U64, _P, _STATS]),
+    "rl_rtc_color_at_rays_device": (_I, [_P, _P, _U64, _P, _P, _STATS]),
+    "rl_rtiow_camera_rays": (_I, [_CAM, _U64, _P, _P, _P, _P, _P]),
+    "rl_rtiow_camera_rays_device": (_I, [_CAM, _U64, _P, _P, _P, _P, _P, _P]),
+    "rl_rtiow_ray_color_rays": (_I, [_P, _P, _P, _U64, _U64, _U32, C.POINTER(_D), _P, _P, _P, _STATS]),
+    "rl_rtiow_ray_color_rays_device": (_I, [_P, _P, _P, _U64, _U64, _U32, C.POINTER(_D), _P, _P, _P, _P, _STATS]),
+    "rl_rtiow_scatter_rays": (_I, [_P, _P, _P, _P, _U64, _U64, _P, _P, _STATS]),
+    "rl_rtiow_scatter_rays_device": (_I, [_P, _P, _P, _P, _U64, _U64, _P, _P, _P, _STATS]),
+    "rl_rtiow_texture_values": (_I, [_P, _P, _P, _P, _U64, _P]),
+    "rl_rtiow_texture_values_device": (_I, [_P, _P, _P, _P, _U64, _P, _P]),
+    "rl_rtiow_hit_rays_seeded": (_I, [_P, _P, _P, _U64, _U64, _D, _D, _P, _P, _STATS]),
+    "rl_rtiow_hit_rays_seeded_device": (_I, [_P, _P, _P, _U64, _U64, _D, _D, _P, _P, _P, _STATS]),
+    "rl_rtc_prepare_rays": (_I, [_P, _P, _U64, _P, _STATS]),
+    "rl_rtc_prepare_rays_device": (_I, [_P, _P, _U64, _P, _P, _STATS]),
+    "rl_rtc_shade_hits": (_I, [_P, _P, _U64, _P, _P, _STATS]),
+    "rl_rtc_shade_hits_device": (_I, [_P, _P, _U64, _P, _P, _P, _STATS]),
+    "rl_rtc_shadow_attenuation": (_I, [_P, _P, _P, _U64, _P, _STATS]),
+    "rl_rtc_shadow_attenuation_device": (_I, [_P, _P, _P, _U64, _P, _P, _STATS]),
+    "rl_rtc_lighting": (_I, [_P, _P, _P, _P, _P, _U64, _P]),
+    "rl_rtc_lighting_device": (_I, [_P, _P, _P, _P, _P, _U64, _P, _P]),
+    "rl_rtiow_render_pixels": (_I, [_P, _CAM, _U64, _P, _P, _U64, _P, _STATS]),
+    "rl_rtiow_render_pixels_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _P, _P, _STATS]),
+    "rl_rtc_render_pixels": (_I, [_P, _RTC_CAM, _U32, _P, _P, _U64, _P, _STATS]),
+    "rl_rtc_render_pixels_device": (_I, [_P, _RTC_CAM, _U32, _P, _P, _U64, _P, _P, _STATS]),
+    "rl_rtiow_render_moments_rows": (_I, [_P, _CAM, _U64, _U32, _U32, _P, _P, _STATS]),
+    "rl_rtiow_render_moments_device": (_I, [_P, _CAM, _U64, _U32, _U32, _P, _P, _P, _STATS]),
+    "rl_rtiow_render_pixels_moments": (_I, [_P, _CAM, _U64, _P, _P, _U64, _P, _P, _STATS]),
+    "rl_rtiow_render_pixels_moments_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _P, _P, _P, _STATS]),
+    "rl_rtiow_render_adaptive_rows": (_I, [_P, _CAM, _U64, _U32, _U32, _ADAPTIVE, _P, _P, _P, _STATS]),
+    "rl_rtiow_render_adaptive_device": (_I, [_P, _CAM, _U64, _U32, _U32, _ADAPTIVE, _P, _P, _P, _P, _STATS]),
+    "rl_rtiow_render_features_rows": (_I, [_P, _CAM, _U64, _U32, _U32, _FEATURES, _STATS]),
+    "rl_rtiow_render_features_device": (_I, [_P, _CAM, _U64, _U32, _U32, _FEATURES, _P, _STATS]),
+    "rl_rtiow_render_pixels_features": (_I, [_P, _CAM, _U64, _P, _P, _U64, _FEATURES, _STATS]),
+    "rl_rtiow_render_pixels_features_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _FEATURES, _P, _STATS]),
+    "rl_denoise_atrous_pass_device": (_I, [_U32, _U32, _U32, _ATROUS, _P, _P, _P, _P, _P, _P]),
+    "rl_denoise_atrous": (_I, [_U32, _U32, _U32, _ATROUS, _P, _P, _P, _P, _P]),
+    "rl_denoise_prepare_device": (_I, [_U32, _U32, _DENOISE_IN, _P, _P, _P, _P]),
+    "rl_denoise_finish_device": (_I, [_U32, _U32, _P, _P, _P, _U32, _P, _P, _P, _P]),
+    "rl_denoise_render_work_bytes": (_U64, [_U32, _U32, _U32]),
+    "rl_denoise_render_device": (_I, [_U32, _U32, _DENOISE_IN, _U32, _ATROUS, _P, _U64, _P, _P, _P, _P]),
+    "rl_denoise_render": (_I, [_U32, _U32, _DENOISE_IN, _U32, _ATROUS, _P, _P, _P]),
+    "rl_rtiow_render_denoised_rgb8": (_I, [_P, _CAM, _ADAPTIVE, _U32, _U32, _U32, _ATROUS, _P]),
+    # ---- the rl_debug_* entry points of csrc/ (switches and read-outs for tests and tools)
+    "rl_debug_init_multi_emulated": (_I, [_I]),
+    "rl_debug_rccl_loadable": (_I, []),
+    "rl_debug_multi_uses_rccl": (_I, []),
+    "rl_debug_host_structures": (_I, [_P, _P]),
+    "rl_debug_set_rtiow_variant": (None, [_I]),
+    "rl_debug_set_lpt": (None, [_I]),
+    "rl_debug_set_coop": (None, [_I]),
+    "rl_debug_set_coop_pixels_max": (None, [_U64]),
+    "rl_debug_set_steal": (None, [_D]),
+    "rl_debug_set_fast_traversal": (None, [_I]),
+    "rl_debug_set_rtc_blocks": (None, [_I]),
+    "rl_debug_set_indep_cap": (None, [_U64]),
+    "rl_debug_set_indep_k": (None, [_U]),
+    "rl_debug_set_pixel_entry": (None, [_I]),
+    "rl_debug_set_pixel_entry_sphere": (None, [_I]),
+    "rl_debug_pixel_entry_read": (_I, [_P, _P, _U64]),
+    "rl_debug_fast_tree": (_I, [_P, _P, _U32, _PU32]),
+    "rl_debug_set_fastg_one_wave": (None, [_I]),
+    "rl_debug_set_status_gap": (_I, [_U, _U]),
+    "rl_debug_fast_stats": (None, [_I]),
+    "rl_debug_fastg_verify": (_I, [_P, _P]),
+    "rl_debug_fastg_counts": (_I, [_P]),
+    "rl_debug_slow_traces": (_U64, []),
+    "rl_debug_live_buffers": (None, [_P]),
+    "rl_debug_sched": (_I, [_P, _P]),
+    "rl_debug_pixel_rays": (_I, [_P, _U64]),
+    "rl_debug_pixel_rays_read": (_I, [_P, _P, _U64]),
+    "rl_debug_last_query": (_I, [_P]),
+    "rl_debug_set_query_pass_cap": (None, [_U64]),
+    "rl_debug_material_query_lanes": (_U64, []),
+    "rl_debug_features_lanes": (_U64, []),
+    "rl_debug_set_denoise_route": (None, [_I]),
+    "rl_debug_last_denoise_route": (_I, []),
+    "rl_debug_set_denoise_blocks": (None, [_U32]),
+    "rl_debug_last_denoise_launch": (None, [_P]),
+}
+# every symbol include/rl_render.h declares (checked by tests/test_abi.py)
+RENDER_SYMBOLS = [n for n in RENDER_SIGNATURES if not n.startswith("rl_debug_")]
+
+_HPARAMS = C.POINTER(_HCameraParams)
+HOST_SIGNATURES = {  # the rlh_* entry points this file calls; test-only probes are declared by the tests that use them
+    "rlh_last_error": (_S, []),
+    "rlh_free": (None, [_P]),
+    "rlh_rtiow_golden_test_scene": (_P, []),
+    "rlh_rtiow_bouncing_spheres": (_P, [_U64]),
+    "rlh_rtiow_cow_scene": (_P, [_S, _U64, _P, _U32, _U32]),
+    "rlh_rtiow_perlin_scene": (_P, [_I]),
+    "rlh_rtiow_earth_scene": (_P, [_P, _U32, _U32]),
+    "rlh_rtiow_example_scene": (_P, [_S, _S, _U64, _P, _U32, _U32]),
+    "rlh_rtiow_stress_scene": (_P, [_I, _I, _S, _U64, _P, _U32, _U32, _U64, _I]),
+    "rlh_rtiow_from_spheres": (_P, [_P, _U32, _P, _U32, _P, _U32, _I]),
+    "rlh_rtiow_desc": (_P, [_P]),
+    "rlh_rtiow_free": (None, [_P]),
+    "rlh_rtiow_counts": (None, [_P, _P]),
+    "rlh_rtiow_get_params": (None, [_P, _HPARAMS]),
+    "rlh_rtiow_camera_new": (_I, [_HPARAMS, _CAM]),
+    "rlh_rtiow_output_ppm": (_P, [_P, _U64, _U64, _U64, _PU64]),
+    "rlh_canvas_to_bincode": (_P, [_U64, _U64, _U64, _P, _U64, _PU64]),
+    "rlh_canvas_from_bincode": (_I, [_S, _U64, _PU64, _PU64, _PU64, _PU64]),
+    "rlh_builder_new": (_P, []),
+    "rlh_builder_free": (None, [_P]),
+    "rlh_b_solid": (_I, [_P, _P]),
+    "rlh_b_checker": (_I, [_P, _D, _I, _I]),
+    "rlh_b_image": (_I, [_P, _P, _U32, _U32]),
+    "rlh_b_noise": (_I, [_P, _D, _U64]),
+    "rlh_b_material": (_I, [_P, _U32, _I, _P, _D, _D]),
+    "rlh_b_sphere": (_I, [_P, _P, _P, _D, _I]),
+    "rlh_b_planar": (_I, [_P, _U32, _P, _P, _P, _I]),
+    "rlh_b_triangle": (_I, [_P, _P, _P, _P, _I]),
+    "rlh_b_translate": (_I, [_P, _I, _P]),
+    "rlh_b_medium": (_I, [_P, _I, _D, _I]),
+    "rlh_b_transform": (_I, [_P, _I, _I, _D]),
+    "rlh_b_group": (_I, [_P, _P, _U32, _I]),
+    "rlh_b_obj": (_I, [_P, _S, _U64, _I]),
+    "rlh_b_finish": (_P, [_P, _I]),
+    "rlh_rtc_test_obj_scene": (_P, [_S, _U64, _U64, _U64]),
+    "rlh_rtc_named_scene": (_P, [_I, _U64, _U64]),
+    "rlh_rtc_desc": (_P, [_P]),
+    "rlh_rtc_get_camera": (None, [_P, _RTC_CAM]),
+    "rlh_rtc_free": (None, [_P]),
+    "rlh_rtc_camera_new": (_I, [_U64, _U64, _D, _P, _P, _P, _RTC_CAM]),
+    "rlh_rtc_camera_from_matrix": (_I, [_U64, _U64, _D, _P, _RTC_CAM]),
+    "rlh_rtc_make_transformed": (_I, [_P, _P]),
+    "rlh_rtc_rotation": (None, [_I, _D, _P]),
+    "rlh_rtc_matmul": (None, [_P, _P, _P]),
+    "rlh_rtc_invert": (_I, [_P, _P]),
+    "rlh_rtc_canvas_ppm": (_P, [_P, _U64, _U64, _PU64]),
+}
+
+
 # ----------------------------------------------------------------------------- library loading
 _host = None
 _render = None
@@ -161,171 +364,6 @@ def _one_hip_runtime():
         pass
 
 
-def host_lib():
-    global _host
-    if _host is None:
-        _one_hip_runtime()  # librl_host.so links librl_render.so
-        if not os.path.exists(HOST_LIB):
-            raise RuntimeError(f"{HOST_LIB} not built — run `python -c 'import __graft_entry__ as g; g.build()'`")
-        L = C.CDLL(HOST_LIB)
-        L.rlh_last_error.restype = C.c_char_p
-        for n in ("rlh_rtiow_golden_test_scene", "rlh_rtiow_bouncing_spheres", "rlh_rtiow_cow_scene", "rlh_rtiow_from_spheres",
-                  "rlh_rtiow_desc", "rlh_rtc_test_obj_scene", "rlh_rtc_desc", "rlh_rtiow_output_ppm", "rlh_rtc_canvas_ppm"):
-            getattr(L, n).restype = C.c_void_p
-        L.rlh_rtiow_bouncing_spheres.argtypes = [C.c_uint64]
-        L.rlh_rtiow_cow_scene.argtypes = [C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32]
-        L.rlh_rtiow_from_spheres.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_int]
-        L.rlh_rtiow_desc.argtypes = [C.c_void_p]
-        L.rlh_rtiow_free.argtypes = [C.c_void_p]
-        L.rlh_rtiow_get_params.argtypes = [C.c_void_p, C.POINTER(_HCameraParams)]
-        L.rlh_rtiow_camera_new.argtypes = [C.POINTER(_HCameraParams), C.POINTER(RtiowCamera)]
-        L.rlh_rtiow_output_ppm.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
-        L.rlh_free.argtypes = [C.c_void_p]
-        L.rlh_rtc_test_obj_scene.argtypes = [C.c_char_p, C.c_uint64, C.c_uint64, C.c_uint64]
-        L.rlh_rtc_desc.argtypes = [C.c_void_p]
-        L.rlh_rtc_get_camera.argtypes = [C.c_void_p, C.POINTER(RtcCamera)]
-        L.rlh_rtc_free.argtypes = [C.c_void_p]
-        L.rlh_rtc_camera_new.argtypes = [C.c_uint64, C.c_uint64, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(RtcCamera)]
-        L.rlh_rtc_camera_from_matrix.argtypes = [C.c_uint64, C.c_uint64, C.c_double, C.c_void_p, C.POINTER(RtcCamera)]
-        L.rlh_rtc_make_transformed.argtypes = [C.c_void_p, C.c_void_p]
-        L.rlh_rtc_rotation.argtypes = [C.c_int, C.c_double, C.c_void_p]
-        L.rlh_rtc_matmul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rlh_rtc_invert.argtypes = [C.c_void_p, C.c_void_p]
-        L.rlh_rtc_canvas_ppm.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
-        _host = L
-    return _host
-
-
-# every symbol include/rl_render.h declares (checked by tests/test_abi.py)
-RENDER_SYMBOLS = ["rl_init", "rl_init_multi", "rl_device_count", "rl_shutdown", "rl_last_error", "rl_abi_version", "rl_device_info", "rl_rtiow_render_progress",
-                  "rl_scene_destroy", "rl_render_status",
-                  "rl_rtiow_scene_create", "rl_bvh_build", "rl_rtiow_render", "rl_rtiow_render_rows", "rl_rtiow_render_device",
-                  "rl_rtiow_render_independent_rows", "rl_rtiow_render_independent_device",
-                  "rl_rtiow_render_multi", "rl_rtiow_render_multi_device", "rl_rtiow_encode_rgb8_device", "rl_rtiow_render_rgb8",
-                  "rl_rtc_scene_create", "rl_rtc_render", "rl_rtc_render_rows", "rl_rtc_render_device",
-                  "rl_rtc_render_multi", "rl_rtc_render_multi_device", "rl_rtc_encode_rgb8_device", "rl_rtc_render_rgb8",
-                  "rl_rtiow_hit_rays", "rl_rtiow_hit_rays_device", "rl_rtc_intersect_rays", "rl_rtc_intersect_rays_device",
-                  "rl_rtc_color_at_rays", "rl_rtc_color_at_rays_device",
-                  "rl_rtiow_camera_rays", "rl_rtiow_camera_rays_device", "rl_rtiow_ray_color_rays", "rl_rtiow_ray_color_rays_device",
-                  "rl_rtiow_scatter_rays", "rl_rtiow_scatter_rays_device", "rl_rtiow_texture_values", "rl_rtiow_texture_values_device",
-                  "rl_rtiow_hit_rays_seeded", "rl_rtiow_hit_rays_seeded_device",
-                  "rl_rtc_prepare_rays", "rl_rtc_prepare_rays_device", "rl_rtc_shade_hits", "rl_rtc_shade_hits_device",
-                  "rl_rtc_shadow_attenuation", "rl_rtc_shadow_attenuation_device", "rl_rtc_lighting", "rl_rtc_lighting_device",
-                  "rl_rtiow_render_pixels", "rl_rtiow_render_pixels_device", "rl_rtc_render_pixels", "rl_rtc_render_pixels_device",
-                  "rl_rtiow_render_moments_rows", "rl_rtiow_render_moments_device", "rl_rtiow_render_pixels_moments", "rl_rtiow_render_pixels_moments_device",
-                  "rl_rtiow_render_adaptive_rows", "rl_rtiow_render_adaptive_device",
-                  "rl_rtiow_render_features_rows", "rl_rtiow_render_features_device", "rl_rtiow_render_pixels_features",
-                  "rl_rtiow_render_pixels_features_device",
-                  "rl_denoise_atrous_pass_device", "rl_denoise_atrous",
-                  "rl_denoise_prepare_device", "rl_denoise_finish_device", "rl_denoise_render_work_bytes", "rl_denoise_render_device", "rl_denoise_render",
-                  "rl_rtiow_render_denoised_rgb8"]
-
-
-def _material_query_argtypes(L):
-    L.rl_rtiow_scatter_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtiow_scatter_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
-                                               C.POINTER(Stats)]
-    L.rl_rtiow_texture_values.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    L.rl_rtiow_texture_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-
-
-def _seeded_hit_query_argtypes(L):
-    L.rl_rtiow_hit_rays_seeded.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                           C.POINTER(Stats)]
-    L.rl_rtiow_hit_rays_seeded_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.POINTER(Stats)]
-
-
-def _rtc_shade_query_argtypes(L):
-    L.rl_rtc_prepare_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtc_prepare_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtc_shade_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtc_shade_hits_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtc_shadow_attenuation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtc_shadow_attenuation_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtc_lighting.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
-    L.rl_rtc_lighting_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-
-
-def _render_pixels_argtypes(L):
-    L.rl_rtiow_render_pixels.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtiow_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                                C.POINTER(Stats)]
-    L.rl_rtc_render_pixels.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtc_render_pixels_device.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                              C.POINTER(Stats)]
-
-
-def _render_moments_argtypes(L):
-    L.rl_rtiow_render_moments_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtiow_render_moments_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                 C.POINTER(Stats)]
-    L.rl_rtiow_render_pixels_moments.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                                 C.POINTER(Stats)]
-    L.rl_rtiow_render_pixels_moments_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
-                                                        C.c_void_p, C.POINTER(Stats)]
-
-
-class RtiowAdaptive(C.Structure):  # rl_rtiow_adaptive
-    _fields_ = [("min_samples", C.c_uint32), ("check_every", C.c_uint32), ("abs_variance", C.c_double), ("rel_variance", C.c_double)]
-
-
-def _render_adaptive_argtypes(L):
-    L.rl_rtiow_render_adaptive_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowAdaptive), C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-    L.rl_rtiow_render_adaptive_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowAdaptive), C.c_void_p,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-
-
-class RtiowFeatures(C.Structure):  # rl_rtiow_features: each pointer optional (None), all None is refused
-    _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p)]
-
-
-FEATURE_OUTPUTS = ("albedo_sum", "normal_sum", "depth_sum", "hit_count")
-
-
-def _render_features_argtypes(L):
-    L.rl_rtiow_render_features_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowFeatures), C.POINTER(Stats)]
-    L.rl_rtiow_render_features_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(RtiowFeatures), C.c_void_p,
-                                                  C.POINTER(Stats)]
-    L.rl_rtiow_render_pixels_features.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(RtiowFeatures),
-                                                  C.POINTER(Stats)]
-    L.rl_rtiow_render_pixels_features_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64,
-                                                         C.POINTER(RtiowFeatures), C.c_void_p, C.POINTER(Stats)]
-
-
-class AtrousParams(C.Structure):  # rl_atrous_params
-    _fields_ = [("color_sigma2", C.c_double), ("variance_floor", C.c_double), ("n_guides", C.c_uint32), ("reserved", C.c_uint32),
-                ("guide_inv_sigma", C.c_double * 8)]
-
-
-def _denoise_argtypes(L):
-    L.rl_denoise_atrous_pass_device.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p]
-    L.rl_denoise_atrous.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-
-
-class DenoiseInputs(C.Structure):  # rl_denoise_inputs: device pointers in the _device forms, host pointers in rl_denoise_render
-    _fields_ = [("sums", C.c_void_p), ("sq", C.c_void_p), ("counts", C.c_void_p), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p),
-                ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p), ("samples", C.c_uint32), ("feature_samples", C.c_uint32), ("want", C.c_uint32),
-                ("reserved", C.c_uint32)]
-
-
-GUIDE_BITS = {"albedo": 1, "normal": 2, "depth": 4, "coverage": 8}  # RL_GUIDE_*
-
-
-def _denoise_render_argtypes(L):
-    L.rl_denoise_prepare_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputs), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rl_denoise_finish_device.argtypes = [C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rl_denoise_render_work_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
-    L.rl_denoise_render_work_bytes.restype = C.c_uint64
-    L.rl_denoise_render_device.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputs), C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_uint64, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rl_denoise_render.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(DenoiseInputs), C.c_uint32, C.POINTER(AtrousParams), C.c_void_p, C.c_void_p, C.c_void_p]
-    L.rl_rtiow_render_denoised_rgb8.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.POINTER(RtiowAdaptive), C.c_uint32, C.c_uint32, C.c_uint32,
-                                                C.POINTER(AtrousParams), C.c_void_p]
-
-
 def _pixel_list(xs, ys):
     """The (xs, ys) of a pixel-list render as two contiguous uint32 arrays; ValueError for what is not a list of pixel coordinates."""
     xs, ys = np.asarray(xs), np.asarray(ys)
@@ -342,75 +380,32 @@ def _pixel_list(xs, ys):
     return np.ascontiguousarray(xs, dtype=np.uint32), np.ascontiguousarray(ys, dtype=np.uint32)
 
 
+def _load(path, signatures, hint):
+    """CDLL(path) with every signature of its table applied: the one place that assigns restype / argtypes.  A symbol the library lacks
+    is skipped — RL_RENDER_LIB may select an older build of the ABI for an A/B run — and calling it then fails loudly (AttributeError)."""
+    _one_hip_runtime()  # (librl_host.so links librl_render.so)
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not built — {hint}run `python -c 'import __graft_entry__ as g; g.build()'`")
+    L = C.CDLL(path)
+    for name, (restype, argtypes) in signatures.items():
+        if hasattr(L, name):
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
+    return L
+
+
+def host_lib():
+    global _host
+    if _host is None:
+        _host = _load(HOST_LIB, HOST_SIGNATURES, "")
+    return _host
+
+
 def render_lib():
     """The HIP product library. Fails loudly when it is not built."""
     global _render
     if _render is None:
-        _one_hip_runtime()
-        if not os.path.exists(RENDER_LIB):
-            raise RuntimeError(f"{RENDER_LIB} not built — the HIP extension is required (no CPU fallback); "
-                               "run `python -c 'import __graft_entry__ as g; g.build()'`")
-        L = C.CDLL(RENDER_LIB)
-        L.rl_last_error.restype = C.c_char_p
-        L.rl_init.argtypes = [C.c_int]
-        L.rl_device_info.argtypes = [C.c_char_p, C.c_int]
-        L.rl_scene_destroy.argtypes = [C.c_void_p]
-        L.rl_rtiow_scene_create.restype = C.c_void_p
-        L.rl_rtiow_scene_create.argtypes = [C.c_void_p]
-        L.rl_rtc_scene_create.restype = C.c_void_p
-        L.rl_rtc_scene_create.argtypes = [C.c_void_p]
-        L.rl_rtiow_render.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_render_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_render_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_render_independent_rows.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
-                                                       C.POINTER(Stats)]
-        L.rl_rtiow_render_independent_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
-                                                         C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_render_rgb8.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_encode_rgb8_device.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]
-        L.rl_rtc_render_rgb8.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_encode_rgb8_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        L.rl_rtc_render.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_render_rows.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_render_device.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_hit_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_hit_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_intersect_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_intersect_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                   C.POINTER(Stats)]
-        L.rl_rtc_color_at_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_color_at_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_camera_rays.argtypes = [C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rl_rtiow_camera_rays_device.argtypes = [C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.rl_rtiow_ray_color_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
-                                              C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_ray_color_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.POINTER(C.c_double), C.c_void_p,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Stats)]
-        if hasattr(L, "rl_rtiow_scatter_rays"):  # (absent from an older library selected with RL_RENDER_LIB for an A/B run: calling them then fails loudly)
-            _material_query_argtypes(L)
-        if hasattr(L, "rl_rtc_prepare_rays"):  # (likewise)
-            _rtc_shade_query_argtypes(L)
-        if hasattr(L, "rl_rtiow_hit_rays_seeded"):  # (likewise)
-            _seeded_hit_query_argtypes(L)
-        if hasattr(L, "rl_rtiow_render_pixels"):  # (likewise)
-            _render_pixels_argtypes(L)
-        if hasattr(L, "rl_rtiow_render_moments_rows"):  # (likewise)
-            _render_moments_argtypes(L)
-        if hasattr(L, "rl_rtiow_render_adaptive_rows"):  # (likewise)
-            _render_adaptive_argtypes(L)
-        if hasattr(L, "rl_rtiow_render_features_rows"):  # (likewise)
-            _render_features_argtypes(L)
-        if hasattr(L, "rl_denoise_atrous"):  # (likewise)
-            _denoise_argtypes(L)
-        if hasattr(L, "rl_denoise_render_device"):  # (likewise)
-            _denoise_render_argtypes(L)
-        L.rl_init_multi.argtypes = [C.c_int]
-        L.rl_render_status.argtypes = [C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_render_multi.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtiow_render_multi_device.argtypes = [C.c_void_p, C.POINTER(RtiowCamera), C.c_uint64, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_render_multi.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        L.rl_rtc_render_multi_device.argtypes = [C.c_void_p, C.POINTER(RtcCamera), C.c_uint32, C.c_void_p, C.POINTER(Stats)]
-        _render = L
+        _render = _load(RENDER_LIB, RENDER_SIGNATURES, "the HIP extension is required (no CPU fallback); ")
     return _render
 
 
@@ -431,33 +426,29 @@ def init_multi(n_devices=0, emulate=0):
     current GPU.  Scenes must be (re)created afterwards so that every context holds a replica."""
     global _inited
     L = render_lib()
-    if emulate:
-        L.rl_debug_init_multi_emulated.argtypes = [C.c_int]
-        rc = L.rl_debug_init_multi_emulated(int(emulate))
-    else:
-        rc = L.rl_init_multi(int(n_devices))
+    rc = L.rl_debug_init_multi_emulated(int(emulate)) if emulate else L.rl_init_multi(int(n_devices))
     if rc != RL_OK:
         raise RLError(rc, L.rl_last_error().decode())
     _inited = True
     return L.rl_device_count()
 
 
+def _ensure_init():
+    if not _inited:
+        init()
+
+
 def render_status(world, allow_degenerate=False):
     """rl_render_status: waits for the scene's last asynchronous render; {'rays', 'flagged', 'rc'}."""
     st = Stats()
-    rc = render_lib().rl_render_status(world.device(), C.byref(st))
-    _check(rc, allow_degenerate)
-    L = render_lib()
-    L.rl_debug_slow_traces.restype = C.c_uint64
-    return {"rays": st.rays, "flagged": st.flagged, "rc": rc, "slow_traces": L.rl_debug_slow_traces()}
+    rc = _check(render_lib().rl_render_status(world.device(), C.byref(st)), allow_degenerate)
+    return {"rays": st.rays, "flagged": st.flagged, "rc": rc, "slow_traces": render_lib().rl_debug_slow_traces()}
 
 
 def render_progress(world):
     """rl_rtiow_render_progress: (pixel slots claimed so far in the running launch, slots of that launch, phase) — does not wait for the render."""
-    L = render_lib()
     a, b, ph = C.c_uint64(), C.c_uint64(), C.c_uint32()
-    L.rl_rtiow_render_progress.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-    _check(L.rl_rtiow_render_progress(world.device(), C.byref(a), C.byref(b), C.byref(ph)))
+    _check(render_lib().rl_rtiow_render_progress(world.device(), C.byref(a), C.byref(b), C.byref(ph)))
     return a.value, b.value, ph.value
 
 
@@ -479,61 +470,45 @@ def set_lpt(on):
 
 def set_coop_pixels_max(n):
     """Tests / tools: the longest pixel list (render_pixels) of a sphere scene the cooperative kernel takes; 0 = the default, 160 per CU."""
-    L = render_lib()
-    L.rl_debug_set_coop_pixels_max.argtypes = [C.c_uint64]
-    L.rl_debug_set_coop_pixels_max(int(n))
+    render_lib().rl_debug_set_coop_pixels_max(int(n))
 
 
 def set_steal(max_fill):
     """Tests / tools: work stealing on small shards (at most max_fill x as many pixels as the GPU has lanes; 0 switches it off)."""
-    L = render_lib()
-    L.rl_debug_set_steal.argtypes = [C.c_double]
-    L.rl_debug_set_steal(float(max_fill))
+    render_lib().rl_debug_set_steal(float(max_fill))
 
 
 def set_indep_cap(nbytes):
     """Tests / tools: cap of the sample-parallel mode's pass buffer in bytes (0: the default 1 GiB); a small cap forces several passes."""
-    L = render_lib()
-    L.rl_debug_set_indep_cap.argtypes = [C.c_ulonglong]
-    L.rl_debug_set_indep_cap(int(nbytes))
+    render_lib().rl_debug_set_indep_cap(int(nbytes))
 
 
 def set_indep_k(k):
     """Tests / tools: samples of one pixel per claim in the sample-parallel mode (default 1)."""
-    L = render_lib()
-    L.rl_debug_set_indep_k.argtypes = [C.c_uint]
-    L.rl_debug_set_indep_k(int(k))
+    render_lib().rl_debug_set_indep_k(int(k))
 
 
 def set_fastg_one_wave(mode):
     """Tests / tools: the fast general kernel's one-wave-per-SIMD form: -1 by frame size (default), 0 never, 1 always (where it applies)."""
-    L = render_lib()
-    L.rl_debug_set_fastg_one_wave.argtypes = [C.c_int]
-    L.rl_debug_set_fastg_one_wave(int(mode))
+    render_lib().rl_debug_set_fastg_one_wave(int(mode))
 
 
 def set_pixel_entry(max_entries):
     """Tests / tools: the fast sphere kernel's camera rays start at their pixel's entry cut of up to max_entries (1 .. 3) entries of the
     fast tree; 0: at the root, as scattered rays do (csrc/rl_pixel_entry.h; the same switch as RL_PIXEL_ENTRY)."""
-    L = render_lib()
-    L.rl_debug_set_pixel_entry.argtypes = [C.c_int]
-    L.rl_debug_set_pixel_entry(int(max_entries))
+    render_lib().rl_debug_set_pixel_entry(int(max_entries))
 
 
 def set_pixel_entry_sphere(on):
     """Tests / tools: the entry cut keeps only the leaves whose SPHERE the pixel's beam may touch (default); off: every leaf whose padded box
     it touches, the box-only cut (csrc/rl_pixel_entry.h; the same switch as RL_PIXEL_ENTRY_SPHERE)."""
-    L = render_lib()
-    L.rl_debug_set_pixel_entry_sphere.argtypes = [C.c_int]
-    L.rl_debug_set_pixel_entry_sphere(int(bool(on)))
+    render_lib().rl_debug_set_pixel_entry_sphere(int(bool(on)))
 
 
 def pixel_entry_table(world, n_pixels):
     """Tests: the entry words of the scene's most recent fast-traversal render (finished), one uint32 per pixel of the rows it rendered."""
-    L = render_lib()
-    L.rl_debug_pixel_entry_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
     out = np.zeros(int(n_pixels), dtype=np.uint32)
-    _check(L.rl_debug_pixel_entry_read(world.device(), out.ctypes.data_as(C.c_void_p), int(n_pixels)))
+    _check(render_lib().rl_debug_pixel_entry_read(world.device(), out.ctypes.data_as(C.c_void_p), int(n_pixels)))
     return out
 
 
@@ -541,8 +516,6 @@ def fast_tree(world):
     """Tests: the fast traversal tree of a sphere scene as (children [n_inner, 2] entry ids, root entry); entry e < n_inner is an inner
     node, e >= n_inner the sphere e - n_inner.  None when the scene has no fast structure."""
     L = render_lib()
-    L.rl_debug_fast_tree.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
-    L.rl_debug_fast_tree.restype = C.c_int
     root = C.c_uint32()
     n = L.rl_debug_fast_tree(world.device(), None, 0, C.byref(root))
     if n < 0:
@@ -555,21 +528,15 @@ def fast_tree(world):
 def set_status_gap(device_us, host_us=0):
     """Tests only: a wait of device_us on the render's stream before each asynchronous status copy, and a host sleep of host_us
     between a multi-GPU frame and its status post (each capped at 20 ms; 0, 0: off, the default)."""
-    if not _inited:
-        init()
-    L = render_lib()
-    L.rl_debug_set_status_gap.argtypes = [C.c_uint, C.c_uint]
-    _check(L.rl_debug_set_status_gap(int(device_us), int(host_us)))
+    _ensure_init()
+    _check(render_lib().rl_debug_set_status_gap(int(device_us), int(host_us)))
 
 
 def live_buffers():
     """Tests: (count, bytes) of the device allocations the library owns right now (rl_debug_live_buffers): scenes' buffers and work
     buffers; the staging of a host-buffer call is gone again when the call returns."""
     out = (C.c_ulonglong * 2)()
-    L = render_lib()
-    L.rl_debug_live_buffers.argtypes = [C.c_void_p]
-    L.rl_debug_live_buffers.restype = None
-    L.rl_debug_live_buffers(out)
+    render_lib().rl_debug_live_buffers(out)
     return int(out[0]), int(out[1])
 
 
@@ -577,6 +544,19 @@ def _check(rc, allow_degenerate=False):
     if rc == RL_OK or (allow_degenerate and rc == RL_E_DEGENERATE):
         return rc
     raise RLError(rc, render_lib().rl_last_error().decode())
+
+
+def _call(fn, *args, stats=None, counting=False, allow_degenerate=False):
+    """The one tail of every wrapper over an entry point whose last parameter is `rl_stats *opt_stats`: fn(*args, opt_stats), checked,
+    the counters and "rc" put into `stats` where the caller gave a dict.  opt_stats is what routes the call inside the library: NULL
+    takes the counter-free kernels (and, in the device forms, returns without waiting); non-NULL the counting, reference-order ones.
+    It is NULL unless the caller gave a dict — or the wrapper is `counting`: one that has always counted, dict or not."""
+    st = Stats() if counting or stats is not None else None
+    rc = _check(fn(*args, None if st is None else C.byref(st)), allow_degenerate)
+    if stats is not None:
+        stats.update(st.as_dict())
+        stats["rc"] = rc
+    return rc
 
 
 def pack_rays(origins, dirs, times=None):
@@ -623,19 +603,14 @@ def _cursors_arg(cursors, n):
 
 def set_query_pass_cap(rays):
     """rl_debug_set_query_pass_cap: rays per pass of ray_color_rays* (0: what the 32-bit work counter allows); tests force several passes."""
-    L = render_lib()
-    L.rl_debug_set_query_pass_cap.argtypes = [C.c_uint64]
-    L.rl_debug_set_query_pass_cap.restype = None
-    L.rl_debug_set_query_pass_cap(int(rays))
+    render_lib().rl_debug_set_query_pass_cap(int(rays))
 
 
 def last_query():
     """rl_debug_last_query: which kernel served the most recent hit_rays* / ray_color_rays* call ("fast" / "reference") or render_features* call
     ("features_fast" / "features_reference") and, for a synchronous call, how many of its rays the fast walk re-traced in the reference's order."""
     out = (C.c_uint64 * 2)()
-    L = render_lib()
-    L.rl_debug_last_query.argtypes = [C.c_void_p]
-    _check(L.rl_debug_last_query(out))
+    _check(render_lib().rl_debug_last_query(out))
     return {"kernel": {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast"}.get(int(out[0]), "none"), "retraced": int(out[1])}
 
 
@@ -653,38 +628,26 @@ def last_denoise_route():
 def set_denoise_blocks(max_blocks):
     """rl_debug_set_denoise_blocks: the most workgroups a denoising pass launches; 0: the default, the CU-derived cap of the route.  With
     fewer workgroups than tiles a workgroup takes several tiles in turn; tests force that on tiny images."""
-    L = render_lib()
-    L.rl_debug_set_denoise_blocks.argtypes = [C.c_uint32]
-    L.rl_debug_set_denoise_blocks.restype = None
-    L.rl_debug_set_denoise_blocks(int(max_blocks))
+    render_lib().rl_debug_set_denoise_blocks(int(max_blocks))
 
 
 def last_denoise_launch():
     """rl_debug_last_denoise_launch: {"tiles", "blocks"} of the most recent denoising pass: its tiles and the workgroups that shared them."""
     out = (C.c_uint64 * 2)()
-    L = render_lib()
-    L.rl_debug_last_denoise_launch.argtypes = [C.c_void_p]
-    L.rl_debug_last_denoise_launch.restype = None
-    L.rl_debug_last_denoise_launch(out)
+    render_lib().rl_debug_last_denoise_launch(out)
     return {"tiles": int(out[0]), "blocks": int(out[1])}
 
 
 def material_query_max_lanes():
     """rl_debug_material_query_lanes: the most lanes one scatter_rays* / texture_values* launch has on the current device (the grid cap,
     csrc/rl_material_query.h MATERIAL_QUERY_MAX_BLOCKS_PER_CU workgroups per CU); a larger batch puts several elements through one lane."""
-    L = render_lib()
-    L.rl_debug_material_query_lanes.restype = C.c_uint64
-    L.rl_debug_material_query_lanes.argtypes = []
-    return int(L.rl_debug_material_query_lanes())
+    return int(render_lib().rl_debug_material_query_lanes())
 
 
 def features_max_lanes():
     """rl_debug_features_lanes: the most lanes one render_features* launch has on the current device; a frame or list with more pixels puts
     several pixels through one lane."""
-    L = render_lib()
-    L.rl_debug_features_lanes.restype = C.c_uint64
-    L.rl_debug_features_lanes.argtypes = []
-    return int(L.rl_debug_features_lanes())
+    return int(render_lib().rl_debug_features_lanes())
 
 
 def _records_arg(a, dtype, n, what):
@@ -692,13 +655,6 @@ def _records_arg(a, dtype, n, what):
     if r.dtype != dtype or r.ndim != 1 or (n is not None and r.shape[0] != n):
         raise ValueError(f"{what} must be [{'n' if n is None else n}] {what.upper()} records; got shape {r.shape}, dtype {r.dtype}")
     return r
-
-
-def _finish_query(rc, st, stats, allow_degenerate):
-    _check(rc, allow_degenerate)
-    if stats is not None:
-        stats.update(st.as_dict())
-        stats["rc"] = rc
 
 
 def rows_for(height, row_first, row_step):
@@ -750,9 +706,7 @@ class World:
     def counts(self):
         """Element counts of the flattened scene (rl_rtiow_scene_desc)."""
         out = (C.c_uint32 * 9)()
-        L = host_lib()
-        L.rlh_rtiow_counts.argtypes = [C.c_void_p, C.c_void_p]
-        L.rlh_rtiow_counts(self._h, out)
+        host_lib().rlh_rtiow_counts(self._h, out)
         return dict(zip(("spheres", "planars", "media", "translates", "transforms", "lists", "bvh_nodes", "materials", "textures"), list(out)))
 
     def _table(self, field, dtype):
@@ -798,48 +752,37 @@ class World:
 
     @staticmethod
     def perlin_spheres():  # examples/perlin_spheres.rs
-        L = host_lib()
-        L.rlh_rtiow_perlin_scene.restype, L.rlh_rtiow_perlin_scene.argtypes = C.c_void_p, [C.c_int]
-        return World(L.rlh_rtiow_perlin_scene(0))
+        return World(host_lib().rlh_rtiow_perlin_scene(0))
 
     @staticmethod
     def simple_light():  # examples/simple_light.rs
-        L = host_lib()
-        L.rlh_rtiow_perlin_scene.restype, L.rlh_rtiow_perlin_scene.argtypes = C.c_void_p, [C.c_int]
-        return World(L.rlh_rtiow_perlin_scene(1))
+        return World(host_lib().rlh_rtiow_perlin_scene(1))
 
     @staticmethod
     def earth_scene(rgb8: np.ndarray):  # examples/earth.rs with the caller's image (sRGB8, [H, W, 3])
-        L = host_lib()
-        L.rlh_rtiow_earth_scene.restype, L.rlh_rtiow_earth_scene.argtypes = C.c_void_p, [C.c_void_p, C.c_uint32, C.c_uint32]
         rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
         h, w = rgb8.shape[:2]
-        return World(L.rlh_rtiow_earth_scene(rgb8.ctypes.data, w, h))
+        return World(host_lib().rlh_rtiow_earth_scene(rgb8.ctypes.data, w, h))
 
     @staticmethod
     def example_scene(name: str, obj_text: bytes = None, rgb8: np.ndarray = None):
         """The reference's other example scenes (host/scenes.hpp): "checkered_spheres", "quads", "flat_world", "cornell_box",
         "cornell_smoke", "teapot" (obj_text = teapot-low.obj), "final_scene" (rgb8 = the earth image, sRGB8 [H, W, 3])."""
-        L = host_lib()
-        L.rlh_rtiow_example_scene.restype = C.c_void_p
-        L.rlh_rtiow_example_scene.argtypes = [C.c_char_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32]
         h = w = 0
         ptr = None
         if rgb8 is not None:
             rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
             h, w = rgb8.shape[:2]
             ptr = rgb8.ctypes.data
-        return World(L.rlh_rtiow_example_scene(name.encode(), obj_text, len(obj_text) if obj_text else 0, ptr, w, h))
+        return World(host_lib().rlh_rtiow_example_scene(name.encode(), obj_text, len(obj_text) if obj_text else 0, ptr, w, h))
 
     @staticmethod
     def stress_scene(n_side=1000, subdiv=2, obj_text: bytes = None, rgb8: np.ndarray = None, seed=5, device_bvh=False):
         """BASELINE configs[4]: n_side^2 small spheres + ground + subdivided spot mesh (see host/scenes.hpp).
         device_bvh: build both BVHs with rl_bvh_build on the GPU instead of the host recursion (same tree)."""
         L = host_lib()
-        L.rlh_rtiow_stress_scene.restype = C.c_void_p
-        L.rlh_rtiow_stress_scene.argtypes = [C.c_int, C.c_int, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int]
-        if device_bvh and not _inited:
-            init()
+        if device_bvh:
+            _ensure_init()
         if obj_text is None:
             return World(L.rlh_rtiow_stress_scene(n_side, subdiv, None, 0, None, 0, 0, seed, int(device_bvh)))
         rgb8 = np.ascontiguousarray(rgb8, dtype=np.uint8)
@@ -869,8 +812,7 @@ class World:
         if self._device is None:
             with _create_mu:
                 if self._device is None:
-                    if not _inited:
-                        init()
+                    _ensure_init()
                     L = render_lib()
                     h = L.rl_rtiow_scene_create(self.desc)
                     if not h:
@@ -882,19 +824,15 @@ class World:
         """Hittable::hit(&Ray, &Interval{tmin, tmax}) on the scene root for every ray (hittable/mod.rs:42), on the GPU -> RTIOW_HIT[n]."""
         rays = pack_rays(origins, dirs, times)
         out = np.zeros(rays.shape[0], dtype=RTIOW_HIT)
-        st = Stats()
         # without `stats` the call is counter-free: the fast traversal serves it where it applies (same bits, see last_query())
-        rc = render_lib().rl_rtiow_hit_rays(self.device(), rays.ctypes.data, rays.shape[0], tmin, tmax, out.ctypes.data,
-                                            C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_hit_rays, self.device(), rays.ctypes.data, rays.shape[0], tmin, tmax, out.ctypes.data, stats=stats,
+              allow_degenerate=allow_degenerate)
         return out
 
     def hit_rays_device(self, d_rays, d_out, n, tmin=1e-10, tmax=float("inf"), stream=0, stats=None, allow_degenerate=False):
         """Device buffers (n rl_ray in, n rl_rtiow_hit out; e.g. torch tensors' data_ptr).  Asynchronous unless stats is a dict."""
-        st = Stats()
-        rc = render_lib().rl_rtiow_hit_rays_device(self.device(), C.c_void_p(d_rays), n, tmin, tmax, C.c_void_p(d_out), C.c_void_p(stream),
-                                                   C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_hit_rays_device, self.device(), C.c_void_p(d_rays), n, tmin, tmax, C.c_void_p(d_out), C.c_void_p(stream),
+              stats=stats, allow_degenerate=allow_degenerate)
 
     def hit_rays_seeded(self, rays, cursors, seed, tmin=1e-10, tmax=float("inf"), stats=None, allow_degenerate=False):
         """Hittable::hit(&Ray, &Interval{tmin, tmax}) for every ray of RAY[n], ray i drawing from cursors[i] of `seed` where the reference's fold
@@ -905,21 +843,16 @@ class World:
         n = rays.shape[0]
         out_cur = _cursors_arg(cursors, n).copy()
         out = np.zeros(n, dtype=RTIOW_HIT)
-        st = Stats()
-        rc = render_lib().rl_rtiow_hit_rays_seeded(self.device(), rays.ctypes.data, out_cur.ctypes.data, n, int(seed), tmin, tmax, out.ctypes.data,
-                                                   out_cur.ctypes.data, C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_hit_rays_seeded, self.device(), rays.ctypes.data, out_cur.ctypes.data, n, int(seed), tmin, tmax, out.ctypes.data,
+              out_cur.ctypes.data, stats=stats, allow_degenerate=allow_degenerate)
         return out, out_cur
 
     def hit_rays_seeded_device(self, d_rays, d_cursors, n, seed, d_out, d_out_cursors=0, tmin=1e-10, tmax=float("inf"), stream=0, stats=None,
                                allow_degenerate=False):
         """Device buffers (n rl_ray and n rl_rng_cursor in; n rl_rtiow_hit and optionally n rl_rng_cursor out, which may be d_cursors).
         Asynchronous unless stats is a dict."""
-        st = Stats()
-        rc = render_lib().rl_rtiow_hit_rays_seeded_device(self.device(), C.c_void_p(d_rays), C.c_void_p(d_cursors), n, int(seed), tmin, tmax,
-                                                          C.c_void_p(d_out), C.c_void_p(d_out_cursors or None), C.c_void_p(stream),
-                                                          C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_hit_rays_seeded_device, self.device(), C.c_void_p(d_rays), C.c_void_p(d_cursors), n, int(seed), tmin, tmax,
+              C.c_void_p(d_out), C.c_void_p(d_out_cursors or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
     def ray_color_rays(self, origins, dirs, times, cursors, seed, max_depth, background, stats=None, allow_degenerate=False, rays=None):
         """Camera::ray_color(&mut rng, &ray, world, max_depth) (camera.rs:232-260) for every ray, on the GPU, ray i drawing from
@@ -933,21 +866,17 @@ class World:
         bg = (C.c_double * 3)(*[float(v) for v in background])
         rgb = np.zeros((n, 3), dtype=np.float64)
         counts = np.zeros(n, dtype=np.uint32)
-        st = Stats()
-        rc = render_lib().rl_rtiow_ray_color_rays(self.device(), rays.ctypes.data, out_cur.ctypes.data, n, int(seed), int(max_depth), bg, rgb.ctypes.data,
-                                                  out_cur.ctypes.data, counts.ctypes.data, C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_ray_color_rays, self.device(), rays.ctypes.data, out_cur.ctypes.data, n, int(seed), int(max_depth), bg,
+              rgb.ctypes.data, out_cur.ctypes.data, counts.ctypes.data, stats=stats, allow_degenerate=allow_degenerate)
         return rgb, out_cur, counts
 
     def ray_color_rays_device(self, d_rays, d_cursors, n, seed, max_depth, background, d_rgb, d_out_cursors=0, d_ray_counts=0, stream=0, stats=None,
                               allow_degenerate=False):
         """Device buffers (n rl_ray and n rl_rng_cursor in; n*3 f64, optionally n rl_rng_cursor and n u32 out).  Asynchronous unless stats is a dict."""
         bg = (C.c_double * 3)(*[float(v) for v in background])
-        st = Stats()
-        rc = render_lib().rl_rtiow_ray_color_rays_device(self.device(), C.c_void_p(d_rays), C.c_void_p(d_cursors), n, int(seed), int(max_depth), bg,
-                                                         C.c_void_p(d_rgb), C.c_void_p(d_out_cursors or None), C.c_void_p(d_ray_counts or None),
-                                                         C.c_void_p(stream), C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_ray_color_rays_device, self.device(), C.c_void_p(d_rays), C.c_void_p(d_cursors), n, int(seed), int(max_depth), bg,
+              C.c_void_p(d_rgb), C.c_void_p(d_out_cursors or None), C.c_void_p(d_ray_counts or None), C.c_void_p(stream), stats=stats,
+              allow_degenerate=allow_degenerate)
 
     def scatter_rays(self, rays, hits, cursors, seed, stats=None, allow_degenerate=False):
         """Material::scatter(&mut rng, &ray, &hit_record) + Material::emitted(u, v, &p) (material.rs:11-20) for every element, on the GPU,
@@ -959,20 +888,15 @@ class World:
         hits = _records_arg(hits, RTIOW_HIT, n, "hits")
         out_cur = _cursors_arg(cursors, n).copy()
         out = np.zeros(n, dtype=SCATTER)
-        st = Stats()
-        rc = render_lib().rl_rtiow_scatter_rays(self.device(), rays.ctypes.data, hits.ctypes.data, out_cur.ctypes.data, n, int(seed), out.ctypes.data,
-                                                out_cur.ctypes.data, C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_scatter_rays, self.device(), rays.ctypes.data, hits.ctypes.data, out_cur.ctypes.data, n, int(seed),
+              out.ctypes.data, out_cur.ctypes.data, stats=stats, allow_degenerate=allow_degenerate)
         return out, out_cur
 
     def scatter_rays_device(self, d_rays, d_hits, d_cursors, n, seed, d_out, d_out_cursors=0, stream=0, stats=None, allow_degenerate=False):
         """Device buffers (n rl_ray, n rl_rtiow_hit and n rl_rng_cursor in; n rl_rtiow_scatter and optionally n rl_rng_cursor out, which may be
         d_cursors).  Asynchronous unless stats is a dict.  A material index outside the scene's table gives a zero record."""
-        st = Stats()
-        rc = render_lib().rl_rtiow_scatter_rays_device(self.device(), C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_void_p(d_cursors), n, int(seed),
-                                                       C.c_void_p(d_out), C.c_void_p(d_out_cursors or None), C.c_void_p(stream),
-                                                       C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_scatter_rays_device, self.device(), C.c_void_p(d_rays), C.c_void_p(d_hits), C.c_void_p(d_cursors), n, int(seed),
+              C.c_void_p(d_out), C.c_void_p(d_out_cursors or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
     def texture_values(self, textures, uv, p):
         """Texture::value(u, v, &p) (texture.rs) of the scene's textures[textures[i]] at (uv[i], p[i]), on the GPU -> rgb [n, 3]."""
@@ -1001,26 +925,8 @@ class SceneBuilder:
     """Thin handle over librl_host's builder: textures, materials and hittables by id (names follow the reference)."""
 
     def __init__(self):
-        L = host_lib()
-        L.rlh_builder_new.restype = C.c_void_p
-        for n, a in (("rlh_builder_free", [C.c_void_p]), ("rlh_b_solid", [C.c_void_p, C.c_void_p]),
-                     ("rlh_b_checker", [C.c_void_p, C.c_double, C.c_int, C.c_int]),
-                     ("rlh_b_image", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]),
-                     ("rlh_b_noise", [C.c_void_p, C.c_double, C.c_uint64]),
-                     ("rlh_b_material", [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_double, C.c_double]),
-                     ("rlh_b_sphere", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int]),
-                     ("rlh_b_planar", [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
-                     ("rlh_b_triangle", [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
-                     ("rlh_b_translate", [C.c_void_p, C.c_int, C.c_void_p]),
-                     ("rlh_b_medium", [C.c_void_p, C.c_int, C.c_double, C.c_int]),
-                     ("rlh_b_transform", [C.c_void_p, C.c_int, C.c_int, C.c_double]),
-                     ("rlh_b_group", [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]),
-                     ("rlh_b_obj", [C.c_void_p, C.c_char_p, C.c_uint64, C.c_int]),
-                     ("rlh_b_finish", [C.c_void_p, C.c_int])):
-            getattr(L, n).argtypes = a
-        L.rlh_b_finish.restype = C.c_void_p
-        self._L = L
-        self._b = L.rlh_builder_new()
+        self._L = host_lib()
+        self._b = self._L.rlh_builder_new()
 
     @staticmethod
     def _v(x):
@@ -1122,9 +1028,7 @@ class SceneBuilder:
 def set_rtiow_variant(v):
     """Tests / tools: force a kernel variant (0 auto, 2 general, 4 wave-scheduled general, 1024 / 1025 / 1027 / 1029 wave layouts, 1031 fast general,
     1033 cooperative); a retired number makes the next render fail with RL_E_UNSUPPORTED."""
-    L = render_lib()
-    L.rl_debug_set_rtiow_variant.argtypes = [C.c_int]
-    L.rl_debug_set_rtiow_variant(int(v))
+    render_lib().rl_debug_set_rtiow_variant(int(v))
 
 
 @dataclass
@@ -1144,8 +1048,6 @@ class Canvas:  # camera.rs:263-296; data = SUMS over samples, [H, W, 3] f64
     def to_bincode(self) -> bytes:
         """The reference's checkpoint bytes: bincode::serialize(&canvas) (examples/common/mod.rs:32)."""
         L = host_lib()
-        L.rlh_canvas_to_bincode.restype = C.c_void_p
-        L.rlh_canvas_to_bincode.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         d = np.ascontiguousarray(self.data, dtype=np.float64)
         n = C.c_uint64()
         p = L.rlh_canvas_to_bincode(self.samples, self.width, self.height, d.ctypes.data, d.size // 3, C.byref(n))
@@ -1157,7 +1059,6 @@ class Canvas:  # camera.rs:263-296; data = SUMS over samples, [H, W, 3] f64
     def from_bincode(b: bytes):
         """bincode::deserialize::<Canvas> (examples/common/mod.rs:45-46)."""
         L = host_lib()
-        L.rlh_canvas_from_bincode.argtypes = [C.c_char_p, C.c_uint64] + [C.POINTER(C.c_uint64)] * 4
         s, w, h, n = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         if L.rlh_canvas_from_bincode(b, len(b), C.byref(s), C.byref(w), C.byref(h), C.byref(n)) != 0:
             raise ValueError("malformed checkpoint: " + L.rlh_last_error().decode())
@@ -1291,12 +1192,8 @@ class Camera:
     def _render(self, first_sample, world: World, row_first=0, row_step=1, stats=None, allow_degenerate=False):
         nrows = rows_for(self.c.image_height, row_first, row_step)
         out = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtiow_render_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, out.ctypes.data, C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_rows, world.device(), C.byref(self.c), first_sample, row_first, row_step, out.ctypes.data, stats=stats,
+              counting=True, allow_degenerate=allow_degenerate)
         return out
 
     def render(self, world: World, stats=None, allow_degenerate=False) -> Canvas:  # camera.rs:122
@@ -1358,25 +1255,15 @@ class Camera:
             out = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
         if out.dtype != np.float64 or not out.flags["C_CONTIGUOUS"] or out.size != nrows * self.c.image_width * 3:
             raise ValueError("out must be a C-contiguous float64 array of nrows * W * 3 values")
-        st = Stats()
-        rc = render_lib().rl_rtiow_render_independent_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, int(bool(accumulate)),
-                                                           out.ctypes.data, C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_independent_rows, world.device(), C.byref(self.c), first_sample, row_first, row_step,
+              int(bool(accumulate)), out.ctypes.data, stats=stats, counting=True, allow_degenerate=allow_degenerate)
         return out
 
     def render_independent_device(self, world: World, d_ptr, stream=0, row_first=0, row_step=1, first_sample=0, accumulate=False, stats=None,
                                   allow_degenerate=False):
         """Output stays in HBM (d_ptr: nrows*W*3 f64, read first when accumulate).  Async unless stats is a dict."""
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_independent_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, int(bool(accumulate)),
-                                                             C.c_void_p(d_ptr), C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_independent_device, world.device(), C.byref(self.c), first_sample, row_first, row_step,
+              int(bool(accumulate)), C.c_void_p(d_ptr), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
     # ---- seeded path queries (include/rl_render.h rl_rtiow_camera_rays*): Camera::get_ray for a batch of pixels, each with its own RNG cursor
     def get_rays(self, px, py, cursors):
@@ -1387,46 +1274,32 @@ class Camera:
             raise ValueError(f"px and py must both be [n] (got {x.shape} and {y.shape})")
         n = x.shape[0]
         out_cur = _cursors_arg(cursors, n).copy()
-        if not _inited:
-            init()
+        _ensure_init()
         rays = np.zeros(n, dtype=RAY)
         _check(render_lib().rl_rtiow_camera_rays(C.byref(self.c), n, x.ctypes.data, y.ctypes.data, out_cur.ctypes.data, rays.ctypes.data, out_cur.ctypes.data))
         return rays, out_cur
 
     def get_rays_device(self, d_px, d_py, d_cursors, d_rays, d_out_cursors, n, stream=0):
         """Device buffers (n u32 px, n u32 py, n rl_rng_cursor in; n rl_ray and n rl_rng_cursor out, which may be d_cursors).  Asynchronous."""
-        if not _inited:
-            init()
+        _ensure_init()
         _check(render_lib().rl_rtiow_camera_rays_device(C.byref(self.c), n, C.c_void_p(d_px), C.c_void_p(d_py), C.c_void_p(d_cursors), C.c_void_p(d_rays),
                                                         C.c_void_p(d_out_cursors), C.c_void_p(stream)))
 
     def render_multi(self, world: World, first_sample=0, stats=None, allow_degenerate=False) -> Canvas:
         """rl_rtiow_render_multi: the whole frame over every GPU of init_multi (rows interleaved, one RCCL exchange)."""
         out = np.empty((self.c.image_height, self.c.image_width, 3), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtiow_render_multi(world.device(), C.byref(self.c), first_sample, out.ctypes.data, C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_multi, world.device(), C.byref(self.c), first_sample, out.ctypes.data, stats=stats, counting=True,
+              allow_degenerate=allow_degenerate)
         return Canvas(self.params.samples_per_pixel, self.c.image_width, self.c.image_height, out)
 
     def render_multi_device(self, world: World, d_ptr, first_sample=0, stats=None):
         """Frame left in GPU 0's HBM; asynchronous unless stats is a dict (api.render_status(world) waits)."""
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_multi_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_ptr), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtiow_render_multi_device, world.device(), C.byref(self.c), first_sample, C.c_void_p(d_ptr), stats=stats)
 
     def render_device(self, world: World, d_ptr, stream=0, row_first=0, row_step=1, first_sample=0, stats=None):
         """Output stays in HBM: d_ptr = device pointer of nrows*W*3 f64. Async unless stats is a dict."""
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_device(world.device(), C.byref(self.c), first_sample, row_first, row_step,
-                                                 C.c_void_p(d_ptr), C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtiow_render_device, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.c_void_p(d_ptr),
+              C.c_void_p(stream), stats=stats)
 
     # ---- pixel-list renders (include/rl_render.h rl_rtiow_render_pixels*): the pixels of the caller's choosing, each bit for bit the
     # frame's pixel; compact output
@@ -1436,24 +1309,15 @@ class Camera:
         it the call is counter-free.  A pixel outside the image: RLError(RL_E_INVALID)."""
         xs, ys = _pixel_list(xs, ys)
         out = np.empty((xs.size, 3), dtype=np.float64)
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_pixels(world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, out.ctypes.data,
-                                                 C.byref(st) if st is not None else None)
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_pixels, world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size,
+              out.ctypes.data, stats=stats, allow_degenerate=allow_degenerate)
         return out
 
     def render_pixels_device(self, world: World, d_xs, d_ys, n, d_out, stream=0, first_sample=0, stats=None):
         """d_xs / d_ys: device pointers of n uint32; d_out: of n*3 f64.  Async unless stats is a dict; an element outside the image is
         written as zeros."""
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_pixels_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
-                                                        C.c_void_p(d_out), C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtiow_render_pixels_device, world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
+              C.c_void_p(d_out), C.c_void_p(stream), stats=stats)
 
     # ---- renders with second moments (include/rl_render.h rl_rtiow_render_moments*, rl_rtiow_render_pixels_moments*): the sums of the plain
     # call, bit for bit, and beside them the sums of the squared sample colours — what an adaptive pass picks its pixels by
@@ -1462,23 +1326,14 @@ class Camera:
         nrows = rows_for(self.c.image_height, row_first, row_step)
         sums = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
         sq = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtiow_render_moments_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, sums.ctypes.data, sq.ctypes.data,
-                                                       C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_moments_rows, world.device(), C.byref(self.c), first_sample, row_first, row_step, sums.ctypes.data,
+              sq.ctypes.data, stats=stats, counting=True, allow_degenerate=allow_degenerate)
         return Moments(self.params.samples_per_pixel, sums, sq)
 
     def render_moments_device(self, world: World, d_sums, d_sq, stream=0, row_first=0, row_step=1, first_sample=0, stats=None):
         """Both outputs stay in HBM: d_sums, d_sq = device pointers of nrows*W*3 f64 each.  Async unless stats is a dict."""
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_moments_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.c_void_p(d_sums),
-                                                         C.c_void_p(d_sq), C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtiow_render_moments_device, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.c_void_p(d_sums),
+              C.c_void_p(d_sq), C.c_void_p(stream), stats=stats)
 
     def render_pixels_moments(self, world: World, xs, ys, first_sample=0, stats=None, allow_degenerate=False):
         """(sums [n, 3], sq [n, 3]) of pixels (xs[i], ys[i]): render_pixels' sums and the second moments, each what render_moments holds at
@@ -1486,24 +1341,15 @@ class Camera:
         xs, ys = _pixel_list(xs, ys)
         sums = np.empty((xs.size, 3), dtype=np.float64)
         sq = np.empty((xs.size, 3), dtype=np.float64)
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_pixels_moments(world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, sums.ctypes.data,
-                                                         sq.ctypes.data, C.byref(st) if st is not None else None)
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_pixels_moments, world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size,
+              sums.ctypes.data, sq.ctypes.data, stats=stats, allow_degenerate=allow_degenerate)
         return sums, sq
 
     def render_pixels_moments_device(self, world: World, d_xs, d_ys, n, d_sums, d_sq, stream=0, first_sample=0, stats=None):
         """d_xs / d_ys: device pointers of n uint32; d_sums, d_sq: of n*3 f64 each.  Async unless stats is a dict; an element outside the image
         is written as zeros in both."""
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_pixels_moments_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
-                                                                C.c_void_p(d_sums), C.c_void_p(d_sq), C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtiow_render_pixels_moments_device, world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys),
+              int(n), C.c_void_p(d_sums), C.c_void_p(d_sq), C.c_void_p(stream), stats=stats)
 
     # ---- adaptive renders (include/rl_render.h rl_rtiow_render_adaptive*): render_moments with a stopping rule evaluated inside the launch.
     # A pixel stops at the first checkpoint n = min_samples + k * check_every (n < samples_per_pixel) at which, in every channel,
@@ -1516,25 +1362,16 @@ class Camera:
         sq = np.empty((nrows, self.c.image_width, 3), dtype=np.float64)
         counts = np.empty((nrows, self.c.image_width), dtype=np.uint32)
         rule = RtiowAdaptive(min_samples, check_every, abs_variance, rel_variance)
-        st = Stats()
-        rc = render_lib().rl_rtiow_render_adaptive_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(rule), sums.ctypes.data,
-                                                        sq.ctypes.data, counts.ctypes.data, C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_adaptive_rows, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(rule),
+              sums.ctypes.data, sq.ctypes.data, counts.ctypes.data, stats=stats, counting=True, allow_degenerate=allow_degenerate)
         return Adaptive(sums, sq, counts)
 
     def render_adaptive_device(self, world: World, min_samples, check_every, d_sums, d_sq, d_counts, abs_variance=0.0, rel_variance=0.0, stream=0, row_first=0,
                                row_step=1, first_sample=0, stats=None):
         """All three outputs stay in HBM: d_sums, d_sq = device pointers of nrows*W*3 f64 each, d_counts of nrows*W uint32.  Async unless stats is a dict."""
         rule = RtiowAdaptive(min_samples, check_every, abs_variance, rel_variance)
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_adaptive_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(rule), C.c_void_p(d_sums),
-                                                          C.c_void_p(d_sq), C.c_void_p(d_counts), C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtiow_render_adaptive_device, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(rule),
+              C.c_void_p(d_sums), C.c_void_p(d_sq), C.c_void_p(d_counts), C.c_void_p(stream), stats=stats)
 
 
     # ---- feature renders (include/rl_render.h rl_rtiow_render_features*): per pixel the sums of the first hit's colour factor, normal and
@@ -1543,9 +1380,8 @@ class Camera:
         """Compact shard rows.  Always a counting call (reference-order trace), as render_rows."""
         nrows = rows_for(self.c.image_height, row_first, row_step)
         arrays, f = _features_host(want, (nrows, self.c.image_width))
-        st = Stats()
-        rc = render_lib().rl_rtiow_render_features_rows(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f), C.byref(st))
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtiow_render_features_rows, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f), stats=stats,
+              counting=True, allow_degenerate=allow_degenerate)
         return Features(self.params.samples_per_pixel, **arrays)
 
     def render_features_device(self, world: World, stream=0, row_first=0, row_step=1, first_sample=0, stats=None, allow_degenerate=False, *, d_albedo_sum=0,
@@ -1553,26 +1389,16 @@ class Camera:
         """Outputs stay in HBM: device pointers of nrows*W*3 f64 (albedo, normal), nrows*W f64 (depth), nrows*W uint32 (hit count); 0 = not
         wanted.  Async unless stats is a dict."""
         f = RtiowFeatures(d_albedo_sum or None, d_normal_sum or None, d_depth_sum or None, d_hit_count or None)
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_features_device(world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f), C.c_void_p(stream),
-                                                          C.byref(st) if st is not None else None)
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_features_device, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f),
+              C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
     def render_pixels_features(self, world: World, xs, ys, first_sample=0, want=None, stats=None, allow_degenerate=False) -> Features:
         """Features of pixels (xs[i], ys[i]), [n, ...]: what render_features(world, first_sample) holds at [ys[i], xs[i]].  The list rules
         are render_pixels'.  stats (a dict): a counting call; without it the call is counter-free and may take the fast walk."""
         xs, ys = _pixel_list(xs, ys)
         arrays, f = _features_host(want, (xs.size,))
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_pixels_features(world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, C.byref(f),
-                                                          C.byref(st) if st is not None else None)
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_pixels_features, world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size,
+              C.byref(f), stats=stats, allow_degenerate=allow_degenerate)
         return Features(self.params.samples_per_pixel, **arrays)
 
     def render_pixels_features_device(self, world: World, d_xs, d_ys, n, stream=0, first_sample=0, stats=None, allow_degenerate=False, *, d_albedo_sum=0,
@@ -1580,13 +1406,8 @@ class Camera:
         """d_xs / d_ys: device pointers of n uint32; outputs as render_features_device with n pixels.  Async unless stats is a dict; an element
         outside the image is written as zeros in every given output."""
         f = RtiowFeatures(d_albedo_sum or None, d_normal_sum or None, d_depth_sum or None, d_hit_count or None)
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtiow_render_pixels_features_device(world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
-                                                                 C.byref(f), C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtiow_render_pixels_features_device, world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys),
+              int(n), C.byref(f), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
 
 # ---- denoising (include/rl_render.h "Denoising", rl_denoise_atrous*; DESIGN.md §3.17).  The default sigmas below are UNMEASURED defaults:
@@ -1834,17 +1655,11 @@ class RtcWorld:
 
     @staticmethod
     def test_mirror_scene(res_x=300, res_y=200):  # tests/ray_tracer.rs:56-240
-        L = host_lib()
-        L.rlh_rtc_named_scene.restype = C.c_void_p
-        L.rlh_rtc_named_scene.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
-        return RtcWorld(L.rlh_rtc_named_scene(0, res_x, res_y))
+        return RtcWorld(host_lib().rlh_rtc_named_scene(0, res_x, res_y))
 
     @staticmethod
     def test_csg_scene(res_x=300, res_y=200):  # tests/ray_tracer.rs:277-368
-        L = host_lib()
-        L.rlh_rtc_named_scene.restype = C.c_void_p
-        L.rlh_rtc_named_scene.argtypes = [C.c_int, C.c_uint64, C.c_uint64]
-        return RtcWorld(L.rlh_rtc_named_scene(1, res_x, res_y))
+        return RtcWorld(host_lib().rlh_rtc_named_scene(1, res_x, res_y))
 
     @staticmethod
     def from_arrays(triangles, materials, objects, lights, groups=(), group_items=(), boundeds=(), transformeds=(),
@@ -1867,8 +1682,7 @@ class RtcWorld:
         if self._device is None:
             with _create_mu:
                 if self._device is None:
-                    if not _inited:
-                        init()
+                    _ensure_init()
                     L = render_lib()
                     h = L.rl_rtc_scene_create(self.desc)
                     if not h:
@@ -1881,12 +1695,8 @@ class RtcWorld:
         cam = camera or self.camera
         nrows = rows_for(cam.vsize, row_first, row_step)
         out = np.empty((nrows, cam.hsize, 3), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtc_render_rows(self.device(), C.byref(cam), aa_samples, row_first, row_step, out.ctypes.data, C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtc_render_rows, self.device(), C.byref(cam), aa_samples, row_first, row_step, out.ctypes.data, stats=stats,
+              counting=True, allow_degenerate=allow_degenerate)
         return out
 
     def render_rgb8(self, aa_samples=1, camera=None) -> np.ndarray:
@@ -1900,44 +1710,28 @@ class RtcWorld:
         """rl_rtc_render_multi: the whole frame over every GPU of init_multi."""
         cam = camera or self.camera
         out = np.empty((cam.vsize, cam.hsize, 3), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtc_render_multi(self.device(), C.byref(cam), aa_samples, out.ctypes.data, C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtc_render_multi, self.device(), C.byref(cam), aa_samples, out.ctypes.data, stats=stats, counting=True,
+              allow_degenerate=allow_degenerate)
         return out
 
     def render_device(self, d_ptr, aa_samples=1, camera=None, stream=0, row_first=0, row_step=1, stats=None):
         cam = camera or self.camera
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtc_render_device(self.device(), C.byref(cam), aa_samples, row_first, row_step, C.c_void_p(d_ptr),
-                                               C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtc_render_device, self.device(), C.byref(cam), aa_samples, row_first, row_step, C.c_void_p(d_ptr), C.c_void_p(stream),
+              stats=stats)
 
     def render_pixels(self, xs, ys, aa_samples=1, camera=None, stats=None, allow_degenerate=False):
         """rl_rtc_render_pixels: [n, 3] means of pixels (xs[i], ys[i]), each bit for bit render(aa_samples)[ys[i], xs[i]]."""
         cam = camera or self.camera
         xs, ys = _pixel_list(xs, ys)
         out = np.empty((xs.size, 3), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtc_render_pixels(self.device(), C.byref(cam), aa_samples, xs.ctypes.data, ys.ctypes.data, xs.size, out.ctypes.data, C.byref(st))
-        _check(rc, allow_degenerate)
-        if stats is not None:
-            stats.update(st.as_dict())
-            stats["rc"] = rc
+        _call(render_lib().rl_rtc_render_pixels, self.device(), C.byref(cam), aa_samples, xs.ctypes.data, ys.ctypes.data, xs.size, out.ctypes.data,
+              stats=stats, counting=True, allow_degenerate=allow_degenerate)
         return out
 
     def render_pixels_device(self, d_xs, d_ys, n, d_out, aa_samples=1, camera=None, stream=0, stats=None):
         cam = camera or self.camera
-        st = Stats() if stats is not None else None
-        rc = render_lib().rl_rtc_render_pixels_device(self.device(), C.byref(cam), aa_samples, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n), C.c_void_p(d_out),
-                                                      C.c_void_p(stream), C.byref(st) if st is not None else None)
-        _check(rc)
-        if stats is not None:
-            stats.update(st.as_dict())
+        _call(render_lib().rl_rtc_render_pixels_device, self.device(), C.byref(cam), aa_samples, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
+              C.c_void_p(d_out), C.c_void_p(stream), stats=stats)
 
     def intersect_rays(self, origins, dirs, k=8, stats=None, allow_degenerate=False):
         """World::intersect (world.rs:46) + hit (intersect.rs:159-168) for every ray -> (counts[n], isects RTC_ISECT[n, k], hit_index[n]);
@@ -1947,33 +1741,26 @@ class RtcWorld:
         counts = np.zeros(n, dtype=np.uint32)
         isects = np.zeros((n, k), dtype=RTC_ISECT)
         hit_index = np.full(n, NO_HIT, dtype=np.uint32)
-        st = Stats()
-        rc = render_lib().rl_rtc_intersect_rays(self.device(), rays.ctypes.data, n, k, isects.ctypes.data if k else None, counts.ctypes.data,
-                                                hit_index.ctypes.data, C.byref(st))
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_intersect_rays, self.device(), rays.ctypes.data, n, k, isects.ctypes.data if k else None, counts.ctypes.data,
+              hit_index.ctypes.data, stats=stats, counting=True, allow_degenerate=allow_degenerate)
         return counts, isects, hit_index
 
     def intersect_rays_device(self, d_rays, n, k, d_isects, d_counts, d_hit_index=0, stream=0, stats=None, allow_degenerate=False):
-        st = Stats()
-        rc = render_lib().rl_rtc_intersect_rays_device(self.device(), C.c_void_p(d_rays), n, k, C.c_void_p(d_isects) if d_isects else None,
-                                                       C.c_void_p(d_counts), C.c_void_p(d_hit_index) if d_hit_index else None, C.c_void_p(stream),
-                                                       C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_intersect_rays_device, self.device(), C.c_void_p(d_rays), n, k, C.c_void_p(d_isects) if d_isects else None,
+              C.c_void_p(d_counts), C.c_void_p(d_hit_index) if d_hit_index else None, C.c_void_p(stream), stats=stats,
+              allow_degenerate=allow_degenerate)
 
     def color_at_rays(self, origins, dirs, stats=None, allow_degenerate=False):
         """World::color_at(&ray) (world.rs:100) for every ray, with the world's max_reflection_depth -> [n, 3]."""
         rays = pack_rays(origins, dirs)
         out = np.zeros((rays.shape[0], 3), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtc_color_at_rays(self.device(), rays.ctypes.data, rays.shape[0], out.ctypes.data, C.byref(st))
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_color_at_rays, self.device(), rays.ctypes.data, rays.shape[0], out.ctypes.data, stats=stats, counting=True,
+              allow_degenerate=allow_degenerate)
         return out
 
     def color_at_rays_device(self, d_rays, d_rgb, n, stream=0, stats=None, allow_degenerate=False):
-        st = Stats()
-        rc = render_lib().rl_rtc_color_at_rays_device(self.device(), C.c_void_p(d_rays), n, C.c_void_p(d_rgb), C.c_void_p(stream),
-                                                      C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_color_at_rays_device, self.device(), C.c_void_p(d_rays), n, C.c_void_p(d_rgb), C.c_void_p(stream), stats=stats,
+              allow_degenerate=allow_degenerate)
 
     # ---- shading queries (include/rl_render.h "RTC shading queries"; DESIGN.md §3.11)
     def _table(self, field, dtype):
@@ -1997,17 +1784,13 @@ class RtcWorld:
         rays = pack_rays(origins, dirs)
         n = rays.shape[0]
         out = np.zeros(n, dtype=RTC_COMPS)
-        st = Stats()
-        rc = render_lib().rl_rtc_prepare_rays(self.device(), rays.ctypes.data, n, out.ctypes.data, C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_prepare_rays, self.device(), rays.ctypes.data, n, out.ctypes.data, stats=stats, allow_degenerate=allow_degenerate)
         return out
 
     def prepare_rays_device(self, d_rays, n, d_comps, stream=0, stats=None, allow_degenerate=False):
         """Device buffers (n rl_ray in, n rl_rtc_comps out).  Asynchronous unless stats is a dict."""
-        st = Stats()
-        rc = render_lib().rl_rtc_prepare_rays_device(self.device(), C.c_void_p(d_rays), n, C.c_void_p(d_comps), C.c_void_p(stream),
-                                                     C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_prepare_rays_device, self.device(), C.c_void_p(d_rays), n, C.c_void_p(d_comps), C.c_void_p(stream), stats=stats,
+              allow_degenerate=allow_degenerate)
 
     def shade_hits(self, comps, stats=None, allow_degenerate=False):
         """What World::shade_hit (world.rs:57-87) computes before it recurses, for every RTC_COMPS record (from prepare_rays or hand-made)
@@ -2017,19 +1800,15 @@ class RtcWorld:
         n = comps.shape[0]
         out = np.zeros(n, dtype=RTC_SHADE)
         shadow = np.zeros((n, RtcSceneDesc.from_address(self.desc).n_lights), dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtc_shade_hits(self.device(), comps.ctypes.data, n, out.ctypes.data, shadow.ctypes.data if shadow.size else None,
-                                            C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_shade_hits, self.device(), comps.ctypes.data, n, out.ctypes.data, shadow.ctypes.data if shadow.size else None,
+              stats=stats, allow_degenerate=allow_degenerate)
         return out, shadow
 
     def shade_hits_device(self, d_comps, n, d_out, d_out_shadow=0, stream=0, stats=None, allow_degenerate=False):
         """Device buffers (n rl_rtc_comps in; n rl_rtc_shade and optionally n * n_lights f64 out).  Asynchronous unless stats is a dict.
         A material index outside the scene's table gives a zero record."""
-        st = Stats()
-        rc = render_lib().rl_rtc_shade_hits_device(self.device(), C.c_void_p(d_comps), n, C.c_void_p(d_out), C.c_void_p(d_out_shadow or None),
-                                                   C.c_void_p(stream), C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_shade_hits_device, self.device(), C.c_void_p(d_comps), n, C.c_void_p(d_out), C.c_void_p(d_out_shadow or None),
+              C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
     @staticmethod
     def _vec3_arg(a, n, what):
@@ -2047,18 +1826,14 @@ class RtcWorld:
         n = pts.shape[0]
         lp = self._vec3_arg(light_positions, n, "light_positions")
         out = np.zeros(n, dtype=np.float64)
-        st = Stats()
-        rc = render_lib().rl_rtc_shadow_attenuation(self.device(), pts.ctypes.data, lp.ctypes.data, n, out.ctypes.data,
-                                                    C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_shadow_attenuation, self.device(), pts.ctypes.data, lp.ctypes.data, n, out.ctypes.data, stats=stats,
+              allow_degenerate=allow_degenerate)
         return out
 
     def shadow_attenuation_device(self, d_points, d_light_positions, n, d_out, stream=0, stats=None, allow_degenerate=False):
         """Device buffers (n * 3 and n * 3 f64 in, n f64 out).  Asynchronous unless stats is a dict."""
-        st = Stats()
-        rc = render_lib().rl_rtc_shadow_attenuation_device(self.device(), C.c_void_p(d_points), C.c_void_p(d_light_positions), n, C.c_void_p(d_out),
-                                                           C.c_void_p(stream), C.byref(st) if stats is not None else None)
-        _finish_query(rc, st, stats, allow_degenerate)
+        _call(render_lib().rl_rtc_shadow_attenuation_device, self.device(), C.c_void_p(d_points), C.c_void_p(d_light_positions), n, C.c_void_p(d_out),
+              C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
     def lighting(self, comps, light_positions, light_intensities, shadow_att):
         """material::lighting (material.rs:54-90) of every RTC_COMPS record under PointLight{light_positions[i], light_intensities[i]} ([n, 3],

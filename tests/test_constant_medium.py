@@ -199,7 +199,6 @@ def test_gpu_fast_traversal_with_every_boundary_shape_equals_counting_kernel_and
                         background=(0.3, 0.4, 0.6), seed=17)
     cam = rl.Camera(p)
     out16 = (rl.api.C.c_uint64 * 16)()
-    rl.api.render_lib().rl_debug_host_structures.argtypes = [rl.api.C.c_void_p, rl.api.C.c_void_p]
     assert rl.api.render_lib().rl_debug_host_structures(world.desc, out16) == 0 and (out16[0] & 2)  # the general fast structure exists
     gs, cs = {}, {}
     counting = cam.render(world, stats=gs).data
@@ -238,7 +237,6 @@ def test_gpu_fast_traversal_with_unbounded_planes_equals_counting_kernel_and_ora
     import torch
     world = rl.World.build(_planes_scene)
     out16 = (rl.api.C.c_uint64 * 16)()
-    rl.api.render_lib().rl_debug_host_structures.argtypes = [rl.api.C.c_void_p, rl.api.C.c_void_p]
     assert rl.api.render_lib().rl_debug_host_structures(world.desc, out16) == 0 and (out16[0] & 2)
     assert out16[14] == 2 and out16[15] == 0x0012  # puff: a sphere behind a box node; slab: general shape, no box node
     for seed, depth in ((3, 1), (4, 12)):

@@ -85,7 +85,6 @@ def test_gpu_example_scenes_equal_oracle(rl, oracle, golden, name):
     assert np.array_equal(buf.cpu().numpy(), counting), name  # the timed (counter-free) kernel: same bits
     if name == "final_scene":  # media + Perlin / sphere-UV code: small frames take the one-wave-per-SIMD instantiation (512 registers) — both forms
         L = rl.api.render_lib()
-        L.rl_debug_set_fastg_one_wave.argtypes = [rl.api.C.c_int]
         try:
             for mode in (0, 1):
                 L.rl_debug_set_fastg_one_wave(mode)

@@ -42,7 +42,6 @@ def test_device_bvh_equals_oracle_bvh(rl, oracle, n, ties):
     rl.init(0)
     api = rl.api
     L = api.render_lib()
-    L.rl_bvh_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     boxes = _random_boxes(n, 77 + n, ties)
     prims = np.zeros(n, dtype=api.HREF)
     prims["kind"] = np.where(np.arange(n) % 5 == 4, 2, 1)
@@ -60,7 +59,6 @@ def test_bvh_build_rejects_bad_input(rl):
     rl.init(0)
     api = rl.api
     L = api.render_lib()
-    L.rl_bvh_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
     boxes = np.zeros((3, 6))
     boxes[:, 1::2] = 1.0
     prims = np.zeros(3, dtype=api.HREF)

@@ -239,7 +239,6 @@ def test_a_sphere_named_twice_renders_from_the_linked_ops(rl, oracle):
     items[6], items[7] = items[0], items[1]  # the last item names sphere 0 again; sphere 3 is left out
     r = (C.c_uint64 * 16)()
     L = rl.api.render_lib()
-    L.rl_debug_host_structures.argtypes = [C.c_void_p, C.c_void_p]
     assert L.rl_debug_host_structures(world.desc, r) == 0 and r[0] == 0  # no fast tree: guards were refused
     p = rl.CameraParams(aspect_ratio=2.0, image_width=16, samples_per_pixel=4, max_depth=8, vfov=50.0, lookfrom=(0, 0.3, 1), lookat=(0, 0, -3),
                         background=(0.6, 0.7, 0.9))

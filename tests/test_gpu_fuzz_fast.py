@@ -96,7 +96,6 @@ def test_fast_and_cooperative_kernels_equal_the_counting_kernel_on_adversarial_w
         gs = {}
         counting = cam.render(world, stats=gs, allow_degenerate=True).data
         out16 = (api.C.c_uint64 * 16)()
-        api.render_lib().rl_debug_host_structures.argtypes = [api.C.c_void_p, api.C.c_void_p]
         assert api.render_lib().rl_debug_host_structures(world.desc, out16) == 0
         fast_structures += int(out16[0] & 1)
         frames = {}

@@ -136,7 +136,6 @@ def test_fast_general_kernel_equals_the_counting_kernel_on_random_compositions(r
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
     out16 = (api.C.c_uint64 * 16)()
-    api.render_lib().rl_debug_host_structures.argtypes = [api.C.c_void_p, api.C.c_void_p]
     fast_structures = slow = rays = media = 0
     cases = int(os.environ.get("RL_FUZZ_CASES", "40"))  # (a one-off deep run: RL_FUZZ_CASES=600 RL_FUZZ_WIDTH=150)
     for case in range(cases):

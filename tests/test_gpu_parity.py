@@ -140,7 +140,6 @@ def test_rtc_teapot_antialiased_and_sharded(rl, oracle, golden):
         assert np.array_equal(world.render(3, row_first=g, row_step=4), img[g::4])
     # the grid is the number of workgroups resident at once (occupancy API); any other count strides over the same pixels: same frame, same counters
     L = rl.api.render_lib()
-    L.rl_debug_set_rtc_blocks.argtypes = [rl.api.C.c_int]
     ref_stats = {}
     world.render(3, stats=ref_stats)
     mirror = rl.RtcWorld.test_mirror_scene(120, 80)  # the full World::color_at kernel

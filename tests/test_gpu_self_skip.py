@@ -13,7 +13,6 @@ pytestmark = pytest.mark.gpu
 
 def _fast_tree(rl, world):
     L = rl.api.render_lib()
-    L.rl_debug_host_structures.argtypes = [C.c_void_p, C.c_void_p]
     out = (C.c_uint64 * 16)()
     assert L.rl_debug_host_structures(world.desc, out) == 0, L.rl_last_error().decode()
     return bool(out[0] & 1)

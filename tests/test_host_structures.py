@@ -11,7 +11,6 @@ import pytest
 
 def _check(rl, world):
     L = rl.api.render_lib()
-    L.rl_debug_host_structures.argtypes = [C.c_void_p, C.c_void_p]
     out = (C.c_uint64 * 16)()
     rc = L.rl_debug_host_structures(world.desc, out)
     assert rc == 0, L.rl_last_error().decode()

@@ -7,7 +7,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.ins
 rl = importlib.import_module("rendering-learning_amd"); rl.init(0)
 dev = torch.device("cuda", 0)
 L = rl.api.render_lib()
-L.rl_debug_pixel_rays.argtypes = [C.c_void_p, C.c_uint64]; L.rl_debug_pixel_rays_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
 spp = int(sys.argv[1]) if len(sys.argv) > 1 else 256
 sizes = [tuple(float(v) if i else int(v) for i, v in enumerate(a.split(':'))) for a in sys.argv[2:]] or [(1, 1.0), (8, 1.0), (32, 16.0 / 9.0), (128, 16.0 / 9.0)]
 for width, aspect in sizes:

@@ -17,8 +17,6 @@ sys.path.insert(0, ROOT)
 rl = importlib.import_module("rendering-learning_amd")
 rl.init(0)
 L = rl.api.render_lib()
-L.rl_debug_pixel_rays.argtypes = [C.c_void_p, C.c_uint64]
-L.rl_debug_pixel_rays_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
 dev = torch.device("cuda", 0)
 spp = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 for width, aspect in ((1, 1.0), (2, 1.0), (8, 1.0), (64, 16.0 / 9.0), (256, 16.0 / 9.0)):

@@ -22,8 +22,6 @@ p.image_width, p.samples_per_pixel, p.max_depth = width, spp, 50
 cam = rl.Camera(p)
 W, H = cam.c.image_width, cam.c.image_height
 L = rl.api.render_lib()
-L.rl_debug_pixel_rays.argtypes = [C.c_void_p, C.c_uint64]
-L.rl_debug_pixel_rays_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
 assert L.rl_debug_pixel_rays(world.device(), W * H) == 0
 st = {}
 cam.render(world, stats=st)

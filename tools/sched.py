@@ -15,7 +15,7 @@ if os.environ.get("RL_SCHED_FAST", "1") != "0":  # the timed kernel's fast trave
 st = {}
 cam.render(w, stats=st)
 out = (C.c_uint64 * 32)()
-L = rl.api.render_lib(); L.rl_debug_sched.argtypes = [C.c_void_p, C.c_void_p]
+L = rl.api.render_lib()
 L.rl_debug_sched(w.device(), out)
 names = {0: "GEN", 1: "TRAV", 2: "SHADE", 3: "FILL", 5: "LEAF", 6: "SHADE2"}
 print("rays", st["rays"], "kernel_ms", st["kernel_ms"], "Mrays/s", st["rays"] / st["kernel_ms"] / 1e3, "box tests/ray", st["node_tests"] / st["rays"], "sphere tests/ray", st["sphere_tests"] / st["rays"])
