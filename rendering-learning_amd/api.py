@@ -100,6 +100,13 @@ RTC_COMPS = np.dtype([("t", "<f8"), ("point", "<f8", 3), ("eye_v", "<f8", 3), ("
                       ("hit", "<u4"), ("inside", "<u4"), ("object", "<u4"), ("material", "<u4")])
 RTC_SHADE = np.dtype([("surface", "<f8", 3), ("schlick", "<f8"), ("reflected", RAY), ("refracted", RAY), ("reflect", "<u4"), ("refract", "<u4")])
 assert RTC_COMPS.itemsize == 208 and RTC_SHADE.itemsize == 152
+# the compiled RTC program as the kernels read it (csrc/rl_program.h DevOp / DevTri / RtcGuard; rtc_program)
+RTC_DEV_OP = np.dtype([("box", "<f8", 6), ("code", "<u4"), ("skip", "<u4"), ("a", "<u4"), ("b", "<u4")])
+RTC_DEV_TRI = np.dtype([("p1", "<f8", 3), ("e1", "<f8", 3), ("e2", "<f8", 3), ("n1", "<f8", 3), ("n2", "<f8", 3), ("n3", "<f8", 3),
+                        ("smooth", "<u4"), ("material", "<u4"), ("_pad", "<f8")])
+RTC_GUARD = np.dtype([("box", "<f4", 6), ("skip", "<u4"), ("tri", "<u4")])
+assert RTC_DEV_OP.itemsize == 64 and RTC_DEV_TRI.itemsize == 160 and RTC_GUARD.itemsize == 32
+ROP_END, ROP_ENTER, ROP_EXIT, ROP_BOUNDS, ROP_TRIS = 0, 1, 2, 3, 4
 NO_HIT = 0xFFFFFFFF  # out_hit_index of a ray hit() returns None for
 
 MAT_FLAT, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC = 0, 1, 2, 3, 4, 5
@@ -289,6 +296,8 @@ RENDER_SIGNATURES = {
     "rl_debug_last_denoise_route": (_I, []),
     "rl_debug_set_denoise_blocks": (None, [_U32]),
     "rl_debug_last_denoise_launch": (None, [_P]),
+    "rl_debug_rtc_program": (_I, [_P, _P, _P, _P, _PU64, _PU64]),
+    "rl_debug_last_rtc_launch": (None, [_P]),
 }
 # every symbol include/rl_render.h declares (checked by tests/test_abi.py)
 RENDER_SYMBOLS = [n for n in RENDER_SIGNATURES if not n.startswith("rl_debug_")]
@@ -636,6 +645,26 @@ def last_denoise_launch():
     out = (C.c_uint64 * 2)()
     render_lib().rl_debug_last_denoise_launch(out)
     return {"tiles": int(out[0]), "blocks": int(out[1])}
+
+
+def last_rtc_launch():
+    """rl_debug_last_rtc_launch: the most recent RTC render launch of this process: {"kernel": "none" / "rtc" (rtc_kernel, rtc_pixels_kernel) /
+    "full", "list": the pixel-list flavour, "lds_bytes": its dynamic LDS (0: the scene is read from global memory), "blocks": its workgroups}."""
+    out = (C.c_uint64 * 4)()
+    render_lib().rl_debug_last_rtc_launch(out)
+    return {"kernel": {1: "rtc", 2: "full"}.get(int(out[0]), "none"), "list": bool(out[1]), "lds_bytes": int(out[2]), "blocks": int(out[3])}
+
+
+def rtc_program(world):
+    """rl_debug_rtc_program (host only, no device): the program an RtcWorld compiles to, as the kernels read it ->
+    {"ops": RTC_DEV_OP[n_ops], "tris": RTC_DEV_TRI[n_tris], "guards": RTC_GUARD[n_guards], "scene_bytes": what the launch compares with 64 KB}."""
+    L = render_lib()
+    counts = (C.c_uint64 * 4)()
+    _check(L.rl_debug_rtc_program(world.desc, None, None, None, None, counts))
+    ops, tris, guards = np.zeros(int(counts[0]), dtype=RTC_DEV_OP), np.zeros(int(counts[1]), dtype=RTC_DEV_TRI), np.zeros(int(counts[2]), dtype=RTC_GUARD)
+    cap = (C.c_uint64 * 3)(ops.size, tris.size, guards.size)
+    _check(L.rl_debug_rtc_program(world.desc, ops.ctypes.data, tris.ctypes.data, guards.ctypes.data, cap, counts))
+    return {"ops": ops, "tris": tris, "guards": guards, "scene_bytes": int(counts[3])}
 
 
 def material_query_max_lanes():

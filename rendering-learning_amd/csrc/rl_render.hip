@@ -66,6 +66,8 @@ struct Switches {
   bool pixel_entry_sphere = true;  // RL_PIXEL_ENTRY_SPHERE=0: that cut keeps every leaf whose BOX the pixel's beam touches; default: only those whose sphere it may touch
 } g_sw;
 std::atomic<unsigned long long> g_last_slow_traces{0};  // rl_debug_slow_traces.  Atomic: rl_render_status of two scenes runs under two locks.
+// rl_debug_last_rtc_launch: the most recent rtc_render_launch of this process (kernel 0: none yet)
+std::atomic<uint64_t> g_last_rtc_kernel{0}, g_last_rtc_list{0}, g_last_rtc_lds{0}, g_last_rtc_blocks{0};
 // The instrumented fast sphere kernel rtiow_wave_kernel<1024, 4, true> (rl_debug_fast_stats, tools/sched.py) is compiled into the verify
 // build only (make verify); in the product library rl_debug_fast_stats does nothing.
 #ifdef RL_FASTG_VERIFY
@@ -1026,6 +1028,26 @@ int rl_debug_host_structures(const rl_rtiow_scene_desc *desc, unsigned long long
   host_structures_report(desc, *H, out16);
   return RL_OK;
 }
+// Not part of the ABI (tests only).  Host-only: the RTC program a scene description compiles to, as the kernels read it — the DevOp, DevTri and
+// RtcGuard records (build_host_rtc), the first cap[0], cap[1], cap[2] of them copied where the pointer is not null — and counts[4] = n_ops,
+// n_tris, n_guards, HostRtc::scene_bytes (what rtc_render_launch compares with the LDS limit).  Returns RL_OK or the compile error.
+int rl_debug_rtc_program(const rl_rtc_scene_desc *desc, void *ops, void *tris, void *guards, const uint64_t cap[3], uint64_t counts[4]) {
+  if (!desc || !counts || ((ops || tris || guards) && !cap)) return set_err(RL_E_INVALID, "bad argument");
+  std::shared_ptr<const HostRtc> H;
+  std::string err;
+  int rc = build_host_rtc(*desc, H, err);
+  if (rc != RL_OK) return set_err(rc, err);
+  counts[0] = H->rc.ops.size(), counts[1] = H->rc.tris.size(), counts[2] = H->guards.size(), counts[3] = H->scene_bytes();
+  if (ops) std::memcpy(ops, H->rc.ops.data(), (size_t)std::min<uint64_t>(cap[0], counts[0]) * sizeof(DevOp));
+  if (tris) std::memcpy(tris, H->rc.tris.data(), (size_t)std::min<uint64_t>(cap[1], counts[1]) * sizeof(DevTri));
+  if (guards) std::memcpy(guards, H->guards.data(), (size_t)std::min<uint64_t>(cap[2], counts[2]) * sizeof(RtcGuard));
+  return RL_OK;
+}
+// Tests: out[4] = which kernel the most recent rtc_render_launch of this process took (0 none yet, 1 rtc_kernel / rtc_pixels_kernel, 2 the
+// full kernel), 1 for the list flavour, the launch's dynamic LDS bytes (0: the scene is read from global memory), its workgroups.
+void rl_debug_last_rtc_launch(uint64_t out[4]) {
+  if (out) out[0] = g_last_rtc_kernel.load(), out[1] = g_last_rtc_list.load(), out[2] = g_last_rtc_lds.load(), out[3] = g_last_rtc_blocks.load();
+}
 // force an RTIOW kernel variant (0 auto, 1 nested-loop, 2 general, 512/768/1024 wave)
 void rl_debug_set_rtiow_variant(int v) { g_sw.rtiow_variant = v; }
 void rl_debug_set_lpt(int on) { g_sw.lpt = on != 0; }
@@ -1283,8 +1305,8 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
   }
   HIP_TRY(hipMemsetAsync(scene->d_scratch, 0, 512, stream));
   constexpr int NT = 256;
-  size_t scene_bytes = (size_t)P.n_ops * sizeof(DevOp) + (size_t)P.n_tris * sizeof(DevTri) + (size_t)P.n_guards * sizeof(RtcGuard);
-  bool lds_scene = scene_bytes <= 65536;
+  size_t scene_bytes = scene->hrc->scene_bytes();
+  bool lds_scene = scene_bytes <= RTC_LDS_SCENE_MAX;
   size_t lds = lds_scene ? scene_bytes : 0;
   uint64_t total = list ? n_list : (uint64_t)W * nrows;
   uint64_t want = (total + NT - 1) / NT;
@@ -1311,7 +1333,8 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
   };
   uint32_t blocks = 0;
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev0, stream));
-  if (rc_.needs_full || g_sw.rtc_force_full) {  // (RL_RTC_FORCE_FULL: A/B, triangle-only worlds through the full kernel)  // shapes / CSG / patterns / reflection / refraction: the full World::color_at kernel
+  const bool full = rc_.needs_full || g_sw.rtc_force_full;
+  if (full) {  // (RL_RTC_FORCE_FULL: A/B, triangle-only worlds through the full kernel)  // shapes / CSG / patterns / reflection / refraction: the full World::color_at kernel
     RtcFullParams F{};
     F.R = P;
     F.shapes = scene->d_shapes, F.csgs = scene->d_csgs, F.patterns = scene->d_patterns;
@@ -1341,6 +1364,7 @@ int rtc_render_launch(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t 
     blocks = grid_for((const void *)rtc_kernel<NT, false>, 0);
     hipLaunchKernelGGL((rtc_kernel<NT, false>), dim3(blocks), dim3(NT), 0, stream, P);
   }
+  g_last_rtc_kernel = full ? 2u : 1u, g_last_rtc_list = list ? 1u : 0u, g_last_rtc_lds = full ? 0u : lds, g_last_rtc_blocks = blocks;
   HIP_TRY(hipGetLastError());
   if (want_stats) HIP_TRY(hipEventRecord(scene->ev1, stream));
   return RL_OK;  // the caller ends the render with collect_stats / post_status, which record ev_last behind the stats copy

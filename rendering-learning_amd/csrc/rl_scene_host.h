@@ -32,7 +32,11 @@ struct HostRtiow {
 struct HostRtc {
   RtcProgram rc;
   std::vector<RtcGuard> guards;
+  // What rtc_kernel / rtc_pixels_kernel stage in LDS: ops, triangles, guards, in that order.  rtc_render_launch sizes the launch's dynamic LDS
+  // with it and takes the global-memory instantiations above RTC_LDS_SCENE_MAX; rl_debug_rtc_program reports it.
+  size_t scene_bytes() const { return rc.ops.size() * sizeof(DevOp) + rc.tris.size() * sizeof(DevTri) + guards.size() * sizeof(RtcGuard); }
 };
+static const size_t RTC_LDS_SCENE_MAX = 65536;
 
 // Both return RL_OK, or the code the entry point hands on (RL_E_INVALID / RL_E_UNSUPPORTED) with `err` filled; `out` is set on RL_OK only.
 // RTIOW: validate + lower the graph, link the ops, flatten the materials, build the fast structures.

@@ -394,6 +394,9 @@ def drive(api, patch):
         run("RtcWorld.shadow_attenuation_device", rtc.shadow_attenuation_device, D, 2 * D, 3, 3 * D)
         run("RtcWorld.lighting", rtc.lighting, comps, (0.0, 10.0, 0.0), (1.0, 1.0, 1.0), 1.0)
         run("RtcWorld.lighting_device", rtc.lighting_device, D, 2 * D, 3 * D, 4 * D, 3, 5 * D, 6 * D)
+        # ---- RTC read-outs (appended: the rows above keep their places in the fixture)
+        run("last_rtc_launch", api.last_rtc_launch)
+        run("rtc_program", api.rtc_program, rtc)
     finally:
         for w in worlds:  # the handles are the recorder's: nothing of the real library may ever see them
             w._device = None
