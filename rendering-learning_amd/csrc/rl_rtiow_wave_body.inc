@@ -94,7 +94,7 @@
   uint32_t pc = 0, hit_prim = NONE, depth = 0;
   // fast traversal: depth carries, in its top ten bits, the entry id of the sphere the ray has just left when fast_self_miss proved that the
   // ray's own LEAF visit would accept nothing (FAST_NONE otherwise, and for camera rays); the remaining depth sits in the low 22 bits
-  // (the host runs variant 1029 for max_depth < 2^22 only).  The kernel is at exactly 128 VGPRs, and one more register costs a wave per SIMD.
+  // (the host runs variant 1029 for max_depth < 2^22 only).  The budget is 128 VGPRs (one more costs a wave per SIMD); the headline kernel uses 119.
   constexpr uint32_t DEPTH_MASK = LDS_SCENE == 4 ? FAST_DEPTH_MASK : ~0u;
   uint32_t c_rays = 0, c_flag = 0, c_slow = 0;  // c_slow: rays the fast traversal handed to the reference-order fold
   unsigned long long c_nodes = 0, c_sph = 0, c_words = 0, c_self = 0;  // c_self (STATS): self tests skipped
@@ -125,31 +125,31 @@
   // Measured (round 3, -DRL_SPLIT_LEAF=true): 6709 -> 5907 Mrays/s, 1/8 shard 173 -> 205 ms — like SPLIT_SHADE, one more scheduling class
   // costs more in population per block than the shorter blocks give back (tools/sched.py: LEAF is 32 % of the time at 35 lanes per block)
   constexpr bool SPLIT_LEAF = RL_SPLIT_LEAF;
+  // shade() writes the next ray over the old one before it knows whether the path goes on (see there).  The fast kernels only: the
+  // reference-order layouts gain nothing (the counting instantiation's SHADE pick path reads 509 -> 824 instructions, 94 -> 102 spilled SGPRs)
+  constexpr bool SHADE_RAY_IN_PLACE = LDS_SCENE == 4;
   auto shade_state = [&]() -> uint32_t {  // where a finished traversal is shaded
     if (!SPLIT_SHADE || LDS_SCENE != 4 || hit_prim == NONE) return ST_SHADE;
     const uint32_t si = hit_prim & SPH_INDEX;
     return ((s_bits[bits_words + (si >> 5)] >> (si & 31u)) & 1u) ? ST_SHADE2 : ST_SHADE;
   };
   auto fast_go = [&](uint32_t e) {  // continue with entry e: an inner node (TRAV), a sphere (LEAF), or nothing left
-    if (e == FAST_NONE) {
+    const bool end = e == FAST_NONE;
 #ifdef RL_FASTG_VERIFY
-      if (LDS_SCENE == 4 && !amb) {  // a walk that trusts its own answer: the reference's fold must give the same one
-        fast_verify_ray(P.ops, spheres, o, d, time, closest, hit_prim, 2.0);
-        atomicAdd(&g_vstats[3], 1ull);
-      }
+    if (LDS_SCENE == 4 && end && !amb) {  // a walk that trusts its own answer: the reference's fold must give the same one
+      fast_verify_ray(P.ops, spheres, o, d, time, closest, hit_prim, 2.0);
+      atomicAdd(&g_vstats[3], 1ull);
+    }
 #endif
-      if (amb) pc = FAST_SLOW, state = ST_LEAF;
-      else if (hit_prim == NONE) {  // a miss needs no SHADE visit: background (camera.rs:257), sample done (+10 %)
-        if constexpr (MOMENTS) {
-          const D3 c = thr * ld3(P.cam.background);
-          sum = sum + c;
-          sq = sq + c * c;
-        } else sum = sum + thr * ld3(P.cam.background);
-        n++;
-        state = ST_GEN;
-      } else state = shade_state();
-    } else if (e >= P.n_fast_inner) pc = e, state = ST_LEAF;
-    else pc = lds_base + (e << 6), state = ST_TRAV;
+    // State and pc are selects, not branches: no divergent region is left in a TRAV step after the push and the pop.  A walk that ends
+    // with a hit leaves pc = FAST_NONE behind, which nothing reads: SHADE and FILL do not look at pc, and GEN only for FAST_MISSED.
+    // A miss needs no SHADE visit (+10 %), and no work here either: the lane goes to GEN in every case, where a sample ends anyway, and
+    // GEN adds the background and counts the sample when it finds the marker.  Resolved here, the three products of thr * background are
+    // hoisted into every TRAV pick's preamble and the adds sit in a nest of exec-mask regions inside the step (DESIGN.md section 3.1)
+    const bool leaf = e >= P.n_fast_inner, miss = hit_prim == NONE, settled = end && !amb;
+    const uint32_t st_hit = SPLIT_SHADE && settled && !miss ? shade_state() : ST_SHADE;
+    pc = settled ? (miss ? FAST_MISSED : e) : end ? FAST_SLOW : leaf ? e : lds_base + (e << 6);
+    state = settled ? (miss ? ST_GEN : st_hit) : leaf ? ST_LEAF : ST_TRAV;
   };
   // w (fast traversal): where the walk starts — up to three entry ids, the first one in the low ten bits, FAST_NONE in the unused slots,
   // the top two bits set.  fast_root_word for a scattered ray; a camera ray takes its pixel's word of P.pixel_entry (rl_pixel_entry.h)
@@ -256,7 +256,8 @@
           }
           // fast traversal: may the next ray skip its test of this sphere?  (decided for every hit: a path that ends here starts its
           // next sample in GEN, which clears the entry.)  The sphere is read again and its centre and oc = p - center re-derived — the
-          // same expressions, the same values — instead of being held through the material code above (that costs 21 spilled VGPRs)
+          // same expressions, the same values — instead of being held through the material code above (held, oc and r2 take the headline
+          // kernel from 119 to 123 VGPRs and make SHADE's pick path longer, 779 -> 784 instructions with 18 more v_mov: tools/wave_codegen.py)
           if (LDS_SCENE == 4) {
             const DevSphere *sp = spheres + si;
             asm volatile("" : "+v"(sp));  // a fresh load, not the registers of the first one
@@ -269,14 +270,18 @@
           depth--;
           if ((depth & DEPTH_MASK) == 0) path_done = true;  // ray_color(.., 0) = black
         }
+        // The next ray is written over the old one whether the path goes on or not, so that the old one dies at its last use above and
+        // the two are not both held through the material code.  A lane whose path ends here enters GEN, which sets o, d, thr, time and
+        // depth before its start_ray; while it waits there inactive (a slot outside the image, no work left) it reads none of them; the
+        // hand-over to a stealing wave stores sum, pos and n only.  For a miss shaded here p == o and nd == d.
+        if (SHADE_RAY_IN_PLACE) o = p, d = nd;
         if (path_done) {
           n++;
           state = ST_GEN;
         } else {
           c_rays++;
           pix_rays++;
-          o = p;
-          d = nd;
+          if (!SHADE_RAY_IN_PLACE) o = p, d = nd;
           start_ray(fast_root_word);
         }
   };
@@ -497,6 +502,17 @@
       bool active = false;
       if (state == ST_GEN) {
         active = true;
+        // fast traversal: a walk that ended without a hit left its marker (fast_go).  The sample is closed here, before anything below looks
+        // at sum, sq or n: background (camera.rs:257), sample done.  thr is the missed ray's: nothing writes it between the walk and this visit.
+        if (LDS_SCENE == 4 && pc == FAST_MISSED) {
+          if constexpr (MOMENTS) {
+            const D3 c = thr * ld3(cam.background);
+            sum = sum + c;
+            sq = sq + c * c;
+          } else sum = sum + thr * ld3(cam.background);
+          n++;
+          pc = 0;
+        }
         if (STEAL && P.steal_state && have_pixel && n < spp) {  // a sample boundary: has a wave without work asked for this pixel?
           const size_t pix = (size_t)pr * W + px;
           if (__atomic_load_n(&P.steal_state[pix], __ATOMIC_RELAXED) == 1u) {
@@ -629,7 +645,8 @@
           c_rays++;
           pix_rays++;
           if (STATS) c_cam_rays++;
-          // the pixel's entry word: read and used up here, so that it is not held across blocks (the kernel sits at 128 VGPRs)
+          // the pixel's entry word: read and used up here, and not loaded ahead of the block pass above: held across it, the word makes GEN's pick
+          // path longer (382 -> 408 instructions) and the stealing instantiation spill 109 SGPRs instead of 97
           start_ray(LDS_SCENE == 4 && P.pixel_entry ? P.pixel_entry[(size_t)pr * W + px] : fast_root_word);
         }
       }
