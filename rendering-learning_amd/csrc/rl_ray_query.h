@@ -305,22 +305,6 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_fast_kernel
   if ((tid & 63) == 0 && v) atomicAdd(&P.stats[7], v);
 }
 
-__device__ __forceinline__ void rtc_query_flush(const RtcFullCounters &cnt, unsigned long long *stats, int tid) {
-  unsigned long long v;
-  v = wave_sum(cnt.rays);
-  if ((tid & 63) == 0) atomicAdd(&stats[0], v);
-  v = wave_sum(cnt.nodes);
-  if ((tid & 63) == 0) atomicAdd(&stats[1], v);
-  v = wave_sum(cnt.spheres);
-  if ((tid & 63) == 0) atomicAdd(&stats[2], v);
-  v = wave_sum(cnt.tris);
-  if ((tid & 63) == 0) atomicAdd(&stats[3], v);
-  v = wave_sum(cnt.enters);
-  if ((tid & 63) == 0) atomicAdd(&stats[4], v);
-  v = wave_sum(cnt.flagged);
-  if ((tid & 63) == 0 && v) atomicAdd(&stats[6], v);
-}
-
 // A ray with more than RL_RTC_K intersections is flagged, as in the renders; its count is then RL_RTC_K.
 template <int NT, int REGS_FOR>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtc_intersect_rays_kernel(RtcFullParams F, RayQuery Q) {
@@ -332,9 +316,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(REGS_FOR) rtc_intersect_rays_k
     const rl_ray &ray = Q.rays[idx];
     cnt.rays++;
     uint32_t n = rtc_intersect_all(F, P.ops, P.tris, ld3(ray.origin), ld3(ray.dir), list, cnt, 1ull);
-    int hi = -1;  // intersect.rs:159-168: lowest t >= 0, later wins ties
-    for (uint32_t i = 0; i < n; i++)
-      if (list[i].t >= 0.0 && (hi < 0 || !(list[hi].t < list[i].t))) hi = (int)i;
+    int hi = rtc_first_hit(list, n);
     Q.counts[idx] = n;
     if (Q.hit_index) Q.hit_index[idx] = hi < 0 ? NONE : (uint32_t)hi;
     if (Q.isects) {

@@ -11,6 +11,8 @@
 // containers walk nor the shadow test keeps a list of its own (both are answered by rescanning the sorted entries).  The reflection / refraction tree is walked with an explicit stack of weighted rays:
 // colour is linear in the sub-rays' colours (reflectivity, transparency and the Schlick factor are scalars), so
 // total = sum over tree nodes of weight * surface colour — a reassociation of the reference's sums (ulp-level).
+// The steps of color_at are functions, each written once for the render body (rl_rtc_color_at_body.inc) and the query kernels
+// (rl_ray_query.h, rl_rtc_shade_query.h): the pointwise ones in rl_rtc_shading.h, those that read the list further down in this file.
 #pragma once
 #include "rl_rtc_kernel.h"
 
@@ -59,6 +61,22 @@ __device__ __forceinline__ uint32_t rtc_leaf_material(const RtcFullParams &F, co
 struct RtcFullCounters {
   unsigned long long rays, nodes, tris, spheres, enters, flagged;
 };
+// One atomic per wave and counter, at the end of every kernel that counts with RtcFullCounters
+__device__ __forceinline__ void rtc_query_flush(const RtcFullCounters &cnt, unsigned long long *stats, int tid) {
+  unsigned long long v;
+  v = wave_sum(cnt.rays);
+  if ((tid & 63) == 0) atomicAdd(&stats[0], v);
+  v = wave_sum(cnt.nodes);
+  if ((tid & 63) == 0) atomicAdd(&stats[1], v);
+  v = wave_sum(cnt.spheres);
+  if ((tid & 63) == 0) atomicAdd(&stats[2], v);
+  v = wave_sum(cnt.tris);
+  if ((tid & 63) == 0) atomicAdd(&stats[3], v);
+  v = wave_sum(cnt.enters);
+  if ((tid & 63) == 0) atomicAdd(&stats[4], v);
+  v = wave_sum(cnt.flagged);
+  if ((tid & 63) == 0 && v) atomicAdd(&stats[6], v);
+}
 
 __device__ __forceinline__ void ent_push(Ent *list, uint32_t &n, double t, uint32_t leaf, uint32_t chain, D3 normal, RtcFullCounters &cnt) {
   if (n < RL_RTC_K) {
@@ -390,6 +408,59 @@ __device__ __forceinline__ bool rtc_are_equal(double a, double b) {  // math/uti
   unsigned long long au = (unsigned long long)__double_as_longlong(a), bu = (unsigned long long)__double_as_longlong(b);
   unsigned long long diff = au > bu ? au - bu : bu - au;
   return diff <= 8;
+}
+
+// ---- The steps of color_at that read a ray's sorted list, written once for the color_at body (rl_rtc_color_at_body.inc) and the query
+// kernels (rl_ray_query.h, rl_rtc_shade_query.h); the pointwise steps are in rl_rtc_shading.h.
+
+// hit() (intersect.rs:159-168): lowest t >= 0, later wins ties; -1 for none
+__device__ __forceinline__ int rtc_first_hit(const Ent *list, uint32_t n) {
+  int hi = -1;
+  for (uint32_t i = 0; i < n; i++)
+    if (list[i].t >= 0.0 && (hi < 0 || !(list[hi].t < list[i].t))) hi = (int)i;
+  return hi;
+}
+
+// The containers walk of prepare_computations (intersect.rs:72-99) for the hit h of list[0 .. n): n1 / n2 keep the caller's values where
+// the walk leaves the containers empty, and when h is not found in the list
+__device__ __forceinline__ void rtc_refractive_indices(const RtcFullParams &F, const DevTri *tris, const Ent *list, uint32_t n, const Ent &h,
+                                                       double &n1, double &n2) {
+  const RtcParams &P = F.R;
+  uint32_t is = 0;
+  while (is < n && !(rtc_are_equal(list[is].t, h.t) && list[is].leaf == h.leaf)) is++;
+  if (is < n) {
+    uint32_t c1 = rtc_last_container(list, is), c2 = rtc_last_container(list, is + 1);
+    if (c1 != NONE) n1 = P.materials[rtc_leaf_material(F, tris, c1)].refractive_index;
+    if (c2 != NONE) n2 = P.materials[rtc_leaf_material(F, tris, c2)].refractive_index;
+  }
+}
+
+// The fold of World::shadow_attenuation (world.rs:110-125) over a shadow ray's sorted list: the product of the transparencies of the
+// entries with 0 < t < distance, up to the first object seen twice
+__device__ __forceinline__ double rtc_shadow_product(const RtcFullParams &F, const DevTri *tris, const Ent *list, uint32_t ns, double distance) {
+  const RtcParams &P = F.R;
+  double shadow_att = 1.0;
+  for (uint32_t i = 0; i < ns; i++) {
+    if (!(list[i].t > 0.0 && list[i].t < distance)) continue;
+    bool dup = false;  // take_while(seen.insert): every earlier in-range entry is in `seen`
+    for (uint32_t k = 0; k < i; k++) dup |= list[k].t > 0.0 && list[k].t < distance && list[k].leaf == list[i].leaf;
+    if (dup) break;
+    shadow_att = shadow_att * P.materials[rtc_leaf_material(F, tris, list[i].leaf)].transparency;
+  }
+  return shadow_att;
+}
+
+// World::shadow_attenuation(&point, light) (world.rs:104-126); the list is scratch for the shadow ray's intersections, mult the number
+// of times the reference traces this shadow ray (Pending::mult; 1 for a query)
+__device__ __forceinline__ double rtc_shadow_walk(const RtcFullParams &F, const DevOp *ops, const DevTri *tris, D3 point, D3 lpos, Ent *list,
+                                                  RtcFullCounters &cnt, unsigned long long mult) {
+  D3 v = lpos - point;
+  double distance = mag(v);
+  D3 sdir;
+  if (!norm(v, sdir)) return 1.0;
+  cnt.rays += mult;
+  uint32_t ns = rtc_intersect_all(F, ops, tris, point, sdir, list, cnt, mult);
+  return rtc_shadow_product(F, tris, list, ns, distance);
 }
 
 // Pending reflection / refraction rays of one camera ray, walked depth-first: a ray with `remaining` bounces left pushes at most

@@ -46,16 +46,4 @@
     double *outp = P.out + idx * 3;
     outp[0] = res.x, outp[1] = res.y, outp[2] = res.z;
   }
-  unsigned long long v;
-  v = wave_sum(cnt.rays);
-  if ((tid & 63) == 0) atomicAdd(&P.stats[0], v);
-  v = wave_sum(cnt.nodes);
-  if ((tid & 63) == 0) atomicAdd(&P.stats[1], v);
-  v = wave_sum(cnt.spheres);
-  if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
-  v = wave_sum(cnt.tris);
-  if ((tid & 63) == 0) atomicAdd(&P.stats[3], v);
-  v = wave_sum(cnt.enters);
-  if ((tid & 63) == 0) atomicAdd(&P.stats[4], v);
-  v = wave_sum(cnt.flagged);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
+  rtc_query_flush(cnt, P.stats, tid);

@@ -1,8 +1,10 @@
 // RTC hot path on gfx950: Camera::render / rays_for_pixel (scene/camera.rs:63-124), World::color_at
 // (world.rs:89-102), World::intersect + hit (world.rs:46-55, intersect.rs:159-172), Transformed /
 // Bounded / Group / Triangle intersect (object/{transformed,bounded,group,triangle}.rs),
-// prepare_computations (intersect.rs:48-115), shade_hit + shadow_attenuation (world.rs:57-126),
-// lighting (material.rs:54-90).
+// prepare_computations (intersect.rs:48-115), shade_hit + shadow_attenuation (world.rs:57-126).
+// lighting (material.rs:54-90) is rtc_lighting of rl_rtc_shading.h, the function the full kernel and the
+// shading queries call; this kernel's prepare_computations is its own text (no under_point, no reflect_v:
+// neither is read here, and the shared function's reflect_v fallback counts `flagged`).
 //
 // The reference gathers every intersection into a Vec, stable-sorts by t and picks the lowest t >= 0
 // with "later wins" on ties.  That selection equals a single pass in evaluation order that replaces
@@ -18,6 +20,7 @@
 #define RL_KERNEL_ALIGN __attribute__((aligned(65536)))
 #endif
 #include "rl_device.h"
+#include "rl_rtc_shading.h"  // mag, norm, reflect; rtc_lighting and the other pointwise steps of color_at
 
 namespace rl {
 
@@ -66,15 +69,6 @@ __device__ __forceinline__ D3 mul_vec(const double *m, D3 p) {
   }
   return D3{o[0], o[1], o[2]};
 }
-__device__ __forceinline__ double mag(D3 v) { return sqrt(v.x * v.x + v.y * v.y + v.z * v.z); }  // vector.rs:32
-// vector.rs:36-43 / 142-156: TRUE division by the magnitude; false when the magnitude is 0
-__device__ __forceinline__ bool norm(D3 v, D3 &out) {
-  double m = mag(v);
-  if (m == 0.0) return false;
-  out = D3{v.x / m, v.y / m, v.z / m};
-  return true;
-}
-__device__ __forceinline__ D3 reflect(D3 v, D3 n) { return v - (n * 2.0) * dot(v, n); }  // vector.rs:57-59
 
 struct RtcCounters {
   unsigned long long rays, nodes, tris, enters, flagged;

@@ -93,24 +93,7 @@
               RtcHit dummy{INF, NONE, 0u, d3(0.0, 0.0, 0.0)};
               shadow_att = rtc_traverse<true>(P, ops, tris, guards, over_point, sdir, distance, dummy, cnt);
             }
-            // lighting (material.rs:54-90)
-            D3 effective = object_color * intensity;
-            D3 lightv;
-            if (!norm(lpos - point, lightv)) lightv = d3(0.0, 0.0, 0.0);
-            D3 ambient = effective * m.ambient;
-            double ldn = dot(lightv, normal_v);
-            D3 diffuse = d3(0.0, 0.0, 0.0), specular = d3(0.0, 0.0, 0.0);
-            if (!(ldn < 0.0)) {
-              D3 diff = (effective * m.diffuse) * ldn;
-              D3 reflectv = -reflect(lightv, normal_v);
-              double rde = dot(reflectv, eye_v);
-              diffuse = diff * shadow_att;
-              if (!(rde <= 0.0)) {
-                double factor = pow(rde, m.shininess);
-                specular = intensity * (m.specular * factor * shadow_att);
-              }
-            }
-            D3 surface = (ambient + diffuse) + specular;
+            D3 surface = rtc_lighting(m, point, object_color, lpos, intensity, eye_v, normal_v, shadow_att);
             // reflectivity == transparency == 0 on this path: surface + (black + black)
             D3 col = surface + (d3(0.0, 0.0, 0.0) + d3(0.0, 0.0, 0.0));
             lsum = (li == 0) ? col : lsum + col;
