@@ -46,7 +46,7 @@ extern "C" {
 #define RL_E_DEVICE (-3)      /* HIP runtime error (text in rl_last_error) */
 #define RL_E_UNSUPPORTED (-4) /* scene uses a feature this build has no kernel for */
 #define RL_E_DEGENERATE (-5)  /* a reference panic site was reached; output is written, stats.flagged > 0 */
-#define RL_E_NOMEM (-6)
+#define RL_E_NOMEM (-6)       /* the host ran out of memory, e.g. while compiling a scene description; nothing was created */
 
 /* ------------------------------------------------------------------ lifetime */
 /* device < 0: keep the process's current HIP device.  One GPU (use this form for one process per GPU, e.g. under
@@ -223,6 +223,36 @@ typedef struct rl_rtiow_camera {
   double background[3];
   uint64_t seed;
 } rl_rtiow_camera;
+
+/* What a description must keep.  Both *_scene_create validate the whole description on the host before any device sees it (every
+ * kernel trusts the compiled program); one that breaks a rule below gives NULL, with the code in the second column behind
+ * rl_last_error()'s text.  Sharing is legal (one record referenced from many places: every reference is lowered again), cycles
+ * are not.  The cost of a refusal is bounded by the size of the description, never by the size of its expansion, and the
+ * compilers use a constant amount of stack whatever the depth of the graph.
+ *   every array with a non-zero count is non-NULL; every index lies inside its table; every kind is a known one
+ *                                                                         RL_E_INVALID
+ *   no hittable / object contains itself                                  RL_E_INVALID  "cycle through ..."
+ *   deepest reference below the root (RTC: below a world object), the
+ *   root being 0, at most RL_SCENE_MAX_NEST                               RL_E_INVALID  "scene graph too deep"
+ *   ops of the expanded program, its end op included, fewer than
+ *   RL_SCENE_MAX_OPS (a sphere, planar, triangle, shape, BVH node or
+ *   Bounded is one op, a Translate / Transform / Transformed /
+ *   ConstantMedium two, a CSG three; lists and groups none.  RTC counts
+ *   every triangle reference as one op although the program merges
+ *   consecutive triangles into one: there the limit bounds the count
+ *   from above, not the program's final size)                             RL_E_INVALID  "program too large"
+ *   RTIOW: Translate / Transform nested at most 8 deep                    RL_E_INVALID
+ *          Checker textures acyclic, nested at most 32 deep               RL_E_INVALID
+ *          no ConstantMedium inside a ConstantMedium's boundary           RL_E_INVALID
+ *          n_spheres <= 0x3FFFFFFF; a BVH node has 1 or 2 children        RL_E_INVALID
+ *   RTC:   Transformed nested at most 8 deep, CSG at most 4 deep          RL_E_INVALID
+ *          at most 0xFFFF lights                                          RL_E_UNSUPPORTED
+ *          max_reflection_depth <= 7 in a world with shapes, CSG,
+ *          patterns, or reflective / transparent materials                RL_E_UNSUPPORTED
+ *   the host has the memory for the compiled program                      RL_E_NOMEM
+ * Not checked: that an array is as long as its count says, cameras, non-finite or degenerate geometry. */
+#define RL_SCENE_MAX_NEST 100000u
+#define RL_SCENE_MAX_OPS 0x7FFFFFFFu
 
 rl_scene *rl_rtiow_scene_create(const rl_rtiow_scene_desc *desc);
 
@@ -413,6 +443,7 @@ typedef struct rl_rtc_camera { /* scene/camera.rs:11-19: the derived fields + tr
   double pixel_size, half_width, half_height;
 } rl_rtc_camera;
 
+/* The limits a description must keep and the codes of a refusal: see rl_rtiow_scene_create. */
 rl_scene *rl_rtc_scene_create(const rl_rtc_scene_desc *desc);
 
 /* Replaces Camera::render(&world, &RenderOpts{anti_aliasing_samples}) (scene/camera.rs:93).

@@ -200,7 +200,9 @@ struct FastGeneral {
 };
 bool build_fast_general(const rl_rtiow_scene_desc &d, const RtiowProgram &rt, FastGeneral &out);
 
-// Returns RL_OK or RL_E_INVALID (err filled).
+// Returns RL_OK or RL_E_INVALID (err filled).  compile_rtiow and compile_rtc (below) THROW std::bad_alloc when the host has no memory for the
+// program (its exact size is reserved before lowering starts): call them through build_host_rtiow / build_host_rtc (rl_scene_host.h), which
+// turn that into RL_E_NOMEM, never directly from behind the C ABI.
 int compile_rtiow(const rl_rtiow_scene_desc &d, RtiowProgram &out, std::string &err);
 
 // ---------------------------------------------------------------- RTC

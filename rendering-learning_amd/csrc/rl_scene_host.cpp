@@ -7,6 +7,8 @@
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <new>
+#include <stdexcept>
 
 namespace rl {
 
@@ -132,7 +134,7 @@ static void flatten_sphere_materials(const RtiowProgram &rt, std::vector<DevMate
   }
 }
 
-int build_host_rtiow(const rl_rtiow_scene_desc *desc, std::shared_ptr<const HostRtiow> &out, std::string &err) {
+static int build_host_rtiow_may_throw(const rl_rtiow_scene_desc *desc, std::shared_ptr<const HostRtiow> &out, std::string &err) {
   auto H = std::make_shared<HostRtiow>();
   if (compile_rtiow(*desc, H->rt, err) != RL_OK) return RL_E_INVALID;
   const RtiowProgram &rt = H->rt;
@@ -238,7 +240,7 @@ static void build_rtc_guards(RtcProgram &rc, std::vector<RtcGuard> &guards) {
     }
 }
 
-int build_host_rtc(const rl_rtc_scene_desc &desc, std::shared_ptr<const HostRtc> &out, std::string &err) {
+static int build_host_rtc_may_throw(const rl_rtc_scene_desc &desc, std::shared_ptr<const HostRtc> &out, std::string &err) {
   auto H = std::make_shared<HostRtc>();
   if (compile_rtc(desc, H->rc, err) != RL_OK) return RL_E_INVALID;
   if (H->rc.lights.size() > 0xFFFFu) {
@@ -254,6 +256,32 @@ int build_host_rtc(const rl_rtc_scene_desc &desc, std::shared_ptr<const HostRtc>
   build_rtc_guards(H->rc, H->guards);  // both kernels walk them (the full kernel with the unbounded line test)
   out = H;
   return RL_OK;
+}
+
+// The entry points are called from behind a C ABI: nothing may be thrown through them.  Every container above is a std::vector sized by
+// the caller's description, so running out of memory is an outcome like any other refusal.
+template <class Build>
+static int no_throw(Build build, std::string &err) {
+  try {
+    return build();
+  } catch (const std::bad_alloc &) {
+    err = "out of memory while compiling the scene";
+    return RL_E_NOMEM;
+  } catch (const std::exception &e) {
+    err = std::string("scene compiler: ") + e.what();
+    return RL_E_INVALID;
+  } catch (...) {
+    err = "scene compiler: unknown exception";
+    return RL_E_INVALID;
+  }
+}
+
+int build_host_rtiow(const rl_rtiow_scene_desc *desc, std::shared_ptr<const HostRtiow> &out, std::string &err) {
+  return no_throw([&] { return build_host_rtiow_may_throw(desc, out, err); }, err);
+}
+
+int build_host_rtc(const rl_rtc_scene_desc &desc, std::shared_ptr<const HostRtc> &out, std::string &err) {
+  return no_throw([&] { return build_host_rtc_may_throw(desc, out, err); }, err);
 }
 
 // ------------------------------------------------------------------ the structure report

@@ -38,7 +38,9 @@ struct HostRtc {
 };
 static const size_t RTC_LDS_SCENE_MAX = 65536;
 
-// Both return RL_OK, or the code the entry point hands on (RL_E_INVALID / RL_E_UNSUPPORTED) with `err` filled; `out` is set on RL_OK only.
+// Both return RL_OK, or the code the entry point hands on (RL_E_INVALID / RL_E_UNSUPPORTED / RL_E_NOMEM) with `err` filled; `out` is set on
+// RL_OK only.  Neither throws (they are called from behind the C ABI), and neither recurses over the caller's graph: the limits a
+// description must keep are listed in include/rl_render.h beside rl_rtiow_scene_create.
 // RTIOW: validate + lower the graph, link the ops, flatten the materials, build the fast structures.
 int build_host_rtiow(const rl_rtiow_scene_desc *desc, std::shared_ptr<const HostRtiow> &out, std::string &err);
 // RTC: lower the graph, refuse what the device kernels have no room for (lights, pending rays), build the triangle guards.
