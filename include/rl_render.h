@@ -998,6 +998,27 @@ int rl_rtc_lighting(const rl_scene *, const rl_rtc_comps *comps, const double *l
 int rl_rtc_lighting_device(const rl_scene *, const void *d_comps, const void *d_light_positions, const void *d_light_intensities,
                            const void *d_shadow_att, uint64_t n, void *d_out_rgb, void *hip_stream);
 
+/* =====================================================================
+ *  RTIOW occlusion queries: any-hit visibility for ray buffers
+ * =====================================================================
+ *   rl_rtiow_occluded_rays*  <- ray-tracing-one-weekend/src/hittable/mod.rs:42  Hittable::hit(&Ray, &Interval).is_some() on the scene root
+ * "Is anything in the way": shadow rays towards a light the host samples itself, ambient occlusion, visibility between probes, picking.
+ * out_occluded[i] = 1 where world.hit(&rays[i], &Interval{min: tmin, max: tmax}) is Some, else 0: the value of `hit` in the record
+ * rl_rtiow_hit_rays writes for the same ray and interval, at one byte per ray.  The interval is closed at both ends, as rl_rtiow_hit_rays
+ * treats it.  Rays are used as given, so an unnormalised dir = target - origin with tmax = 1 is the segment test between the two points
+ * (tmin = 1e-10 keeps the origin's own surface out, as camera.rs:242-245 does).
+ * With opt_stats the call is counting: it runs the reference-order fold, and every counter, flagged included, is bit for bit that of
+ * rl_rtiow_hit_rays on the same batch.  Without opt_stats it is counter-free and, with tmin == 1e-10, may be served by an any-hit tree
+ * walk that stops at the first primitive that is certainly hit and evaluates no normal of its own: flagged and RL_E_DEGENERATE then
+ * come only from the rays that walk handed to the reference's fold (roots next to tmax, grazing / edge hits, far spheres, rays outside
+ * the filter's range), so a panic site on a ray the walk decided by itself goes unreported; the bytes are the same either way.
+ * Rules: those of rl_rtiow_hit_rays — n = 0 touches no buffer and zeroes opt_stats; NULL buffers with n > 0, n > 2^40, a NaN bound or an
+ * RTC scene: RL_E_INVALID; a scene with ConstantMedium objects: RL_E_UNSUPPORTED (there is no seeded form of this call).  The _device
+ * form is asynchronous unless opt_stats is given; status, concurrency and rl_init_multi: as stated for the batched ray queries. */
+int rl_rtiow_occluded_rays(const rl_scene *, const rl_ray *rays, uint64_t n, double tmin, double tmax, uint8_t *out_occluded, rl_stats *opt_stats);
+int rl_rtiow_occluded_rays_device(const rl_scene *, const void *d_rays, uint64_t n, double tmin, double tmax, void *d_out_occluded,
+                                  void *hip_stream, rl_stats *opt_stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,3 +8,5 @@ from .api import (Adaptive, AtrousParams, Camera, CameraParams, Canvas, Features
                   denoise_atrous, denoise_atrous_pass_device, denoise_render, init, output_ppm, rtc_camera)
 from .api import (DenoiseInputs, denoise_finish_device, denoise_inputs, denoise_prepare_device, denoise_render_device, denoise_render_gpu,  # noqa: F401
                   denoise_render_work_bytes)
+from . import occlusion  # noqa: F401
+from .occlusion import occluded_rays, occluded_rays_device  # noqa: F401

@@ -238,6 +238,8 @@ RENDER_SIGNATURES = {
     "rl_rtc_shadow_attenuation_device": (_I, [_P, _P, _P, _U64, _P, _P, _STATS]),
     "rl_rtc_lighting": (_I, [_P, _P, _P, _P, _P, _U64, _P]),
     "rl_rtc_lighting_device": (_I, [_P, _P, _P, _P, _P, _U64, _P, _P]),
+    "rl_rtiow_occluded_rays": (_I, [_P, _P, _U64, _D, _D, _P, _STATS]),
+    "rl_rtiow_occluded_rays_device": (_I, [_P, _P, _U64, _D, _D, _P, _P, _STATS]),
     "rl_rtiow_render_pixels": (_I, [_P, _CAM, _U64, _P, _P, _U64, _P, _STATS]),
     "rl_rtiow_render_pixels_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _P, _P, _STATS]),
     "rl_rtc_render_pixels": (_I, [_P, _RTC_CAM, _U32, _P, _P, _U64, _P, _STATS]),
@@ -620,7 +622,8 @@ def last_query():
     ("features_fast" / "features_reference") and, for a synchronous call, how many of its rays the fast walk re-traced in the reference's order."""
     out = (C.c_uint64 * 2)()
     _check(render_lib().rl_debug_last_query(out))
-    return {"kernel": {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast"}.get(int(out[0]), "none"), "retraced": int(out[1])}
+    names = {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast", 5: "occlusion_reference", 6: "occlusion_fast"}
+    return {"kernel": names.get(int(out[0]), "none"), "retraced": int(out[1])}
 
 
 def set_denoise_route(route):

@@ -32,6 +32,7 @@
 #include "rl_material_query.h"
 #include "rl_rtc_shade_query.h"
 #include "rl_rtiow_features.h"
+#include "rl_occlusion_query.h"
 
 using namespace rl;
 
@@ -1460,3 +1461,4 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 #include "rl_features_api.h"
 #include "rl_denoise.h"
 #include "rl_denoise_render.h"
+#include "rl_occlusion_api.h"  // behind everything: its kernels are instantiated last, every earlier kernel keeps its place

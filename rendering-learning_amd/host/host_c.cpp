@@ -494,6 +494,19 @@ int rlh_ray_query_probe(int which, const rl_ray *rays, uint64_t n, double tmin, 
     return -1;
   }
 }
+// Occlusion queries through the C++ mirror: rtiow::occluded_rays on golden_test_scene with Interval{tmin, tmax}, out = n bytes.
+// 0 or -1 (rlh_last_error).
+int rlh_occlusion_probe(const rl_ray *rays, uint64_t n, double tmin, double tmax, void *out) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    std::vector<uint8_t> h = rtiow::occluded_rays(*s.world, rays, (size_t)n, rtiow::Interval{tmin, tmax});
+    std::memcpy(out, h.data(), h.size());
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // Seeded path queries through the C++ mirror on golden_test_scene and its camera.  which = 0: Camera::get_rays for pixels (i % W, 0),
 // out = n rl_ray; which = 1: rtiow::ray_color_rays of `rays`, out = n * 3 doubles.  cursors are advanced in place.  0 or -1 (rlh_last_error).
 int rlh_path_query_probe(int which, const rl_ray *rays, rl_rng_cursor *cursors, uint64_t n, void *out) {

@@ -160,6 +160,18 @@ std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t 
   if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_hit_rays: ") + rl_last_error());
   return out;
 }
+std::vector<uint8_t> occluded_rays(const Hittable &world, const rl_ray *rays, size_t n, Interval ray_t) {  // hittable/mod.rs:42 .is_some()
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  std::vector<uint8_t> out(n);
+  int rc = rl_rtiow_occluded_rays(sc, rays, n, ray_t.min, ray_t.max, out.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK && rc != RL_E_DEGENERATE) throw std::runtime_error(std::string("rl_rtiow_occluded_rays: ") + rl_last_error());
+  return out;
+}
 std::vector<rl_rtiow_hit> hit_rays_seeded(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed,
                                           Interval ray_t) {  // hittable/mod.rs:42 with constant_medium.rs:27-80
   Flattened f;

@@ -675,7 +675,12 @@ struct DeviceBvh : Hittable {
 // world.hit(&rays[i], &ray_t), out[i].hit == 0 for None.  Throws on any error but RL_E_DEGENERATE (host_render.cpp).
 std::vector<rl_rtiow_hit> hit(const Hittable &world, const rl_ray *rays, size_t n, Interval ray_t);
 
-// The same for rays that carry an RNG cursor (rl_rtiow_hit_rays_seeded): worlds with ConstantMedium objects are served, the free path of
+// world.hit(&rays[i], &ray_t).is_some() for a batch of rays, on the GPU (rl_rtiow_occluded_rays): out[i] is 1 where something lies in the
+// interval, the `hit` field of hit()'s record at one byte per ray.  dir = target - origin with ray_t.max = 1 tests the segment between
+// two points.  Throws on any error but RL_E_DEGENERATE.
+std::vector<uint8_t> occluded_rays(const Hittable &world, const rl_ray *rays, size_t n, Interval ray_t);
+
+// The same as hit() for rays that carry an RNG cursor (rl_rtiow_hit_rays_seeded): worlds with ConstantMedium objects are served, the free path of
 // every medium the fold evaluates drawn from cursors[i] of `seed` (constant_medium.rs:55); cursors[i] is advanced behind the draws, and
 // stays as it is where none was taken.  Throws on any error but RL_E_DEGENERATE.
 std::vector<rl_rtiow_hit> hit_rays_seeded(const Hittable &world, const rl_ray *rays, rl_rng_cursor *cursors, size_t n, uint64_t seed, Interval ray_t);
