@@ -65,6 +65,7 @@ struct Switches {
   size_t indep_cap = (size_t)1 << 30;  // RL_INDEP_CAP_MB=<MiB>: cap of that mode's pass buffer (a smaller one forces more passes: tests)
   int pixel_entry = rl::PIXEL_ENTRY_DEFAULT;  // RL_PIXEL_ENTRY=0|1|2|3: the fast kernel's camera rays start at the root / at their pixel's entry cut of up to n entries (rl_pixel_entry.h)
   bool pixel_entry_sphere = true;  // RL_PIXEL_ENTRY_SPHERE=0: that cut keeps every leaf whose BOX the pixel's beam touches; default: only those whose sphere it may touch
+  bool coop_quad = true;         // RL_COOP_QUAD=0: the wave kernels' block passes lane-per-block only and FILL per lane (default: thin passes four lanes to a block, FILL wave-wide)
 } g_sw;
 std::atomic<unsigned long long> g_last_slow_traces{0};  // rl_debug_slow_traces.  Atomic: rl_render_status of two scenes runs under two locks.
 // rl_debug_last_rtc_launch: the most recent rtc_render_launch of this process (kernel 0: none yet)
@@ -105,6 +106,7 @@ void read_switches() {
   if (const char *v = std::getenv("RL_INDEP_K")) w.indep_k = (unsigned)std::max(1, std::atoi(v));
   if (const char *v = std::getenv("RL_PIXEL_ENTRY")) w.pixel_entry = std::min(3, std::max(0, std::atoi(v)));
   if (const char *v = std::getenv("RL_PIXEL_ENTRY_SPHERE")) w.pixel_entry_sphere = std::string(v) != "0";
+  if (const char *v = std::getenv("RL_COOP_QUAD")) w.coop_quad = std::string(v) != "0";
   if (const char *v = std::getenv("RL_INDEP_CAP_MB")) w.indep_cap = (size_t)std::max(1, std::atoi(v)) << 20;
   g_sw = w;
 }
@@ -461,6 +463,7 @@ static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, 
   P.k8u = 8.8817841970012523e-16;
   P.tune[0] = g_sw.tune[0], P.tune[1] = g_sw.tune[1], P.tune[2] = g_sw.tune[2], P.tune[3] = g_sw.tune[3];
   P.pix_rays = want_stats ? scene->d_pix_rays : nullptr;
+  P.coop_quad = g_sw.coop_quad ? 1u : 0u;
   return RL_OK;
 }
 

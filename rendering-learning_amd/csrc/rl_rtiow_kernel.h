@@ -101,6 +101,9 @@ struct RtiowParams {
   uint32_t *out_count;
   rl_rtiow_adaptive adapt;
   uint32_t adapt_total;
+  // wave kernels (rl_rtiow_wave.h Ring::coop_blocks): non-zero = thin block passes run four lanes to a block and FILL generates wave-wide;
+  // 0 (RL_COOP_QUAD=0) = lane-per-block passes only, FILL per lane.  Same blocks in the same ring slots either way.
+  uint32_t coop_quad;
 };
 
 // MOMENTS, the compile-time flavour of the chained render kernels that keeps second moments (P.out_sq), is `false` in every kernel without
@@ -193,6 +196,59 @@ __device__ __forceinline__ void chacha8_block_to_lds_job(const uint32_t *key, Jo
   s_rng[5 * NT + tid] = (unsigned long long)x10 | ((unsigned long long)x11 << 32);
   s_rng[6 * NT + tid] = (unsigned long long)x12 | ((unsigned long long)x13 << 32);
   s_rng[7 * NT + tid] = (unsigned long long)x14 | ((unsigned long long)x15 << 32);
+}
+// Four lanes to a block (rl_rtiow_wave.h Ring::coop_blocks, a thin pass: at most a quarter of the wave's lanes have a job).  Lane
+// q = lane & 3 of a quad holds column q of the state, a = x[q], b = x[4 + q], c = x[8 + q], d = x[12 + q], so the column round is ONE
+// quarter round per lane; the diagonal round is the same quarter round with rows b, c, d turned by 1, 2, 3 lanes inside the quad
+// (DPP quad_perm, no LDS traffic), and turned back after it.  A double round is 24 + 6 instructions before the compiler folds turns into
+// the adds and xors that read them, against 96 of the lane-per-block form: a pass costs about a third and serves 16 blocks instead of 64.
+// MUST run with all four lanes of every quad enabled (the callers run it with full exec; a quad without a job computes and discards).
+// `job()` as above, but called once; d_in is the lane's word of the last row: {counter, 0, stream low, stream high}[q].  Word w of the
+// block goes where the lane-per-block form puts it: u64 slot w >> 1, half w & 1 of the requester's column `tid` in s_rng.
+struct ChachaQuadJob {
+  uint32_t q;     // lane & 3
+  uint32_t d_in;  // input word 12 + q
+  unsigned long long *s_rng;
+  int tid;
+  bool store;
+};
+template <int CTRL>
+__device__ __forceinline__ uint32_t quad_perm(uint32_t v) {  // CTRL = s0 | s1 << 2 | s2 << 4 | s3 << 6: lane k of a quad reads lane s_k
+  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, CTRL, 0xF, 0xF, true);
+}
+template <int NT, bool ROLLED, class Job>
+__device__ __forceinline__ void chacha8_quad_block_to_lds_job(const uint32_t *key, Job job) {
+  auto column = [&](uint32_t q, uint32_t &a, uint32_t &b, uint32_t &c) {  // input words q, 4 + q, 8 + q
+    // (the four words pass through an empty asm as scalars: a plain select of key[..] compiles to a VECTOR load from the kernel
+    // arguments at a selected address, and plain constants are held in four VGPRs through the whole scheduler loop)
+    auto sel4 = [&](uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) {
+      asm volatile("" : "+s"(w0), "+s"(w1), "+s"(w2), "+s"(w3));
+      return (q & 2u) ? ((q & 1u) ? w3 : w2) : ((q & 1u) ? w1 : w0);
+    };
+    a = sel4(0x61707865u, 0x3320646eu, 0x79622d32u, 0x6b206574u);
+    b = sel4(key[0], key[1], key[2], key[3]);
+    c = sel4(key[4], key[5], key[6], key[7]);
+  };
+  // the job is derived ONCE and its four input words are held through the rounds for the feed-forward: with four state words instead of
+  // sixteen the pass still needs eight registers fewer than the lane-per-block form, and a second derivation is a third of the pass
+  const ChachaQuadJob j = job();
+  uint32_t ia, ib, ic;
+  column(j.q, ia, ib, ic);
+  uint32_t a = ia, b = ib, c = ic, d = j.d_in;
+#pragma unroll(ROLLED ? 1 : 4)
+  for (int r = 0; r < 4; r++) {
+    RL_QR(a, b, c, d)
+    b = quad_perm<0x39>(b), c = quad_perm<0x4E>(c), d = quad_perm<0x93>(d);  // lane q now holds x[4 + (q+1)%4], x[8 + (q+2)%4], x[12 + (q+3)%4]
+    RL_QR(a, b, c, d)
+    b = quad_perm<0x93>(b), c = quad_perm<0x4E>(c), d = quad_perm<0x39>(d);
+  }
+  a += ia, b += ib, c += ic, d += j.d_in;
+  if (!j.store) return;
+  uint32_t *w = (uint32_t *)(j.s_rng + (size_t)(j.q >> 1) * NT + j.tid) + (j.q & 1u);  // word q; word 4 i + q is 2 i slots on
+  w[0 * 4 * NT] = a;
+  w[1 * 4 * NT] = b;
+  w[2 * 4 * NT] = c;
+  w[3 * 4 * NT] = d;
 }
 template <int NT, bool ROLLED = false>
 __device__ __forceinline__ void chacha8_block_to_lds(const uint32_t *key, uint32_t ctr_lo, uint64_t stream, unsigned long long *s_rng, int tid) {

@@ -48,7 +48,9 @@ namespace rl {
 // ODD (the ray-buffer kernels, rl_rng_cursor): the word position may be odd — a caller's cursor may stand anywhere in the stream, and a
 // draw is words pos, pos + 1 (rand_core BlockRng::next_u64), so an odd position reads the halves of two neighbouring u64 slots, the
 // second one possibly in the next block.  A render's positions are always even: its kernels keep the plain form.
-template <int NT, bool ROLL_HOT = true, bool ODD = false>
+// QUAD = false: coop_blocks runs lane-per-block passes only, whatever the runtime switch says (an instantiation that would spill more
+// with the four-lanes-per-block pass in it: rtiow_wave_moments_kernel<1024, 0>, rl_rtiow_wave_body.inc COOP_QUAD).
+template <int NT, bool ROLL_HOT = true, bool ODD = false, bool QUAD = true>
 struct Ring {
   const uint32_t *key;
   unsigned long long *s_rng;  // [16][NT]
@@ -88,9 +90,16 @@ struct Ring {
   // into the REQUESTER's column: 2 x 25 stream resets of a GEN block are one pass of the block function instead of two passes at
   // 40 % lane use.  Same blocks, same LDS slots as per-lane generation.  Cross-lane traffic is permutes only (no LDS allocation).
   // ONES: some lanes may want one block (else nb is 0 or 2 and one compaction serves both halves of the job list).
-  template <bool ONES>
-  __device__ __forceinline__ void coop_blocks(uint32_t nb, uint32_t first) {
-    const unsigned long long m1 = __ballot(nb != 0u), m2 = ONES ? __ballot(nb == 2u) : m1;
+  // TWOS = false: no lane wants two (FILL: nb is 0 or 1, the job list is its first half only).
+  // The pass plan (`quad`, wave-uniform: RtiowParams::coop_quad): full passes of 64 jobs, one lane per block, while more than
+  // COOP_QUAD_MAX jobs are left, and the rest in quad passes of 16 jobs, four lanes per block (chacha8_quad_block_to_lds_job).  A
+  // quad pass costs about a third of a full one (tools/wave_codegen.py prints both counts of the built kernel and the bound that
+  // follows), so a remainder of up to two quad passes is cheaper than one more full pass.  quad = false: full passes only.
+  static constexpr uint32_t COOP_QUAD_MAX = 32u;
+  // Returns the passes it ran, full | quad << 16 (wave-uniform; the STATS census counts them, nothing else reads it).
+  template <bool ONES, bool TWOS = true>
+  __device__ __forceinline__ uint32_t coop_blocks(uint32_t nb, uint32_t first, bool quad) {
+    const unsigned long long m1 = __ballot(nb != 0u), m2 = !TWOS ? 0ull : ONES ? __ballot(nb == 2u) : m1;
     const uint32_t n1 = (uint32_t)__popcll(m1), jobs = n1 + (uint32_t)__popcll(m2);
     // compaction (a forward permute): lane r receives the id of the r-th lane of mask m; the lanes outside it all send to lane 63,
     // which is then never read (it is the mask's last member only when all 64 lanes are in it)
@@ -99,33 +108,63 @@ struct Ring {
       return (uint32_t)__builtin_amdgcn_ds_permute((int)((((m >> lane) & 1ull) ? r : 63u) << 2), (int)lane);
     };
     __builtin_amdgcn_wave_barrier();  // every lane has finished reading the blocks about to be overwritten
+    uint32_t j0 = 0;
+    // the job of lane l: j0 + l in a full pass, j0 + (l >> 2) in a quad pass.  Requester, counter, stream and destination, all derived
+    // from the wave-uniform masks and the lane id — in a full pass twice (chacha8_block_to_lds_job; the empty asm makes the second
+    // derivation a new one), so that nothing but the block's 16 words is held through the rounds: the headline kernel stays within its
+    // 128 VGPRs; a quad pass holds four words and derives once
+    struct Derived {
+      uint32_t lane, c, slo, shi;
+      int tid;
+      bool store;
+    };
+    auto derive = [&](uint32_t shift) {
+      uint32_t lane = (uint32_t)tid & 63u;
+      asm volatile("" : "+v"(lane));
+      const uint32_t j = j0 + (lane >> shift);
+      const bool second = TWOS && j >= n1;
+      const int k4 = (int)((second ? j - n1 : j) << 2);
+      uint32_t req = (uint32_t)__builtin_amdgcn_ds_bpermute(k4, (int)compact(m1, lane));
+      if (ONES && TWOS) {
+        const uint32_t r2 = (uint32_t)__builtin_amdgcn_ds_bpermute(k4, (int)compact(m2, lane));
+        req = second ? r2 : req;
+      }
+      const int r4 = (int)((req & 63u) << 2);
+      const uint32_t slo = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)(uint32_t)stream);
+      const uint32_t shi = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)(uint32_t)(stream >> 32));
+      const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)first) + (second ? 1u : 0u);
+      return Derived{lane, c, slo, shi, (tid & ~63) | (r4 >> 2), j < jobs};
+    };
+    const uint32_t quad_max = QUAD && quad ? COOP_QUAD_MAX : 0u;
+    uint32_t passes = 0;
 #pragma unroll 1
-    for (uint32_t j0 = 0; j0 < jobs; j0 += 64u) {  // a second pass only when more than 64 blocks are wanted (launch start)
-      // lane l's job j0 + l: requester, counter, stream and destination, all re-derived from the wave-uniform masks and the lane id —
-      // twice (chacha8_block_to_lds_job; the empty asm makes the second derivation a new one), so that nothing but the block's 16
-      // words is held through the rounds: the headline kernel stays within its 128 VGPRs
+    for (; j0 + quad_max < jobs; j0 += 64u) {  // full passes while more than quad_max jobs are left (two of them: launch start, more than 64 blocks wanted)
+      RL_CG_MARK("FULL_B");
       auto job = [&] {
-        uint32_t lane = (uint32_t)tid & 63u;
-        asm volatile("" : "+v"(lane));
-        const uint32_t j = j0 + lane;
-        const bool second = j >= n1;
-        const int k4 = (int)((second ? j - n1 : j) << 2);
-        uint32_t req = (uint32_t)__builtin_amdgcn_ds_bpermute(k4, (int)compact(m1, lane));
-        if (ONES) {
-          const uint32_t r2 = (uint32_t)__builtin_amdgcn_ds_bpermute(k4, (int)compact(m2, lane));
-          req = second ? r2 : req;
-        }
-        const int r4 = (int)((req & 63u) << 2);
-        const uint32_t slo = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)(uint32_t)stream);
-        const uint32_t shi = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)(uint32_t)(stream >> 32));
-        const uint32_t c = (uint32_t)__builtin_amdgcn_ds_bpermute(r4, (int)first) + (second ? 1u : 0u);
-        return ChachaJob{c, ((uint64_t)shi << 32) | slo, s_rng + (size_t)(c & 1u) * 8 * NT, (tid & ~63) | (r4 >> 2), j < jobs};
+        const Derived v = derive(0u);
+        return ChachaJob{v.c, ((uint64_t)v.shi << 32) | v.slo, s_rng + (size_t)(v.c & 1u) * 8 * NT, v.tid, v.store};
       };
       chacha8_block_to_lds_job<NT, ROLL_HOT>(key, job);  // all 64 lanes (the permutes read from lanes that have no job)
+      RL_CG_MARK("FULL_E");
+      passes += 1u;
+    }
+#pragma unroll 1
+    for (; QUAD && j0 < jobs; j0 += 16u) {  // the remainder of at most COOP_QUAD_MAX jobs (none without `quad`: the loop above has passed `jobs`)
+      RL_CG_MARK("QUAD_B");
+      auto job = [&] {
+        const Derived v = derive(2u);
+        const uint32_t q = v.lane & 3u;
+        const uint32_t d_in = (q & 2u) ? ((q & 1u) ? v.shi : v.slo) : ((q & 1u) ? 0u : v.c);
+        return ChachaQuadJob{q, d_in, s_rng + (size_t)(v.c & 1u) * 8 * NT, v.tid, v.store};
+      };
+      chacha8_quad_block_to_lds_job<NT, ROLL_HOT>(key, job);  // all 64 lanes: the quad permutes of the rounds need every quad whole
+      RL_CG_MARK("QUAD_E");
+      passes += 1u << 16;
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return passes;
   }
   __device__ __forceinline__ uint64_t next_u64() {
     if (ODD) return next_u64_any();

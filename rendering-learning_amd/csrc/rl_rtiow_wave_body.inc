@@ -79,7 +79,10 @@
 
   // ---- per-lane persistent state
   // (the stealing instantiation keeps the unrolled block function on its hot paths: measured, 1/8 and 1/4 shard 170 / 263 ms against 163 / 283 rolled)
-  Ring<NT, !STEAL> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
+  // (the moments kernel with the scene in global memory keeps lane-per-block passes and the per-lane FILL: with the four-lanes-per-block
+  // pass in it, it spills a VGPR, 8 bytes of scratch, where it spilled none)
+  constexpr bool COOP_QUAD = !(MOMENTS && LDS_SCENE == 0);
+  Ring<NT, !STEAL, false, COOP_QUAD> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
   uint32_t state = ST_GEN;
   uint32_t px = 0, pr = 0, n = spp;  // n == spp: no pixel owned yet
   uint32_t n_end = spp;              // INDEP: end of the lane's sample group
@@ -288,6 +291,7 @@
 
   unsigned long long sc_exec[7] = {0, 0, 0, 0, 0, 0, 0}, sc_pop[7] = {0, 0, 0, 0, 0, 0, 0}, sc_cyc[7] = {0, 0, 0, 0, 0, 0, 0};
   unsigned long long sc_trav_picks = 0;  // STATS: scheduling decisions that chose TRAV (sc_exec[ST_TRAV] counts its steps)
+  unsigned long long sc_pass[4] = {0, 0, 0, 0};  // STATS: block passes of Ring::coop_blocks: GEN's full / quad, FILL's full / quad
   for (;;) {
     RL_CG_MARK("HEAD");
     // a finished traversal goes to SHADE; lanes reading from their newest ChaCha block top the ring up first
@@ -491,7 +495,16 @@
     }
     if (picked(ST_FILL)) {
       RL_CG_MARK("FILL_B");
-      if (state == ST_FILL) {
+      if (COOP_QUAD && RL_COOP_GEN && P.coop_quad) {  // the FILL lanes' blocks as one job list, like GEN's stream resets: one block each, top_up's
+        uint32_t nb = 0u, first = 0u;
+        if (state == ST_FILL) nb = 1u, first = rng.blk_lo + rng.nres;
+        const uint32_t np = rng.template coop_blocks<true, false>(nb, first, true);
+        if (STATS) sc_pass[2] += np & 0xFFFFu, sc_pass[3] += np >> 16;
+        if (state == ST_FILL) {
+          rng.top_up_done();
+          state = shade_state();
+        }
+      } else if (state == ST_FILL) {
         rng.top_up();
         state = shade_state();
       }
@@ -613,7 +626,8 @@
           fill = state == ST_FILL && (g2 + nf + 63u) / 64u <= (g2 > 64u ? 2u : 1u);
           if (fill) nb = 1u, first = rng.blk_lo + rng.nres;
         }
-        rng.template coop_blocks<RL_COOP_GEN == 2>(nb, first);
+        const uint32_t np = rng.template coop_blocks<RL_COOP_GEN == 2>(nb, first, P.coop_quad != 0u);
+        if (STATS) sc_pass[0] += np & 0xFFFFu, sc_pass[1] += np >> 16;
         if (active) rng.nres = 2;
         if (fill) {
           rng.top_up_done();
@@ -671,6 +685,8 @@
       atomicAdd(&sched[3 * s + 2], sc_cyc[s]);
     }
     atomicAdd(&sched[29], sc_trav_picks);  // rl_debug_sched out[29]
+    atomicAdd(&sched[21], sc_pass[0]), atomicAdd(&sched[22], sc_pass[1]);  // out[21], out[22]: GEN's full and quad passes
+    atomicAdd(&sched[23], sc_pass[2]), atomicAdd(&sched[30], sc_pass[3]);  // out[23], out[30]: FILL's
   }
 
   if (STEAL && LDS_SCENE == 4 && P.steal_state) {

@@ -36,3 +36,5 @@ for k, nm in names.items():
     ex, pop, cyc = out[3 * k], out[3 * k + 1], out[3 * k + 2]
     if ex or cyc: ex = max(ex, 1); print(f"{nm:6s} execs {ex:12d}  lanes served {pop:14d}  avg pop {pop/ex:6.2f}  lane-visits/ray {pop/st['rays']:.3f}  "
                  f"cycles/exec {cyc/ex:8.1f}  time share {100*cyc/tot:5.1f}%")
+if out[21] or out[22] or out[23] or out[30]:  # block passes of Ring::coop_blocks: a lane per block (64 jobs) / four lanes per block (16 jobs)
+    print(f"block passes  GEN full {out[21]} quad {out[22]}  FILL full {out[23]} quad {out[30]}")

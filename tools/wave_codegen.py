@@ -11,6 +11,10 @@ The path is the shortest one (in instructions) through the way points that the b
 with divergent regions entered: an s_cbranch_execz is not followed, unless it is a lane loop's only exit.  TRAV's path runs its step loop once (two steps);
 `step` is the VALU count of one step body on its own, so  valu - 2 * step  is what a TRAV pick costs around its steps.
 The kernel's register figures are those tools/kernel_regs.py reads from a built library.
+`passes`: the VALU count of ONE block pass of Ring::coop_blocks in each form, FULL (a lane per block, 64 jobs) and QUAD (four lanes per
+block, 16 jobs), between their marks, for every copy in the kernel (GEN's, then FILL's), with the rolled round loop (a block that
+branches to itself) counted four times; and `quad_max`, the largest remainder R for which ceil(R / 16) quad passes cost fewer VALU
+instructions than one full pass, from the first copy: what Ring::COOP_QUAD_MAX must not exceed.
 
 With --base the same report is made for a second tree and printed beside the first (base -> tree).  A tree from before the marks
 existed gets them inserted into a temporary copy of its body, at the same places (they are comment lines in the assembly, but a
@@ -225,6 +229,26 @@ def pick_paths(nodes):
     return out
 
 
+ROUNDS = 4  # double rounds of ChaCha8: the trip count of the rolled loop
+
+
+def pass_counts(nodes):
+    """{"FULL": [valu per copy], "QUAD": [...], "quad_max": R} — empty lists for a tree without the pass marks."""
+    out = {}
+    for form in ("FULL", "QUAD"):
+        out[form] = []
+        for i, n in enumerate(nodes):
+            if n.mark != f"{form}_B":
+                continue
+            seg, _ = shortest(nodes, i, f"{form}_E")
+            if seg is None:
+                continue
+            out[form].append(sum(sum(op.startswith("v_") for op in nodes[u].insts) * (ROUNDS if u in nodes[u].succ else 1) for u in seg))
+    if out["FULL"] and out["QUAD"]:
+        out["quad_max"] = min(63, (out["FULL"][0] - 1) // out["QUAD"][0] * 16)
+    return out
+
+
 def report_instance(tree, name, workdir):
     asm = compile_instance(tree, name, workdir)
     _, lines, meta = kernel_text(asm, INSTANCES[name].split("::")[1].split("<")[0])
@@ -232,7 +256,7 @@ def report_instance(tree, name, workdir):
     ops = [op for n in nodes for op in n.insts]
     meta.update(insts=len(ops), valu=sum(op.startswith("v_") for op in ops), mov=sum(op.startswith("v_mov_b") for op in ops),
                 lane=sum(op.startswith(("v_readlane", "v_writelane")) for op in ops))
-    return {"kernel": meta, "paths": pick_paths(nodes)}
+    return {"kernel": meta, "paths": pick_paths(nodes), "passes": pass_counts(nodes)}
 
 
 def report(tree=ROOT, names=None):
@@ -259,6 +283,9 @@ def print_report(rep, base=None):
                 print(f"  {blk:5s} path not found")
                 continue
             print(f"  {blk:5s} " + "  ".join(f"{key} {cell(p[key], pb.get(key) if pb else None)}" for key in ("insts", "valu", "mov", "lane") + (("step",) if blk == "TRAV" else ())))
+        ps = r.get("passes") or {}
+        if ps.get("FULL") or ps.get("QUAD"):
+            print(f"  pass  full valu {ps.get('FULL')}  quad valu {ps.get('QUAD')}  quad_max {ps.get('quad_max')}")
 
 
 def main():
