@@ -1343,6 +1343,11 @@ int rlo_rtiow_hit(const rl_rtiow_scene_desc *desc, const double o[3], const doub
 void rlo_sphere_uv(const double p[3], double out[2]) { sphere_uv(v3(p), out[0], out[1]); }
 double rlo_perlin_noise(const rl_perlin *pn, const double p[3]) { return perlin_noise(*pn, v3(p)); }
 double rlo_perlin_turb(const rl_perlin *pn, const double p[3], uint32_t depth) { return perlin_turb(*pn, v3(p), depth); }
+// Texture::value(u, v, &p) of desc->textures[tex]
+void rlo_rtiow_texture_value(const rl_rtiow_scene_desc *desc, uint32_t tex, double u, double v, const double p[3], double out[3]) {
+  V3 c = texture_value(*desc, tex, u, v, v3(p));
+  out[0] = c.x, out[1] = c.y, out[2] = c.z;
+}
 int rlo_aabb_hit(const double bbox[6], const double o[3], const double d[3], double tmin, double tmax) {
   Ray r{v3(o), v3(d), 0.0};
   return aabb_hit(bbox, r, tmin, tmax) ? 1 : 0;

@@ -41,6 +41,8 @@ def lib():
         L.rlo_perlin_noise.restype = dbl
         L.rlo_perlin_turb.argtypes = [vp, vp, u32]
         L.rlo_perlin_turb.restype = dbl
+        L.rlo_rtiow_texture_value.argtypes = [vp, u32, dbl, dbl, vp, vp]
+        L.rlo_rtiow_texture_value.restype = None
         L.rlo_rtc_intersect.argtypes = [vp, vp, vp, vp, vp, vp, u32]
         L.rlo_rtc_color_at.argtypes = [vp, vp, vp, vp]
         L.rlo_rtc_lighting.argtypes = [vp, vp, vp, vp, vp, vp, dbl, vp]
@@ -170,6 +172,14 @@ def perlin_noise(perlin, p):
 def perlin_turb(perlin, p, depth=7):
     p = np.ascontiguousarray(p, dtype=np.float64)
     return float(lib().rlo_perlin_turb(perlin.ctypes.data, p.ctypes.data, depth))
+
+
+def texture_value(desc, tex, u, v, p):
+    """Texture::value(u, v, &p) of the description's textures[tex] -> rgb [3]"""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    out = np.zeros(3)
+    lib().rlo_rtiow_texture_value(desc, int(tex), float(u), float(v), p.ctypes.data, out.ctypes.data)
+    return out
 
 
 def aabb_hit(bbox, o, d, tmin, tmax):

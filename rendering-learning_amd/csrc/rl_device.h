@@ -29,6 +29,17 @@ __device__ __forceinline__ D3 normalize(D3 a) { return div_s(a, sqrt(len2(a))); 
 // float-cmp approx_eq with F64Margin::zero().epsilon(e): a == b || |a - b| <= e
 __device__ __forceinline__ bool approx_eq_eps(double a, double b, double e) { return a == b || fabs(a - b) <= e; }
 
+// The low bit of Rust's `f as i64` for f = floor(..): the parity the checker textures and the RTC patterns decide on.  The cast
+// saturates: f >= 2^63 (+inf included) is i64::MAX, odd; f <= -2^63 (-inf included) is i64::MIN, even; NaN is 0.  gfx950 has no 64-bit
+// convert instruction, and the expansion of a bare (long long) cast keeps the exact low word of f instead: even for every f >= 2^63.
+// No integer is needed for the bit: f / 2 is exact, and its fraction is 1/2 for an odd f and 0 for an even one, which every binary64
+// integer from 2^53 on is, -2^63 and below included; inf - inf and NaN compare false.  Integer sums wrap in the reference's release
+// build and a wrapping sum keeps the low bit, so the parity of a sum of casts is the xor of these.
+__device__ __forceinline__ uint32_t f64_as_i64_low_bit(double f) {
+  const double h = 0.5 * f;
+  return (uint32_t)((f >= 9223372036854775808.0) | (h - floor(h) > 0.0));
+}
+
 // wave-level sum of a u64 (64-wide wavefront), result valid in lane 0
 __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 #pragma unroll

@@ -37,21 +37,19 @@ struct Ent {  // one Intersection (intersect.rs:11-16) + the CSG side tag
 };
 static const uint32_t ENT_RIGHT = 0x80000000u;
 
-__device__ __forceinline__ long long f2i64(double f) { return (long long)f; }  // v_cvt saturates; NaN -> 0
-
 __device__ inline D3 rtc_surface_color(const RtcFullParams &F, const rl_rtc_material &m, D3 p) {  // material.rs:13-20
   if (m.pattern == 0) return ld3(m.color);
   const rl_rtc_pattern &pt = F.patterns[m.pattern - 1];
   D3 q = mul_point(pt.inverse, p);
   D3 a = ld3(pt.a), b = ld3(pt.b);
-  if (pt.kind == RL_PAT_STRIPE) return (f2i64(floor(q.x)) % 2 == 0) ? a : b;
-  if (pt.kind == RL_PAT_RING) return (f2i64(floor(sqrt(q.x * q.x + q.z * q.z))) % 2 == 0) ? a : b;
+  if (pt.kind == RL_PAT_STRIPE) return f64_as_i64_low_bit(floor(q.x)) ? b : a;  // `as i64 % 2 == 0`, saturating (rl_device.h)
+  if (pt.kind == RL_PAT_RING) return f64_as_i64_low_bit(floor(sqrt(q.x * q.x + q.z * q.z))) ? b : a;
   if (pt.kind == RL_PAT_GRADIENT) {
     D3 distance = b - a;
     double fraction = q.x - floor(q.x);
     return a + distance * fraction;
   }
-  return (f2i64(floor(q.x) + floor(q.y) + floor(q.z)) % 2 == 0) ? a : b;
+  return f64_as_i64_low_bit(floor(q.x) + floor(q.y) + floor(q.z)) ? b : a;
 }
 
 __device__ __forceinline__ uint32_t rtc_leaf_material(const RtcFullParams &F, const DevTri *tris, uint32_t leaf) {

@@ -416,12 +416,11 @@ __device__ __forceinline__ D3 texture_value(const RtiowParams &P, uint32_t tex, 
     const DevTexture &t = P.textures[tex];
     if (t.kind == RL_TEX_SOLID) return ld3(t.color);
     if (t.kind == RL_TEX_CHECKER) {  // texture.rs:41-55
-      // floor() as i64 (saturating; |p*inv_scale| < 2^63 for every sane scene), Rust % keeps the sign
-      long long xi = (long long)floor(p.x * t.inv_scale);
-      long long yi = (long long)floor(p.y * t.inv_scale);
-      long long zi = (long long)floor(p.z * t.inv_scale);
-      long long sum = (long long)((unsigned long long)xi + (unsigned long long)yi + (unsigned long long)zi);
-      tex = ((sum % 2) == 0) ? t.even : t.odd;
+      // floor() as i64, saturating, summed wrapping (the release build; a debug build panics on the overflow); Rust's % keeps the
+      // sign, so `sum % 2 == 0` asks for the low bit alone
+      uint32_t odd = f64_as_i64_low_bit(floor(p.x * t.inv_scale)) ^ f64_as_i64_low_bit(floor(p.y * t.inv_scale)) ^
+                     f64_as_i64_low_bit(floor(p.z * t.inv_scale));
+      tex = odd ? t.odd : t.even;
       continue;
     }
     if (MODE == 0) return D3{0.0, 0.0, 0.0};

@@ -108,8 +108,9 @@ struct ImageData {
   uint32_t width = 0, height = 0;
   std::vector<float> rgb;  // linear
 };
-// perlin.rs:9-36 Perlin::new(rand): 256 random unit vectors, then three Fisher-Yates permutations of 0..255, all
-// drawn from the caller's Rng in that order.  R needs next_u64() (rand_core RngCore).  The draws restate
+// perlin.rs:9-36 Perlin::new(rand): 256 random unit vectors, then three permutations of 0..255, all drawn from the
+// caller's Rng in that order.  permute swaps p[i] with p[gen_range(0..i)], the upper end excluded: Sattolo's variant
+// of the shuffle, not Fisher-Yates, so every table is a single 256-cycle (tests/test_procedural_model.py).  R needs next_u64() (rand_core RngCore).  The draws restate
 // rand_distr 0.4.3 UnitSphere (Uniform::new(-1., 1.) pairs, Marsaglia) and rand 0.8.5 gen_range(0..i) for usize
 // (widening-multiply rejection, UniformInt::sample_single).  No reference test pins these tables: "unpinned".
 struct Perlin {

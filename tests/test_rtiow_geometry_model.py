@@ -1021,16 +1021,7 @@ def image_value(img, u, v):
     return img[image_index(img.shape[1], img.shape[0], u, v)].astype(np.float64)
 
 
-def checker_leaf(tree, p):
-    """Checker::value (texture.rs:42-54): tree = colour | (scale, even, odd); floor(p / scale as p * (1 / scale)) per axis, summed as
-    integers; Rust's % keeps the sign, so an odd negative sum is -1 != 0: odd"""
-    while not isinstance(tree[0], float):
-        scale, even, odd = tree
-        inv = 1.0 / scale[0]
-        s = sum(int(math.floor(c * inv)) for c in p)
-        rem = int(math.fmod(s, 2))  # sign of the dividend, as Rust's %
-        tree = even if rem == 0 else odd
-    return np.array(tree)
+from procedural_model import checker_leaf  # noqa: E402  Checker::value with Rust's saturating casts, shared with the procedural tiers
 
 
 IMAGE_SIZES = [(1, 1), (2, 3), (3, 2), (5, 4)]  # (W, H)
