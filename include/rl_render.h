@@ -619,6 +619,62 @@ int rl_rtiow_render_pixels_features_device(const rl_scene *, const rl_rtiow_came
                                            uint64_t n, const rl_rtiow_features *d_out, void *hip_stream, rl_stats *opt_stats);
 
 /* =====================================================================
+ *  Ambient-occlusion renders: seeded any-hit rays at first hits
+ * =====================================================================
+ * One launch traces cam->samples_per_pixel jittered camera rays per pixel to their first hit and sends ao_rays cosine-weighted any-hit
+ * rays from each hit.  Let the pixel be (x, y) of the camera's whole W x H frame, F = first_sample, S = cam->samples_per_pixel,
+ * K = ao_rays, R = radius.  For s = F, F+1, .., F+S-1, in this order:
+ *     rng = ChaCha8Rng::seed_from_u64(cam->seed), set_stream(s*W*H + x*W + y), word position 0
+ *     ray = Camera::get_ray(&mut rng, x, y)                  -- camera.rs:203-216, what rl_rtiow_camera_rays returns for that cursor
+ *     hit = world.hit(&ray, &Interval{1e-10, +inf})          -- what rl_rtiow_hit_rays returns
+ *     if hit:  hit_count += 1
+ *              repeat K times:
+ *                d = hit.normal + Vec3::random_unit_vector(&mut rng);  if d.near_zero() { d = hit.normal }
+ *                                                            -- Lambertian::scatter's direction (material.rs:80-86), whatever the
+ *                                                               hit's material
+ *                a = d.normalize()                           -- vec3.rs:56: d * (1.0 / d.length()), length_squared as vec3.rs:36-38, no FMA
+ *                occluded = world.hit(&Ray{hit.p, a, ray.time}, &Interval{1e-10, R}).is_some()
+ *                                                            -- what rl_rtiow_occluded_rays returns
+ *                open_count += !occluded
+ * The two outputs are uint32_t open_count[n] and uint32_t hit_count[n]; each is optional, an output that is not asked for is not
+ * written and the other has the same bits.  Both counts start at 0.  The visibility of a pixel is open_count / (K * hit_count): the
+ * cosine weighting of `normal + unit vector` makes that the ambient-occlusion integral.  The ambient ray inherits the camera ray's
+ * time, so moving spheres occlude where they are for that sample.  R is a Euclidean distance, because `a` is normalised.
+ * What follows from the definition:
+ *  - A pixel's values depend on nothing but the pixel, F, S, K, R, the camera and the scene: row shards and pixel lists give the frame's
+ *    bits.
+ *  - The outputs are integers, so calls that continue each other add EXACTLY: (F = 0, S = 2) + (F = 2, S = 1) equals (F = 0, S = 3).  (The
+ *    floating-point sums of the feature renders do not promise this.)
+ *  - The camera rays are those of rl_rtiow_render_independent* and rl_rtiow_render_features*, sample for sample.
+ *  - cam->max_depth is not read.
+ * Layout is that of the feature renders: compact shard rows for _rows and _device ([nrows][W]), out[i] for the lists.  The plain forms
+ * take host pointers, the _device forms device pointers and a hipStream_t; those are asynchronous unless opt_stats is given.
+ * Errors.  ao_rays == 0, S * ao_rays >= 2^32, a radius that is NaN or <= 0 (+inf is legal), or both outputs NULL: RL_E_INVALID, before a
+ * device is looked at, outputs untouched; then, without a device, RL_E_NO_DEVICE (no CPU fallback), outputs untouched; then the plain
+ * renders' rules (a NULL scene or camera, row_step 0, an RTC scene, an empty image: RL_E_INVALID).  A scene with ConstantMedium objects:
+ * RL_E_UNSUPPORTED, for rl_rtiow_occluded_rays' reason (there is no seeded any-hit).  Pixel lists follow
+ * rl_rtiow_render_pixels_features* exactly: unsorted, duplicates allowed, n = 0 is RL_OK, the host form refuses a pixel outside the
+ * image, the _device form writes zeros to every given output for such an element and traces nothing; n >= 0xFFFF0000: RL_E_INVALID;
+ * under rl_init_multi device 0's replica.  A reached panic site sets flagged and returns RL_E_DEGENERATE with every output written; in
+ * the counter-free form this holds with rl_rtiow_occluded_rays' caveat for ambient rays the any-hit walk decides by itself.
+ * Stats.  With opt_stats the call is counting and every ray runs the reference-order fold: rays = S * pixels + K * (sum of hit_count);
+ * the traversal counters are the sums of what rl_rtiow_hit_rays and rl_rtiow_occluded_rays report for those rays; rng_words = the words
+ * get_ray and the K unit-vector draws consumed.  Without it the call is counter-free, may take the fast walks and gives the same bytes.
+ * _rows counts or not exactly as rl_rtiow_render_features_rows does (always).  rl_render_status and per-scene serialisation: as the
+ * feature renders.
+ * Not offered: media scenes, a bent-normal output (a floating-point sum would need an order), a radius per sample, multi-GPU forms,
+ * rgb8 output, the RTC family. */
+int rl_rtiow_render_ao_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step, uint32_t ao_rays,
+                            double radius, uint32_t *out_open_count, uint32_t *out_hit_count, rl_stats *opt_stats);
+int rl_rtiow_render_ao_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step, uint32_t ao_rays,
+                              double radius, void *d_out_open_count, void *d_out_hit_count, void *hip_stream, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_ao(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys, uint64_t n,
+                              uint32_t ao_rays, double radius, uint32_t *out_open_count, uint32_t *out_hit_count, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_ao_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs, const void *d_ys, uint64_t n,
+                                     uint32_t ao_rays, double radius, void *d_out_open_count, void *d_out_hit_count, void *hip_stream,
+                                     rl_stats *opt_stats);
+
+/* =====================================================================
  *  Denoising: an edge-avoiding a-trous filter for noisy and adaptive renders
  * =====================================================================
  * What consumes the mean and variance of the moments and adaptive renders and the guide buffers of the feature renders.  It needs no scene.

@@ -10,3 +10,5 @@ from .api import (DenoiseInputs, denoise_finish_device, denoise_inputs, denoise_
                   denoise_render_work_bytes)
 from . import occlusion  # noqa: F401
 from .occlusion import occluded_rays, occluded_rays_device  # noqa: F401
+from . import ao  # noqa: F401
+from .ao import AmbientOcclusion, render_ao, render_ao_device, render_pixels_ao, render_pixels_ao_device  # noqa: F401

@@ -254,6 +254,10 @@ RENDER_SIGNATURES = {
     "rl_rtiow_render_features_device": (_I, [_P, _CAM, _U64, _U32, _U32, _FEATURES, _P, _STATS]),
     "rl_rtiow_render_pixels_features": (_I, [_P, _CAM, _U64, _P, _P, _U64, _FEATURES, _STATS]),
     "rl_rtiow_render_pixels_features_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _FEATURES, _P, _STATS]),
+    "rl_rtiow_render_ao_rows": (_I, [_P, _CAM, _U64, _U32, _U32, _U32, _D, _P, _P, _STATS]),
+    "rl_rtiow_render_ao_device": (_I, [_P, _CAM, _U64, _U32, _U32, _U32, _D, _P, _P, _P, _STATS]),
+    "rl_rtiow_render_pixels_ao": (_I, [_P, _CAM, _U64, _P, _P, _U64, _U32, _D, _P, _P, _STATS]),
+    "rl_rtiow_render_pixels_ao_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _U32, _D, _P, _P, _P, _STATS]),
     "rl_denoise_atrous_pass_device": (_I, [_U32, _U32, _U32, _ATROUS, _P, _P, _P, _P, _P, _P]),
     "rl_denoise_atrous": (_I, [_U32, _U32, _U32, _ATROUS, _P, _P, _P, _P, _P]),
     "rl_denoise_prepare_device": (_I, [_U32, _U32, _DENOISE_IN, _P, _P, _P, _P]),
@@ -622,7 +626,8 @@ def last_query():
     ("features_fast" / "features_reference") and, for a synchronous call, how many of its rays the fast walk re-traced in the reference's order."""
     out = (C.c_uint64 * 2)()
     _check(render_lib().rl_debug_last_query(out))
-    names = {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast", 5: "occlusion_reference", 6: "occlusion_fast"}
+    names = {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast", 5: "occlusion_reference", 6: "occlusion_fast",
+             7: "ao_reference", 8: "ao_fast"}
     return {"kernel": names.get(int(out[0]), "none"), "retraced": int(out[1])}
 
 

@@ -1465,3 +1465,5 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 #include "rl_denoise.h"
 #include "rl_denoise_render.h"
 #include "rl_occlusion_api.h"  // behind everything: its kernels are instantiated last, every earlier kernel keeps its place
+#include "rl_rtiow_ao.h"       // (and the ambient-occlusion renders behind those, for the same reason)
+#include "rl_ao_api.h"

@@ -638,6 +638,22 @@ int rlh_render_features_probe(uint64_t width, uint64_t spp, uint64_t first_sampl
     return -1;
   }
 }
+// An ambient-occlusion render through the C++ mirror: golden_test_scene at image_width = width, samples_per_pixel = spp, rtiow::render_ao
+// from sample first_sample on.  open_count and hit_count = W * H uint32 each.  0 or -1 (rlh_last_error).
+int rlh_ao_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32_t ao_rays, double radius, uint32_t *open_count, uint32_t *hit_count) {
+  try {
+    scenes::RtiowScene s = scenes::golden_test_scene();
+    s.params.image_width = (size_t)width, s.params.samples_per_pixel = (size_t)spp;
+    rtiow::Camera cam(s.params);
+    rtiow::Camera::AmbientOcclusion ao = rtiow::render_ao(cam, *s.world, ao_rays, radius, first_sample);
+    std::memcpy(open_count, ao.open_count.data(), ao.open_count.size() * sizeof(uint32_t));
+    std::memcpy(hit_count, ao.hit_count.data(), ao.hit_count.size() * sizeof(uint32_t));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // rtiow::denoise_atrous through the C++ mirror: color, variance and the two outputs = width * height * 3 doubles, guides = width * height *
 // params->n_guides doubles.  0 or -1 (rlh_last_error).
 int rlh_denoise_atrous_probe(uint64_t width, uint64_t height, uint32_t iterations, const rl_atrous_params *params, const double *color, const double *variance,

@@ -108,6 +108,20 @@ Camera::Features Camera::render_features(const Hittable &world, uint64_t first_s
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_features_rows: ") + rl_last_error());
   return ft;
 }
+Camera::AmbientOcclusion Camera::render_ao(const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample) const {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  rl_rtiow_camera cam = derived();
+  const size_t n = params.image_width * image_height;
+  AmbientOcclusion ao{ao_rays, std::vector<uint32_t>(n), std::vector<uint32_t>(n)};
+  int rc = rl_rtiow_render_ao_rows(sc, &cam, first_sample, 0, 1, ao_rays, radius, ao.open_count.data(), ao.hit_count.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_ao_rows: ") + rl_last_error());
+  return ao;
+}
 Denoised denoise_atrous(size_t width, size_t height, uint32_t iterations, const rl_atrous_params &params, const std::vector<double> &color,
                         const std::vector<double> &variance, const std::vector<double> &guides) {
   const size_t n = width * height;

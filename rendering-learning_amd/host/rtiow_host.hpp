@@ -836,7 +836,23 @@ struct Camera {
   // ray_color_rays with seed = params.seed; cursors[i] is advanced behind the draws.  _render's stream of sample s at pixel (x, y) is
   // s * W * H + x * W + y (camera.rs:161-170).
   std::vector<rl_ray> get_rays(const uint32_t *px, const uint32_t *py, rl_rng_cursor *cursors, size_t n) const;
+  // an ambient-occlusion render (rl_rtiow_render_ao_rows): per pixel, over the samples_per_pixel jittered camera rays of render_independent
+  // (samples first_sample ..), the number that hit and, over the ao_rays rays (normal + random_unit_vector).normalize() sent from each
+  // first hit at the camera ray's time, the number that find nothing within `radius`.  Integers: renders that continue each other add
+  // exactly.  max_depth is not read; worlds with a ConstantMedium are refused.
+  struct AmbientOcclusion {
+    size_t ao_rays;
+    std::vector<uint32_t> open_count;  // [H][W]
+    std::vector<uint32_t> hit_count;   // [H][W]
+    // open_count / (ao_rays * hit_count); `miss` where no camera ray hit
+    double visibility(size_t i, double miss = 1.0) const { return hit_count[i] ? (double)open_count[i] / ((double)ao_rays * (double)hit_count[i]) : miss; }
+  };
+  AmbientOcclusion render_ao(const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample = 0) const;
 };
+// Camera::render_ao as a function of the camera and the world
+inline Camera::AmbientOcclusion render_ao(const Camera &camera, const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample = 0) {
+  return camera.render_ao(world, ao_rays, radius, first_sample);
+}
 
 // ---------------------------------------------------------------- denoising (rl_denoise_atrous; defined in host_render.cpp)
 // `iterations` passes (step 1, 2, 4, ..) of the edge-avoiding a-trous filter of include/rl_render.h "Denoising" over color [H][W][3] with
