@@ -675,6 +675,76 @@ int rl_rtiow_render_pixels_ao_device(const rl_scene *, const rl_rtiow_camera *, 
                                      rl_stats *opt_stats);
 
 /* =====================================================================
+ *  Direct-lighting renders: seeded shadow segments to quad lights
+ * =====================================================================
+ * One launch traces cam->samples_per_pixel jittered camera rays per pixel to their first hit and, from each hit, tests the segments to
+ * light_samples points drawn on each of n_lights quad lights with the any-hit query.  A light is 12 doubles, Q[3], u[3], v[3], E[3]: the
+ * parallelogram Q + a*u + b*v, a, b in [0,1) (Quad::new(Q, u, v, ..), quad.rs) and its emitted radiance (what DiffuseLight{SolidColor}
+ * returns from `emitted`, two-sided as there).  `lights` is [n_lights][12].  For every light nl = u.cross(v) with vec3.rs:48-54's
+ * component order, every product rounded, no FMA.  Let the pixel be (x, y) of the camera's whole W x H frame, F = first_sample,
+ * S = cam->samples_per_pixel, L = n_lights, K = light_samples, T = seg_tmax.  For s = F, F+1, .., F+S-1, in this order:
+ *     rng = ChaCha8Rng::seed_from_u64(cam->seed), set_stream(s*W*H + x*W + y), word position 0     -- as the AO and feature renders
+ *     ray = Camera::get_ray(&mut rng, x, y)
+ *     hit = world.hit(&ray, &Interval{1e-10, +inf})
+ *     if hit:  hit_count += 1
+ *       for l in 0..L:  for k in 0..K:
+ *          a = rng.gen::<f64>();  b = rng.gen::<f64>()       -- always drawn: 4 words per light sample
+ *          yl = (Q + u*a) + v*b
+ *          d  = yl - hit.p
+ *          d2 = d.x*d.x + d.y*d.y + d.z*d.z                   -- vec3.rs length_squared order
+ *          cs = hit.normal.dot(d)                             -- the record's normal (it faces the camera ray), whatever the material
+ *          cl = |nl.dot(d)|
+ *          if !(cs > 0) or !(cl > 0) or !(d2 > 0):  continue  -- faces away, edge-on or degenerate: nothing traced
+ *          g  = (cs * cl) / (d2 * d2)                         -- = cos(theta) cos(theta_l) area / |d|^2: no sqrt and no normalisation
+ *          occluded = world.hit(&Ray{hit.p, d, ray.time}, &Interval{1e-10, T}).is_some()      -- what rl_rtiow_occluded_rays returns
+ *          for c in r, g, b:  e = E[c] * g;  unshadowed[c] = unshadowed[c] + e;  if !occluded: direct[c] = direct[c] + e
+ * Every operation is one rounded binary64 + - x or /.  The outputs are double direct[n][3], double unshadowed[n][3] and
+ * uint32_t hit_count[n]; each is optional (not all three), an output that is not asked for is not written and the others have the same
+ * bits.  All start at 0.
+ *  - direct / (K * hit_count) is the unoccluded irradiance estimate at the first hits.  It is DEMODULATED: no albedo and no 1/pi are
+ *    applied; rl_rtiow_render_features' albedo supplies those.  (That also keeps texture evaluation out of the kernel.)
+ *  - direct / unshadowed is the shadow ratio of a compositing pass.
+ *  - T is in (1e-10, 1].  A light that is also geometry of the scene (cornell_box's) sits at t = 1 of its segments, so such callers pass
+ *    T a little under 1.
+ * What follows from the definition:
+ *  - A pixel's values depend on nothing but the pixel and the call's scalars, lights, camera and scene: row shards and pixel lists give
+ *    the frame's bits.
+ *  - hit_count of calls that continue each other adds EXACTLY.  The floating-point sums of a continued call are those of THAT call, a
+ *    fresh fold from 0, as for the feature renders.
+ *  - The camera rays are those of rl_rtiow_render_independent*, rl_rtiow_render_features* and rl_rtiow_render_ao*, sample for sample.
+ *  - cam->max_depth is not read.
+ *  - The shadow segment inherits the camera ray's time, so moving spheres shadow where they are for that sample.
+ * Layout, _device asynchrony, _rows always counting, the pixel-list rules (unsorted, duplicates allowed, n = 0 is RL_OK, the host form
+ * refuses a pixel outside the image, the _device form writes zeros to every given output for such an element and traces nothing),
+ * rl_init_multi (device 0's replica), rl_render_status and the degenerate flag follow rl_rtiow_render_ao* exactly; direct and
+ * unshadowed are laid out [n][3] where the AO counts are [n].  The lights travel by value in the launch: n_lights <=
+ * RL_DIRECT_MAX_LIGHTS, and the asynchronous forms keep no pointer of the caller's.
+ * Errors.  n_lights == 0 or > RL_DIRECT_MAX_LIGHTS, lights == NULL, light_samples == 0, S * L * K >= 2^32, a light component that is not
+ * finite, u x v == 0 (all three components), seg_tmax NaN, <= 1e-10 or > 1, or all three outputs NULL: RL_E_INVALID, before a device is
+ * looked at, outputs untouched; then, without a device, RL_E_NO_DEVICE (no CPU fallback), outputs untouched; then the plain renders'
+ * rules.  A scene with ConstantMedium objects: RL_E_UNSUPPORTED, for rl_rtiow_occluded_rays' reason (there is no seeded any-hit).
+ * Stats.  With opt_stats the call is counting and every ray runs the reference-order fold: rays = S * pixels + (segments traced) — a
+ * skipped light sample traces nothing and counts nothing; the traversal counters are the sums of what rl_rtiow_hit_rays and
+ * rl_rtiow_occluded_rays report for those rays; rng_words = get_ray's words + 4 * L * K * (sum of hit_count).  Without it the call is
+ * counter-free, may take the fast walks and gives the same bytes.
+ * Not offered: sphere and textured lights, media scenes, a light picked at random instead of looped, multi-GPU forms, rgb8 output, the
+ * RTC family. */
+#define RL_DIRECT_MAX_LIGHTS 16u /* 16 x 12 doubles = 1536 bytes of launch arguments */
+int rl_rtiow_render_direct_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, double *out_direct,
+                                double *out_unshadowed, uint32_t *out_hit_count, rl_stats *opt_stats);
+int rl_rtiow_render_direct_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                  uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, void *d_out_direct,
+                                  void *d_out_unshadowed, void *d_out_hit_count, void *hip_stream, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_direct(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys,
+                                  uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
+                                  double *out_direct, double *out_unshadowed, uint32_t *out_hit_count, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_direct_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs, const void *d_ys,
+                                         uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
+                                         void *d_out_direct, void *d_out_unshadowed, void *d_out_hit_count, void *hip_stream,
+                                         rl_stats *opt_stats);
+
+/* =====================================================================
  *  Denoising: an edge-avoiding a-trous filter for noisy and adaptive renders
  * =====================================================================
  * What consumes the mean and variance of the moments and adaptive renders and the guide buffers of the feature renders.  It needs no scene.

@@ -1467,3 +1467,5 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 #include "rl_occlusion_api.h"  // behind everything: its kernels are instantiated last, every earlier kernel keeps its place
 #include "rl_rtiow_ao.h"       // (and the ambient-occlusion renders behind those, for the same reason)
 #include "rl_ao_api.h"
+#include "rl_rtiow_direct.h"   // (and the direct-lighting renders behind those; rl_rtiow_direct.h calls rl_rtiow_ao.h's any-hit walk)
+#include "rl_direct_api.h"

@@ -848,10 +848,38 @@ struct Camera {
     double visibility(size_t i, double miss = 1.0) const { return hit_count[i] ? (double)open_count[i] / ((double)ao_rays * (double)hit_count[i]) : miss; }
   };
   AmbientOcclusion render_ao(const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample = 0) const;
+  // a direct-lighting render (rl_rtiow_render_direct_rows): per pixel, over the same camera rays, the number that hit and, over
+  // light_samples points drawn on each quad light from every first hit, the sums of E * cos cos_l area / |d|^2 over all of them
+  // (unshadowed) and over those whose segment to the light point is free within Interval{1e-10, seg_tmax} (direct).  Demodulated: no
+  // albedo, no 1/pi.  The sums are one call's fold; hit_count of renders that continue each other adds exactly.  max_depth is not read;
+  // worlds with a ConstantMedium are refused.
+  struct QuadLight {
+    Vec3 q, u, v;  // the parallelogram q + a u + b v of Quad::new(q, u, v, ..)
+    Vec3 emit;     // the radiance DiffuseLight{SolidColor} emits
+  };
+  struct DirectLight {
+    size_t light_samples;
+    std::vector<double> direct;       // [H][W][3]
+    std::vector<double> unshadowed;   // [H][W][3]
+    std::vector<uint32_t> hit_count;  // [H][W]
+    // direct / (light_samples * hit_count) of channel c; `miss` where no camera ray hit
+    double irradiance(size_t i, int c, double miss = 0.0) const {
+      return hit_count[i] ? direct[3 * i + c] / ((double)light_samples * (double)hit_count[i]) : miss;
+    }
+    // direct / unshadowed of channel c; 1 where nothing is lit either way
+    double shadow(size_t i, int c) const { return unshadowed[3 * i + c] == 0.0 ? 1.0 : direct[3 * i + c] / unshadowed[3 * i + c]; }
+  };
+  DirectLight render_direct(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples, double seg_tmax = 1.0 - 1e-6,
+                            uint64_t first_sample = 0) const;
 };
 // Camera::render_ao as a function of the camera and the world
 inline Camera::AmbientOcclusion render_ao(const Camera &camera, const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample = 0) {
   return camera.render_ao(world, ao_rays, radius, first_sample);
+}
+// Camera::render_direct as a function of the camera and the world
+inline Camera::DirectLight render_direct(const Camera &camera, const Hittable &world, const std::vector<Camera::QuadLight> &lights, uint32_t light_samples,
+                                         double seg_tmax = 1.0 - 1e-6, uint64_t first_sample = 0) {
+  return camera.render_direct(world, lights, light_samples, seg_tmax, first_sample);
 }
 
 // ---------------------------------------------------------------- denoising (rl_denoise_atrous; defined in host_render.cpp)
