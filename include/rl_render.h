@@ -745,6 +745,77 @@ int rl_rtiow_render_pixels_direct_device(const rl_scene *, const rl_rtiow_camera
                                          rl_stats *opt_stats);
 
 /* =====================================================================
+ *  NEE path renders: ray_color with shadow segments to quad lights
+ * =====================================================================
+ * One launch traces cam->samples_per_pixel paths per pixel, Camera::ray_color (camera.rs:232-260) with next-event estimation: every
+ * Lambertian vertex but the last connects to light_samples points drawn on each of n_lights quad lights with the direct-lighting renders'
+ * draws, geometry term and any-hit segment test, and in exchange the emission its scattered ray finds is not counted.  A light is the
+ * direct-lighting renders' 12 doubles Q, u, v, E; `lights` is [n_lights][12], nl = u.cross(v) as there.  Let the pixel be (x, y) of the
+ * camera's whole W x H frame, F = first_sample, S = cam->samples_per_pixel, L = n_lights, K = light_samples, T = seg_tmax,
+ * kf = 1.0 / (M_PI * (double)K) (one rounded product, one rounded quotient; computed once on the host).  For s = F, F+1, .., F+S-1, in
+ * this order:
+ *     rng = ChaCha8Rng::seed_from_u64(cam->seed), set_stream(s*W*H + x*W + y), word position 0     -- as the AO and direct renders
+ *     ray = Camera::get_ray(&mut rng, x, y);  time = ray.time
+ *     c = (0,0,0);  thr = (1,1,1);  count_emission = true
+ *     for i in 1 ..= cam->max_depth:
+ *       1. hit = world.hit(&ray, &Interval{1e-10, +inf});   if none:  c = c + thr * cam->background;  break
+ *       2. em = hit.mat.emitted(hit.u, hit.v, &hit.p);      if count_emission:  c = c + thr * em
+ *       3. if hit.mat is RL_MAT_LAMBERTIAN and i < cam->max_depth:
+ *            tex = the material's texture value at the hit     -- the attenuation `scatter` will return
+ *            dsum = (0,0,0)
+ *            for l in 0..L:  for k in 0..K:
+ *               a = rng.gen::<f64>();  b = rng.gen::<f64>()       -- always drawn: 4 words per light sample
+ *               yl = (Q + u*a) + v*b;  d = yl - hit.p
+ *               d2 = d.x*d.x + d.y*d.y + d.z*d.z;  cs = hit.normal.dot(d);  cl = |nl.dot(d)|
+ *               if !(cs > 0) or !(cl > 0) or !(d2 > 0):  continue  -- faces away, edge-on or degenerate: nothing traced
+ *               g = (cs * cl) / (d2 * d2)
+ *               if world.hit(&Ray{hit.p, d, time}, &Interval{1e-10, T}).is_none():
+ *                  for ch in r, g, b:  dsum[ch] = dsum[ch] + E[ch] * g
+ *            for ch in r, g, b:  c[ch] = c[ch] + ((thr[ch] * tex[ch]) * dsum[ch]) * kf
+ *       4. match hit.mat.scatter(&mut rng, &ray, &hit):        -- drawing AFTER the light points
+ *            None:  break
+ *            Some((scattered, attenuation)):  thr = thr * attenuation;  ray = scattered;  count_emission = (step 3 was not taken)
+ *     for ch in r, g, b:  sums[ch] = sums[ch] + c[ch];  sq[ch] = sq[ch] + c[ch] * c[ch]
+ * Every operation is one rounded binary64 + - x or /.  The outputs are double sums[n][3] and double sq[n][3], what
+ * rl_rtiow_render_moments_rows gives for the plain path; each is optional (not both), an output that is not asked for is not written
+ * and the other has the same bits.  Both start at 0.
+ * What follows from the definition:
+ *  - Step 3's `i < max_depth` makes the estimator's expectation equal to ray_color's at the same max_depth: a connection made at vertex
+ *    i stands for the emission plain path tracing would find at vertex i+1.  This holds PROVIDED `lights` LISTS EVERY DiffuseLight
+ *    SURFACE OF THE SCENE (as quads with a SolidColor emission).  An emitter that is not listed is seen only directly and through Metal,
+ *    Dielectric, Isotropic and Flat chains; a light that is listed but is not geometry of the scene lights Lambertian surfaces and is
+ *    never seen.  The background is always counted on a miss.
+ *  - Isotropic vertices do no light sampling (a phase function needs 1/|d|^3, hence a sqrt).  The Dielectric's panic site (a zero
+ *    direction, material.rs:150-151) is flagged and behaves as in rl_rtiow_scatter_rays.
+ *  - A pixel's values depend on nothing but the pixel and the call's scalars, lights, camera and scene: row shards and pixel lists give
+ *    the frame's bits.  sums and sq of calls that continue each other are added by the caller, as for rl_rtiow_render_moments_rows.
+ *  - The camera rays are those of rl_rtiow_render_independent* and of the feature, AO and direct-lighting renders, sample for sample.
+ *  - Segments and scattered rays inherit the camera ray's time.
+ * Layout, _device asynchrony, _rows always counting, the pixel-list rules, rl_init_multi, rl_render_status and the degenerate flag
+ * follow rl_rtiow_render_direct* exactly.
+ * Errors.  The direct-lighting renders' rules on n_lights, lights, light_samples, S * L * K and seg_tmax, cam->max_depth == 0, or both
+ * outputs NULL: RL_E_INVALID, before a device is looked at, outputs untouched; then, without a device, RL_E_NO_DEVICE (no CPU
+ * fallback); then the plain renders' rules.  A scene with ConstantMedium objects: RL_E_UNSUPPORTED (there is no seeded any-hit).
+ * Stats.  With opt_stats the call is counting and every ray runs the reference-order fold: rays = path rays + segments traced; the
+ * traversal counters are the sums of what rl_rtiow_hit_rays and rl_rtiow_occluded_rays report for those rays; rng_words = the words
+ * drawn (get_ray's, 4 per light sample, the scatters').  Without it the call is counter-free, may take the fast walks and gives the
+ * same bytes.
+ * Not offered: sphere and textured lights, media scenes, multiple importance sampling with the scattered ray, Russian roulette, adaptive
+ * stopping, multi-GPU forms, rgb8 output, the RTC family. */
+int rl_rtiow_render_nee_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                             uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, double *out_sums, double *out_sq,
+                             rl_stats *opt_stats);
+int rl_rtiow_render_nee_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                               uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, void *d_out_sums, void *d_out_sq,
+                               void *hip_stream, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_nee(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys,
+                               uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, double *out_sums,
+                               double *out_sq, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_nee_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs, const void *d_ys,
+                                      uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
+                                      void *d_out_sums, void *d_out_sq, void *hip_stream, rl_stats *opt_stats);
+
+/* =====================================================================
  *  Denoising: an edge-avoiding a-trous filter for noisy and adaptive renders
  * =====================================================================
  * What consumes the mean and variance of the moments and adaptive renders and the guide buffers of the feature renders.  It needs no scene.

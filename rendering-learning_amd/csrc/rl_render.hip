@@ -1469,3 +1469,5 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 #include "rl_ao_api.h"
 #include "rl_rtiow_direct.h"   // (and the direct-lighting renders behind those; rl_rtiow_direct.h calls rl_rtiow_ao.h's any-hit walk)
 #include "rl_direct_api.h"
+#include "rl_rtiow_nee.h"      // (and the NEE path renders behind those; rl_rtiow_nee.h calls both walks, the texture and the scatter)
+#include "rl_nee_api.h"

@@ -1,0 +1,206 @@
+// NEE path renders (include/rl_render.h "NEE path renders", rl_rtiow_render_nee*): per pixel, over S jittered camera rays,
+// the sum and the sum of squares of a path estimate of max_depth vertices that connects every Lambertian vertex but the last to K points
+// drawn on each of L quad lights and, in exchange, does not count the emission the scattered ray of such a vertex finds.
+//
+//   rtiow_nee_kernel<NT, STATS, FAST, SD>   one pixel per lane, grid-stride over the frame's or the list's slots; per lane a loop over the
+//                                           samples F .. F + S - 1, inside it over the path's vertices and, at a vertex that samples the
+//                                           lights, over the L lights and their K points.
+//
+// Per vertex the kernel joins texts the library already has, so that the host composition of rl_rtiow_camera_rays, rl_rtiow_hit_rays, the
+// definition's arithmetic, rl_rtiow_occluded_rays and rl_rtiow_scatter_rays gives the same bytes (tests/test_gpu_render_nee.py):
+//   1. the stream start and the camera arithmetic of rtiow_direct_kernel: Ring in an LDS column, word 0
+//   2. the closest hit of the path's ray, Interval{1e-10, +inf}
+//        FAST = false  general_trace<STATS, false>
+//        FAST = true   features_fast_trace, the function the feature, the AO and the direct kernel call (it takes any world ray)
+//   3. material_texture (rl_rtiow_scatter.h), BEFORE anything of the scatter is live, as that file asks
+//   4. at a Lambertian vertex that is not the last: rtiow_direct_kernel's L x K loop with the record's normal, the sum kept per vertex
+//        FAST = false  general_trace<STATS, false>, rec.any
+//        FAST = true   ao_any_hit_walk (rl_rtiow_ao.h), then general_trace for a segment the walk leaves undecided (stats[7])
+//   5. material_scatter (rl_rtiow_scatter.h) drawing from the sample's ring AFTER the light points
+// None of the walks, of the texture or of the scatter is copied here.  The lights travel by value in the kernel argument (NeeQuery::lights,
+// indexed by the loop counter alone: scalar loads), nl = u x v and kf = 1 / (pi K) computed once on the host.  c, thr and the two sums
+// live in registers and are stored once per pixel: no atomics.
+//
+// Scenes with ConstantMedium objects are refused on the host (there is no seeded any-hit), so no trace here draws.
+// No barrier and no wave-wide operation inside a lane's loops: lanes leave their walks, their loops and their paths at different times.
+// LDS (dynamic): rtiow_ao_kernel's plan; the one [SD][NT] stack serves the closest-hit and the any-hit walk in turn.
+// stats: [0] rays = path rays + segments traced, [5] words drawn, [6] flagged (the walks' and the Dielectric's panic site), [7] segments AND
+// path rays the fast walks handed to general_trace; STATS: [1..4] over both kinds of ray.
+#pragma once
+#include "rl_rtiow_direct.h"
+
+namespace rl {
+
+struct NeeQuery {
+  unsigned long long n;     // slots: nrows * W of the shard, or the list's length
+  const uint32_t *xs, *ys;  // pixel list (null: the shard's rows, slot = r * W + x, y = row_first + r * row_step)
+  uint32_t n_lights;        // L in 1 .. RL_DIRECT_MAX_LIGHTS
+  uint32_t light_samples;   // K >= 1
+  double seg_tmax;          // T in (1e-10, 1]: the closed end of the segments' interval
+  double kf;                // 1.0 / (M_PI * (double)K), the host's double
+  double *sums;             // [n][3] or null
+  double *sq;               // [n][3] or null
+  DirectLight lights[RL_DIRECT_MAX_LIGHTS];
+};
+static_assert(sizeof(RtiowParams) + sizeof(NeeQuery) <= 4096, "the two by-value kernel arguments must fit the 4 KiB kernarg segment");
+
+// P: the scene's tables (hit_query_params + materials, textures, images, Perlin), cam, key, first_sample, row_first / row_step, stats;
+// FAST: also the query tree (fg_*, fg_top).
+// Register budget (DESIGN.md §3.22 has the table): compiled for two workgroups per SIMD row as rtiow_direct_kernel is, FAST takes all 256
+// VGPRs and spills 68 more to 276 bytes of scratch, so it is compiled for ONE (NEE_FAST_WG = 1) and spills nothing.
+constexpr int NEE_FAST_WG = 1;
+template <int NT, bool STATS, bool FAST, int SD>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) rtiow_nee_kernel(RtiowParams P, NeeQuery Q) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  unsigned long long *s_rng = (unsigned long long *)smem;                                 // [16][NT]
+  uint32_t *s_stack = (uint32_t *)(smem + (size_t)16 * NT * sizeof(unsigned long long));  // FAST: [SD][NT], both walks in turn
+  uint4 *s_top = (uint4 *)(s_stack + (size_t)NT * SD);                                    // FAST: [fg_top] FastNodeQ
+  const DevOp *ops = P.ops;
+  if (FAST && P.fg_top) {
+    for (uint32_t i = (uint32_t)tid; i < P.fg_top * 8u; i += (uint32_t)NT) s_top[i] = ((const uint4 *)P.fg_nodes)[i];
+    __syncthreads();
+  }
+  const rl_rtiow_camera &cam = P.cam;
+  const uint32_t W = cam.image_width, H = cam.image_height, S = cam.samples_per_pixel, L = Q.n_lights, K = Q.light_samples;
+  const uint32_t max_depth = cam.max_depth;
+  const uint64_t WH = (uint64_t)W * (uint64_t)H;
+  const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  const double T = Q.seg_tmax, kf = Q.kf;
+  Ring<NT, true, true> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
+  unsigned long long c_rays = 0, c_nodes = 0, c_sph = 0, c_pl = 0, c_inst = 0, c_flag = 0, c_words = 0, c_slow = 0;
+  for (unsigned long long idx = (unsigned long long)blockIdx.x * NT + tid; idx < Q.n; idx += (unsigned long long)gridDim.x * NT) {
+    uint32_t px, y;
+    if (Q.xs) px = Q.xs[idx], y = Q.ys[idx];
+    else px = (uint32_t)(idx % W), y = P.row_first + (uint32_t)(idx / W) * P.row_step;
+    D3 sum = d3(0.0, 0.0, 0.0), sum2 = d3(0.0, 0.0, 0.0);
+    const bool inside = px < W && y < H;  // (a list element outside the image, device form: zeros, nothing traced)
+#pragma unroll 1
+    for (uint32_t n = 0; inside && n < S; n++) {
+      const uint64_t sample_index = (uint64_t)n + P.first_sample;
+      rng.pos = 0u, rng.nres = 0;
+      rng.reset_stream(sample_index * WH + (uint64_t)px * (uint64_t)W + (uint64_t)y);
+      // 1. Camera::get_ray (rtiow_camera_rays_kernel)
+      D3 wo, wd;
+      {
+        D3 p00 = ld3(cam.pixel_00), du = ld3(cam.pixel_du), dv = ld3(cam.pixel_dv);
+        D3 pixel_center = (p00 + du * (double)px) + dv * (double)y;
+        double sx = -0.5 + rng.gen_f64();
+        double sy = -0.5 + rng.gen_f64();
+        D3 pixel_sample = pixel_center + (du * sx + dv * sy);
+        if (cam.defocus_angle <= 0.0) wo = ld3(cam.lookfrom);
+        else {
+          double a, b;
+          rng.unit_disc(a, b);
+          wo = (ld3(cam.lookfrom) + ld3(cam.defocus_disk_u) * a) + ld3(cam.defocus_disk_v) * b;
+        }
+        wd = pixel_sample - wo;
+      }
+      const double time = rng.gen_f64();
+      D3 c = d3(0.0, 0.0, 0.0), thr = d3(1.0, 1.0, 1.0);
+      bool count_emission = true;
+#pragma unroll 1
+      for (uint32_t i = 1; i <= max_depth; i++) {
+        // 2. world.hit(&ray, &Interval{1e-10, +inf})
+        c_rays++;
+        Rec rec;
+        if (FAST) {
+          bool slow;
+          c_flag += features_fast_trace<NT, SD>(P, ops, s_stack, s_top, tid, wo, wd, time, rec, slow);
+          if (slow) c_slow++;
+        } else {
+          rec = rec_none(INF);
+          GenCounters gc{0, 0, 0, 0, 0};
+          auto draw = []() { return 0.0; };
+          general_trace<STATS, false, true>(P, ops, 0u, NONE, wo, wd, wo, wd, time, 1e-10, rec, gc, draw);
+          c_nodes += gc.nodes, c_sph += gc.spheres, c_pl += gc.planars, c_inst += gc.instances, c_flag += gc.flagged;
+        }
+        if (!rec.any) {
+          c = c + thr * ld3(cam.background);
+          break;
+        }
+        const DevMaterial &m = P.materials[rec.mat];
+        // 3. the texture value: the Lambertian attenuation, the DiffuseLight emission
+        const D3 texc = material_texture<true>(m, [&](uint32_t tex) {
+          double tu, tv;
+          rec_uv(rec, tu, tv);
+          return texture_value<2>(P, tex, tu, tv, rec.p);
+        });
+        const D3 hp = rec.p, hn = rec.normal;
+        // 4. L x K light points: Ray{hit.p, yl - hit.p, ray.time} against Interval{1e-10, T}
+        const bool sampled = m.kind == RL_MAT_LAMBERTIAN && i < max_depth;
+        if (sampled) {
+          D3 dsum = d3(0.0, 0.0, 0.0);
+#pragma unroll 1
+          for (uint32_t l = 0; l < L; l++) {
+            const DirectLight &lt = Q.lights[l];
+#pragma unroll 1
+            for (uint32_t k = 0; k < K; k++) {
+              const double a = rng.gen_f64();
+              const double b = rng.gen_f64();
+              const D3 yl = (ld3(lt.Q) + ld3(lt.u) * a) + ld3(lt.v) * b;
+              const D3 sd = yl - hp;
+              const double d2 = len2(sd);
+              const double cs = dot(hn, sd);
+              const double cl = fabs(dot(ld3(lt.nl), sd));
+              if (!(cs > 0.0) || !(cl > 0.0) || !(d2 > 0.0)) continue;  // faces away, edge-on or degenerate: nothing traced
+              const double g = (cs * cl) / (d2 * d2);
+              c_rays++;
+              bool occluded = false, fold = !FAST;
+              if (FAST) {
+                const int w = ao_any_hit_walk<NT, SD>(P, ops, s_stack, s_top, tid, hp, sd, time, T);
+                occluded = w == AO_WALK_OCCLUDED;
+                if (w == AO_WALK_UNDECIDED) fold = true, c_slow++;
+              }
+              if (fold) {  // the reference's own fold: every segment of !FAST, the undecided ones of FAST
+                Rec orec = rec_none(T);
+                GenCounters gc{0, 0, 0, 0, 0};
+                auto draw = []() { return 0.0; };
+                general_trace<STATS, false, false>(P, ops, 0u, NONE, hp, sd, hp, sd, time, 1e-10, orec, gc, draw);
+                c_nodes += gc.nodes, c_sph += gc.spheres, c_pl += gc.planars, c_inst += gc.instances, c_flag += gc.flagged;
+                occluded = orec.any;
+              }
+              if (!occluded) dsum = d3(dsum.x + lt.E[0] * g, dsum.y + lt.E[1] * g, dsum.z + lt.E[2] * g);
+            }
+          }
+          c = c + ((thr * texc) * dsum) * kf;
+        }
+        // 5. mat.emitted and mat.scatter, drawing after the light points
+        const Scatter s = material_scatter<true>(m, wd, hn, rec.front, [&] { return texc; }, rng);
+        if (s.flagged) c_flag++;
+        if (count_emission) c = c + thr * s.emitted;  // (zeros unless the material is a DiffuseLight)
+        if (s.what != SCATTER_RAY) break;
+        thr = thr * s.att;
+        wo = hp, wd = s.dir;
+        count_emission = !sampled;
+      }
+      c_words += rng.pos;
+      sum = sum + c, sum2 = sum2 + c * c;
+    }
+    if (Q.sums) Q.sums[idx * 3 + 0] = sum.x, Q.sums[idx * 3 + 1] = sum.y, Q.sums[idx * 3 + 2] = sum.z;
+    if (Q.sq) Q.sq[idx * 3 + 0] = sum2.x, Q.sq[idx * 3 + 1] = sum2.y, Q.sq[idx * 3 + 2] = sum2.z;
+  }
+  unsigned long long v;
+  v = wave_sum(c_rays);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[0], v);
+  v = wave_sum(c_words);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[5], v);
+  v = wave_sum(c_flag);
+  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
+  if (FAST) {
+    v = wave_sum(c_slow);
+    if ((tid & 63) == 0 && v) atomicAdd(&P.stats[7], v);
+  }
+  if (STATS) {
+    v = wave_sum(c_nodes);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[1], v);
+    v = wave_sum(c_sph);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
+    v = wave_sum(c_pl);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[3], v);
+    v = wave_sum(c_inst);
+    if ((tid & 63) == 0) atomicAdd(&P.stats[4], v);
+  }
+}
+
+}  // namespace rl

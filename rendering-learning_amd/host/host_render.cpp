@@ -141,6 +141,25 @@ Camera::DirectLight Camera::render_direct(const Hittable &world, const std::vect
   if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_direct_rows: ") + rl_last_error());
   return dl;
 }
+Camera::Moments Camera::render_nee(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples, double seg_tmax,
+                                   uint64_t first_sample) const {
+  Flattened f;
+  f.root = world.flatten(f);
+  rl_rtiow_scene_desc d = f.desc();
+  rl_scene *sc = rl_rtiow_scene_create(&d);
+  if (!sc) throw std::runtime_error(std::string("rl_rtiow_scene_create: ") + rl_last_error());
+  rl_rtiow_camera cam = derived();
+  const size_t n = params.image_width * image_height;
+  std::vector<double> packed;  // [L][12]: Q, u, v, E
+  for (const QuadLight &l : lights)
+    for (const Vec3 *v : {&l.q, &l.u, &l.v, &l.emit}) packed.insert(packed.end(), v->e, v->e + 3);
+  Moments m{params.samples_per_pixel, std::vector<double>(3 * n), std::vector<double>(3 * n)};
+  int rc = rl_rtiow_render_nee_rows(sc, &cam, first_sample, 0, 1, (uint32_t)std::min<size_t>(lights.size(), 0xFFFFFFFFu), packed.data(), light_samples, seg_tmax,
+                                    m.sums.data(), m.sq.data(), nullptr);
+  rl_scene_destroy(sc);
+  if (rc != RL_OK) throw std::runtime_error(std::string("rl_rtiow_render_nee_rows: ") + rl_last_error());
+  return m;
+}
 Denoised denoise_atrous(size_t width, size_t height, uint32_t iterations, const rl_atrous_params &params, const std::vector<double> &color,
                         const std::vector<double> &variance, const std::vector<double> &guides) {
   const size_t n = width * height;

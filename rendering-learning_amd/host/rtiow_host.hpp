@@ -871,6 +871,12 @@ struct Camera {
   };
   DirectLight render_direct(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples, double seg_tmax = 1.0 - 1e-6,
                             uint64_t first_sample = 0) const;
+  // an NEE path render (rl_rtiow_render_nee_rows): ray_color with next-event estimation, max_depth vertices; every Lambertian vertex but the
+  // last connects to light_samples points on each quad light (render_direct's draws, geometry term and segment) and the emission its
+  // scattered ray finds is not counted.  `lights` must list every DiffuseLight surface of the world for the estimate to have ray_color's
+  // expectation.  -> render_moments' sums and second moments, [H][W][3].  Worlds with a ConstantMedium are refused.
+  Moments render_nee(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples = 1, double seg_tmax = 1.0 - 1e-6,
+                     uint64_t first_sample = 0) const;
 };
 // Camera::render_ao as a function of the camera and the world
 inline Camera::AmbientOcclusion render_ao(const Camera &camera, const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample = 0) {
@@ -880,6 +886,11 @@ inline Camera::AmbientOcclusion render_ao(const Camera &camera, const Hittable &
 inline Camera::DirectLight render_direct(const Camera &camera, const Hittable &world, const std::vector<Camera::QuadLight> &lights, uint32_t light_samples,
                                          double seg_tmax = 1.0 - 1e-6, uint64_t first_sample = 0) {
   return camera.render_direct(world, lights, light_samples, seg_tmax, first_sample);
+}
+// Camera::render_nee as a function of the camera and the world
+inline Camera::Moments render_nee(const Camera &camera, const Hittable &world, const std::vector<Camera::QuadLight> &lights, uint32_t light_samples = 1,
+                                  double seg_tmax = 1.0 - 1e-6, uint64_t first_sample = 0) {
+  return camera.render_nee(world, lights, light_samples, seg_tmax, first_sample);
 }
 
 // ---------------------------------------------------------------- denoising (rl_denoise_atrous; defined in host_render.cpp)

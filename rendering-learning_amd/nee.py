@@ -1,0 +1,104 @@
+"""NEE path renders (include/rl_render.h "NEE path renders", rl_rtiow_render_nee*).
+
+Camera::ray_color with next-event estimation: per pixel, over the camera's samples_per_pixel jittered camera rays (those of render_independent,
+render_features, render_ao and render_direct), a path of at most max_depth vertices that, at every Lambertian vertex but the last, connects to
+light_samples points drawn on each quad light from the sample's own stream (render_direct's draws, geometry term and shadow segment) and in
+exchange does not count the emission its scattered ray finds.  `lights` must list every DiffuseLight surface of the scene for the estimate
+to have ray_color's expectation.  The outputs are render_moments': the sum of the sample colours and the sum of their squares.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import api
+from .direct import SEG_TMAX, pack_lights
+
+OUTPUTS = ("sums", "sq")
+
+
+class PathNEE:
+    """sums, sq: float64 [..., 3] (None where not asked for); samples: the camera's samples_per_pixel; light_samples: the K of the render."""
+
+    def __init__(self, sums, sq, samples, light_samples):
+        self.sums, self.sq, self.samples, self.light_samples = sums, sq, int(samples), int(light_samples)
+
+    def moments(self):
+        """-> api.Moments(samples, sums, sq): what variance_of_mean, merge and denoise_render take from render_moments."""
+        if self.sums is None or self.sq is None:
+            raise ValueError("moments needs sums and sq")
+        return api.Moments(self.samples, self.sums, self.sq)
+
+    def mean(self):
+        if self.sums is None:
+            raise ValueError("mean needs sums")
+        return self.sums / float(self.samples)
+
+
+def _host(want, shape):
+    want = OUTPUTS if want is None else tuple(want)
+    if not want or any(k not in OUTPUTS for k in want):
+        raise ValueError(f"want must be a non-empty subset of {OUTPUTS}")
+    a = {k: None for k in OUTPUTS}
+    for k in want:
+        a[k] = np.zeros(tuple(shape) + (3,), dtype=np.float64)
+    return a, [None if a[k] is None else C.c_void_p(a[k].ctypes.data) for k in OUTPUTS]
+
+
+def _scalars(lights, light_samples, seg_tmax):
+    L = pack_lights(lights)
+    return L, (L.shape[0], C.c_void_p(L.ctypes.data), int(light_samples), float(seg_tmax))
+
+
+def render_nee(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, first_sample=0, row_first=0, row_step=1, stats=None, want=None,
+               allow_degenerate=False):
+    """Compact shard rows -> PathNEE([nrows, W, 3]).  Always a counting call (reference-order trace), as render_direct."""
+    nrows = api.rows_for(camera.c.image_height, row_first, row_step)
+    a, ptrs = _host(want, (nrows, camera.c.image_width))
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_nee_rows, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, *ptrs, stats=stats,
+              counting=True, allow_degenerate=allow_degenerate)
+    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+
+
+def render_nee_device(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, stream=0, row_first=0, row_step=1, first_sample=0, stats=None,
+                      allow_degenerate=False, *, d_sums=0, d_sq=0):
+    """Outputs stay in HBM: device pointers of nrows*W*3 float64 each; 0 = not wanted.  Async and counter-free unless stats is a dict.  The
+    lights are copied into the launch: nothing of `lights` is read after the call returns."""
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_nee_device, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc,
+              C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+
+
+def render_pixels_nee(camera, world, xs, ys, lights, light_samples=1, seg_tmax=SEG_TMAX, first_sample=0, stats=None, want=None, allow_degenerate=False):
+    """The values of pixels (xs[i], ys[i]), [n, 3]: what render_nee holds at [ys[i], xs[i]].  The list rules are render_pixels_direct's.
+    stats (a dict): a counting call; without it the call is counter-free and may take the fast walks (api.last_query())."""
+    xs, ys = api._pixel_list(xs, ys)
+    a, ptrs = _host(want, (xs.size,))
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_pixels_nee, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, *sc, *ptrs,
+              stats=stats, allow_degenerate=allow_degenerate)
+    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+
+
+def render_pixels_nee_device(camera, world, d_xs, d_ys, n, lights, light_samples=1, seg_tmax=SEG_TMAX, stream=0, first_sample=0, stats=None,
+                             allow_degenerate=False, *, d_sums=0, d_sq=0):
+    """d_xs / d_ys: device pointers of n uint32; outputs as render_nee_device with n pixels.  Async unless stats is a dict; an element outside
+    the image is written as zeros in every given output."""
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_pixels_nee_device, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
+              *sc, C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+
+
+def cpp_mirror_probe(width, spp, first_sample, lights, light_samples, seg_tmax=SEG_TMAX):
+    """rtiow::render_nee of the C++ mirror on golden_test_scene at image_width = width -> PathNEE([H, W, 3]) (the height is the scene's
+    aspect ratio's).  For tests of the mirror; RLError carries rlh_last_error."""
+    H = api.host_lib()
+    world = api.World.golden_test_scene()
+    p = world.params
+    p.image_width, p.samples_per_pixel = int(width), int(spp)
+    cam = api.Camera(p)
+    a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    if H.rlh_nee_probe(int(width), int(spp), int(first_sample), *sc, *ptrs) != 0:
+        raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
+    return PathNEE(a["sums"], a["sq"], spp, light_samples)
