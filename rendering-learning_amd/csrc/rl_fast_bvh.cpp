@@ -185,6 +185,57 @@ bool build_fast_bvh(const rl_rtiow_scene_desc &d, const RtiowProgram &rt, const 
   return true;
 }
 
+// ---- centre / half-extent form of the nodes (what the wave kernels' TRAV step reads; derivation at ray_aux32_direct, rl_rtiow_wave.h).
+// Per axis c = the binary32 nearest the midpoint of [lo, hi] and h = the smallest binary32 with c - h <= lo - delta and c + h >= hi + delta,
+// both inequalities decided EXACTLY (sums of a few binary64 numbers, by expansions).  delta = 8u (|c| + (hi - lo)), u = 2^-24: the step's
+// rounding errors that do not scale with the ray's own t or |o / d| are at most 4.01u |c| + 3.01u h in space units, so this is twice the
+// |c| term and more than five times the h term (h <= (hi - lo) / 2 + delta + an ulp of c and of h).
+namespace {
+// sign of x[0] + ... + x[n-1], exactly (n <= 8): Shewchuk's grow-expansion; the largest component of a nonoverlapping expansion has its sign
+int sum_sign(const double *x, int n) {
+  double e[8];
+  int m = 0;
+  for (int i = 0; i < n; i++) {
+    double q = x[i];
+    for (int j = 0; j < m; j++) {  // two-sum: q + e[j] = s + err exactly
+      const double s = q + e[j], bv = s - q, av = s - bv;
+      e[j] = (q - av) + (e[j] - bv), q = s;
+    }
+    e[m++] = q;
+  }
+  for (int j = m - 1; j >= 0; j--)
+    if (e[j] != 0.0) return e[j] > 0.0 ? 1 : -1;
+  return 0;
+}
+}  // namespace
+
+double fast_ch_delta(float c, float lo, float hi) { return 4.76837158203125e-07 * (std::fabs((double)c) + ((double)hi - (double)lo)); }  // 8u
+
+FastNodeCH fast_node_ch(const FastNode &nd) {
+  FastNodeCH out{};
+  out.child = nd.child;
+  for (int side = 0; side < 2; side++)
+    for (int ax = 0; ax < 3; ax++) {
+      const float lo = nd.box[side][2 * ax], hi = nd.box[side][2 * ax + 1];
+      float c = (float)(0.5 * (double)lo + 0.5 * (double)hi), h = NAN;
+      if (std::isfinite(lo) && std::isfinite(hi) && lo <= hi) {
+        const double delta = fast_ch_delta(c, lo, hi);
+        auto encloses = [&](float hh) {
+          const double below[4] = {(double)c, -(double)hh, -(double)lo, delta}, above[4] = {(double)hi, delta, -(double)c, -(double)hh};
+          return sum_sign(below, 4) <= 0 && sum_sign(above, 4) <= 0;
+        };
+        h = round_up(std::fmax((double)c - (double)lo, (double)hi - (double)c) + delta);
+        while (std::isfinite(h) && !encloses(h)) h = std::nextafterf(h, INFINITY);  // (the binary64 sum above may have rounded down)
+        for (float t = std::nextafterf(h, 0.0f); std::isfinite(h) && t < h && encloses(t); t = std::nextafterf(h, 0.0f)) h = t;
+        // (h = +inf, a box beyond binary32's range: t_near = -inf, t_far = +inf, the axis never rejects)
+      } else {
+        c = NAN;  // no finite box: NaN arithmetic in the step, no comparison holds, the child is visited (build_fast_bvh makes none)
+      }
+      out.ch[side][ax] = c, out.ch[side][3 + ax] = h;
+    }
+  return out;
+}
+
 // The ball the entry table tests a leaf's sphere with: centre at time 1/2, R = r + pad + |dc| / 2, where pad is the largest of the three pads
 // of the sphere's leaf box above (>= guard_pad: a ray that stays R away from this centre stays r + guard_pad away from the centre at every
 // time in [0, 1], and its rounded discriminant is negative).  Everything is rounded upwards by a relative 1e-12, thousands of roundings.

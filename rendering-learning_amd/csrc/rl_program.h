@@ -65,6 +65,17 @@ struct alignas(16) FastNode {
   uint32_t pad[3];
 };
 static_assert(sizeof(FastNode) == 64, "FastNode must be 64 B");
+// The form of the same node that the wave kernels stage into LDS: each child box as centre and half-extent, so that the step's slab test
+// needs no ordering of a slab's two planes (rl_rtiow_wave.h ray_aux32_direct).  Derived from a FastNode by fast_node_ch; same child word.
+struct alignas(16) FastNodeCH {
+  float ch[2][6];  // [child][c.x, c.y, c.z, h.x, h.y, h.z]
+  uint32_t child;  // eA | eB << 16
+  uint32_t pad[3];
+};
+static_assert(sizeof(FastNodeCH) == 64, "FastNodeCH must be 64 B");
+// How far the box [c - h, c + h] must reach beyond [lo, hi] on one axis: the space-unit share of the step's rounding errors, twice over
+double fast_ch_delta(float c, float lo, float hi);
+FastNodeCH fast_node_ch(const FastNode &nd);
 
 struct alignas(16) DevSphere {  // 64 B
   double c0[3];

@@ -321,7 +321,7 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
       (rc = scene_common(s)) ||
       (!H->lops.empty() && ((rc = s->d_lops.upload(H->lops)) || (rc = s->d_sphere_flat.upload(H->sphere_flat)))) ||
       (!H->cops.empty() && ((rc = s->d_cops.upload(H->cops)) || (rc = s->d_movbits.upload(H->movbits)))) ||
-      (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)) ||
+      (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_nodes_ch.upload(H->fast_nodes_ch)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)) ||
                                       (rc = s->d_fast_leaf_balls.upload(H->fast_leaf_balls)))) ||
       (QF.ok && ((rc = s->d_fg_nodes.upload(QF.qnodes)) || (rc = s->d_fg_seg_roots.upload(QF.stage_roots)) ||
                  (rc = s->d_fg_media.upload(QF.media)) || (rc = s->d_fg_items.upload(QF.items)) || (rc = s->d_fg_spheres.upload(QF.item_spheres)) || (rc = s->d_fg_material.upload(QF.item_material))))) {
@@ -443,7 +443,7 @@ static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, 
   P.n_ops = (uint32_t)rt.ops.size(), P.n_spheres = (uint32_t)rt.spheres.size();
   P.lops = scene->d_lops, P.entry0 = H.entry0, P.sphere_flat = scene->d_sphere_flat;
   P.cops = scene->d_cops, P.n_cops = (uint32_t)H.cops.size(), P.centry0 = H.centry0, P.movbits = scene->d_movbits;
-  P.fast_nodes = scene->d_fast_nodes, P.n_fast_inner = (uint32_t)H.fast_nodes.size(), P.fast_root = H.fast_root;
+  P.fast_nodes = scene->d_fast_nodes, P.fast_nodes_ch = scene->d_fast_nodes_ch, P.n_fast_inner = (uint32_t)H.fast_nodes.size(), P.fast_root = H.fast_root;
   P.fg_nodes = scene->d_fg_nodes, P.fg_items = scene->d_fg_items, P.fg_spheres = scene->d_fg_spheres, P.fg_material = scene->d_fg_material, P.fg_root = H.fg.qroot, P.fg_rsafe2 = H.fg.r_safe * H.fg.r_safe * 0.9999f;  // binary32 evaluation on the device: keep a margin
   P.fg_seg_roots = scene->d_fg_seg_roots, P.fg_media = scene->d_fg_media, P.fg_n_seg = (uint32_t)H.fg.stage_roots.size();
   P.fg_top = 0;  // (set by the launch that stages it: fastg_prepare)
@@ -512,7 +512,7 @@ static int choose_rtiow_variant(const rl_scene *scene, const rl_rtiow_camera *ca
   }
   // 1029 = the FAST traversal (ordered binary tree, reject-only boxes, exact re-trace of ambiguous rays): counter-free renders only —
   // its box / sphere test counts are not the reference's, so a render that asks for rl_stats runs the counting kernel (1027)
-  const size_t fast_bytes = ((size_t)P.n_fast_inner * sizeof(FastNode) + 2 * (((size_t)P.n_spheres + 31) / 32 + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
+  const size_t fast_bytes = ((size_t)P.n_fast_inner * sizeof(FastNodeCH) + 2 * (((size_t)P.n_spheres + 31) / 32 + 1) * sizeof(uint32_t) + 15) & ~(size_t)15;
   const bool fits_fast = fits_compact && H.fast_root != FAST_NONE && (!want_stats || g_fast_debug_stats) && (size_t)16 * 1024 * sizeof(unsigned long long) + fast_bytes <= g_lds_max &&
                          g_sw.fast_traversal;
   const bool fits_ops = (size_t)16 * 1024 * sizeof(unsigned long long) + (size_t)P.n_ops * sizeof(DevOp) <= g_lds_max;

@@ -40,6 +40,7 @@ struct RtiowParams {
   const uint32_t *movbits;  // ... one bit per sphere: Center::Moving
   uint32_t n_cops, centry0;
   const FastNode *fast_nodes;  // wave kernel LDS_SCENE = 4: the fast traversal structure (n_fast_inner nodes; entry ids, rl_program.h)
+  const FastNodeCH *fast_nodes_ch;  // ... the same nodes as centre / half-extent boxes: what the wave kernels stage into LDS and step through
   uint32_t n_fast_inner, fast_root;
   const FastNodeQ *fg_nodes;  // rl_rtiow_fastgen.h: fast traversal structure of a general scene (rl_fast_bvh.cpp build_fast_general)
   const DevSphere *fg_spheres;  // [item] sphere record of sphere items

@@ -27,9 +27,8 @@
 
 namespace rl {
 
-#ifndef RL_PK_FMA
-#define RL_PK_FMA 0  // the slab test's plane pairs as v_pk_fma_f32: measured 6750 -> 6600 Mrays/s — the broadcast operand pairs cost moves, one VGPR spills
-#endif
+// (RL_PK_FMA, the lo / hi slab test's plane pairs as v_pk_fma_f32, went with that form of the step: measured 6750 -> 6600 Mrays/s — the
+// broadcast operand pairs cost moves, one VGPR spilled)
 #ifndef RL_SPLIT_LEAF
 #define RL_SPLIT_LEAF false
 #endif
@@ -308,6 +307,27 @@ __device__ __forceinline__ bool aabb_fast32(const float *b, const RayAux32 &ra, 
 // (the bound for both ends together, plus room for the roundings of this comparison itself).  Rays with a zero, denormal-scale or
 // huge direction component or a far-away origin get slack = +inf: nothing is ever certain for them, and start_ray() sends them
 // to the reference-order fold.
+//
+// The wave kernels' TRAV step (LDS_SCENE = 4) reads its boxes as centre c and half-extent h (FastNodeCH) and forms per axis
+//   t_c'' = fma(c, inv32, -oi32),  t_near'' = fma(-h, |inv32|, t_c''),  t_far'' = fma(h, |inv32|, t_c''),
+// tmin'' = max(t_near'' of the three axes, 1e-10f), tmax'' = min(t_far'' of the three, closest32), with the same decision.  The bound
+// above does not carry over as it stands: it rests on every plane's t'' being off by a multiple of |t''| ITSELF (and of max|o/d|), which
+// survives min and max, whereas t_near'' inherits the rounding of t_c'', a multiple of |t_c| that can be far larger than |t_near|.
+// Per axis, with t_c = (c - o)/d, t_near = t_c - h/|d| (exact values for the STORED box) and oi32 = o32 inv32 (1 + e), |e| <= u:
+//   c inv32 - oi32 = inv32 (c - o) + inv32 (o - o32) - o32 inv32 e: off from t_c by <= 3u|t_c| + 2.01u|o/d|, and <= u|t_c''| more in the fma;
+//   h |inv32| is off from h/|d| by <= 3u h/|d|, and the second fma adds <= u|t_near''|:
+//   |t_near'' - t_near| <= 4.01u|t_c| + 3u h/|d| + 2.01u|o/d| + u|t_near''| <= (4.01u|c| + 3u h)/|d| + 6.02u|o/d| + u|t_near''|
+// by |t_c| <= |c|/|d| + |o/d|; the same for t_far''.  The first term is a length, (4.01u|c| + 3u h), over |d|: moving the slab's planes
+// outwards by that length changes t_near and t_far by exactly that much.  So the host stores every box with c - h <= lo - delta and
+// c + h >= hi + delta, delta = 8u(|c| + hi - lo) per node, child and axis (rl_fast_bvh.cpp fast_node_ch: twice the |c| term, five times
+// the h term), where [lo, hi] is the FastNode's outward-rounded box, and then against the planes of [lo, hi] itself
+//   t_near'' <= t_near[lo] + 6.02u max|o/d| + u|t_near''|,   t_far'' >= t_far[hi] - 6.02u max|o/d| - u|t_far''|:
+// errors relative to the value itself again, which max and min preserve; the clamps 1e-10f and closest32 add u of themselves.  A ray
+// that touches [lo, hi] inside [1e-10, closest] therefore has tmin'' - tmax'' <= 1.01u(|tmin''| + |tmax''|) + 12.04u max|o/d|, and the
+// decision keeps its constants, 12u(|tmin''| + |tmax''|) + 24u max|oi32|: twice the per-ray part (max|oi32| >= (1 - 5u) max|o/d|) and
+// far more than the relative part, with room for the roundings of the subtraction, of the threshold and of the comparison.  No
+// per-ray constant is added.  As before all of this needs NORMAL binary32 results (an fma that underflows is off by <= 2^-126, far
+// below 12u * 1e-10, the smallest threshold); an infinite or NaN t'' makes the comparison false, and the child is visited.
 __device__ __forceinline__ RayAux32 ray_aux32_direct(D3 o, D3 d) {
   RayAux32 r;
   float dx = (float)d.x, dy = (float)d.y, dz = (float)d.z;

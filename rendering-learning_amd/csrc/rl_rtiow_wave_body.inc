@@ -4,7 +4,7 @@
   const int tid = threadIdx.x;
   // LDS layout: [linked ops][spheres][ChaCha rings 16 x NT u64]; with the scene in HBM the rings start at 0
   const size_t bits_words = ((size_t)P.n_spheres + 31) / 32 + 1;
-  const size_t scene_lds = LDS_SCENE == 4   ? (((size_t)P.n_fast_inner * sizeof(FastNode) + 2 * bits_words * sizeof(uint32_t) + 15) & ~(size_t)15)
+  const size_t scene_lds = LDS_SCENE == 4   ? (((size_t)P.n_fast_inner * sizeof(FastNodeCH) + 2 * bits_words * sizeof(uint32_t) + 15) & ~(size_t)15)
                            : LDS_SCENE == 3 ? (((size_t)P.n_cops * sizeof(CompactOp) + bits_words * sizeof(uint32_t) + 15) & ~(size_t)15)
                            : LDS_SCENE      ? ((size_t)P.n_ops * sizeof(DevOp) + (LDS_SCENE == 1 ? (size_t)P.n_spheres * sizeof(DevSphere) : 0))
                                             : 0;
@@ -14,10 +14,10 @@
   const uint32_t *s_bits = nullptr;  // LDS_SCENE == 3: one bit per sphere (Center::Moving)
   const uint32_t lds_base = (uint32_t)(uintptr_t)smem;  // the dynamic LDS segment's own address (low half of the flat address)
   if (LDS_SCENE == 4) {
-    const uint4 *g = (const uint4 *)P.fast_nodes;
+    const uint4 *g = (const uint4 *)P.fast_nodes_ch;
     uint4 *l = (uint4 *)smem;
     for (uint32_t i = tid; i < P.n_fast_inner * 4u; i += NT) l[i] = g[i];
-    uint32_t *bl = (uint32_t *)(smem + (size_t)P.n_fast_inner * sizeof(FastNode));
+    uint32_t *bl = (uint32_t *)(smem + (size_t)P.n_fast_inner * sizeof(FastNodeCH));
     for (uint32_t i = tid; i < 2u * (uint32_t)bits_words; i += NT) bl[i] = P.movbits[i];  // [moving bits][specular-material bits]
     __syncthreads();
     opbase = smem;
@@ -360,20 +360,13 @@
             const Float4 q0 = nd[0], q1 = nd[1], q2 = nd[2];
             const uint32_t w = *(LdsU32 *)(size_t)(pc + 48u);
             const float c32 = (float)closest;
-            auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) {
-#if RL_PK_FMA  // both planes of a slab in one v_pk_fma_f32 (same IEEE fma per component)
-              typedef float F2 __attribute__((ext_vector_type(2)));
-              const F2 tx = __builtin_elementwise_fma(F2{b0, b1}, F2{ra32.invx, ra32.invx}, F2{-ra32.oix, -ra32.oix});
-              const F2 ty = __builtin_elementwise_fma(F2{b2, b3}, F2{ra32.invy, ra32.invy}, F2{-ra32.oiy, -ra32.oiy});
-              const F2 tz = __builtin_elementwise_fma(F2{b4, b5}, F2{ra32.invz, ra32.invz}, F2{-ra32.oiz, -ra32.oiz});
-              const float t0x = tx.x, t1x = tx.y, t0y = ty.x, t1y = ty.y, t0z = tz.x, t1z = tz.y;
-#else
-              float t0x = fmaf(b0, ra32.invx, -ra32.oix), t1x = fmaf(b1, ra32.invx, -ra32.oix);
-              float t0y = fmaf(b2, ra32.invy, -ra32.oiy), t1y = fmaf(b3, ra32.invy, -ra32.oiy);
-              float t0z = fmaf(b4, ra32.invz, -ra32.oiz), t1z = fmaf(b5, ra32.invz, -ra32.oiz);
-#endif
-              tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)), 1e-10f);
-              float tmax = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)), c32);
+            // a child box as centre c and half-extent h (FastNodeCH): per axis the ray enters the slab at t_c - h |1/d| and leaves it at
+            // t_c + h |1/d|, whatever the sign of d, so no min / max orders a slab's two planes (error bound and the host's pad: ray_aux32_direct)
+            auto missed = [&](float cx, float cy, float cz, float hx, float hy, float hz, float &tmin) {
+              const float tcx = fmaf(cx, ra32.invx, -ra32.oix), tcy = fmaf(cy, ra32.invy, -ra32.oiy), tcz = fmaf(cz, ra32.invz, -ra32.oiz);
+              const float ax = fabsf(ra32.invx), ay = fabsf(ra32.invy), az = fabsf(ra32.invz);
+              tmin = fmaxf(fmaxf(fmaxf(fmaf(-hx, ax, tcx), fmaf(-hy, ay, tcy)), fmaf(-hz, az, tcz)), 1e-10f);
+              float tmax = fminf(fminf(fminf(fmaf(hx, ax, tcx), fmaf(hy, ay, tcy)), fmaf(hz, az, tcz)), c32);
               float diff = tmax - tmin;
               float thresh = fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
               return diff < -thresh;  // certainly tmin > tmax; false for NaN arithmetic: visit
@@ -382,7 +375,7 @@
             if (STATS && (depth & DEPTH_MASK) == cam.max_depth) c_cam_trav++;
             float tA, tB;
             const uint32_t eA = w & 0xFFFFu, eB = w >> 16, self = depth >> 22;  // self: the sphere the ray left, proven missed (fast_self_miss)
-            const bool boxA = !missed(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tA);
+            const bool boxA = !missed(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, tA);  // {c.xyz, h.xyz} of child A, then of child B
             const bool boxB = !missed(q1.z, q1.w, q2.x, q2.y, q2.z, q2.w, tB);
             const bool hitA = boxA && eA != self, hitB = boxB && eB != self;
             if (STATS) c_self += (boxA && !hitA) + (boxB && !hitB);

@@ -41,6 +41,7 @@ struct rl_scene {
   rl::DevBuf<rl::CompactOp> d_cops;
   rl::DevBuf<uint32_t> d_movbits;
   rl::DevBuf<rl::FastNode> d_fast_nodes;
+  rl::DevBuf<rl::FastNodeCH> d_fast_nodes_ch;
   rl::DevBuf<float> d_fast_leaf_boxes;
   rl::DevBuf<double> d_fast_leaf_balls;
   rl::DevBuf<uint32_t> d_coop_pixels;  // cooperative kernel: pixel list (scratch, grown on demand)

@@ -168,6 +168,8 @@ static int build_host_rtiow_may_throw(const rl_rtiow_scene_desc *desc, std::shar
     if (!H->cops.empty() && !build_fast_bvh(*desc, rt, frame, H->fast_nodes, H->fast_root)) H->fast_nodes.clear(), H->fast_root = FAST_NONE;
     if (H->fast_root != FAST_NONE) {  // the spheres' own (padded) leaf boxes, by sphere index: what the cooperative kernel scans
       const uint32_t n_inner = (uint32_t)H->fast_nodes.size(), ns = (uint32_t)rt.spheres.size();
+      H->fast_nodes_ch.reserve(n_inner);
+      for (const FastNode &nd : H->fast_nodes) H->fast_nodes_ch.push_back(fast_node_ch(nd));
       H->fast_leaf_boxes.assign((size_t)ns * 8, 0.0f);
       for (uint32_t s = 0; s < ns; s++)  // a sphere the tree does not hold (n == 1: no node at all) is always a candidate
         for (int k = 0; k < 3; k++) H->fast_leaf_boxes[(size_t)s * 8 + 2 * k] = -3.0e38f, H->fast_leaf_boxes[(size_t)s * 8 + 2 * k + 1] = 3.0e38f;

@@ -21,6 +21,7 @@ struct HostRtiow {
   uint32_t entry0 = 0, centry0 = 0;
   std::vector<FastNode> fast_nodes;  // fast traversal structure (rl_fast_bvh.cpp); fast_root == FAST_NONE: the scene does not qualify
   uint32_t fast_root = FAST_NONE;
+  std::vector<FastNodeCH> fast_nodes_ch;  // fast_nodes as centre / half-extent boxes: what the wave kernels stage into LDS (fast_node_ch)
   std::vector<float> fast_leaf_boxes;  // [n_spheres][8]: each sphere's padded leaf box of the fast tree (rl_rtiow_coop.h)
   std::vector<double> fast_leaf_balls;  // [n_spheres][4]: centre and radius of a ball around each padded sphere (rl_fast_bvh.cpp fast_leaf_balls)
   FastGeneral fg;  // fast traversal structure of a general scene (fg.ok == false: the scene does not qualify)
