@@ -95,6 +95,14 @@ struct alignas(16) DevPlanar {  // 128 B core (plane.rs:12-20) + optional per-ve
 };
 
 static const uint32_t MAT_TEX_SOLID = 0x100u;  // flag in a flattened per-sphere material's kind: albedo holds the Solid texture's colour
+// flag in a flattened per-sphere material's kind: the texture is a Checker of two Solid colours — albedo holds the even one, and the
+// sphere's DevChecker record the odd one and inv_scale (rl_scene_host.cpp flatten_sphere_materials)
+static const uint32_t MAT_TEX_CHECKER = 0x200u;
+struct alignas(16) DevChecker {  // 32 B, one per sphere beside its flattened material; all zero where the flag is not set
+  double odd[3];
+  double inv_scale;
+};
+static_assert(sizeof(DevChecker) == 32, "DevChecker must be 32 B");
 struct DevMaterial {  // 48 B
   uint32_t kind, texture;
   double albedo[3];

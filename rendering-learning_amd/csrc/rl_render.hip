@@ -319,7 +319,7 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
       (rc = s->d_materials.upload(rt.materials)) || (rc = s->d_textures.upload(rt.textures)) || (rc = s->d_images.upload(rt.images)) ||
       (rc = s->d_image_pool.upload(rt.image_pool)) || (rc = s->d_perlins.upload(rt.perlins)) || (rc = s->d_media.upload(rt.media)) ||
       (rc = scene_common(s)) ||
-      (!H->lops.empty() && ((rc = s->d_lops.upload(H->lops)) || (rc = s->d_sphere_flat.upload(H->sphere_flat)))) ||
+      (!H->lops.empty() && ((rc = s->d_lops.upload(H->lops)) || (rc = s->d_sphere_flat.upload(H->sphere_flat)) || (rc = s->d_sphere_checker.upload(H->sphere_checker)))) ||
       (!H->cops.empty() && ((rc = s->d_cops.upload(H->cops)) || (rc = s->d_movbits.upload(H->movbits)))) ||
       (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_nodes_ch.upload(H->fast_nodes_ch)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)) ||
                                       (rc = s->d_fast_leaf_balls.upload(H->fast_leaf_balls)))) ||
@@ -441,7 +441,7 @@ static int fill_rtiow_params(const rl_scene *scene, const rl_rtiow_camera *cam, 
   P.planars = scene->d_planars, P.translates = scene->d_translates, P.transforms = scene->d_transforms;
   P.materials = scene->d_materials, P.textures = scene->d_textures, P.images = scene->d_images, P.image_pool = scene->d_image_pool, P.perlins = scene->d_perlins, P.media = scene->d_media;
   P.n_ops = (uint32_t)rt.ops.size(), P.n_spheres = (uint32_t)rt.spheres.size();
-  P.lops = scene->d_lops, P.entry0 = H.entry0, P.sphere_flat = scene->d_sphere_flat;
+  P.lops = scene->d_lops, P.entry0 = H.entry0, P.sphere_flat = scene->d_sphere_flat, P.sphere_checker = scene->d_sphere_checker;
   P.cops = scene->d_cops, P.n_cops = (uint32_t)H.cops.size(), P.centry0 = H.centry0, P.movbits = scene->d_movbits;
   P.fast_nodes = scene->d_fast_nodes, P.fast_nodes_ch = scene->d_fast_nodes_ch, P.n_fast_inner = (uint32_t)H.fast_nodes.size(), P.fast_root = H.fast_root;
   P.fg_nodes = scene->d_fg_nodes, P.fg_items = scene->d_fg_items, P.fg_spheres = scene->d_fg_spheres, P.fg_material = scene->d_fg_material, P.fg_root = H.fg.qroot, P.fg_rsafe2 = H.fg.r_safe * H.fg.r_safe * 0.9999f;  // binary32 evaluation on the device: keep a margin

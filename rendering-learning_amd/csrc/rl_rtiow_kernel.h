@@ -105,6 +105,9 @@ struct RtiowParams {
   // wave kernels (rl_rtiow_wave.h Ring::coop_blocks): non-zero = thin block passes run four lanes to a block and FILL generates wave-wide;
   // 0 (RL_COOP_QUAD=0) = lane-per-block passes only, FILL per lane.  Same blocks in the same ring slots either way.
   uint32_t coop_quad;
+  // wave kernels' SHADE: beside sphere_flat, one 32-byte record per sphere — the odd colour and inv_scale of a Checker of two Solid colours
+  // (MAT_TEX_CHECKER; zeros otherwise), fetched by sphere index in the same round trip as the flattened material
+  const DevChecker *sphere_checker;
 };
 
 // MOMENTS, the compile-time flavour of the chained render kernels that keeps second moments (P.out_sq), is `false` in every kernel without

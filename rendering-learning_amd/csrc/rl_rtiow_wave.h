@@ -37,6 +37,13 @@ namespace rl {
 #ifndef RL_COOP_GEN
 #define RL_COOP_GEN 1
 #endif
+// A/B: the unit-sphere draw of SHADE in at most this many tries per visit (0 = unbounded: the rejection loop runs to its end); a lane without
+// an accepted draw stays in ST_SHADE and draws on at its next pick.  Measured and lost, like SPLIT_SHADE and SPLIT_LEAF (the extra SHADE
+// visits thin the other blocks, and the colour's loads become a second round behind the draw): 483.2 ms per step unbounded, 534.5 with
+// one try, 492.3 with two, the parent 494.4; 121 VGPRs in the headline kernel instead of 118 (profiles/shade_tail.txt section 7)
+#ifndef RL_SHADE_TRIES
+#define RL_SHADE_TRIES 0
+#endif
 // tools/wave_codegen.py finds the scheduler loop's header, its blocks and the TRAV step in a kernel's assembly by these comment lines (no code)
 #define RL_CG_MARK(name) asm volatile("; rl_cg " name)
 // (the scheduler states ST_GEN .. ST_LEAF2: rl_program.h, beside the successor words that encode them)
@@ -207,6 +214,35 @@ struct Ring {
       double f = 2.0 * sqrt(1.0 - s);
       return D3{x1 * f, x2 * f, 1.0 - 2.0 * s};
     }
+  }
+  // unit_sphere() with the point formed BEHIND the loop, which only finds the accepted (x1, x2, s): the wave kernels' SHADE
+  // (rl_rtiow_wave_body.inc).  Returned from inside the loop, the accepted draw's arithmetic (the correctly rounded sqrt's expansion:
+  // 24 VALU instructions, 20 of them binary64) sits in the loop's accept branch, and a wave runs that branch in every iteration in which
+  // any of its lanes accepts — about three times per SHADE block where once will do.  Same operations in the same order on the same
+  // accepted values.  (The other kernels that draw from a Ring keep the form above: with this one some rtiow_fast_general instantiations
+  // spill up to 8 more VGPRs, tools/kernel_regs.py.)
+  __device__ __forceinline__ D3 unit_sphere_tail() {
+    double x1, x2, s;
+    do {
+      x1 = uniform_m1_1(), x2 = uniform_m1_1();
+      s = x1 * x1 + x2 * x2;
+    } while (s >= 1.0);
+    double f = 2.0 * sqrt(1.0 - s);
+    return D3{x1 * f, x2 * f, 1.0 - 2.0 * s};
+  }
+  // unit_sphere_tail() in at most TRIES tries: false when none was accepted (the tried words are consumed; the caller draws on later)
+  template <int TRIES>
+  __device__ __forceinline__ bool unit_sphere_tries(D3 &out) {
+    double x1 = 0.0, x2 = 0.0, s = 1.0;
+#pragma unroll 1
+    for (int k = 0; k < TRIES && s >= 1.0; k++) {
+      x1 = uniform_m1_1(), x2 = uniform_m1_1();
+      s = x1 * x1 + x2 * x2;
+    }
+    if (s >= 1.0) return false;
+    double f = 2.0 * sqrt(1.0 - s);
+    out = D3{x1 * f, x2 * f, 1.0 - 2.0 * s};
+    return true;
   }
   __device__ __forceinline__ void unit_disc(double &a, double &b) {
     for (;;) {

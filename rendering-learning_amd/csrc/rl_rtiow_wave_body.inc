@@ -131,6 +131,7 @@
   // shade() writes the next ray over the old one before it knows whether the path goes on (see there).  The fast kernels only: the
   // reference-order layouts gain nothing (the counting instantiation's SHADE pick path reads 509 -> 824 instructions, 94 -> 102 spilled SGPRs)
   constexpr bool SHADE_RAY_IN_PLACE = LDS_SCENE == 4;
+  constexpr int SHADE_TRIES = RL_SHADE_TRIES;  // rl_rtiow_wave.h
   auto shade_state = [&]() -> uint32_t {  // where a finished traversal is shaded
     if (!SPLIT_SHADE || LDS_SCENE != 4 || hit_prim == NONE) return ST_SHADE;
     const uint32_t si = hit_prim & SPH_INDEX;
@@ -203,13 +204,64 @@
           // colour inlined, and for a Dielectric the constants 1/ior and Schlick's r0 of both orientations — one load
           // instead of the sphere -> material -> texture chain, same values bit for bit
           const DevMaterial &m = P.sphere_flat[si];
+          // ... and, for a Checker of two Solid colours, the odd colour and inv_scale from the sphere's own record beside it (the even
+          // colour is in albedo): addressed by sphere index alone; apply_texture below is what makes it one round of loads with the material's
+          const DevChecker &ck = P.sphere_checker[si];
           const uint32_t kind = m.kind & 0xFFu;
-          const bool solid = (m.kind & MAT_TEX_SOLID) != 0u;
+          const bool solid = (m.kind & MAT_TEX_SOLID) != 0u, checker = (m.kind & MAT_TEX_CHECKER) != 0u;
           // shared sub-expressions, evaluated once per block instead of once per material branch (same values, same
           // RNG order: the unit-sphere draw is the first draw of both Lambertian and Metal scatter)
           const bool is_lamb = MODE != 2 && kind == RL_MAT_LAMBERTIAN, is_metal = MODE != 1 && kind == RL_MAT_METAL, is_diel = MODE != 1 && kind == RL_MAT_DIELECTRIC;
+          const bool is_light = MODE != 2 && kind == RL_MAT_DIFFUSE_LIGHT;
+          // Texture::value at p, once for both materials that have a texture.  Solid: albedo.  Two-colour checker: texture_value's own
+          // parity expression on the inlined inv_scale, then one of the two inlined colours, as they are.  Anything else (a nested
+          // checker): the generic walk, a region no wave enters unless it has such a lane.
+          // The records' fields are made values before the flag is looked at: the compiler issues a load where its value is used, i.e.
+          // inside the region of the branch that needs it — albedo behind kind, inv_scale behind the checker flag, the odd colour behind
+          // the parity: four rounds in series.  The empty asm makes each a value that exists here, so the loads stand beside kind's
+          // and the one wait that kind needs anyway covers them.
+          // The colour is used up at once — thr for Lambertian, sum for DiffuseLight: both apply it whatever the draw gives — so that
+          // neither it nor the checker record is held through the rejection loop and normalize(): held to the material branches the
+          // headline kernel takes 124 VGPRs, with the records' values held through the loop 128, instead of 118 (tools/wave_codegen.py).
+          // (TEX_EARLY = false, the layouts that read the scene from global memory, LDS_SCENE = 0, for scenes too large for LDS: the
+          // statements stay in the material branches, a Solid's colour inlined and every other texture walked, MAT_TEX_CHECKER ignored.
+          // With this block those instantiations, which spill as they are, spill more: rtiow_wave_kernel<1024, 0, true> 18 VGPRs
+          // instead of 6, tools/kernel_regs.py)
+          constexpr bool TEX_EARLY = LDS_SCENE != 0;
+          auto tex_late = [&] { return solid ? ld3(m.albedo) : texture_value(P, m.texture, 0.0, 0.0, p); };
+          auto apply_texture = [&] {
+            if (!TEX_EARLY) return;
+            D3 texc = ld3(m.albedo), tex_odd = ld3(ck.odd);
+            double inv_scale = ck.inv_scale;
+            asm volatile("" : "+v"(texc.x), "+v"(texc.y), "+v"(texc.z), "+v"(tex_odd.x), "+v"(tex_odd.y), "+v"(tex_odd.z), "+v"(inv_scale));
+            if (is_lamb | is_light) {
+              if (checker) {
+                const uint32_t odd = f64_as_i64_low_bit(floor(p.x * inv_scale)) ^ f64_as_i64_low_bit(floor(p.y * inv_scale)) ^
+                                     f64_as_i64_low_bit(floor(p.z * inv_scale));
+                if (odd) texc = tex_odd;
+              } else if (!solid) texc = texture_value(P, m.texture, 0.0, 0.0, p);
+              if (is_lamb) thr = thr * texc;
+              else {
+                if constexpr (MOMENTS) {
+                  const D3 c = thr * texc;
+                  sum = sum + c;
+                  sq = sq + c * c;
+                } else sum = sum + thr * texc;
+              }
+            }
+          };
+          // The unit-sphere draw, the first draw of both Lambertian and Metal scatter.  SHADE_TRIES > 0 (A/B): a lane that has not
+          // accepted after that many tries leaves shade() here with nothing but rng.pos advanced — it stays in ST_SHADE and draws on
+          // at its next SHADE pick (the rejected words are consumed, the loop is memoryless), passing rng.low() and FILL on the way.
+          // Everything above it writes locals only, so the colour is then fetched and applied behind the draw: a second round of loads.
+          if (SHADE_TRIES == 0) apply_texture();
           D3 us = d3(0.0, 0.0, 0.0);
-          if (is_lamb | is_metal) us = rng.unit_sphere();
+          if (is_lamb | is_metal) {
+            if constexpr (SHADE_TRIES > 0) {
+              if (!rng.template unit_sphere_tries<SHADE_TRIES>(us)) return;
+            } else us = rng.unit_sphere_tail();
+          }
+          if (SHADE_TRIES > 0) apply_texture();
           D3 reflected = d - normal * (2.0 * dot(d, normal));  // material.rs reflect(): used by Metal
           D3 vin = is_metal ? reflected : d;
           D3 vn = vin;
@@ -219,7 +271,7 @@
             D3 dir = normal + us;
             bool near_zero = approx_eq_eps(dir.x, 0.0, 1e-8) && approx_eq_eps(dir.y, 0.0, 1e-8) && approx_eq_eps(dir.z, 0.0, 1e-8);
             nd = near_zero ? normal : dir;
-            thr = thr * (solid ? ld3(m.albedo) : texture_value(P, m.texture, 0.0, 0.0, p));
+            if (!TEX_EARLY) thr = thr * tex_late();  // (else thr has its texture colour already)
           } else if (is_metal) {
             nd = vn + us * m.fuzz;
             if (!(dot(nd, normal) > 0.0)) path_done = true;  // absorbed
@@ -247,12 +299,14 @@
               D3 par = normal * (-sqrt(fabs(1.0 - len2(perp))));
               nd = perp + par;
             }
-          } else if (MODE != 2 && kind == RL_MAT_DIFFUSE_LIGHT) {
-            if constexpr (MOMENTS) {
-              const D3 c = thr * (solid ? ld3(m.albedo) : texture_value(P, m.texture, 0.0, 0.0, p));
-              sum = sum + c;
-              sq = sq + c * c;
-            } else sum = sum + thr * (solid ? ld3(m.albedo) : texture_value(P, m.texture, 0.0, 0.0, p));
+          } else if (is_light) {
+            if (!TEX_EARLY) {  // (else its emission is in sum already)
+              if constexpr (MOMENTS) {
+                const D3 c = thr * tex_late();
+                sum = sum + c;
+                sq = sq + c * c;
+              } else sum = sum + thr * tex_late();
+            }
             path_done = true;
           } else {
             path_done = true;  // Flat

@@ -38,6 +38,7 @@ struct rl_scene {
   // RTIOW
   rl::DevBuf<rl::DevOp> d_ops, d_lops;
   rl::DevBuf<rl::DevMaterial> d_sphere_flat;
+  rl::DevBuf<rl::DevChecker> d_sphere_checker;
   rl::DevBuf<rl::CompactOp> d_cops;
   rl::DevBuf<uint32_t> d_movbits;
   rl::DevBuf<rl::FastNode> d_fast_nodes;

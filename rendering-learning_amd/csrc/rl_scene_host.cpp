@@ -114,14 +114,27 @@ static uint32_t link_ops(const std::vector<DevOp> &ops, std::vector<DevOp> &out,
 // One DevMaterial per sphere for the wave kernel's SHADE: the sphere's material with (a) a Solid texture's colour copied
 // into albedo (flag MAT_TEX_SOLID) and (b) for a Dielectric albedo = {1/ior, r0(ri = 1/ior), r0(ri = ior)} with
 // r0 = ((1 - ri) / (1 + ri))^2 — the very expressions material.rs:140-166 evaluates per scatter (IEEE, no contraction).
-static void flatten_sphere_materials(const RtiowProgram &rt, std::vector<DevMaterial> &out) {
+// (c) A Checker whose two children are Solid is as constant per scene as a Solid: its even colour goes into albedo (flag
+// MAT_TEX_CHECKER) and its odd colour and inv_scale into the sphere's record of `checker`, all copied as they are, so that SHADE
+// fetches them by sphere index beside the material instead of walking texture -> child -> colour.  Any other texture tree (a nested
+// checker, say) keeps the generic walk.  `checker` has a record for every sphere, zeros where the flag is not set: SHADE loads it
+// before it knows the flag.
+static void flatten_sphere_materials(const RtiowProgram &rt, std::vector<DevMaterial> &out, std::vector<DevChecker> &checker) {
   out.resize(rt.spheres.size());
+  checker.assign(rt.spheres.size(), DevChecker{{0.0, 0.0, 0.0}, 0.0});
   for (size_t i = 0; i < rt.spheres.size(); i++) {
     DevMaterial m = rt.materials[rt.sphere_material[i]];
-    if ((m.kind == RL_MAT_LAMBERTIAN || m.kind == RL_MAT_DIFFUSE_LIGHT) && rt.textures[m.texture].kind == RL_TEX_SOLID) {
+    const bool textured = m.kind == RL_MAT_LAMBERTIAN || m.kind == RL_MAT_DIFFUSE_LIGHT;
+    if (textured && rt.textures[m.texture].kind == RL_TEX_SOLID) {
       const DevTexture &t = rt.textures[m.texture];
       m.albedo[0] = t.color[0], m.albedo[1] = t.color[1], m.albedo[2] = t.color[2];
       m.kind |= MAT_TEX_SOLID;
+    } else if (textured && rt.textures[m.texture].kind == RL_TEX_CHECKER && rt.textures[rt.textures[m.texture].even].kind == RL_TEX_SOLID &&
+               rt.textures[rt.textures[m.texture].odd].kind == RL_TEX_SOLID) {
+      const DevTexture &t = rt.textures[m.texture], &ev = rt.textures[t.even], &od = rt.textures[t.odd];
+      m.albedo[0] = ev.color[0], m.albedo[1] = ev.color[1], m.albedo[2] = ev.color[2];
+      checker[i] = DevChecker{{od.color[0], od.color[1], od.color[2]}, t.inv_scale};
+      m.kind |= MAT_TEX_CHECKER;
     } else if (m.kind == RL_MAT_DIELECTRIC) {
       auto r0 = [](double ri) {
         double q = (1.0 - ri) / (1.0 + ri);
@@ -140,7 +153,7 @@ static int build_host_rtiow_may_throw(const rl_rtiow_scene_desc *desc, std::shar
   const RtiowProgram &rt = H->rt;
   if (!(rt.has_planars || rt.has_instances || rt.has_images || rt.has_noise || rt.has_media) && rt.ops.size() < (1u << 29)) {
     H->entry0 = link_ops(rt.ops, H->lops);
-    flatten_sphere_materials(rt, H->sphere_flat);
+    flatten_sphere_materials(rt, H->sphere_flat, H->sphere_checker);
     // compact guarded form (32-byte ops: binary32 box + the two successor words) for the 4-waves-per-SIMD layout
     std::vector<DevOp> gops;
     bool gok = false;

@@ -16,6 +16,7 @@ struct HostRtiow {
   RtiowProgram rt;
   std::vector<DevOp> lops;  // linked ops (sphere-only scenes)
   std::vector<DevMaterial> sphere_flat;
+  std::vector<DevChecker> sphere_checker;  // beside sphere_flat, one per sphere: a two-colour checker's odd colour and inv_scale
   std::vector<CompactOp> cops;  // guarded compact ops
   std::vector<uint32_t> movbits;
   uint32_t entry0 = 0, centry0 = 0;
