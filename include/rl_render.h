@@ -800,8 +800,8 @@ int rl_rtiow_render_pixels_direct_device(const rl_scene *, const rl_rtiow_camera
  * traversal counters are the sums of what rl_rtiow_hit_rays and rl_rtiow_occluded_rays report for those rays; rng_words = the words
  * drawn (get_ray's, 4 per light sample, the scatters').  Without it the call is counter-free, may take the fast walks and gives the
  * same bytes.
- * Not offered: sphere and textured lights, media scenes, multiple importance sampling with the scattered ray, Russian roulette, adaptive
- * stopping, multi-GPU forms, rgb8 output, the RTC family. */
+ * Not offered: sphere and textured lights, media scenes, Russian roulette, adaptive stopping, multi-GPU forms, rgb8 output, the RTC
+ * family.  Multiple importance sampling with the scattered ray is the next section's rl_rtiow_render_nee_mis*. */
 int rl_rtiow_render_nee_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
                              uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, double *out_sums, double *out_sq,
                              rl_stats *opt_stats);
@@ -814,6 +814,81 @@ int rl_rtiow_render_pixels_nee(const rl_scene *, const rl_rtiow_camera *, uint64
 int rl_rtiow_render_pixels_nee_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs, const void *d_ys,
                                       uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
                                       void *d_out_sums, void *d_out_sq, void *hip_stream, rl_stats *opt_stats);
+
+/* =====================================================================
+ *  NEE path renders with multiple importance sampling: weighted light and scattered-ray samples
+ * =====================================================================
+ * The NEE path renders above with one more argument, `heuristic`: RL_MIS_BALANCE or RL_MIS_POWER (exponent 2).  A vertex that samples
+ * the lights now has TWO strategies for the listed lights' contribution: the light points, and its own scattered ray where that ray
+ * crosses a light's parallelogram.  Each is weighted by its density's share of the pair.  For a Lambertian vertex that share needs no
+ * sqrt: with p_bsdf = cos(theta) / pi, p_light = |d|^2 / (A cos(theta_l)) and kf = 1 / (pi K), the ratio p_bsdf / (K p_light) is
+ * exactly q = g * kf, g the geometry term the light points already form.  The draws, the path, the `i < max_depth` rule,
+ * count_emission and the outputs are the NEE path renders'; what is NEW is marked.  With the names of that definition:
+ *       3. if hit.mat is RL_MAT_LAMBERTIAN and i < cam->max_depth:
+ *            ... a, b, yl, d, d2, cs, cl, the skip and g = (cs * cl) / (d2 * d2) as there, then
+ *               NEW  if !(g < +inf):  continue                                    -- not traced
+ *               NEW  q = g * kf
+ *               NEW  RL_MIS_BALANCE:  wl = g / (1.0 + q)         RL_MIS_POWER:  wl = g / (1.0 + q*q)
+ *               if world.hit(&Ray{hit.p, d, time}, &Interval{1e-10, T}).is_none():
+ *                  for ch in r, g, b:  dsum[ch] = dsum[ch] + E[ch] * wl             -- wl in g's place
+ *            for ch in r, g, b:  c[ch] = c[ch] + ((thr[ch] * tex[ch]) * dsum[ch]) * kf
+ *       4. match hit.mat.scatter(&mut rng, &ray, &hit):
+ *            None:  break
+ *            Some((scattered, attenuation)):  thr = thr * attenuation
+ *               NEW  if step 3 was taken:                                           -- draws nothing
+ *                      x = hit.p;  n = hit.normal;  w = scattered.direction         -- as rl_rtiow_scatter_rays returns it, not normalised
+ *                      bsum = (0,0,0)
+ *                      for l in 0..L:
+ *                         den = nl.dot(w);                          if !(|den| > 0):  continue
+ *                         r = Q - x;  t = nl.dot(r) / den;          if !(t > 0) or !(t < +inf):  continue
+ *                         d = w * t;  y = x + d;  h = y - Q
+ *                         nn = nl.dot(nl);  al = nl.dot(h.cross(v)) / nn;  be = nl.dot(u.cross(h)) / nn
+ *                         if !(0 <= al <= 1) or !(0 <= be <= 1):  continue                     -- beside the parallelogram
+ *                         d2 = d.dot(d);  cs = n.dot(d);  cl = |nl.dot(d)|
+ *                         if !(cs > 0) or !(cl > 0) or !(d2 > 0):  continue
+ *                         g = (cs * cl) / (d2 * d2);                if !(g < +inf):  continue
+ *                         q = g * kf
+ *                         RL_MIS_BALANCE:  wb = q / (1.0 + q)       RL_MIS_POWER:  wb = (q*q) / (1.0 + q*q)
+ *                         if world.hit(&Ray{x, d, time}, &Interval{1e-10, T}).is_none():
+ *                            for ch in r, g, b:  bsum[ch] = bsum[ch] + E[ch] * wb
+ *                      for ch in r, g, b:  c[ch] = c[ch] + thr[ch] * bsum[ch]
+ *               ray = scattered;  count_emission = (step 3 was not taken)
+ * a.dot(b) is (a.x*b.x + a.y*b.y) + a.z*b.z and cross is vec3.rs:48-54's, every product rounded; every line is one rounded binary64
+ * + - x or /.  The segment of a scattered ray is tested exactly as a light point's is (the same any-hit query, the same T) and is counted
+ * in `rays`.
+ * What follows from the definition:
+ *  - Both strategies estimate the listed lights' contribution THROUGH THE SEGMENT TEST, and wl * kf / (g * kf) + wb = 1, so the
+ *    expectation is the NEE path renders' for ANY `lights`, whether or not they are geometry of the scene; with every emitter listed it
+ *    is ray_color's.  The emission a scattered ray finds after step 3 stays uncounted, as there.
+ *  - wl * kf <= 1 and wb <= 1: one weighted light sample adds at most thr * tex * E and the scattered-ray term at most thr * E per light,
+ *    however close the light point is.  What uniform area sampling lets grow without bound (g, where a light is near a surface) is
+ *    capped.  It does NOT lower the variance everywhere: away from a light at small K the rare scattered ray that reaches it adds a
+ *    little noise of its own (DESIGN.md §3.23 has the measurements).
+ *  - rng_words equals the NEE path renders' for the same arguments (the new strategy draws nothing); rays = theirs + the scattered-ray
+ *    segments traced.  The path itself (every closest hit, every scatter) is theirs.
+ *  - The two heuristics give different bytes; neither gives the NEE path renders' bytes unless no light point counts and no scattered
+ *    ray crosses a light.
+ * Everything else (outputs, layout, _device asynchrony, _rows always counting, the pixel-list rules, stats, rl_render_status) follows
+ * rl_rtiow_render_nee* exactly.
+ * Errors.  The NEE path renders' rules, or heuristic > RL_MIS_POWER: RL_E_INVALID, before a device is looked at, outputs untouched; then
+ * as there.
+ * Not offered: sphere and textured lights, media scenes, Isotropic vertices (no light sampling, as there), Russian roulette, adaptive
+ * stopping, multi-GPU forms, rgb8 output, the RTC family. */
+#define RL_MIS_BALANCE 0u
+#define RL_MIS_POWER 1u
+int rl_rtiow_render_nee_mis_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                 uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, uint32_t heuristic,
+                                 double *out_sums, double *out_sq, rl_stats *opt_stats);
+int rl_rtiow_render_nee_mis_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
+                                   uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax, uint32_t heuristic,
+                                   void *d_out_sums, void *d_out_sq, void *hip_stream, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_nee_mis(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs, const uint32_t *ys,
+                                   uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
+                                   uint32_t heuristic, double *out_sums, double *out_sq, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_nee_mis_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs,
+                                          const void *d_ys, uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples,
+                                          double seg_tmax, uint32_t heuristic, void *d_out_sums, void *d_out_sq, void *hip_stream,
+                                          rl_stats *opt_stats);
 
 /* =====================================================================
  *  Denoising: an edge-avoiding a-trous filter for noisy and adaptive renders

@@ -16,3 +16,4 @@ from . import direct  # noqa: F401
 from .direct import DirectLight, pack_lights, render_direct, render_direct_device, render_pixels_direct, render_pixels_direct_device  # noqa: F401
 from . import nee  # noqa: F401
 from .nee import PathNEE, render_nee, render_nee_device, render_pixels_nee, render_pixels_nee_device  # noqa: F401
+from .nee import render_nee_mis, render_nee_mis_device, render_pixels_nee_mis, render_pixels_nee_mis_device  # noqa: F401

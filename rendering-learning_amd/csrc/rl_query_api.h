@@ -184,7 +184,7 @@ int rl_rtiow_hit_rays_device(const rl_scene *scene, const void *d_rays, uint64_t
 // the most recent SYNCHRONOUS one the fast walk re-traced in the reference's order (asynchronous calls: rl_render_status + rl_debug_slow_traces).
 // The feature renders (rl_rtiow_render_features*, rl_features_api.h) report here too, under ids of their own: 3 reference order, 4 fast walk;
 // so do the occlusion queries (rl_rtiow_occluded_rays*, rl_occlusion_api.h): 5 reference order, 6 any-hit walk; and the ambient-occlusion renders (rl_ao_api.h): 7, 8;
-// the direct-lighting renders (rl_direct_api.h): 9, 10; and the NEE path renders (rl_nee_api.h): 11, 12.
+// the direct-lighting renders (rl_direct_api.h): 9, 10; and the NEE path renders (rl_nee_api.h): 11, 12, with multiple importance sampling 13, 14.
 int rl_debug_last_query(unsigned long long *out2) {
   if (!out2) return set_err(RL_E_INVALID, "bad argument");
   out2[0] = (unsigned long long)g_last_query_kernel, out2[1] = g_last_query_retraced;

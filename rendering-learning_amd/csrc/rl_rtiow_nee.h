@@ -2,9 +2,13 @@
 // the sum and the sum of squares of a path estimate of max_depth vertices that connects every Lambertian vertex but the last to K points
 // drawn on each of L quad lights and, in exchange, does not count the emission the scattered ray of such a vertex finds.
 //
-//   rtiow_nee_kernel<NT, STATS, FAST, SD>   one pixel per lane, grid-stride over the frame's or the list's slots; per lane a loop over the
-//                                           samples F .. F + S - 1, inside it over the path's vertices and, at a vertex that samples the
-//                                           lights, over the L lights and their K points.
+//   rtiow_nee_kernel<NT, STATS, FAST, SD, MIS>   one pixel per lane, grid-stride over the frame's or the list's slots; per lane a loop over
+//                                                the samples F .. F + S - 1, inside it over the path's vertices and, at a vertex that
+//                                                samples the lights, over the L lights and their K points.
+// MIS = true is the flavour of the renders with multiple importance sampling (include/rl_render.h "NEE path renders with multiple importance
+// sampling", rl_rtiow_render_nee_mis*): every light point's g becomes wl, and the scattered ray of a vertex that sampled
+// the lights is intersected with each light's parallelogram and, where it crosses one, connected with wb.  The heuristic is a runtime
+// scalar of the launch (NeeMisQuery::heuristic).
 //
 // Per vertex the kernel joins texts the library already has, so that the host composition of rl_rtiow_camera_rays, rl_rtiow_hit_rays, the
 // definition's arithmetic, rl_rtiow_occluded_rays and rl_rtiow_scatter_rays gives the same bytes (tests/test_gpu_render_nee.py):
@@ -17,6 +21,14 @@
 //        FAST = false  general_trace<STATS, false>, rec.any
 //        FAST = true   ao_any_hit_walk (rl_rtiow_ao.h), then general_trace for a segment the walk leaves undecided (stats[7])
 //   5. material_scatter (rl_rtiow_scatter.h) drawing from the sample's ring AFTER the light points
+//   MIS, at a vertex that took step 4, behind step 5's thr = thr * att: the ray-parallelogram crossing and the weights are this file's own
+//        text (the header's lines, one rounded operation each; dot, cross and len2 are rl_device.h's, in vec3.rs' order); the segment from
+//        the crossing point goes through step 4's segment statement, so the flavour has ONE inlined copy of ao_any_hit_walk and of the fold.
+//        A vertex of the MIS flavour is a loop of two passes for that: pass 0 the light points, pass 1 step 5 and then the scattered ray's
+//        candidates, one per light, through the same inner statement.
+// The plain flavour's vertex body is kept VERBATIM beside the MIS flavour's under `if constexpr`: with the segment statement moved into a
+// lambda shared by both (alone, or with the loops and step 5 shared as well), the three plain instantiations came out as other code (hundreds
+// to thousands of changed lines, 328 -> 340 VGPRs for the counting one); kept apart they are the parent's instruction for instruction.
 // None of the walks, of the texture or of the scatter is copied here.  The lights travel by value in the kernel argument (NeeQuery::lights,
 // indexed by the loop counter alone: scalar loads), nl = u x v and kf = 1 / (pi K) computed once on the host.  c, thr and the two sums
 // live in registers and are stored once per pixel: no atomics.
@@ -24,7 +36,7 @@
 // Scenes with ConstantMedium objects are refused on the host (there is no seeded any-hit), so no trace here draws.
 // No barrier and no wave-wide operation inside a lane's loops: lanes leave their walks, their loops and their paths at different times.
 // LDS (dynamic): rtiow_ao_kernel's plan; the one [SD][NT] stack serves the closest-hit and the any-hit walk in turn.
-// stats: [0] rays = path rays + segments traced, [5] words drawn, [6] flagged (the walks' and the Dielectric's panic site), [7] segments AND
+// stats (MIS: the scattered rays' segments are segments): [0] rays = path rays + segments traced, [5] words drawn, [6] flagged (the walks' and the Dielectric's panic site), [7] segments AND
 // path rays the fast walks handed to general_trace; STATS: [1..4] over both kinds of ray.
 #pragma once
 #include "rl_rtiow_direct.h"
@@ -42,15 +54,22 @@ struct NeeQuery {
   double *sq;               // [n][3] or null
   DirectLight lights[RL_DIRECT_MAX_LIGHTS];
 };
-static_assert(sizeof(RtiowParams) + sizeof(NeeQuery) <= 4096, "the two by-value kernel arguments must fit the 4 KiB kernarg segment");
+// The MIS flavour's argument: one scalar more, in a type of its own so that the plain flavour's kernarg segment keeps its size
+struct NeeMisQuery : NeeQuery {
+  uint32_t heuristic;  // RL_MIS_BALANCE or RL_MIS_POWER (wave-uniform: a scalar load and a scalar branch)
+};
+template <bool MIS>
+using NeeQueryOf = typename std::conditional<MIS, NeeMisQuery, NeeQuery>::type;
+static_assert(sizeof(RtiowParams) + sizeof(NeeMisQuery) <= 4096, "the two by-value kernel arguments must fit the 4 KiB kernarg segment");
 
 // P: the scene's tables (hit_query_params + materials, textures, images, Perlin), cam, key, first_sample, row_first / row_step, stats;
 // FAST: also the query tree (fg_*, fg_top).
 // Register budget (DESIGN.md §3.22 has the table): compiled for two workgroups per SIMD row as rtiow_direct_kernel is, FAST takes all 256
-// VGPRs and spills 68 more to 276 bytes of scratch, so it is compiled for ONE (NEE_FAST_WG = 1) and spills nothing.
+// VGPRs and spills 68 more to 276 bytes of scratch, so it is compiled for ONE (NEE_FAST_WG = 1) and spills nothing.  The MIS flavour at one
+// (DESIGN.md §3.23): FAST 338 VGPRs + 82 AGPRs, counting 324 + 68, counter-free reference order 308 + 52; no VGPR spilled, no scratch.
 constexpr int NEE_FAST_WG = 1;
-template <int NT, bool STATS, bool FAST, int SD>
-__global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) rtiow_nee_kernel(RtiowParams P, NeeQuery Q) {
+template <int NT, bool STATS, bool FAST, int SD, bool MIS>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) rtiow_nee_kernel(RtiowParams P, NeeQueryOf<MIS> Q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   unsigned long long *s_rng = (unsigned long long *)smem;                                 // [16][NT]
@@ -127,52 +146,129 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) 
           return texture_value<2>(P, tex, tu, tv, rec.p);
         });
         const D3 hp = rec.p, hn = rec.normal;
-        // 4. L x K light points: Ray{hit.p, yl - hit.p, ray.time} against Interval{1e-10, T}
         const bool sampled = m.kind == RL_MAT_LAMBERTIAN && i < max_depth;
-        if (sampled) {
-          D3 dsum = d3(0.0, 0.0, 0.0);
+        if constexpr (!MIS) {
+          // 4. L x K light points: Ray{hit.p, yl - hit.p, ray.time} against Interval{1e-10, T}
+          if (sampled) {
+            D3 dsum = d3(0.0, 0.0, 0.0);
 #pragma unroll 1
-          for (uint32_t l = 0; l < L; l++) {
-            const DirectLight &lt = Q.lights[l];
+            for (uint32_t l = 0; l < L; l++) {
+              const DirectLight &lt = Q.lights[l];
 #pragma unroll 1
-            for (uint32_t k = 0; k < K; k++) {
-              const double a = rng.gen_f64();
-              const double b = rng.gen_f64();
-              const D3 yl = (ld3(lt.Q) + ld3(lt.u) * a) + ld3(lt.v) * b;
-              const D3 sd = yl - hp;
-              const double d2 = len2(sd);
-              const double cs = dot(hn, sd);
-              const double cl = fabs(dot(ld3(lt.nl), sd));
-              if (!(cs > 0.0) || !(cl > 0.0) || !(d2 > 0.0)) continue;  // faces away, edge-on or degenerate: nothing traced
-              const double g = (cs * cl) / (d2 * d2);
-              c_rays++;
-              bool occluded = false, fold = !FAST;
-              if (FAST) {
-                const int w = ao_any_hit_walk<NT, SD>(P, ops, s_stack, s_top, tid, hp, sd, time, T);
-                occluded = w == AO_WALK_OCCLUDED;
-                if (w == AO_WALK_UNDECIDED) fold = true, c_slow++;
+              for (uint32_t k = 0; k < K; k++) {
+                const double a = rng.gen_f64();
+                const double b = rng.gen_f64();
+                const D3 yl = (ld3(lt.Q) + ld3(lt.u) * a) + ld3(lt.v) * b;
+                const D3 sd = yl - hp;
+                const double d2 = len2(sd);
+                const double cs = dot(hn, sd);
+                const double cl = fabs(dot(ld3(lt.nl), sd));
+                if (!(cs > 0.0) || !(cl > 0.0) || !(d2 > 0.0)) continue;  // faces away, edge-on or degenerate: nothing traced
+                const double g = (cs * cl) / (d2 * d2);
+                c_rays++;
+                bool occluded = false, fold = !FAST;
+                if (FAST) {
+                  const int w = ao_any_hit_walk<NT, SD>(P, ops, s_stack, s_top, tid, hp, sd, time, T);
+                  occluded = w == AO_WALK_OCCLUDED;
+                  if (w == AO_WALK_UNDECIDED) fold = true, c_slow++;
+                }
+                if (fold) {  // the reference's own fold: every segment of !FAST, the undecided ones of FAST
+                  Rec orec = rec_none(T);
+                  GenCounters gc{0, 0, 0, 0, 0};
+                  auto draw = []() { return 0.0; };
+                  general_trace<STATS, false, false>(P, ops, 0u, NONE, hp, sd, hp, sd, time, 1e-10, orec, gc, draw);
+                  c_nodes += gc.nodes, c_sph += gc.spheres, c_pl += gc.planars, c_inst += gc.instances, c_flag += gc.flagged;
+                  occluded = orec.any;
+                }
+                if (!occluded) dsum = d3(dsum.x + lt.E[0] * g, dsum.y + lt.E[1] * g, dsum.z + lt.E[2] * g);
               }
-              if (fold) {  // the reference's own fold: every segment of !FAST, the undecided ones of FAST
-                Rec orec = rec_none(T);
-                GenCounters gc{0, 0, 0, 0, 0};
-                auto draw = []() { return 0.0; };
-                general_trace<STATS, false, false>(P, ops, 0u, NONE, hp, sd, hp, sd, time, 1e-10, orec, gc, draw);
-                c_nodes += gc.nodes, c_sph += gc.spheres, c_pl += gc.planars, c_inst += gc.instances, c_flag += gc.flagged;
-                occluded = orec.any;
-              }
-              if (!occluded) dsum = d3(dsum.x + lt.E[0] * g, dsum.y + lt.E[1] * g, dsum.z + lt.E[2] * g);
             }
+            c = c + ((thr * texc) * dsum) * kf;
           }
-          c = c + ((thr * texc) * dsum) * kf;
+          // 5. mat.emitted and mat.scatter, drawing after the light points
+          const Scatter s = material_scatter<true>(m, wd, hn, rec.front, [&] { return texc; }, rng);
+          if (s.flagged) c_flag++;
+          if (count_emission) c = c + thr * s.emitted;  // (zeros unless the material is a DiffuseLight)
+          if (s.what != SCATTER_RAY) break;
+          thr = thr * s.att;
+          wo = hp, wd = s.dir;
+          count_emission = !sampled;
+        } else {
+          // MIS.  pass 0: step 4 at a sampling vertex with wl in g's place; pass 1: step 5 and, behind a sampling vertex, its scattered ray
+          // against each light's parallelogram with wb (no draw).  Both passes run the ONE segment statement below: one copy of the walks.
+          bool ended = false;
+#pragma unroll 1
+          for (uint32_t pass = sampled ? 0u : 1u; pass < 2u; pass++) {
+            if (pass) {
+              const Scatter s = material_scatter<true>(m, wd, hn, rec.front, [&] { return texc; }, rng);
+              if (s.flagged) c_flag++;
+              if (count_emission) c = c + thr * s.emitted;
+              if (s.what != SCATTER_RAY) {
+                ended = true;
+                break;
+              }
+              thr = thr * s.att;
+              wo = hp, wd = s.dir;
+              count_emission = !sampled;
+              if (!sampled) break;
+            }
+            D3 dsum = d3(0.0, 0.0, 0.0);
+#pragma unroll 1
+            for (uint32_t l = 0; l < L; l++) {
+              const DirectLight &lt = Q.lights[l];
+#pragma unroll 1
+              for (uint32_t k = 0; k < (pass ? 1u : K); k++) {
+                D3 sd;
+                if (!pass) {
+                  const double a = rng.gen_f64();
+                  const double b = rng.gen_f64();
+                  const D3 yl = (ld3(lt.Q) + ld3(lt.u) * a) + ld3(lt.v) * b;
+                  sd = yl - hp;
+                } else {  // wd is the scattered direction by now, as material_scatter gives it (not normalised)
+                  const D3 nl = ld3(lt.nl);
+                  const double den = dot(nl, wd);
+                  if (!(fabs(den) > 0.0)) continue;  // along the light's plane
+                  const double t = dot(nl, ld3(lt.Q) - hp) / den;
+                  if (!(t > 0.0) || !(t < INF)) continue;  // the plane is behind the vertex
+                  sd = wd * t;
+                  const D3 h = (hp + sd) - ld3(lt.Q);
+                  const double nn = dot(nl, nl);
+                  const double al = dot(nl, cross(h, ld3(lt.v))) / nn;
+                  const double be = dot(nl, cross(ld3(lt.u), h)) / nn;
+                  if (!(0.0 <= al && al <= 1.0) || !(0.0 <= be && be <= 1.0)) continue;  // beside the parallelogram
+                }
+                const double d2 = len2(sd);
+                const double cs = dot(hn, sd);
+                const double cl = fabs(dot(ld3(lt.nl), sd));
+                if (!(cs > 0.0) || !(cl > 0.0) || !(d2 > 0.0)) continue;  // faces away, edge-on or degenerate: nothing traced
+                const double g = (cs * cl) / (d2 * d2);
+                if (!(g < INF)) continue;
+                // q = p_bsdf / (K p_light) exactly; wl = g / (1 + q^b), wb = q^b / (1 + q^b), b = 1 (balance) or 2 (power)
+                const double q = g * kf;
+                const double qb = Q.heuristic == RL_MIS_POWER ? q * q : q;
+                const double wt = (pass ? qb : g) / (1.0 + qb);
+                c_rays++;
+                bool occluded = false, fold = !FAST;
+                if (FAST) {
+                  const int w = ao_any_hit_walk<NT, SD>(P, ops, s_stack, s_top, tid, hp, sd, time, T);
+                  occluded = w == AO_WALK_OCCLUDED;
+                  if (w == AO_WALK_UNDECIDED) fold = true, c_slow++;
+                }
+                if (fold) {  // the reference's own fold: every segment of !FAST, the undecided ones of FAST
+                  Rec orec = rec_none(T);
+                  GenCounters gc{0, 0, 0, 0, 0};
+                  auto draw = []() { return 0.0; };
+                  general_trace<STATS, false, false>(P, ops, 0u, NONE, hp, sd, hp, sd, time, 1e-10, orec, gc, draw);
+                  c_nodes += gc.nodes, c_sph += gc.spheres, c_pl += gc.planars, c_inst += gc.instances, c_flag += gc.flagged;
+                  occluded = orec.any;
+                }
+                if (!occluded) dsum = d3(dsum.x + lt.E[0] * wt, dsum.y + lt.E[1] * wt, dsum.z + lt.E[2] * wt);
+              }
+            }
+            c = pass ? c + thr * dsum : c + ((thr * texc) * dsum) * kf;
+          }
+          if (ended) break;
         }
-        // 5. mat.emitted and mat.scatter, drawing after the light points
-        const Scatter s = material_scatter<true>(m, wd, hn, rec.front, [&] { return texc; }, rng);
-        if (s.flagged) c_flag++;
-        if (count_emission) c = c + thr * s.emitted;  // (zeros unless the material is a DiffuseLight)
-        if (s.what != SCATTER_RAY) break;
-        thr = thr * s.att;
-        wo = hp, wd = s.dir;
-        count_emission = !sampled;
       }
       c_words += rng.pos;
       sum = sum + c, sum2 = sum2 + c * c;

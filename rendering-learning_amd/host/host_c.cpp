@@ -681,8 +681,19 @@ int rlh_direct_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32
 // An NEE path render through the C++ mirror: golden_test_scene at image_width = width, samples_per_pixel = spp, rtiow::render_nee from
 // sample first_sample on with the n_lights quad lights of lights [n_lights][12] (Q, u, v, E).  sums and sq = W * H * 3 doubles.  0 or -1
 // (rlh_last_error).
+static int nee_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
+                     const uint32_t *heuristic, double *sums, double *sq);
 int rlh_nee_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
                   double *sums, double *sq) {
+  return nee_probe(width, spp, first_sample, n_lights, lights, light_samples, seg_tmax, nullptr, sums, sq);
+}
+// The same through rtiow::render_nee_mis; heuristic = RL_MIS_BALANCE or RL_MIS_POWER (anything else is handed on and refused by the library).
+int rlh_nee_mis_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
+                      uint32_t heuristic, double *sums, double *sq) {
+  return nee_probe(width, spp, first_sample, n_lights, lights, light_samples, seg_tmax, &heuristic, sums, sq);
+}
+static int nee_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32_t n_lights, const double *lights, uint32_t light_samples, double seg_tmax,
+                     const uint32_t *heuristic, double *sums, double *sq) {
   try {
     scenes::RtiowScene s = scenes::golden_test_scene();
     s.params.image_width = (size_t)width, s.params.samples_per_pixel = (size_t)spp;
@@ -692,7 +703,8 @@ int rlh_nee_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32_t 
       const double *p = lights + (size_t)l * 12;
       ql.push_back({rtiow::Vec3(p[0], p[1], p[2]), rtiow::Vec3(p[3], p[4], p[5]), rtiow::Vec3(p[6], p[7], p[8]), rtiow::Vec3(p[9], p[10], p[11])});
     }
-    rtiow::Camera::Moments m = rtiow::render_nee(cam, *s.world, ql, light_samples, seg_tmax, first_sample);
+    rtiow::Camera::Moments m = heuristic ? rtiow::render_nee_mis(cam, *s.world, ql, light_samples, seg_tmax, (rtiow::Camera::MisHeuristic)*heuristic, first_sample)
+                                         : rtiow::render_nee(cam, *s.world, ql, light_samples, seg_tmax, first_sample);
     std::memcpy(sums, m.sums.data(), m.sums.size() * sizeof(double));
     std::memcpy(sq, m.sq.data(), m.sq.size() * sizeof(double));
     return 0;

@@ -877,6 +877,16 @@ struct Camera {
   // expectation.  -> render_moments' sums and second moments, [H][W][3].  Worlds with a ConstantMedium are refused.
   Moments render_nee(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples = 1, double seg_tmax = 1.0 - 1e-6,
                      uint64_t first_sample = 0) const;
+  // render_nee with multiple importance sampling (rl_rtiow_render_nee_mis_rows): every light point is weighted against the scattered ray's
+  // density and the scattered ray of a vertex that sampled the lights is connected to each light it crosses with the complementary weight.
+  // The same draws, path and expectation as render_nee; no single sample exceeds what the lights emit.
+  enum class MisHeuristic : uint32_t { Balance = RL_MIS_BALANCE, Power = RL_MIS_POWER };
+  Moments render_nee_mis(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples = 1, double seg_tmax = 1.0 - 1e-6,
+                         MisHeuristic heuristic = MisHeuristic::Balance, uint64_t first_sample = 0) const;
+
+ private:
+  Moments nee_moments(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples, double seg_tmax, uint64_t first_sample,
+                      const uint32_t *heuristic) const;
 };
 // Camera::render_ao as a function of the camera and the world
 inline Camera::AmbientOcclusion render_ao(const Camera &camera, const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample = 0) {
@@ -891,6 +901,11 @@ inline Camera::DirectLight render_direct(const Camera &camera, const Hittable &w
 inline Camera::Moments render_nee(const Camera &camera, const Hittable &world, const std::vector<Camera::QuadLight> &lights, uint32_t light_samples = 1,
                                   double seg_tmax = 1.0 - 1e-6, uint64_t first_sample = 0) {
   return camera.render_nee(world, lights, light_samples, seg_tmax, first_sample);
+}
+// Camera::render_nee_mis as a function of the camera and the world
+inline Camera::Moments render_nee_mis(const Camera &camera, const Hittable &world, const std::vector<Camera::QuadLight> &lights, uint32_t light_samples = 1,
+                                      double seg_tmax = 1.0 - 1e-6, Camera::MisHeuristic heuristic = Camera::MisHeuristic::Balance, uint64_t first_sample = 0) {
+  return camera.render_nee_mis(world, lights, light_samples, seg_tmax, heuristic, first_sample);
 }
 
 // ---------------------------------------------------------------- denoising (rl_denoise_atrous; defined in host_render.cpp)

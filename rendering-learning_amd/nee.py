@@ -5,6 +5,9 @@ render_features, render_ao and render_direct), a path of at most max_depth verti
 light_samples points drawn on each quad light from the sample's own stream (render_direct's draws, geometry term and shadow segment) and in
 exchange does not count the emission its scattered ray finds.  `lights` must list every DiffuseLight surface of the scene for the estimate
 to have ray_color's expectation.  The outputs are render_moments': the sum of the sample colours and the sum of their squares.
+
+render_nee_mis* weight the light points against the scattered ray and connect that ray to the lights it crosses (multiple importance
+sampling): the same expectation, and no sample larger than what the lights emit.
 """
 import ctypes as C
 
@@ -89,6 +92,62 @@ def render_pixels_nee_device(camera, world, d_xs, d_ys, n, lights, light_samples
               *sc, C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
 
+# ----------------------------------------------------------------------------- with multiple importance sampling
+HEURISTICS = {"balance": 0, "power": 1}  # RL_MIS_BALANCE, RL_MIS_POWER
+
+
+def _heuristic(heuristic):
+    if not isinstance(heuristic, str) or heuristic not in HEURISTICS:
+        raise ValueError(f"heuristic must be one of {tuple(HEURISTICS)}")
+    return HEURISTICS[heuristic]
+
+
+def render_nee_mis(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", first_sample=0, row_first=0, row_step=1, stats=None,
+                   want=None, allow_degenerate=False):
+    """render_nee with multiple importance sampling (include/rl_render.h "NEE path renders with multiple importance sampling"; DESIGN.md
+    §3.23): every light point is weighted against the scattered ray's density, and the scattered ray of a vertex that sampled the lights is
+    connected to each light it crosses with the complementary weight.  heuristic: "balance" or "power" (exponent 2).  The same draws, the
+    same path and the same expectation as render_nee; no single sample exceeds what the lights emit.  -> PathNEE([nrows, W, 3])."""
+    h = _heuristic(heuristic)
+    nrows = api.rows_for(camera.c.image_height, row_first, row_step)
+    a, ptrs = _host(want, (nrows, camera.c.image_width))
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_nee_mis_rows, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, h, *ptrs, stats=stats,
+              counting=True, allow_degenerate=allow_degenerate)
+    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+
+
+def render_nee_mis_device(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", stream=0, row_first=0, row_step=1, first_sample=0,
+                          stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0):
+    """render_nee_device's buffers and asynchrony, render_nee_mis's estimate."""
+    h = _heuristic(heuristic)
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_nee_mis_device, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, h,
+              C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+
+
+def render_pixels_nee_mis(camera, world, xs, ys, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", first_sample=0, stats=None, want=None,
+                          allow_degenerate=False):
+    """The values of pixels (xs[i], ys[i]), [n, 3]: what render_nee_mis holds at [ys[i], xs[i]].  The list rules and the meaning of stats are
+    render_pixels_nee's."""
+    h = _heuristic(heuristic)
+    xs, ys = api._pixel_list(xs, ys)
+    a, ptrs = _host(want, (xs.size,))
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_pixels_nee_mis, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, *sc, h,
+              *ptrs, stats=stats, allow_degenerate=allow_degenerate)
+    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+
+
+def render_pixels_nee_mis_device(camera, world, d_xs, d_ys, n, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", stream=0, first_sample=0,
+                                 stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0):
+    """render_pixels_nee_device's buffers, list rules and asynchrony, render_nee_mis's estimate."""
+    h = _heuristic(heuristic)
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    api._call(api.render_lib().rl_rtiow_render_pixels_nee_mis_device, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys),
+              int(n), *sc, h, C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+
+
 def cpp_mirror_probe(width, spp, first_sample, lights, light_samples, seg_tmax=SEG_TMAX):
     """rtiow::render_nee of the C++ mirror on golden_test_scene at image_width = width -> PathNEE([H, W, 3]) (the height is the scene's
     aspect ratio's).  For tests of the mirror; RLError carries rlh_last_error."""
@@ -100,5 +159,20 @@ def cpp_mirror_probe(width, spp, first_sample, lights, light_samples, seg_tmax=S
     a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
     keep, sc = _scalars(lights, light_samples, seg_tmax)
     if H.rlh_nee_probe(int(width), int(spp), int(first_sample), *sc, *ptrs) != 0:
+        raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
+    return PathNEE(a["sums"], a["sq"], spp, light_samples)
+
+
+def cpp_mirror_probe_mis(width, spp, first_sample, lights, light_samples, seg_tmax=SEG_TMAX, heuristic="balance"):
+    """rtiow::render_nee_mis of the C++ mirror, as cpp_mirror_probe."""
+    h = _heuristic(heuristic)
+    H = api.host_lib()
+    world = api.World.golden_test_scene()
+    p = world.params
+    p.image_width, p.samples_per_pixel = int(width), int(spp)
+    cam = api.Camera(p)
+    a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
+    keep, sc = _scalars(lights, light_samples, seg_tmax)
+    if H.rlh_nee_mis_probe(int(width), int(spp), int(first_sample), *sc, h, *ptrs) != 0:
         raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
     return PathNEE(a["sums"], a["sq"], spp, light_samples)

@@ -1,0 +1,195 @@
+"""CPU tier: the entry points of the NEE path renders with multiple importance sampling (rl_rtiow_render_nee_mis_rows / _device,
+rl_rtiow_render_pixels_nee_mis / _device) are exported, declared in include/rl_render.h, listed in api.RENDER_SYMBOLS and wired into the
+Python module (nee.py) and the C++ mirror; every refusal of the NEE path renders and a heuristic beyond the two end in RL_E_INVALID before
+a device is looked at; without a GPU they fail LOUDLY (RL_E_NO_DEVICE, no CPU fallback).  Outputs stay untouched in every case."""
+import ctypes as C
+import math
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NEW = {"rl_rtiow_render_nee_mis_rows": 13, "rl_rtiow_render_nee_mis_device": 14, "rl_rtiow_render_pixels_nee_mis": 14,
+       "rl_rtiow_render_pixels_nee_mis_device": 15}
+INF = float("inf")
+NAN = float("nan")
+GOOD = [0.0, 4.0, 0.0, 2.0, 0.0, 0.0, 0.0, 0.0, 2.0, 5.0, 4.0, 3.0]  # Q, u, v, E
+
+
+def _gpu_present():
+    try:
+        import torch
+        return torch.cuda.is_available()
+    except Exception:
+        return False
+
+
+def _camera(rl, spp=2, max_depth=5):
+    return rl.Camera(rl.CameraParams(aspect_ratio=1.5, image_width=6, samples_per_pixel=spp, max_depth=max_depth))
+
+
+def _forms(lib, cam, scene=None):
+    """The four entry points as f(L, lights, K, T, heuristic, sums, sq) -> rc with everything else valid but the scene (NULL: a later rule)."""
+    xs = np.arange(4, dtype=np.uint32)
+    ys = np.zeros(4, dtype=np.uint32)
+    c = C.byref(cam.c)
+    return {
+        "rows": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_nee_mis_rows(scene, c, 0, 0, 1, L, li, k, t, h, s, q, None),
+        "device": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_nee_mis_device(scene, c, 0, 0, 1, L, li, k, t, h, s, q, None, None),
+        "pixels": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_pixels_nee_mis(scene, c, 0, xs.ctypes.data, ys.ctypes.data, 4, L, li, k, t, h, s, q, None),
+        "pixels_device": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_pixels_nee_mis_device(scene, c, 0, xs.ctypes.data, ys.ctypes.data, 4, L, li, k, t, h, s,
+                                                                                                q, None, None),
+    }
+
+
+def test_mis_entry_points_are_exported_declared_and_listed(rl):
+    lib = rl.api.render_lib()
+    text = open(os.path.join(ROOT, "include", "rl_render.h")).read()
+    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    for s, nargs in NEW.items():
+        assert hasattr(lib, s), s
+        assert s in rl.api.RENDER_SYMBOLS, s
+        assert re.search(r"\bint\s+%s\s*\(" % s, header), s
+        assert len(getattr(lib, s).argtypes) == nargs, s
+        plain = getattr(lib, s.replace("_mis", ""))
+        # the NEE signature with a uint32_t heuristic behind seg_tmax
+        at = list(getattr(lib, s).argtypes)
+        i = at.index(C.c_double)
+        assert at[i + 1] is C.c_uint32 and at[:i + 1] + at[i + 2:] == list(plain.argtypes), s
+    assert re.search(r"#define\s+RL_MIS_BALANCE\s+0u", header) and re.search(r"#define\s+RL_MIS_POWER\s+1u", header)
+    assert "NEE path renders with multiple importance sampling" in text
+    assert lib.rl_abi_version() == 6  # the additions are backward compatible
+    assert hasattr(rl.api.host_lib(), "rlh_nee_mis_probe") and "rlh_nee_mis_probe" in rl.api.HOST_SIGNATURES
+    for m in ("render_nee_mis", "render_nee_mis_device", "render_pixels_nee_mis", "render_pixels_nee_mis_device"):
+        assert callable(getattr(rl, m)) and getattr(rl, m) is getattr(rl.nee, m), m
+    assert rl.nee.HEURISTICS == {"balance": 0, "power": 1}
+    # not on api.Camera and not in api: tests/test_binding_calls.py compares their public callables with a committed fixture
+    assert not any("nee" in n.split("_") for n in dir(rl.api.Camera)) and not hasattr(rl.api, "render_nee_mis")
+
+
+def test_every_nee_refusal_and_a_third_heuristic_come_before_a_device_is_looked_at(rl):
+    """The NEE path renders' rules (the direct-lighting renders' on n_lights, lights, light_samples, S L K and seg_tmax; max_depth == 0;
+    both outputs NULL) with either heuristic, and heuristic = 2, 3 or 2^32 - 1 with everything else legal: RL_E_INVALID "bad argument" from
+    every form, whether or not the library has a device (nothing here initialises one), outputs untouched.  Calls that get past these rules
+    reach RL_E_NO_DEVICE on a machine without a GPU."""
+    api = rl.api
+    lib = api.render_lib()
+    cam, big, flat = _camera(rl), _camera(rl, spp=1 << 16), _camera(rl, max_depth=0)
+    sums, sq = np.full((24, 3), 7.0), np.full((24, 3), 8.0)
+    s, q = sums.ctypes.data, sq.ctypes.data
+    arr = lambda rows: np.array(rows, dtype=np.float64).reshape(-1, 12)
+    one = arr([GOOD])
+    seventeen = arr([GOOD] * 17)
+
+    def bad(i, v):
+        a = arr([GOOD, GOOD])
+        a[1, i] = v
+        return a
+    parallel = arr([GOOD])
+    parallel[0, 6:9] = (-4.0, 0.0, 0.0)  # v = -2 u: u x v == 0
+    zero_u = arr([GOOD])
+    zero_u[0, 3:6] = 0.0
+    T = 1.0 - 1e-6
+    refused = [(0, one, 1, T, s, q), (17, seventeen, 1, T, s, q), (1, None, 1, T, s, q), (1, one, 0, T, s, q),
+               (2, bad(0, NAN), 1, T, s, q), (2, bad(4, INF), 1, T, s, q), (2, bad(8, -INF), 1, T, s, q), (2, bad(11, NAN), 1, T, s, q),
+               (1, parallel, 1, T, s, q), (1, zero_u, 1, T, s, q),
+               (1, one, 1, NAN, s, q), (1, one, 1, 1e-10, s, q), (1, one, 1, 0.0, s, q), (1, one, 1, -0.5, s, q),
+               (1, one, 1, math.nextafter(1.0, 2.0), s, q), (1, one, 1, INF, s, q), (1, one, 1, T, None, None)]
+    for h in (0, 1):
+        for name, f in _forms(lib, cam).items():
+            for L, li, k, t, ps, pq in refused:
+                assert f(L, None if li is None else li.ctypes.data, k, t, h, ps, pq) == api.RL_E_INVALID, (name, h, L, k, t)
+                assert b"bad argument" in lib.rl_last_error(), (name, h, L, k, t, lib.rl_last_error())
+        for name, f in _forms(lib, flat).items():  # a path has at least one vertex
+            assert f(1, one.ctypes.data, 1, T, h, s, q) == api.RL_E_INVALID, name
+            assert b"bad argument" in lib.rl_last_error(), name
+    sixteen = arr([GOOD] * 16)
+    for name, f in _forms(lib, big).items():  # S = 2^16, L = 16: K = 2^12 is S L K = 2^32, one less is legal
+        assert f(16, sixteen.ctypes.data, 1 << 12, T, 1, s, q) == api.RL_E_INVALID, name
+        assert b"bad argument" in lib.rl_last_error(), name
+    for name, f in _forms(lib, cam).items():  # L K alone beyond 32 bits
+        assert f(16, sixteen.ctypes.data, 0xFFFFFFFF, T, 0, s, q) == api.RL_E_INVALID, name
+    for h in (2, 3, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF):  # the heuristic alone
+        for name, f in _forms(lib, cam).items():
+            assert f(1, one.ctypes.data, 4, T, h, s, q) == api.RL_E_INVALID, (name, h)
+            assert b"bad argument" in lib.rl_last_error(), (name, h)
+    assert (sums == 7.0).all() and (sq == 8.0).all()
+    if not _gpu_present():
+        assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
+        legal = [(cam, 1, one, 4, T, s, q), (big, 16, sixteen, (1 << 12) - 1, T, s, q), (cam, 16, sixteen, 3, 1.0, s, q),
+                 (cam, 1, one, 4, math.nextafter(1e-10, 1.0), s, q), (cam, 1, one, 4, T, s, None), (cam, 1, one, 4, T, None, q),
+                 (_camera(rl, max_depth=1), 1, one, 1, T, s, q)]
+        for h in (0, 1):
+            for cm, L, li, k, t, ps, pq in legal:
+                for name, f in _forms(lib, cm).items():
+                    assert f(L, li.ctypes.data, k, t, h, ps, pq) == api.RL_E_NO_DEVICE, (name, h, L, k, t)
+        assert (sums == 7.0).all() and (sq == 8.0).all()
+
+
+def test_heuristic_and_want_are_checked_in_python(rl, monkeypatch):
+    def no_library():
+        raise AssertionError("the library was reached")
+    cam = _camera(rl)
+    monkeypatch.setattr(rl.api, "render_lib", no_library)
+    monkeypatch.setattr(rl.api, "host_lib", no_library)
+    one = np.array([GOOD])
+    for h in ("Balance", "max", "", None, 0, 1, 2, b"power"):  # the two names, as strings, and nothing else
+        for call in (lambda: rl.render_nee_mis(cam, object(), one, 4, heuristic=h),
+                     lambda: rl.render_pixels_nee_mis(cam, object(), [0], [0], one, 4, heuristic=h),
+                     lambda: rl.render_nee_mis_device(cam, object(), one, 4, heuristic=h, d_sums=0x1000),
+                     lambda: rl.render_pixels_nee_mis_device(cam, object(), 0x1000, 0x2000, 1, one, 4, heuristic=h, d_sq=0x3000),
+                     lambda: rl.nee.cpp_mirror_probe_mis(6, 2, 0, one, 4, heuristic=h)):
+            with pytest.raises(ValueError):
+                call()
+    for h in ("balance", "power"):
+        with pytest.raises(ValueError):
+            rl.render_nee_mis(cam, object(), one, 4, heuristic=h, want=())
+        with pytest.raises(ValueError):
+            rl.render_nee_mis(cam, object(), one, 4, heuristic=h, want=("sums", "direct"))
+        with pytest.raises(ValueError):
+            rl.render_pixels_nee_mis(cam, object(), [0, 1], [0], one, 4, heuristic=h)
+        with pytest.raises(ValueError):
+            rl.render_nee_mis(cam, object(), np.zeros((0, 12)), 4, heuristic=h)
+
+
+def test_last_query_names_the_mis_kernels(rl, monkeypatch):
+    api = rl.api
+
+    class Lib:
+        def __init__(self, kid):
+            self.kid = kid
+
+        def rl_debug_last_query(self, out):
+            out[0], out[1] = self.kid, 3
+            return 0
+    for kid, name in ((11, "nee_reference"), (12, "nee_fast"), (13, "nee_mis_reference"), (14, "nee_mis_fast")):
+        monkeypatch.setattr(api, "render_lib", lambda kid=kid: Lib(kid))
+        assert api.last_query() == {"kernel": name, "retraced": 3}
+
+
+@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+def test_mis_renders_without_a_device_fail_loudly_and_media_scenes_come_after(rl):
+    """Without a device every call that passes the argument rules ends at RL_E_NO_DEVICE, a media scene included: the media refusal
+    (RL_E_UNSUPPORTED) is a rule about the compiled scene and is asserted on the device (tests/test_gpu_render_nee_mis.py)."""
+    api = rl.api
+    lib = api.render_lib()
+    assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
+    world = rl.World.golden_test_scene()
+    smoke = rl.World.example_scene("cornell_smoke")
+    cam = _camera(rl)
+    lights = [((0, 4, 0), (2, 0, 0), (0, 0, 2), 5.0)]
+    for call in (lambda: rl.render_nee_mis(cam, world, lights, 4), lambda: rl.render_nee_mis(cam, world, lights, 4, 0.5, "power", stats={}),
+                 lambda: rl.render_pixels_nee_mis(cam, world, [0, 1], [0, 1], lights, 4, heuristic="power"),
+                 lambda: rl.render_nee_mis_device(cam, world, lights, 4, d_sums=0x1000),
+                 lambda: rl.render_pixels_nee_mis_device(cam, world, 0x1000, 0x2000, 2, lights, 4, heuristic="power", d_sq=0x3000, stats={}),
+                 lambda: rl.render_nee_mis(cam, smoke, lights, 4)):
+        with pytest.raises(rl.RLError) as e:
+            call()
+        assert e.value.code == api.RL_E_NO_DEVICE
+    # the C++ mirror reaches the same wall
+    for h in ("balance", "power"):
+        with pytest.raises(rl.RLError) as e:
+            rl.nee.cpp_mirror_probe_mis(6, 2, 0, lights, 4, heuristic=h)
+        assert "rl_init has not succeeded" in str(e.value)  # (the mirror creates its scene first)
