@@ -107,6 +107,13 @@ RTC_DEV_TRI = np.dtype([("p1", "<f8", 3), ("e1", "<f8", 3), ("e2", "<f8", 3), ("
 RTC_GUARD = np.dtype([("box", "<f4", 6), ("skip", "<u4"), ("tri", "<u4")])
 assert RTC_DEV_OP.itemsize == 64 and RTC_DEV_TRI.itemsize == 160 and RTC_GUARD.itemsize == 32
 ROP_END, ROP_ENTER, ROP_EXIT, ROP_BOUNDS, ROP_TRIS = 0, 1, 2, 3, 4
+# one record of the RTIOW launch log (csrc/rl_rtiow_launch.h RtiowLaunchRecord)
+RTIOW_LAUNCH = np.dtype([("kernel", "S192"), ("seq", "<u8"), ("work_items", "<u8"), ("lds_bytes", "<u8"), ("funnel", "<u4"), ("wg_size", "<u4"),
+                         ("blocks", "<u4"), ("sample_begin", "<u4"), ("sample_end", "<u4"), ("resume", "<u4"), ("tile_order", "<u4"),
+                         ("steal_state", "<u4"), ("fg_top", "<u4"), ("tune", "<u4", 4), ("n_pixels", "<u4")])
+assert RTIOW_LAUNCH.itemsize == 272
+RTIOW_LAUNCH_LOG = 64  # records the library keeps
+NEVER_OFFERED = 0xFFFFFFFF  # steal_record: a pixel no lane released
 NO_HIT = 0xFFFFFFFF  # out_hit_index of a ray hit() returns None for
 
 MAT_FLAT, MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_DIFFUSE_LIGHT, MAT_ISOTROPIC = 0, 1, 2, 3, 4, 5
@@ -316,6 +323,9 @@ RENDER_SIGNATURES = {
     "rl_debug_last_denoise_launch": (None, [_P]),
     "rl_debug_rtc_program": (_I, [_P, _P, _P, _P, _PU64, _PU64]),
     "rl_debug_last_rtc_launch": (None, [_P]),
+    "rl_debug_rtiow_launch_total": (_U64, []),
+    "rl_debug_rtiow_launch_log": (_I, [_P, _U32]),
+    "rl_debug_steal_read": (_I, [_P, _PU32, _PU32, _U64]),
 }
 # every symbol include/rl_render.h declares (checked by tests/test_abi.py)
 RENDER_SYMBOLS = [n for n in RENDER_SIGNATURES if not n.startswith("rl_debug_")]
@@ -677,6 +687,60 @@ def last_rtc_launch():
     out = (C.c_uint64 * 4)()
     render_lib().rl_debug_last_rtc_launch(out)
     return {"kernel": {1: "rtc", 2: "full"}.get(int(out[0]), "none"), "list": bool(out[1]), "lds_bytes": int(out[2]), "blocks": int(out[3])}
+
+
+def rtiow_launch_total():
+    """rl_debug_rtiow_launch_total: how many RTIOW render launches this process has made (frame / moments / adaptive, sample-parallel, pixel
+    list and path query: the three launch funnels of csrc/rl_rtiow_launch.h).  Read it before a call, hand it to rtiow_launches() after."""
+    return int(render_lib().rl_debug_rtiow_launch_total())
+
+
+def rtiow_launches(since_total=0):
+    """rl_debug_rtiow_launch_log: the launches made since rtiow_launch_total() returned since_total, oldest first, one dict each:
+      "kernel"        the instantiation launched, as the runtime names the function pointer that was handed to the launch, without return
+                      type, namespace and parameter list: "rtiow_wave_kernel<1024, 4, false, true>"; "name" holds the string as recorded
+      "funnel"        "value" / "pointer" (how the persistent kernel takes its parameter block) / "coop"
+      "wg_size", "blocks", "lds_bytes" (dynamic LDS), "work_items" (what the grid was sized for)
+      "sample_begin", "sample_end", "resume", "tile_order", "steal_state" (the last two: whether the pointer was set), "fg_top", "tune"
+      "n_pixels"      of a cooperative launch; 0 otherwise
+    The library keeps the last RTIOW_LAUNCH_LOG launches: asking for more than that raises."""
+    L = render_lib()
+    want = int(L.rl_debug_rtiow_launch_total()) - int(since_total)
+    if want < 0 or want > RTIOW_LAUNCH_LOG:
+        raise ValueError(f"{want} launches since total {since_total}: the log holds the last {RTIOW_LAUNCH_LOG}")
+    buf = np.zeros(max(want, 1), dtype=RTIOW_LAUNCH)
+    got = int(L.rl_debug_rtiow_launch_log(buf.ctypes.data_as(C.c_void_p), want)) if want else 0
+    out = []
+    for r in buf[:got]:
+        if int(r["seq"]) <= int(since_total):  # (a launch of another thread moved the ring between the two calls)
+            continue
+        name = bytes(r["kernel"]).decode()
+        short = name[5:] if name.startswith("void ") else name
+        depth = 0
+        for i, ch in enumerate(short):  # cut the parameter list: the first "(" outside the template arguments
+            depth += ch == "<"
+            depth -= ch == ">"
+            if ch == "(" and depth == 0 and i > 0:
+                short = short[:i]
+                break
+        short = short.replace("rl::", "")
+        out.append({"kernel": short, "name": name, "seq": int(r["seq"]), "funnel": ("value", "pointer", "coop")[int(r["funnel"])],
+                    "wg_size": int(r["wg_size"]), "blocks": int(r["blocks"]), "lds_bytes": int(r["lds_bytes"]), "work_items": int(r["work_items"]),
+                    "sample_begin": int(r["sample_begin"]), "sample_end": int(r["sample_end"]), "resume": int(r["resume"]),
+                    "tile_order": bool(r["tile_order"]), "steal_state": bool(r["steal_state"]), "fg_top": int(r["fg_top"]),
+                    "tune": tuple(int(t) for t in r["tune"]), "n_pixels": int(r["n_pixels"])})
+    return out
+
+
+def steal_record(world, n_pixels):
+    """rl_debug_steal_read: waits for the device, then (state, n) of the first n_pixels pixels (rows x W of the shard) of the scene's most
+    recent stealing launch, two uint32 arrays.  state 3: the pixel finished.  n: the sample at which the lane that rendered the pixel last
+    released it to a wave that had asked for it (csrc/rl_rtiow_wave_body.inc, the sample boundary in GEN); NEVER_OFFERED where none did.
+    A pixel is offered to one wave at most, so n counts hand-overs: one per pixel whose n is set — but for a request withdrawn in the
+    instant of its release, whose pixel stays with its lane.  A render that does not steal leaves the record as it was."""
+    state, n = np.zeros(int(n_pixels), dtype=np.uint32), np.zeros(int(n_pixels), dtype=np.uint32)
+    _check(render_lib().rl_debug_steal_read(world.device(), state.ctypes.data_as(_PU32), n.ctypes.data_as(_PU32), int(n_pixels)))
+    return state, n
 
 
 def rtc_program(world):

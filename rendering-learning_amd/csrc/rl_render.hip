@@ -6,6 +6,7 @@
 // No CPU fallback: every compute entry point fails with RL_E_NO_DEVICE unless rl_init succeeded on a GPU.
 #include <hip/hip_runtime.h>
 
+#include <cxxabi.h>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -696,6 +697,7 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
       HIP_TRY(ms->d_steal_state.reserve(npix));
       HIP_TRY(ms->d_steal_n.reserve(npix));
       HIP_TRY(hipMemsetAsync(ms->d_steal_state, 0, npix * sizeof(uint32_t), stream));
+      HIP_TRY(hipMemsetAsync(ms->d_steal_n, 0xFF, npix * sizeof(uint32_t), stream));  // 0xFFFFFFFF: never released (rl_debug_steal_read)
       HIP_TRY(hipMemsetAsync(scene->d_scratch + 256, 0, 4, stream));
       P.steal_state = ms->d_steal_state, P.steal_n = ms->d_steal_n, P.steal_counter = (uint32_t *)(scene->d_scratch + 256);
       P.coop_leaf_boxes = scene->d_fast_leaf_boxes;
@@ -1051,6 +1053,33 @@ int rl_debug_rtc_program(const rl_rtc_scene_desc *desc, void *ops, void *tris, v
 // full kernel), 1 for the list flavour, the launch's dynamic LDS bytes (0: the scene is read from global memory), its workgroups.
 void rl_debug_last_rtc_launch(uint64_t out[4]) {
   if (out) out[0] = g_last_rtc_kernel.load(), out[1] = g_last_rtc_list.load(), out[2] = g_last_rtc_lds.load(), out[3] = g_last_rtc_blocks.load();
+}
+// Tests: the RTIOW launch log (rl_rtiow_launch.h).  The number of launches the three funnels have made in this process ...
+unsigned long long rl_debug_rtiow_launch_total(void) {
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  return g_launch_total;
+}
+// ... and the newest min(cap, 64, total) of their records (RtiowLaunchRecord, 272 bytes each), oldest of them first.  Returns their number.
+int rl_debug_rtiow_launch_log(void *out, uint32_t cap) {
+  if (!out) return 0;
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  const uint64_t n = std::min<uint64_t>(std::min<uint64_t>(cap, RTIOW_LAUNCH_LOG), g_launch_total);
+  for (uint64_t i = 0; i < n; i++) ((RtiowLaunchRecord *)out)[i] = g_launch_log[(g_launch_total - n + i) % RTIOW_LAUNCH_LOG];
+  return (int)n;
+}
+// Tests: the hand-over record of the scene's most recent stealing launch (rtiow_render_launch: the resume launch of a small shard), after
+// everything enqueued has finished: steal_state (3 = the pixel finished) and steal_n (the sample at which a lane last offered the pixel to
+// a wave that asked for it; 0xFFFFFFFF: never) of its first n_pixels pixels.
+int rl_debug_steal_read(const rl_scene *scene, uint32_t *state_out, uint32_t *n_out, uint64_t n_pixels) {
+  if (!scene || !state_out || !n_out || !scene->d_steal_state || !scene->d_steal_n || n_pixels > scene->d_steal_state.size() || n_pixels > scene->d_steal_n.size())
+    return RL_E_INVALID;
+  DevCtx *c;
+  int rc0 = scene_context(scene, c);
+  if (rc0 != RL_OK) return rc0;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(state_out, scene->d_steal_state, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(n_out, scene->d_steal_n, n_pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RL_OK;
 }
 // force an RTIOW kernel variant (0 auto, 1 nested-loop, 2 general, 512/768/1024 wave)
 void rl_debug_set_rtiow_variant(int v) { g_sw.rtiow_variant = v; }

@@ -5,6 +5,7 @@
 //   kernel tables    — runtime flags -> template instantiation, one function per kernel family
 //   LDS layouts      — fastg_prepare (fast general kernel), wave_general_lds (reference-order kernel)
 //   persistent grid  — persistent_blocks and the two launch_persistent forms (parameter block by value / by pointer); coop_launch
+//   launch log       — what those three funnels launched, by the kernel pointer's own name (rl_debug_rtiow_launch_log; tests assert routes from it)
 // Routing (which family a call takes) and flow (passes, the cost-sorted two-phase render) stay with the launchers.
 // A new flavour is one row in a table: taking a kernel's address is what instantiates it, so a table reaches exactly the kernels it names.
 #pragma once
@@ -147,6 +148,53 @@ FastgLayout fastg_prepare(const FastGeneral &tree, bool trans, bool media, bool 
 // LDS of a reference-order general launch (512 lanes): the rings, + the parked HitRecord of a medium scope: 96 B of LDS per lane
 size_t wave_general_lds(bool media) { return (size_t)512 * (16 + (media ? MEDIA_SAVE_WORDS : 0)) * sizeof(unsigned long long); }
 
+// ---- launch log
+// Every launch of the three funnels below leaves one record in a process-wide ring of the last RTIOW_LAUNCH_LOG records (host only: one
+// guarded copy per launch).  The kernel's name is asked of the runtime for the FUNCTION POINTER the launch was handed
+// (hipKernelNameRefByPtr, demangled; once per distinct pointer), never derived from the flags that chose it: a table row that returns
+// another instantiation than the one a test expects shows here even where both render the same bits.  api.RTIOW_LAUNCH mirrors the layout.
+struct RtiowLaunchRecord {
+  char kernel[192];       // e.g. "void rl::rtiow_wave_kernel<1024, 4, false, true>(rl::RtiowParams)"; "?" where the runtime knows no name
+  uint64_t seq;           // 1 for the process's first launch
+  uint64_t work_items;    // persistent funnels: the slots / list elements the grid was sized for; cooperative: n_pixels
+  uint64_t lds_bytes;     // dynamic LDS
+  uint32_t funnel;        // 0 parameter block by value, 1 by pointer, 2 coop_launch
+  uint32_t wg_size, blocks;
+  uint32_t sample_begin, sample_end, resume, has_tile_order, has_steal_state, fg_top, tune[4];  // of the RtiowParams launched
+  uint32_t n_pixels;      // coop_launch: CoopParams::n_pixels; 0 otherwise
+};
+static_assert(sizeof(RtiowLaunchRecord) == 272, "api.RTIOW_LAUNCH states this layout");
+constexpr unsigned RTIOW_LAUNCH_LOG = 64;
+std::mutex g_launch_log_mu;
+RtiowLaunchRecord g_launch_log[RTIOW_LAUNCH_LOG];
+uint64_t g_launch_total = 0;
+std::map<const void *, std::string> g_kernel_names;
+
+void log_launch(const void *kern, hipStream_t stream, uint32_t funnel, uint32_t nt, uint32_t blocks, size_t lds, uint64_t work_items, const RtiowParams &P, uint32_t n_pixels) {
+  std::lock_guard<std::mutex> lk(g_launch_log_mu);
+  auto it = g_kernel_names.find(kern);
+  if (it == g_kernel_names.end()) {
+    const char *raw = hipKernelNameRefByPtr(kern, stream);
+    std::string name = raw && *raw ? raw : "?";
+    if (name.size() > 3 && name.compare(name.size() - 3, 3, ".kd") == 0) name.resize(name.size() - 3);  // (the descriptor's symbol)
+    if (name.compare(0, 2, "_Z") == 0) {
+      int status = 0;
+      if (char *d = abi::__cxa_demangle(name.c_str(), nullptr, nullptr, &status)) {
+        if (status == 0) name = d;
+        std::free(d);
+      }
+    }
+    it = g_kernel_names.emplace(kern, std::move(name)).first;
+  }
+  RtiowLaunchRecord &r = g_launch_log[g_launch_total % RTIOW_LAUNCH_LOG];
+  r = RtiowLaunchRecord{};
+  std::strncpy(r.kernel, it->second.c_str(), sizeof r.kernel - 1);
+  r.seq = ++g_launch_total, r.work_items = work_items, r.lds_bytes = lds, r.funnel = funnel, r.wg_size = nt, r.blocks = blocks;
+  r.sample_begin = P.sample_begin, r.sample_end = P.sample_end, r.resume = P.resume, r.has_tile_order = P.tile_order != nullptr, r.has_steal_state = P.steal_state != nullptr;
+  r.fg_top = P.fg_top, r.tune[0] = P.tune[0], r.tune[1] = P.tune[1], r.tune[2] = P.tune[2], r.tune[3] = P.tune[3];
+  r.n_pixels = n_pixels;
+}
+
 // ---- persistent grid
 
 // persistent lanes: as many workgroups as stay resident (LDS, 2048 lanes per CU), at most one lane per work item
@@ -168,8 +216,10 @@ int launch_prepare(const void *kern, size_t lds) {
 int launch_persistent(ValueKernel kern, int nt, size_t lds, uint64_t work_items, const RtiowParams &P, const rl_scene *, hipStream_t stream) {
   int rc = launch_prepare((const void *)kern, lds);
   if (rc != RL_OK) return rc;
-  hipLaunchKernelGGL(kern, dim3(persistent_blocks(work_items, nt, lds)), dim3(nt), lds, stream, P);
+  const uint32_t blocks = persistent_blocks(work_items, nt, lds);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, P);
   HIP_TRY(hipGetLastError());
+  log_launch((const void *)kern, stream, 0, (uint32_t)nt, blocks, lds, work_items, P, 0);
   return RL_OK;
 }
 // by pointer: every launch its own stream-ordered device copy (stage_params: two slots)
@@ -178,8 +228,10 @@ int launch_persistent(PointerKernel kern, int nt, size_t lds, uint64_t work_item
   if (rc != RL_OK) return rc;
   const RtiowParams *slot = nullptr;
   if ((rc = stage_params(scene, P, stream, slot)) != RL_OK) return rc;
-  hipLaunchKernelGGL(kern, dim3(persistent_blocks(work_items, nt, lds)), dim3(nt), lds, stream, slot);
+  const uint32_t blocks = persistent_blocks(work_items, nt, lds);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(nt), lds, stream, slot);
   HIP_TRY(hipGetLastError());
+  log_launch((const void *)kern, stream, 1, (uint32_t)nt, blocks, lds, work_items, P, 0);
   return RL_OK;
 }
 
@@ -199,6 +251,7 @@ int coop_launch(const RtiowParams &P, CoopParams C, uint64_t n, bool moments, bo
   if (ensure_lds_attr((const void *)kern, lds) != 0) return set_err(RL_E_DEVICE, "hipFuncSetAttribute failed");
   hipLaunchKernelGGL(kern, dim3(blocks), dim3(COOP_NW * 64), lds, stream, P, C);
   HIP_TRY(hipGetLastError());
+  log_launch((const void *)kern, stream, 2, COOP_NW * 64, blocks, lds, n, P, C.n_pixels);
   return RL_OK;
 }
 

@@ -397,6 +397,10 @@ def drive(api, patch):
         # ---- RTC read-outs (appended: the rows above keep their places in the fixture)
         run("last_rtc_launch", api.last_rtc_launch)
         run("rtc_program", api.rtc_program, rtc)
+        # ---- RTIOW launch log and hand-over record (appended likewise; the recorder's total is 7: seven launches asked for)
+        run("rtiow_launch_total", api.rtiow_launch_total)
+        run("rtiow_launches", api.rtiow_launches, 0)
+        run("steal_record", api.steal_record, world, 8)
     finally:
         for w in worlds:  # the handles are the recorder's: nothing of the real library may ever see them
             w._device = None

@@ -7,7 +7,11 @@ One small frame that takes all of them, 64 x 36 at 72 spp (>= 64: the probe laun
 run), is rendered by the plain fast kernel, without the per-pixel entry table, by the work-stealing instantiation on a row shard, by the
 sample-parallel kernel with k = 1 and k = 4, by the moments kernel, and by an adaptive render that stops some pixels at its first
 checkpoint.  No tolerance between GPU forms: each must give the bits of its reference-order form (the counting render with stats=,
-the LDS_SCENE = 3 layout), and the counting frame must be the CPU oracle's within the tight bar test_gpu_fast_traversal.py uses."""
+the LDS_SCENE = 3 layout), and the counting frame must be the CPU oracle's within the tight bar test_gpu_fast_traversal.py uses.
+
+Equal bits do not tell which kernel rendered them, so every step also asserts, from the library's launch log (api.rtiow_launches), the
+instantiation its comment names.  (That is how the moments and adaptive steps were found to have compared the counting reference-order
+kernel with itself: Camera.render_moments and render_adaptive always count.  Their counter-free device forms now run beside them.)"""
 import numpy as np
 import pytest
 
@@ -98,6 +102,38 @@ def _indep(rl, cam, world, k):
     return buf.cpu().numpy(), st, counted, gs
 
 
+def _device(rl, world, shapes, call):
+    """A counter-free `_device` call into NaN- / 0xFF-filled buffers -> (host arrays, status)."""
+    import torch
+    dev = torch.device("cuda", 0)
+    bufs = [torch.full(s, float("nan"), dtype=torch.float64, device=dev) if dt is np.float64 else torch.full(s, -1, dtype=torch.int32, device=dev) for s, dt in shapes]
+    call(torch.cuda.current_stream(dev).cuda_stream, *[b.data_ptr() for b in bufs])
+    st = rl.api.render_status(world)
+    return [b.cpu().numpy() if dt is np.float64 else b.cpu().numpy().view(np.uint32) for b, (_, dt) in zip(bufs, shapes)], st
+
+
+# the instantiations the steps below name (1024 lanes, sphere layouts 4 = fast tree, 3 = guarded compact ops; the reference-order kernel)
+FAST, STEALING, COUNTING = "rtiow_wave_kernel<1024, 4, false, false>", "rtiow_wave_kernel<1024, 4, false, true>", "rtiow_wave_kernel<1024, 3, true, false>"
+INDEP, INDEP_COUNTING = "rtiow_wave_indep_kernel<1024, 4, false>", "rtiow_wave_general_indep_kernel<512, false, true, false>"
+MOMENTS_FAST, MOMENTS_GUARD, MOMENTS_COUNTING = "rtiow_wave_moments_kernel<1024, 4>", "rtiow_wave_moments_kernel<1024, 3>", "rtiow_wave_general_moments_kernel<512, false, true, false>"
+TWO = [(0, 8, 0, False), (8, SPP, 1, True)]  # the probe launch and the resumed launch in the sorted tile order
+ONE = [(0, SPP, 0, False)]
+
+
+class _Log:
+    def __init__(self, api):
+        self.api, self.total = api, api.rtiow_launch_total()
+
+    def ran(self, kernels, flow, what):
+        """The launches since the last call: these kernels, in this flow (sample range, resume, tile order)."""
+        recs = self.api.rtiow_launches(self.total)
+        self.total += len(recs)
+        assert [r["kernel"] for r in recs] == kernels, (what, [r["kernel"] for r in recs])
+        assert [(r["sample_begin"], r["sample_end"], r["resume"], r["tile_order"]) for r in recs] == flow, (what, recs)
+        assert [r["steal_state"] for r in recs] == [k == STEALING for k in kernels], what
+        return recs
+
+
 @pytest.fixture
 def wave_kernels(rl):
     """Small frames through the wave-scheduled kernels (not the cooperative one); every switch back to its default afterwards."""
@@ -115,7 +151,9 @@ def test_every_instantiation_renders_the_reference_order_bits(rl, oracle, wave_k
     world, cam = _scene(rl, name, depth)
     # the yardstick: the reference-order counting render, pinned to the CPU oracle
     gs, cs = {}, {}
+    log = _Log(api)
     counting = cam.render(world, stats=gs).data
+    log.ran([COUNTING] * 2, TWO, "counting")
     cpu = oracle.rtiow_render(world.desc, cam.c, stats=cs)
     for k in COUNTERS:
         assert gs[k] == cs[k], (k, gs[k], cs[k])
@@ -127,24 +165,35 @@ def test_every_instantiation_renders_the_reference_order_bits(rl, oracle, wave_k
     # plain fast kernel (probe launch + resumed launch, no stealing), with and without the per-pixel entry table
     api.set_steal(0.0)
     plain, st = _timed(rl, cam, world)
+    log.ran([FAST] * 2, TWO, "plain")
     assert _bits(plain, counting) and st["rays"] == gs["rays"] and st["flagged"] == 0
     if name == "built" and depth:
         assert st["slow_traces"] > 0  # the coincident pair
         assert np.unique(api.pixel_entry_table(world, 64 * 36)).size > 3  # sky pixels, leaf-only pixels, pixels that enter at inner nodes
     api.set_pixel_entry(0)
     root, st_root = _timed(rl, cam, world)
+    log.ran([FAST] * 2, TWO, "root walk")
     api.set_pixel_entry(3)
     assert _bits(root, counting) and st_root["rays"] == gs["rays"] and st_root["slow_traces"] == st["slow_traces"]
     api.set_lpt(False)  # one launch: no resume
     single, st_single = _timed(rl, cam, world)
+    log.ran([FAST], ONE, "single launch")
     api.set_lpt(True)
     assert _bits(single, counting) and st_single["rays"] == gs["rays"] and st_single["slow_traces"] == st["slow_traces"]
 
     # the work-stealing instantiation: the resumed launch of a row shard
     api.set_steal(3.0)
     shard, st_shard = _timed(rl, cam, world, 1, 2)
+    log.ran([FAST, STEALING], TWO, "stealing shard")
+    state, n = api.steal_record(world, 18 * W)
+    handed = n != api.NEVER_OFFERED
+    print(name, depth, "pixels handed over on the shard:", int(handed.sum()), "of", 18 * W)
+    assert (state == 3).all() and ((n[handed] >= 8) & (n[handed] < SPP)).all()
+    if depth:  # (without a ray a sample is a few instructions: a wave that asks may find every pixel finished)
+        assert handed.any()
     gs_shard = {}
     assert _bits(shard, cam.render_rows(world, 1, 2, stats=gs_shard)) and st_shard["rays"] == gs_shard["rays"]
+    log.ran([COUNTING] * 2, TWO, "counting shard")
     assert _bits(shard, counting[1::2])
     api.set_steal(0.0)
 
@@ -152,6 +201,7 @@ def test_every_instantiation_renders_the_reference_order_bits(rl, oracle, wave_k
     frames = []
     for k in (1, 4):
         fast, st_k, counted, gs_k = _indep(rl, cam, world, k)
+        log.ran([INDEP, INDEP_COUNTING], ONE * 2, ("indep", k))
         assert _bits(fast, counted) and st_k["rays"] == gs_k["rays"] and gs_k["flagged"] == 0, k
         frames.append((fast, gs_k["rays"]))
     api.set_indep_k(1)
@@ -163,7 +213,17 @@ def test_every_instantiation_renders_the_reference_order_bits(rl, oracle, wave_k
     api.set_fast_traversal(False)
     mom_ref = cam.render_moments(world)
     api.set_fast_traversal(True)
+    log.ran([MOMENTS_COUNTING] * 4, TWO * 2, "counting moments")  # (Camera.render_moments always counts: both are the reference-order kernel)
     assert _bits(mom.sums, counting) and _bits(mom.sq, mom_ref.sq) and _bits(mom_ref.sums, counting) and ms["rays"] == gs["rays"]
+    frame_shape = [((36, W, 3), np.float64)] * 2
+    (f_sums, f_sq), st_m = _device(rl, world, frame_shape, lambda stream, d0, d1: cam.render_moments_device(world, d0, d1, stream=stream))
+    log.ran([MOMENTS_FAST] * 2, TWO, "moments, fast layout")
+    api.set_fast_traversal(False)
+    (g_sums, g_sq), st_g = _device(rl, world, frame_shape, lambda stream, d0, d1: cam.render_moments_device(world, d0, d1, stream=stream))
+    api.set_fast_traversal(True)
+    log.ran([MOMENTS_GUARD] * 2, TWO, "moments, guarded layout")
+    assert _bits(f_sums, counting) and _bits(f_sq, mom.sq) and _bits(g_sums, counting) and _bits(g_sq, mom.sq)
+    assert st_m["rays"] == gs["rays"] == st_g["rays"] and st_m["flagged"] == 0
 
     # an adaptive render: some pixels stop at the first checkpoint (inside the probe launch: they must not be resumed), others never
     bound = 1e-6
@@ -171,7 +231,15 @@ def test_every_instantiation_renders_the_reference_order_bits(rl, oracle, wave_k
     api.set_fast_traversal(False)
     ad_ref = cam.render_adaptive(world, MIN, EVERY, abs_variance=bound)
     api.set_fast_traversal(True)
+    log.ran([MOMENTS_COUNTING] * 4, TWO * 2, "counting adaptive")  # (Camera.render_adaptive always counts)
     assert np.array_equal(ad.counts, ad_ref.counts) and _bits(ad.sums, ad_ref.sums) and _bits(ad.sq, ad_ref.sq)
+    shapes = frame_shape + [((36, W), np.uint32)]
+    for fast, kernel in ((True, MOMENTS_FAST), (False, MOMENTS_GUARD)):  # the stopping rule in the wave kernel's two layouts
+        api.set_fast_traversal(fast)
+        (d_sums, d_sq, d_counts), _ = _device(rl, world, shapes, lambda stream, d0, d1, d2: cam.render_adaptive_device(world, MIN, EVERY, d0, d1, d2, abs_variance=bound, stream=stream))
+        api.set_fast_traversal(True)
+        log.ran([kernel] * 2, TWO, ("adaptive", kernel))
+        assert np.array_equal(d_counts, ad.counts) and _bits(d_sums, ad.sums) and _bits(d_sq, ad.sq), kernel
     assert (ad.counts == MIN).any()
     full = ad.counts == SPP
     if depth:
