@@ -7,8 +7,6 @@
 
 namespace {
 constexpr int OCCLUSION_SD = 40;
-// rl_debug_last_query ids of the occlusion queries (1 / 2 are the ray queries', 3 / 4 the feature renders')
-constexpr int LAST_QUERY_OCCLUSION_REFERENCE = 5, LAST_QUERY_OCCLUSION_FAST = 6;
 }  // namespace
 
 // counting: the caller wants the reference's counters (reference-order kernel).  Otherwise the any-hit walk serves the call where the

@@ -87,8 +87,25 @@ int query_check(const void *subject, int kind, uint64_t n, bool buffers_ok, rl_s
   return RL_OK;
 }
 
-// rl_debug_last_query.  Atomic: queries of two scenes run under two locks.
-std::atomic<int> g_last_query_kernel{0};                  // 1 reference order, 2 fast
+// rl_debug_last_query: which kernel served the process's most recent query or pixel render.  Every family's pair, in one place.
+enum LastQuery : int {
+  LAST_QUERY_REFERENCE = 1,  // rl_rtiow_hit_rays*, rl_rtiow_hit_rays_seeded*, rl_rtiow_ray_color_rays*
+  LAST_QUERY_FAST = 2,
+  LAST_QUERY_FEATURES_REFERENCE = 3,  // the feature renders (rl_features_api.h)
+  LAST_QUERY_FEATURES_FAST = 4,
+  LAST_QUERY_OCCLUSION_REFERENCE = 5,  // the occlusion queries (rl_occlusion_api.h)
+  LAST_QUERY_OCCLUSION_FAST = 6,
+  LAST_QUERY_AO_REFERENCE = 7,  // the ambient-occlusion renders (rl_ao_api.h)
+  LAST_QUERY_AO_FAST = 8,
+  LAST_QUERY_DIRECT_REFERENCE = 9,  // the direct-lighting renders (rl_direct_api.h)
+  LAST_QUERY_DIRECT_FAST = 10,
+  LAST_QUERY_NEE_REFERENCE = 11,  // the NEE path renders (rl_nee_api.h)
+  LAST_QUERY_NEE_FAST = 12,
+  LAST_QUERY_NEE_MIS_REFERENCE = 13,  // ... with multiple importance sampling
+  LAST_QUERY_NEE_MIS_FAST = 14,
+};
+// Atomic: queries of two scenes run under two locks.
+std::atomic<int> g_last_query_kernel{0};                  // a LastQuery
 std::atomic<unsigned long long> g_last_query_retraced{0};  // the rays the fast kernel re-traced (synchronous calls)
 
 // One query of `scene` on `stream`: ordered behind the scene's previous work, then what `launch` enqueues (-> RL_*), then the status.
@@ -157,7 +174,7 @@ static int rtiow_hit_rays_impl(const rl_scene *scene, const void *d_rays, uint64
       hipLaunchKernelGGL((rtiow_hit_rays_kernel<QNT, true>), dim3(query_grid(scene, (const void *)rtiow_hit_rays_kernel<QNT, true>, n)), dim3(QNT), 0, stream, P, Q);
     else
       hipLaunchKernelGGL((rtiow_hit_rays_kernel<QNT, false>), dim3(query_grid(scene, (const void *)rtiow_hit_rays_kernel<QNT, false>, n)), dim3(QNT), 0, stream, P, Q);
-    g_last_query_kernel = fast ? 2 : 1;
+    g_last_query_kernel = fast ? LAST_QUERY_FAST : LAST_QUERY_REFERENCE;
     return RL_OK;
   };
   return query_run(scene, stream, sync_st, launch, true);
@@ -182,9 +199,7 @@ int rl_rtiow_hit_rays_device(const rl_scene *scene, const void *d_rays, uint64_t
 
 // which kernel served the most recent rl_rtiow_hit_rays* / rl_rtiow_ray_color_rays* call of this process (1: reference order, 2: fast walk), and how many rays of
 // the most recent SYNCHRONOUS one the fast walk re-traced in the reference's order (asynchronous calls: rl_render_status + rl_debug_slow_traces).
-// The feature renders (rl_rtiow_render_features*, rl_features_api.h) report here too, under ids of their own: 3 reference order, 4 fast walk;
-// so do the occlusion queries (rl_rtiow_occluded_rays*, rl_occlusion_api.h): 5 reference order, 6 any-hit walk; and the ambient-occlusion renders (rl_ao_api.h): 7, 8;
-// the direct-lighting renders (rl_direct_api.h): 9, 10; and the NEE path renders (rl_nee_api.h): 11, 12, with multiple importance sampling 13, 14.
+// The occlusion queries and the pixel renders report here too, under ids of their own: enum LastQuery above.
 int rl_debug_last_query(unsigned long long *out2) {
   if (!out2) return set_err(RL_E_INVALID, "bad argument");
   out2[0] = (unsigned long long)g_last_query_kernel, out2[1] = g_last_query_retraced;
@@ -318,7 +333,7 @@ static int rtiow_ray_color_impl(const rl_scene *scene, const void *d_rays, const
       int rcl = launch_pass();
       if (rcl != RL_OK) return rcl;
     }
-    g_last_query_kernel = fast ? 2 : 1;
+    g_last_query_kernel = fast ? LAST_QUERY_FAST : LAST_QUERY_REFERENCE;
     return RL_OK;
   };
   return query_run(scene, stream, sync_st, passes, true);
@@ -410,7 +425,7 @@ static int rtiow_hit_rays_seeded_impl(const rl_scene *scene, const void *d_rays,
     else
       hipLaunchKernelGGL((rtiow_hit_rays_seeded_kernel<QNT, false>), dim3(query_grid(scene, (const void *)rtiow_hit_rays_seeded_kernel<QNT, false>, n)), dim3(QNT), 0,
                          stream, P, Q);
-    g_last_query_kernel = 1, g_last_query_retraced = 0;  // (no fast walk, nothing re-traced: nothing to read back after the call)
+    g_last_query_kernel = LAST_QUERY_REFERENCE, g_last_query_retraced = 0;  // (no fast walk, nothing re-traced: nothing to read back after the call)
     return RL_OK;
   };
   return query_run(scene, stream, sync_st, launch);

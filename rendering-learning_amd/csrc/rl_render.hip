@@ -1490,6 +1490,7 @@ int rl_rtc_render(const rl_scene *scene, const rl_rtc_camera *cam, uint32_t aa, 
 
 // the batched queries' host layer (22 entry points); last, so that its kernels keep their order of first use
 #include "rl_query_api.h"
+#include "rl_pixel_render_api.h"  // the entry forms and the launch of rl_features_api.h, rl_ao_api.h, rl_direct_api.h, rl_nee_api.h
 #include "rl_features_api.h"
 #include "rl_denoise.h"
 #include "rl_denoise_render.h"

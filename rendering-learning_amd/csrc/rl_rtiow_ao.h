@@ -7,7 +7,7 @@
 //
 // Per sample the kernel joins texts the library already has, so that the host composition of rl_rtiow_camera_rays, rl_rtiow_hit_rays,
 // rl_rtiow_scatter_rays (on a Lambertian) and rl_rtiow_occluded_rays gives the same counts (tests/test_gpu_render_ao.py):
-//   1. the stream start and the camera arithmetic of rtiow_features_kernel (rl_rtiow_features.h): Ring in an LDS column, word 0
+//   1. the stream start and the camera arithmetic of every pixel-render kernel: Ring in an LDS column, word 0
 //   2. the first hit, Interval{1e-10, +inf}
 //        FAST = false  general_trace<STATS, false>
 //        FAST = true   features_fast_trace, the function the feature kernel calls (no further copy of the closest-hit walk)
@@ -21,6 +21,8 @@
 //
 // Scenes with ConstantMedium objects are refused on the host (there is no seeded any-hit), so no trace here draws.
 // No barrier and no wave-wide operation inside a lane's loops: lanes leave their walks, their K loops and their samples at different times.
+// The LDS carve and the counters' way into P.stats are rl_rtiow_pixel_skeleton.h's (pixel_lds, pixel_flush_counters); the other texts this
+// kernel has in common with the feature, direct-lighting and NEE kernels stay written out, with a note where each stands.
 // LDS (dynamic): [16][NT] u64 ChaCha ring; FAST: + [SD][NT] u32 stack, used by the two walks in turn, + P.fg_top FastNodeQ staged once.
 // stats: [0] rays = camera rays + ambient rays, [5] words drawn (get_ray + the K unit vectors), [6] flagged, [7] ambient rays AND camera
 // rays the fast walks handed to general_trace; STATS: [1..4] over both kinds of ray.
@@ -137,14 +139,11 @@ template <int NT, bool STATS, bool FAST, int SD>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_ao_kernel(RtiowParams P, AoQuery Q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
-  unsigned long long *s_rng = (unsigned long long *)smem;                                 // [16][NT]
-  uint32_t *s_stack = (uint32_t *)(smem + (size_t)16 * NT * sizeof(unsigned long long));  // FAST: [SD][NT], both walks in turn
-  uint4 *s_top = (uint4 *)(s_stack + (size_t)NT * SD);                                    // FAST: [fg_top] FastNodeQ
+  unsigned long long *s_rng;
+  uint32_t *s_stack;
+  uint4 *s_top;
+  pixel_lds<NT, FAST, SD>(smem, P, tid, s_rng, s_stack, s_top);
   const DevOp *ops = P.ops;
-  if (FAST && P.fg_top) {
-    for (uint32_t i = (uint32_t)tid; i < P.fg_top * 8u; i += (uint32_t)NT) s_top[i] = ((const uint4 *)P.fg_nodes)[i];
-    __syncthreads();
-  }
   const rl_rtiow_camera &cam = P.cam;
   const uint32_t W = cam.image_width, H = cam.image_height, S = cam.samples_per_pixel, K = Q.ao_rays;
   const uint64_t WH = (uint64_t)W * (uint64_t)H;
@@ -155,6 +154,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_ao_k
   Ring<NT, true, true> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
   unsigned long long c_rays = 0, c_nodes = 0, c_sph = 0, c_pl = 0, c_inst = 0, c_flag = 0, c_words = 0, c_slow = 0;
   for (unsigned long long idx = (unsigned long long)blockIdx.x * NT + tid; idx < Q.n; idx += (unsigned long long)gridDim.x * NT) {
+    // (written out: as pixel_of_slot(), the operands of three v_add_f64 changed places in every instantiation)
     uint32_t px, y;
     if (Q.xs) px = Q.xs[idx], y = Q.ys[idx];
     else px = (uint32_t)(idx % W), y = P.row_first + (uint32_t)(idx / W) * P.row_step;
@@ -162,6 +162,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_ao_k
     const bool inside = px < W && y < H;  // (a list element outside the image, device form: zeros, nothing traced)
 #pragma unroll 1
     for (uint32_t n = 0; inside && n < S; n++) {
+      // (stream start, get_ray and time written out: as one function, 2 - 140 lines of every instantiation changed)
       const uint64_t sample_index = (uint64_t)n + P.first_sample;
       rng.pos = 0u, rng.nres = 0;
       rng.reset_stream(sample_index * WH + (uint64_t)px * (uint64_t)W + (uint64_t)y);
@@ -181,6 +182,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_ao_k
       const D3 wd = pixel_sample - wo;
       const double time = rng.gen_f64();
       // 2. world.hit(&ray, &Interval{1e-10, +inf})
+      // (written out: as one function with general_trace's flags, 1,400 - 15,000 lines of every instantiation changed)
       c_rays++;
       Rec rec;
       if (FAST) {
@@ -204,6 +206,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_ao_k
           const Scatter sc = material_scatter<false>(lambertian, wd, hn, front, [] { return d3(0.0, 0.0, 0.0); }, rng);
           const D3 ad = normalize(sc.dir);
           c_rays++;
+          // (written out: as one function, 500 - 9,700 lines of every instantiation changed)
           bool occluded = false, fold = !FAST;
           if (FAST) {
             const int w = ao_any_hit_walk<NT, SD>(P, ops, s_stack, s_top, tid, hp, ad, time, R);
@@ -226,27 +229,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_ao_k
     if (Q.open_count) Q.open_count[idx] = open;
     if (Q.hit_count) Q.hit_count[idx] = hits;
   }
-  unsigned long long v;
-  v = wave_sum(c_rays);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[0], v);
-  v = wave_sum(c_words);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[5], v);
-  v = wave_sum(c_flag);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
-  if (FAST) {
-    v = wave_sum(c_slow);
-    if ((tid & 63) == 0 && v) atomicAdd(&P.stats[7], v);
-  }
-  if (STATS) {
-    v = wave_sum(c_nodes);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[1], v);
-    v = wave_sum(c_sph);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
-    v = wave_sum(c_pl);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[3], v);
-    v = wave_sum(c_inst);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[4], v);
-  }
+  pixel_flush_counters<STATS, FAST>(P.stats, tid, c_rays, c_words, c_flag, c_slow, c_nodes, c_sph, c_pl, c_inst);
 }
 
 }  // namespace rl

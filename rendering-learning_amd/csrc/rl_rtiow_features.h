@@ -17,11 +17,14 @@
 // it stays the code object it was.  What the copy leaves out is the finite-tmax tie test (tmax is +inf here).  A change to one walk belongs in the other; the tests hold the two against each other through the host composition.
 //
 // The kernel takes its own parameter struct beside RtiowParams, as the ray queries take RayQuery: RtiowParams does not grow.
+// The LDS carve and the counters' way into P.stats are rl_rtiow_pixel_skeleton.h's (pixel_lds, pixel_flush_counters), shared with the AO,
+// direct-lighting and NEE kernels; the other texts those kernels repeat stay written out, with a note where each stands.
 // LDS (dynamic): [16][NT] u64 ChaCha ring; FAST: + [SD][NT] u32 stack + P.fg_top FastNodeQ.
 // stats: [0] rays = samples traced, [5] words drawn (get_ray + media), [6] flagged, [7] rays the fast walk re-traced; STATS: [1..4].
 #pragma once
 #include "rl_material_query.h"
 #include "rl_ray_query.h"
+#include "rl_rtiow_pixel_skeleton.h"
 
 namespace rl {
 
@@ -176,14 +179,11 @@ template <int NT, bool STATS, bool FAST, int SD>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_features_kernel(RtiowParams P, FeaturesQuery Q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
-  unsigned long long *s_rng = (unsigned long long *)smem;                               // [16][NT]
-  uint32_t *s_stack = (uint32_t *)(smem + (size_t)16 * NT * sizeof(unsigned long long));  // FAST: [SD][NT]
-  uint4 *s_top = (uint4 *)(s_stack + (size_t)NT * SD);                                  // FAST: [fg_top] FastNodeQ
+  unsigned long long *s_rng;
+  uint32_t *s_stack;
+  uint4 *s_top;
+  pixel_lds<NT, FAST, SD>(smem, P, tid, s_rng, s_stack, s_top);
   const DevOp *ops = P.ops;
-  if (FAST && P.fg_top) {
-    for (uint32_t i = (uint32_t)tid; i < P.fg_top * 8u; i += (uint32_t)NT) s_top[i] = ((const uint4 *)P.fg_nodes)[i];
-    __syncthreads();
-  }
   const rl_rtiow_camera &cam = P.cam;
   const uint32_t W = cam.image_width, H = cam.image_height, S = cam.samples_per_pixel;
   const uint64_t WH = (uint64_t)W * (uint64_t)H;
@@ -192,6 +192,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_feat
   Ring<NT, true, true> rng{P.key, s_rng, tid, 0ull, 0u, 0u, 0u};
   unsigned long long c_rays = 0, c_nodes = 0, c_sph = 0, c_pl = 0, c_inst = 0, c_flag = 0, c_words = 0, c_slow = 0;
   for (unsigned long long idx = (unsigned long long)blockIdx.x * NT + tid; idx < Q.n; idx += (unsigned long long)gridDim.x * NT) {
+    // (written out: as pixel_of_slot(), the operands of three v_add_f64 changed places in every instantiation)
     uint32_t px, y;
     if (Q.xs) px = Q.xs[idx], y = Q.ys[idx];
     else px = (uint32_t)(idx % W), y = P.row_first + (uint32_t)(idx / W) * P.row_step;
@@ -201,6 +202,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_feat
     const bool inside = px < W && y < H;  // (a list element outside the image, device form: zeros, nothing traced)
 #pragma unroll 1
     for (uint32_t n = 0; inside && n < S; n++) {
+      // (stream start, get_ray and time written out: as one function, 2 - 140 lines of every instantiation changed)
       const uint64_t sample_index = (uint64_t)n + P.first_sample;
       rng.pos = 0u, rng.nres = 0;
       rng.reset_stream(sample_index * WH + (uint64_t)px * (uint64_t)W + (uint64_t)y);
@@ -220,6 +222,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_feat
       const D3 wd = pixel_sample - wo;
       const double time = rng.gen_f64();
       // 2. world.hit(&ray, &Interval{1e-10, +inf})
+      // (written out: as one function with general_trace's flags, 1,400 - 15,000 lines of every instantiation changed)
       c_rays++;
       Rec rec;
       if (FAST) {
@@ -261,27 +264,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? 2 * NT : NT) rtiow_feat
     if (Q.depth_sum) Q.depth_sum[idx] = depth;
     if (Q.hit_count) Q.hit_count[idx] = hits;
   }
-  unsigned long long v;
-  v = wave_sum(c_rays);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[0], v);
-  v = wave_sum(c_words);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[5], v);
-  v = wave_sum(c_flag);
-  if ((tid & 63) == 0 && v) atomicAdd(&P.stats[6], v);
-  if (FAST) {
-    v = wave_sum(c_slow);
-    if ((tid & 63) == 0 && v) atomicAdd(&P.stats[7], v);
-  }
-  if (STATS) {
-    v = wave_sum(c_nodes);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[1], v);
-    v = wave_sum(c_sph);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[2], v);
-    v = wave_sum(c_pl);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[3], v);
-    v = wave_sum(c_inst);
-    if ((tid & 63) == 0) atomicAdd(&P.stats[4], v);
-  }
+  pixel_flush_counters<STATS, FAST>(P.stats, tid, c_rays, c_words, c_flag, c_slow, c_nodes, c_sph, c_pl, c_inst);
 }
 
 }  // namespace rl

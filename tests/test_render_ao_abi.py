@@ -40,6 +40,30 @@ def _forms(lib, cam, n_pix=24):
     }
 
 
+def _with_a_later_defect(lib, stem, cam):
+    """Every entry point of the family as f(*particular) -> rc, each time with ONE rule that comes later in its check sequence broken as
+    well: no scene, no camera, row_step == 0, an image without pixels, row_first past the last row; a NULL list, the empty list, a list
+    beyond the work counter.  -> {(form, defect): f}, and what the calls point into (to be kept alive)."""
+    rows, dev = getattr(lib, "rl_rtiow_render_%s_rows" % stem), getattr(lib, "rl_rtiow_render_%s_device" % stem)
+    pix, pixdev = getattr(lib, "rl_rtiow_render_pixels_%s" % stem), getattr(lib, "rl_rtiow_render_pixels_%s_device" % stem)
+    xs, ys = np.arange(4, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    empty = type(cam.c).from_buffer_copy(cam.c)
+    empty.image_width = 0
+    c, e, X, Y = C.byref(cam.c), C.byref(empty), xs.ctypes.data, ys.ctypes.data
+    row_heads = {"scene": (None, c, 0, 0, 1), "camera": (None, None, 0, 0, 1), "row_step": (None, c, 0, 0, 0), "empty image": (None, e, 0, 0, 1),
+                 "row_first": (None, c, 0, cam.c.image_height, 1)}
+    list_heads = {"scene": (None, c, 0, X, Y, 4), "camera": (None, None, 0, X, Y, 4), "xs": (None, c, 0, None, Y, 4), "ys": (None, c, 0, X, None, 4),
+                  "empty list": (None, c, 0, None, None, 0), "empty image": (None, e, 0, X, Y, 4), "length": (None, c, 0, X, Y, 0xFFFF0000)}
+    calls = {}
+    for what, head in row_heads.items():
+        calls["rows", what] = lambda *p, head=head: rows(*head, *p, None)
+        calls["device", what] = lambda *p, head=head: dev(*head, *p, None, None)
+    for what, head in list_heads.items():
+        calls["pixels", what] = lambda *p, head=head: pix(*head, *p, None)
+        calls["pixels_device", what] = lambda *p, head=head: pixdev(*head, *p, None, None)
+    return calls, (xs, ys, empty)
+
+
 def test_ao_entry_points_are_exported_declared_and_listed(rl):
     lib = rl.api.render_lib()
     header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rl_render.h")).read(), flags=re.S)
@@ -81,6 +105,34 @@ def test_what_is_particular_to_the_calls_is_refused_before_a_device_is_looked_at
                 for r, po, ph in ((INF, o, h), (1e-300, o, h), (2.0, o, None), (2.0, None, h)):
                     assert f(k, r, po, ph) == api.RL_E_NO_DEVICE, (name, k, r)
         assert (op == 7).all() and (hits == 9).all()
+
+
+def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl):
+    """The order of each entry point's check sequence as far as a machine without a GPU shows it: what is particular to the family is
+    refused first ("bad argument") whatever else is wrong with the call (no scene, no camera, row_step == 0, an empty image, row_first
+    past the last row, a NULL, empty or too long list), and a call that is legal in that respect looks for the device before any of those."""
+    api = rl.api
+    lib = api.render_lib()
+    cam = _camera(rl)
+    op, hits = np.full(24, 7, dtype=np.uint32), np.full(24, 9, dtype=np.uint32)
+    o, h = op.ctypes.data, hits.ctypes.data
+    refused = [(0, 1.0, o, h), (4, NAN, o, h), (4, 1.0, None, None)]
+    legal = [(4, 1.0, o, h), (1, INF, None, h)]
+    untouched = lambda: (op == 7).all() and (hits == 9).all()
+    calls, keep = _with_a_later_defect(lib, "ao", cam)
+    assert len(calls) == 2 * 5 + 2 * 7
+    for key, f in calls.items():
+        for p in refused:
+            assert f(*p) == api.RL_E_INVALID, (key, p)
+            assert b"bad argument" in lib.rl_last_error(), (key, p, lib.rl_last_error())
+    assert untouched()
+    if not _gpu_present():
+        assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
+        for key, f in calls.items():
+            for p in legal:
+                assert f(*p) == api.RL_E_NO_DEVICE, (key, p)
+                assert b"rl_init has not succeeded" in lib.rl_last_error(), (key, p, lib.rl_last_error())
+        assert untouched()
 
 
 def test_want_and_merge_are_checked_in_python(rl, monkeypatch):

@@ -43,6 +43,30 @@ def _forms(lib, cam, scene=None):
     }
 
 
+def _with_a_later_defect(lib, stem, cam):
+    """Every entry point of the family as f(*particular) -> rc, each time with ONE rule that comes later in its check sequence broken as
+    well: no scene, no camera, row_step == 0, an image without pixels, row_first past the last row; a NULL list, the empty list, a list
+    beyond the work counter.  -> {(form, defect): f}, and what the calls point into (to be kept alive)."""
+    rows, dev = getattr(lib, "rl_rtiow_render_%s_rows" % stem), getattr(lib, "rl_rtiow_render_%s_device" % stem)
+    pix, pixdev = getattr(lib, "rl_rtiow_render_pixels_%s" % stem), getattr(lib, "rl_rtiow_render_pixels_%s_device" % stem)
+    xs, ys = np.arange(4, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
+    empty = type(cam.c).from_buffer_copy(cam.c)
+    empty.image_width = 0
+    c, e, X, Y = C.byref(cam.c), C.byref(empty), xs.ctypes.data, ys.ctypes.data
+    row_heads = {"scene": (None, c, 0, 0, 1), "camera": (None, None, 0, 0, 1), "row_step": (None, c, 0, 0, 0), "empty image": (None, e, 0, 0, 1),
+                 "row_first": (None, c, 0, cam.c.image_height, 1)}
+    list_heads = {"scene": (None, c, 0, X, Y, 4), "camera": (None, None, 0, X, Y, 4), "xs": (None, c, 0, None, Y, 4), "ys": (None, c, 0, X, None, 4),
+                  "empty list": (None, c, 0, None, None, 0), "empty image": (None, e, 0, X, Y, 4), "length": (None, c, 0, X, Y, 0xFFFF0000)}
+    calls = {}
+    for what, head in row_heads.items():
+        calls["rows", what] = lambda *p, head=head: rows(*head, *p, None)
+        calls["device", what] = lambda *p, head=head: dev(*head, *p, None, None)
+    for what, head in list_heads.items():
+        calls["pixels", what] = lambda *p, head=head: pix(*head, *p, None)
+        calls["pixels_device", what] = lambda *p, head=head: pixdev(*head, *p, None, None)
+    return calls, (xs, ys, empty)
+
+
 def test_nee_entry_points_are_exported_declared_and_listed(rl):
     lib = rl.api.render_lib()
     text = open(os.path.join(ROOT, "include", "rl_render.h")).read()
@@ -119,6 +143,36 @@ def test_what_is_particular_to_the_calls_is_refused_before_a_device_is_looked_at
             for name, f in _forms(lib, cm).items():
                 assert f(L, li.ctypes.data, k, t, ps, pq) == api.RL_E_NO_DEVICE, (name, L, k, t)
         assert (sums == 7.0).all() and (sq == 8.0).all()
+
+
+def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl):
+    """The order of each entry point's check sequence as far as a machine without a GPU shows it: what is particular to the family is
+    refused first ("bad argument") whatever else is wrong with the call (no scene, no camera, row_step == 0, an empty image, row_first
+    past the last row, a NULL, empty or too long list), and a call that is legal in that respect looks for the device before any of those."""
+    api = rl.api
+    lib = api.render_lib()
+    cam = _camera(rl)
+    sums, sq = np.full((24, 3), 7.0), np.full((24, 3), 8.0)
+    s, q = sums.ctypes.data, sq.ctypes.data
+    one = np.array([GOOD], dtype=np.float64)
+    li = one.ctypes.data
+    refused = [(0, li, 1, 0.5, s, q), (1, None, 1, 0.5, s, q), (1, li, 0, 0.5, s, q), (1, li, 1, NAN, s, q), (1, li, 1, 0.5, None, None)]
+    legal = [(1, li, 1, 0.5, s, q), (1, li, 3, 1.0, None, q)]
+    untouched = lambda: (sums == 7.0).all() and (sq == 8.0).all()
+    calls, keep = _with_a_later_defect(lib, "nee", cam)
+    assert len(calls) == 2 * 5 + 2 * 7
+    for key, f in calls.items():
+        for p in refused:
+            assert f(*p) == api.RL_E_INVALID, (key, p)
+            assert b"bad argument" in lib.rl_last_error(), (key, p, lib.rl_last_error())
+    assert untouched()
+    if not _gpu_present():
+        assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
+        for key, f in calls.items():
+            for p in legal:
+                assert f(*p) == api.RL_E_NO_DEVICE, (key, p)
+                assert b"rl_init has not succeeded" in lib.rl_last_error(), (key, p, lib.rl_last_error())
+        assert untouched()
 
 
 def test_want_and_path_nee_are_checked_in_python(rl, monkeypatch):
