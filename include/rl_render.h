@@ -872,8 +872,8 @@ int rl_rtiow_render_pixels_nee_device(const rl_scene *, const rl_rtiow_camera *,
  * rl_rtiow_render_nee* exactly.
  * Errors.  The NEE path renders' rules, or heuristic > RL_MIS_POWER: RL_E_INVALID, before a device is looked at, outputs untouched; then
  * as there.
- * Not offered: sphere and textured lights, media scenes, Isotropic vertices (no light sampling, as there), Russian roulette, adaptive
- * stopping, multi-GPU forms, rgb8 output, the RTC family. */
+ * Not offered: textured lights, media scenes, Isotropic vertices (no light sampling, as there), Russian roulette, adaptive
+ * stopping, multi-GPU forms, rgb8 output, the RTC family.  (Sphere lights: the next block.) */
 #define RL_MIS_BALANCE 0u
 #define RL_MIS_POWER 1u
 int rl_rtiow_render_nee_mis_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first, uint32_t row_step,
@@ -889,6 +889,65 @@ int rl_rtiow_render_pixels_nee_mis_device(const rl_scene *, const rl_rtiow_camer
                                           const void *d_ys, uint64_t n, uint32_t n_lights, const double *lights, uint32_t light_samples,
                                           double seg_tmax, uint32_t heuristic, void *d_out_sums, void *d_out_sq, void *hip_stream,
                                           rl_stats *opt_stats);
+
+/* =====================================================================
+ *  NEE path renders with sphere lights: a second light shape for the renders with multiple importance sampling
+ * =====================================================================
+ * The renders with multiple importance sampling above with a second light array behind `lights`:
+ *    n_sphere_lights, sphere_lights [Ls][7] = C[3], r, E[3]
+ * A sphere light is stationary, has its centre at C and radius r > 0, and emits E OUTWARD ONLY.  It is sampled uniformly by area with
+ * rand_distr's UnitSphere (Marsaglia's draw, the one Lambertian::scatter takes from the same stream: two Uniform(-1, 1) per try, tries
+ * until x1^2 + x2^2 < 1, one sqrt).  On the host, once per light: A = (4.0 * M_PI) * (r * r).  With cl carrying A the way a quad's
+ * |nl . d| carries |u x v|, q = g * kf is again exactly p_bsdf / (K p_light): no sqrt in the weights.
+ * Everything is the MIS definition's except what is named here.  With its names (x = hit.p, n = hit.normal, w = scattered.direction):
+ *   Step 3, the light strategy.  Behind the L quads (unchanged), for each sphere light j in 0..Ls, K times:
+ *        wu = UnitSphere.sample(rng)                            -- rng.unit_sphere(): 4 words per try, drawn whether or not the point counts
+ *        yl = C + wu * r;  d = yl - x;  d2 = d.dot(d);  cs = n.dot(d);  co = -(wu.dot(d));  cl = co * A
+ *        if !(cs > 0) or !(co > 0) or !(d2 > 0):  continue       -- not traced
+ *        g = (cs * cl) / (d2 * d2);                  if !(g < +inf):  continue
+ *        q, wl, the segment test and dsum as there.
+ *   Step 4, the scattered-ray strategy.  Behind the quads' candidates, one candidate per sphere light, no draw:
+ *        oc = x - C;  a = w.dot(w);  hb = oc.dot(w);  cc = oc.dot(oc) - r * r;  disc = hb * hb - a * cc      -- Sphere::hit's order
+ *        if !(disc > 0):  continue
+ *        sd = sqrt(disc);  t = (-hb - sd) / a                    -- the near root only
+ *        if !(t > 0) or !(t < +inf):  continue
+ *        d = w * t;  y = x + d;  wn = (y - C) / r;  co = -(wn.dot(d));  cl = co * A             -- three divisions by r
+ *        d2, cs, the same skip, g, q and wb; the same segment test, counted in `rays`; a free segment adds E * wb to bsum.
+ * Every line is one rounded binary64 + - x /, or sqrt where named; the negations are exact.
+ * What follows from the definition:
+ *  - Both strategies estimate the OUTWARD emission of the listed sphere through the segment test, and wl / g + wb = 1 at a crossing: the
+ *    expectation is ray_color's at the same max_depth where `lights` and `sphere_lights` together list every DiffuseLight surface (the
+ *    reference's simple_light with its quad and its sphere listed), for sphere lights that are geometry of the scene or not.
+ *  - Points on the far side of a sphere have co <= 0: they cost their draws but no trace (about half of them, seen from far away).
+ *  - A vertex INSIDE a listed sphere gets nothing from it by either strategy (every point faces away; the near root is behind the
+ *    vertex).  The reference's DiffuseLight emits from both sides of its surface, so for that one configuration the expectation differs.
+ *  - wl * kf <= 1 and wb <= 1: the MIS renders' cap holds with L + Ls in L's place, no sample exceeds
+ *    max(background) + Emax * (1 + (max_depth - 1) * (L + Ls) * (K + 1)) for textures and albedos <= 1.
+ *  - rng_words has no closed form any more: the tries of a sphere point vary.  rays = path rays + every segment traced.
+ * Arguments.  n_lights may be 0; 1 <= n_lights + n_sphere_lights <= RL_DIRECT_MAX_LIGHTS (the two kinds share the slots).
+ * With n_sphere_lights == 0 a call IS the MIS call of the same form: the same kernels, bytes and counters.
+ * Errors.  RL_E_INVALID before a device is looked at, outputs untouched: a total of 0 or above RL_DIRECT_MAX_LIGHTS, a null array with a
+ * nonzero count, a component that is not finite, !(r > 0), A not finite, S * (L + Ls) * K >= 2^32, and the MIS renders' rules; then as
+ * there (RL_E_NO_DEVICE, the renders' rules, RL_E_UNSUPPORTED on media scenes).
+ * Not offered: sphere lights for the direct-lighting and the plain NEE renders (uniform area sampling without weights has their tail),
+ * visible-cap or cone sampling, moving centres, textured lights, two-sided spheres, media scenes, and what the MIS renders do not offer. */
+int rl_rtiow_render_nee_mis_spheres_rows(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first,
+                                         uint32_t row_step, uint32_t n_lights, const double *lights, uint32_t n_sphere_lights,
+                                         const double *sphere_lights, uint32_t light_samples, double seg_tmax, uint32_t heuristic,
+                                         double *out_sums, double *out_sq, rl_stats *opt_stats);
+int rl_rtiow_render_nee_mis_spheres_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, uint32_t row_first,
+                                           uint32_t row_step, uint32_t n_lights, const double *lights, uint32_t n_sphere_lights,
+                                           const double *sphere_lights, uint32_t light_samples, double seg_tmax, uint32_t heuristic,
+                                           void *d_out_sums, void *d_out_sq, void *hip_stream, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_nee_mis_spheres(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const uint32_t *xs,
+                                           const uint32_t *ys, uint64_t n, uint32_t n_lights, const double *lights, uint32_t n_sphere_lights,
+                                           const double *sphere_lights, uint32_t light_samples, double seg_tmax, uint32_t heuristic,
+                                           double *out_sums, double *out_sq, rl_stats *opt_stats);
+int rl_rtiow_render_pixels_nee_mis_spheres_device(const rl_scene *, const rl_rtiow_camera *, uint64_t first_sample, const void *d_xs,
+                                                  const void *d_ys, uint64_t n, uint32_t n_lights, const double *lights,
+                                                  uint32_t n_sphere_lights, const double *sphere_lights, uint32_t light_samples,
+                                                  double seg_tmax, uint32_t heuristic, void *d_out_sums, void *d_out_sq, void *hip_stream,
+                                                  rl_stats *opt_stats);
 
 /* =====================================================================
  *  Denoising: an edge-avoiding a-trous filter for noisy and adaptive renders

@@ -17,3 +17,4 @@ from .direct import DirectLight, pack_lights, render_direct, render_direct_devic
 from . import nee  # noqa: F401
 from .nee import PathNEE, render_nee, render_nee_device, render_pixels_nee, render_pixels_nee_device  # noqa: F401
 from .nee import render_nee_mis, render_nee_mis_device, render_pixels_nee_mis, render_pixels_nee_mis_device  # noqa: F401
+from .nee import pack_sphere_lights  # noqa: F401

@@ -277,6 +277,10 @@ RENDER_SIGNATURES = {
     "rl_rtiow_render_nee_mis_device": (_I, [_P, _CAM, _U64, _U32, _U32, _U32, _P, _U32, _D, _U32, _P, _P, _P, _STATS]),
     "rl_rtiow_render_pixels_nee_mis": (_I, [_P, _CAM, _U64, _P, _P, _U64, _U32, _P, _U32, _D, _U32, _P, _P, _STATS]),
     "rl_rtiow_render_pixels_nee_mis_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _U32, _P, _U32, _D, _U32, _P, _P, _P, _STATS]),
+    "rl_rtiow_render_nee_mis_spheres_rows": (_I, [_P, _CAM, _U64, _U32, _U32, _U32, _P, _U32, _P, _U32, _D, _U32, _P, _P, _STATS]),
+    "rl_rtiow_render_nee_mis_spheres_device": (_I, [_P, _CAM, _U64, _U32, _U32, _U32, _P, _U32, _P, _U32, _D, _U32, _P, _P, _P, _STATS]),
+    "rl_rtiow_render_pixels_nee_mis_spheres": (_I, [_P, _CAM, _U64, _P, _P, _U64, _U32, _P, _U32, _P, _U32, _D, _U32, _P, _P, _STATS]),
+    "rl_rtiow_render_pixels_nee_mis_spheres_device": (_I, [_P, _CAM, _U64, _P, _P, _U64, _U32, _P, _U32, _P, _U32, _D, _U32, _P, _P, _P, _STATS]),
     "rl_denoise_atrous_pass_device": (_I, [_U32, _U32, _U32, _ATROUS, _P, _P, _P, _P, _P, _P]),
     "rl_denoise_atrous": (_I, [_U32, _U32, _U32, _ATROUS, _P, _P, _P, _P, _P]),
     "rl_denoise_prepare_device": (_I, [_U32, _U32, _DENOISE_IN, _P, _P, _P, _P]),
@@ -381,6 +385,7 @@ HOST_SIGNATURES = {  # the rlh_* entry points this file calls; test-only probes 
     "rlh_direct_probe": (_I, [_U64, _U64, _U64, _U32, _P, _U32, _D, _P, _P, _P]),  # (direct.py's cpp_mirror_probe)
     "rlh_nee_probe": (_I, [_U64, _U64, _U64, _U32, _P, _U32, _D, _P, _P]),  # (nee.py's cpp_mirror_probe)
     "rlh_nee_mis_probe": (_I, [_U64, _U64, _U64, _U32, _P, _U32, _D, _U32, _P, _P]),  # (nee.py's cpp_mirror_probe_mis)
+    "rlh_nee_spheres_probe": (_I, [_U64, _U64, _U64, _U32, _P, _U32, _P, _U32, _D, _U32, _P, _P]),  # (nee.py's cpp_mirror_probe_spheres)
 }
 
 
@@ -653,7 +658,7 @@ def last_query():
     _check(render_lib().rl_debug_last_query(out))
     names = {1: "reference", 2: "fast", 3: "features_reference", 4: "features_fast", 5: "occlusion_reference", 6: "occlusion_fast",
              7: "ao_reference", 8: "ao_fast", 9: "direct_reference", 10: "direct_fast",
-             11: "nee_reference", 12: "nee_fast", 13: "nee_mis_reference", 14: "nee_mis_fast"}
+             11: "nee_reference", 12: "nee_fast", 13: "nee_mis_reference", 14: "nee_mis_fast", 15: "nee_spheres_reference", 16: "nee_spheres_fast"}
     return {"kernel": names.get(int(out[0]), "none"), "retraced": int(out[1])}
 
 

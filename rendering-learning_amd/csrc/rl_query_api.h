@@ -103,6 +103,8 @@ enum LastQuery : int {
   LAST_QUERY_NEE_FAST = 12,
   LAST_QUERY_NEE_MIS_REFERENCE = 13,  // ... with multiple importance sampling
   LAST_QUERY_NEE_MIS_FAST = 14,
+  LAST_QUERY_NEE_SPHERES_REFERENCE = 15,  // ... and sphere lights (at least one)
+  LAST_QUERY_NEE_SPHERES_FAST = 16,
 };
 // Atomic: queries of two scenes run under two locks.
 std::atomic<int> g_last_query_kernel{0};                  // a LastQuery

@@ -2,13 +2,19 @@
 // the sum and the sum of squares of a path estimate of max_depth vertices that connects every Lambertian vertex but the last to K points
 // drawn on each of L quad lights and, in exchange, does not count the emission the scattered ray of such a vertex finds.
 //
-//   rtiow_nee_kernel<NT, STATS, FAST, SD, MIS>   one pixel per lane, grid-stride over the frame's or the list's slots; per lane a loop over
+//   rtiow_nee_kernel<NT, STATS, FAST, SD, MIS, SPH>   one pixel per lane, grid-stride over the frame's or the list's slots; per lane a loop over
 //                                                the samples F .. F + S - 1, inside it over the path's vertices and, at a vertex that
 //                                                samples the lights, over the L lights and their K points.
 // MIS = true is the flavour of the renders with multiple importance sampling (include/rl_render.h "NEE path renders with multiple importance
 // sampling", rl_rtiow_render_nee_mis*): every light point's g becomes wl, and the scattered ray of a vertex that sampled
 // the lights is intersected with each light's parallelogram and, where it crosses one, connected with wb.  The heuristic is a runtime
 // scalar of the launch (NeeMisQuery::heuristic).
+// SPH = true (with MIS) is the flavour of the renders with sphere lights (include/rl_render.h "NEE path renders with sphere lights",
+// rl_rtiow_render_nee_mis_spheres*): behind the L quads the light loop runs over Ls sphere lights, whose points are drawn
+// with rng.unit_sphere() (pass 0) and whose near root the scattered ray is tested for (pass 1).  The light kind picks only how the
+// candidate (sd, co) is made; d2, cs, g, the weight, the walk, the fold and the sum are the MIS flavour's one statement, under
+// `if constexpr (SPH)` inside its body: the three MIS instantiations came out as the parent's, instruction for instruction, except with
+// the skip stated once over a flag (two compares and their s_and_b64 changed places), hence the skip's two statements.
 //
 // Per vertex the kernel joins texts the library already has, so that the host composition of rl_rtiow_camera_rays, rl_rtiow_hit_rays, the
 // definition's arithmetic, rl_rtiow_occluded_rays and rl_rtiow_scatter_rays gives the same bytes (tests/test_gpu_render_nee.py):
@@ -60,18 +66,29 @@ struct NeeQuery {
 struct NeeMisQuery : NeeQuery {
   uint32_t heuristic;  // RL_MIS_BALANCE or RL_MIS_POWER (wave-uniform: a scalar load and a scalar branch)
 };
-template <bool MIS>
-using NeeQueryOf = typename std::conditional<MIS, NeeMisQuery, NeeQuery>::type;
-static_assert(sizeof(RtiowParams) + sizeof(NeeMisQuery) <= 4096, "the two by-value kernel arguments must fit the 4 KiB kernarg segment");
+// The sphere-light flavour's argument: the number of sphere lights, again in a type of its own.  The two kinds share the RL_DIRECT_MAX_LIGHTS
+// slots: lights[0 .. n_lights) are the quads, lights[n_lights .. n_lights + n_sphere_lights) the spheres, a sphere in a slot as
+//   Q = C, E = E, u[0] = r, u[1] = A = (4.0 * M_PI) * (r * r), the host's double (sphere_r, sphere_A below); v and nl are not read.
+struct NeeSpheresQuery : NeeMisQuery {
+  uint32_t n_sphere_lights;  // Ls; L + Ls in 1 .. RL_DIRECT_MAX_LIGHTS, L may be 0
+};
+__host__ __device__ inline double &sphere_r(DirectLight &l) { return l.u[0]; }
+__host__ __device__ inline double &sphere_A(DirectLight &l) { return l.u[1]; }
+template <bool MIS, bool SPH = false>
+using NeeQueryOf = typename std::conditional<SPH, NeeSpheresQuery, typename std::conditional<MIS, NeeMisQuery, NeeQuery>::type>::type;
+static_assert(sizeof(RtiowParams) + sizeof(NeeSpheresQuery) <= 4096, "the two by-value kernel arguments must fit the 4 KiB kernarg segment");
 
 // P: the scene's tables (hit_query_params + materials, textures, images, Perlin), cam, key, first_sample, row_first / row_step, stats;
 // FAST: also the query tree (fg_*, fg_top).
 // Register budget (DESIGN.md §3.22 has the table): compiled for two workgroups per SIMD row as rtiow_direct_kernel is, FAST takes all 256
 // VGPRs and spills 68 more to 276 bytes of scratch, so it is compiled for ONE (NEE_FAST_WG = 1) and spills nothing.  The MIS flavour at one
 // (DESIGN.md §3.23): FAST 338 VGPRs + 82 AGPRs, counting 324 + 68, counter-free reference order 308 + 52; no VGPR spilled, no scratch.
+// The sphere-light flavour at one: FAST 344 + 88, counting 328 + 72, counter-free reference order 312 + 56; again no VGPR
+// spilled and no scratch.
 constexpr int NEE_FAST_WG = 1;
-template <int NT, bool STATS, bool FAST, int SD, bool MIS>
-__global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) rtiow_nee_kernel(RtiowParams P, NeeQueryOf<MIS> Q) {
+template <int NT, bool STATS, bool FAST, int SD, bool MIS, bool SPH = false>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) rtiow_nee_kernel(RtiowParams P, NeeQueryOf<MIS, SPH> Q) {
+  static_assert(MIS || !SPH, "sphere lights are a flavour of the renders with multiple importance sampling");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   unsigned long long *s_rng;
@@ -216,13 +233,41 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) 
               if (!sampled) break;
             }
             D3 dsum = d3(0.0, 0.0, 0.0);
+            uint32_t LT = L;  // SPH: the Ls sphere lights follow the L quads in Q.lights
+            if constexpr (SPH) LT = L + Q.n_sphere_lights;
 #pragma unroll 1
-            for (uint32_t l = 0; l < L; l++) {
+            for (uint32_t l = 0; l < LT; l++) {
               const DirectLight &lt = Q.lights[l];
 #pragma unroll 1
               for (uint32_t k = 0; k < (pass ? 1u : K); k++) {
                 D3 sd;
-                if (!pass) {
+                // SPH, a sphere light: only how the candidate (sd, co) is made differs; co * A stands where a quad has |nl . sd|
+                bool sph = false;
+                double co = 0.0;
+                if constexpr (SPH) sph = l >= L;
+                if (SPH && sph) {
+                  const D3 C = ld3(lt.Q);
+                  const double r = lt.u[0];
+                  if (!pass) {  // UnitSphere.sample(rng): 4 words per try, drawn whether or not the point counts
+                    const D3 w = rng.unit_sphere();
+                    const D3 yl = C + w * r;
+                    sd = yl - hp;
+                    co = -dot(w, sd);
+                  } else {  // Sphere::hit's order (sphere.rs:36-49), the near root only: a vertex inside the sphere gets nothing
+                    const D3 oc = hp - C;
+                    const double a = len2(wd);
+                    const double hb = dot(oc, wd);
+                    const double cc = len2(oc) - r * r;
+                    const double disc = hb * hb - a * cc;
+                    if (!(disc > 0.0)) continue;  // beside the sphere, or grazing it
+                    const double t = (-hb - sqrt(disc)) / a;
+                    if (!(t > 0.0) || !(t < INF)) continue;  // the sphere is behind the vertex, or the vertex is inside it
+                    sd = wd * t;
+                    const D3 yc = (hp + sd) - C;
+                    const D3 wn = d3(yc.x / r, yc.y / r, yc.z / r);
+                    co = -dot(wn, sd);
+                  }
+                } else if (!pass) {
                   const double a = rng.gen_f64();
                   const double b = rng.gen_f64();
                   const D3 yl = (ld3(lt.Q) + ld3(lt.u) * a) + ld3(lt.v) * b;
@@ -242,8 +287,11 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(FAST ? NEE_FAST_WG * NT : NT) 
                 }
                 const double d2 = len2(sd);
                 const double cs = dot(hn, sd);
-                const double cl = fabs(dot(ld3(lt.nl), sd));
-                if (!(cs > 0.0) || !(cl > 0.0) || !(d2 > 0.0)) continue;  // faces away, edge-on or degenerate: nothing traced
+                const double cl = (SPH && sph) ? co * lt.u[1] : fabs(dot(ld3(lt.nl), sd));
+                // (the skip twice: with one statement over a flag, the MIS instantiations ordered these compares otherwise)
+                if constexpr (SPH) {  // a quad emits from both sides, a sphere outward only: its far side costs draws but no trace
+                  if (!(cs > 0.0) || !(sph ? co > 0.0 : cl > 0.0) || !(d2 > 0.0)) continue;
+                } else if (!(cs > 0.0) || !(cl > 0.0) || !(d2 > 0.0)) continue;  // faces away, edge-on or degenerate: nothing traced
                 const double g = (cs * cl) / (d2 * d2);
                 if (!(g < INF)) continue;
                 // q = p_bsdf / (K p_light) exactly; wl = g / (1 + q^b), wb = q^b / (1 + q^b), b = 1 (balance) or 2 (power)

@@ -713,6 +713,34 @@ static int nee_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32
     return -1;
   }
 }
+// rtiow::render_nee_mis with sphere lights through the C++ mirror, on simple_light (examples/simple_light.rs: Perlin textures, a quad and a
+// sphere light) at image_width = width, samples_per_pixel = spp, max_depth 6: lights [n_lights][12] and sphere_lights [n_sphere_lights][7]
+// (C, r, E).  sums and sq = W * H * 3 doubles.  0 or -1 (rlh_last_error).
+int rlh_nee_spheres_probe(uint64_t width, uint64_t spp, uint64_t first_sample, uint32_t n_lights, const double *lights, uint32_t n_sphere_lights,
+                          const double *sphere_lights, uint32_t light_samples, double seg_tmax, uint32_t heuristic, double *sums, double *sq) {
+  try {
+    scenes::RtiowScene s = scenes::perlin_scene(true);
+    s.params.image_width = (size_t)width, s.params.samples_per_pixel = (size_t)spp, s.params.max_depth = 6;
+    rtiow::Camera cam(s.params);
+    std::vector<rtiow::Camera::QuadLight> ql;
+    for (uint32_t l = 0; lights && l < n_lights; l++) {
+      const double *p = lights + (size_t)l * 12;
+      ql.push_back({rtiow::Vec3(p[0], p[1], p[2]), rtiow::Vec3(p[3], p[4], p[5]), rtiow::Vec3(p[6], p[7], p[8]), rtiow::Vec3(p[9], p[10], p[11])});
+    }
+    std::vector<rtiow::Camera::SphereLight> sl;
+    for (uint32_t j = 0; sphere_lights && j < n_sphere_lights; j++) {
+      const double *p = sphere_lights + (size_t)j * 7;
+      sl.push_back({rtiow::Point3(p[0], p[1], p[2]), p[3], rtiow::Vec3(p[4], p[5], p[6])});
+    }
+    rtiow::Camera::Moments m = rtiow::render_nee_mis(cam, *s.world, ql, sl, light_samples, seg_tmax, (rtiow::Camera::MisHeuristic)heuristic, first_sample);
+    std::memcpy(sums, m.sums.data(), m.sums.size() * sizeof(double));
+    std::memcpy(sq, m.sq.data(), m.sq.size() * sizeof(double));
+    return 0;
+  } catch (std::exception &e) {
+    g_err = e.what();
+    return -1;
+  }
+}
 // rtiow::denoise_atrous through the C++ mirror: color, variance and the two outputs = width * height * 3 doubles, guides = width * height *
 // params->n_guides doubles.  0 or -1 (rlh_last_error).
 int rlh_denoise_atrous_probe(uint64_t width, uint64_t height, uint32_t iterations, const rl_atrous_params *params, const double *color, const double *variance,

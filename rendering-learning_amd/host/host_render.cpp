@@ -150,9 +150,14 @@ Camera::Moments Camera::render_nee_mis(const Hittable &world, const std::vector<
   const uint32_t h = (uint32_t)heuristic;
   return nee_moments(world, lights, light_samples, seg_tmax, first_sample, &h);
 }
-// heuristic == null: rl_rtiow_render_nee_rows, else rl_rtiow_render_nee_mis_rows
+Camera::Moments Camera::render_nee_mis(const Hittable &world, const std::vector<QuadLight> &lights, const std::vector<SphereLight> &sphere_lights,
+                                       uint32_t light_samples, double seg_tmax, MisHeuristic heuristic, uint64_t first_sample) const {
+  const uint32_t h = (uint32_t)heuristic;
+  return nee_moments(world, lights, light_samples, seg_tmax, first_sample, &h, &sphere_lights);
+}
+// heuristic == null: rl_rtiow_render_nee_rows, else rl_rtiow_render_nee_mis_rows, or with sphere_lights rl_rtiow_render_nee_mis_spheres_rows
 Camera::Moments Camera::nee_moments(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples, double seg_tmax, uint64_t first_sample,
-                                    const uint32_t *heuristic) const {
+                                    const uint32_t *heuristic, const std::vector<SphereLight> *sphere_lights) const {
   Flattened f;
   f.root = world.flatten(f);
   rl_rtiow_scene_desc d = f.desc();
@@ -165,11 +170,22 @@ Camera::Moments Camera::nee_moments(const Hittable &world, const std::vector<Qua
     for (const Vec3 *v : {&l.q, &l.u, &l.v, &l.emit}) packed.insert(packed.end(), v->e, v->e + 3);
   Moments m{params.samples_per_pixel, std::vector<double>(3 * n), std::vector<double>(3 * n)};
   const uint32_t n_lights = (uint32_t)std::min<size_t>(lights.size(), 0xFFFFFFFFu);
-  int rc = heuristic ? rl_rtiow_render_nee_mis_rows(sc, &cam, first_sample, 0, 1, n_lights, packed.data(), light_samples, seg_tmax, *heuristic, m.sums.data(),
-                                                    m.sq.data(), nullptr)
-                     : rl_rtiow_render_nee_rows(sc, &cam, first_sample, 0, 1, n_lights, packed.data(), light_samples, seg_tmax, m.sums.data(), m.sq.data(), nullptr);
+  std::vector<double> spheres;  // [Ls][7]: C, r, E
+  for (size_t j = 0; sphere_lights && j < sphere_lights->size(); j++) {
+    const SphereLight &l = (*sphere_lights)[j];
+    spheres.insert(spheres.end(), l.center.e, l.center.e + 3);
+    spheres.push_back(l.radius);
+    spheres.insert(spheres.end(), l.emit.e, l.emit.e + 3);
+  }
+  const uint32_t n_spheres = sphere_lights ? (uint32_t)std::min<size_t>(sphere_lights->size(), 0xFFFFFFFFu) : 0u;
+  const char *call = sphere_lights ? "rl_rtiow_render_nee_mis_spheres_rows: " : heuristic ? "rl_rtiow_render_nee_mis_rows: " : "rl_rtiow_render_nee_rows: ";
+  int rc = sphere_lights ? rl_rtiow_render_nee_mis_spheres_rows(sc, &cam, first_sample, 0, 1, n_lights, packed.data(), n_spheres, spheres.data(), light_samples, seg_tmax,
+                                                                *heuristic, m.sums.data(), m.sq.data(), nullptr)
+           : heuristic ? rl_rtiow_render_nee_mis_rows(sc, &cam, first_sample, 0, 1, n_lights, packed.data(), light_samples, seg_tmax, *heuristic, m.sums.data(),
+                                                      m.sq.data(), nullptr)
+                       : rl_rtiow_render_nee_rows(sc, &cam, first_sample, 0, 1, n_lights, packed.data(), light_samples, seg_tmax, m.sums.data(), m.sq.data(), nullptr);
   rl_scene_destroy(sc);
-  if (rc != RL_OK) throw std::runtime_error(std::string(heuristic ? "rl_rtiow_render_nee_mis_rows: " : "rl_rtiow_render_nee_rows: ") + rl_last_error());
+  if (rc != RL_OK) throw std::runtime_error(std::string(call) + rl_last_error());
   return m;
 }
 Denoised denoise_atrous(size_t width, size_t height, uint32_t iterations, const rl_atrous_params &params, const std::vector<double> &color,

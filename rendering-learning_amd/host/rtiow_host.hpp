@@ -883,10 +883,20 @@ struct Camera {
   enum class MisHeuristic : uint32_t { Balance = RL_MIS_BALANCE, Power = RL_MIS_POWER };
   Moments render_nee_mis(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples = 1, double seg_tmax = 1.0 - 1e-6,
                          MisHeuristic heuristic = MisHeuristic::Balance, uint64_t first_sample = 0) const;
+  // render_nee_mis with sphere lights beside the quads (rl_rtiow_render_nee_mis_spheres_rows): stationary spheres that emit outward only,
+  // sampled uniformly by area and met by the scattered ray at its near root.  `lights` may be empty.  With both kinds listing every
+  // DiffuseLight surface of the world (simple_light's quad and sphere) the expectation is ray_color's.
+  struct SphereLight {
+    Point3 center;
+    double radius;
+    Vec3 emit;  // the radiance DiffuseLight{SolidColor} emits
+  };
+  Moments render_nee_mis(const Hittable &world, const std::vector<QuadLight> &lights, const std::vector<SphereLight> &sphere_lights, uint32_t light_samples = 1,
+                         double seg_tmax = 1.0 - 1e-6, MisHeuristic heuristic = MisHeuristic::Balance, uint64_t first_sample = 0) const;
 
  private:
   Moments nee_moments(const Hittable &world, const std::vector<QuadLight> &lights, uint32_t light_samples, double seg_tmax, uint64_t first_sample,
-                      const uint32_t *heuristic) const;
+                      const uint32_t *heuristic, const std::vector<SphereLight> *sphere_lights = nullptr) const;
 };
 // Camera::render_ao as a function of the camera and the world
 inline Camera::AmbientOcclusion render_ao(const Camera &camera, const Hittable &world, uint32_t ao_rays, double radius, uint64_t first_sample = 0) {
@@ -906,6 +916,12 @@ inline Camera::Moments render_nee(const Camera &camera, const Hittable &world, c
 inline Camera::Moments render_nee_mis(const Camera &camera, const Hittable &world, const std::vector<Camera::QuadLight> &lights, uint32_t light_samples = 1,
                                       double seg_tmax = 1.0 - 1e-6, Camera::MisHeuristic heuristic = Camera::MisHeuristic::Balance, uint64_t first_sample = 0) {
   return camera.render_nee_mis(world, lights, light_samples, seg_tmax, heuristic, first_sample);
+}
+// ... with sphere lights
+inline Camera::Moments render_nee_mis(const Camera &camera, const Hittable &world, const std::vector<Camera::QuadLight> &lights,
+                                      const std::vector<Camera::SphereLight> &sphere_lights, uint32_t light_samples = 1, double seg_tmax = 1.0 - 1e-6,
+                                      Camera::MisHeuristic heuristic = Camera::MisHeuristic::Balance, uint64_t first_sample = 0) {
+  return camera.render_nee_mis(world, lights, sphere_lights, light_samples, seg_tmax, heuristic, first_sample);
 }
 
 // ---------------------------------------------------------------- denoising (rl_denoise_atrous; defined in host_render.cpp)

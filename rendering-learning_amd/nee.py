@@ -7,7 +7,8 @@ exchange does not count the emission its scattered ray finds.  `lights` must lis
 to have ray_color's expectation.  The outputs are render_moments': the sum of the sample colours and the sum of their squares.
 
 render_nee_mis* weight the light points against the scattered ray and connect that ray to the lights it crosses (multiple importance
-sampling): the same expectation, and no sample larger than what the lights emit.
+sampling): the same expectation, and no sample larger than what the lights emit.  With sphere_lights= they also take
+sphere lights (pack_sphere_lights): stationary spheres that emit outward only.
 """
 import ctypes as C
 
@@ -102,50 +103,87 @@ def _heuristic(heuristic):
     return HEURISTICS[heuristic]
 
 
+def pack_sphere_lights(sphere_lights):
+    """[(C, r, E), ...] -> float64 [Ls, 7] = C[3], r, E[3], the layout of the sphere_lights argument; E may be a scalar (a grey light).  An
+    [Ls, 7] array passes through.  Ls may be 0 (the call then is render_nee_mis' own)."""
+    if isinstance(sphere_lights, np.ndarray):
+        a = np.ascontiguousarray(sphere_lights, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 7:
+            raise ValueError(f"sphere_lights must be [Ls, 7] (C, r, E); got shape {a.shape}")
+        return a
+    rows = []
+    for i, light in enumerate(sphere_lights):
+        try:
+            c, r, e = light
+            c = np.asarray(c, dtype=np.float64).reshape(-1)
+            r = np.asarray(r, dtype=np.float64)
+            e = np.asarray(e, dtype=np.float64)
+        except (TypeError, ValueError) as err:
+            raise ValueError(f"sphere light {i}: expected (C, r, E)") from err
+        if c.shape != (3,) or r.shape != () or e.shape not in ((), (3,)):
+            raise ValueError(f"sphere light {i}: C is 3 numbers, r is one, E is one or 3")
+        rows.append(np.concatenate([c, r.reshape(1), np.broadcast_to(e, (3,))]))
+    return np.ascontiguousarray(np.array(rows, dtype=np.float64).reshape(len(rows), 7))
+
+
+def _mis_call(name, lights, sphere_lights, light_samples, seg_tmax, h):
+    """-> (what must stay alive over the call, the library function, the arguments from n_lights to heuristic): render_nee_mis*'s own
+    symbol and checks without sphere_lights, else the _spheres symbol, where `lights` may be empty."""
+    if sphere_lights is None:
+        keep, sc = _scalars(lights, light_samples, seg_tmax)
+        return keep, getattr(api.render_lib(), name), (*sc, h)
+    Sp = pack_sphere_lights(sphere_lights)
+    L = pack_lights(lights) if len(lights) else np.zeros((0, 12), dtype=np.float64)
+    fn = getattr(api.render_lib(), name.replace("nee_mis", "nee_mis_spheres"))
+    ptr = lambda a: C.c_void_p(a.ctypes.data) if a.shape[0] else None
+    return (L, Sp), fn, (L.shape[0], ptr(L), Sp.shape[0], ptr(Sp), int(light_samples), float(seg_tmax), h)
+
+
 def render_nee_mis(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", first_sample=0, row_first=0, row_step=1, stats=None,
-                   want=None, allow_degenerate=False):
+                   want=None, allow_degenerate=False, sphere_lights=None):
     """render_nee with multiple importance sampling (include/rl_render.h "NEE path renders with multiple importance sampling"; DESIGN.md
     §3.23): every light point is weighted against the scattered ray's density, and the scattered ray of a vertex that sampled the lights is
     connected to each light it crosses with the complementary weight.  heuristic: "balance" or "power" (exponent 2).  The same draws, the
-    same path and the same expectation as render_nee; no single sample exceeds what the lights emit.  -> PathNEE([nrows, W, 3])."""
+    same path and the same expectation as render_nee; no single sample exceeds what the lights emit.  -> PathNEE([nrows, W, 3]).
+    sphere_lights (pack_sphere_lights' input; include/rl_render.h "NEE path renders with sphere lights"): spheres that emit
+    outward only, sampled by area and met by the scattered ray; `lights` may then be empty."""
     h = _heuristic(heuristic)
     nrows = api.rows_for(camera.c.image_height, row_first, row_step)
     a, ptrs = _host(want, (nrows, camera.c.image_width))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_nee_mis_rows, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, h, *ptrs, stats=stats,
-              counting=True, allow_degenerate=allow_degenerate)
+    keep, fn, sc = _mis_call("rl_rtiow_render_nee_mis_rows", lights, sphere_lights, light_samples, seg_tmax, h)
+    api._call(fn, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, *ptrs, stats=stats, counting=True, allow_degenerate=allow_degenerate)
     return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
 
 
 def render_nee_mis_device(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", stream=0, row_first=0, row_step=1, first_sample=0,
-                          stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0):
+                          stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0, sphere_lights=None):
     """render_nee_device's buffers and asynchrony, render_nee_mis's estimate."""
     h = _heuristic(heuristic)
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_nee_mis_device, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, h,
-              C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+    keep, fn, sc = _mis_call("rl_rtiow_render_nee_mis_device", lights, sphere_lights, light_samples, seg_tmax, h)
+    api._call(fn, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, C.c_void_p(d_sums or None), C.c_void_p(d_sq or None),
+              C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
 
 def render_pixels_nee_mis(camera, world, xs, ys, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", first_sample=0, stats=None, want=None,
-                          allow_degenerate=False):
+                          allow_degenerate=False, sphere_lights=None):
     """The values of pixels (xs[i], ys[i]), [n, 3]: what render_nee_mis holds at [ys[i], xs[i]].  The list rules and the meaning of stats are
     render_pixels_nee's."""
     h = _heuristic(heuristic)
     xs, ys = api._pixel_list(xs, ys)
     a, ptrs = _host(want, (xs.size,))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_pixels_nee_mis, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, *sc, h,
-              *ptrs, stats=stats, allow_degenerate=allow_degenerate)
+    keep, fn, sc = _mis_call("rl_rtiow_render_pixels_nee_mis", lights, sphere_lights, light_samples, seg_tmax, h)
+    api._call(fn, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, *sc, *ptrs, stats=stats,
+              allow_degenerate=allow_degenerate)
     return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
 
 
 def render_pixels_nee_mis_device(camera, world, d_xs, d_ys, n, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", stream=0, first_sample=0,
-                                 stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0):
+                                 stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0, sphere_lights=None):
     """render_pixels_nee_device's buffers, list rules and asynchrony, render_nee_mis's estimate."""
     h = _heuristic(heuristic)
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_pixels_nee_mis_device, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys),
-              int(n), *sc, h, C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+    keep, fn, sc = _mis_call("rl_rtiow_render_pixels_nee_mis_device", lights, sphere_lights, light_samples, seg_tmax, h)
+    api._call(fn, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n), *sc, C.c_void_p(d_sums or None),
+              C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
 
 
 def cpp_mirror_probe(width, spp, first_sample, lights, light_samples, seg_tmax=SEG_TMAX):
@@ -174,5 +212,20 @@ def cpp_mirror_probe_mis(width, spp, first_sample, lights, light_samples, seg_tm
     a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
     keep, sc = _scalars(lights, light_samples, seg_tmax)
     if H.rlh_nee_mis_probe(int(width), int(spp), int(first_sample), *sc, h, *ptrs) != 0:
+        raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
+    return PathNEE(a["sums"], a["sq"], spp, light_samples)
+
+
+def cpp_mirror_probe_spheres(width, spp, first_sample, lights, sphere_lights, light_samples, seg_tmax=SEG_TMAX, heuristic="balance"):
+    """rtiow::render_nee_mis with sphere lights of the C++ mirror on simple_light at image_width = width, max_depth 6 -> PathNEE([H, W, 3])."""
+    h = _heuristic(heuristic)
+    H = api.host_lib()
+    world = api.World.simple_light()
+    p = world.params
+    p.image_width, p.samples_per_pixel, p.max_depth = int(width), int(spp), 6
+    cam = api.Camera(p)
+    a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
+    keep, fn, sc = _mis_call("rl_rtiow_render_nee_mis_rows", lights, sphere_lights, light_samples, seg_tmax, h)
+    if H.rlh_nee_spheres_probe(int(width), int(spp), int(first_sample), *sc, *ptrs) != 0:
         raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
     return PathNEE(a["sums"], a["sq"], spp, light_samples)
