@@ -5,8 +5,11 @@
 //                                    place of the record: counting calls, tmin != 1e-10, scenes without a query tree, RL_FAST=0.
 //   rtiow_occluded_rays_fast_kernel  counter-free calls with tmin == 1e-10 on scenes that have a fast tree: an ANY-hit walk of that tree.
 //
-// The any-hit walk is the four-wide reject-only TRAV step of rtiow_hit_rays_fast_kernel (rl_ray_query.h) — a third copy of that text
-// (rl_rtiow_features.h holds the second); see DESIGN.md §3.19 for why it stays a copy — with three differences:
+// The any-hit walk is the four-wide reject-only TRAV step of rtiow_hit_rays_fast_kernel (rl_ray_query.h).  The pieces it has in common
+// with that kernel and the other bodies that walk this tree are called from rl_rtiow_fast_walk.h: the LDS carve with
+// the tree-top staging, the ray start, the per-lane stack, the leaf's oimax, the box test with the filter's threshold.  The loop
+// skeleton with its head, the node fetch with the four child tests and the stored-order visit remain a copy (ao_any_hit_walk,
+// rl_rtiow_ao.h, holds the other of this form): as functions they changed this kernel's code.  Against the closest-hit form, three differences:
 //   * the pruning bound is the caller's tmax from the first step to the last: nothing narrows it, no closest hit is kept, and the
 //     children are visited in stored order (no sorting network);
 //   * a leaf yields its root by the reference's expressions (those of fastg_sphere_hit / fastg_planar_hit) and the root is CLASSIFIED:
@@ -134,16 +137,13 @@ template <int NT, int SD>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_occluded_rays_fast_kernel(RtiowParams P, OcclusionQuery Q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
-  uint32_t *s_stack = (uint32_t *)smem;                                 // [SD][NT]
-  uint4 *s_top = (uint4 *)(smem + (size_t)NT * SD * sizeof(uint32_t));  // [fg_top] FastNodeQ
+  uint32_t *s_stack;
+  uint4 *s_top;
+  fastq_query_lds<NT, SD>(smem, P, tid, s_stack, s_top);
   const DevOp *ops = P.ops;
   const FastNodeQ *nodes = P.fg_nodes;
   const FastItem *items = P.fg_items;
   const uint32_t top = P.fg_top;
-  if (top) {
-    for (uint32_t i = (uint32_t)tid; i < top * 8u; i += (uint32_t)NT) s_top[i] = ((const uint4 *)nodes)[i];
-    __syncthreads();
-  }
   const float FINF = __int_as_float(0x7F800000);
   const double tmax = Q.tmax;
   unsigned long long c_rays = 0, c_flag = 0, c_slow = 0;
@@ -154,27 +154,12 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_occluded_rays_fast_k
     c_rays++;
     uint32_t sp = 0, steps = 0;
     const RayAux32 ra32 = ray_aux32_direct(wo, wd);
-    bool amb = !(ra32.slack < FINF);  // outside the binary32 filter's range: the reference's order
-    bool unc = false, sure = false;   // an uncertain root was seen; a certain one ends the walk
-    float grow = 0.0f;
-    const float fx = (float)wo.x - P.fg_center[0], fy = (float)wo.y - P.fg_center[1], fz = (float)wo.z - P.fg_center[2];
-    const float far2 = fmaf(fx, fx, fmaf(fy, fy, fz * fz));
-    const bool unsafe = !(far2 <= P.fg_rsafe2);
-    if (unsafe) {  // start_ray of rl_rtiow_fastgen_body.inc: boxes widened, no pruning by the interval's end
-      const float L = sqrtf(far2) + P.fg_radius;
-      grow = P.fg_pad_k * L * L * fmaxf(fmaxf(fabsf(ra32.invx), fabsf(ra32.invy)), fabsf(ra32.invz));
-      if (!(grow < FINF)) amb = true;
-    }
-    auto pop = [&]() -> uint32_t {
-      if (sp == 0) return NONE;
-      sp--;
-      return s_stack[(size_t)sp * NT + tid];
-    };
-    auto push = [&](uint32_t e) {
-      if (sp < (uint32_t)SD) s_stack[(size_t)sp * NT + tid] = e, sp++;
-      else amb = true;  // more pending children than the stack holds: the reference's order decides
-    };
+    bool amb, unsafe;
+    bool unc = false, sure = false;  // an uncertain root was seen; a certain one ends the walk
+    float grow;
+    fastq_ray_start(P, wo, ra32, amb, unsafe, grow);
     const float c32 = unsafe ? FINF : (float)tmax;  // the pruning bound: the caller's tmax, first step to last
+    // (loop head written out: as fastq_next_step() / fastq_first_entry(), 1,492 - 13,819 lines of every kernel that walks this tree flat changed)
     uint32_t seg = 0;
     uint32_t e = amb ? NONE : (P.fg_n_seg > 1u ? P.fg_seg_roots[0] : P.fg_root);
 #pragma unroll 1
@@ -190,11 +175,7 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_occluded_rays_fast_k
         const FastItem it = items[item];
         D3 o, d;
         replay_chain(P, ops, it.chain, wo, wd, o, d);
-        float oimax = ra32.oimax();
-        if (it.chain != NONE)
-          oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
-                        fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
-        if (!(oimax < FINF)) oimax = FINF;
+        const float oimax = fastq_leaf_oimax(ra32, it.chain, o, d);
         const int found = it.kind == 0 ? occ_sphere_root(P.fg_spheres[item], it.payload, o, d, time, oimax, tmax)
                                        : occ_planar_root(P.planars[it.payload], o, d, oimax, tmax);
         if (found == OCC_CERTAIN) {
@@ -202,19 +183,12 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_occluded_rays_fast_k
           break;
         }
         unc = unc || found == OCC_UNCERTAIN;
-        e = pop();
+        e = fastq_pop<NT>(s_stack, tid, sp);
         continue;
       }
-      auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) {
-        float t0x = fmaf(b0, ra32.invx, -ra32.oix), t1x = fmaf(b1, ra32.invx, -ra32.oix);
-        float t0y = fmaf(b2, ra32.invy, -ra32.oiy), t1y = fmaf(b3, ra32.invy, -ra32.oiy);
-        float t0z = fmaf(b4, ra32.invz, -ra32.oiz), t1z = fmaf(b5, ra32.invz, -ra32.oiz);
-        tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)) - grow, 1e-10f);
-        float tmax32 = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)) + grow, c32);
-        float diff = tmax32 - tmin;
-        float thresh = fmaf(tmin + fabsf(tmax32), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
-        return diff < -thresh;
-      };
+      // (a one-line lambda, not direct calls: called directly, fastq_missed changed 200 lines of this kernel)
+      auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) { return fastq_missed(ra32, grow, c32, b0, b1, b2, b3, b4, b5, tmin); };
+      // (node fetch, child tests and child order written out: as functions over a node struct, 214 - 1,608 lines of the same kernels changed)
       const Float4 *nd = e < top ? (const Float4 *)(s_top + e * 8u) : (const Float4 *)(nodes + e);
       const Float4 lx = nd[0], ly = nd[1], lz = nd[2], hx = nd[3], hy = nd[4], hz = nd[5];
       const uint4 ch = *(const uint4 *)(nd + 6);
@@ -229,11 +203,11 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_occluded_rays_fast_k
       uint32_t first = NONE;
       auto visit = [&](bool h, uint32_t c) {
         if (!h) return;
-        if (first != NONE) push(first);
+        if (first != NONE) fastq_push<NT, SD>(s_stack, tid, sp, amb, first);
         first = c;
       };
       visit(h3, ch.w), visit(h2, ch.z), visit(h1, ch.y), visit(h0, ch.x);
-      e = first != NONE ? first : pop();
+      e = first != NONE ? first : fastq_pop<NT>(s_stack, tid, sp);
     }
     uint8_t occluded = sure ? (uint8_t)1 : (uint8_t)0;
     if (!sure && (amb || unc)) {  // the reference's own fold decides

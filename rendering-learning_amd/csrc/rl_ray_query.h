@@ -149,20 +149,20 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_seeded_kern
 // filter's range, ties (fast_tie_band), grazing / edge hits, far origins, stack overflow, the step budget — and a winner within the tie
 // band of a finite tmax.  The render's "skip the scattered ray's own sphere" shortcut is NOT applied: a caller's ray does not say
 // where it came from.  stats[7] counts the re-traced rays.
+// The LDS carve with the tree-top staging, the ray start, the per-lane stack, the leaf's oimax and the box test are rl_rtiow_fast_walk.h's,
+// shared with the other four bodies that walk this tree; the rest of the walk is this kernel's own text, and
+// features_fast_trace (rl_rtiow_features.h) holds the other copy of the closest-hit form.
 template <int NT, int SD>
 __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_fast_kernel(RtiowParams P, RayQuery Q) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
-  uint32_t *s_stack = (uint32_t *)smem;                                 // [SD][NT]
-  uint4 *s_top = (uint4 *)(smem + (size_t)NT * SD * sizeof(uint32_t));  // [fg_top] FastNodeQ
+  uint32_t *s_stack;
+  uint4 *s_top;
+  fastq_query_lds<NT, SD>(smem, P, tid, s_stack, s_top);
   const DevOp *ops = P.ops;
   const FastNodeQ *nodes = P.fg_nodes;
   const FastItem *items = P.fg_items;
   const uint32_t top = P.fg_top;
-  if (top) {
-    for (uint32_t i = (uint32_t)tid; i < top * 8u; i += (uint32_t)NT) s_top[i] = ((const uint4 *)nodes)[i];
-    __syncthreads();
-  }
   const double INF = __longlong_as_double(0x7FF0000000000000ll);
   const float FINF = __int_as_float(0x7F800000);
   unsigned long long c_rays = 0, c_flag = 0, c_slow = 0;
@@ -174,26 +174,14 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_fast_kernel
     double closest = Q.tmax;
     uint32_t best = NONE, sp = 0, steps = 0;
     const RayAux32 ra32 = ray_aux32_direct(wo, wd);
-    bool amb = !(ra32.slack < FINF);  // outside the binary32 filter's range: the reference's order
-    float grow = 0.0f;
-    const float fx = (float)wo.x - P.fg_center[0], fy = (float)wo.y - P.fg_center[1], fz = (float)wo.z - P.fg_center[2];
-    const float far2 = fmaf(fx, fx, fmaf(fy, fy, fz * fz));
-    const bool unsafe = !(far2 <= P.fg_rsafe2);
-    if (unsafe) {  // start_ray of rl_rtiow_fastgen_body.inc: boxes widened, no pruning by the closest hit
-      const float L = sqrtf(far2) + P.fg_radius;
-      grow = P.fg_pad_k * L * L * fmaxf(fmaxf(fabsf(ra32.invx), fabsf(ra32.invy)), fabsf(ra32.invz));
-      if (!(grow < FINF)) amb = true;
-    }
-    auto pop = [&]() -> uint32_t {
-      if (sp == 0) return NONE;
-      sp--;
-      return s_stack[(size_t)sp * NT + tid];
-    };
-    auto push = [&](uint32_t e) {
-      if (sp < (uint32_t)SD) s_stack[(size_t)sp * NT + tid] = e, sp++;
-      else amb = true;  // more pending children than the stack holds: the reference's order decides
-    };
+    bool amb, unsafe;
+    float grow;
+    fastq_ray_start(P, wo, ra32, amb, unsafe, grow);
+    // (one-line lambdas, not direct calls: called directly, fastq_missed changed 1 line of this kernel, fastq_pop / fastq_push 55)
+    auto pop = [&]() -> uint32_t { return fastq_pop<NT>(s_stack, tid, sp); };
+    auto push = [&](uint32_t e) { fastq_push<NT, SD>(s_stack, tid, sp, amb, e); };
     // several stages (a scene's unbounded Planes are leaf stages of their own, FastGeneral::stage_roots): walked one after the other
+    // (loop head written out: as fastq_next_step() / fastq_first_entry(), 1,492 - 13,819 lines of every kernel that walks this tree flat changed)
     uint32_t seg = 0;
     uint32_t e = amb ? NONE : (P.fg_n_seg > 1u ? P.fg_seg_roots[0] : P.fg_root);
 #pragma unroll 1
@@ -210,27 +198,15 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_fast_kernel
         const DevSphere isph = P.fg_spheres[item];
         D3 o, d;
         replay_chain(P, ops, it.chain, wo, wd, o, d);
-        float oimax = ra32.oimax();
-        if (it.chain != NONE)
-          oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
-                        fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
-        if (!(oimax < FINF)) oimax = FINF;
+        const float oimax = fastq_leaf_oimax(ra32, it.chain, o, d);
         if (it.kind == 0) fastg_sphere_hit(isph, it.payload, o, d, time, oimax, item, closest, best, amb);
         else fastg_planar_hit(P.planars[it.payload], o, d, oimax, item, closest, best, amb);
         e = pop();
         continue;
       }
       const float c32 = unsafe ? FINF : (float)closest;
-      auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) {
-        float t0x = fmaf(b0, ra32.invx, -ra32.oix), t1x = fmaf(b1, ra32.invx, -ra32.oix);
-        float t0y = fmaf(b2, ra32.invy, -ra32.oiy), t1y = fmaf(b3, ra32.invy, -ra32.oiy);
-        float t0z = fmaf(b4, ra32.invz, -ra32.oiz), t1z = fmaf(b5, ra32.invz, -ra32.oiz);
-        tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)) - grow, 1e-10f);
-        float tmax = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)) + grow, c32);
-        float diff = tmax - tmin;
-        float thresh = fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
-        return diff < -thresh;
-      };
+      auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) { return fastq_missed(ra32, grow, c32, b0, b1, b2, b3, b4, b5, tmin); };
+      // (node fetch, child tests and child order written out: as functions over a node struct, 214 - 1,608 lines of the same kernels changed)
       const Float4 *nd = e < top ? (const Float4 *)(s_top + e * 8u) : (const Float4 *)(nodes + e);
       const Float4 lx = nd[0], ly = nd[1], lz = nd[2], hx = nd[3], hy = nd[4], hz = nd[5];
       const uint4 ch = *(const uint4 *)(nd + 6);
@@ -258,17 +234,15 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(NT) rtiow_hit_rays_fast_kernel
     }
     Rec rec = rec_none(Q.tmax);
     uint32_t hit_flags = 0;
-    if (!amb && best != NONE) {  // the winner's HitRecord: the same test once more with ray_t.max = its root, then the POP chain
+    // the winner's HitRecord: the same test once more with ray_t.max = its root, then the POP chain
+    // (written out: as one function with features_fast_trace's, tmax passed in, 276 lines of this kernel and 2 - 14 of the pixel renders changed)
+    if (!amb && best != NONE) {
       const FastItem it = items[best];
       const DevSphere sph = P.fg_spheres[best];
       const uint32_t wmat = P.fg_material[best];
       D3 o, d;
       replay_chain(P, ops, it.chain, wo, wd, o, d);
-      float oimax = ra32.oimax();
-      if (it.chain != NONE)
-        oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
-                      fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
-      if (!(oimax < FINF)) oimax = FINF;
+      const float oimax = fastq_leaf_oimax(ra32, it.chain, o, d);
       // a finite tmax: a winner within the tie band of it may be one the reference's boxes, cut at tmax, never let it reach
       if (Q.tmax < INF && !(fabs(closest - Q.tmax) > fast_tie_band(fabs(closest) + fabs(Q.tmax), oimax))) amb = true;
       rec.t = closest;

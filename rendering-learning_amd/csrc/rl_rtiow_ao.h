@@ -15,9 +15,11 @@
 //      ring, normalize(), and the any-hit test of Interval{1e-10, R} from the hit point at the camera ray's time
 //        FAST = false  general_trace<STATS, false>, rec.any
 //        FAST = true   ao_any_hit_walk below, then general_trace for a ray the walk leaves undecided (stats[7])
-// ao_any_hit_walk is the per-ray text of rtiow_occluded_rays_fast_kernel (rl_occlusion_query.h) as a function: a FOURTH copy of the
-// four-wide reject-only TRAV step, and a second of the any-hit form.  DESIGN.md §3.20 says why it is a copy; a change to one walk belongs
-// in the other, and the tests hold the two against each other through the host composition.
+// ao_any_hit_walk is the per-ray text of rtiow_occluded_rays_fast_kernel (rl_occlusion_query.h) as a function; the kernel does not call
+// it (two more spilled SGPRs there).  Both call the pieces of rl_rtiow_fast_walk.h: the ray start,
+// the per-lane stack, the leaf's oimax, the box test with the filter's threshold.  What remains a second copy of the any-hit form: the
+// loop skeleton with its head, the node fetch with the four child tests, the stored-order visit.  A change to one of those belongs in
+// the other body, and the tests hold the two against each other through the host composition.
 //
 // Scenes with ConstantMedium objects are refused on the host (there is no seeded any-hit), so no trace here draws.
 // No barrier and no wave-wide operation inside a lane's loops: lanes leave their walks, their K loops and their samples at different times.
@@ -56,27 +58,12 @@ __device__ __forceinline__ int ao_any_hit_walk(const RtiowParams &P, const DevOp
   const float FINF = __int_as_float(0x7F800000);
   uint32_t sp = 0, steps = 0;
   const RayAux32 ra32 = ray_aux32_direct(wo, wd);
-  bool amb = !(ra32.slack < FINF);  // outside the binary32 filter's range: the reference's order
-  bool unc = false;                 // an uncertain root was seen
-  float grow = 0.0f;
-  const float fx = (float)wo.x - P.fg_center[0], fy = (float)wo.y - P.fg_center[1], fz = (float)wo.z - P.fg_center[2];
-  const float far2 = fmaf(fx, fx, fmaf(fy, fy, fz * fz));
-  const bool unsafe = !(far2 <= P.fg_rsafe2);
-  if (unsafe) {  // start_ray of rl_rtiow_fastgen_body.inc: boxes widened, no pruning by the interval's end
-    const float L = sqrtf(far2) + P.fg_radius;
-    grow = P.fg_pad_k * L * L * fmaxf(fmaxf(fabsf(ra32.invx), fabsf(ra32.invy)), fabsf(ra32.invz));
-    if (!(grow < FINF)) amb = true;
-  }
-  auto pop = [&]() -> uint32_t {
-    if (sp == 0) return NONE;
-    sp--;
-    return s_stack[(size_t)sp * NT + tid];
-  };
-  auto push = [&](uint32_t e) {
-    if (sp < (uint32_t)SD) s_stack[(size_t)sp * NT + tid] = e, sp++;
-    else amb = true;  // more pending children than the stack holds: the reference's order decides
-  };
+  bool amb, unsafe;
+  bool unc = false;  // an uncertain root was seen
+  float grow;
+  fastq_ray_start(P, wo, ra32, amb, unsafe, grow);
   const float c32 = unsafe ? FINF : (float)tmax;  // the pruning bound: R, first step to last
+  // (loop head written out: as fastq_next_step() / fastq_first_entry(), 1,492 - 13,819 lines of every kernel that walks this tree flat changed)
   uint32_t seg = 0;
   uint32_t e = amb ? NONE : (P.fg_n_seg > 1u ? P.fg_seg_roots[0] : P.fg_root);
 #pragma unroll 1
@@ -92,43 +79,31 @@ __device__ __forceinline__ int ao_any_hit_walk(const RtiowParams &P, const DevOp
       const FastItem it = items[item];
       D3 o, d;
       replay_chain(P, ops, it.chain, wo, wd, o, d);
-      float oimax = ra32.oimax();
-      if (it.chain != NONE)
-        oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
-                      fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
-      if (!(oimax < FINF)) oimax = FINF;
+      const float oimax = fastq_leaf_oimax(ra32, it.chain, o, d);
       const int found = it.kind == 0 ? occ_sphere_root(P.fg_spheres[item], it.payload, o, d, time, oimax, tmax)
                                      : occ_planar_root(P.planars[it.payload], o, d, oimax, tmax);
       if (found == OCC_CERTAIN) return AO_WALK_OCCLUDED;
       unc = unc || found == OCC_UNCERTAIN;
-      e = pop();
+      e = fastq_pop<NT>(s_stack, tid, sp);
       continue;
     }
-    auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5) {
-      float t0x = fmaf(b0, ra32.invx, -ra32.oix), t1x = fmaf(b1, ra32.invx, -ra32.oix);
-      float t0y = fmaf(b2, ra32.invy, -ra32.oiy), t1y = fmaf(b3, ra32.invy, -ra32.oiy);
-      float t0z = fmaf(b4, ra32.invz, -ra32.oiz), t1z = fmaf(b5, ra32.invz, -ra32.oiz);
-      float tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)) - grow, 1e-10f);
-      float tmax32 = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)) + grow, c32);
-      float diff = tmax32 - tmin;
-      float thresh = fmaf(tmin + fabsf(tmax32), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
-      return diff < -thresh;
-    };
+    // (node fetch, child tests and child order written out: as functions over a node struct, 214 - 1,608 lines of the same kernels changed)
     const Float4 *nd = e < top ? (const Float4 *)(s_top + e * 8u) : (const Float4 *)(nodes + e);
     const Float4 lx = nd[0], ly = nd[1], lz = nd[2], hx = nd[3], hy = nd[4], hz = nd[5];
     const uint4 ch = *(const uint4 *)(nd + 6);
-    const bool h0 = !missed(lx.x, hx.x, ly.x, hy.x, lz.x, hz.x) && ch.x != NONE;
-    const bool h1 = !missed(lx.y, hx.y, ly.y, hy.y, lz.y, hz.y) && ch.y != NONE;
-    const bool h2 = !missed(lx.z, hx.z, ly.z, hy.z, lz.z, hz.z) && ch.z != NONE;
-    const bool h3 = !missed(lx.w, hx.w, ly.w, hy.w, lz.w, hz.w) && ch.w != NONE;
-    uint32_t first = NONE;  // children in STORED order
+    float k0, k1, k2, k3;  // (the entry distances: not used, the children are visited in stored order)
+    const bool h0 = !fastq_missed(ra32, grow, c32, lx.x, hx.x, ly.x, hy.x, lz.x, hz.x, k0) && ch.x != NONE;
+    const bool h1 = !fastq_missed(ra32, grow, c32, lx.y, hx.y, ly.y, hy.y, lz.y, hz.y, k1) && ch.y != NONE;
+    const bool h2 = !fastq_missed(ra32, grow, c32, lx.z, hx.z, ly.z, hy.z, lz.z, hz.z, k2) && ch.z != NONE;
+    const bool h3 = !fastq_missed(ra32, grow, c32, lx.w, hx.w, ly.w, hy.w, lz.w, hz.w, k3) && ch.w != NONE;
+    uint32_t first = NONE;  // children in STORED order (rtiow_occluded_rays_fast_kernel says why)
     auto visit = [&](bool h, uint32_t c) {
       if (!h) return;
-      if (first != NONE) push(first);
+      if (first != NONE) fastq_push<NT, SD>(s_stack, tid, sp, amb, first);
       first = c;
     };
     visit(h3, ch.w), visit(h2, ch.z), visit(h1, ch.y), visit(h0, ch.x);
-    e = first != NONE ? first : pop();
+    e = first != NONE ? first : fastq_pop<NT>(s_stack, tid, sp);
   }
   return (amb || unc) ? AO_WALK_UNDECIDED : AO_WALK_OPEN;
 }

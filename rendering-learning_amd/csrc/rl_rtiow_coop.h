@@ -166,7 +166,7 @@ __device__ __forceinline__ void rtiow_coop_body(const RtiowParams &P, const floa
               float t0z = fmaf(bz0, ra32.invz, -ra32.oiz), t1z = fmaf(bz1, ra32.invz, -ra32.oiz);
               float tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)), 1e-10f);
               float tmax = fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z));
-              float thresh = fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
+              float thresh = fast_miss_thresh(ra32, tmin, tmax);
               cand = !((tmax - tmin) < -thresh);                                           // NaN arithmetic: candidate
             }
             const unsigned long long mask = __ballot(cand);

@@ -13,6 +13,7 @@
 // Order-sensitive rays (rl_fast_bvh.cpp): two roots within fast_tie_band of each other, grazing sphere hits, planar hits within 1e-9 of an edge,
 // rays outside the binary32 filter's range or whose origin is farther than r_safe from the scene's centre, stack overflow.
 #pragma once
+#include "rl_rtiow_fast_walk.h"  // FASTG_STEP_BUDGET and the pieces of the walk that its five bodies call
 #include "rl_rtiow_general.h"
 #include "rl_rtiow_wave.h"
 
@@ -87,13 +88,6 @@ __device__ __forceinline__ uint32_t general_slow_trace(const RtiowParams &P, con
   return flags;
 }
 
-// A fast walk that has taken this many steps (nodes + primitive tests) is given up: the ray is re-traced by the reference's own fold, which
-// prunes by ITS boxes (cfg 5: ~140 tests).  The rays that get here are far-origin rays (`unsafe`: every box widened by `grow`, no pruning by
-// the closest hit) whose widened boxes overlap half the scene — a handful per frame walk 1e5 ... 1e6 steps, 30 ... 460 ms EACH in a
-// traversal-only launch, and the megakernel's last lanes were those too: cfg 5 at 64 spp 2.54 -> 1.87 s.  Any budget is correct (the fold
-// is the reference); measured at 64 spp: 64 steps 3.56 s (16.7 M rays re-traced), 128: 2.20 s (5.1 M), 256: 1.89 s, 512: 1.87 s, 2048: 1.88 s
-// (4.15 M: the rays that are re-traced for other reasons).
-static const uint32_t FASTG_STEP_BUDGET = 512;
 #ifdef RL_FASTG_VERIFY  // debug build (tools/verify_fastg.py): every ray is ALSO traced in the reference's order; mismatches are logged
 // (g_vcount / g_vlog / g_vstats: rl_rtiow_wave.h — the sphere kernels log into them too)
 #endif

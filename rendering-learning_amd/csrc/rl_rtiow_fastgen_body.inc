@@ -76,15 +76,14 @@
       state = (e & FASTG_LEAF) ? ST_LEAF : ST_TRAV;
     }
   };
-  auto pop = [&]() -> uint32_t {
-    if (sp == 0) return NONE;
-    sp--;
-    return s_stack[(size_t)sp * NT + tid];
-  };
+  // (missed, push and pop: one-line lambdas around the shared functions, not direct calls — fastq_missed called directly changed
+  // 14 - 6,229 lines of the 27 instantiations)
+  auto pop = [&]() -> uint32_t { return fastq_pop<NT>(s_stack, tid, sp); };
   auto start_ray = [&]() {
     closest = INF, best = NONE, sp = 0, steps = 0;
     if (MEDIA) seg = 0, pos0 = rng.pos, ray_flags = 0;
     ra32 = ray_aux32_direct(wo, wd);
+    // (fastq_ray_start's arithmetic, written out: as that function 27 - 85 lines of the 27 instantiations changed)
     float fx = (float)wo.x - P.fg_center[0], fy = (float)wo.y - P.fg_center[1], fz = (float)wo.z - P.fg_center[2];
     float far2 = fmaf(fx, fx, fmaf(fy, fy, fz * fz));
     amb = !(ra32.slack < FINF);  // outside the binary32 filter's range: the reference's order
@@ -132,20 +131,8 @@
           c_steps++;
 #endif
           const float c32 = unsafe ? FINF : (float)closest;
-          auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) {
-            float t0x = fmaf(b0, ra32.invx, -ra32.oix), t1x = fmaf(b1, ra32.invx, -ra32.oix);
-            float t0y = fmaf(b2, ra32.invy, -ra32.oiy), t1y = fmaf(b3, ra32.invy, -ra32.oiy);
-            float t0z = fmaf(b4, ra32.invz, -ra32.oiz), t1z = fmaf(b5, ra32.invz, -ra32.oiz);
-            tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)) - grow, 1e-10f);
-            float tmax = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)) + grow, c32);
-            float diff = tmax - tmin;
-            float thresh = fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
-            return diff < -thresh;
-          };
-          auto push = [&](uint32_t e) {
-            if (sp < (uint32_t)SD) s_stack[(size_t)sp * NT + tid] = e, sp++;
-            else amb = true;  // more pending children than the stack holds: the reference's order decides
-          };
+          auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) { return fastq_missed(ra32, grow, c32, b0, b1, b2, b3, b4, b5, tmin); };
+          auto push = [&](uint32_t e) { fastq_push<NT, SD>(s_stack, tid, sp, amb, e); };
           // the tree's top (breadth first, FastGeneral::top_nodes) sits in LDS, the rest comes through L1 / L2 / Infinity Cache
           const Float4 *nd = pc < top ? (const Float4 *)(s_top + pc * 8u) : (const Float4 *)(nodes + pc);
           // Measured and dropped (round 3, RL_TUNE experiment bits): the node's first 16 bytes alone, then an s_waitcnt, then the other six
@@ -288,6 +275,7 @@
         D3 o, d;
         replay_chain(P, ops, it.chain, wo, wd, o, d);
         // the tie band's coordinate scale max |o_k / d_k| of the ray the test actually sees (binary32 is plenty for a tolerance)
+        // (fastq_leaf_oimax's text, written out here and in SHADE: as that function 22 - 62 lines of the 27 instantiations changed)
         float oimax = ra32.oimax();
         if (it.chain != NONE)
           oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),

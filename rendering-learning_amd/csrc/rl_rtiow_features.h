@@ -12,9 +12,13 @@
 //        FAST = true   the flat four-wide SAH walk of rtiow_hit_rays_fast_kernel with tmax = +inf: LDS stack, tree top in LDS, every
 //                      order-sensitive ray re-traced by general_trace — the same record, bit for bit
 //   3. rec_uv + material_texture / texture_value<2> as rtiow_scatter_rays_kernel (rl_material_query.h) calls them
-// The walk of FAST is a SECOND COPY of rtiow_hit_rays_fast_kernel's per-ray text (features_fast_trace below), not a function shared with
-// it: factored into one function for both, the query kernel came out at 274 VGPRs + 18 AGPRs instead of 247; as it is,
-// it stays the code object it was.  What the copy leaves out is the finite-tmax tie test (tmax is +inf here).  A change to one walk belongs in the other; the tests hold the two against each other through the host composition.
+// The walk of FAST (features_fast_trace below) and rtiow_hit_rays_fast_kernel's are two bodies, not one function: factored into one for
+// both, the query kernel came out at 274 VGPRs + 18 AGPRs instead of 247.  What the two CALL, with the other bodies
+// that walk this tree, is in rl_rtiow_fast_walk.h: the ray start, the per-lane stack, the leaf's oimax and the box
+// test with the filter's threshold.  What remains a copy here: the loop skeleton with its head, the node fetch with the four child
+// tests, the nearest-first order and the winner's record (without the finite-tmax tie test: tmax is +inf here) — each failed §3.26's
+// rule as a function and says so at its place.  A change to one of those belongs in the other body; the tests hold the two against each
+// other through the host composition.
 //
 // The kernel takes its own parameter struct beside RtiowParams, as the ray queries take RayQuery: RtiowParams does not grow.
 // The LDS carve and the counters' way into P.stats are rl_rtiow_pixel_skeleton.h's (pixel_lds, pixel_flush_counters), shared with the AO,
@@ -50,25 +54,10 @@ __device__ __forceinline__ uint32_t features_fast_trace(const RtiowParams &P, co
   double closest = INF;
   uint32_t best = NONE, sp = 0, steps = 0;
   const RayAux32 ra32 = ray_aux32_direct(wo, wd);
-  bool amb = !(ra32.slack < FINF);  // outside the binary32 filter's range: the reference's order
-  float grow = 0.0f;
-  const float fx = (float)wo.x - P.fg_center[0], fy = (float)wo.y - P.fg_center[1], fz = (float)wo.z - P.fg_center[2];
-  const float far2 = fmaf(fx, fx, fmaf(fy, fy, fz * fz));
-  const bool unsafe = !(far2 <= P.fg_rsafe2);
-  if (unsafe) {  // start_ray of rl_rtiow_fastgen_body.inc: boxes widened, no pruning by the closest hit
-    const float L = sqrtf(far2) + P.fg_radius;
-    grow = P.fg_pad_k * L * L * fmaxf(fmaxf(fabsf(ra32.invx), fabsf(ra32.invy)), fabsf(ra32.invz));
-    if (!(grow < FINF)) amb = true;
-  }
-  auto pop = [&]() -> uint32_t {
-    if (sp == 0) return NONE;
-    sp--;
-    return s_stack[(size_t)sp * NT + tid];
-  };
-  auto push = [&](uint32_t e) {
-    if (sp < (uint32_t)SD) s_stack[(size_t)sp * NT + tid] = e, sp++;
-    else amb = true;  // more pending children than the stack holds: the reference's order decides
-  };
+  bool amb, unsafe;
+  float grow;
+  fastq_ray_start(P, wo, ra32, amb, unsafe, grow);
+  // (loop head written out: as fastq_next_step() / fastq_first_entry(), 1,492 - 13,819 lines of every kernel that walks this tree flat changed)
   uint32_t seg = 0;
   uint32_t e = amb ? NONE : (P.fg_n_seg > 1u ? P.fg_seg_roots[0] : P.fg_root);
 #pragma unroll 1
@@ -85,35 +74,22 @@ __device__ __forceinline__ uint32_t features_fast_trace(const RtiowParams &P, co
       const DevSphere isph = P.fg_spheres[item];
       D3 o, d;
       replay_chain(P, ops, it.chain, wo, wd, o, d);
-      float oimax = ra32.oimax();
-      if (it.chain != NONE)
-        oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
-                      fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
-      if (!(oimax < FINF)) oimax = FINF;
+      const float oimax = fastq_leaf_oimax(ra32, it.chain, o, d);
       if (it.kind == 0) fastg_sphere_hit(isph, it.payload, o, d, time, oimax, item, closest, best, amb);
       else fastg_planar_hit(P.planars[it.payload], o, d, oimax, item, closest, best, amb);
-      e = pop();
+      e = fastq_pop<NT>(s_stack, tid, sp);
       continue;
     }
     const float c32 = unsafe ? FINF : (float)closest;
-    auto missed = [&](float b0, float b1, float b2, float b3, float b4, float b5, float &tmin) {
-      float t0x = fmaf(b0, ra32.invx, -ra32.oix), t1x = fmaf(b1, ra32.invx, -ra32.oix);
-      float t0y = fmaf(b2, ra32.invy, -ra32.oiy), t1y = fmaf(b3, ra32.invy, -ra32.oiy);
-      float t0z = fmaf(b4, ra32.invz, -ra32.oiz), t1z = fmaf(b5, ra32.invz, -ra32.oiz);
-      tmin = fmaxf(fmaxf(fmaxf(fminf(t0x, t1x), fminf(t0y, t1y)), fminf(t0z, t1z)) - grow, 1e-10f);
-      float tmax = fminf(fminf(fminf(fmaxf(t0x, t1x), fmaxf(t0y, t1y)), fmaxf(t0z, t1z)) + grow, c32);
-      float diff = tmax - tmin;
-      float thresh = fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
-      return diff < -thresh;
-    };
+    // (node fetch, child tests and child order written out: as functions over a node struct, 214 - 1,608 lines of the same kernels changed)
     const Float4 *nd = e < top ? (const Float4 *)(s_top + e * 8u) : (const Float4 *)(nodes + e);
     const Float4 lx = nd[0], ly = nd[1], lz = nd[2], hx = nd[3], hy = nd[4], hz = nd[5];
     const uint4 ch = *(const uint4 *)(nd + 6);
     float k0, k1, k2, k3;
-    const bool h0 = !missed(lx.x, hx.x, ly.x, hy.x, lz.x, hz.x, k0) && ch.x != NONE;
-    const bool h1 = !missed(lx.y, hx.y, ly.y, hy.y, lz.y, hz.y, k1) && ch.y != NONE;
-    const bool h2 = !missed(lx.z, hx.z, ly.z, hy.z, lz.z, hz.z, k2) && ch.z != NONE;
-    const bool h3 = !missed(lx.w, hx.w, ly.w, hy.w, lz.w, hz.w, k3) && ch.w != NONE;
+    const bool h0 = !fastq_missed(ra32, grow, c32, lx.x, hx.x, ly.x, hy.x, lz.x, hz.x, k0) && ch.x != NONE;
+    const bool h1 = !fastq_missed(ra32, grow, c32, lx.y, hx.y, ly.y, hy.y, lz.y, hz.y, k1) && ch.y != NONE;
+    const bool h2 = !fastq_missed(ra32, grow, c32, lx.z, hx.z, ly.z, hy.z, lz.z, hz.z, k2) && ch.z != NONE;
+    const bool h3 = !fastq_missed(ra32, grow, c32, lx.w, hx.w, ly.w, hy.w, lz.w, hz.w, k3) && ch.w != NONE;
     const int nh = (int)h0 + (int)h1 + (int)h2 + (int)h3;
     k0 = h0 ? k0 : FINF, k1 = h1 ? k1 : FINF, k2 = h2 ? k2 : FINF, k3 = h3 ? k3 : FINF;
     uint32_t c0 = ch.x, c1 = ch.y, c2 = ch.z, c3 = ch.w;
@@ -126,24 +102,22 @@ __device__ __forceinline__ uint32_t features_fast_trace(const RtiowParams &P, co
       ka = tk, ca = tc;
     };
     cex(u0, u1, c0, c1), cex(u2, u3, c2, c3), cex(u0, u2, c0, c2), cex(u1, u3, c1, c3), cex(u1, u2, c1, c2);
-    if (nh >= 4) push(c3);
-    if (nh >= 3) push(c2);
-    if (nh >= 2) push(c1);
-    e = nh ? c0 : pop();
+    if (nh >= 4) fastq_push<NT, SD>(s_stack, tid, sp, amb, c3);
+    if (nh >= 3) fastq_push<NT, SD>(s_stack, tid, sp, amb, c2);
+    if (nh >= 2) fastq_push<NT, SD>(s_stack, tid, sp, amb, c1);
+    e = nh ? c0 : fastq_pop<NT>(s_stack, tid, sp);
   }
   rec = rec_none(INF);
   uint32_t hit_flags = 0;
-  if (!amb && best != NONE) {  // the winner's HitRecord: the same test once more with ray_t.max = its root, then the POP chain
+  // the winner's HitRecord: the same test once more with ray_t.max = its root, then the POP chain
+  // (written out: as one function with rtiow_hit_rays_fast_kernel's, 2 - 14 lines of the pixel renders and 276 of that kernel changed)
+  if (!amb && best != NONE) {
     const FastItem it = items[best];
     const DevSphere sph = P.fg_spheres[best];
     const uint32_t wmat = P.fg_material[best];
     D3 o, d;
     replay_chain(P, ops, it.chain, wo, wd, o, d);
-    float oimax = ra32.oimax();
-    if (it.chain != NONE)
-      oimax = fmaxf(fmaxf(fabsf((float)o.x * __builtin_amdgcn_rcpf((float)d.x)), fabsf((float)o.y * __builtin_amdgcn_rcpf((float)d.y))),
-                    fabsf((float)o.z * __builtin_amdgcn_rcpf((float)d.z)));
-    if (!(oimax < FINF)) oimax = FINF;
+    const float oimax = fastq_leaf_oimax(ra32, it.chain, o, d);
     rec.t = closest;
     if (it.kind == 0) {
       if (sphere_hit_rec(sph, it.payload | SPH_UV, wmat, it.op_pc, o, d, time, rec)) hit_flags++;

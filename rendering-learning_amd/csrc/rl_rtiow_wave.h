@@ -377,6 +377,10 @@ __device__ __forceinline__ RayAux32 ray_aux32_direct(D3 o, D3 d) {
   r.slack = ok ? m * 1.430511474609375e-06f : __int_as_float(0x7F800000);  // 24u, or +inf: never certain
   return r;
 }
+// The decision's threshold, the ONE statement of it: a box with tmax'' - tmin'' < -fast_miss_thresh is certainly missed.
+__device__ __forceinline__ float fast_miss_thresh(const RayAux32 &ra32, float tmin, float tmax) {
+  return fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
+}
 // Two accepted roots closer than this are treated as a tie (the ray is re-traced in the reference's order).  The reference's own
 // decisions that involve two different primitives — `tmin < closest` on its boxes, `t <= closest` in Sphere::hit — compare values
 // whose rounding errors are a few u (2^-53) times the SCALES involved: the far root of the sphere (cancellation in -half_b -+ sqrt),

@@ -422,7 +422,7 @@
               tmin = fmaxf(fmaxf(fmaxf(fmaf(-hx, ax, tcx), fmaf(-hy, ay, tcy)), fmaf(-hz, az, tcz)), 1e-10f);
               float tmax = fminf(fminf(fminf(fmaf(hx, ax, tcx), fmaf(hy, ay, tcy)), fmaf(hz, az, tcz)), c32);
               float diff = tmax - tmin;
-              float thresh = fmaf(tmin + fabsf(tmax), 7.152557373046875e-07f, ra32.slack);  // 12u(|tmin|+|tmax|) + slack (ray_aux32_direct)
+              float thresh = fast_miss_thresh(ra32, tmin, tmax);
               return diff < -thresh;  // certainly tmin > tmax; false for NaN arithmetic: visit
             };
             if (STATS) c_nodes += 2;  // debug instantiation only (rl_debug_fast_stats): the fast structure's own tests, not the reference's
