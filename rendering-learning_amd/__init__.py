@@ -18,3 +18,4 @@ from . import nee  # noqa: F401
 from .nee import PathNEE, render_nee, render_nee_device, render_pixels_nee, render_pixels_nee_device  # noqa: F401
 from .nee import render_nee_mis, render_nee_mis_device, render_pixels_nee_mis, render_pixels_nee_mis_device  # noqa: F401
 from .nee import pack_sphere_lights  # noqa: F401
+from . import entry_table  # noqa: F401

@@ -306,6 +306,11 @@ RENDER_SIGNATURES = {
     "rl_debug_set_pixel_entry": (None, [_I]),
     "rl_debug_set_pixel_entry_sphere": (None, [_I]),
     "rl_debug_pixel_entry_read": (_I, [_P, _P, _U64]),
+    "rl_debug_set_pixel_entry_time": (None, [_I]),
+    "rl_debug_set_pixel_entry_reuse": (None, [_I]),
+    "rl_debug_pixel_entry_builds": (_U64, []),
+    "rl_debug_pixel_entry_time_read": (_I, [_P, _P, _U64, _U32]),
+    "rl_debug_pixel_entry_census": (_I, [_P, _P]),
     "rl_debug_fast_tree": (_I, [_P, _P, _U32, _PU32]),
     "rl_debug_set_fastg_one_wave": (None, [_I]),
     "rl_debug_set_status_gap": (_I, [_U, _U]),

@@ -239,8 +239,12 @@ FastNodeCH fast_node_ch(const FastNode &nd) {
 // The ball the entry table tests a leaf's sphere with: centre at time 1/2, R = r + pad + |dc| / 2, where pad is the largest of the three pads
 // of the sphere's leaf box above (>= guard_pad: a ray that stays R away from this centre stays r + guard_pad away from the centre at every
 // time in [0, 1], and its rounded discriminant is negative).  Everything is rounded upwards by a relative 1e-12, thousands of roundings.
-void fast_leaf_balls(const rl_rtiow_scene_desc &d, const GuardFrame &f, std::vector<double> &balls) {
+// motion (time slices of the table, rl_pixel_entry.h): per sphere {dc.x, dc.y, dc.z, h}, dc = RN(c1 - c0) as the device's DevSphere has it
+// (zeros for a stationary sphere) and h = RN(sqrt(dc2) / 2), the very term that went into R.  Returns false when some of it is not finite.
+bool fast_leaf_balls(const rl_rtiow_scene_desc &d, const GuardFrame &f, std::vector<double> &balls, std::vector<double> &motion) {
   balls.assign((size_t)d.n_spheres * 4, 0.0);
+  motion.assign((size_t)d.n_spheres * 4, 0.0);
+  bool finite = true;
   for (uint32_t i = 0; i < d.n_spheres; i++) {
     const rl_sphere &sp = d.spheres[i];
     double r = std::fabs(sp.radius), pad = guard_pad(f, r), dc2 = 0.0, cmax = 0.0;
@@ -250,9 +254,14 @@ void fast_leaf_balls(const rl_rtiow_scene_desc &d, const GuardFrame &f, std::vec
       balls[(size_t)i * 4 + ax] = 0.5 * c0 + 0.5 * c1;
       dc2 += (c1 - c0) * (c1 - c0);
       cmax = std::fmax(cmax, std::fmax(std::fabs(c0), std::fabs(c1)));
+      motion[(size_t)i * 4 + ax] = c1 - c0;
     }
-    balls[(size_t)i * 4 + 3] = (r + pad + 0.5 * std::sqrt(dc2)) * (1.0 + 1e-12) + 1e-12 * cmax;  // (+ the rounding of the midpoint and of c0 + dc t)
+    const double h = 0.5 * std::sqrt(dc2);
+    motion[(size_t)i * 4 + 3] = h;
+    balls[(size_t)i * 4 + 3] = (r + pad + h) * (1.0 + 1e-12) + 1e-12 * cmax;  // (+ the rounding of the midpoint and of c0 + dc t)
+    for (int k = 0; k < 4; k++) finite = finite && std::isfinite(motion[(size_t)i * 4 + k]) && std::isfinite(balls[(size_t)i * 4 + k]);
   }
+  return finite;
 }
 
 // =====================================================================================================================

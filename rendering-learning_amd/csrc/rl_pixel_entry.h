@@ -57,8 +57,34 @@
 // the difference carries u (|c| + |lookfrom|) per axis, each component of the product 4u |c - lookfrom| |D|, root and quotient 3u:
 // under 16u (|c| + |lookfrom|) in all, and the test allows eps = 2^-40 (|c|_1 + |lookfrom|_1 + R), five hundred times that.  An infinite t_hi
 // and a NaN w are tested for; a non-finite R, dist or delta, or D = 0 (NaN by 0 * inf) fail the final comparison: "touched".  The test only ever removes a leaf.
+//
+// Time slices (RL_PIXEL_ENTRY_TIME = T = 1 | 2 | 4 | 8, default 4; leaves of moving spheres only).  The ball above holds a moving sphere for
+// the whole shutter interval: R = r + pad + |dc| / 2 where the sphere's own radius is r, and in bouncing_spheres |dc| is of the order of r, so
+// the ball's silhouette is several times the sphere's and every pixel in the difference sends all its camera rays through a Sphere::hit that
+// the sample's time alone rules out (measured: 0.50 of the 0.68 wasted visits per camera ray, profiles/pixel_entry_time.txt).  GEN draws
+// `time` before it starts the ray, so the table holds T words per pixel, [pixel][T], and a camera ray takes word k = floor(time T) —
+// exact: T is a power of two and time = gen_f64() < 1, so time * T is exact and the conversion truncates (rl_pixel_entry_slices.h time_slice).
+// The walk is ONE walk per pixel: inner boxes hold the whole sweep and are tested once, as above; a leaf the all-times test keeps is then
+// tested, if its sphere moves, against the ball of each slice,
+//     c_k = c(1/2) + dc ((k + 1/2) / T - 1/2),        R_k = R - h (1 - 1 / T),   h = RN(|dc| / 2) (fast_leaf_balls' own term of R)
+// and the walk carries T + 1 cuts, the all-times one (written to the one-word table, bit for bit what the one-slice kernel writes: the root
+// walks of the other kernels, T = 1 and the tests read it) and one per slice.  The split loop is the all-times table's: a slice takes ITS
+// reductions of the child subtrees that loop visits, so a slice's entries lie inside the all-times entries — fewer leaves below them, never
+// others — and a stationary world's slice words are the all-times word.
+// Why the frames cannot change.  For time in [k / T, (k + 1) / T] the exact centre c0 + dc time lies within |dc| / (2 T) of the exact slice
+// centre.  R carries r + pad + h plus a relative 1e-12 of itself plus 1e-12 |c|_max (fast_leaf_balls), about 9000u (R + |c|_max), which
+// was there for the rounding of c(1/2) and of the kernel's own c0 + dc time: 2u |c|_max.  The slices add: h against |dc| / 2 (three
+// roundings, 3u h), the product and the difference in R_k (2u R), and two roundings per coordinate of c_k, under 2u (|c| + |dc|) per axis,
+// 4u (|c|_max + 2 h) as a length: 13u (R + |c|_max) in all, still a seven-hundredth of what R carries, so no term is added to eps:
+//     R_k >= r + pad + |dc| / (2 T) + |RN(c_k) - c_k| + what the ball test's own rounding (eps, above) needs.
+// (eps is taken of the ball that is tested, RN(c_k) and R_k: the distance's 16u (|c| + |lookfrom|) is in terms of that very centre.)  A leaf dropped from slice k is therefore one that no camera
+// ray of the pixel, at a time of that slice, approaches within r + pad of its centre: by the argument of "The sphere test" fast_sphere_hit
+// returns at `disc < 0` or at the window test, before it touches closest, hit_prim or amb.  Answer, re-traces (slow_traces) and panic-site
+// counts are the all-times table's.  A motion value that is not finite (rl_fast_bvh.cpp) leaves the call with one slice; so does a box-only
+// table (RL_PIXEL_ENTRY_SPHERE=0), and a sliced table above 256 MB.
 #pragma once
 #include "rl_rtiow_kernel.h"
+#include "rl_pixel_entry_slices.h"  // time_slice, slice_ball, PIXEL_ENTRY_TIME_DEFAULT
 
 namespace rl {
 
@@ -125,11 +151,29 @@ __device__ __forceinline__ bool beam_may_touch_ball(const PixelBeam &B, const do
   return !(dist - fmax(w_lo, w_hi) - eps > R);
 }
 
-// a leaf: its box and, with `balls`, its sphere
-__device__ __forceinline__ bool beam_touches_leaf(const PixelBeam &B, const float *box, const double *balls, uint32_t sphere, double &t_near) {
+// A leaf: its box and, with `balls`, its sphere.  Returns the tables of `want` the leaf belongs to: bit 0 the all-times table, bit 1 + k slice k
+// of NS - 1 (NS = 1: the all-times table alone).  A leaf the all-times ball excludes is in no slice (no ray comes within r + pad at any time),
+// a stationary sphere (h == 0) is in every slice its all-times test leaves it in, a moving one in the slices whose own ball the beam may touch.
+template <int NS>
+__device__ __forceinline__ uint32_t beam_leaf_tables(const PixelBeam &B, const float *box, const double *balls, const double *motion, uint32_t sphere, uint32_t want,
+                                                     double &t_near) {
   double t_far;
-  if (!beam_touches(B, box, t_near, t_far)) return false;
-  return !balls || beam_may_touch_ball(B, balls + (size_t)sphere * 4, t_near, t_far);
+  if (!beam_touches(B, box, t_near, t_far)) return 0u;
+  if (!balls) return want;
+  const double *ball = balls + (size_t)sphere * 4;
+  if (!beam_may_touch_ball(B, ball, t_near, t_far)) return 0u;
+  if (NS == 1) return want;
+  const double *mo = motion + (size_t)sphere * 4;
+  if (mo[3] == 0.0) return want;
+  uint32_t in = want & 1u;
+#pragma unroll
+  for (int k = 0; k + 1 < NS; k++)
+    if ((want >> (k + 1)) & 1u) {
+      double sb[4];
+      slice_ball(ball, mo, (uint32_t)k, (uint32_t)(NS - 1), sb);
+      if (beam_may_touch_ball(B, sb, t_near, t_far)) in |= 2u << k;
+    }
+  return in;
 }
 
 // What a subtree reduces to: the number of its leaves the beam may touch, the deepest entry that holds them all, the nearest t among them
@@ -138,20 +182,31 @@ struct EntryCut {
   double t_near;
 };
 
+
 // Reduces the subtree of entry e (its own box already found touched, at t_e): post-order walk with an explicit stack, depth <= FAST_MAX_DEPTH
-// (a leaf e has passed beam_touches_leaf at its parent; balls: null = box-only cut)
-__device__ __forceinline__ EntryCut reduce_subtree(const RtiowParams &P, const PixelBeam &B, const double *balls, uint32_t e, double t_e) {
-  if (e >= P.n_fast_inner) return EntryCut{1u, e, t_e};
+// (a leaf e has passed beam_leaf_tables at its parent for every table of `want`; balls: null = box-only cut).  ONE walk for all NS tables: a box is
+// tested once, a leaf counts in the tables beam_leaf_tables names, and out[s] is what the walk of table s alone would return.
+template <int NS>
+__device__ __forceinline__ void reduce_subtree(const RtiowParams &P, const PixelBeam &B, const double *balls, const double *motion, uint32_t e, double t_e, uint32_t want,
+                                               EntryCut *out) {
   const double INF = __longlong_as_double(0x7FF0000000000000ll);
+  const EntryCut none{0u, FAST_NONE, INF};
+  if (e >= P.n_fast_inner) {
+#pragma unroll
+    for (int s = 0; s < NS; s++) out[s] = ((want >> s) & 1u) ? EntryCut{1u, e, t_e} : none;
+    return;
+  }
   constexpr int MAXD = (int)FAST_MAX_DEPTH + 2;
   uint32_t node[MAXD], phase[MAXD];  // phase: children of node[] already handled (0 .. 2)
-  EntryCut acc[MAXD];                // what the handled children reduced to
+  EntryCut acc[MAXD][NS];            // what the handled children reduced to, per table
   int sp = 0;
-  node[0] = e, phase[0] = 0, acc[0] = EntryCut{0u, FAST_NONE, INF};
-  EntryCut done{0u, FAST_NONE, INF};
+  node[0] = e, phase[0] = 0;
+#pragma unroll
+  for (int s = 0; s < NS; s++) acc[0][s] = none, out[s] = none;
   for (;;) {
     if (phase[sp] == 2u) {  // both children handled: this node's result goes to its parent
-      done = acc[sp];
+#pragma unroll
+      for (int s = 0; s < NS; s++) out[s] = acc[sp][s];
       if (sp == 0) break;
       sp--;
     } else {
@@ -159,36 +214,35 @@ __device__ __forceinline__ EntryCut reduce_subtree(const RtiowParams &P, const P
       const uint32_t side = phase[sp]++;
       const uint32_t ce = side ? (nd.child >> 16) : (nd.child & 0xFFFFu);
       double tc;
-      done = EntryCut{0u, FAST_NONE, INF};
-      if (ce >= P.n_fast_inner) {
-        if (beam_touches_leaf(B, nd.box[side], balls, ce - P.n_fast_inner, tc)) done = EntryCut{1u, ce, tc};
-      } else if (beam_touches(B, nd.box[side], tc)) {
+      uint32_t in = 0u, cnt = 1u;  // the tables the child counts in, with cnt leaves
+      if (ce >= P.n_fast_inner) in = beam_leaf_tables<NS>(B, nd.box[side], balls, motion, ce - P.n_fast_inner, want, tc);
+      else if (beam_touches(B, nd.box[side], tc)) {
         if (sp + 1 < MAXD) {  // (always: the tree is at most FAST_MAX_DEPTH deep)
           sp++;
-          node[sp] = ce, phase[sp] = 0, acc[sp] = EntryCut{0u, FAST_NONE, INF};
+          node[sp] = ce, phase[sp] = 0;
+#pragma unroll
+          for (int s = 0; s < NS; s++) acc[sp][s] = none;
           continue;
-        } else done = EntryCut{2u, ce, tc};  // not walked: the child itself holds whatever lies below it
+        } else in = want, cnt = 2u;  // not walked: the child itself holds whatever lies below it
+      }
+#pragma unroll
+      for (int s = 0; s < NS; s++) out[s] = ((in >> s) & 1u) ? EntryCut{cnt, ce, tc} : none;
+    }
+    // fold out[] (a child's result) into the node on top of the stack
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+      EntryCut &a = acc[sp][s];
+      if (out[s].count != 0u) {
+        if (a.count != 0u) a = EntryCut{a.count + out[s].count, node[sp], fmin(a.t_near, out[s].t_near)};
+        else a = out[s];
       }
     }
-    // fold `done` (a child's result) into the node on top of the stack
-    EntryCut &a = acc[sp];
-    if (done.count != 0u) {
-      if (a.count != 0u) a = EntryCut{a.count + done.count, node[sp], fmin(a.t_near, done.t_near)};
-      else a = done;
-    }
   }
-  return done;
 }
 
-// One thread per pixel of the rows this call renders: out[pr * W + px] (the kernels' shard-local pixel index)
-__global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(RtiowParams P, const float *leaf_boxes, const double *leaf_balls, uint32_t max_entries, uint32_t *out) {
-  const uint32_t W = P.cam.image_width;
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (uint64_t)P.nrows * W) return;
-  const uint32_t pr = (uint32_t)(i / W), px = (uint32_t)(i - (uint64_t)pr * W);
-  const uint32_t y = P.row_first + pr * P.row_step;
-  const rl_rtiow_camera &cam = P.cam;
-  PixelBeam B;
+// The beam of pixel (px, y) of the camera's frame.  False when a radius of the sphere test came out NaN: the box-only cut then.
+__device__ __forceinline__ bool pixel_beam(const rl_rtiow_camera &cam, uint32_t px, uint32_t y, PixelBeam &B) {
+  const uint32_t W = cam.image_width;
   double M = 0.0, len2 = 0.0, uu = 0.0, vv = 0.0, uv = 0.0, dp2 = 0.0, dm2 = 0.0;
   const bool lens = !(cam.defocus_angle <= 0.0);  // (NaN: GEN takes the disc branch too)
 #pragma unroll
@@ -208,45 +262,84 @@ __global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(
   B.inv_len = 1.0 / sqrt(len2);
   B.rho_o = lens ? sqrt(0.5 * ((uu + vv) + sqrt((uu - vv) * (uu - vv) + 4.0 * uv * uv))) * (1.0 + 0x1.0p-40) : 0.0;
   B.rho_t = 0.5 * sqrt(fmax(dp2, dm2)) * (1.0 + 0x1.0p-40);
-  if (!(B.rho_o >= 0.0) || !(B.rho_t >= 0.0)) leaf_balls = nullptr;  // NaN: the box-only cut
   B.delta = M * 0x1.0p-40;
   if (!(M >= 0.0)) B.delta = __longlong_as_double(0x7FF0000000000000ll);  // NaN
+  return B.rho_o >= 0.0 && B.rho_t >= 0.0;
+}
+
+// One thread per pixel of the rows this call renders: out[pr * W + px] (the kernels' shard-local pixel index), the all-times word, and with
+// NS = T + 1 > 1 the words of the T time slices beside it, out_t[(pr * W + px) * T + k].  NS = 1 is the kernel of the one-word table.
+template <int NS>
+__global__ void RL_KERNEL_ALIGN __launch_bounds__(256) rtiow_pixel_entry_kernel(RtiowParams P, const float *leaf_boxes, const double *leaf_balls, const double *leaf_motion,
+                                                                                uint32_t max_entries, uint32_t *out, uint32_t *out_t) {
+  const uint32_t W = P.cam.image_width;
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (uint64_t)P.nrows * W) return;
+  const uint32_t pr = (uint32_t)(i / W), px = (uint32_t)(i - (uint64_t)pr * W);
+  const uint32_t y = P.row_first + pr * P.row_step;
+  PixelBeam B;
+  if (!pixel_beam(P.cam, px, y, B)) leaf_balls = nullptr;  // NaN: the box-only cut
+  constexpr uint32_t ALL = (1u << NS) - 1u;
   // the root: a leaf of its own (one sphere, no node) is tested against its leaf box, an inner node is walked
   const uint32_t root = P.fast_root;
-  EntryCut c[3];
+  EntryCut c[3][NS];
   uint32_t nc = 1;
   if (root >= P.n_fast_inner) {
     double t0;
-    const bool hit = beam_touches_leaf(B, leaf_boxes + (size_t)(root - P.n_fast_inner) * 8, leaf_balls, root - P.n_fast_inner, t0);
-    c[0] = hit ? EntryCut{1u, root, t0} : EntryCut{0u, FAST_NONE, 0.0};
-  } else c[0] = reduce_subtree(P, B, leaf_balls, root, 0.0);
-  // split the holder of several leaves into its children's reduced entries, the one with the most leaves first, up to max_entries
+    const uint32_t in = beam_leaf_tables<NS>(B, leaf_boxes + (size_t)(root - P.n_fast_inner) * 8, leaf_balls, leaf_motion, root - P.n_fast_inner, ALL, t0);
+#pragma unroll
+    for (int s = 0; s < NS; s++) c[0][s] = ((in >> s) & 1u) ? EntryCut{1u, root, t0} : EntryCut{0u, FAST_NONE, 0.0};
+  } else reduce_subtree<NS>(P, B, leaf_balls, leaf_motion, root, 0.0, ALL, c[0]);
+  // split the holder of several leaves into its children's reduced entries, the one with the most leaves first, up to max_entries.  The
+  // all-times table (c[.][0]) decides which holder is split; a slice takes its own reduction of the same child subtrees, out of the same walk,
+  // so its entries lie inside the all-times entries: fewer leaves below them, never other ones.
   while (nc < max_entries && nc < 3u) {
     uint32_t pick = 3u, best = 1u;
     for (uint32_t k = 0; k < nc; k++)
-      if (c[k].entry < P.n_fast_inner && c[k].count > best) pick = k, best = c[k].count;
+      if (c[k][0].entry < P.n_fast_inner && c[k][0].count > best) pick = k, best = c[k][0].count;
     if (pick == 3u) break;
-    const FastNode &nd = P.fast_nodes[c[pick].entry];
+    const FastNode &nd = P.fast_nodes[c[pick][0].entry];
     double ta, tb;
     // (a holder of several leaves has them on both sides: both boxes are touched, both reductions count at least one, and a child that is
     // a leaf itself is one the reduction accepted)
     const bool ha = beam_touches(B, nd.box[0], ta), hb = beam_touches(B, nd.box[1], tb);
     if (!(ha && hb)) break;
-    const EntryCut ra = reduce_subtree(P, B, leaf_balls, nd.child & 0xFFFFu, ta), rb = reduce_subtree(P, B, leaf_balls, nd.child >> 16, tb);
-    if (ra.count == 0u || rb.count == 0u) break;
-    c[pick] = ra, c[nc++] = rb;
-  }
-  // nearest first (at most three: a sorting network)
-  auto order = [&](uint32_t a, uint32_t b) {
-    if (b < nc && c[b].t_near < c[a].t_near) {
-      const EntryCut t = c[a];
-      c[a] = c[b], c[b] = t;
+    // a slice whose own cut of this holder's subtree is a node below it has its leaves on one side; a child that is a leaf counts for the slices
+    // that hold it: both are what the walk's leaf tests say again
+    EntryCut ra[NS], rb[NS];
+    const uint32_t ea = nd.child & 0xFFFFu, eb = nd.child >> 16;
+    uint32_t wa = ALL, wb = ALL;
+    if (NS > 1) {  // a leaf child: which slices hold it (the walk above tested it; the same test, the same answer)
+      double tt;
+      if (ea >= P.n_fast_inner) wa = beam_leaf_tables<NS>(B, nd.box[0], leaf_balls, leaf_motion, ea - P.n_fast_inner, ALL, tt) | 1u;
+      if (eb >= P.n_fast_inner) wb = beam_leaf_tables<NS>(B, nd.box[1], leaf_balls, leaf_motion, eb - P.n_fast_inner, ALL, tt) | 1u;
     }
-  };
-  order(0, 1), order(1, 2), order(0, 1);
-  uint32_t w = 3u << 30;
-  for (uint32_t k = 0; k < 3u; k++) w |= (k < nc && c[k].count != 0u ? c[k].entry : FAST_NONE) << (10u * k);
-  out[i] = w;
+    reduce_subtree<NS>(P, B, leaf_balls, leaf_motion, ea, ta, wa, ra);
+    reduce_subtree<NS>(P, B, leaf_balls, leaf_motion, eb, tb, wb, rb);
+    if (ra[0].count == 0u || rb[0].count == 0u) break;
+#pragma unroll
+    for (int s = 0; s < NS; s++) c[pick][s] = ra[s], c[nc][s] = rb[s];
+    nc++;
+  }
+#pragma unroll
+  for (int s = 0; s < NS; s++) {
+    // the table's own cuts (a slice may hold none of an all-times entry's leaves), nearest first (at most three: a sorting network)
+    EntryCut v[3];
+    uint32_t m = 0;
+    for (uint32_t k = 0; k < nc; k++)
+      if (c[k][s].count != 0u) v[m++] = c[k][s];
+    auto order = [&](uint32_t a, uint32_t b) {
+      if (b < m && v[b].t_near < v[a].t_near) {
+        const EntryCut t = v[a];
+        v[a] = v[b], v[b] = t;
+      }
+    };
+    order(0, 1), order(1, 2), order(0, 1);
+    uint32_t w = 3u << 30;
+    for (uint32_t k = 0; k < 3u; k++) w |= (k < m ? v[k].entry : FAST_NONE) << (10u * k);
+    if (s == 0) out[i] = w;
+    else out_t[i * (uint64_t)(NS - 1) + (uint32_t)(s - 1)] = w;
+  }
 }
 
 }  // namespace rl

@@ -151,8 +151,9 @@ double guard_pad(const GuardFrame &f, double radius);  // how far outside a sphe
 // degenerate spheres, spheres referenced more than once or not at all...).  root_entry: entry id a new ray starts at.
 bool build_fast_bvh(const rl_rtiow_scene_desc &d, const RtiowProgram &rt, const GuardFrame &f, std::vector<FastNode> &nodes, uint32_t &root_entry);
 // For a scene build_fast_bvh accepted: per sphere {c.x, c.y, c.z, R}, a ball that holds the sphere grown by its leaf box's pad at every time
-// in [0, 1] (the per-pixel entry table's sphere test, rl_pixel_entry.h)
-void fast_leaf_balls(const rl_rtiow_scene_desc &d, const GuardFrame &f, std::vector<double> &balls);
+// in [0, 1] (the per-pixel entry table's sphere test, rl_pixel_entry.h), and per sphere {dc.x, dc.y, dc.z, |dc| / 2}, from which the table's
+// time slices shrink that ball.  False when a value of either is not finite (the table then keeps to one slice).
+bool fast_leaf_balls(const rl_rtiow_scene_desc &d, const GuardFrame &f, std::vector<double> &balls, std::vector<double> &motion);
 
 // ---- fast traversal structure for GENERAL scenes (planars, instances, any number of primitives; rl_fast_bvh.cpp, rl_rtiow_fastgen.h):
 // a surface-area-heuristic binary tree in WORLD space over the primitive OCCURRENCES of the threaded program (a primitive under a

@@ -66,6 +66,8 @@ struct Switches {
   size_t indep_cap = (size_t)1 << 30;  // RL_INDEP_CAP_MB=<MiB>: cap of that mode's pass buffer (a smaller one forces more passes: tests)
   int pixel_entry = rl::PIXEL_ENTRY_DEFAULT;  // RL_PIXEL_ENTRY=0|1|2|3: the fast kernel's camera rays start at the root / at their pixel's entry cut of up to n entries (rl_pixel_entry.h)
   bool pixel_entry_sphere = true;  // RL_PIXEL_ENTRY_SPHERE=0: that cut keeps every leaf whose BOX the pixel's beam touches; default: only those whose sphere it may touch
+  int pixel_entry_time = rl::PIXEL_ENTRY_TIME_DEFAULT;  // RL_PIXEL_ENTRY_TIME=1|2|4|8: time slices of that table, a word per pixel and slice (1: the one word for all times)
+  bool pixel_entry_reuse = true;   // RL_PIXEL_ENTRY_REUSE=0: every call builds the table; default: a call that repeats the last build's camera, rows and switches reads it as it is
   bool coop_quad = true;         // RL_COOP_QUAD=0: the wave kernels' block passes lane-per-block only and FILL per lane (default: thin passes four lanes to a block, FILL wave-wide)
 } g_sw;
 std::atomic<unsigned long long> g_last_slow_traces{0};  // rl_debug_slow_traces.  Atomic: rl_render_status of two scenes runs under two locks.
@@ -107,6 +109,8 @@ void read_switches() {
   if (const char *v = std::getenv("RL_INDEP_K")) w.indep_k = (unsigned)std::max(1, std::atoi(v));
   if (const char *v = std::getenv("RL_PIXEL_ENTRY")) w.pixel_entry = std::min(3, std::max(0, std::atoi(v)));
   if (const char *v = std::getenv("RL_PIXEL_ENTRY_SPHERE")) w.pixel_entry_sphere = std::string(v) != "0";
+  if (const char *v = std::getenv("RL_PIXEL_ENTRY_TIME")) w.pixel_entry_time = rl::pixel_entry_slices(std::atoi(v));
+  if (const char *v = std::getenv("RL_PIXEL_ENTRY_REUSE")) w.pixel_entry_reuse = std::string(v) != "0";
   if (const char *v = std::getenv("RL_COOP_QUAD")) w.coop_quad = std::string(v) != "0";
   if (const char *v = std::getenv("RL_INDEP_CAP_MB")) w.indep_cap = (size_t)std::max(1, std::atoi(v)) << 20;
   g_sw = w;
@@ -323,7 +327,7 @@ static rl_scene *upload_rtiow(const std::shared_ptr<const HostRtiow> &H, int ctx
       (!H->lops.empty() && ((rc = s->d_lops.upload(H->lops)) || (rc = s->d_sphere_flat.upload(H->sphere_flat)) || (rc = s->d_sphere_checker.upload(H->sphere_checker)))) ||
       (!H->cops.empty() && ((rc = s->d_cops.upload(H->cops)) || (rc = s->d_movbits.upload(H->movbits)))) ||
       (H->fast_root != FAST_NONE && ((rc = s->d_fast_nodes.upload(H->fast_nodes)) || (rc = s->d_fast_nodes_ch.upload(H->fast_nodes_ch)) || (rc = s->d_fast_leaf_boxes.upload(H->fast_leaf_boxes)) ||
-                                      (rc = s->d_fast_leaf_balls.upload(H->fast_leaf_balls)))) ||
+                                      (rc = s->d_fast_leaf_balls.upload(H->fast_leaf_balls)) || (rc = s->d_fast_leaf_motion.upload(H->fast_leaf_motion)))) ||
       (QF.ok && ((rc = s->d_fg_nodes.upload(QF.qnodes)) || (rc = s->d_fg_seg_roots.upload(QF.stage_roots)) ||
                  (rc = s->d_fg_media.upload(QF.media)) || (rc = s->d_fg_items.upload(QF.items)) || (rc = s->d_fg_spheres.upload(QF.item_spheres)) || (rc = s->d_fg_material.upload(QF.item_material))))) {
     destroy_one(s);
@@ -556,17 +560,53 @@ static void route_adaptive_variant(RtiowChoice &choice, const rl_rtiow_camera *c
 }
 
 // Variant 1029 only: the per-pixel entry table of this render's camera and rows (rl_pixel_entry.h), built on `stream` ahead of the render
-// kernels into the scene's own buffer (grown on demand, like d_pos).  Nothing is kept from call to call: the camera may differ.
+// kernels into the scene's own buffers (grown on demand, like d_pos): the one-word table, and with T = g_sw.pixel_entry_time > 1 slices the
+// [pixel][T] table beside it, out of the same walk.  One slice for the whole call where the slices' rounding argument has nothing to stand
+// on (a motion value that is not finite), without the sphere test (the slices are a sphere test), and where the sliced table would pass 256 MB.
+// The tables depend on the scene and on the key below only — progressive passes, adaptive loops and denoise_render repeat all of it call
+// after call — so a call that repeats the key of the last build launches nothing (RL_PIXEL_ENTRY_REUSE=0: every call builds).
+std::atomic<unsigned long long> g_pixel_entry_builds{0};  // rl_debug_pixel_entry_builds: table kernels launched by this process
 static int build_pixel_entry(const rl_scene *scene, RtiowParams &P, uint32_t nrows, hipStream_t stream) {
-  P.pixel_entry = nullptr;
+  P.pixel_entry = nullptr, P.pixel_entry_t = nullptr, P.pixel_entry_log2t = 0;
   const size_t npix = (size_t)nrows * P.cam.image_width;
   if (g_sw.pixel_entry <= 0 || npix == 0) return RL_OK;
   rl_scene *ms = const_cast<rl_scene *>(scene);  // work buffers only
+  uint32_t T = (uint32_t)g_sw.pixel_entry_time;
+  if (!g_sw.pixel_entry_sphere || !scene->hrt->fast_motion_finite || npix * T * sizeof(uint32_t) > ((size_t)256 << 20)) T = 1;
+  rl_scene::PixelEntryKey key;
+  std::memset(&key, 0, sizeof key);  // (padding too: the keys are compared as bytes)
+  const rl_rtiow_camera &c = P.cam;
+  key.image_width = c.image_width, key.image_height = c.image_height, key.defocus_angle = c.defocus_angle;
+  std::memcpy(key.lookfrom, c.lookfrom, sizeof key.lookfrom), std::memcpy(key.pixel_00, c.pixel_00, sizeof key.pixel_00);
+  std::memcpy(key.pixel_du, c.pixel_du, sizeof key.pixel_du), std::memcpy(key.pixel_dv, c.pixel_dv, sizeof key.pixel_dv);
+  std::memcpy(key.defocus_disk_u, c.defocus_disk_u, sizeof key.defocus_disk_u), std::memcpy(key.defocus_disk_v, c.defocus_disk_v, sizeof key.defocus_disk_v);
+  key.row_first = P.row_first, key.row_step = P.row_step, key.nrows = nrows;
+  key.max_entries = (uint32_t)g_sw.pixel_entry, key.sphere = g_sw.pixel_entry_sphere ? 1u : 0u, key.slices = T;
+  // (a buffer that has to grow is a new allocation: whatever was built is gone with the old one)
+  if (ms->d_pixel_entry.size() < npix || (T > 1 && ms->d_pixel_entry_t.size() < npix * T)) ms->entry_key_valid = false;
   HIP_TRY(ms->d_pixel_entry.reserve(npix));
-  hipLaunchKernelGGL(rtiow_pixel_entry_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, P, (const float *)scene->d_fast_leaf_boxes,
-                     g_sw.pixel_entry_sphere ? (const double *)scene->d_fast_leaf_balls : (const double *)nullptr, (uint32_t)g_sw.pixel_entry, ms->d_pixel_entry);
-  HIP_TRY(hipGetLastError());
+  if (T > 1) HIP_TRY(ms->d_pixel_entry_t.reserve(npix * T));
+  HIP_TRY(ms->ev_entry.create(hipEventDisableTiming));
+  if (g_sw.pixel_entry_reuse && ms->entry_key_valid && std::memcmp(&key, &ms->entry_key, sizeof key) == 0) {
+    if (ms->entry_stream != stream) HIP_TRY(hipStreamWaitEvent(stream, ms->ev_entry, 0));  // built on another stream: behind that build
+  } else {
+    ms->entry_key_valid = false;
+    const dim3 grid((unsigned)((npix + 255) / 256)), block(256);
+    const float *boxes = scene->d_fast_leaf_boxes;
+    const double *balls = g_sw.pixel_entry_sphere ? (const double *)scene->d_fast_leaf_balls : (const double *)nullptr, *motion = scene->d_fast_leaf_motion;
+    const uint32_t me = (uint32_t)g_sw.pixel_entry;
+    uint32_t *one = ms->d_pixel_entry, *sliced = T > 1 ? (uint32_t *)ms->d_pixel_entry_t : nullptr;
+    if (T == 8) hipLaunchKernelGGL(rtiow_pixel_entry_kernel<9>, grid, block, 0, stream, P, boxes, balls, motion, me, one, sliced);
+    else if (T == 4) hipLaunchKernelGGL(rtiow_pixel_entry_kernel<5>, grid, block, 0, stream, P, boxes, balls, motion, me, one, sliced);
+    else if (T == 2) hipLaunchKernelGGL(rtiow_pixel_entry_kernel<3>, grid, block, 0, stream, P, boxes, balls, motion, me, one, sliced);
+    else hipLaunchKernelGGL(rtiow_pixel_entry_kernel<1>, grid, block, 0, stream, P, boxes, balls, motion, me, one, sliced);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ms->ev_entry, stream));
+    g_pixel_entry_builds++;
+    ms->entry_key = key, ms->entry_key_valid = true, ms->entry_stream = stream;
+  }
   P.pixel_entry = ms->d_pixel_entry;
+  if (T > 1) P.pixel_entry_t = ms->d_pixel_entry_t, P.pixel_entry_log2t = T == 8 ? 3u : T == 4 ? 2u : 1u;
   return RL_OK;
 }
 
@@ -623,6 +663,11 @@ int rtiow_render_launch(const rl_scene *scene, const rl_rtiow_camera *cam, uint6
   if (variant == 1029) {
     int rce = build_pixel_entry(scene, P, nrows, stream);
     if (rce != RL_OK) return rce;
+    if (want_stats) {  // the instrumented kernel (verify build, tools/sched.py) repeats the table's tests on the visits it counts as wasted
+      CensusTables ct{nullptr, nullptr, nullptr, *cam};
+      if (P.pixel_entry) ct = CensusTables{scene->d_fast_leaf_boxes, scene->d_fast_leaf_balls, scene->d_fast_leaf_motion, *cam};
+      HIP_TRY(hipMemcpyToSymbol(HIP_SYMBOL(rl::g_census), &ct, sizeof ct));  // (a tool's path: the blocking copy)
+    }
   }
   bool steal = false;  // set for the resume launch of a small shard (variant 1029)
   const Mode mode = moments ? Mode::MOMENTS : Mode::FRAME;
@@ -1093,6 +1138,29 @@ void rl_debug_set_indep_cap(unsigned long long bytes) { g_sw.indep_cap = bytes ?
 void rl_debug_set_indep_k(unsigned k) { g_sw.indep_k = k ? k : 1u; }  // samples of one pixel per claim in the sample-parallel mode
 void rl_debug_set_pixel_entry(int max_entries) { g_sw.pixel_entry = std::min(3, std::max(0, max_entries)); }  // 0: camera rays start at the root (A/B, tests)
 void rl_debug_set_pixel_entry_sphere(int on) { g_sw.pixel_entry_sphere = on != 0; }  // 0: the box-only cut (A/B, tests)
+void rl_debug_set_pixel_entry_time(int slices) { g_sw.pixel_entry_time = rl::pixel_entry_slices(slices); }  // 1, 2, 4 or 8 (anything else: the default); 1: one word per pixel
+void rl_debug_set_pixel_entry_reuse(int on) { g_sw.pixel_entry_reuse = on != 0; }  // 0: every call builds its table
+// Tests: how many table kernels this process has launched (the launch log lists the render kernels only); a call that reuses the table adds none
+unsigned long long rl_debug_pixel_entry_builds(void) { return g_pixel_entry_builds.load(); }
+// Tests: the sliced table of the scene's most recent fast-traversal render, n_pixels * slices words as [pixel][slice]; returns RL_E_INVALID when that render had one slice
+int rl_debug_pixel_entry_time_read(const rl_scene *scene, uint32_t *out, uint64_t n_pixels, uint32_t slices) {
+  if (!scene || !out || !scene->d_pixel_entry_t || !scene->entry_key_valid || scene->entry_key.slices != slices || slices < 2 ||
+      n_pixels * slices > scene->d_pixel_entry_t.size())
+    return RL_E_INVALID;
+  DevCtx *c;
+  int rc0 = scene_context(scene, c);
+  if (rc0 != RL_OK) return rc0;
+  HIP_TRY(hipMemcpy(out, scene->d_pixel_entry_t, n_pixels * slices * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return RL_OK;
+}
+// Tools (tools/sched.py): the census of the instrumented fast kernel's last launch, 6 x u64: camera LEAF visits that ended at disc < 0 on a moving
+// sphere; those of them / of the ones on stationary spheres whose leaf the all-times table holds for the pixel; of the moving ones the table
+// holds, those the ball of the sample's time slice leaves out, for 2, 4 and 8 slices
+int rl_debug_pixel_entry_census(const rl_scene *scene, unsigned long long *out6) {
+  if (!scene || !out6) return RL_E_INVALID;
+  HIP_TRY(hipMemcpy(out6, scene->d_scratch + 128 + 31 * 8, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  return RL_OK;
+}
 // Tests: the entry table of the scene's most recent fast-traversal render (n_pixels words, rows x W of the shard rendered), after that render has finished
 int rl_debug_pixel_entry_read(const rl_scene *scene, uint32_t *out, uint64_t n_pixels) {
   if (!scene || !out || !scene->d_pixel_entry || n_pixels > scene->d_pixel_entry.size()) return RL_E_INVALID;
@@ -1140,7 +1208,8 @@ void rl_debug_live_buffers(unsigned long long out[2]) { out[0] = rl::g_live_buff
 
 // Not part of the ABI (tools only): scheduler occupancy counters of the last STATS launch, 32 x u64 ([3s .. 3s+2] per state; [24]: the
 // fast kernel's skipped self tests, rl_rtiow_wave.h fast_self_miss; [25 .. 28]: the camera rays' TRAV lane-steps, LEAF visits, number, and
-// LEAF visits that ended at disc < 0; [29]: the scheduling decisions that chose TRAV — [3] counts its steps).
+// LEAF visits that ended at disc < 0; [29]: the scheduling decisions that chose TRAV — [3] counts its steps; [31]: those of [28] on a moving
+// sphere, the first word of rl_debug_pixel_entry_census).
 int rl_debug_sched(const rl_scene *scene, unsigned long long *out32) {
   if (!scene || !out32) return RL_E_INVALID;
   HIP_TRY(hipMemcpy(out32, scene->d_scratch + 128, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));

@@ -108,6 +108,10 @@ struct RtiowParams {
   // wave kernels' SHADE: beside sphere_flat, one 32-byte record per sphere — the odd colour and inv_scale of a Checker of two Solid colours
   // (MAT_TEX_CHECKER; zeros otherwise), fetched by sphere index in the same round trip as the flattened material
   const DevChecker *sphere_checker;
+  // fast traversal: the entry words by time slice, [nrows * W][1 << pixel_entry_log2t] (rl_pixel_entry.h, time slices): a camera ray takes the
+  // word of its pixel and of the slice its time falls into.  Null: the one word of pixel_entry.
+  const uint32_t *pixel_entry_t;
+  uint32_t pixel_entry_log2t;
 };
 
 // MOMENTS, the compile-time flavour of the chained render kernels that keeps second moments (P.out_sq), is `false` in every kernel without

@@ -24,6 +24,7 @@
 
 #include "rl_rtiow_kernel.h"
 #include "rl_rtiow_adaptive.h"  // the adaptive renders' stopping rule, the one statement
+#include "rl_pixel_entry.h"     // time_slice: which of its pixel's entry words a camera ray takes; the instrumented kernel's census repeats the table's tests
 
 namespace rl {
 
@@ -543,6 +544,33 @@ __device__ __forceinline__ uint32_t fast_slow_trace(const DevOp *ops, const DevS
   }
   closest = h.t, hit_prim = h.prim;
   return flags;
+}
+
+// The instrumented fast kernel's census of wasted LEAF visits (tools/sched.py; the STATS instantiation, verify build) repeats the entry table's
+// tests on the visits it counts: leaf boxes, balls and motion as the table kernel reads them, set by the host ahead of such a launch (all null
+// otherwise: no census).  A device symbol, not kernel arguments: nothing a product kernel receives is for the tool alone.
+struct CensusTables {
+  const float *boxes;
+  const double *balls, *motion;
+  rl_rtiow_camera cam;  // the launch's camera: the census builds the pixel's beam from here
+};
+__device__ CensusTables g_census;
+// What the entry table says of sphere `sidx` for pixel (px, y) and a sample at `time` (rl_pixel_entry.h, the same tests): bit 0 the leaf is in
+// the all-times table's leaf set (else it only lies below one of its entries); bit 1 + i, for a moving sphere in that set, the ball of the
+// sample's slice of 2 << i leaves it out.  (Inlined: out of line the instrumented kernel spills more, 292 VGPRs against 233.)
+__device__ __forceinline__ uint32_t census_leaf(uint32_t px, uint32_t y, uint32_t sidx, double time, bool moving) {
+  PixelBeam B;
+  double t_lo, t_hi;
+  const bool sph = pixel_beam(g_census.cam, px, y, B);
+  const double *ball = g_census.balls + (size_t)sidx * 4;
+  if (!beam_touches(B, g_census.boxes + (size_t)sidx * 8, t_lo, t_hi) || (sph && !beam_may_touch_ball(B, ball, t_lo, t_hi))) return 0u;
+  uint32_t r = 1u;
+  for (uint32_t lg = 1; lg <= 3u; lg++) {
+    double sb[4];
+    slice_ball(ball, g_census.motion + (size_t)sidx * 4, time_slice(time, lg), 1u << lg, sb);
+    if (moving && sph && !beam_may_touch_ball(B, sb, t_lo, t_hi)) r |= 1u << lg;
+  }
+  return r;
 }
 
 #ifdef RL_FASTG_VERIFY  // debug build (make verify, tools/verify_fastg.py): every ray of the fast kernels is ALSO traced in the reference's order

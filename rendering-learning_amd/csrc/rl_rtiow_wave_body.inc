@@ -104,6 +104,9 @@
   // STATS census (tools/sched.py): the camera rays' share — a camera ray is the one whose remaining depth is still cam.max_depth
   // c_cam_miss: those of their LEAF visits that return at the discriminant test (disc < 0) — a sphere whose box the ray passed but not the sphere
   unsigned long long c_cam_trav = 0, c_cam_leaf = 0, c_cam_rays = 0, c_cam_miss = 0;
+  // ... split: on a moving sphere; on a moving / a stationary sphere that the all-times entry table holds for the pixel (the others lie below an
+  // entry without being in its leaf set); and of the moving ones in the table, those the ball of the sample's time slice excludes, T = 2, 4, 8
+  unsigned long long c_cam_miss_mov = 0, c_cam_miss_mov_tab = 0, c_cam_miss_sta_tab = 0, c_cam_miss_cut[3] = {0, 0, 0};
 
   // fast traversal (LDS_SCENE = 4): 16 ten-bit entry ids in five registers, newest in the low bits of stk0; all ones = empty
   uint32_t stk0 = ~0u, stk1 = ~0u, stk2 = ~0u, stk3 = ~0u, stk4 = ~0u;
@@ -490,7 +493,20 @@
             if (STATS) c_sph++;
             if (STATS && (depth & DEPTH_MASK) == cam.max_depth) {
               c_cam_leaf++;
-              if (fast_sphere_misses(spheres[sidx], payload, o, d, time)) c_cam_miss++;
+              if (fast_sphere_misses(spheres[sidx], payload, o, d, time)) {
+                c_cam_miss++;
+                const bool moving = (payload & SPH_MOVING) != 0u;
+                if (moving) c_cam_miss_mov++;
+                // what the entry table says of this leaf for this pixel, and whether the ball of the sample's time slice would have left it out
+                if (g_census.boxes) {
+                  const uint32_t ct = census_leaf(px, P.row_first + pr * P.row_step, sidx, time, moving);
+                  if (ct & 1u) {
+                    if (moving) c_cam_miss_mov_tab++;
+                    else c_cam_miss_sta_tab++;
+                  }
+                  c_cam_miss_cut[0] += (ct >> 1) & 1u, c_cam_miss_cut[1] += (ct >> 2) & 1u, c_cam_miss_cut[2] += (ct >> 3) & 1u;
+                }
+              }
             }
             if (SPLIT_LEAF) {
               if (fast_sphere_misses(spheres[sidx], payload, o, d, time)) fast_go(fast_pop());
@@ -696,7 +712,10 @@
           o = (ld3(cam.lookfrom) + ld3(cam.defocus_disk_u) * a) + ld3(cam.defocus_disk_v) * b;
         }
         d = pixel_sample - o;
-        time = rng.gen_f64();
+        // (gen_f64, spelled out: the draw's high word also names the time slice of the pixel's entry word below)
+        const uint64_t time_bits = rng.next_u64();
+        const uint32_t time_hi = (uint32_t)(time_bits >> 32);
+        time = (double)(time_bits >> 11) * 0x1.0p-53;
         thr = d3(1.0, 1.0, 1.0);
         depth = LDS_SCENE == 4 ? cam.max_depth | (FAST_NONE << 22) : cam.max_depth;  // a camera ray has no sphere of its own
         if (cam.max_depth == 0) {  // ray_color(depth 0) = black: the sample contributes (0,0,0)
@@ -708,7 +727,17 @@
           if (STATS) c_cam_rays++;
           // the pixel's entry word: read and used up here, and not loaded ahead of the block pass above: held across it, the word makes GEN's pick
           // path longer (382 -> 408 instructions) and the stealing instantiation spill 109 SGPRs instead of 97
-          start_ray(LDS_SCENE == 4 && P.pixel_entry ? P.pixel_entry[(size_t)pr * W + px] : fast_root_word);
+          // With time slices (P.pixel_entry_t; null: the one word of P.pixel_entry) the word is the one of the slice `time` falls into, k =
+          // floor(time T), taken from the draw's high word: the index instructions are all it adds, and one load serves both tables (table and
+          // shift are scalar selects).  Measured: with k = (uint32_t)(time * T) the headline kernel takes 120 VGPRs instead of 118.  A frame has
+          // fewer than 2^32 pixels and the sliced table at most 2^26 words (rl_render.hip build_pixel_entry): the index is formed in 32 bits.
+          uint32_t word = fast_root_word;
+          if (LDS_SCENE == 4 && P.pixel_entry) {
+            const uint32_t *tab = P.pixel_entry_t ? P.pixel_entry_t : P.pixel_entry;
+            const uint32_t lg = P.pixel_entry_t ? P.pixel_entry_log2t : 0u;
+            word = tab[((pr * W + px) << lg) + time_slice_bits(time_hi, lg)];
+          }
+          start_ray(word);
         }
       }
       RL_CG_MARK("GEN_E");
@@ -768,5 +797,16 @@
       if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 27], v);
       v = wave_sum(c_cam_miss);  // out[28]
       if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 28], v);
+      v = wave_sum(c_cam_miss_mov);  // out[31]; rl_debug_pixel_entry_census: [0] this one, [1] .. [5] the ones below
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 31], v);
+      v = wave_sum(c_cam_miss_mov_tab);
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 32], v);
+      v = wave_sum(c_cam_miss_sta_tab);
+      if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 33], v);
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        v = wave_sum(c_cam_miss_cut[k]);
+        if ((tid & 63) == 0) atomicAdd(&P.stats[8 + 34 + k], v);
+      }
     }
   }

@@ -44,7 +44,7 @@ struct rl_scene {
   rl::DevBuf<rl::FastNode> d_fast_nodes;
   rl::DevBuf<rl::FastNodeCH> d_fast_nodes_ch;
   rl::DevBuf<float> d_fast_leaf_boxes;
-  rl::DevBuf<double> d_fast_leaf_balls;
+  rl::DevBuf<double> d_fast_leaf_balls, d_fast_leaf_motion;
   rl::DevBuf<uint32_t> d_coop_pixels;  // cooperative kernel: pixel list (scratch, grown on demand)
   rl::DevBuf<uint32_t> d_steal_state, d_steal_n;  // work stealing on small shards (RtiowParams::steal_state)
   rl::DevBuf<rl::FastNodeQ> d_fg_nodes;
@@ -98,6 +98,17 @@ struct rl_scene {
   rl::DevBuf<uint32_t> d_pos, d_tile_cost, d_tile_order, d_tile_keys, d_tile_iota;
   rl::DevBuf<unsigned char> d_sort_temp;
   rl::DevBuf<uint32_t> d_pixel_entry;  // fast traversal: the current render's per-pixel entry words (rl_pixel_entry.h), grown on demand
+  rl::DevBuf<uint32_t> d_pixel_entry_t;  // ... and its words by time slice, [pixel][T], grown on demand
+  // What the two tables were last built from (rl_render.hip build_pixel_entry): a call that repeats all of it reads them as they are.  The event
+  // follows the build, so that a call on another stream waits for it; entry_key_valid is false until a build and after a buffer was regrown.
+  struct PixelEntryKey {
+    uint32_t image_width, image_height;
+    double lookfrom[3], pixel_00[3], pixel_du[3], pixel_dv[3], defocus_disk_u[3], defocus_disk_v[3], defocus_angle;
+    uint32_t row_first, row_step, nrows, max_entries, sphere, slices;
+  } entry_key;
+  bool entry_key_valid = false;
+  rl::Event ev_entry;
+  hipStream_t entry_stream = nullptr;
   // multi-GPU: this replica's row shard / on replica 0 the gather buffer [G][max_rows][W][3]
   rl::DevBuf<double> d_shard;
   rl::Event ev_gather_read;  // replica 0: recorded behind the de-interleave kernel that reads the gather slots
@@ -113,7 +124,9 @@ struct rl_scene {
   unsigned params_slot = 0;
   rl::DevBuf<uint32_t> d_pix_rays;  // debug (tools/): per-pixel ray counts of the last counting render
   rl::DevBuf<double> d_indep;       // sample-parallel mode: the pass buffer [samples of a pass][shard pixels][3] (rl_rtiow_render_independent*)
-  // per-scene scratch: [0] work counter (u32), [64..] 8 x u64 stats, [128..] scheduler debug counters.  Declared LAST, so released FIRST:
+  // per-scene scratch, 512 bytes: [0] work counter (u32), [64..] 8 x u64 stats, [128..384) the 32 scheduler debug words of rl_debug_sched
+  // (word 31, byte 376: the first census word), [384..424) the other five census words of rl_debug_pixel_entry_census; [256] is also the
+  // cooperative / stealing counter, which no counting launch uses.  Declared LAST, so released FIRST:
   // every scene has it, and its hipFree waits for the device's work in flight before the events and the pinned memory above go.
   rl::DevBuf<unsigned char> d_scratch;
 };

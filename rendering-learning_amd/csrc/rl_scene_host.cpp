@@ -191,7 +191,7 @@ static int build_host_rtiow_may_throw(const rl_rtiow_scene_desc *desc, std::shar
           const uint32_t e = k == 0 ? (nd.child & 0xFFFFu) : (nd.child >> 16);
           if (e >= n_inner && e - n_inner < ns) std::memcpy(&H->fast_leaf_boxes[(size_t)(e - n_inner) * 8], nd.box[k], 6 * sizeof(float));
         }
-      fast_leaf_balls(*desc, frame, H->fast_leaf_balls);
+      H->fast_motion_finite = fast_leaf_balls(*desc, frame, H->fast_leaf_balls, H->fast_leaf_motion);
     }
     // ray queries walk the four-wide world-space tree on every kind of scene (rl_ray_query.h rtiow_hit_rays_fast_kernel)
     if (rt.ops.size() < (1u << 31) && !build_fast_general(*desc, rt, H->qfg)) H->qfg = FastGeneral{};

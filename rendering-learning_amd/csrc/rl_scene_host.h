@@ -25,6 +25,8 @@ struct HostRtiow {
   std::vector<FastNodeCH> fast_nodes_ch;  // fast_nodes as centre / half-extent boxes: what the wave kernels stage into LDS (fast_node_ch)
   std::vector<float> fast_leaf_boxes;  // [n_spheres][8]: each sphere's padded leaf box of the fast tree (rl_rtiow_coop.h)
   std::vector<double> fast_leaf_balls;  // [n_spheres][4]: centre and radius of a ball around each padded sphere (rl_fast_bvh.cpp fast_leaf_balls)
+  std::vector<double> fast_leaf_motion;  // [n_spheres][4]: dc and |dc| / 2 of each sphere; fast_motion_finite: every value of both arrays is finite
+  bool fast_motion_finite = false;
   FastGeneral fg;  // fast traversal structure of a general scene (fg.ok == false: the scene does not qualify)
   FastGeneral qfg;  // sphere-only scenes: the same structure for ray queries (rl_ray_query.h; the renders walk fast_nodes from LDS instead)
   const FastGeneral &query_tree() const { return fg.ok ? fg : qfg; }

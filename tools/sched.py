@@ -28,6 +28,15 @@ if out[27]:  # census of the fast kernel's camera rays (remaining depth still ma
           f"LEAF visits {out[26]} of {leaf} ({100 * out[26] / max(leaf, 1):.1f} %, {out[26] / out[27]:.3f} per camera ray)")
     # of those, the visits that end at the discriminant test: the ray passed the sphere's box, not the sphere
     print(f"camera LEAF visits with disc < 0: {out[28]} ({out[28] / out[27]:.3f} per camera ray, {100 * out[28] / max(leaf, 1):.1f} % of all LEAF visits)")
+if out[28]:  # ... split by what the sphere is and by what the entry table says of its leaf for the pixel (rl_debug_pixel_entry_census)
+    c = rl.entry_table.census(w)
+    assert c["moving"] == out[31]
+    cam_rays, miss, mov = out[27], out[28], c["moving"]
+    print(f"  of them on a moving sphere {mov} ({mov / cam_rays:.3f} per camera ray), on a stationary one {miss - mov} ({(miss - mov) / cam_rays:.3f})")
+    print(f"  leaf in the pixel's all-times table: moving {c['moving_in_table']} ({c['moving_in_table'] / cam_rays:.3f} per camera ray), "
+          f"stationary {c['static_in_table']} ({c['static_in_table'] / cam_rays:.3f}); the rest lie below an entry outside its leaf set")
+    for T, n in c["sliced_out"].items():  # what-if: the moving ones in the table that the ball of the sample's own time slice leaves out
+        print(f"  what-if T = {T}: slice ball excludes {n} ({n / cam_rays:.3f} per camera ray, {100 * n / max(mov, 1):.1f} % of the moving misses)")
 if out[29]:  # scheduling decisions that chose TRAV: what a per-pick cost (the way round the loop, tools/wave_codegen.py) weighs against the steps
     steps = out[3 * 1]
     print(f"TRAV picks {out[29]} ({steps / out[29]:.2f} steps per pick, {out[29] / st['rays']:.4f} picks per ray)")
