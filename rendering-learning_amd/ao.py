@@ -5,7 +5,7 @@ that hit and `open` counts, over the ao_rays directions (normal + random_unit_ve
 first hit, the rays that find nothing within `radius` at the camera ray's time.  Both are integers, so renders that continue each other
 (first_sample) add exactly: AmbientOcclusion.merge.
 """
-import ctypes as C
+import functools
 
 import numpy as np
 
@@ -45,46 +45,34 @@ class AmbientOcclusion:
         return AmbientOcclusion(add(self.open, other.open), add(self.hits, other.hits), self.ao_rays)
 
 
-OUTPUTS = ("open", "hits")
-
-
-def _host(want, shape):
-    want = OUTPUTS if want is None else tuple(want)
-    if not want or any(k not in OUTPUTS for k in want):
-        raise ValueError(f"want must be a non-empty subset of {OUTPUTS}")
-    a = {k: (np.zeros(shape, dtype=np.uint32) if k in want else None) for k in OUTPUTS}
-    return a, [None if a[k] is None else C.c_void_p(a[k].ctypes.data) for k in OUTPUTS]
+OUTPUTS = {"open": (np.uint32, ()), "hits": (np.uint32, ())}  # name -> (dtype, trailing shape), in the C order
+_outputs = functools.partial(api.host_outputs, OUTPUTS)
 
 
 def render_ao(camera, world, ao_rays, radius, first_sample=0, row_first=0, row_step=1, stats=None, want=None, allow_degenerate=False):
     """Compact shard rows -> AmbientOcclusion([nrows, W]).  Always a counting call (reference-order trace), as Camera.render_features."""
-    nrows = api.rows_for(camera.c.image_height, row_first, row_step)
-    a, ptrs = _host(want, (nrows, camera.c.image_width))
-    api._call(api.render_lib().rl_rtiow_render_ao_rows, world.device(), C.byref(camera.c), first_sample, row_first, row_step, int(ao_rays), float(radius),
-              *ptrs, stats=stats, counting=True, allow_degenerate=allow_degenerate)
-    return AmbientOcclusion(a["open"], a["hits"], ao_rays)
+    a = api.rows_form("rl_rtiow_render_ao_rows", camera, world, first_sample, row_first, row_step, (int(ao_rays), float(radius)), _outputs, want,
+                      stats=stats, allow_degenerate=allow_degenerate)
+    return AmbientOcclusion(*a.values(), ao_rays)
 
 
 def render_ao_device(camera, world, ao_rays, radius, stream=0, row_first=0, row_step=1, first_sample=0, stats=None, allow_degenerate=False, *, d_open=0,
                      d_hits=0):
     """Outputs stay in HBM: device pointers of nrows*W uint32 each; 0 = not wanted.  Async and counter-free unless stats is a dict."""
-    api._call(api.render_lib().rl_rtiow_render_ao_device, world.device(), C.byref(camera.c), first_sample, row_first, row_step, int(ao_rays), float(radius),
-              C.c_void_p(d_open or None), C.c_void_p(d_hits or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+    api.rows_device_form("rl_rtiow_render_ao_device", camera, world, first_sample, row_first, row_step, (int(ao_rays), float(radius)), (d_open, d_hits),
+                         stream, stats=stats, allow_degenerate=allow_degenerate)
 
 
 def render_pixels_ao(camera, world, xs, ys, ao_rays, radius, first_sample=0, stats=None, want=None, allow_degenerate=False):
     """The counts of pixels (xs[i], ys[i]), [n]: what render_ao holds at [ys[i], xs[i]].  The list rules are render_pixels_features'.
     stats (a dict): a counting call; without it the call is counter-free and may take the fast walks (api.last_query())."""
-    xs, ys = api._pixel_list(xs, ys)
-    a, ptrs = _host(want, (xs.size,))
-    api._call(api.render_lib().rl_rtiow_render_pixels_ao, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, int(ao_rays),
-              float(radius), *ptrs, stats=stats, allow_degenerate=allow_degenerate)
-    return AmbientOcclusion(a["open"], a["hits"], ao_rays)
+    a = api.list_form("rl_rtiow_render_pixels_ao", camera, world, first_sample, xs, ys, (int(ao_rays), float(radius)), _outputs, want, stats=stats,
+                      allow_degenerate=allow_degenerate)
+    return AmbientOcclusion(*a.values(), ao_rays)
 
 
 def render_pixels_ao_device(camera, world, d_xs, d_ys, n, ao_rays, radius, stream=0, first_sample=0, stats=None, allow_degenerate=False, *, d_open=0, d_hits=0):
     """d_xs / d_ys: device pointers of n uint32; outputs as render_ao_device with n pixels.  Async unless stats is a dict; an element outside
     the image is written as zeros in every given output."""
-    api._call(api.render_lib().rl_rtiow_render_pixels_ao_device, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
-              int(ao_rays), float(radius), C.c_void_p(d_open or None), C.c_void_p(d_hits or None), C.c_void_p(stream), stats=stats,
-              allow_degenerate=allow_degenerate)
+    api.list_device_form("rl_rtiow_render_pixels_ao_device", camera, world, first_sample, d_xs, d_ys, n, (int(ao_rays), float(radius)), (d_open, d_hits),
+                         stream, stats=stats, allow_degenerate=allow_degenerate)

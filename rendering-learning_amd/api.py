@@ -163,7 +163,9 @@ class RtiowFeatures(C.Structure):  # rl_rtiow_features: each pointer optional (N
     _fields_ = [("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p), ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p)]
 
 
-FEATURE_OUTPUTS = ("albedo_sum", "normal_sum", "depth_sum", "hit_count")
+# name -> (dtype, trailing shape), in the struct's order
+FEATURE_TABLE = {"albedo_sum": (np.float64, (3,)), "normal_sum": (np.float64, (3,)), "depth_sum": (np.float64, ()), "hit_count": (np.uint32, ())}
+FEATURE_OUTPUTS = tuple(FEATURE_TABLE)
 
 
 class AtrousParams(C.Structure):  # rl_atrous_params
@@ -607,6 +609,77 @@ def _call(fn, *args, stats=None, counting=False, allow_degenerate=False):
         stats.update(st.as_dict())
         stats["rc"] = rc
     return rc
+
+
+# ---- the four entry forms of the pixel-render families (csrc/rl_pixel_render_api.h): features, ambient occlusion,
+# direct lighting, NEE, NEE-MIS with and without sphere lights.  Every wrapper of a family is one of them, handed the C symbol's NAME
+# (the library is looked up after every check in Python has passed), the family's particular arguments (the C arguments between the
+# form's head and the outputs) and its outputs.  struct: the ctypes structure the outputs travel in (RtiowFeatures) where they are
+# not one pointer argument each.  kw: stats, allow_degenerate.
+def _subset_wanted(table, want):
+    want = tuple(table) if want is None else tuple(want)
+    if not want or any(k not in table for k in want):
+        raise ValueError(f"want must be a non-empty subset of {tuple(table)}")
+    return want
+
+
+def host_outputs(table, want, shape, alloc=np.zeros, wanted=_subset_wanted):
+    """The host arrays of a family's outputs at pixel shape `shape`: {name: array, None where `want` leaves it out}, in the C order.
+    table: name -> (dtype, trailing shape)."""
+    want = wanted(table, want)
+    return {k: alloc(tuple(shape) + tail, dtype=dtype) if k in want else None for k, (dtype, tail) in table.items()}
+
+
+def _pixel_form(symbol, camera, world, head, particular, outputs, struct, tail, **kw):
+    outputs = [None if p is None else C.c_void_p(p) for p in outputs]
+    return _call(getattr(render_lib(), symbol), world.device(), C.byref(camera.c), *head, *particular,
+                 *([C.byref(struct(*outputs))] if struct else outputs), *tail, **kw)
+
+
+def _host_pointers(arrays):
+    return [None if a is None else a.ctypes.data for a in arrays.values()]
+
+
+def rows_form(symbol, camera, world, first_sample, row_first, row_step, particular, outputs, want, struct=None, **kw):
+    """The compact rows of a shard into host arrays, outputs(want, [nrows, W]) -> those arrays.  Always a counting call."""
+    arrays = outputs(want, (rows_for(camera.c.image_height, row_first, row_step), camera.c.image_width))
+    _pixel_form(symbol, camera, world, (first_sample, row_first, row_step), particular, _host_pointers(arrays), struct, (), counting=True, **kw)
+    return arrays
+
+
+def rows_device_form(symbol, camera, world, first_sample, row_first, row_step, particular, d_outputs, stream, struct=None, **kw):
+    """The same rows into device buffers (d_outputs in the C order; 0 = not wanted), on `stream`."""
+    _pixel_form(symbol, camera, world, (first_sample, row_first, row_step), particular, [d or None for d in d_outputs], struct, (C.c_void_p(stream),), **kw)
+
+
+def list_form(symbol, camera, world, first_sample, xs, ys, particular, outputs, want, struct=None, **kw):
+    """The pixels (xs[i], ys[i]) into host arrays, outputs(want, [n]) -> those arrays."""
+    xs, ys = _pixel_list(xs, ys)
+    arrays = outputs(want, (xs.size,))
+    _pixel_form(symbol, camera, world, (first_sample, xs.ctypes.data, ys.ctypes.data, xs.size), particular, _host_pointers(arrays), struct, (), **kw)
+    return arrays
+
+
+def list_device_form(symbol, camera, world, first_sample, d_xs, d_ys, n, particular, d_outputs, stream, struct=None, **kw):
+    """A device list of n pixels into device buffers, on `stream`."""
+    _pixel_form(symbol, camera, world, (first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n)), particular, [d or None for d in d_outputs], struct,
+                (C.c_void_p(stream),), **kw)
+
+
+def mirror_probe(scene, width, spp, symbol, args, outputs, result, *extra, max_depth=None):
+    """A render of the C++ mirror through the host library's `symbol`(width, spp, *args, *outputs) on scene() at image_width = width
+    (the height is the scene's aspect ratio's) -> result(*arrays, *extra).  For tests of the mirror; RLError carries rlh_last_error."""
+    H = host_lib()
+    world = scene()
+    p = world.params
+    p.image_width, p.samples_per_pixel = int(width), int(spp)
+    if max_depth is not None:
+        p.max_depth = max_depth
+    cam = Camera(p)
+    arrays = outputs(None, (cam.c.image_height, cam.c.image_width))
+    if getattr(H, symbol)(int(width), int(spp), *args, *(C.c_void_p(a.ctypes.data) for a in arrays.values())) != 0:
+        raise RLError(-1, H.rlh_last_error().decode(errors="replace"))
+    return result(*arrays.values(), *extra)
 
 
 def pack_rays(origins, dirs, times=None):
@@ -1300,11 +1373,9 @@ def _features_want(want):
     return want
 
 
-def _features_host(want, shape):
-    """(Features arrays by name, the ctypes struct over them) for `want` at pixel shape `shape`."""
-    arrays = {k: np.empty(shape + ((3,) if k in ("albedo_sum", "normal_sum") else ()), dtype=np.uint32 if k == "hit_count" else np.float64)
-              for k in _features_want(want)}
-    return arrays, RtiowFeatures(**{k: a.ctypes.data for k, a in arrays.items()})
+def _features_outputs(want, shape):
+    """The feature renders' host arrays: uninitialised, and an empty `want` goes through (the library refuses the all-NULL struct)."""
+    return host_outputs(FEATURE_TABLE, want, shape, alloc=np.empty, wanted=lambda table, want: _features_want(want))
 
 
 class Camera:
@@ -1505,36 +1576,30 @@ class Camera:
     # depth over the S jittered camera rays of render_independent, and the number of rays that hit; want= a subset of FEATURE_OUTPUTS
     def render_features(self, world: World, first_sample=0, row_first=0, row_step=1, want=None, stats=None, allow_degenerate=False) -> Features:
         """Compact shard rows.  Always a counting call (reference-order trace), as render_rows."""
-        nrows = rows_for(self.c.image_height, row_first, row_step)
-        arrays, f = _features_host(want, (nrows, self.c.image_width))
-        _call(render_lib().rl_rtiow_render_features_rows, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f), stats=stats,
-              counting=True, allow_degenerate=allow_degenerate)
+        arrays = rows_form("rl_rtiow_render_features_rows", self, world, first_sample, row_first, row_step, (), _features_outputs, want, RtiowFeatures,
+                           stats=stats, allow_degenerate=allow_degenerate)
         return Features(self.params.samples_per_pixel, **arrays)
 
     def render_features_device(self, world: World, stream=0, row_first=0, row_step=1, first_sample=0, stats=None, allow_degenerate=False, *, d_albedo_sum=0,
                                d_normal_sum=0, d_depth_sum=0, d_hit_count=0):
         """Outputs stay in HBM: device pointers of nrows*W*3 f64 (albedo, normal), nrows*W f64 (depth), nrows*W uint32 (hit count); 0 = not
         wanted.  Async unless stats is a dict."""
-        f = RtiowFeatures(d_albedo_sum or None, d_normal_sum or None, d_depth_sum or None, d_hit_count or None)
-        _call(render_lib().rl_rtiow_render_features_device, world.device(), C.byref(self.c), first_sample, row_first, row_step, C.byref(f),
-              C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+        rows_device_form("rl_rtiow_render_features_device", self, world, first_sample, row_first, row_step, (),
+                         (d_albedo_sum, d_normal_sum, d_depth_sum, d_hit_count), stream, RtiowFeatures, stats=stats, allow_degenerate=allow_degenerate)
 
     def render_pixels_features(self, world: World, xs, ys, first_sample=0, want=None, stats=None, allow_degenerate=False) -> Features:
         """Features of pixels (xs[i], ys[i]), [n, ...]: what render_features(world, first_sample) holds at [ys[i], xs[i]].  The list rules
         are render_pixels'.  stats (a dict): a counting call; without it the call is counter-free and may take the fast walk."""
-        xs, ys = _pixel_list(xs, ys)
-        arrays, f = _features_host(want, (xs.size,))
-        _call(render_lib().rl_rtiow_render_pixels_features, world.device(), C.byref(self.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size,
-              C.byref(f), stats=stats, allow_degenerate=allow_degenerate)
+        arrays = list_form("rl_rtiow_render_pixels_features", self, world, first_sample, xs, ys, (), _features_outputs, want, RtiowFeatures, stats=stats,
+                           allow_degenerate=allow_degenerate)
         return Features(self.params.samples_per_pixel, **arrays)
 
     def render_pixels_features_device(self, world: World, d_xs, d_ys, n, stream=0, first_sample=0, stats=None, allow_degenerate=False, *, d_albedo_sum=0,
                                       d_normal_sum=0, d_depth_sum=0, d_hit_count=0):
         """d_xs / d_ys: device pointers of n uint32; outputs as render_features_device with n pixels.  Async unless stats is a dict; an element
         outside the image is written as zeros in every given output."""
-        f = RtiowFeatures(d_albedo_sum or None, d_normal_sum or None, d_depth_sum or None, d_hit_count or None)
-        _call(render_lib().rl_rtiow_render_pixels_features_device, world.device(), C.byref(self.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys),
-              int(n), C.byref(f), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+        list_device_form("rl_rtiow_render_pixels_features_device", self, world, first_sample, d_xs, d_ys, n, (),
+                         (d_albedo_sum, d_normal_sum, d_depth_sum, d_hit_count), stream, RtiowFeatures, stats=stats, allow_degenerate=allow_degenerate)
 
 
 # ---- denoising (include/rl_render.h "Denoising", rl_denoise_atrous*; DESIGN.md §3.17).  The default sigmas below are UNMEASURED defaults:

@@ -7,6 +7,7 @@ are DEMODULATED: no albedo and no 1/pi (DirectLight.radiance applies them).  hit
 exactly; the float sums of a call are that call's own fold.
 """
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -85,20 +86,12 @@ class DirectLight:
         return DirectLight(add(self.direct, other.direct), add(self.unshadowed, other.unshadowed), hits, self.light_samples)
 
 
-OUTPUTS = ("direct", "unshadowed", "hits")
+OUTPUTS = {"direct": (np.float64, (3,)), "unshadowed": (np.float64, (3,)), "hits": (np.uint32, ())}  # name -> (dtype, trailing shape), in the C order
+_outputs = functools.partial(api.host_outputs, OUTPUTS)
 
 
-def _host(want, shape):
-    want = OUTPUTS if want is None else tuple(want)
-    if not want or any(k not in OUTPUTS for k in want):
-        raise ValueError(f"want must be a non-empty subset of {OUTPUTS}")
-    a = {k: None for k in OUTPUTS}
-    for k in want:
-        a[k] = np.zeros(shape, dtype=np.uint32) if k == "hits" else np.zeros(tuple(shape) + (3,), dtype=np.float64)
-    return a, [None if a[k] is None else C.c_void_p(a[k].ctypes.data) for k in OUTPUTS]
-
-
-def _scalars(lights, light_samples, seg_tmax):
+def _light_args(lights, light_samples, seg_tmax):
+    """-> (what must stay alive over the call, the C arguments n_lights, lights, light_samples, seg_tmax); also the NEE families'."""
     L = pack_lights(lights)
     return L, (L.shape[0], C.c_void_p(L.ctypes.data), int(light_samples), float(seg_tmax))
 
@@ -106,56 +99,41 @@ def _scalars(lights, light_samples, seg_tmax):
 def render_direct(camera, world, lights, light_samples, seg_tmax=SEG_TMAX, first_sample=0, row_first=0, row_step=1, stats=None, want=None,
                   allow_degenerate=False):
     """Compact shard rows -> DirectLight([nrows, W(, 3)]).  Always a counting call (reference-order trace), as render_ao."""
-    nrows = api.rows_for(camera.c.image_height, row_first, row_step)
-    a, ptrs = _host(want, (nrows, camera.c.image_width))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_direct_rows, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, *ptrs, stats=stats,
-              counting=True, allow_degenerate=allow_degenerate)
-    return DirectLight(a["direct"], a["unshadowed"], a["hits"], light_samples)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    a = api.rows_form("rl_rtiow_render_direct_rows", camera, world, first_sample, row_first, row_step, args, _outputs, want, stats=stats,
+                      allow_degenerate=allow_degenerate)
+    return DirectLight(*a.values(), light_samples)
 
 
 def render_direct_device(camera, world, lights, light_samples, seg_tmax=SEG_TMAX, stream=0, row_first=0, row_step=1, first_sample=0, stats=None,
                          allow_degenerate=False, *, d_direct=0, d_unshadowed=0, d_hits=0):
     """Outputs stay in HBM: device pointers of nrows*W*3 float64 (direct, unshadowed) and nrows*W uint32 (hits); 0 = not wanted.  Async and
     counter-free unless stats is a dict.  The lights are copied into the launch: nothing of `lights` is read after the call returns."""
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_direct_device, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc,
-              C.c_void_p(d_direct or None), C.c_void_p(d_unshadowed or None), C.c_void_p(d_hits or None), C.c_void_p(stream), stats=stats,
-              allow_degenerate=allow_degenerate)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    api.rows_device_form("rl_rtiow_render_direct_device", camera, world, first_sample, row_first, row_step, args, (d_direct, d_unshadowed, d_hits), stream,
+                         stats=stats, allow_degenerate=allow_degenerate)
 
 
 def render_pixels_direct(camera, world, xs, ys, lights, light_samples, seg_tmax=SEG_TMAX, first_sample=0, stats=None, want=None, allow_degenerate=False):
     """The values of pixels (xs[i], ys[i]), [n(, 3)]: what render_direct holds at [ys[i], xs[i]].  The list rules are render_pixels_ao's.
     stats (a dict): a counting call; without it the call is counter-free and may take the fast walks (api.last_query())."""
-    xs, ys = api._pixel_list(xs, ys)
-    a, ptrs = _host(want, (xs.size,))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_pixels_direct, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, *sc, *ptrs,
-              stats=stats, allow_degenerate=allow_degenerate)
-    return DirectLight(a["direct"], a["unshadowed"], a["hits"], light_samples)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    a = api.list_form("rl_rtiow_render_pixels_direct", camera, world, first_sample, xs, ys, args, _outputs, want, stats=stats,
+                      allow_degenerate=allow_degenerate)
+    return DirectLight(*a.values(), light_samples)
 
 
 def render_pixels_direct_device(camera, world, d_xs, d_ys, n, lights, light_samples, seg_tmax=SEG_TMAX, stream=0, first_sample=0, stats=None,
                                 allow_degenerate=False, *, d_direct=0, d_unshadowed=0, d_hits=0):
     """d_xs / d_ys: device pointers of n uint32; outputs as render_direct_device with n pixels.  Async unless stats is a dict; an element
     outside the image is written as zeros in every given output."""
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_pixels_direct_device, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
-              *sc, C.c_void_p(d_direct or None), C.c_void_p(d_unshadowed or None), C.c_void_p(d_hits or None), C.c_void_p(stream), stats=stats,
-              allow_degenerate=allow_degenerate)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    api.list_device_form("rl_rtiow_render_pixels_direct_device", camera, world, first_sample, d_xs, d_ys, n, args, (d_direct, d_unshadowed, d_hits),
+                         stream, stats=stats, allow_degenerate=allow_degenerate)
 
 
 def cpp_mirror_probe(width, spp, first_sample, lights, light_samples, seg_tmax=SEG_TMAX):
     """rtiow::render_direct of the C++ mirror on golden_test_scene at image_width = width -> DirectLight([H, W(, 3)]) (the height is the
     scene's aspect ratio's).  For tests of the mirror; RLError carries rlh_last_error."""
-    H = api.host_lib()
-    world = api.World.golden_test_scene()
-    p = world.params
-    p.image_width, p.samples_per_pixel = int(width), int(spp)
-    cam = api.Camera(p)
-    shape = (cam.c.image_height, cam.c.image_width)
-    a, ptrs = _host(None, shape)
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    if H.rlh_direct_probe(int(width), int(spp), int(first_sample), *sc, *ptrs) != 0:
-        raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
-    return DirectLight(a["direct"], a["unshadowed"], a["hits"], light_samples)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    return api.mirror_probe(api.World.golden_test_scene, width, spp, "rlh_direct_probe", (int(first_sample), *args), _outputs, DirectLight, light_samples)

@@ -11,13 +11,12 @@ sampling): the same expectation, and no sample larger than wha
 sphere lights (pack_sphere_lights): stationary spheres that emit outward only.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 
 from . import api
-from .direct import SEG_TMAX, pack_lights
-
-OUTPUTS = ("sums", "sq")
+from .direct import SEG_TMAX, _light_args, pack_lights
 
 
 class PathNEE:
@@ -38,59 +37,43 @@ class PathNEE:
         return self.sums / float(self.samples)
 
 
-def _host(want, shape):
-    want = OUTPUTS if want is None else tuple(want)
-    if not want or any(k not in OUTPUTS for k in want):
-        raise ValueError(f"want must be a non-empty subset of {OUTPUTS}")
-    a = {k: None for k in OUTPUTS}
-    for k in want:
-        a[k] = np.zeros(tuple(shape) + (3,), dtype=np.float64)
-    return a, [None if a[k] is None else C.c_void_p(a[k].ctypes.data) for k in OUTPUTS]
-
-
-def _scalars(lights, light_samples, seg_tmax):
-    L = pack_lights(lights)
-    return L, (L.shape[0], C.c_void_p(L.ctypes.data), int(light_samples), float(seg_tmax))
+OUTPUTS = {"sums": (np.float64, (3,)), "sq": (np.float64, (3,))}  # name -> (dtype, trailing shape), in the C order
+_outputs = functools.partial(api.host_outputs, OUTPUTS)
 
 
 def render_nee(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, first_sample=0, row_first=0, row_step=1, stats=None, want=None,
                allow_degenerate=False):
     """Compact shard rows -> PathNEE([nrows, W, 3]).  Always a counting call (reference-order trace), as render_direct."""
-    nrows = api.rows_for(camera.c.image_height, row_first, row_step)
-    a, ptrs = _host(want, (nrows, camera.c.image_width))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_nee_rows, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, *ptrs, stats=stats,
-              counting=True, allow_degenerate=allow_degenerate)
-    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    a = api.rows_form("rl_rtiow_render_nee_rows", camera, world, first_sample, row_first, row_step, args, _outputs, want, stats=stats,
+                      allow_degenerate=allow_degenerate)
+    return PathNEE(*a.values(), camera.c.samples_per_pixel, light_samples)
 
 
 def render_nee_device(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, stream=0, row_first=0, row_step=1, first_sample=0, stats=None,
                       allow_degenerate=False, *, d_sums=0, d_sq=0):
     """Outputs stay in HBM: device pointers of nrows*W*3 float64 each; 0 = not wanted.  Async and counter-free unless stats is a dict.  The
     lights are copied into the launch: nothing of `lights` is read after the call returns."""
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_nee_device, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc,
-              C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    api.rows_device_form("rl_rtiow_render_nee_device", camera, world, first_sample, row_first, row_step, args, (d_sums, d_sq), stream, stats=stats,
+                         allow_degenerate=allow_degenerate)
 
 
 def render_pixels_nee(camera, world, xs, ys, lights, light_samples=1, seg_tmax=SEG_TMAX, first_sample=0, stats=None, want=None, allow_degenerate=False):
     """The values of pixels (xs[i], ys[i]), [n, 3]: what render_nee holds at [ys[i], xs[i]].  The list rules are render_pixels_direct's.
     stats (a dict): a counting call; without it the call is counter-free and may take the fast walks (api.last_query())."""
-    xs, ys = api._pixel_list(xs, ys)
-    a, ptrs = _host(want, (xs.size,))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_pixels_nee, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, *sc, *ptrs,
-              stats=stats, allow_degenerate=allow_degenerate)
-    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    a = api.list_form("rl_rtiow_render_pixels_nee", camera, world, first_sample, xs, ys, args, _outputs, want, stats=stats, allow_degenerate=allow_degenerate)
+    return PathNEE(*a.values(), camera.c.samples_per_pixel, light_samples)
 
 
 def render_pixels_nee_device(camera, world, d_xs, d_ys, n, lights, light_samples=1, seg_tmax=SEG_TMAX, stream=0, first_sample=0, stats=None,
                              allow_degenerate=False, *, d_sums=0, d_sq=0):
     """d_xs / d_ys: device pointers of n uint32; outputs as render_nee_device with n pixels.  Async unless stats is a dict; an element outside
     the image is written as zeros in every given output."""
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    api._call(api.render_lib().rl_rtiow_render_pixels_nee_device, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n),
-              *sc, C.c_void_p(d_sums or None), C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    api.list_device_form("rl_rtiow_render_pixels_nee_device", camera, world, first_sample, d_xs, d_ys, n, args, (d_sums, d_sq), stream, stats=stats,
+                         allow_degenerate=allow_degenerate)
 
 
 # ----------------------------------------------------------------------------- with multiple importance sampling
@@ -126,17 +109,17 @@ def pack_sphere_lights(sphere_lights):
     return np.ascontiguousarray(np.array(rows, dtype=np.float64).reshape(len(rows), 7))
 
 
-def _mis_call(name, lights, sphere_lights, light_samples, seg_tmax, h):
-    """-> (what must stay alive over the call, the library function, the arguments from n_lights to heuristic): render_nee_mis*'s own
-    symbol and checks without sphere_lights, else the _spheres symbol, where `lights` may be empty."""
+def _mis_args(lights, sphere_lights, light_samples, seg_tmax, heuristic):
+    """-> (the family's stem in the C symbols, what must stay alive over the call, the C arguments from n_lights to heuristic):
+    render_nee_mis*'s own symbols and checks without sphere_lights, else the _spheres symbols, where `lights` may be empty."""
+    h = _heuristic(heuristic)
     if sphere_lights is None:
-        keep, sc = _scalars(lights, light_samples, seg_tmax)
-        return keep, getattr(api.render_lib(), name), (*sc, h)
+        keep, args = _light_args(lights, light_samples, seg_tmax)
+        return "nee_mis", keep, (*args, h)
     Sp = pack_sphere_lights(sphere_lights)
     L = pack_lights(lights) if len(lights) else np.zeros((0, 12), dtype=np.float64)
-    fn = getattr(api.render_lib(), name.replace("nee_mis", "nee_mis_spheres"))
     ptr = lambda a: C.c_void_p(a.ctypes.data) if a.shape[0] else None
-    return (L, Sp), fn, (L.shape[0], ptr(L), Sp.shape[0], ptr(Sp), int(light_samples), float(seg_tmax), h)
+    return "nee_mis_spheres", (L, Sp), (L.shape[0], ptr(L), Sp.shape[0], ptr(Sp), int(light_samples), float(seg_tmax), h)
 
 
 def render_nee_mis(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", first_sample=0, row_first=0, row_step=1, stats=None,
@@ -147,85 +130,53 @@ def render_nee_mis(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, he
     same path and the same expectation as render_nee; no single sample exceeds what the lights emit.  -> PathNEE([nrows, W, 3]).
     sphere_lights (pack_sphere_lights' input; include/rl_render.h "NEE path renders with sphere lights"): spheres that emit
     outward only, sampled by area and met by the scattered ray; `lights` may then be empty."""
-    h = _heuristic(heuristic)
-    nrows = api.rows_for(camera.c.image_height, row_first, row_step)
-    a, ptrs = _host(want, (nrows, camera.c.image_width))
-    keep, fn, sc = _mis_call("rl_rtiow_render_nee_mis_rows", lights, sphere_lights, light_samples, seg_tmax, h)
-    api._call(fn, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, *ptrs, stats=stats, counting=True, allow_degenerate=allow_degenerate)
-    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+    stem, keep, args = _mis_args(lights, sphere_lights, light_samples, seg_tmax, heuristic)
+    a = api.rows_form(f"rl_rtiow_render_{stem}_rows", camera, world, first_sample, row_first, row_step, args, _outputs, want, stats=stats,
+                      allow_degenerate=allow_degenerate)
+    return PathNEE(*a.values(), camera.c.samples_per_pixel, light_samples)
 
 
 def render_nee_mis_device(camera, world, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", stream=0, row_first=0, row_step=1, first_sample=0,
                           stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0, sphere_lights=None):
     """render_nee_device's buffers and asynchrony, render_nee_mis's estimate."""
-    h = _heuristic(heuristic)
-    keep, fn, sc = _mis_call("rl_rtiow_render_nee_mis_device", lights, sphere_lights, light_samples, seg_tmax, h)
-    api._call(fn, world.device(), C.byref(camera.c), first_sample, row_first, row_step, *sc, C.c_void_p(d_sums or None), C.c_void_p(d_sq or None),
-              C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+    stem, keep, args = _mis_args(lights, sphere_lights, light_samples, seg_tmax, heuristic)
+    api.rows_device_form(f"rl_rtiow_render_{stem}_device", camera, world, first_sample, row_first, row_step, args, (d_sums, d_sq), stream, stats=stats,
+                         allow_degenerate=allow_degenerate)
 
 
 def render_pixels_nee_mis(camera, world, xs, ys, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", first_sample=0, stats=None, want=None,
                           allow_degenerate=False, sphere_lights=None):
     """The values of pixels (xs[i], ys[i]), [n, 3]: what render_nee_mis holds at [ys[i], xs[i]].  The list rules and the meaning of stats are
     render_pixels_nee's."""
-    h = _heuristic(heuristic)
-    xs, ys = api._pixel_list(xs, ys)
-    a, ptrs = _host(want, (xs.size,))
-    keep, fn, sc = _mis_call("rl_rtiow_render_pixels_nee_mis", lights, sphere_lights, light_samples, seg_tmax, h)
-    api._call(fn, world.device(), C.byref(camera.c), first_sample, xs.ctypes.data, ys.ctypes.data, xs.size, *sc, *ptrs, stats=stats,
-              allow_degenerate=allow_degenerate)
-    return PathNEE(a["sums"], a["sq"], camera.c.samples_per_pixel, light_samples)
+    stem, keep, args = _mis_args(lights, sphere_lights, light_samples, seg_tmax, heuristic)
+    a = api.list_form(f"rl_rtiow_render_pixels_{stem}", camera, world, first_sample, xs, ys, args, _outputs, want, stats=stats,
+                      allow_degenerate=allow_degenerate)
+    return PathNEE(*a.values(), camera.c.samples_per_pixel, light_samples)
 
 
 def render_pixels_nee_mis_device(camera, world, d_xs, d_ys, n, lights, light_samples=1, seg_tmax=SEG_TMAX, heuristic="balance", stream=0, first_sample=0,
                                  stats=None, allow_degenerate=False, *, d_sums=0, d_sq=0, sphere_lights=None):
     """render_pixels_nee_device's buffers, list rules and asynchrony, render_nee_mis's estimate."""
-    h = _heuristic(heuristic)
-    keep, fn, sc = _mis_call("rl_rtiow_render_pixels_nee_mis_device", lights, sphere_lights, light_samples, seg_tmax, h)
-    api._call(fn, world.device(), C.byref(camera.c), first_sample, C.c_void_p(d_xs), C.c_void_p(d_ys), int(n), *sc, C.c_void_p(d_sums or None),
-              C.c_void_p(d_sq or None), C.c_void_p(stream), stats=stats, allow_degenerate=allow_degenerate)
+    stem, keep, args = _mis_args(lights, sphere_lights, light_samples, seg_tmax, heuristic)
+    api.list_device_form(f"rl_rtiow_render_pixels_{stem}_device", camera, world, first_sample, d_xs, d_ys, n, args, (d_sums, d_sq), stream, stats=stats,
+                         allow_degenerate=allow_degenerate)
 
 
 def cpp_mirror_probe(width, spp, first_sample, lights, light_samples, seg_tmax=SEG_TMAX):
     """rtiow::render_nee of the C++ mirror on golden_test_scene at image_width = width -> PathNEE([H, W, 3]) (the height is the scene's
     aspect ratio's).  For tests of the mirror; RLError carries rlh_last_error."""
-    H = api.host_lib()
-    world = api.World.golden_test_scene()
-    p = world.params
-    p.image_width, p.samples_per_pixel = int(width), int(spp)
-    cam = api.Camera(p)
-    a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    if H.rlh_nee_probe(int(width), int(spp), int(first_sample), *sc, *ptrs) != 0:
-        raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
-    return PathNEE(a["sums"], a["sq"], spp, light_samples)
+    keep, args = _light_args(lights, light_samples, seg_tmax)
+    return api.mirror_probe(api.World.golden_test_scene, width, spp, "rlh_nee_probe", (int(first_sample), *args), _outputs, PathNEE, spp, light_samples)
 
 
 def cpp_mirror_probe_mis(width, spp, first_sample, lights, light_samples, seg_tmax=SEG_TMAX, heuristic="balance"):
     """rtiow::render_nee_mis of the C++ mirror, as cpp_mirror_probe."""
-    h = _heuristic(heuristic)
-    H = api.host_lib()
-    world = api.World.golden_test_scene()
-    p = world.params
-    p.image_width, p.samples_per_pixel = int(width), int(spp)
-    cam = api.Camera(p)
-    a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
-    keep, sc = _scalars(lights, light_samples, seg_tmax)
-    if H.rlh_nee_mis_probe(int(width), int(spp), int(first_sample), *sc, h, *ptrs) != 0:
-        raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
-    return PathNEE(a["sums"], a["sq"], spp, light_samples)
+    stem, keep, args = _mis_args(lights, None, light_samples, seg_tmax, heuristic)
+    return api.mirror_probe(api.World.golden_test_scene, width, spp, "rlh_nee_mis_probe", (int(first_sample), *args), _outputs, PathNEE, spp, light_samples)
 
 
 def cpp_mirror_probe_spheres(width, spp, first_sample, lights, sphere_lights, light_samples, seg_tmax=SEG_TMAX, heuristic="balance"):
     """rtiow::render_nee_mis with sphere lights of the C++ mirror on simple_light at image_width = width, max_depth 6 -> PathNEE([H, W, 3])."""
-    h = _heuristic(heuristic)
-    H = api.host_lib()
-    world = api.World.simple_light()
-    p = world.params
-    p.image_width, p.samples_per_pixel, p.max_depth = int(width), int(spp), 6
-    cam = api.Camera(p)
-    a, ptrs = _host(None, (cam.c.image_height, cam.c.image_width))
-    keep, fn, sc = _mis_call("rl_rtiow_render_nee_mis_rows", lights, sphere_lights, light_samples, seg_tmax, h)
-    if H.rlh_nee_spheres_probe(int(width), int(spp), int(first_sample), *sc, *ptrs) != 0:
-        raise api.RLError(-1, H.rlh_last_error().decode(errors="replace"))
-    return PathNEE(a["sums"], a["sq"], spp, light_samples)
+    stem, keep, args = _mis_args(lights, sphere_lights, light_samples, seg_tmax, heuristic)
+    return api.mirror_probe(api.World.simple_light, width, spp, "rlh_nee_spheres_probe", (int(first_sample), *args), _outputs, PathNEE, spp, light_samples,
+                            max_depth=6)

@@ -1,8 +1,8 @@
 """What the C side says about the Python binding, read from the C text itself: a small prototype parser over include/rl_render.h
 (declarations), csrc/ (the rl_debug_* definitions, which no header declares) and host/*.cpp (the rlh_* definitions), and the classes
-both sides are compared in (tests/test_binding_signatures.py).  Below it, a recorder that stands in for the render library and a driver
-that calls every wrapper of api.py on tiny inputs (tests/test_binding_calls.py, tools/record_binding_calls.py): what each wrapper
-hands to C, pinned without a GPU.
+both sides are compared in (tests/test_binding_signatures.py).  Below it, a recorder that stands in for the render library, one for
+the host library's probes, and a driver that calls every wrapper of api.py, ao.py, direct.py, nee.py, occlusion.py and entry_table.py
+on tiny inputs (tests/test_binding_calls.py, tools/record_binding_calls.py): what each wrapper hands to C, pinned without a GPU.
 
 Classes.  A parameter or return is one of
   None                      void (returns only)
@@ -212,25 +212,51 @@ class Recorder:
         return self._entries.setdefault(name, _Entry(self, name))
 
 
+class HostProbes:
+    """Stands in for api.host_lib(), for the rlh_*_probe symbols only: they note (symbol, normalised arguments) in the Recorder's list
+    and return 0.  Every other name is the real host library's, which still serves Camera, World and the rest."""
+    rc, stats_params, status_calls = 0, {}, ()
+
+    def __init__(self, real, rec):
+        self._real, self._rec = real, rec
+        self.protos = {n: p for n, p in host_prototypes().items() if n.endswith("_probe")}
+
+    calls = property(lambda self: self._rec.calls)
+
+    def __getattr__(self, name):
+        if name.startswith("_"):
+            raise AttributeError(name)
+        return _Entry(self, name) if name in self.protos else getattr(self._real, name)
+
+
+FAMILY_MODULES = ("ao", "direct", "nee", "occlusion", "entry_table")  # the package's modules beside api whose public functions are wrappers
+PURE_PACKERS = {"pack_lights", "pack_sphere_lights"}  # ... except these: they reach no library
+
+
 def drive(api, patch):
-    """Calls every public wrapper of api.py that reaches the render library, against a Recorder, on tiny inputs: a 4 x 2 camera, three
-    rays / pixels / records, a 4 x 2 image with two guide channels.  patch(object, name, value) is monkeypatch.setattr or a stand-in
-    that restores.  Each wrapper runs up to four times:
+    """Calls every public wrapper of api.py and of the FAMILY_MODULES that reaches the render library (or, the cpp_mirror_probe*, an
+    rlh_*_probe of the host library), against a Recorder, on tiny inputs: a 4 x 2 camera, three rays / pixels / records, a 4 x 2 image
+    with two guide channels, one quad light and one sphere light.  patch(object, name, value) is monkeypatch.setattr or a stand-in
+    that restores.  Each entry holds the wrapper's inspect.signature as text, and each wrapper runs up to four times:
       plain        as listed                                   -> the calls it made
       stats        with stats={} where it takes stats          -> the calls, and the dict's keys
       degenerate   the library answering RL_E_DEGENERATE       -> whether it raised; the dict's keys and rc
       allowed      likewise with allow_degenerate=True where the wrapper has it
     Returns [{"wrapper": label, variant: result, ...}] in a fixed order."""
+    import importlib
     import inspect
     import numpy as np
     rec = Recorder()
+    probes = HostProbes(api.host_lib(), rec)
     patch(api, "render_lib", lambda: rec)
+    patch(api, "host_lib", lambda: probes)
     patch(api, "_inited", False)
+    ao, direct, nee, occlusion, entry_table = (importlib.import_module(f"{api.__package__}.{m}") for m in FAMILY_MODULES)
     worlds, out = [], []
 
     def run(label, fn, *args, **kw):
         names = inspect.signature(fn).parameters
-        entry = {"wrapper": label}
+        entry = {"wrapper": label, "signature": str(inspect.signature(fn))}
 
         def once(variant, rc, **extra):
             api._inited = False
@@ -401,14 +427,62 @@ def drive(api, patch):
         run("rtiow_launch_total", api.rtiow_launch_total)
         run("rtiow_launches", api.rtiow_launches, 0)
         run("steal_record", api.steal_record, world, 8)
+
+        # ---- the modules beside api (appended likewise): occlusion queries, the entry table's switches, the pixel-render families
+        run("occlusion.occluded_rays", occlusion.occluded_rays, world, o3, d3, t3)
+        run("occlusion.occluded_rays_device", occlusion.occluded_rays_device, world, D, 2 * D, 3, 0.5, 2.0, stream=3 * D)
+        run("entry_table.set_slices", entry_table.set_slices, 2)
+        run("entry_table.set_reuse", entry_table.set_reuse, False)
+        run("entry_table.builds", entry_table.builds)
+        run("entry_table.sliced_table", entry_table.sliced_table, world, 8, 2)
+        run("entry_table.census", entry_table.census, world)
+
+        quad, ball = [((0, 4, 0), (2, 0, 0), (0, 0, 2), (5, 4, 3))], [((0, 5, 0), 1.0, 2.0)]
+        shard = {"row_first": 1, "row_step": 2}
+
+        def family(mod, stem, outputs, *particular, subset={}, routes={}):
+            """The four wrappers of one family, each plain and with a strict subset of its outputs (the row forms on a shard; `subset`:
+            more keyword arguments of those rows), then once per route (routes: {tag: keyword arguments})."""
+            name = mod.__name__.rsplit(".", 1)[1]
+            rows, dev = getattr(mod, f"render_{stem}"), getattr(mod, f"render_{stem}_device")
+            pix, pixdev = getattr(mod, f"render_pixels_{stem}"), getattr(mod, f"render_pixels_{stem}_device")
+            d_all = {f"d_{k}": (i + 4) * D for i, k in enumerate(outputs)}
+            d_some = {f"d_{outputs[-1]}": 7 * D}
+            run(f"{name}.{rows.__name__}", rows, cam, world, *particular)
+            run(f"{name}.{rows.__name__}[want]", rows, cam, world, *particular, first_sample=4, want=outputs[:1], **shard, **subset)
+            run(f"{name}.{dev.__name__}", dev, cam, world, *particular, stream=3 * D, **d_all)
+            run(f"{name}.{dev.__name__}[subset]", dev, cam, world, *particular, first_sample=4, **shard, **d_some, **subset)
+            run(f"{name}.{pix.__name__}", pix, cam, world, xs, ys, *particular)
+            run(f"{name}.{pix.__name__}[want]", pix, cam, world, xs, ys, *particular, first_sample=1, want=outputs[1:], **subset)
+            run(f"{name}.{pixdev.__name__}", pixdev, cam, world, D, 2 * D, 3, *particular, stream=3 * D, **d_all)
+            run(f"{name}.{pixdev.__name__}[subset]", pixdev, cam, world, D, 2 * D, 3, *particular, first_sample=1, **d_some, **subset)
+            for tag, kw in routes.items():
+                run(f"{name}.{rows.__name__}[{tag}]", rows, cam, world, **kw)
+                run(f"{name}.{dev.__name__}[{tag}]", dev, cam, world, **d_some, **kw)
+                run(f"{name}.{pix.__name__}[{tag}]", pix, cam, world, xs, ys, **kw)
+                run(f"{name}.{pixdev.__name__}[{tag}]", pixdev, cam, world, D, 2 * D, 3, **d_all, **kw)
+
+        family(ao, "ao", ("open", "hits"), 4, 1.5)
+        family(direct, "direct", ("direct", "unshadowed", "hits"), quad, 2, subset={"seg_tmax": 0.5})
+        family(nee, "nee", ("sums", "sq"), quad, 2, subset={"seg_tmax": 0.5})
+        family(nee, "nee_mis", ("sums", "sq"), quad, 2, subset={"seg_tmax": 0.5, "heuristic": "power"},
+               routes={"spheres": {"lights": quad, "light_samples": 2, "sphere_lights": ball},
+                       "spheres, no lights": {"lights": [], "light_samples": 3, "heuristic": "power", "sphere_lights": ball}})
+
+        # ---- the C++ mirror's probes: the host library's rlh_*_probe, noted by HostProbes
+        run("direct.cpp_mirror_probe", direct.cpp_mirror_probe, 4, 2, 1, quad, 2)
+        run("nee.cpp_mirror_probe", nee.cpp_mirror_probe, 4, 2, 1, quad, 3, seg_tmax=0.5)
+        run("nee.cpp_mirror_probe_mis", nee.cpp_mirror_probe_mis, 4, 2, 1, quad, 2, heuristic="power")
+        run("nee.cpp_mirror_probe_spheres", nee.cpp_mirror_probe_spheres, 4, 2, 1, quad, ball, 2)
+        run("nee.cpp_mirror_probe_spheres[power, no lights]", nee.cpp_mirror_probe_spheres, 4, 2, 0, [], ball, 3, seg_tmax=0.5, heuristic="power")
     finally:
         for w in worlds:  # the handles are the recorder's: nothing of the real library may ever see them
             w._device = None
     return out
 
 
-def covered_wrappers(api):
-    """The public callables of Camera, World, RtcWorld and the module whose source names render_lib(): what drive() has to call."""
+def names_render_lib(api):
+    """The public callables of Camera, World, RtcWorld and api itself whose source names render_lib()."""
     import inspect
     names = []
     for owner, label in ((api.Camera, "Camera."), (api.World, "World."), (api.RtcWorld, "RtcWorld."), (api, "")):
@@ -418,4 +492,18 @@ def covered_wrappers(api):
                 continue
             if "render_lib()" in inspect.getsource(f):
                 names.append(label + k)
+    return names
+
+
+def covered_wrappers(api, at_least=()):
+    """What drive() has to call.  Of api: `at_least` and whatever else names_render_lib finds (a wrapper that reaches the library through
+    a shared form does not name it, so the rule alone would let it go).  Of the FAMILY_MODULES, by exclusion: every public function
+    defined there but the PURE_PACKERS, labelled "module.name"."""
+    import importlib
+    import inspect
+    names = list(at_least) + [n for n in names_render_lib(api) if n not in at_least]
+    for m in FAMILY_MODULES:
+        mod = importlib.import_module(f"{api.__package__}.{m}")
+        names += [f"{m}.{k}" for k, f in vars(mod).items()
+                  if not k.startswith("_") and inspect.isfunction(f) and f.__module__ == mod.__name__ and k not in PURE_PACKERS]
     return names

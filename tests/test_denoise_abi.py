@@ -12,20 +12,13 @@ import numpy as np
 import pytest
 
 import atrous_model as M
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_denoise_atrous_pass_device": 10, "rl_denoise_atrous": 9}
 FIELDS = ["color_sigma2", "variance_floor", "n_guides", "reserved", "guide_inv_sigma"]
 W, H, G = 5, 4, 2
 DBL_MIN = float(np.finfo(np.float64).tiny)  # 2^-1022, the smallest normal number: the least variance_floor the library takes
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_denoise_entry_points_are_exported_declared_and_listed(rl):
@@ -107,7 +100,7 @@ def _bad_params(api):
 
 def test_every_refusal_is_rl_e_invalid_with_or_without_a_device(rl):
     api = rl.api
-    if _gpu_present():
+    if gpu_present():
         rl.init(0)
     images = _images()
     outs = np.full((H, W, 3), 7.0), np.full((H, W, 3), 7.0)
@@ -151,7 +144,7 @@ def test_every_refusal_is_rl_e_invalid_with_or_without_a_device(rl):
             bad()
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_denoise_without_a_device_fails_loudly(rl):
     api = rl.api
     lib = api.render_lib()

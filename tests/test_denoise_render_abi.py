@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import denoise_render_model as DM
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_denoise_prepare_device": 7, "rl_denoise_finish_device": 10, "rl_denoise_render_work_bytes": 3, "rl_denoise_render_device": 11,
@@ -21,14 +22,6 @@ FIELDS = ["sums", "sq", "counts", "albedo_sum", "normal_sum", "depth_sum", "hit_
 OFFSETS = [0, 8, 16, 24, 32, 40, 48, 56, 60, 64, 68]
 H, W = DM.HAND_COUNTS.shape
 KINDS = {"all four": ("albedo", "normal", "depth", "coverage"), "albedo": ("albedo",), "depth + coverage": ("depth", "coverage"), "normal": ("normal",)}
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_entry_points_are_exported_declared_and_listed(rl):
@@ -146,7 +139,7 @@ def _bad_params(api, G):
 
 def test_every_refusal_is_rl_e_invalid_with_or_without_a_device(rl):
     api = rl.api
-    if _gpu_present():
+    if gpu_present():
         rl.init(0)
     INV = api.RL_E_INVALID
     _, d = _host_inputs(rl)
@@ -219,7 +212,7 @@ def test_every_refusal_is_rl_e_invalid_with_or_without_a_device(rl):
             bad()
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_without_a_device_fails_loudly(rl):
     api = rl.api
     lib = api.render_lib()

@@ -4,16 +4,9 @@ import ctypes
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present
 
 NEW = ("rl_rtiow_render_independent_rows", "rl_rtiow_render_independent_device")
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_independent_entry_points_are_exported_and_listed(rl):
@@ -31,7 +24,7 @@ def test_independent_entry_points_are_exported_and_listed(rl):
         assert callable(getattr(rl.Camera, m)), m
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_independent_renders_without_a_device_fail_loudly(rl):
     api = rl.api
     lib = api.render_lib()

@@ -7,17 +7,10 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_scatter_rays": 9, "rl_rtiow_scatter_rays_device": 10, "rl_rtiow_texture_values": 6, "rl_rtiow_texture_values_device": 7}
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_material_query_entry_points_are_exported_declared_and_listed(rl):
@@ -81,7 +74,7 @@ def test_shape_errors_are_caught_before_the_library(rl):
             bad()
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_material_queries_without_a_device_fail_loudly(rl):
     api = rl.api
     lib = api.render_lib()

@@ -9,18 +9,11 @@ import numpy as np
 import pytest
 
 import binding_model as bm
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_occluded_rays": 7, "rl_rtiow_occluded_rays_device": 8}
 INF = float("inf")
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_occlusion_entry_points_are_exported_declared_and_listed(rl):
@@ -108,7 +101,7 @@ def test_last_query_names_the_occlusion_kernels(rl, monkeypatch):
         assert api.last_query() == {"kernel": name, "retraced": 3}
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_occlusion_queries_without_a_device_fail_loudly(rl):
     api = rl.api
     lib = api.render_lib()

@@ -7,17 +7,10 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_camera_rays": 7, "rl_rtiow_camera_rays_device": 8, "rl_rtiow_ray_color_rays": 11, "rl_rtiow_ray_color_rays_device": 12}
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_path_query_entry_points_are_exported_declared_and_listed(rl):
@@ -68,7 +61,7 @@ def test_cursor_shape_errors_are_caught_before_the_library(rl):
         cam.get_rays([0, 1], [0, 0], api.pack_cursors([0]))
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_path_queries_without_a_device_fail_loudly(rl):
     api = rl.api
     lib = api.render_lib()

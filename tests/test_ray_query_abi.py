@@ -7,18 +7,11 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_hit_rays": 7, "rl_rtiow_hit_rays_device": 8, "rl_rtc_intersect_rays": 8, "rl_rtc_intersect_rays_device": 9,
        "rl_rtc_color_at_rays": 5, "rl_rtc_color_at_rays_device": 6}
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_query_entry_points_are_exported_declared_and_listed(rl):
@@ -57,7 +50,7 @@ def test_ray_shape_errors_are_caught_before_the_library(rl):
     assert r.dtype == api.RAY and tuple(r["origin"][0]) == (1.0, 2.0, 3.0) and tuple(r["dir"][0]) == (0.0, 0.0, -1.0) and r["time"][0] == 0.5
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_queries_without_a_device_fail_loudly(rl, golden):
     api = rl.api
     lib = api.render_lib()

@@ -8,19 +8,12 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_render_adaptive_rows": 10, "rl_rtiow_render_adaptive_device": 11}
 PROBE_ARGS = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
               ctypes.c_void_p]
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_render_adaptive_entry_points_are_exported_declared_and_listed(rl):
@@ -67,7 +60,7 @@ def test_every_invalid_rule_is_refused_with_outputs_untouched(rl):
     sums, sq, counts = np.full(npix * 3, 7.0), np.full(npix * 3, 7.0), np.full(npix, 7, dtype=np.uint32)
     c = ctypes.byref(cam.c)
     dev = None  # without a device there is no scene either: the rule is still looked at first
-    if _gpu_present():
+    if gpu_present():
         rl.init(0)
         dev = world.device()
     S, Q, N = sums.ctypes.data, sq.ctypes.data, counts.ctypes.data
@@ -91,7 +84,7 @@ def test_every_invalid_rule_is_refused_with_outputs_untouched(rl):
         assert e.value.code == api.RL_E_INVALID, kw
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_render_adaptive_without_a_device_fails_loudly(rl):
     api = rl.api
     lib = api.render_lib()

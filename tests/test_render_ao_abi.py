@@ -8,60 +8,12 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import camera as _camera, forms, gpu_present, the_family_check_comes_first_and_the_device_before_every_later_rule as family_check_comes_first
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_render_ao_rows": 10, "rl_rtiow_render_ao_device": 11, "rl_rtiow_render_pixels_ao": 11, "rl_rtiow_render_pixels_ao_device": 12}
 INF = float("inf")
 NAN = float("nan")
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
-
-
-def _camera(rl, spp=2):
-    return rl.Camera(rl.CameraParams(aspect_ratio=1.5, image_width=6, samples_per_pixel=spp, max_depth=5))
-
-
-def _forms(lib, cam, n_pix=24):
-    """The four entry points as f(ao_rays, radius, open, hits) -> rc with everything else valid but the scene (NULL: a later rule)."""
-    xs = np.arange(4, dtype=np.uint32)
-    ys = np.zeros(4, dtype=np.uint32)
-    c = C.byref(cam.c)
-    return {
-        "rows": lambda k, r, o, h: lib.rl_rtiow_render_ao_rows(None, c, 0, 0, 1, k, r, o, h, None),
-        "device": lambda k, r, o, h: lib.rl_rtiow_render_ao_device(None, c, 0, 0, 1, k, r, o, h, None, None),
-        "pixels": lambda k, r, o, h: lib.rl_rtiow_render_pixels_ao(None, c, 0, xs.ctypes.data, ys.ctypes.data, 4, k, r, o, h, None),
-        "pixels_device": lambda k, r, o, h: lib.rl_rtiow_render_pixels_ao_device(None, c, 0, xs.ctypes.data, ys.ctypes.data, 4, k, r, o, h, None, None),
-    }
-
-
-def _with_a_later_defect(lib, stem, cam):
-    """Every entry point of the family as f(*particular) -> rc, each time with ONE rule that comes later in its check sequence broken as
-    well: no scene, no camera, row_step == 0, an image without pixels, row_first past the last row; a NULL list, the empty list, a list
-    beyond the work counter.  -> {(form, defect): f}, and what the calls point into (to be kept alive)."""
-    rows, dev = getattr(lib, "rl_rtiow_render_%s_rows" % stem), getattr(lib, "rl_rtiow_render_%s_device" % stem)
-    pix, pixdev = getattr(lib, "rl_rtiow_render_pixels_%s" % stem), getattr(lib, "rl_rtiow_render_pixels_%s_device" % stem)
-    xs, ys = np.arange(4, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
-    empty = type(cam.c).from_buffer_copy(cam.c)
-    empty.image_width = 0
-    c, e, X, Y = C.byref(cam.c), C.byref(empty), xs.ctypes.data, ys.ctypes.data
-    row_heads = {"scene": (None, c, 0, 0, 1), "camera": (None, None, 0, 0, 1), "row_step": (None, c, 0, 0, 0), "empty image": (None, e, 0, 0, 1),
-                 "row_first": (None, c, 0, cam.c.image_height, 1)}
-    list_heads = {"scene": (None, c, 0, X, Y, 4), "camera": (None, None, 0, X, Y, 4), "xs": (None, c, 0, None, Y, 4), "ys": (None, c, 0, X, None, 4),
-                  "empty list": (None, c, 0, None, None, 0), "empty image": (None, e, 0, X, Y, 4), "length": (None, c, 0, X, Y, 0xFFFF0000)}
-    calls = {}
-    for what, head in row_heads.items():
-        calls["rows", what] = lambda *p, head=head: rows(*head, *p, None)
-        calls["device", what] = lambda *p, head=head: dev(*head, *p, None, None)
-    for what, head in list_heads.items():
-        calls["pixels", what] = lambda *p, head=head: pix(*head, *p, None)
-        calls["pixels_device", what] = lambda *p, head=head: pixdev(*head, *p, None, None)
-    return calls, (xs, ys, empty)
 
 
 def test_ao_entry_points_are_exported_declared_and_listed(rl):
@@ -77,7 +29,7 @@ def test_ao_entry_points_are_exported_declared_and_listed(rl):
     assert hasattr(rl.api.host_lib(), "rlh_ao_probe")
     for m in ("render_ao", "render_ao_device", "render_pixels_ao", "render_pixels_ao_device", "AmbientOcclusion"):
         assert callable(getattr(rl, m)) and getattr(rl, m) is getattr(rl.ao, m), m
-    # not on api.Camera and not in api: tests/test_binding_calls.py compares their public callables with a committed fixture
+    # not on api.Camera and not in api
     assert not any("ao" in n.split("_") for n in dir(rl.api.Camera)) and not hasattr(rl.api, "render_ao")
 
 
@@ -90,49 +42,31 @@ def test_what_is_particular_to_the_calls_is_refused_before_a_device_is_looked_at
     cam, big = _camera(rl), _camera(rl, spp=1 << 16)
     op, hits = np.full(24, 7, dtype=np.uint32), np.full(24, 9, dtype=np.uint32)
     o, h = op.ctypes.data, hits.ctypes.data
-    for name, f in _forms(lib, cam).items():
+    for name, f in forms(lib, "ao", cam).items():
         for k, r, po, ph in ((0, 1.0, o, h), (4, NAN, o, h), (4, 0.0, o, h), (4, -0.0, o, h), (4, -1.0, o, h), (4, -INF, o, h), (4, 1.0, None, None)):
             assert f(k, r, po, ph) == api.RL_E_INVALID, (name, k, r)
             assert b"bad argument" in lib.rl_last_error(), (name, k, r, lib.rl_last_error())
-    for name, f in _forms(lib, big).items():  # S = 2^16: K = 2^16 is S K = 2^32, one less is legal
+    for name, f in forms(lib, "ao", big).items():  # S = 2^16: K = 2^16 is S K = 2^32, one less is legal
         assert f(1 << 16, 1.0, o, h) == api.RL_E_INVALID, name
         assert b"bad argument" in lib.rl_last_error(), name
     assert (op == 7).all() and (hits == 9).all()
-    if not _gpu_present():
+    if not gpu_present():
         assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
         for cm, k in ((cam, 4), (big, (1 << 16) - 1), (cam, 0xFFFFFFFF >> 1)):
-            for name, f in _forms(lib, cm).items():
+            for name, f in forms(lib, "ao", cm).items():
                 for r, po, ph in ((INF, o, h), (1e-300, o, h), (2.0, o, None), (2.0, None, h)):
                     assert f(k, r, po, ph) == api.RL_E_NO_DEVICE, (name, k, r)
         assert (op == 7).all() and (hits == 9).all()
 
 
 def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl):
-    """The order of each entry point's check sequence as far as a machine without a GPU shows it: what is particular to the family is
-    refused first ("bad argument") whatever else is wrong with the call (no scene, no camera, row_step == 0, an empty image, row_first
-    past the last row, a NULL, empty or too long list), and a call that is legal in that respect looks for the device before any of those."""
-    api = rl.api
-    lib = api.render_lib()
-    cam = _camera(rl)
+    """pixel_family_abi's statement of the order, over this family's refused and legal arguments."""
     op, hits = np.full(24, 7, dtype=np.uint32), np.full(24, 9, dtype=np.uint32)
     o, h = op.ctypes.data, hits.ctypes.data
     refused = [(0, 1.0, o, h), (4, NAN, o, h), (4, 1.0, None, None)]
     legal = [(4, 1.0, o, h), (1, INF, None, h)]
     untouched = lambda: (op == 7).all() and (hits == 9).all()
-    calls, keep = _with_a_later_defect(lib, "ao", cam)
-    assert len(calls) == 2 * 5 + 2 * 7
-    for key, f in calls.items():
-        for p in refused:
-            assert f(*p) == api.RL_E_INVALID, (key, p)
-            assert b"bad argument" in lib.rl_last_error(), (key, p, lib.rl_last_error())
-    assert untouched()
-    if not _gpu_present():
-        assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
-        for key, f in calls.items():
-            for p in legal:
-                assert f(*p) == api.RL_E_NO_DEVICE, (key, p)
-                assert b"rl_init has not succeeded" in lib.rl_last_error(), (key, p, lib.rl_last_error())
-        assert untouched()
+    family_check_comes_first(rl, "ao", refused, legal, untouched)
 
 
 def test_want_and_merge_are_checked_in_python(rl, monkeypatch):
@@ -176,7 +110,7 @@ def test_last_query_names_the_ao_kernels(rl, monkeypatch):
         assert api.last_query() == {"kernel": name, "retraced": 3}
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_ao_renders_without_a_device_fail_loudly(rl):
     api = rl.api
     lib = api.render_lib()

@@ -9,44 +9,13 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present, the_family_check_comes_first_and_the_device_before_every_later_rule as family_check_comes_first
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_render_features_rows": 7, "rl_rtiow_render_features_device": 8, "rl_rtiow_render_pixels_features": 8,
        "rl_rtiow_render_pixels_features_device": 9}
 FIELDS = ["albedo_sum", "normal_sum", "depth_sum", "hit_count"]
 PROBE_ARGS = [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
-
-
-def _with_a_later_defect(lib, stem, cam):
-    """Every entry point of the family as f(*particular) -> rc, each time with ONE rule that comes later in its check sequence broken as
-    well: no scene, no camera, row_step == 0, an image without pixels, row_first past the last row; a NULL list, the empty list, a list
-    beyond the work counter.  -> {(form, defect): f}, and what the calls point into (to be kept alive)."""
-    rows, dev = getattr(lib, "rl_rtiow_render_%s_rows" % stem), getattr(lib, "rl_rtiow_render_%s_device" % stem)
-    pix, pixdev = getattr(lib, "rl_rtiow_render_pixels_%s" % stem), getattr(lib, "rl_rtiow_render_pixels_%s_device" % stem)
-    xs, ys = np.arange(4, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
-    empty = type(cam.c).from_buffer_copy(cam.c)
-    empty.image_width = 0
-    c, e, X, Y = C.byref(cam.c), C.byref(empty), xs.ctypes.data, ys.ctypes.data
-    row_heads = {"scene": (None, c, 0, 0, 1), "camera": (None, None, 0, 0, 1), "row_step": (None, c, 0, 0, 0), "empty image": (None, e, 0, 0, 1),
-                 "row_first": (None, c, 0, cam.c.image_height, 1)}
-    list_heads = {"scene": (None, c, 0, X, Y, 4), "camera": (None, None, 0, X, Y, 4), "xs": (None, c, 0, None, Y, 4), "ys": (None, c, 0, X, None, 4),
-                  "empty list": (None, c, 0, None, None, 0), "empty image": (None, e, 0, X, Y, 4), "length": (None, c, 0, X, Y, 0xFFFF0000)}
-    calls = {}
-    for what, head in row_heads.items():
-        calls["rows", what] = lambda *p, head=head: rows(*head, *p, None)
-        calls["device", what] = lambda *p, head=head: dev(*head, *p, None, None)
-    for what, head in list_heads.items():
-        calls["pixels", what] = lambda *p, head=head: pix(*head, *p, None)
-        calls["pixels_device", what] = lambda *p, head=head: pixdev(*head, *p, None, None)
-    return calls, (xs, ys, empty)
 
 
 def test_render_features_entry_points_are_exported_declared_and_listed(rl):
@@ -94,7 +63,7 @@ def test_null_and_all_null_struct_are_refused_with_outputs_untouched(rl):
     bufs = _buffers(npix)
     c = ctypes.byref(cam.c)
     dev = None
-    if _gpu_present():
+    if gpu_present():
         rl.init(0)
         dev = world.device()
     xs, ys = np.zeros(4, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
@@ -122,9 +91,7 @@ def test_null_and_all_null_struct_are_refused_with_outputs_untouched(rl):
 
 
 def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl):
-    """The order of each entry point's check sequence as far as a machine without a GPU shows it: what is particular to the family is
-    refused first ("bad argument") whatever else is wrong with the call (no scene, no camera, row_step == 0, an empty image, row_first
-    past the last row, a NULL, empty or too long list), and a call that is legal in that respect looks for the device before any of those."""
+    """pixel_family_abi's statement of the order, over this family's refused and legal arguments."""
     api = rl.api
     lib = api.render_lib()
     world = rl.World.golden_test_scene()
@@ -134,23 +101,10 @@ def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl)
     refused = [(None,), (C.byref(none),)]
     legal = [(C.byref(full),), (C.byref(depth_only),)]
     untouched = lambda: all((b == 7).all() for b in bufs)
-    calls, keep = _with_a_later_defect(lib, "features", cam)
-    assert len(calls) == 2 * 5 + 2 * 7
-    for key, f in calls.items():
-        for p in refused:
-            assert f(*p) == api.RL_E_INVALID, (key, p)
-            assert b"bad argument" in lib.rl_last_error(), (key, p, lib.rl_last_error())
-    assert untouched()
-    if not _gpu_present():
-        assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
-        for key, f in calls.items():
-            for p in legal:
-                assert f(*p) == api.RL_E_NO_DEVICE, (key, p)
-                assert b"rl_init has not succeeded" in lib.rl_last_error(), (key, p, lib.rl_last_error())
-        assert untouched()
+    family_check_comes_first(rl, "features", refused, legal, untouched, cam)
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_render_features_without_a_device_fails_loudly(rl):
     api = rl.api
     lib = api.render_lib()

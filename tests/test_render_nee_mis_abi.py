@@ -9,6 +9,7 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import camera as _camera, forms, gpu_present, the_family_check_comes_first_and_the_device_before_every_later_rule as family_check_comes_first
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_render_nee_mis_rows": 13, "rl_rtiow_render_nee_mis_device": 14, "rl_rtiow_render_pixels_nee_mis": 14,
@@ -16,56 +17,6 @@ NEW = {"rl_rtiow_render_nee_mis_rows": 13, "rl_rtiow_render_nee_mis_device": 14,
 INF = float("inf")
 NAN = float("nan")
 GOOD = [0.0, 4.0, 0.0, 2.0, 0.0, 0.0, 0.0, 0.0, 2.0, 5.0, 4.0, 3.0]  # Q, u, v, E
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
-
-
-def _camera(rl, spp=2, max_depth=5):
-    return rl.Camera(rl.CameraParams(aspect_ratio=1.5, image_width=6, samples_per_pixel=spp, max_depth=max_depth))
-
-
-def _forms(lib, cam, scene=None):
-    """The four entry points as f(L, lights, K, T, heuristic, sums, sq) -> rc with everything else valid but the scene (NULL: a later rule)."""
-    xs = np.arange(4, dtype=np.uint32)
-    ys = np.zeros(4, dtype=np.uint32)
-    c = C.byref(cam.c)
-    return {
-        "rows": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_nee_mis_rows(scene, c, 0, 0, 1, L, li, k, t, h, s, q, None),
-        "device": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_nee_mis_device(scene, c, 0, 0, 1, L, li, k, t, h, s, q, None, None),
-        "pixels": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_pixels_nee_mis(scene, c, 0, xs.ctypes.data, ys.ctypes.data, 4, L, li, k, t, h, s, q, None),
-        "pixels_device": lambda L, li, k, t, h, s, q: lib.rl_rtiow_render_pixels_nee_mis_device(scene, c, 0, xs.ctypes.data, ys.ctypes.data, 4, L, li, k, t, h, s,
-                                                                                                q, None, None),
-    }
-
-
-def _with_a_later_defect(lib, stem, cam):
-    """Every entry point of the family as f(*particular) -> rc, each time with ONE rule that comes later in its check sequence broken as
-    well: no scene, no camera, row_step == 0, an image without pixels, row_first past the last row; a NULL list, the empty list, a list
-    beyond the work counter.  -> {(form, defect): f}, and what the calls point into (to be kept alive)."""
-    rows, dev = getattr(lib, "rl_rtiow_render_%s_rows" % stem), getattr(lib, "rl_rtiow_render_%s_device" % stem)
-    pix, pixdev = getattr(lib, "rl_rtiow_render_pixels_%s" % stem), getattr(lib, "rl_rtiow_render_pixels_%s_device" % stem)
-    xs, ys = np.arange(4, dtype=np.uint32), np.zeros(4, dtype=np.uint32)
-    empty = type(cam.c).from_buffer_copy(cam.c)
-    empty.image_width = 0
-    c, e, X, Y = C.byref(cam.c), C.byref(empty), xs.ctypes.data, ys.ctypes.data
-    row_heads = {"scene": (None, c, 0, 0, 1), "camera": (None, None, 0, 0, 1), "row_step": (None, c, 0, 0, 0), "empty image": (None, e, 0, 0, 1),
-                 "row_first": (None, c, 0, cam.c.image_height, 1)}
-    list_heads = {"scene": (None, c, 0, X, Y, 4), "camera": (None, None, 0, X, Y, 4), "xs": (None, c, 0, None, Y, 4), "ys": (None, c, 0, X, None, 4),
-                  "empty list": (None, c, 0, None, None, 0), "empty image": (None, e, 0, X, Y, 4), "length": (None, c, 0, X, Y, 0xFFFF0000)}
-    calls = {}
-    for what, head in row_heads.items():
-        calls["rows", what] = lambda *p, head=head: rows(*head, *p, None)
-        calls["device", what] = lambda *p, head=head: dev(*head, *p, None, None)
-    for what, head in list_heads.items():
-        calls["pixels", what] = lambda *p, head=head: pix(*head, *p, None)
-        calls["pixels_device", what] = lambda *p, head=head: pixdev(*head, *p, None, None)
-    return calls, (xs, ys, empty)
 
 
 def test_mis_entry_points_are_exported_declared_and_listed(rl):
@@ -89,7 +40,7 @@ def test_mis_entry_points_are_exported_declared_and_listed(rl):
     for m in ("render_nee_mis", "render_nee_mis_device", "render_pixels_nee_mis", "render_pixels_nee_mis_device"):
         assert callable(getattr(rl, m)) and getattr(rl, m) is getattr(rl.nee, m), m
     assert rl.nee.HEURISTICS == {"balance": 0, "power": 1}
-    # not on api.Camera and not in api: tests/test_binding_calls.py compares their public callables with a committed fixture
+    # not on api.Camera and not in api
     assert not any("nee" in n.split("_") for n in dir(rl.api.Camera)) and not hasattr(rl.api, "render_nee_mis")
 
 
@@ -122,43 +73,38 @@ def test_every_nee_refusal_and_a_third_heuristic_come_before_a_device_is_looked_
                (1, one, 1, NAN, s, q), (1, one, 1, 1e-10, s, q), (1, one, 1, 0.0, s, q), (1, one, 1, -0.5, s, q),
                (1, one, 1, math.nextafter(1.0, 2.0), s, q), (1, one, 1, INF, s, q), (1, one, 1, T, None, None)]
     for h in (0, 1):
-        for name, f in _forms(lib, cam).items():
+        for name, f in forms(lib, "nee_mis", cam).items():
             for L, li, k, t, ps, pq in refused:
                 assert f(L, None if li is None else li.ctypes.data, k, t, h, ps, pq) == api.RL_E_INVALID, (name, h, L, k, t)
                 assert b"bad argument" in lib.rl_last_error(), (name, h, L, k, t, lib.rl_last_error())
-        for name, f in _forms(lib, flat).items():  # a path has at least one vertex
+        for name, f in forms(lib, "nee_mis", flat).items():  # a path has at least one vertex
             assert f(1, one.ctypes.data, 1, T, h, s, q) == api.RL_E_INVALID, name
             assert b"bad argument" in lib.rl_last_error(), name
     sixteen = arr([GOOD] * 16)
-    for name, f in _forms(lib, big).items():  # S = 2^16, L = 16: K = 2^12 is S L K = 2^32, one less is legal
+    for name, f in forms(lib, "nee_mis", big).items():  # S = 2^16, L = 16: K = 2^12 is S L K = 2^32, one less is legal
         assert f(16, sixteen.ctypes.data, 1 << 12, T, 1, s, q) == api.RL_E_INVALID, name
         assert b"bad argument" in lib.rl_last_error(), name
-    for name, f in _forms(lib, cam).items():  # L K alone beyond 32 bits
+    for name, f in forms(lib, "nee_mis", cam).items():  # L K alone beyond 32 bits
         assert f(16, sixteen.ctypes.data, 0xFFFFFFFF, T, 0, s, q) == api.RL_E_INVALID, name
     for h in (2, 3, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF):  # the heuristic alone
-        for name, f in _forms(lib, cam).items():
+        for name, f in forms(lib, "nee_mis", cam).items():
             assert f(1, one.ctypes.data, 4, T, h, s, q) == api.RL_E_INVALID, (name, h)
             assert b"bad argument" in lib.rl_last_error(), (name, h)
     assert (sums == 7.0).all() and (sq == 8.0).all()
-    if not _gpu_present():
+    if not gpu_present():
         assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
         legal = [(cam, 1, one, 4, T, s, q), (big, 16, sixteen, (1 << 12) - 1, T, s, q), (cam, 16, sixteen, 3, 1.0, s, q),
                  (cam, 1, one, 4, math.nextafter(1e-10, 1.0), s, q), (cam, 1, one, 4, T, s, None), (cam, 1, one, 4, T, None, q),
                  (_camera(rl, max_depth=1), 1, one, 1, T, s, q)]
         for h in (0, 1):
             for cm, L, li, k, t, ps, pq in legal:
-                for name, f in _forms(lib, cm).items():
+                for name, f in forms(lib, "nee_mis", cm).items():
                     assert f(L, li.ctypes.data, k, t, h, ps, pq) == api.RL_E_NO_DEVICE, (name, h, L, k, t)
         assert (sums == 7.0).all() and (sq == 8.0).all()
 
 
 def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl):
-    """The order of each entry point's check sequence as far as a machine without a GPU shows it: what is particular to the family is
-    refused first ("bad argument") whatever else is wrong with the call (no scene, no camera, row_step == 0, an empty image, row_first
-    past the last row, a NULL, empty or too long list), and a call that is legal in that respect looks for the device before any of those."""
-    api = rl.api
-    lib = api.render_lib()
-    cam = _camera(rl)
+    """pixel_family_abi's statement of the order, over this family's refused and legal arguments."""
     sums, sq = np.full((24, 3), 7.0), np.full((24, 3), 8.0)
     s, q = sums.ctypes.data, sq.ctypes.data
     one = np.array([GOOD], dtype=np.float64)
@@ -167,20 +113,7 @@ def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl)
                (1, li, 1, 0.5, 2, s, q)]
     legal = [(1, li, 1, 0.5, 0, s, q), (1, li, 3, 1.0, 1, None, q)]
     untouched = lambda: (sums == 7.0).all() and (sq == 8.0).all()
-    calls, keep = _with_a_later_defect(lib, "nee_mis", cam)
-    assert len(calls) == 2 * 5 + 2 * 7
-    for key, f in calls.items():
-        for p in refused:
-            assert f(*p) == api.RL_E_INVALID, (key, p)
-            assert b"bad argument" in lib.rl_last_error(), (key, p, lib.rl_last_error())
-    assert untouched()
-    if not _gpu_present():
-        assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
-        for key, f in calls.items():
-            for p in legal:
-                assert f(*p) == api.RL_E_NO_DEVICE, (key, p)
-                assert b"rl_init has not succeeded" in lib.rl_last_error(), (key, p, lib.rl_last_error())
-        assert untouched()
+    family_check_comes_first(rl, "nee_mis", refused, legal, untouched)
 
 
 def test_heuristic_and_want_are_checked_in_python(rl, monkeypatch):
@@ -224,7 +157,7 @@ def test_last_query_names_the_mis_kernels(rl, monkeypatch):
         assert api.last_query() == {"kernel": name, "retraced": 3}
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_mis_renders_without_a_device_fail_loudly_and_media_scenes_come_after(rl):
     """Without a device every call that passes the argument rules ends at RL_E_NO_DEVICE, a media scene included: the media refusal
     (RL_E_UNSUPPORTED) is a rule about the compiled scene and is asserted on the device (tests/test_gpu_render_nee_mis.py)."""

@@ -9,7 +9,8 @@ import re
 
 import numpy as np
 import pytest
-from test_render_nee_mis_abi import GOOD, _camera, _gpu_present, _with_a_later_defect
+from test_render_nee_mis_abi import GOOD, _camera
+from pixel_family_abi import forms, gpu_present, the_family_check_comes_first_and_the_device_before_every_later_rule as family_check_comes_first
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_render_nee_mis_spheres_rows": 15, "rl_rtiow_render_nee_mis_spheres_device": 16, "rl_rtiow_render_pixels_nee_mis_spheres": 16,
@@ -18,19 +19,6 @@ INF = float("inf")
 NAN = float("nan")
 BALL = [0.0, 7.0, 0.0, 2.0, 4.0, 4.0, 4.0]  # C, r, E
 T = 1.0 - 1e-6
-
-
-def _forms(lib, cam, scene=None):
-    """The four entry points as f(L, lights, Ls, spheres, K, T, heuristic, sums, sq) -> rc with everything else valid but the scene."""
-    xs = np.arange(4, dtype=np.uint32)
-    ys = np.zeros(4, dtype=np.uint32)
-    c = C.byref(cam.c)
-    return {
-        "rows": lambda *p: lib.rl_rtiow_render_nee_mis_spheres_rows(scene, c, 0, 0, 1, *p, None),
-        "device": lambda *p: lib.rl_rtiow_render_nee_mis_spheres_device(scene, c, 0, 0, 1, *p, None, None),
-        "pixels": lambda *p: lib.rl_rtiow_render_pixels_nee_mis_spheres(scene, c, 0, xs.ctypes.data, ys.ctypes.data, 4, *p, None),
-        "pixels_device": lambda *p: lib.rl_rtiow_render_pixels_nee_mis_spheres_device(scene, c, 0, xs.ctypes.data, ys.ctypes.data, 4, *p, None, None),
-    }
 
 
 def test_sphere_entry_points_are_exported_declared_and_listed(rl):
@@ -97,20 +85,20 @@ def test_every_refusal_comes_before_a_device_is_looked_at(rl):
                (0, None, 1, balls(1), 0, T, 0, s, q), (0, None, 1, balls(1), 1, NAN, 0, s, q), (0, None, 1, balls(1), 1, 1e-10, 0, s, q),
                (0, None, 1, balls(1), 1, math.nextafter(1.0, 2.0), 0, s, q), (0, None, 1, balls(1), 1, T, 0, None, None),
                (0, None, 1, balls(1), 1, T, 2, s, q), (1, quads(1), 1, balls(1), 1, T, 0xFFFFFFFF, s, q)]
-    for name, f in _forms(lib, cam).items():
+    for name, f in forms(lib, "nee_mis_spheres", cam).items():
         for L, li, Ls, sp, k, t, h, ps, pq in refused:
             assert f(L, p(li), Ls, p(sp), k, t, h, ps, pq) == api.RL_E_INVALID, (name, L, Ls, k, t, h)
             assert b"bad argument" in lib.rl_last_error(), (name, L, Ls, k, t, h, lib.rl_last_error())
-    for name, f in _forms(lib, flat).items():  # a path has at least one vertex
+    for name, f in forms(lib, "nee_mis_spheres", flat).items():  # a path has at least one vertex
         assert f(0, None, 1, p(balls(1)), 1, T, 0, s, q) == api.RL_E_INVALID, name
     keep = (quads(8), balls(8))
-    for name, f in _forms(lib, big).items():  # S = 2^16, L + Ls = 16: K = 2^12 is S (L + Ls) K = 2^32
+    for name, f in forms(lib, "nee_mis_spheres", big).items():  # S = 2^16, L + Ls = 16: K = 2^12 is S (L + Ls) K = 2^32
         assert f(8, p(keep[0]), 8, p(keep[1]), 1 << 12, T, 1, s, q) == api.RL_E_INVALID, name
         assert f(0, None, 8, p(keep[1]), 1 << 13, T, 1, s, q) == api.RL_E_INVALID, name
-    for name, f in _forms(lib, cam).items():  # (L + Ls) K alone beyond 32 bits
+    for name, f in forms(lib, "nee_mis_spheres", cam).items():  # (L + Ls) K alone beyond 32 bits
         assert f(8, p(keep[0]), 8, p(keep[1]), 0xFFFFFFFF, T, 0, s, q) == api.RL_E_INVALID, name
     assert (sums == 7.0).all() and (sq == 8.0).all()
-    if not _gpu_present():
+    if not gpu_present():
         assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
         tiny = balls(1)
         tiny[0, 3] = 5e-324  # r > 0, A = 0: finite
@@ -119,17 +107,13 @@ def test_every_refusal_comes_before_a_device_is_looked_at(rl):
                  (big, 8, quads(8), 8, balls(8), (1 << 12) - 1, T, 0, s, q), (cam, 0, None, 1, tiny, 1, T, 0, s, q),
                  (_camera(rl, max_depth=1), 0, None, 1, balls(1), 1, T, 0, s, q)]
         for cm, L, li, Ls, sp, k, t, h, ps, pq in legal:
-            for name, f in _forms(lib, cm).items():
+            for name, f in forms(lib, "nee_mis_spheres", cm).items():
                 assert f(L, p(li), Ls, p(sp), k, t, h, ps, pq) == api.RL_E_NO_DEVICE, (name, L, Ls, k, t, h)
         assert (sums == 7.0).all() and (sq == 8.0).all()
 
 
 def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl):
-    """As the MIS suite's test of the same name, over the same later defects (no scene, no camera, row_step == 0, an empty image,
-    row_first past the last row, a NULL, empty or too long list)."""
-    api = rl.api
-    lib = api.render_lib()
-    cam = _camera(rl)
+    """pixel_family_abi's statement of the order, over this family's refused and legal arguments."""
     sums, sq = np.full((24, 3), 7.0), np.full((24, 3), 8.0)
     s, q = sums.ctypes.data, sq.ctypes.data
     one, ball = np.array([GOOD], dtype=np.float64), np.array([BALL], dtype=np.float64)
@@ -139,20 +123,7 @@ def test_the_family_check_comes_first_and_the_device_before_every_later_rule(rl)
                (0, None, 1, sp, 0, 0.5, 0, s, q), (0, None, 1, sp, 1, NAN, 1, s, q), (0, None, 1, sp, 1, 0.5, 0, None, None), (0, None, 1, sp, 1, 0.5, 2, s, q)]
     legal = [(0, None, 1, sp, 1, 0.5, 0, s, q), (1, li, 1, sp, 3, 1.0, 1, None, q), (1, li, 0, None, 3, 1.0, 1, s, None)]
     untouched = lambda: (sums == 7.0).all() and (sq == 8.0).all()
-    calls, keep = _with_a_later_defect(lib, "nee_mis_spheres", cam)
-    assert len(calls) == 2 * 5 + 2 * 7
-    for key, f in calls.items():
-        for pr in refused:
-            assert f(*pr) == api.RL_E_INVALID, (key, pr)
-            assert b"bad argument" in lib.rl_last_error(), (key, pr, lib.rl_last_error())
-    assert untouched()
-    if not _gpu_present():
-        assert lib.rl_init(-1) == api.RL_E_NO_DEVICE
-        for key, f in calls.items():
-            for pr in legal:
-                assert f(*pr) == api.RL_E_NO_DEVICE, (key, pr)
-                assert b"rl_init has not succeeded" in lib.rl_last_error(), (key, pr, lib.rl_last_error())
-        assert untouched()
+    family_check_comes_first(rl, "nee_mis_spheres", refused, legal, untouched)
 
 
 def test_pack_sphere_lights_and_its_value_errors(rl):
@@ -203,7 +174,7 @@ def test_last_query_names_the_sphere_kernels(rl, monkeypatch):
         assert api.last_query() == {"kernel": name, "retraced": 3}
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_sphere_renders_without_a_device_fail_loudly_and_media_scenes_come_after(rl):
     api = rl.api
     lib = api.render_lib()

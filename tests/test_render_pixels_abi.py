@@ -7,18 +7,11 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtiow_render_pixels": 8, "rl_rtiow_render_pixels_device": 9, "rl_rtc_render_pixels": 8, "rl_rtc_render_pixels_device": 9}
 PROBE_ARGS = [ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p]
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_render_pixels_entry_points_are_exported_declared_and_listed(rl):
@@ -54,7 +47,7 @@ def test_shape_errors_are_caught_before_the_library(rl):
                 render(xs, ys)
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_render_pixels_without_a_device_fail_loudly(rl):
     api = rl.api
     lib = api.render_lib()

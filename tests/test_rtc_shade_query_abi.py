@@ -7,18 +7,11 @@ import re
 
 import numpy as np
 import pytest
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = {"rl_rtc_prepare_rays": 5, "rl_rtc_prepare_rays_device": 6, "rl_rtc_shade_hits": 6, "rl_rtc_shade_hits_device": 7,
        "rl_rtc_shadow_attenuation": 6, "rl_rtc_shadow_attenuation_device": 7, "rl_rtc_lighting": 7, "rl_rtc_lighting_device": 8}
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_rtc_shade_query_entry_points_are_exported_declared_and_listed(rl):
@@ -85,7 +78,7 @@ def test_shape_errors_are_caught_before_the_library(rl):
             bad()
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_rtc_shade_queries_without_a_device_fail_loudly(rl):
     api = rl.api
     lib = api.render_lib()

@@ -3,16 +3,9 @@ exported, wrapped in api.py, and fails LOUDLY (RL_E_NO_DEVICE) when no GPU is pr
 import os
 
 import pytest
+from pixel_family_abi import gpu_present
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _gpu_present():
-    try:
-        import torch
-        return torch.cuda.is_available()
-    except Exception:
-        return False
 
 
 def test_status_gap_hook_is_exported_and_wrapped(rl):
@@ -24,7 +17,7 @@ def test_status_gap_hook_is_exported_and_wrapped(rl):
     assert "rl_debug_set_status_gap" not in open(os.path.join(ROOT, "include", "rl_render.h")).read()
 
 
-@pytest.mark.skipif(_gpu_present(), reason="GPU present: the failure path is not reachable")
+@pytest.mark.skipif(gpu_present(), reason="GPU present: the failure path is not reachable")
 def test_status_gap_hook_without_a_device_fails_loudly(rl):
     api = rl.api
     assert api.render_lib().rl_init(-1) == api.RL_E_NO_DEVICE

@@ -1,11 +1,12 @@
-"""Writes tests/golden/binding_calls.json: what every wrapper of api.py hands to the render library, as tests/binding_model.py's driver
-records it against a stand-in library (no GPU; the host library is the real one).  tests/test_binding_calls.py compares the working
-tree's api.py with it.  Run it on the commit whose behaviour is to be kept:
+"""Writes tests/golden/binding_calls.json: the signature of every wrapper of the Python binding (api.py and the modules beside it: ao,
+direct, nee, occlusion, entry_table) and what it hands to the render library — the cpp_mirror_probe* to the host library's probes —, as
+tests/binding_model.py's driver records it against stand-in libraries (no GPU; the rest of the host library is the real one).
+tests/test_binding_calls.py compares the working tree's package with it.  Run it on the commit whose behaviour is to be kept:
 
     python tools/record_binding_calls.py [--commit NAME] [--out FILE]
 
 The file's first line names that commit (default: git's HEAD) and, with --note, what was changed on purpose since; one line per
-wrapper follows."""
+wrapper follows, then one line per wrapper's signature (rows "name[variant]" share that of "name")."""
 import argparse
 import importlib
 import json
@@ -18,7 +19,13 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
 
 def dumps(commit, entries, note=None):
-    lines = [json.dumps({"recorded_from": commit, **({"note": note} if note else {})})] + [json.dumps(e) for e in entries]
+    """One line per wrapper without its signature, then one line per signature: a signature added later leaves the wrapper's line as it was."""
+    lines = [json.dumps({"recorded_from": commit, **({"note": note} if note else {})})]
+    lines += [json.dumps({k: v for k, v in e.items() if k != "signature"}) for e in entries]
+    signatures = {}
+    for e in entries:  # the rows of one wrapper ("name", "name[variant]") drive one callable
+        assert signatures.setdefault(e["wrapper"].split("[")[0], e["signature"]) == e["signature"], e["wrapper"]
+    lines += [json.dumps({"signature_of": k, "signature": v}) for k, v in signatures.items()]
     return "[\n" + ",\n".join(lines) + "\n]\n"
 
 
